@@ -31,6 +31,13 @@ Rank 0 prints ONE JSON line (contract in the task statement) carrying, besides t
 
 --data FILE (.fvecs / .npy / .hdf5 with a "train" dataset): build THAT point set instead of the synthetic one (real SIFT-1M /
 GloVe / NYTimes when a file is on disk; there is none in this image), N = 1 only.
+
+--dump-outputs DIR: after the timed builds, rank 0 writes the neighbour graph its last timed build left in HBM (what a caller
+of the device path receives) to DIR, so that two builds of the project can be compared output for output on the same inputs:
+  rows.npy               float64 (m,)    the rows written: all of rank 0's rows, or a fixed seeded sample when they exceed the cap
+  neighbor_indices.npy   float64 (m, k)  neighbour ids (int32 in HBM; exact in float64)
+  neighbor_distances.npy float32 (m, k)  distances as returned (squared euclidean)
+at most DUMP_BYTES in all.
 """
 import argparse
 import json
@@ -51,6 +58,7 @@ import torch  # noqa: E402  (device memory, streams, torch.distributed: plumbing
 HBM_PEAK_GBS = 8000.0     # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 MFMA_F32_PEAK_TF = 157.3  # same guide: f32-input MFMA (v_mfma_f32_16x16x4_f32) = the f32 vector rate
 MFMA_FLOP = 2048.0        # one v_mfma_f32_16x16x4_f32: 16 * 16 * 4 multiply-adds
+DUMP_BYTES = 60_000_000   # --dump-outputs: cap of the .npy payload (below 64 MB with the headers)
 
 
 def sift_like(n, d, seed, device, latent=16, n_clusters=1024, noise=0.3, sample_seed=None):
@@ -221,6 +229,19 @@ def recall_at(true_idx, approx_idx, k_true=10, cols=None):
     a = approx_idx.cpu().numpy() if cols is None else approx_idx[:, :cols].cpu().numpy()
     hits = sum(np.isin(tr, ar).sum() for tr, ar in zip(t, a))
     return hits / float(t.shape[0] * k_true)
+
+
+def dump_outputs(path, out_idx, out_dist):
+    """--dump-outputs: the graph in HBM as .npy files (module docstring); rows sampled with a fixed seed above DUMP_BYTES."""
+    n, k = out_idx.shape
+    m = min(n, DUMP_BYTES // (8 + 12 * k))  # per row: its id (f64) + k ids (f64) + k distances (f32)
+    rows = np.arange(n) if m == n else np.sort(np.random.RandomState(7).choice(n, m, replace=False))
+    sel = torch.from_numpy(rows).to(out_idx.device)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(path, "neighbor_indices.npy"), out_idx[sel].cpu().numpy().astype(np.float64))
+    np.save(os.path.join(path, "neighbor_distances.npy"), out_dist[sel].cpu().numpy().astype(np.float32))
+    return {"dir": path, "rows": int(m), "of_rows": int(n), "k": int(k)}
 
 
 def cpu_baseline(O, xs, k, n_trees, true_rows=None, true_idx=None):
@@ -438,14 +459,20 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip value_host_inclusive, value_class_api, workload_hard, workload_k30")
     ap.add_argument("--data", default=None, help="build this point set (.fvecs / .npy / .hdf5 'train') instead of the synthetic one")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed builds, write the last one's neighbour graph (rank 0's rows) to DIR/*.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     share_gpu = os.environ.get("PYNND_BENCH_SHARE_GPU") == "1"  # debug: all ranks on GPU 0 over gloo
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # plain `python bench.py --gpus N`: become N ranks, one per GPU (torch.distributed.run, RCCL)
-        ndev = torch.cuda.device_count()
-        if ndev < args.gpus and not share_gpu:
-            sys.exit("bench.py: --gpus %d requested but only %d HIP device(s) are visible" % (args.gpus, ndev))
+        # plain `python bench.py --gpus N`: become N ranks, one per GPU (torch.distributed.run, RCCL).  With a shared GPU
+        # the device count is not asked: this parent process then never opens the GPU beside its N ranks
+        if not share_gpu:
+            ndev = torch.cuda.device_count()
+            if ndev < args.gpus:
+                sys.exit("bench.py: --gpus %d requested but only %d HIP device(s) are visible" % (args.gpus, ndev))
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
                "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.abspath(__file__)] + sys.argv[1:]
         sys.exit(subprocess.call(cmd))
@@ -615,6 +642,9 @@ def run(args, world, rank, local_rank, share_gpu, wd):
         elapsed = float(t.item())
     ms_per_step = elapsed * 1000.0 / args.steps
     value = n_total * args.steps / elapsed
+    dumped = None
+    if args.dump_outputs is not None and rank == 0:  # outside the timed region, before the extras reuse the output buffers
+        dumped = dump_outputs(args.dump_outputs, out_idx, out_dist)
 
     # recall vs exact brute force on a sample of this rank's rows (outside the timed region)
     x_all = gather_rows(x, world) if world > 1 else x
@@ -866,6 +896,8 @@ def run(args, world, rank, local_rank, share_gpu, wd):
             "workload_c5": c5,
             "cpu_baseline": cpu,
         }
+        if dumped is not None:
+            result["dump_outputs"] = dumped
         if world > 1 and rccl_error is not None:
             result["degraded"] = "RCCL unavailable (%s): exchanged through the HOST transport -- functional check, not a scaling number" % rccl_error
         if wd is not None:

@@ -446,7 +446,10 @@ static int after_data(nnd_ctx *ctx) {
 // another (round-5 review: 32.9 vs 42.2 ms for the whole nnd_build call).  Here: eight pinned 8 MB buffers per device (allocated
 // once per process), eight host threads -- thread t copies chunks t, t + 8, ... into ITS buffer and queues the DMA of each on the
 // handle's stream itself (the chunks are independent; what follows on the stream is ordered behind all of them).  A pinned
-// source is copied directly.
+// source is copied directly.  Each thread waits for its last DMA before the call returns: the staging events are shared by
+// every handle of the device, and a later call (another handle, another stream) must never wait on an event last recorded
+// on a stream that may have been destroyed since (such a wait has failed with hipErrorCapturedEvent, although no stream is
+// ever captured in the process).
 static std::mutex g_up_mu[64];  // per device: the ranks of nnd_build_multi upload side by side
 static char *g_up_stage[64][16] = {};
 static hipEvent_t g_up_ev[64][16] = {};
@@ -474,11 +477,7 @@ static int h2d_parallel(nnd_ctx *ctx, void *dst_dev, const void *src, size_t byt
             API_HIP(hipMemcpyAsync(dst_dev, src, bytes, hipMemcpyHostToDevice, ctx->stream));
             return 0;
         }
-        if (!g_up_ev[dev][b]) {
-            API_HIP(hipEventCreateWithFlags(&g_up_ev[dev][b], hipEventDisableTiming));
-        } else {
-            API_HIP(hipEventSynchronize(g_up_ev[dev][b]));  // (a previous call's last DMA out of this buffer)
-        }
+        if (!g_up_ev[dev][b]) API_HIP(hipEventCreateWithFlags(&g_up_ev[dev][b], hipEventDisableTiming));
     }
     const size_t nchunks = (bytes + STAGE - 1) / STAGE;
     std::atomic<int> failed{0};
@@ -494,12 +493,18 @@ static int h2d_parallel(nnd_ctx *ctx, void *dst_dev, const void *src, size_t byt
             if (hipMemcpyAsync((char *)dst_dev + o, g_up_stage[dev][t], len, hipMemcpyHostToDevice, st) != hipSuccess ||
                 hipEventRecord(g_up_ev[dev][t], st) != hipSuccess) { failed = 1; return; }
         }
+        if (!first && hipEventSynchronize(g_up_ev[dev][t]) != hipSuccess) failed = 1;  // this call's last DMA out of buffer t
     };
     std::vector<std::thread> th;
     for (int t = 1; t < P; t++) th.emplace_back(work, t);
     work(0);
     for (auto &t : th) t.join();
-    if (failed) { (void)hipGetLastError(); ctx->set_error("nnd_set_data_host: staged host-to-device copy failed"); return 1; }
+    if (failed) {  // (no DMA out of a staging buffer may outlive the call: the next one writes into them)
+        (void)hipStreamSynchronize(st);
+        (void)hipGetLastError();
+        ctx->set_error("nnd_set_data_host: staged host-to-device copy failed");
+        return 1;
+    }
     return 0;
 }
 

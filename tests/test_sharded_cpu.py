@@ -104,3 +104,34 @@ def test_bench_load_points_formats(tmp_path):
     assert a.dtype == b.dtype == np.float32 and a.flags.c_contiguous and b.flags.c_contiguous
     np.testing.assert_array_equal(a, x)
     np.testing.assert_array_equal(b, x)
+
+
+def test_bench_dump_outputs_sample_and_cap(tmp_path):
+    """bench.py --dump-outputs: every row when the graph fits under the cap, else the same seeded sample on every call; ids
+    exact in float64, distances float32, the files within the cap."""
+    import torch
+
+    import bench
+
+    rs = np.random.RandomState(1)
+    for n, k in ((500, 15), (2_000_000, 30)):
+        idx = torch.from_numpy(rs.randint(0, n, size=(n, k)).astype(np.int32))
+        dist = torch.from_numpy(rs.uniform(0, 1e4, size=(n, k)).astype(np.float32))
+        info = [bench.dump_outputs(str(tmp_path / ("%d_%d" % (n, r))), idx, dist) for r in range(2)]
+        assert info[0]["rows"] == info[1]["rows"] and info[0]["of_rows"] == n and info[0]["k"] == k
+        got = [{name: np.load(tmp_path / ("%d_%d" % (n, r)) / (name + ".npy")) for name in
+                ("rows", "neighbor_indices", "neighbor_distances")} for r in range(2)]
+        for name in got[0]:
+            np.testing.assert_array_equal(got[0][name], got[1][name])
+        rows = got[0]["rows"].astype(np.int64)
+        assert got[0]["rows"].dtype == got[0]["neighbor_indices"].dtype == np.float64
+        assert got[0]["neighbor_distances"].dtype == np.float32
+        assert len(rows) == info[0]["rows"] and np.all(np.diff(rows) > 0)
+        if n == 500:
+            assert len(rows) == n
+        else:
+            assert 0 < len(rows) < n
+        np.testing.assert_array_equal(got[0]["neighbor_indices"], idx.numpy()[rows].astype(np.float64))
+        np.testing.assert_array_equal(got[0]["neighbor_distances"], dist.numpy()[rows])
+        size = sum(os.path.getsize(tmp_path / ("%d_0" % n) / (name + ".npy")) for name in got[0])
+        assert size <= 64_000_000, size
