@@ -20,10 +20,13 @@
  *     available from nnd_last_error(handle) (or nnd_last_global_error() when no
  *     handle exists yet).  There is NO CPU fallback: without a gfx950 device
  *     nnd_create fails.
- *   - "alt space": distances are squared-euclidean (metric 0) or
- *     log2(|x||y|/<x,y>) (metric 1), exactly what the reference keeps in
- *     NNDescent._neighbor_graph (distances.py:63-91, 583-630); the caller applies
- *     sqrt / 1-2^-d itself (distances.py:2170-2173), as NNDescent.neighbor_graph does.
+ *   - "alt space": distances are squared-euclidean (metric 0),
+ *     log2(|x||y|/<x,y>) (metric 1), -log2<x,y> of L2-normalised rows (2),
+ *     1/<x,y> (3), 1 - Pearson correlation (4) or log2(sqrt(|x|_1|y|_1) /
+ *     sum sqrt(x_i y_i)) (5), exactly what the reference keeps in
+ *     NNDescent._neighbor_graph (distances.py:63-91, 583-630, 680, 759, 1284, 1387);
+ *     the caller applies sqrt / 1-2^-d / -1/d / sqrt(1-2^-d) itself
+ *     (distances.py:2170-2173), as NNDescent.neighbor_graph does.
  *   - Output rows are ascending in distance; missing entries are (-1, +inf) at
  *     the row tail (utils.py:130-158, 189-218).
  *   - One handle = one GPU = one HIP stream.  Calls on one handle must be
@@ -40,6 +43,10 @@ extern "C" {
 
 #define NND_METRIC_SQEUCLIDEAN 0 /* reference distances.py:63  squared_euclidean  */
 #define NND_METRIC_ALT_COSINE 1  /* reference distances.py:583 alternative_cosine */
+#define NND_METRIC_ALT_DOT 2     /* reference distances.py:680 alternative_dot (rows L2-normalised by the kernels) */
+#define NND_METRIC_ALT_INNER_PRODUCT 3 /* reference distances.py:759 alternative_inner_product (rows as given) */
+#define NND_METRIC_CORRELATION 4 /* reference distances.py:1284 correlation (a true distance: no correction) */
+#define NND_METRIC_ALT_HELLINGER 5 /* reference distances.py:1387 alternative_hellinger (input must be >= 0) */
 
 #define NND_ABI_VERSION 6 /* 6 (round 6): nnd_stats grew join_substeps[] and nnd_shard_info grew gather_bytes[] / gather_section[] at their ends; nnd_host_alloc / nnd_host_free; 5: nnd_search_graph / nnd_search_graph_fetch */
 
@@ -173,6 +180,10 @@ int32_t nnd_set_data_device(nnd_handle_t h, const float *x_dev);
  * rejects such input in check_array (pynndescent_.py:1054) with a scan of its own; the host mirror raises the same
  * error from this flag instead of scanning 488 MB on one core (24 ms at 1 M x 128). */
 int32_t nnd_data_nonfinite(nnd_handle_t h, int32_t *out);
+/* *out = 1 when the metric is NND_METRIC_ALT_HELLINGER and the point set held a negative entry (raised by the prep kernel
+ * in the same pass).  The reference computes NaN distances from such input without a word; the host mirror raises
+ * ValueError instead.  0 for every other metric. */
+int32_t nnd_data_negative(nnd_handle_t h, int32_t *out);
 
 /* make_forest (rp_trees.py:2815-2888): builds all n_trees trees level-synchronously on device. */
 int32_t nnd_make_forest(nnd_handle_t h);
@@ -417,7 +428,7 @@ int32_t nnd_search_graph_fetch(nnd_handle_t h, int32_t *indptr_host, int32_t *in
  * Built level-synchronously on the device from the ORIGINAL rows (nnd_set_data_*; the handle must have been created
  * with n_trees >= 1: the builder borrows the forest's scan / scatter buffers) and the finished graph's in-degrees:
  * rank_order = the point ids sorted by (-in-degree, id) (compute_global_degrees, rp_trees.py:714-744, is a bincount of
- * the neighbour array; the order is host glue).  Angular splits when the handle's metric is NND_METRIC_ALT_COSINE.
+ * the neighbour array; the order is host glue).  Angular splits when the handle's metric is one of the angular codes (1, 2, 4, 5).
  * Result: the reference's FlatTree in pre-order numbering: hyperplanes (n_nodes, dim), offsets (n_nodes),
  * children (n_nodes, 2) [internal: child node ids; leaf: (-leaf_start, -leaf_end) into indices], indices (n). */
 int32_t nnd_hub_tree_build(nnd_handle_t h, const int32_t *rank_order_host, int32_t leaf_size, int32_t max_depth,

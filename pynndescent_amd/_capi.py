@@ -13,10 +13,15 @@ LIB_PATH = os.environ.get("PYNND_AMD_LIB", os.path.join(_HERE, "libpynnd_amd.so"
 
 NND_METRIC_SQEUCLIDEAN = 0
 NND_METRIC_ALT_COSINE = 1
-# the reference's metric names on this path -> the space the kernels work in ("sqeuclidean" is that space itself: no correction,
-# distances.py named_distances / fast_distance_alternatives)
+NND_METRIC_ALT_DOT = 2
+NND_METRIC_ALT_INNER_PRODUCT = 3
+NND_METRIC_CORRELATION = 4
+NND_METRIC_ALT_HELLINGER = 5
+# the reference's metric names on this path -> the space the kernels work in ("sqeuclidean" and "correlation" are that space
+# itself: no correction, distances.py named_distances / fast_distance_alternatives)
 METRIC_CODES = {"euclidean": NND_METRIC_SQEUCLIDEAN, "l2": NND_METRIC_SQEUCLIDEAN, "sqeuclidean": NND_METRIC_SQEUCLIDEAN,
-                "cosine": NND_METRIC_ALT_COSINE}
+                "cosine": NND_METRIC_ALT_COSINE, "dot": NND_METRIC_ALT_DOT, "inner_product": NND_METRIC_ALT_INNER_PRODUCT,
+                "correlation": NND_METRIC_CORRELATION, "hellinger": NND_METRIC_ALT_HELLINGER}
 NND_FLAG_NO_GRAPH = 1  # auxiliary handle: no k-lists / candidate / proposal tables (pruning pass, hub tree)
 NND_FLAG_NO_PREP = 2   # ... and no prepared copy of the rows (hub tree only)
 NND_FLAG_TEST_SELECT_WAVE = 4  # test hook: the one-wave-per-vertex selection kernel
@@ -169,6 +174,7 @@ _SIGNATURES = [
     ("nnd_set_data_host", C.c_int32, [_H, C.c_void_p]),
     ("nnd_set_data_device", C.c_int32, [_H, C.c_void_p]),
     ("nnd_data_nonfinite", C.c_int32, [_H, C.POINTER(C.c_int32)]),
+    ("nnd_data_negative", C.c_int32, [_H, C.POINTER(C.c_int32)]),
     ("nnd_release_pending", C.c_int32, []),
     ("nnd_host_copy", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64]),
     ("nnd_host_sqrt_f32", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64]),
@@ -323,6 +329,12 @@ class Builder:
         """True when the point set handed in held a NaN or an infinity (flag raised by the prep kernel)."""
         out = C.c_int32()
         self._check(self.lib.nnd_data_nonfinite(self._h, C.byref(out)))
+        return bool(out.value)
+
+    def data_negative(self):
+        """True when the metric is hellinger and the point set held a negative entry (flag raised by the prep kernel)."""
+        out = C.c_int32()
+        self._check(self.lib.nnd_data_negative(self._h, C.byref(out)))
         return bool(out.value)
 
     def set_data_device(self, dev_ptr, keepalive=None):

@@ -131,7 +131,7 @@ int nnd_create_impl(nnd_handle_t *out, const nnd_params *p, const int64_t *bound
     if (!out || !p) { gerr("nnd_create: null argument"); return 1; }
     *out = nullptr;
     if (p->n < 1 || p->dim < 1) { gerr("nnd_create: need n >= 1 and dim >= 1 (got n=%lld dim=%d)", (long long)p->n, p->dim); return 1; }
-    if (p->metric != NND_METRIC_SQEUCLIDEAN && p->metric != NND_METRIC_ALT_COSINE) { gerr("nnd_create: unknown metric %d", p->metric); return 1; }
+    if (p->metric < NND_METRIC_SQEUCLIDEAN || p->metric > NND_METRIC_ALT_HELLINGER) { gerr("nnd_create: unknown metric %d", p->metric); return 1; }
     if (p->n_neighbors < 1 || p->n_neighbors > NND_WIDE_K) { gerr("nnd_create: n_neighbors must be in 1..%d (got %d)", NND_WIDE_K, p->n_neighbors); return 1; }
     if (p->max_candidates < 1 || p->max_candidates > 128) { gerr("nnd_create: max_candidates must be in 1..128 (got %d)", p->max_candidates); return 1; }
     if (p->n_trees < 0 || p->n_trees > 4096 || p->leaf_size < 1) { gerr("nnd_create: bad n_trees (0..4096) / leaf_size"); return 1; }
@@ -539,7 +539,16 @@ extern "C" int32_t nnd_data_nonfinite(nnd_handle_t ctx, int32_t *out) {
     if (need_data(ctx)) return 1;
     if (ctx->p.flags & NND_FLAG_NO_PREP) { *out = 0; return 0; }
     API_HIP(nnd_sync_spin(ctx));
-    *out = ctx->h_pin[63] != 0 ? 1 : 0;
+    *out = (ctx->h_pin[63] & 1) != 0 ? 1 : 0;
+    return 0;
+}
+// 1 when a hellinger point set held a negative entry (bit 1 of the prep kernel's flag word; bit 0 is the non-finite flag)
+extern "C" int32_t nnd_data_negative(nnd_handle_t ctx, int32_t *out) {
+    ENTER(ctx);
+    if (need_data(ctx)) return 1;
+    if (ctx->p.flags & NND_FLAG_NO_PREP) { *out = 0; return 0; }
+    API_HIP(nnd_sync_spin(ctx));
+    *out = (ctx->h_pin[63] & 2) != 0 ? 1 : 0;
     return 0;
 }
 
@@ -1186,7 +1195,7 @@ extern "C" int32_t nnd_hub_tree_build(nnd_handle_t ctx, const int32_t *rank_orde
     ENTER(ctx);
     if (need_data(ctx)) return 1;
     if (!rank_order) { ctx->set_error("nnd_hub_tree_build: null rank order"); return 1; }
-    if (nnd_hub_tree_build_impl(ctx, rank_order, leaf_size, max_depth, ctx->p.metric == NND_METRIC_ALT_COSINE)) return 1;
+    if (nnd_hub_tree_build_impl(ctx, rank_order, leaf_size, max_depth, nnd_metric_unit(ctx->p.metric))) return 1;
     if (n_nodes_out) *n_nodes_out = nnd_hub_tree_nodes(ctx);
     return 0;
 }

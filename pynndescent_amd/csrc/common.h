@@ -165,15 +165,52 @@ __device__ __forceinline__ float nnd_h16_to_f32(uint16_t b, float inv_scale) { r
 
 __device__ __forceinline__ float nnd_clamp_dist(float d) { return d > 0.0f ? d : 0.0f; }
 
-// Gram value -> alt-space distance.
-//   euclid: |a|^2 + |b|^2 - 2<a,b>          (reference distances.py:63-91 in Gram form)
-//   cosine: rows are pre-normalised, na/nb are 1 (non-zero row) or 0 (zero row):
-//           0 if both zero, FLT_MAX if one zero or <a,b> <= 0, else -log2(<a,b>) (distances.py:583-630)
+// Metric codes (include/pynnd_amd.h NND_METRIC_*): 0 sqeuclidean, 1 alt cosine, 2 alt dot, 3 alt inner product,
+// 4 correlation, 5 alt hellinger.  The prep kernel turns every row into a "prepared" row whose inner products give the
+// distance (DESIGN.md "Metrics"):
+//   unit metrics (1, 2, 4, 5): rows L2-normalised after a per-metric transform (none / none / minus the row mean / sqrt);
+//     nrm = 1 (non-zero row) or 0 (zero row); the trees split angularly;
+//   norm metrics (0, 3): rows centred on the column mean (0) or as given (3); nrm = |x|^2; euclidean trees.
+__host__ __device__ __forceinline__ bool nnd_metric_unit(int metric) { return metric == 1 || metric == 2 || metric == 4 || metric == 5; }
+
+// Gram value -> alt-space distance.  Every value is >= 0: the k-lists order distances by their float bits.
+//   euclid:  |a|^2 + |b|^2 - 2<a,b>          (reference distances.py:63-91 in Gram form)
+//   cosine / hellinger: rows are pre-normalised, na/nb are 1 (non-zero row) or 0 (zero row):
+//            0 if both zero, FLT_MAX if one zero or <a,b> <= 0, else -log2(<a,b>) (distances.py:583-630, 1387-1417)
+//   dot:     FLT_MAX if either row is zero (both zero too) or <a,b> <= 0, else -log2(<a,b>) (distances.py:680-702)
+//   inner product: FLT_MAX if <a,b> <= 0, else 1 / <a,b> (distances.py:759-790)
+//   correlation: rows centred and normalised: 0 if both zero, else 1 - <a,b> clamped >= 0 (distances.py:1284-1313)
 __device__ __forceinline__ float nnd_gram_to_dist(int metric, float g, float na, float nb) {
+    if (metric == 0) return nnd_clamp_dist(na + nb - 2.0f * g);
+    if (metric == 3) return g > 0.0f ? fminf(1.0f / g, NND_FLT_MAX) : NND_FLT_MAX;
+    if (na == 0.0f && nb == 0.0f && metric != 2) return 0.0f;
+    if (metric == 4) return nnd_clamp_dist(1.0f - g);
+    if (na == 0.0f || nb == 0.0f || g <= 0.0f) return NND_FLT_MAX;
+    return nnd_clamp_dist(-__log2f(g));
+}
+// d(x, x) of a row with prepared norm value n (nrm): the join kernels set the self pair by this rule instead of the Gram
+// value.  The reference does evaluate the pair (utils.py:619 starts the inner loop at j): 0 for every metric whose
+// distance to itself is 0, FLT_MAX for a zero row under dot, 1 / |x|^2 under inner product.
+__device__ __forceinline__ float nnd_self_dist(int metric, float n) {
+    if (metric == 3) return n > 0.0f ? fminf(1.0f / n, NND_FLT_MAX) : NND_FLT_MAX;
+    if (metric == 2 && n == 0.0f) return NND_FLT_MAX;
+    return 0.0f;
+}
+
+// The same with the metric family fixed at compile time.  XM = false: sqeuclidean / cosine only (the conversion of the
+// kernels before the other metrics existed, instruction for instruction); XM = true: every metric.
+template <bool XM>
+__device__ __forceinline__ float nnd_gram_to_dist_t(int metric, float g, float na, float nb) {
+    if constexpr (XM) return nnd_gram_to_dist(metric, g, na, nb);
     if (metric == 0) return nnd_clamp_dist(na + nb - 2.0f * g);
     if (na == 0.0f && nb == 0.0f) return 0.0f;
     if (na == 0.0f || nb == 0.0f || g <= 0.0f) return NND_FLT_MAX;
     return nnd_clamp_dist(-__log2f(g));
+}
+template <bool XM>
+__device__ __forceinline__ float nnd_self_dist_t(int metric, float n) {
+    if constexpr (XM) return nnd_self_dist(metric, n);
+    return 0.0f;
 }
 
 // Swizzled LDS addressing for row tiles read as MFMA operands.

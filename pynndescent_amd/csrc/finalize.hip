@@ -4,7 +4,9 @@
 // slots (-1, +inf) last.  The k-lists carry Gram-form f32 distances of centred / normalised rows
 // (good enough to RANK); the distances handed back are recomputed from the ORIGINAL rows in the
 // reference's own formulas (distances.py:63-91 squared difference sum; distances.py:583-630
-// log2(sqrt(|x|^2|y|^2)/<x,y>)) with float64 accumulation, then rows are re-sorted by that value.
+// log2(sqrt(|x|^2|y|^2)/<x,y>); dot -log2<x,y> :680 on the rows as given (NNDescent normalises them on the host);
+// inner product 1/<x,y> :759; correlation :1284 with the row means first; hellinger :1387) with float64 accumulation,
+// then rows are re-sorted by that value.
 #include "common.h"
 #include "state.h"
 
@@ -15,11 +17,49 @@ __device__ __forceinline__ double fin_group16_sum_f64(double v) {
     return v;
 }
 
+// The metrics of codes 2..5 (include/pynnd_amd.h): one coordinate pair into the float64 accumulators (correlation: a and b
+// already centred), then the accumulated sums into the reference's distance.
+__device__ __forceinline__ void fin_acc_x(int metric, double a, double b, double &dot, double &nx, double &ny) {
+    if (metric == 5) {
+        dot += (double)sqrtf((float)a * (float)b);  // alternative_hellinger: sum sqrt(x_i y_i) (float32 terms, as the reference's), |x|_1, |y|_1
+        nx += a;
+        ny += b;
+    } else {
+        dot += a * b;
+        nx += a * a;
+        ny += b * b;
+    }
+}
+__device__ __forceinline__ float fin_value_x(int metric, double dt, double ax, double ay) {
+    if (metric == 2 || metric == 3) {  // alternative_dot / alternative_inner_product: FLT_MAX for <x,y> <= 0
+        if (!(dt > 0.0)) return NND_FLT_MAX;
+        const double r = metric == 2 ? -log2(dt) : 1.0 / dt;
+        return r > 0.0 ? (float)fmin(r, (double)NND_FLT_MAX) : 0.0f;
+    }
+    if (metric == 4) {  // correlation: 0 if both rows have zero variance, 1 if <x,y> = 0
+        if (ax == 0.0 && ay == 0.0) return 0.0f;
+        if (dt == 0.0) return 1.0f;
+        const double r = 1.0 - dt / sqrt(ax * ay);
+        return r > 0.0 ? (float)r : 0.0f;
+    }
+    if (ax == 0.0 && ay == 0.0) return 0.0f;  // alternative_hellinger
+    if (ax == 0.0 || ay == 0.0 || dt <= 0.0) return NND_FLT_MAX;
+    const double r = log2(sqrt(ax * ay) / dt);
+    return r > 0.0 ? (float)r : 0.0f;
+}
+// correlation: the mean of row `xr` over the 16 lanes of a group (float64, as the reference's correlation)
+__device__ __forceinline__ double fin_row_mean(const float *xr, int d, int l16) {
+    double m = 0.0;
+    for (int t = l16; t < d; t += 16) m += (double)xr[t];
+    return fin_group16_sum_f64(m) / (double)d;
+}
+
 // One wave per row.  The 64 lanes work as 4 groups of 16: group g takes neighbours g, 4+g, 8+g, ... so four distances
 // are accumulated side by side and up to 16 neighbour rows are in flight per wave (the gather is latency bound when
 // the rows are fetched one after another).
 // METRIC is a template parameter: the euclidean instance does not carry the cosine accumulators (146 -> far fewer
-// registers, i.e. more waves per SIMD for what is a gather-latency-bound kernel).
+// registers, i.e. more waves per SIMD for what is a gather-latency-bound kernel).  METRIC 2..5: the other metrics, one
+// instance each (fin_acc_x / fin_value_x).
 template <int METRIC>
 __global__ __launch_bounds__(256, METRIC == 0 ? 6 : 4) void k_finalize(const float *__restrict__ x, int d, int64_t lo, int64_t n, int k, int ks,
                                                   const uint32_t *__restrict__ knn_e, const int32_t *__restrict__ order,
@@ -51,6 +91,12 @@ __global__ __launch_bounds__(256, METRIC == 0 ? 6 : 4) void k_finalize(const flo
             xu[u] = x + (int64_t)(on[u] ? (ej & NND_IDX_MASK) : 0) * d;
             s[u] = dot[u] = nx[u] = ny[u] = 0.0;
         }
+        double mua = 0.0, mub[4] = {0.0, 0.0, 0.0, 0.0};  // correlation: the row means
+        if (metric == 4) {
+            mua = fin_row_mean(xv, d, l16);
+#pragma unroll
+            for (int u = 0; u < 4; u++) mub[u] = fin_row_mean(xu[u], d, l16);
+        }
         if (vec) {
             for (int t = 4 * l16; t < d; t += 64) {
                 const float4 a = *(const float4 *)(xv + t);
@@ -63,10 +109,15 @@ __global__ __launch_bounds__(256, METRIC == 0 ? 6 : 4) void k_finalize(const flo
                     const double b0 = q[u].x, b1 = q[u].y, b2 = q[u].z, b3 = q[u].w;
                     if (metric == 0) {
                         s[u] += (a0 - b0) * (a0 - b0) + (a1 - b1) * (a1 - b1) + (a2 - b2) * (a2 - b2) + (a3 - b3) * (a3 - b3);
-                    } else {
+                    } else if (metric == 1) {
                         dot[u] += a0 * b0 + a1 * b1 + a2 * b2 + a3 * b3;
                         nx[u] += a0 * a0 + a1 * a1 + a2 * a2 + a3 * a3;
                         ny[u] += b0 * b0 + b1 * b1 + b2 * b2 + b3 * b3;
+                    } else {
+                        fin_acc_x(metric, a0 - mua, b0 - mub[u], dot[u], nx[u], ny[u]);
+                        fin_acc_x(metric, a1 - mua, b1 - mub[u], dot[u], nx[u], ny[u]);
+                        fin_acc_x(metric, a2 - mua, b2 - mub[u], dot[u], nx[u], ny[u]);
+                        fin_acc_x(metric, a3 - mua, b3 - mub[u], dot[u], nx[u], ny[u]);
                     }
                 }
             }
@@ -77,10 +128,12 @@ __global__ __launch_bounds__(256, METRIC == 0 ? 6 : 4) void k_finalize(const flo
                 for (int u = 0; u < 4; u++) {
                     const double b0 = xu[u][t];
                     if (metric == 0) s[u] += (a0 - b0) * (a0 - b0);
-                    else {
+                    else if (metric == 1) {
                         dot[u] += a0 * b0;
                         nx[u] += a0 * a0;
                         ny[u] += b0 * b0;
+                    } else {
+                        fin_acc_x(metric, a0 - mua, b0 - mub[u], dot[u], nx[u], ny[u]);
                     }
                 }
             }
@@ -90,6 +143,9 @@ __global__ __launch_bounds__(256, METRIC == 0 ? 6 : 4) void k_finalize(const flo
             float val;
             if (metric == 0) {
                 val = (float)fin_group16_sum_f64(s[u]);
+            } else if (metric != 1) {
+                const double dt = fin_group16_sum_f64(dot[u]), ax = fin_group16_sum_f64(nx[u]), ay = fin_group16_sum_f64(ny[u]);
+                val = fin_value_x(metric, dt, ax, ay);
             } else {
                 const double dt = fin_group16_sum_f64(dot[u]), ax = fin_group16_sum_f64(nx[u]), ay = fin_group16_sum_f64(ny[u]);
                 if (ax == 0.0 && ay == 0.0) val = 0.0f;
@@ -120,7 +176,9 @@ __global__ __launch_bounds__(256, METRIC == 0 ? 6 : 4) void k_finalize(const flo
 }
 
 // 64 < k <= NND_WIDE_K: one wave per row, ids / exact distances through LDS, four neighbours at a time (16 lanes each), ranks by
-// counting over the LDS copy.  Same arithmetic as k_finalize (float64 accumulation of the reference's formulas).
+// counting over the LDS copy.  Same arithmetic as k_finalize (float64 accumulation of the reference's formulas).  XM: the
+// instance for the metrics of codes 2..5 (the sqeuclidean / cosine instance does not carry their registers).
+template <bool XM>
 __global__ __launch_bounds__(256) void k_finalize_wide(const float *__restrict__ x, int d, int64_t lo, int64_t n, int k, int ks, int metric,
                                                        const uint32_t *__restrict__ knn_e, int32_t *__restrict__ out_idx,
                                                        float *__restrict__ out_dist) {
@@ -138,18 +196,25 @@ __global__ __launch_bounds__(256) void k_finalize_wide(const float *__restrict__
         const bool on = ej != NND_EMPTY_E;
         const float *xu = x + (int64_t)(on ? (ej & NND_IDX_MASK) : 0) * d;
         double s = 0.0, dot = 0.0, nx = 0.0, ny = 0.0;
-        for (int t = l16; t < d; t += 16) {
-            const double a0 = xv[t], b0 = xu[t];
-            if (metric == 0) s += (a0 - b0) * (a0 - b0);
-            else {
-                dot += a0 * b0;
-                nx += a0 * a0;
-                ny += b0 * b0;
+        if constexpr (XM) {  // the metrics of codes 2..5 (fin_acc_x)
+            const double mua = metric == 4 ? fin_row_mean(xv, d, l16) : 0.0, mub = metric == 4 ? fin_row_mean(xu, d, l16) : 0.0;
+            for (int t = l16; t < d; t += 16) fin_acc_x(metric, (double)xv[t] - mua, (double)xu[t] - mub, dot, nx, ny);
+        } else {
+            for (int t = l16; t < d; t += 16) {
+                const double a0 = xv[t], b0 = xu[t];
+                if (metric == 0) s += (a0 - b0) * (a0 - b0);
+                else {
+                    dot += a0 * b0;
+                    nx += a0 * a0;
+                    ny += b0 * b0;
+                }
             }
         }
         float val;
         if (metric == 0) {
             val = (float)fin_group16_sum_f64(s);
+        } else if (XM) {
+            val = fin_value_x(metric, fin_group16_sum_f64(dot), fin_group16_sum_f64(nx), fin_group16_sum_f64(ny));
         } else {
             const double dt = fin_group16_sum_f64(dot), ax = fin_group16_sum_f64(nx), ay = fin_group16_sum_f64(ny);
             if (ax == 0.0 && ay == 0.0) val = 0.0f;
@@ -181,18 +246,22 @@ __global__ __launch_bounds__(256) void k_finalize_wide(const float *__restrict__
 int nnd_launch_finalize(nnd_ctx *ctx, int32_t *out_idx_dev, float *out_dist_dev) {
     unsigned grid = (unsigned)((ctx->own_hi - ctx->own_lo + 3) / 4);
     if (ctx->k > 64) {
-        hipLaunchKernelGGL(k_finalize_wide, dim3(grid), dim3(256), 0, ctx->stream, ctx->x_orig, ctx->d, ctx->own_lo, ctx->own_hi, ctx->k, ctx->ks,
+        hipLaunchKernelGGL(ctx->p.metric >= 2 ? k_finalize_wide<true> : k_finalize_wide<false>, dim3(grid), dim3(256), 0, ctx->stream, ctx->x_orig, ctx->d, ctx->own_lo, ctx->own_hi, ctx->k, ctx->ks,
                            ctx->p.metric, ctx->knn_e, out_idx_dev, out_dist_dev);
         NND_HIP_CHECK(hipGetLastError());
         return 0;
     }
     grid = (grid + 7u) & ~7u;  // whole multiples of the XCD count
-    if (ctx->p.metric == 0)
-        hipLaunchKernelGGL(k_finalize<0>, dim3(grid), dim3(256), 0, ctx->stream, ctx->x_orig, ctx->d, ctx->own_lo, ctx->own_hi,
-                           ctx->k, ctx->ks, ctx->knn_e, nnd_vertex_order(ctx), out_idx_dev, out_dist_dev);
-    else
-        hipLaunchKernelGGL(k_finalize<1>, dim3(grid), dim3(256), 0, ctx->stream, ctx->x_orig, ctx->d, ctx->own_lo, ctx->own_hi,
-                           ctx->k, ctx->ks, ctx->knn_e, nnd_vertex_order(ctx), out_idx_dev, out_dist_dev);
+    auto kern = k_finalize<0>;
+    switch (ctx->p.metric) {
+        case 1: kern = k_finalize<1>; break;
+        case 2: kern = k_finalize<2>; break;
+        case 3: kern = k_finalize<3>; break;
+        case 4: kern = k_finalize<4>; break;
+        case 5: kern = k_finalize<5>; break;
+    }
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, ctx->stream, ctx->x_orig, ctx->d, ctx->own_lo, ctx->own_hi,
+                       ctx->k, ctx->ks, ctx->knn_e, nnd_vertex_order(ctx), out_idx_dev, out_dist_dev);
     NND_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -54,7 +54,7 @@ __device__ __forceinline__ bool klist_has(const uint32_t *kl, uint32_t id) {
 #ifndef NND_J16_WAVES
 #define NND_J16_WAVES 3
 #endif
-template <int DC, int KS16, bool SHARD>
+template <int DC, int KS16, bool SHARD, bool XM = false>
 __global__ __launch_bounds__(256, NND_J16_WAVES) void k_local_join16(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
                                                          int metric, const int32_t *__restrict__ cand,
                                                          const int32_t *__restrict__ order, int64_t v_begin,
@@ -334,7 +334,7 @@ __global__ __launch_bounds__(256, NND_J16_WAVES) void k_local_join16(const float
                     const bool valid = pid >= 0 && qid >= 0 && (jj >= MCP || jj >= i);
                     tot_pairs += valid ? 1 : 0;
                     const bool self = (pid == qid);
-                    const float d = self ? 0.0f : nnd_gram_to_dist(metric, acc[J][r], pn4[r], qn_);
+                    const float d = self ? nnd_self_dist_t<XM>(metric, pn4[r]) : nnd_gram_to_dist_t<XM>(metric, acc[J][r], pn4[r], qn_);
 #ifdef NND_JOIN_NOEPI
                     const bool need_p = valid && d == -12345.0f, need_q = false;
 #else
@@ -392,12 +392,12 @@ static const int32_t *join_order(const nnd_ctx *ctx, int64_t &v_begin, int64_t &
     return order;
 }
 
-template <int DC, int KS16, bool SHARD>
+template <int DC, int KS16, bool SHARD, bool XM>
 static int launch_join16_t(nnd_ctx *ctx, int64_t v_begin, int64_t v_end) {
     constexpr int RV = 32, kls = KS16 * 16 + 4;
     constexpr int WAVE_BYTES = NND_J16_QCAP * 8 + 2 * RV * 4 + 4 * 4 + 5 * RV * 4 + RV * kls * 4 + 8;  // = the kernel's
     size_t smem = 4 * (size_t)((WAVE_BYTES + 15) & ~15);
-    auto kern = k_local_join16<DC, KS16, SHARD>;
+    auto kern = k_local_join16<DC, KS16, SHARD, XM>;
     // function attributes and occupancy are per DEVICE: cached per device ordinal, not per process
     static int wg_per_cu_dev[64] = {0}, n_cu_dev[64] = {0};
     int &wg_per_cu = wg_per_cu_dev[ctx->p.device & 63], &n_cu = n_cu_dev[ctx->p.device & 63];
@@ -429,16 +429,16 @@ static int launch_join16_t(nnd_ctx *ctx, int64_t v_begin, int64_t v_end) {
     return 0;
 }
 
-template <int DC>
+template <int DC, bool XM>
 static int launch_join16_ks(nnd_ctx *ctx, int64_t v_begin, int64_t v_end) {
     if (ctx->pbuf_r) {  // a shard of a row-sharded build: proposals for rows owned elsewhere go to the narrow table
-        if (ctx->ks <= 16) return launch_join16_t<DC, 1, true>(ctx, v_begin, v_end);
-        if (ctx->ks <= 32) return launch_join16_t<DC, 2, true>(ctx, v_begin, v_end);
-        return launch_join16_t<DC, 4, true>(ctx, v_begin, v_end);
+        if (ctx->ks <= 16) return launch_join16_t<DC, 1, true, XM>(ctx, v_begin, v_end);
+        if (ctx->ks <= 32) return launch_join16_t<DC, 2, true, XM>(ctx, v_begin, v_end);
+        return launch_join16_t<DC, 4, true, XM>(ctx, v_begin, v_end);
     }
-    if (ctx->ks <= 16) return launch_join16_t<DC, 1, false>(ctx, v_begin, v_end);
-    if (ctx->ks <= 32) return launch_join16_t<DC, 2, false>(ctx, v_begin, v_end);
-    return launch_join16_t<DC, 4, false>(ctx, v_begin, v_end);
+    if (ctx->ks <= 16) return launch_join16_t<DC, 1, false, XM>(ctx, v_begin, v_end);
+    if (ctx->ks <= 32) return launch_join16_t<DC, 2, false, XM>(ctx, v_begin, v_end);
+    return launch_join16_t<DC, 4, false, XM>(ctx, v_begin, v_end);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -487,7 +487,7 @@ __device__ __forceinline__ void nnd_glds16(const void *src, void *lds_dst_wave_u
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(uintptr_t)src,
                                      (__attribute__((address_space(3))) void *)off, 16, 0, 0);
 }
-template <int MCP, int DC, bool SHARD, bool BLOCKED = false, bool SKIP_TRI = false, int ASEL = -1, bool KL = false>
+template <int MCP, int DC, bool SHARD, bool BLOCKED = false, bool SKIP_TRI = false, int ASEL = -1, bool KL = false, bool XM = false>
 __global__ __launch_bounds__(256, MCP == 32 ? (ASEL >= 0 ? NND_JW_WAVES_SPLIT : NND_JW_WAVES) : 2) void k_local_join_w(const float *__restrict__ xp, int dp,
                                                                        const float *__restrict__ nrm, int metric,
                                                                        const int32_t *__restrict__ cand,
@@ -794,7 +794,7 @@ __global__ __launch_bounds__(256, MCP == 32 ? (ASEL >= 0 ? NND_JW_WAVES_SPLIT : 
                         const bool valid = pid >= 0 && qid >= 0 && (jj >= MCP || jj >= i);
                         tot_pairs += valid ? 1 : 0;
                         const bool self = (pid == qid);
-                        const float d = self ? 0.0f : nnd_gram_to_dist(metric, acc[a][b][r], pn4[r], qn_);
+                        const float d = self ? nnd_self_dist_t<XM>(metric, pn4[r]) : nnd_gram_to_dist_t<XM>(metric, acc[a][b][r], pn4[r], qn_);
                         const bool need_p = valid && d < pth4[r], need_q = valid && !self && d < qth;
                         const unsigned long long pm = __ballot(need_p | need_q);
                         if (pm) {  // wave-uniform
@@ -841,12 +841,12 @@ __global__ __launch_bounds__(256, MCP == 32 ? (ASEL >= 0 ? NND_JW_WAVES_SPLIT : 
     }
 }
 
-template <int MCP, int DC, bool SHARD, bool BLOCKED = false, bool SKIP_TRI = false, int ASEL = -1, bool KL = false>
+template <int MCP, int DC, bool SHARD, bool BLOCKED, bool SKIP_TRI, int ASEL, bool KL, bool XM>
 static int launch_join_w_t(nnd_ctx *ctx, int64_t v_begin, int64_t v_end, int cstride = 0, int new_off = 0, int old_off = 0) {
     constexpr int RV = 2 * MCP;
     constexpr int WAVE_BYTES = join_w_lds<KL>::wave_bytes(RV);
     size_t smem = 4 * (size_t)((WAVE_BYTES + 15) & ~15);
-    auto kern = k_local_join_w<MCP, DC, SHARD, BLOCKED, SKIP_TRI, ASEL, KL>;
+    auto kern = k_local_join_w<MCP, DC, SHARD, BLOCKED, SKIP_TRI, ASEL, KL, XM>;
     // function attributes and occupancy are per DEVICE: cached per device ordinal, not per process
     static int wg_per_cu_dev[64] = {0}, n_cu_dev[64] = {0};
     int &wg_per_cu = wg_per_cu_dev[ctx->p.device & 63], &n_cu = n_cu_dev[ctx->p.device & 63];
@@ -875,16 +875,16 @@ static int launch_join_w_t(nnd_ctx *ctx, int64_t v_begin, int64_t v_end, int cst
     return 0;
 }
 
-template <int MCP, int DC>
+template <int MCP, int DC, bool XM>
 static int launch_join_w(nnd_ctx *ctx, int64_t v_begin, int64_t v_end) {
 #ifdef NND_JW_SPLIT  // two launches, one tile row of new candidates each (k_local_join_w, ASEL)
     if (MCP == 32) {
         if (ctx->pbuf_r) {
-            if (launch_join_w_t<MCP, DC, true, false, false, 0>(ctx, v_begin, v_end)) return 1;
-            return launch_join_w_t<MCP, DC, true, false, false, 1>(ctx, v_begin, v_end);
+            if (launch_join_w_t<MCP, DC, true, false, false, 0, false, XM>(ctx, v_begin, v_end)) return 1;
+            return launch_join_w_t<MCP, DC, true, false, false, 1, false, XM>(ctx, v_begin, v_end);
         }
-        if (launch_join_w_t<MCP, DC, false, false, false, 0>(ctx, v_begin, v_end)) return 1;
-        return launch_join_w_t<MCP, DC, false, false, false, 1>(ctx, v_begin, v_end);
+        if (launch_join_w_t<MCP, DC, false, false, false, 0, false, XM>(ctx, v_begin, v_end)) return 1;
+        return launch_join_w_t<MCP, DC, false, false, false, 1, false, XM>(ctx, v_begin, v_end);
     }
 #endif
 #ifndef NND_JW_NO_LDS_LISTS
@@ -895,7 +895,7 @@ static int launch_join_w(nnd_ctx *ctx, int64_t v_begin, int64_t v_end) {
             int &kl_ok = kl_ok_dev[ctx->p.device & 63];
             if (kl_ok == 0) {
                 constexpr size_t smem = 4 * (size_t)((join_w_lds<true>::wave_bytes(2 * MCP) + 15) & ~15);
-                auto kern = k_local_join_w<MCP, DC, false, false, false, -1, true>;
+                auto kern = k_local_join_w<MCP, DC, false, false, false, -1, true, XM>;
                 int occ = 0;
                 if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess ||
                     hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)kern, 256, smem) != hipSuccess) {
@@ -904,37 +904,45 @@ static int launch_join_w(nnd_ctx *ctx, int64_t v_begin, int64_t v_end) {
                 }
                 kl_ok = occ >= 3 ? 1 : -1;
             }
-            if (kl_ok > 0) return launch_join_w_t<MCP, DC, false, false, false, -1, true>(ctx, v_begin, v_end);
+            if (kl_ok > 0) return launch_join_w_t<MCP, DC, false, false, false, -1, true, XM>(ctx, v_begin, v_end);
         }
     }
 #endif
-    return ctx->pbuf_r ? launch_join_w_t<MCP, DC, true>(ctx, v_begin, v_end) : launch_join_w_t<MCP, DC, false>(ctx, v_begin, v_end);
+    return ctx->pbuf_r ? launch_join_w_t<MCP, DC, true, false, false, -1, false, XM>(ctx, v_begin, v_end)
+                        : launch_join_w_t<MCP, DC, false, false, false, -1, false, XM>(ctx, v_begin, v_end);
 }
 
 // max_candidates 65..128: candidate lists [newA(64) newB(64) | oldA(64) oldB(64)] (filled from the front: the B blocks are empty
 // unless a class has more than 64 candidates, and a pass whose `new` block is empty does nothing).  Five passes of the 64-slot
 // kernel cover every pair once: A x A + A x oldA, A x oldB, B x B + B x oldA, B x oldB, A x B.
-template <bool SHARD>
+template <bool SHARD, bool XM>
 static int launch_join_blocked(nnd_ctx *ctx, int64_t v_begin, int64_t v_end) {
-    if (launch_join_w_t<64, 32, SHARD, true, false>(ctx, v_begin, v_end, 256, 0, 128)) return 1;
-    if (launch_join_w_t<64, 32, SHARD, true, true>(ctx, v_begin, v_end, 256, 0, 192)) return 1;
-    if (launch_join_w_t<64, 32, SHARD, true, false>(ctx, v_begin, v_end, 256, 64, 128)) return 1;
-    if (launch_join_w_t<64, 32, SHARD, true, true>(ctx, v_begin, v_end, 256, 64, 192)) return 1;
-    return launch_join_w_t<64, 32, SHARD, true, true>(ctx, v_begin, v_end, 256, 0, 64);
+    if (launch_join_w_t<64, 32, SHARD, true, false, -1, false, XM>(ctx, v_begin, v_end, 256, 0, 128)) return 1;
+    if (launch_join_w_t<64, 32, SHARD, true, true, -1, false, XM>(ctx, v_begin, v_end, 256, 0, 192)) return 1;
+    if (launch_join_w_t<64, 32, SHARD, true, false, -1, false, XM>(ctx, v_begin, v_end, 256, 64, 128)) return 1;
+    if (launch_join_w_t<64, 32, SHARD, true, true, -1, false, XM>(ctx, v_begin, v_end, 256, 64, 192)) return 1;
+    return launch_join_w_t<64, 32, SHARD, true, true, -1, false, XM>(ctx, v_begin, v_end, 256, 0, 64);
 }
 
-int nnd_launch_join(nnd_ctx *ctx, int64_t v_begin, int64_t v_end) {
-    if (v_end <= v_begin) return 0;
+// XM: the instances for the metrics of codes 2..5 (common.h nnd_gram_to_dist_t); the sqeuclidean / cosine instances do not
+// carry their conversions (a runtime branch among six metrics costs the k_local_join16<32, *, false> epilogue four registers)
+template <bool XM>
+static int launch_join_xm(nnd_ctx *ctx, int64_t v_begin, int64_t v_end) {
     const bool wide = ctx->dp >= 128;
     switch (ctx->mcp) {
 #ifndef NND_J16_DCW
 #define NND_J16_DCW 64
 #endif
-        case 16: return wide ? launch_join16_ks<NND_J16_DCW>(ctx, v_begin, v_end) : launch_join16_ks<32>(ctx, v_begin, v_end);
-        case 32: return wide ? launch_join_w<32, NND_JW_DCW>(ctx, v_begin, v_end) : launch_join_w<32, NND_JW_DC>(ctx, v_begin, v_end);
-        case 64: return launch_join_w<64, NND_JW64_DC>(ctx, v_begin, v_end);
-        case 128: return ctx->pbuf_r ? launch_join_blocked<true>(ctx, v_begin, v_end) : launch_join_blocked<false>(ctx, v_begin, v_end);
+        case 16: return wide ? launch_join16_ks<NND_J16_DCW, XM>(ctx, v_begin, v_end) : launch_join16_ks<32, XM>(ctx, v_begin, v_end);
+        case 32: return wide ? launch_join_w<32, NND_JW_DCW, XM>(ctx, v_begin, v_end) : launch_join_w<32, NND_JW_DC, XM>(ctx, v_begin, v_end);
+        case 64: return launch_join_w<64, NND_JW64_DC, XM>(ctx, v_begin, v_end);
+        case 128: return ctx->pbuf_r ? launch_join_blocked<true, XM>(ctx, v_begin, v_end) : launch_join_blocked<false, XM>(ctx, v_begin, v_end);
     }
     ctx->set_error("unsupported padded max_candidates %d", ctx->mcp);
     return 1;
+}
+
+int nnd_launch_join(nnd_ctx *ctx, int64_t v_begin, int64_t v_end) {
+    if (v_end <= v_begin) return 0;
+    return ctx->p.metric >= 2 ? launch_join_xm<true>(ctx, v_begin, v_end) : launch_join_xm<false>(ctx, v_begin, v_end);
 }

@@ -209,7 +209,7 @@ __device__ __forceinline__ float row_dist(const float *__restrict__ xp, int dp, 
     }
     s = nnd_wave_sum_f32(s);
     if (metric == 0) return nnd_clamp_dist(s);
-    return nnd_gram_to_dist(1, s, nrm[a], nrm[b]);
+    return nnd_gram_to_dist(metric, s, nrm[a], nrm[b]);
 }
 
 // init_random (pynndescent_.py:188-203): rows that are not full get (k - filled) random candidates

@@ -7,6 +7,9 @@
 //       cosine rows are L2-normalised once (the reference recomputes both norms in every
 //       distance call, distances.py:617-620); zero rows stay zero and are flagged in nrm.
 //   nrm (n) float32: |xp_i|^2 for euclidean; 1 (non-zero row) / 0 (zero row) for cosine.
+// The other metrics (common.h nnd_metric_unit): dot rows are L2-normalised like cosine rows, correlation rows have their own
+// mean subtracted first, hellinger rows are sqrt(x) first (|sqrt x|^2 = |x|_1), all with nrm 1 / 0; inner-product rows stay
+// as given (no column mean: the distance is not translation invariant) with nrm = |x|^2.
 #include "common.h"
 #include "state.h"
 
@@ -67,7 +70,8 @@ __global__ __launch_bounds__(256) void k_colsum_final(const double *__restrict__
 // mean[dp] = scale of the screening copies (common.h nnd_f32_to_h16), mean[dp + 1] = 1 / scale^2 (a screened margin is
 // sum (s x_i)(s h_i)).  A power of two that takes the largest prepared component to <= 2^11: a hyperplane is a difference of
 // two rows (<= 2^12 after scaling), far from the half-precision overflow at 65504 (a row beyond the sampled maximum by
-// more than 16x overflows to inf and is always rechecked exactly: correct, slower).  Cosine rows are unit vectors.
+// more than 16x overflows to inf and is always rechecked exactly: correct, slower).  Unit-row metrics: bound 1; inner
+// product: rows as given, bound max |x|.
 __global__ void k_screen_scale(float *__restrict__ mean, int d, int dp, int metric) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     float bound = 1.0f;
@@ -75,12 +79,22 @@ __global__ void k_screen_scale(float *__restrict__ mean, int d, int dp, int metr
         float mm = 0.0f;
         for (int j = 0; j < d; j++) mm = fmaxf(mm, fabsf(mean[j]));
         bound = mean[dp + 2] + mm;  // |x_ij - mean_j| <= max |x| + max |mean|
+    } else if (metric == 3) {
+        bound = mean[dp + 2];
     }
     int e = 0;
     if (bound > 0.0f && bound < 3.0e38f) e = 11 - (int)ceilf(log2f(bound));
     e = e < -100 ? -100 : (e > 100 ? 100 : e);
     mean[dp] = exp2f((float)e);
     mean[dp + 1] = exp2f((float)(-2 * e));
+}
+
+// per-row transform of the unit-row metrics before the normalisation: correlation subtracts the row mean mu, hellinger
+// takes the square root (a negative entry raises the negative-input flag; its NaN never reaches a distance the host hands out)
+__device__ __forceinline__ float prep_unit_transform(int metric, float v, float mu) {
+    if (metric == 4) return v - mu;
+    if (metric == 5) return sqrtf(v);
+    return v;
 }
 
 // ---- one wave per row: pad + centre / normalise + norm ----
@@ -97,12 +111,13 @@ __global__ __launch_bounds__(256) void k_prep_rows(const float *__restrict__ x, 
     const float *src = x + row * d;
     float *dst = xp + row * dp;
     bool bad = false;  // a NaN / inf in the input: the host raises what check_array raises in the reference (pynndescent_.py:1054)
-    if (metric == 0) {
+    bool neg = false;  // hellinger: a negative entry (nnd_data_negative)
+    if (!nnd_metric_unit(metric)) {  // sqeuclidean: centred on the column mean; inner product: as given
         float s = 0.0f, r2 = 0.0f;
         for (int j = lane; j < dp; j += 64) {
             const float raw = j < d ? src[j] : 0.0f;
             bad |= !isfinite(raw);
-            float v = j < d ? raw - mean[j] : 0.0f;
+            float v = j < d ? (metric == 0 ? raw - mean[j] : raw) : 0.0f;
             dst[j] = v;
             if (xh) {
                 const uint16_t b = nnd_f32_to_h16(v, hsc);
@@ -119,17 +134,25 @@ __global__ __launch_bounds__(256) void k_prep_rows(const float *__restrict__ x, 
             if (xh) nr2[row] = make_float2(s, sqrtf(r2) * 1.000001f);
         }
     } else {
+        float mu = 0.0f;
+        if (metric == 4) {  // the row mean in float64, as the reference's correlation does: a constant row centres to exact zeros
+            double m = 0.0;
+            for (int j = lane; j < d; j += 64) m += (double)src[j];
+            mu = (float)(nnd_wave_sum_f64(m) / (double)d);
+        }
         float s = 0.0f;
         for (int j = lane; j < d; j += 64) {
-            float v = src[j];
-            bad |= !isfinite(v);
+            const float raw = src[j];
+            bad |= !isfinite(raw);
+            neg |= metric == 5 && raw < 0.0f;
+            const float v = prep_unit_transform(metric, raw, mu);
             s += v * v;
         }
         s = nnd_wave_sum_f32(s);
         float inv = s > 0.0f ? 1.0f / sqrtf(s) : 0.0f;
         float r2 = 0.0f;
         for (int j = lane; j < dp; j += 64) {
-            const float v = j < d ? src[j] * inv : 0.0f;
+            const float v = j < d ? prep_unit_transform(metric, src[j], mu) * inv : 0.0f;
             dst[j] = v;
             if (xh) {
                 const uint16_t b = nnd_f32_to_h16(v, hsc);
@@ -145,6 +168,7 @@ __global__ __launch_bounds__(256) void k_prep_rows(const float *__restrict__ x, 
         }
     }
     if (__ballot(bad) && lane == 0) atomicOr((unsigned long long *)nonfinite, 1ull);
+    if (__ballot(neg) && lane == 0) atomicOr((unsigned long long *)nonfinite, 2ull);
 }
 
 // ---- the same, 16 bytes per lane (d a multiple of 4, rows 16-byte aligned): LPR = dp/4 rounded up to a power of two
@@ -162,11 +186,24 @@ __global__ __launch_bounds__(256) void k_prep_rows_v4(const float *__restrict__ 
     const float4 *src = (const float4 *)(x + (on ? row : row_lo) * d);
     float4 *dst = (float4 *)(xp + (on ? row : row_lo) * dp);
     uint2 *dsth = xh ? (uint2 *)(xh + (on ? row : row_lo) * dp) : nullptr;
-    bool bad = false;
-    float s = 0.0f, r2 = 0.0f, inv = 1.0f;
-    if (metric != 0) {  // cosine: the norm first (the row stays in L1 / L2 for the second pass)
+    bool bad = false, neg = false;
+    float s = 0.0f, r2 = 0.0f, inv = 1.0f, mu = 0.0f;
+    const bool unit = nnd_metric_unit(metric);
+    if (unit) {  // unit rows: the norm first (the row stays in L1 / L2 for the second pass)
+        if (metric == 4) {  // correlation: the row mean first, in float64 (see k_prep_rows)
+            double m = 0.0;
+            for (int c = jl; c < ncd; c += lpr) {
+                const float4 v = on ? src[c] : make_float4(0, 0, 0, 0);
+                m += ((double)v.x + (double)v.y) + ((double)v.z + (double)v.w);
+            }
+            for (int o = lpr >> 1; o > 0; o >>= 1) m += __shfl_xor(m, o, 64);
+            mu = (float)(m / (double)d);
+        }
         for (int c = jl; c < ncd; c += lpr) {
-            const float4 v = on ? src[c] : make_float4(0, 0, 0, 0);
+            float4 v = on ? src[c] : make_float4(0, 0, 0, 0);
+            neg |= metric == 5 && (v.x < 0.0f || v.y < 0.0f || v.z < 0.0f || v.w < 0.0f);
+            v.x = prep_unit_transform(metric, v.x, mu); v.y = prep_unit_transform(metric, v.y, mu);
+            v.z = prep_unit_transform(metric, v.z, mu); v.w = prep_unit_transform(metric, v.w, mu);
             s += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
         }
         for (int o = lpr >> 1; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
@@ -181,7 +218,11 @@ __global__ __launch_bounds__(256) void k_prep_rows_v4(const float *__restrict__ 
                 const float4 m = ((const float4 *)mean)[c];
                 v.x -= m.x; v.y -= m.y; v.z -= m.z; v.w -= m.w;
             }
-        } else {
+        } else if (unit) {
+            if (c < ncd) {  // (the padding stays zero: a centred zero is not)
+                v.x = prep_unit_transform(metric, v.x, mu); v.y = prep_unit_transform(metric, v.y, mu);
+                v.z = prep_unit_transform(metric, v.z, mu); v.w = prep_unit_transform(metric, v.w, mu);
+            }
             v.x *= inv; v.y *= inv; v.z *= inv; v.w *= inv;
         }
         if (on) dst[c] = v;
@@ -199,17 +240,21 @@ __global__ __launch_bounds__(256) void k_prep_rows_v4(const float *__restrict__ 
         r2 += __shfl_xor(r2, o, 64);
     }
     if (on && jl == 0) {
-        const float nv = metric == 0 ? acc : (s > 0.0f ? 1.0f : 0.0f);
+        const float nv = unit ? (s > 0.0f ? 1.0f : 0.0f) : acc;
         nrm[row] = nv;
         if (xh) nr2[row] = make_float2(nv, sqrtf(r2) * 1.000001f);
     }
     if (__ballot(bad) && lane == 0) atomicOr((unsigned long long *)nonfinite, 1ull);
+    if (__ballot(neg) && lane == 0) atomicOr((unsigned long long *)nonfinite, 2ull);
 }
 
 // The sample rows of the column means are members r = 0 .. n_s - 1, row r * stride of the whole set.  The sharded build
 // computes the partial sums of the members among a rank's OWN rows (x_rows points at row `row0`), exchanges them, and
 // finishes the means from all of them in rank order (nnd_prep_mean_finish): the double-precision sums make the rounded
 // float means the same whatever the split.
+// the sampled column pass runs for sqeuclidean (the centre, and max |x| for the screening scale) and for inner product (max |x|
+// only: its rows are not centred and its column means are never read)
+bool nnd_prep_column_pass(int metric) { return metric == 0 || metric == 3; }
 void nnd_prep_mean_geometry(int64_t n, int64_t *n_s, int64_t *stride) {
     *n_s = n < NND_MEAN_ROWS ? n : NND_MEAN_ROWS;
     *stride = *n_s > 0 ? n / *n_s : 1;
@@ -226,7 +271,7 @@ int nnd_prep_mean_partial(nnd_ctx *ctx, const float *x_rows, int64_t row0, int64
 }
 int nnd_prep_mean_finish(nnd_ctx *ctx, const double *partial, int nblocks, int64_t n_s) {
     const int d = ctx->d, dp = ctx->dp;
-    if (ctx->p.metric == 0) {
+    if (nnd_prep_column_pass(ctx->p.metric)) {
         hipLaunchKernelGGL(k_colsum_final, dim3(dp + 1), dim3(256), 0, ctx->stream, partial, nblocks, d, dp, n_s, ctx->mean);
     } else {
         NND_HIP_CHECK(hipMemsetAsync(ctx->mean, 0, sizeof(float) * (dp + 4), ctx->stream));
@@ -273,7 +318,7 @@ int nnd_launch_prep(nnd_ctx *ctx) {
     nnd_prep_mean_geometry(n, &n_s, &stride);
     int nblocks = 0;
     double *partial = nullptr;
-    if (ctx->p.metric == 0) {
+    if (nnd_prep_column_pass(ctx->p.metric)) {
         partial = nnd_prep_partial_buffer(ctx, (size_t)nnd_prep_partial_blocks(n_s) * (ctx->d + 1));
         if (!partial) return 1;
         nblocks = nnd_prep_mean_partial(ctx, ctx->x_orig, 0, 0, n_s, stride, partial);

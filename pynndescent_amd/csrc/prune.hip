@@ -33,7 +33,7 @@ __device__ __forceinline__ float prune_pair_dist(const float *__restrict__ xp, i
     }
     s = nnd_wave_sum_f32(s);
     if (metric == 0) return nnd_clamp_dist(s);
-    return nnd_gram_to_dist(1, s, nrm[a], nrm[b]);
+    return nnd_gram_to_dist(metric, s, nrm[a], nrm[b]);
 }
 
 // u in [0,1): the coin of one pruning test (reference: tau_rand(rng_state) < prune_probability)

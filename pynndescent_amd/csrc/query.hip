@@ -2,7 +2,7 @@
 //
 // Replaces the search closure of NNDescent._init_search_function (reference pynndescent_.py:1793-1883), the tree
 // descent select_side / search_flat_tree (rp_trees.py:2662-2741) and the final deheap_sort (utils.py:189-218) for
-// dense float32 data with the euclidean / cosine metrics.  The reference walks one query at a time (optionally one
+// dense float32 data with the euclidean / cosine / dot / inner-product / correlation / hellinger metrics.  The reference walks one query at a time (optionally one
 // numba thread per query); here ONE WAVE owns one query:
 //   * result list: the k best (distance, vertex) pairs, sorted ascending, one entry per lane (k <= 64; two per lane up to k = 128) -- the
 //     reference's max-heap of size k (simple_heap_push, utils.py:352-406): a candidate enters iff it beats the worst
@@ -13,7 +13,10 @@
 //   * visited set (a bitset over all n points in the reference, utils.py:323-349): a hash set in LDS (open addressing);
 //   * distances: a quad (4 lanes) per candidate, 16 candidates of an adjacency row per step, rows gathered from HBM,
 //     the query vector in LDS; float32 in the reference's formulas (distances.py:63-91, 583-630) on the RAW rows --
-//     cosine queries are normalised first (pynndescent_.py:1808-1815), data rows are not;
+//     cosine queries are normalised first (pynndescent_.py:1808-1815), data rows are not.  The other metrics (codes 2..5)
+//     work on prepared rows, as the build does (common.h nnd_gram_to_dist): the searcher's copy of the data gets the
+//     metric's transform once (k_searcher_prep_rows), each query gets it in the kernel (dot: normalised, a zero query is
+//     skipped as for cosine; correlation: centred, then normalised; hellinger: sqrt, then normalised; inner product: raw);
 //   * stop rule: the nearest unexpanded frontier vertex is farther than
 //         bound = worst + epsilon * (worst - min_distance)                         (pynndescent_.py:1850-1853).
 // Random choices (ties in the tree descent, random start vertices when the tree leaf holds fewer than
@@ -47,7 +50,7 @@ struct nnd_searcher_s {
     float min_distance = 0.0f;
     uint32_t seed = 0;
     float *x = nullptr;        // (n, dp) rows padded to a multiple of 4 floats
-    float *xn2 = nullptr;      // (n) squared norms (cosine)
+    float *xn2 = nullptr;      // (n) squared norms (cosine; the prepared rows' for the codes 2..5)
     int32_t *indptr = nullptr, *indices = nullptr;
     float *hyper = nullptr, *offsets = nullptr;  // (n_nodes, dp), (n_nodes)
     int32_t *children = nullptr, *tree_idx = nullptr;
@@ -86,6 +89,7 @@ __device__ __forceinline__ float q_quad_dist(const float *__restrict__ x, const 
     acc += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc), 0xB1, 0xF, 0xF, false));
     acc += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc), 0x4E, 0xF, 0xF, false));
     if (metric == 0) return acc;
+    if (metric != 1) return nnd_gram_to_dist(metric, acc, qn2, xn2[v]);  // prepared rows and query (codes 2..5)
     // alternative_cosine (distances.py:600-630)
     const float nx = xn2[v];
     if (qn2 == 0.0f && nx == 0.0f) return 0.0f;
@@ -145,7 +149,7 @@ __global__ __launch_bounds__(256) void k_query(const float *__restrict__ x, cons
     float qn2 = nnd_wave_sum_f32(part);
     for (int64_t s = lane; s < vis_words; s += 64) vis[s] = BIG ? 0u : Q_EMPTY;
     bool dead = false;
-    if (metric == 1) {
+    if (metric == 1 || metric == 2) {  // cosine / dot (the reference's normalize_query, pynndescent_.py:1764-1768)
         const float nrm = sqrtf(qn2);
         if (nrm > 0.0f) {
             nnd_wave_lds_sync();
@@ -292,6 +296,27 @@ __global__ __launch_bounds__(256) void k_query(const float *__restrict__ x, cons
             ls = -children[2 * node];
             le = -children[2 * node + 1];
         }
+        if (metric == 4 || metric == 5) {  // correlation / hellinger: the tree splits the raw rows (angular), the distances the prepared ones
+            float mu = 0.0f;
+            if (metric == 4) {
+                double m = 0.0;
+                for (int j = lane; j < d; j += 64) m += (double)qs[j];
+                mu = (float)(nnd_wave_sum_f64(m) / (double)d);
+            }
+            nnd_wave_lds_sync();
+            float p2 = 0.0f;
+            for (int j = lane; j < d; j += 64) {
+                const float v = metric == 4 ? qs[j] - mu : sqrtf(qs[j]);
+                qs[j] = v;
+                p2 += v * v;
+            }
+            p2 = nnd_wave_sum_f32(p2);
+            const float inv = p2 > 0.0f ? 1.0f / sqrtf(p2) : 0.0f;
+            nnd_wave_lds_sync();
+            for (int j = lane; j < d; j += 64) qs[j] *= inv;
+            nnd_wave_lds_sync();
+            qn2 = p2 > 0.0f ? 1.0f : 0.0f;
+        }
         const int n_initial = le - ls;
         for (int c0 = 0; c0 < n_initial; c0 += Q_CHUNK) {
             const int nc = n_initial - c0 < Q_CHUNK ? n_initial - c0 : Q_CHUNK;
@@ -395,6 +420,30 @@ __global__ __launch_bounds__(256) void k_query(const float *__restrict__ x, cons
         }
 }
 
+// the searcher's copy of the rows for the codes 2..5: the build's row transform (prep.hip), one wave per row, in place --
+// dot: L2-normalised; correlation: minus the row mean (float64), then normalised; hellinger: sqrt, then normalised
+__global__ void k_searcher_prep_rows(float *__restrict__ x, int64_t n, int d, int dp, int metric) {
+    const int lane = nnd_lane();
+    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= n) return;
+    float *row = x + r * dp;
+    float mu = 0.0f;
+    if (metric == 4) {
+        double m = 0.0;
+        for (int j = lane; j < d; j += 64) m += (double)row[j];
+        mu = (float)(nnd_wave_sum_f64(m) / (double)d);
+    }
+    float s = 0.0f;
+    for (int j = lane; j < d; j += 64) {
+        const float v = metric == 4 ? row[j] - mu : (metric == 5 ? sqrtf(row[j]) : row[j]);
+        row[j] = v;
+        s += v * v;
+    }
+    s = nnd_wave_sum_f32(s);
+    const float inv = s > 0.0f ? 1.0f / sqrtf(s) : 0.0f;
+    for (int j = lane; j < d; j += 64) row[j] *= inv;
+}
+
 // squared norms of the padded rows (alternative_cosine recomputes them per call, distances.py:617-620)
 __global__ void k_row_norm2(const float *__restrict__ x, int64_t n, int dp, float *__restrict__ out) {
     const int lane = nnd_lane();
@@ -450,6 +499,8 @@ static int searcher_fill(nnd_searcher_s *s, const float *data, const int32_t *in
     S_HIP(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
     if (upload_padded(s, &s->x, data, s->n, s->d, s->dp)) return 1;
     S_HIP(hipMalloc((void **)&s->xn2, sizeof(float) * (size_t)s->n));
+    if (s->metric == NND_METRIC_ALT_DOT || s->metric == NND_METRIC_CORRELATION || s->metric == NND_METRIC_ALT_HELLINGER)
+        hipLaunchKernelGGL(k_searcher_prep_rows, dim3((unsigned)((s->n + 3) / 4)), dim3(256), 0, s->stream, s->x, s->n, s->d, s->dp, s->metric);
     hipLaunchKernelGGL(k_row_norm2, dim3((unsigned)((s->n + 3) / 4)), dim3(256), 0, s->stream, s->x, s->n, s->dp, s->xn2);
     S_HIP(hipMalloc((void **)&s->indptr, sizeof(int32_t) * (size_t)(s->n + 1)));
     S_HIP(hipMemcpy(s->indptr, indptr, sizeof(int32_t) * (size_t)(s->n + 1), hipMemcpyHostToDevice));
@@ -477,7 +528,7 @@ extern "C" int32_t nnd_searcher_create(nnd_searcher_t *out, int32_t device, int6
         return 1;
     };
     if (!out || !data || !indptr || !indices || n < 1 || dim < 1) return fail("bad arguments");
-    if (metric != NND_METRIC_SQEUCLIDEAN && metric != NND_METRIC_ALT_COSINE) return fail("unknown metric");
+    if (metric < NND_METRIC_SQEUCLIDEAN || metric > NND_METRIC_ALT_HELLINGER) return fail("unknown metric");
     if (n_nodes > 0 && (!hyperplanes || !offsets || !children || !tree_indices)) return fail("tree arrays missing");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail("no HIP device visible (this library has no CPU path)");

@@ -223,7 +223,7 @@ __global__ __launch_bounds__(256) void k_margin(const float *__restrict__ xp, co
             if (c + 4 * j < (dp >> 3)) acc = rp_dot8(q[j], p[j], acc);
     }
     const float m = rp_quad_sum(acc) * scal[1] + off;
-    const float band = rp_band(metric == 0 ? sqrtf(xn) : xn, rx, hnorm, rh);
+    const float band = rp_band(nnd_metric_unit(metric) ? xn : sqrtf(xn), rx, hnorm, rh);
     const uint8_t sd = rp_side(m, band, xp + pt * dp, h, off, dp, sub, seed, (uint32_t)g + pos_bias, depth);
     if (sub == 0) side[g] = sd;
 }
@@ -244,7 +244,7 @@ __global__ __launch_bounds__(256) void k_margin_fused(const float *__restrict__ 
     const uint4 *x8 = (const uint4 *)(xh + i * dp);
     const float2 nrv = nr[i];
     const float xn = nrv.x, rx = nrv.y;
-    const float xnorm = metric == 0 ? sqrtf(xn) : xn;
+    const float xnorm = nnd_metric_unit(metric) ? xn : sqrtf(xn);
     const int nch = dp >> 3;
     // trees in batches of 4: segment ids, then hyperplane chunks of the whole batch, are independent loads issued together
     for (int t0 = 0; t0 < n_trees; t0 += 4) {
@@ -732,7 +732,7 @@ __global__ __launch_bounds__(NTHR, NTHR == 64 ? 5 : 1) void k_finish_subtrees(co
             const int32_t id = perm[a + i];
             ids[i] = id;
             const float2 nrv = nr[id];
-            const float xnm = metric == 0 ? sqrtf(nrv.x) : nrv.x;
+            const float xnm = nnd_metric_unit(metric) ? nrv.x : sqrtf(nrv.x);
             cellA = fmaxf(cellA, nrv.y + RP_ACC * xnm);
             cellB = fmaxf(cellB, xnm + nrv.y);
         }
@@ -917,7 +917,7 @@ __global__ __launch_bounds__(NTHR, NTHR == 64 ? 5 : 1) void k_finish_subtrees(co
                 const int i = i0 + u * GQ + grp;
                 if (i >= l) continue;  // whole quad
                 const float m = rp_quad_sum(acc[u]) * inv_s2 + off;
-                const float band = BIG ? rp_band(metric == 0 ? sqrtf(xn[u]) : xn[u], rxv[u], hnorm, rhv) : hnorm * cellA + rhv * cellB + RP_EPS;
+                const float band = BIG ? rp_band(nnd_metric_unit(metric) ? xn[u] : sqrtf(xn[u]), rxv[u], hnorm, rhv) : hnorm * cellA + rhv * cellB + RP_EPS;
                 const uint8_t side = rp_side(m, band, xp + pt[u] * dp, h, off, dp, sub, seedt, (uint32_t)pt[u], dep);
                 if (sub == 0) sd[i] = side;
             }
@@ -1162,7 +1162,7 @@ __global__ __launch_bounds__(512) void k_route(const float *__restrict__ xp, con
         }
         const float2 nrv = nr[i];
         const float xn = nrv.x, rx = nrv.y;
-        const float xnorm = metric == 0 ? sqrtf(xn) : xn;
+        const float xnorm = nnd_metric_unit(metric) ? xn : sqrtf(xn);
         for (int t0 = 0; t0 < n_trees; t0 += TB) {
             int node[TB];  // >= 0: current node (the root of tree t is node t); -1: this walk is over
             int rk[TB];    // the point's slot in its cell: the atomic's return value is not touched before the walks of
@@ -1370,7 +1370,7 @@ __global__ __launch_bounds__(1024) void k_route_top(const float *__restrict__ xp
             for (int q = 0; q < NC2; q++) xq[q] = row[sub + 2 * q];
         }
         const float2 nrv = nr[i];
-        const float xnorm = metric == 0 ? sqrtf(nrv.x) : nrv.x;
+        const float xnorm = nnd_metric_unit(metric) ? nrv.x : sqrtf(nrv.x);
         const float bA = nrv.y + RP_ACC * xnorm, bB = xnorm + nrv.y;  // band = |h| bA + |h - half(h)| bB + eps (rp_band regrouped)
         for (int tl = 0; tl < tgn; tl++) {
             const int t = tg0 + tl;
@@ -1499,7 +1499,7 @@ __global__ __launch_bounds__(256) void k_bucket_scatter(const int32_t *__restric
         const int at = bucket_start[c] + base[c - t * nslots] + myr[it];
         bucket_rows[at] = (int32_t)(row_lo + r);
         const float2 nrv = nr[row_lo + r];
-        const float xnm = metric == 0 ? sqrtf(nrv.x) : nrv.x;
+        const float xnm = nnd_metric_unit(metric) ? nrv.x : sqrtf(nrv.x);
         bucket_ab[at] = (rp_bf16_up(nrv.y + RP_ACC * xnm) << 16) | rp_bf16_up(xnm + nrv.y);
     }
 }
@@ -1813,7 +1813,7 @@ struct forest_view {
 // big list (global-memory variant; its nodes join the workgroup list as they shrink) -> workgroup list -> small list
 static int launch_finishers(nnd_ctx *ctx, int32_t *perm, int32_t *other, const int32_t *big_start, const int32_t *big_len,
                             const int32_t *big_depth, int depth0, long long n_big, long long n_small = 0, rp_tree_map tm = rp_tree_map{}) {
-    const int dp = ctx->dp, angular = ctx->p.metric == NND_METRIC_ALT_COSINE;
+    const int dp = ctx->dp, angular = nnd_metric_unit(ctx->p.metric);
     int32_t *fin_start = ctx->seg_child + 2 * ctx->max_segs;  // finisher work list lives behind seg_child
     int32_t *fin_len = fin_start + ctx->max_segs;
     int32_t *fin_depth = fin_len + ctx->max_segs;
@@ -1857,7 +1857,7 @@ static int forest_levels(nnd_ctx *ctx, forest_view &v) {
     const uint32_t pos_bias = (uint32_t)((int64_t)v.tree_bias * n);
     rp_tree_map tm;
     tm.tree_bias = v.tree_bias;
-    const int angular = ctx->p.metric == NND_METRIC_ALT_COSINE;
+    const int angular = nnd_metric_unit(ctx->p.metric);
     const int hs = dp + 4;
     int32_t *scan_total = (int32_t *)(ctx->counters + CNT_SCRATCH);  // device scratch word(s)
     int splittable = (n > leaf_size && max_depth > 0) ? 1 : 0;

@@ -452,14 +452,14 @@ static int forest_by_cell(nnd_shard_s *s, const float *x_local_dev, hipEvent_t e
         section_timer sec(s);
         const int tp = t_begin(h);
         double *partial = nullptr;
-        if (h->p.metric == 0) {
+        if (nnd_prep_column_pass(h->p.metric)) {
             partial = nnd_prep_partial_buffer(h, (size_t)pblocks[G] * (d + 1));
             if (!partial) { s->set_error("%s", h->err); return 1; }
             (void)nnd_prep_mean_partial(h, x_local_dev, lo, rlo[me], rlo[me + 1], mstride, partial + (size_t)pblocks[me] * (d + 1));
         }
         t_end(h, tp, &h->stats.ms_prep, false);
         sec.end();
-        if (h->p.metric == 0) {  // all-gather of the partial sums, in place
+        if (nnd_prep_column_pass(h->p.metric)) {  // all-gather of the partial sums, in place
             size_t soff[NND_MAX_RANKS], scnt[NND_MAX_RANKS], roff[NND_MAX_RANKS], rcnt[NND_MAX_RANKS];
             for (int r = 0; r < G; r++) {
                 soff[r] = (size_t)pblocks[me] * (d + 1);

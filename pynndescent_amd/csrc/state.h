@@ -201,6 +201,7 @@ int nnd_create_impl(nnd_handle_t *out, const nnd_params *p, const int64_t *bound
 // ---- implemented in the kernel translation units; each returns 0 / sets ctx->err ----
 int nnd_launch_prep(nnd_ctx *ctx);
 // the pieces of nnd_launch_prep (prep.hip), for the sharded build: a rank preps its own rows first, the others once they arrive
+bool nnd_prep_column_pass(int metric);
 void nnd_prep_mean_geometry(int64_t n, int64_t *n_s, int64_t *stride);
 int nnd_prep_partial_blocks(int64_t members);
 double *nnd_prep_partial_buffer(nnd_ctx *ctx, size_t doubles);

@@ -9,7 +9,9 @@ if the HIP library or a gfx950 device is missing, construction raises.
 
 Also on the GPU: ``update`` (warm start, pynndescent_.py:2381-2553), ``build_search_graph`` (the pruning
 pass of ``_init_search_graph``, all diversify methods), ``prepare`` (hub search tree + reordering) and
-``query``.  Out of scope: sparse input, metrics other than euclidean / l2 / sqeuclidean / cosine, ``n_neighbors`` above 256 or
+``query``.  Metrics: euclidean / l2 / sqeuclidean / cosine / dot / inner_product / correlation / hellinger (hellinger input
+must be non-negative: a negative entry raises ``ValueError``, where the reference computes NaN distances without a word).
+Out of scope: sparse input, every other metric, ``n_neighbors`` above 256 or
 ``max_candidates`` above 128 (``query``: more than 256 results per query).  Those raise ``NotImplementedError`` naming the reference entry point to use
 instead; ``pynndescent_amd.make_index`` hands such inputs to ``pynndescent.NNDescent`` when it is importable.
 """
@@ -51,9 +53,24 @@ def correct_alternative_cosine(d):
     return 1.0 - np.power(2.0, -np.asarray(d, dtype=np.float64))
 
 
+def correct_alternative_inner_product(d):
+    """-1/d, and 0 for FLT_MAX (reference distances.py:842-853); float64 like the reference's ufunc."""
+    d = np.asarray(d, dtype=np.float64)
+    with np.errstate(divide="ignore"):
+        return np.where(d >= np.finfo(np.float32).max, 0.0, -1.0 / d)
+
+
+def correct_alternative_hellinger(d):
+    """sqrt(1 - 2^-d) (reference distances.py:1420-1426); float64 like the reference's ufunc."""
+    return np.sqrt(1.0 - np.power(2.0, -np.asarray(d, dtype=np.float64)))
+
+
 # (numpy.sqrt; large float32 arrays go through the library's threaded sqrtf -- the same bits, the fresh pages touched in parallel)
 # ("sqeuclidean": the reference applies no correction, pynndescent_.py:1271-1298; neighbor_graph still hands out a copy)
-_DISTANCE_CORRECTIONS = {"euclidean": _capi.host_sqrt, "l2": _capi.host_sqrt, "sqeuclidean": _capi.host_copy, "cosine": correct_alternative_cosine}
+# ("correlation": a true distance, no correction either, pynndescent_.py:1271-1298)
+_DISTANCE_CORRECTIONS = {"euclidean": _capi.host_sqrt, "l2": _capi.host_sqrt, "sqeuclidean": _capi.host_copy, "cosine": correct_alternative_cosine,
+                         "dot": correct_alternative_cosine, "inner_product": correct_alternative_inner_product,
+                         "correlation": _capi.host_copy, "hellinger": correct_alternative_hellinger}
 
 
 class _DeviceForestSentinel:
@@ -150,7 +167,8 @@ class NNDescent:
         if callable(metric) or metric not in _METRIC_CODES:
             if callable(metric) or metric in _KNOWN_REFERENCE_METRICS:
                 raise NotImplementedError(
-                    "pynndescent_amd accelerates the dense euclidean / l2 / sqeuclidean / cosine build only; "
+                    "pynndescent_amd accelerates the dense euclidean / l2 / sqeuclidean / cosine / dot / inner_product / "
+                    "correlation / hellinger build only; "
                     "use pynndescent.NNDescent for metric %r" % (metric,)
                 )
             raise ValueError("Metric is neither callable, " + "nor a recognised string")  # pynndescent_.py:1292
@@ -168,7 +186,14 @@ class NNDescent:
         # pynndescent_.py:1054 check_array(data, dtype=np.float32, order="C") -- minus its single-core scan for NaN / inf
         # (24 ms at 1 M x 128): the prep kernel looks at every value anyway and raises a flag; _raise_if_nonfinite then
         # lets sklearn produce the reference's own error
+        # pynndescent_.py:1041-1046: a float32 C-contiguous input is the caller's own array after check_array -- normalised
+        # into a copy; any other input has been copied by check_array already and is normalised in place
+        copy_on_normalize = getattr(data, "dtype", None) == np.float32 and bool(getattr(getattr(data, "flags", None), "c_contiguous", False))
         data = _check_array_no_scan(data)
+        if metric == "dot":  # pynndescent_.py:1101-1102
+            from sklearn.preprocessing import normalize
+
+            data = normalize(data, norm="l2", copy=copy_on_normalize)
         self._input_dtype = np.float32
         self._raw_data = data
 
@@ -245,6 +270,7 @@ class NNDescent:
         from . import sharded
 
         assert_all_finite(data)  # check_array's scan (pynndescent_.py:1054): the one-call multi-GPU build has no flag to read
+        _raise_if_negative_host(data, metric)
         if verbose:
             print(ts(), "NN descent for", str(n_iters), "iterations on", self.n_devices, "GPUs")
         idx, dst, st, info = sharded.build_multi(
@@ -269,6 +295,8 @@ class NNDescent:
         try:
             builder.set_data_host(data)
             _raise_if_nonfinite(builder, data)
+            if metric == "hellinger" and builder.data_negative():
+                raise ValueError(_NEGATIVE_HELLINGER)
             if self.tree_init:
                 builder.make_forest()
                 st = builder.stats()
@@ -393,6 +421,11 @@ class NNDescent:
         if indices.shape != distances.shape or indices.shape[0] != n:
             raise ValueError("Init graph size does not match dataset size!")
         _check_supported_sizes(indices.shape[1], self.max_candidates, None)
+        if metric == "dot":  # the data NNDescent would hold (pynndescent_.py:1101-1102)
+            from sklearn.preprocessing import normalize
+
+            data = normalize(data, norm="l2", copy=True)
+        _raise_if_negative_host(data, metric)
         self.metric, self.n_neighbors = metric, indices.shape[1]
         self.n_trees, self.n_iters = n_trees, n_iters
         self.n_trees_after_update = max(2, int(np.round(n_trees / 3)))
@@ -482,6 +515,7 @@ class NNDescent:
         query_data = np.asarray(query_data).astype(np.float32, order="C")  # pynndescent_.py:2316
         if query_data.ndim != 2 or query_data.shape[1] != self._raw_data.shape[1]:
             raise ValueError("query_data must have shape (n_queries, %d)" % self._raw_data.shape[1])
+        _raise_if_negative_host(query_data, self.metric)
         indices, dists = self._searcher.query(query_data, k, epsilon)
         found = indices >= 0
         indices = np.where(found, self._vertex_order[np.where(found, indices, 0)], -1).astype(np.int32)  # pynndescent_.py:2373
@@ -581,6 +615,7 @@ class NNDescent:
             from . import sharded
 
             assert_all_finite(raw)
+            _raise_if_negative_host(raw, self.metric)
             idx, dst, st, info = sharded.build_multi(
                 raw, self.n_devices, self.devices, self.metric, self.n_neighbors, self.n_trees, eff_leaf_size, effective_max_candidates,
                 self.n_iters, self.delta, max_rptree_depth=self.max_rptree_depth, rng_state=self.rng_state, tree_state=tree_states[0],
@@ -603,6 +638,8 @@ class NNDescent:
         )
         try:
             builder.set_data_host(raw)
+            if self.metric == "hellinger" and builder.data_negative():
+                raise ValueError(_NEGATIVE_HELLINGER)
             builder.make_forest()
             self._rp_forest = _DeviceForestSentinel(self.n_trees, builder.stats()["n_leaves"], eff_leaf_size)
             builder.reset_graph()
@@ -635,7 +672,13 @@ EMPTY_GRAPH = (np.array([[-1]], dtype=np.int32), np.array([[np.inf]], dtype=np.f
 _ND_DISTS = {"squared_euclidean": (_capi.NND_METRIC_SQEUCLIDEAN, None), "sqeuclidean": (_capi.NND_METRIC_SQEUCLIDEAN, None),
              "euclidean": (_capi.NND_METRIC_SQEUCLIDEAN, np.sqrt), "l2": (_capi.NND_METRIC_SQEUCLIDEAN, np.sqrt),
              "alternative_cosine": (_capi.NND_METRIC_ALT_COSINE, None),
-             "cosine": (_capi.NND_METRIC_ALT_COSINE, correct_alternative_cosine)}
+             "cosine": (_capi.NND_METRIC_ALT_COSINE, correct_alternative_cosine),
+             "alternative_dot": (_capi.NND_METRIC_ALT_DOT, None), "dot": (_capi.NND_METRIC_ALT_DOT, correct_alternative_cosine),
+             "alternative_inner_product": (_capi.NND_METRIC_ALT_INNER_PRODUCT, None),
+             "inner_product": (_capi.NND_METRIC_ALT_INNER_PRODUCT, correct_alternative_inner_product),
+             "correlation": (_capi.NND_METRIC_CORRELATION, None),
+             "alternative_hellinger": (_capi.NND_METRIC_ALT_HELLINGER, None),
+             "hellinger": (_capi.NND_METRIC_ALT_HELLINGER, correct_alternative_hellinger)}
 
 
 def nn_descent(data, n_neighbors, rng_state, max_candidates=50, dist="squared_euclidean", n_iters=10, delta=0.001,
@@ -643,9 +686,11 @@ def nn_descent(data, n_neighbors, rng_state, max_candidates=50, dist="squared_eu
     """The reference's ``nn_descent`` (pynndescent_.py:323-366) with the same arguments, on the GPU: the seam a caller
     uses who keeps the reference's ``make_forest`` / ``rptree_leaf_array`` and hands the leaves in.
 
-    data float32 (n, d); rng_state int64[3]; ``dist``: "squared_euclidean" / "alternative_cosine" (what NNDescent passes,
-    pynndescent_.py:1247-1260), "euclidean" / "cosine" (true distances: the same kernels, corrected on return), or the
-    reference function of one of those names; ``init_graph``: EMPTY_GRAPH, or the heap triple ``(indices (n, k),
+    data float32 (n, d); rng_state int64[3]; ``dist``: "squared_euclidean" / "alternative_cosine" / "alternative_dot" /
+    "alternative_inner_product" / "correlation" / "alternative_hellinger" (what NNDescent passes, pynndescent_.py:1247-1260),
+    "euclidean" / "cosine" / "dot" / "inner_product" / "hellinger" (true distances: the same kernels, corrected on return),
+    or the reference function of one of those names (dot: the kernels rank by the L2-normalised rows, as NNDescent's
+    normalised data gives; hand in normalised rows for the reference's ranking); ``init_graph``: EMPTY_GRAPH, or the heap triple ``(indices (n, k),
     distances (n, k), flags (n, k))`` the reference accepts (entries with index -1 are empty); ``leaf_array`` int32
     (n_leaves, max_leaf_size), -1 padded, used when ``rp_tree_init``.  ``low_memory`` is accepted and unused, as in the
     reference (pynndescent_.py:335).  Returns ``(indices int32 (n, k), distances float32 (n, k))``, rows ascending."""
@@ -664,6 +709,8 @@ def nn_descent(data, n_neighbors, rng_state, max_candidates=50, dist="squared_eu
                             device=device)
     try:
         builder.set_data_host(data)
+        if code == _capi.NND_METRIC_ALT_HELLINGER and builder.data_negative():
+            raise ValueError(_NEGATIVE_HELLINGER)
         if empty:
             if rp_tree_init:
                 if leaf_array is None:
@@ -704,6 +751,15 @@ def _raise_if_nonfinite(builder, data):
         raise ValueError("Input contains NaN or infinity.")  # (unreachable unless the two scans disagree)
 
 
+# hellinger takes sqrt(x): the reference computes NaN distances from a negative entry without a word; here it is an error
+_NEGATIVE_HELLINGER = "the hellinger metric needs non-negative input: the data holds a negative entry"
+
+
+def _raise_if_negative_host(data, metric):
+    if metric == "hellinger" and data.size and data.min() < 0:
+        raise ValueError(_NEGATIVE_HELLINGER)
+
+
 def _check_supported_sizes(n_neighbors, max_candidates, init_graph):
     """The GPU k-lists hold at most 256 entries (four per lane of a wave; rows above 64 take the LDS-merge kernels) and the
     candidate lists at most 128 (above 64: five passes of the 64-slot join over blocks of the lists); the reference has no such bounds (pynndescent_.py:976-982), so the limits are reported up
@@ -718,7 +774,8 @@ def _check_supported_sizes(n_neighbors, max_candidates, init_graph):
 
 
 def make_index(data, *args, **kwargs):
-    """``NNDescent(data, ...)`` on the GPU when the input is in scope (dense data, euclidean / l2 / sqeuclidean / cosine, k <= 256);
+    """``NNDescent(data, ...)`` on the GPU when the input is in scope (dense data, euclidean / l2 / sqeuclidean / cosine / dot /
+    inner_product / correlation / hellinger, k <= 256);
     otherwise -- and only then -- the reference ``pynndescent.NNDescent`` on the CPU when that package is importable
     (SURVEY.md section 8b), with a warning.  A missing HIP library or GPU is never papered over: that still raises."""
     device = kwargs.pop("device", 0)
