@@ -456,6 +456,19 @@ int32_t nnd_searcher_query(nnd_searcher_t s, const float *queries /* (nq, dim) *
  * nnd_searcher_set_tier(s, 1) sends every query there (tests), 0 = automatic. */
 int64_t nnd_searcher_last_spilled(nnd_searcher_t s);
 int32_t nnd_searcher_set_tier(nnd_searcher_t s, int32_t tier);
+/* quantization="uint8" (reference prepare() / query(), pynndescent_.py:2191-2225, 2309-2364; metrics sqeuclidean, alt
+ * cosine, alt dot).  nnd_searcher_quantize_u8: codes = np.searchsorted(values, rows).astype(np.uint8) on the device (a value
+ * above the last entry gets n_values; 256 wraps to 0), values ascending, 1 <= n_values <= 256.  rows: (n, dim) host rows in
+ * the searcher's order, or NULL to quantize the searcher's own copy (dot: that copy is normalised again on the device, so
+ * hand in the rows whose codes are wanted).  codes_out (n, dim) may be NULL.  nnd_searcher_set_codes_u8: the same state from
+ * codes computed before (an unpickled index).  nnd_searcher_query_proxy: the walk on the codes with the proxy distances keeps
+ * search_k results (1 <= k <= search_k <= 256), then reranks them by the exact distance of the raw query to the float rows
+ * and returns the k best, (nq, k), ascending, as nnd_searcher_query. */
+int32_t nnd_searcher_quantize_u8(nnd_searcher_t s, const float *rows /* may be NULL */, const float *values, int32_t n_values,
+                                 uint8_t *codes_out /* may be NULL */);
+int32_t nnd_searcher_set_codes_u8(nnd_searcher_t s, const float *values, int32_t n_values, const uint8_t *codes /* (n, dim) */);
+int32_t nnd_searcher_query_proxy(nnd_searcher_t s, const float *queries /* (nq, dim) */, int64_t nq, int32_t k, int32_t search_k,
+                                 float epsilon, int32_t *out_idx /* (nq, k) */, float *out_dist /* (nq, k) */);
 int32_t nnd_searcher_destroy(nnd_searcher_t s);
 const char *nnd_searcher_last_error(nnd_searcher_t s /* NULL: the error of a failed create */);
 

@@ -247,6 +247,9 @@ _SIGNATURES = [
     ("nnd_searcher_query", C.c_int32, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
     ("nnd_searcher_last_spilled", C.c_int64, [_H]),
     ("nnd_searcher_set_tier", C.c_int32, [_H, C.c_int32]),
+    ("nnd_searcher_quantize_u8", C.c_int32, [_H, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    ("nnd_searcher_set_codes_u8", C.c_int32, [_H, C.c_void_p, C.c_int32, C.c_void_p]),
+    ("nnd_searcher_query_proxy", C.c_int32, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
     ("nnd_searcher_destroy", C.c_int32, [_H]),
     ("nnd_searcher_last_error", C.c_char_p, [_H]),
 ]
@@ -540,6 +543,7 @@ class Searcher:
             hyper = offs = children = tidx = None
             n_nodes = 0
         rng = np.ascontiguousarray(search_rng_state, np.int64)
+        self.has_codes = False  # quantize_u8 / set_codes_u8 ran
         self._h = _H()
         rc = self.lib.nnd_searcher_create(C.byref(self._h), int(device), self.n, self.dim, int(metric), _ptr(data), _ptr(indptr),
                                           _ptr(indices), int(indices.shape[0]), _ptr(hyper), _ptr(offs), _ptr(children), _ptr(tidx),
@@ -553,6 +557,40 @@ class Searcher:
         idx = np.empty((q.shape[0], k), np.int32)
         dist = np.empty((q.shape[0], k), np.float32)
         if self.lib.nnd_searcher_query(self._h, _ptr(q), q.shape[0], int(k), float(epsilon), _ptr(idx), _ptr(dist)) != 0:
+            raise NNDError(self.lib.nnd_searcher_last_error(self._h).decode())
+        return idx, dist
+
+    def quantize_u8(self, values, rows=None, fetch=True):
+        """Device codes of the rows (``np.searchsorted(values, rows).astype(np.uint8)``) for ``query_proxy``; ``rows``
+        (n, dim) in the searcher's order, or None for the searcher's own copy.  Returns the (n, dim) uint8 codes, or None
+        when ``fetch`` is false."""
+        values = np.ascontiguousarray(values, np.float32)
+        if rows is not None:
+            rows = np.ascontiguousarray(rows, np.float32)
+            assert rows.shape == (self.n, self.dim)
+        codes = np.empty((self.n, self.dim), np.uint8) if fetch else None
+        if self.lib.nnd_searcher_quantize_u8(self._h, _ptr(rows), _ptr(values), int(values.shape[0]), _ptr(codes)) != 0:
+            raise NNDError(self.lib.nnd_searcher_last_error(self._h).decode())
+        self.has_codes = True
+        return codes
+
+    def set_codes_u8(self, values, codes):
+        """The state of ``quantize_u8`` from codes computed before."""
+        values = np.ascontiguousarray(values, np.float32)
+        codes = np.ascontiguousarray(codes, np.uint8)
+        assert codes.shape == (self.n, self.dim)
+        if self.lib.nnd_searcher_set_codes_u8(self._h, _ptr(values), int(values.shape[0]), _ptr(codes)) != 0:
+            raise NNDError(self.lib.nnd_searcher_last_error(self._h).decode())
+        self.has_codes = True
+
+    def query_proxy(self, queries, k, search_k, epsilon):
+        """The walk on the codes keeps ``search_k`` results, the exact rerank returns the best ``k`` (alt space)."""
+        q = np.ascontiguousarray(queries, np.float32)
+        assert q.ndim == 2 and q.shape[1] == self.dim
+        idx = np.empty((q.shape[0], k), np.int32)
+        dist = np.empty((q.shape[0], k), np.float32)
+        if self.lib.nnd_searcher_query_proxy(self._h, _ptr(q), q.shape[0], int(k), int(search_k), float(epsilon), _ptr(idx),
+                                             _ptr(dist)) != 0:
             raise NNDError(self.lib.nnd_searcher_last_error(self._h).decode())
         return idx, dist
 

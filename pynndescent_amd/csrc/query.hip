@@ -19,6 +19,10 @@
 //     skipped as for cosine; correlation: centred, then normalised; hellinger: sqrt, then normalised; inner product: raw);
 //   * stop rule: the nearest unexpanded frontier vertex is farther than
 //         bound = worst + epsilon * (worst - min_distance)                         (pynndescent_.py:1850-1853).
+//   * quantization="uint8" (Q8 instances, euclidean / cosine / dot): the walk runs on the searcher's uint8 code rows with
+//     the reference's proxy distances (q_quad_proxy) and keeps search_k = proxy_beam_size * k results; its epilogue is
+//     the reference's rerank (pynndescent_.py:776-789): exact distances of the RAW query to the float rows of those
+//     candidates, pushed in ascending proxy order into a list of k (DESIGN.md "Quantized search").
 // Random choices (ties in the tree descent, random start vertices when the tree leaf holds fewer than
 // min(k, n_neighbors) points) come from the counter hash, keyed by the query's number.
 #include <stdarg.h>
@@ -51,6 +55,11 @@ struct nnd_searcher_s {
     uint32_t seed = 0;
     float *x = nullptr;        // (n, dp) rows padded to a multiple of 4 floats
     float *xn2 = nullptr;      // (n) squared norms (cosine; the prepared rows' for the codes 2..5)
+    uint8_t *codes = nullptr;  // quantization="uint8": (n, dcs) codes, rows padded to 16 bytes with code 0
+    float *cn2 = nullptr;      // (n) sum of LUT[c]^2 over a code row (cosine / dot)
+    float *lut = nullptr;      // 512: the walk's codebook (256, padded with the last value), then the search table (+inf padded)
+    int dcs = 0;               // code row stride: d rounded up to 16
+    float tab_host[512];       // the host side of `lut` (the source of its stream-ordered upload)
     int32_t *indptr = nullptr, *indices = nullptr;
     float *hyper = nullptr, *offsets = nullptr;  // (n_nodes, dp), (n_nodes)
     int32_t *children = nullptr, *tree_idx = nullptr;
@@ -98,8 +107,68 @@ __device__ __forceinline__ float q_quad_dist(const float *__restrict__ x, const 
     return r > 1.0f ? log2f(r) : 0.0f;
 }
 
+// quad-cooperative proxy distance between the float query (LDS, |q|^2 = qn2) and the uint8 code row `v`, each code looked
+// up in the codebook `lut` (LDS): quantized_uint8_sq_euclidean / _alternative_cosine / _alternative_dot (distances.py:1869,
+// 1905, 1948).  A lane takes 16 codes per 16-byte load; the query's padding columns are 0 (no term under cosine / dot), the
+// euclidean tail chunk of a row whose d is no multiple of 16 masks them.
+__device__ __forceinline__ float q_quad_proxy(const uint8_t *__restrict__ codes, const float *__restrict__ cn2, int dcs, int d,
+                                              int metric, const float *lut, const float *qs, float qn2, int64_t v, int sub) {
+    const uint4 *row = (const uint4 *)(codes + v * dcs);
+    float acc = 0.0f;
+    auto chunk = [&](int c, int lim) {  // codes 16 c .. 16 c + 15, the first `lim` of them live
+        const uint4 w = row[c];
+        const uint32_t ws[4] = {w.x, w.y, w.z, w.w};
+        const float4 *q4 = (const float4 *)(qs + 16 * c);
+#pragma unroll
+        for (int h = 0; h < 4; h++) {
+            const float4 q = q4[h];
+            const float qv[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+            for (int b = 0; b < 4; b++) {
+                const float y = lut[(ws[h] >> (8 * b)) & 0xFFu];
+                if (metric == 0) {
+                    const float df = qv[b] - y;
+                    if (4 * h + b < lim) acc += df * df;
+                } else {
+                    acc += qv[b] * y;
+                }
+            }
+        }
+    };
+    const int full = d >> 4;
+    for (int c = sub; c < full; c += 4) chunk(c, 16);
+    if ((d & 15) && sub == (full & 3)) chunk(full, d & 15);
+    acc += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc), 0xB1, 0xF, 0xF, false));
+    acc += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc), 0x4E, 0xF, 0xF, false));
+    if (metric == 0) return acc;
+    const float ny = cn2[v];
+    if (metric == 2) return acc > 0.0f ? -log2f(acc / sqrtf(ny)) : NND_FLT_MAX;  // distances.py:1948-1966
+    if (qn2 == 0.0f && ny == 0.0f) return 0.0f;                                  // distances.py:1905-1930
+    if (qn2 == 0.0f || ny == 0.0f || acc <= 0.0f) return NND_FLT_MAX;
+    return -log2f((acc / sqrtf(qn2 * ny) + 1.0f) / 2.0f);
+}
+
+// the rerank's exact distance (the reference's _distance_func on the raw query and the float row): q_quad_dist, except
+// that dot is alternative_dot on the un-normalised query (distances.py:680-701), so it is not clamped at 0
+__device__ __forceinline__ float q_rerank_dist(const float *__restrict__ x, const float *__restrict__ xn2, int dp, int metric,
+                                               const float *qs, float qn2, int64_t v, int sub) {
+    if (metric != 2) return q_quad_dist(x, xn2, dp, metric, qs, qn2, v, sub);
+    const float4 *row = (const float4 *)(x + v * dp);
+    const float4 *q4 = (const float4 *)qs;
+    float acc = 0.0f;
+    for (int c = sub; c < (dp >> 2); c += 4) {
+        const float4 a = row[c], b = q4[c];
+        acc += a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w;
+    }
+    acc += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc), 0xB1, 0xF, 0xF, false));
+    acc += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc), 0x4E, 0xF, 0xF, false));
+    return acc > 0.0f ? -log2f(acc) : NND_FLT_MAX;
+}
+
 // KU: result entries per lane -- entry u of lane j is position 64 u + j of the list (k <= 64 KU: 1, 2 or 4)
-template <bool BIG, int KU>
+// Q8: quantization="uint8" -- the walk on the code rows (k = search_k), the rerank to k_out in the epilogue; the codebook
+// (256 floats) sits in front of the waves' LDS.  The float instances (Q8 = false) never touch the last five arguments.
+template <bool BIG, int KU, bool Q8 = false>
 __global__ __launch_bounds__(256) void k_query(const float *__restrict__ x, const float *__restrict__ xn2, int dp, int d, int metric,
                                                int64_t n, const int32_t *__restrict__ indptr, const int32_t *__restrict__ indices,
                                                const float *__restrict__ hyper, const float *__restrict__ offsets,
@@ -108,16 +177,23 @@ __global__ __launch_bounds__(256) void k_query(const float *__restrict__ x, cons
                                                float min_distance, int n_neighbors, uint32_t seed, int32_t *__restrict__ out_idx,
                                                float *__restrict__ out_dist, uint8_t *__restrict__ overflow /* (nq) LDS tier: set when the query needs the big tier */,
                                                const int32_t *__restrict__ qlist /* BIG: the queries of this batch */,
-                                               int n_list, unsigned char *__restrict__ scratch, size_t scratch_stride) {
+                                               int n_list, unsigned char *__restrict__ scratch, size_t scratch_stride,
+                                               const uint8_t *__restrict__ codes, int dcs, const float *__restrict__ lut,
+                                               const float *__restrict__ cn2, int k_out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char qsm[];
     const int lane = nnd_lane(), w = threadIdx.x >> 6;
+    if constexpr (Q8) {  // the codebook, once per workgroup (256 threads: one entry each)
+        ((float *)qsm)[threadIdx.x] = lut[threadIdx.x];
+        __syncthreads();
+    }
     const int64_t slot = (int64_t)blockIdx.x * 4 + w;
     if (BIG ? slot >= n_list : slot >= nq) return;  // whole wave; no workgroup barrier below
     const int64_t qi = BIG ? (int64_t)qlist[slot] : slot;
     constexpr int FCAP = BIG ? Q_BIG_FRONTIER : Q_FRONTIER;
-    const size_t per_wave = BIG ? (size_t)dp * 4 + Q_CHUNK * 8 : (size_t)dp * 4 + Q_FRONTIER * 8 + Q_VISITED * 4 + Q_CHUNK * 8;
-    unsigned char *mine = qsm + (size_t)w * ((per_wave + 15) & ~(size_t)15);
-    float *qs = (float *)mine;                       // dp
+    const int qp = Q8 ? dcs : dp;  // query floats in LDS (Q8: as many as a code row has columns)
+    const size_t per_wave = BIG ? (size_t)qp * 4 + Q_CHUNK * 8 : (size_t)qp * 4 + Q_FRONTIER * 8 + Q_VISITED * 4 + Q_CHUNK * 8;
+    unsigned char *mine = qsm + (Q8 ? 1024 : 0) + (size_t)w * ((per_wave + 15) & ~(size_t)15);
+    float *qs = (float *)mine;                       // qp
     float *fd;                                       // FCAP distances
     int32_t *fv;                                     // FCAP vertices
     uint32_t *vis;                                   // LDS tier: Q_VISITED hash slots; big tier: (n + 31) / 32 bit words
@@ -127,9 +203,9 @@ __global__ __launch_bounds__(256) void k_query(const float *__restrict__ x, cons
         fd = (float *)gs;
         fv = (int32_t *)(fd + FCAP);
         vis = (uint32_t *)(fv + FCAP);
-        cl = (int32_t *)(qs + dp);
+        cl = (int32_t *)(qs + qp);
     } else {
-        fd = qs + dp;
+        fd = qs + qp;
         fv = (int32_t *)(fd + FCAP);
         vis = (uint32_t *)(fv + FCAP);
         cl = (int32_t *)(vis + Q_VISITED);
@@ -141,7 +217,7 @@ __global__ __launch_bounds__(256) void k_query(const float *__restrict__ x, cons
 
     // ---- the query: cosine queries are normalised (pynndescent_.py:1808-1815); a zero cosine query returns nothing ----
     float part = 0.0f;
-    for (int j = lane; j < dp; j += 64) {
+    for (int j = lane; j < qp; j += 64) {
         const float v = j < d ? queries[qi * d + j] : 0.0f;
         qs[j] = v;
         part += v * v;
@@ -264,7 +340,9 @@ __global__ __launch_bounds__(256) void k_query(const float *__restrict__ x, cons
         for (int c0 = 0; c0 < nc; c0 += 16) {
             const int c = c0 + grp;
             const int64_t v = cl[c < nc ? c : 0];
-            const float dv = q_quad_dist(x, xn2, dp, metric, qs, qn2, v, sub);
+            float dv;
+            if constexpr (Q8) dv = q_quad_proxy(codes, cn2, dcs, d, metric, (const float *)qsm, qs, qn2, v, sub);
+            else dv = q_quad_dist(x, xn2, dp, metric, qs, qn2, v, sub);
             if (sub == 0 && c < nc) cd[c] = dv;
         }
         nnd_wave_lds_sync();
@@ -411,6 +489,40 @@ __global__ __launch_bounds__(256) void k_query(const float *__restrict__ x, cons
             }
         }
     }
+    if constexpr (Q8) {  // rerank (pynndescent_.py:776-789, 2364): the walk's search_k results -> the k_out best by exact distance
+        const int ks = k;
+        k = k_out;  // from here on the result list (worst(), result_push) and the output hold k_out entries
+        if (!spilled && !dead) {
+            nnd_wave_lds_sync();
+#pragma unroll
+            for (int u = 0; u < KU; u++)
+                if (64 * u + lane < ks) fv[64 * u + lane] = rv[u];  // candidates in ascending proxy order (the frontier is spent)
+            float p = 0.0f;  // the RAW query: the rerank takes query_data, not the normalised query
+            for (int j = lane; j < dp; j += 64) {
+                const float v = j < d ? queries[qi * d + j] : 0.0f;
+                qs[j] = v;
+                p += v * v;
+            }
+            qn2 = nnd_wave_sum_f32(p);
+            nnd_wave_lds_sync();
+            for (int c0 = 0; c0 < ks; c0 += 16) {
+                const int c = c0 + grp;
+                const int32_t vc = fv[c < ks ? c : 0];
+                const float dv = q_rerank_dist(x, xn2, dp, metric, qs, qn2, vc < 0 ? 0 : vc, sub);
+                if (sub == 0 && c < ks) fd[c] = dv;
+            }
+            nnd_wave_lds_sync();
+#pragma unroll
+            for (int u = 0; u < KU; u++) {
+                rd[u] = INFINITY;
+                rv[u] = -1;
+            }
+            for (int j = 0; j < ks; j++) {  // simple_heap_push in the walk's order; idx < 0 is skipped (pynndescent_.py:783-784)
+                const int32_t vc = fv[j];
+                if (vc >= 0) result_push(fd[j], vc);
+            }
+        }
+    }
     if (!BIG && lane == 0) overflow[qi] = spilled ? 1 : 0;  // the host re-runs flagged queries on the big tier
 #pragma unroll
     for (int u = 0; u < KU; u++)
@@ -458,6 +570,45 @@ __global__ void k_row_norm2(const float *__restrict__ x, int64_t n, int dp, floa
     if (lane == 0) out[r] = s;
 }
 
+// uint8 codes of the searcher's rows (pynndescent_.py:2207-2209: np.searchsorted(values, raw).astype(np.uint8)): one wave
+// per row, one element per lane.  The search is a branchless searchsorted-left over the 256-entry table `tab` (the codebook,
+// +inf past its n_values entries): a value above the last entry gets n_values, and 256 wraps to code 0 through the uint8
+// cast, bit for bit as the reference.  Code rows have stride dcs, padding bytes 0.  cn2 (cosine / dot; may be null): the
+// row's sum of lut[c]^2 with the walk's table.  x == nullptr: the codes are already in place, only cn2 is computed.
+__global__ __launch_bounds__(256) void k_quantize_u8(const float *__restrict__ x, int64_t xstride, int64_t n, int d, int dcs,
+                                                     const float *__restrict__ lut, const float *__restrict__ tab,
+                                                     uint8_t *__restrict__ codes, float *__restrict__ cn2) {
+    __shared__ float st[256], lt[256];
+    st[threadIdx.x] = tab[threadIdx.x];
+    lt[threadIdx.x] = lut[threadIdx.x];
+    __syncthreads();
+    const int lane = nnd_lane();
+    for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < n; r += (int64_t)gridDim.x * 4) {  // wave-uniform
+        float s = 0.0f;
+        for (int j = lane; j < dcs; j += 64) {
+            uint32_t c = 0;
+            if (x) {
+                if (j < d) {
+                    const float v = x[r * xstride + j];
+                    int lo = 0;
+#pragma unroll
+                    for (int h = 128; h > 0; h >>= 1) lo += st[lo + h - 1] < v ? h : 0;
+                    lo += st[lo] < v ? 1 : 0;  // 0 .. 256
+                    c = (uint32_t)lo & 0xFFu;
+                }
+                codes[r * dcs + j] = (uint8_t)c;
+            } else {
+                c = codes[r * dcs + j];
+            }
+            if (j < d) s += lt[c] * lt[c];
+        }
+        if (cn2) {
+            s = nnd_wave_sum_f32(s);
+            if (lane == 0) cn2[r] = s;
+        }
+    }
+}
+
 #define S_HIP(expr)                                                                                 \
     do {                                                                                            \
         hipError_t _e = (expr);                                                                     \
@@ -485,7 +636,7 @@ extern "C" int32_t nnd_searcher_destroy(nnd_searcher_t s) {
     if (!s) return 0;
     (void)hipSetDevice(s->device);
     if (s->stream) (void)hipStreamSynchronize(s->stream);
-    void *ptrs[] = {s->x, s->xn2, s->indptr, s->indices, s->hyper, s->offsets, s->children, s->tree_idx};
+    void *ptrs[] = {s->x, s->xn2, s->codes, s->cn2, s->lut, s->indptr, s->indices, s->hyper, s->offsets, s->children, s->tree_idx};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (s->stream) (void)hipStreamDestroy(s->stream);
@@ -564,13 +715,15 @@ extern "C" int32_t nnd_searcher_set_tier(nnd_searcher_t s, int32_t tier) {
     return 0;
 }
 
-extern "C" int32_t nnd_searcher_query(nnd_searcher_t s, const float *queries, int64_t nq, int32_t k, float epsilon, int32_t *out_idx,
-                                      float *out_dist) {
-    if (!s) { snprintf(g_serr, sizeof(g_serr), "nnd_searcher_query: null searcher"); return 1; }
-    if (k < 1 || k > 256) { s->set_error("nnd_searcher_query: k must be in 1..256 (got %d)", k); return 1; }
+// both query entry points: the walk keeps k results (the float rows) or k = search_k results and reranks them to k_out
+// (q8: the code rows); out_idx / out_dist are (nq, k_out)
+static int searcher_run(nnd_searcher_s *s, const float *queries, int64_t nq, int32_t k, int32_t k_out, float epsilon, bool q8,
+                        int32_t *out_idx, float *out_dist) {
     // (k > 64, round 5: the result list as two or four entries per lane; the reference takes any k, pynndescent_.py:2275-2379)
-    auto kq_lds = k > 128 ? k_query<false, 4> : (k > 64 ? k_query<false, 2> : k_query<false, 1>);
-    auto kq_big = k > 128 ? k_query<true, 4> : (k > 64 ? k_query<true, 2> : k_query<true, 1>);
+    auto kq_lds = q8 ? (k > 128 ? k_query<false, 4, true> : (k > 64 ? k_query<false, 2, true> : k_query<false, 1, true>))
+                     : (k > 128 ? k_query<false, 4> : (k > 64 ? k_query<false, 2> : k_query<false, 1>));
+    auto kq_big = q8 ? (k > 128 ? k_query<true, 4, true> : (k > 64 ? k_query<true, 2, true> : k_query<true, 1, true>))
+                     : (k > 128 ? k_query<true, 4> : (k > 64 ? k_query<true, 2> : k_query<true, 1>));
     if (nq <= 0) return 0;
     if (nq >= (int64_t)0x7FFFFFF0) { s->set_error("nnd_searcher_query: too many queries in one call"); return 1; }
     S_HIP(hipSetDevice(s->device));
@@ -579,14 +732,16 @@ extern "C" int32_t nnd_searcher_query(nnd_searcher_t s, const float *queries, in
     uint8_t *dov = nullptr;
     unsigned char *scratch = nullptr;
     int rc = 0;
-    const size_t per_wave = ((size_t)s->dp * 4 + Q_FRONTIER * 8 + Q_VISITED * 4 + Q_CHUNK * 8 + 15) & ~(size_t)15;
-    const size_t smem = 4 * per_wave;
-    const size_t per_wave_big = ((size_t)s->dp * 4 + Q_CHUNK * 8 + 15) & ~(size_t)15;
+    const size_t qp = q8 ? (size_t)s->dcs : (size_t)s->dp;  // query floats per wave in LDS (k_query's qp)
+    const size_t lut_bytes = q8 ? 1024 : 0;                  // the codebook in front of the waves
+    const size_t per_wave = (qp * 4 + Q_FRONTIER * 8 + Q_VISITED * 4 + Q_CHUNK * 8 + 15) & ~(size_t)15;
+    const size_t smem = 4 * per_wave + lut_bytes;
+    const size_t per_wave_big = (qp * 4 + Q_CHUNK * 8 + 15) & ~(size_t)15;
     s->last_spilled = 0;
     std::vector<uint8_t> hov((size_t)nq, 1);
     do {
-        if (hipMalloc((void **)&dq, sizeof(float) * (size_t)nq * s->d) != hipSuccess || hipMalloc((void **)&di, sizeof(int32_t) * (size_t)nq * k) != hipSuccess ||
-            hipMalloc((void **)&dd, sizeof(float) * (size_t)nq * k) != hipSuccess || hipMalloc((void **)&dov, (size_t)nq) != hipSuccess) { s->set_error("nnd_searcher_query: out of device memory"); rc = 1; break; }
+        if (hipMalloc((void **)&dq, sizeof(float) * (size_t)nq * s->d) != hipSuccess || hipMalloc((void **)&di, sizeof(int32_t) * (size_t)nq * k_out) != hipSuccess ||
+            hipMalloc((void **)&dd, sizeof(float) * (size_t)nq * k_out) != hipSuccess || hipMalloc((void **)&dov, (size_t)nq) != hipSuccess) { s->set_error("nnd_searcher_query: out of device memory"); rc = 1; break; }
         if (hipMemcpyAsync(dq, queries, sizeof(float) * (size_t)nq * s->d, hipMemcpyHostToDevice, s->stream) != hipSuccess) { s->set_error("H2D of the queries failed"); rc = 1; break; }
         if (!s->force_big) {
             if (smem > 64 * 1024 && hipFuncSetAttribute((const void *)kq_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) {
@@ -594,7 +749,8 @@ extern "C" int32_t nnd_searcher_query(nnd_searcher_t s, const float *queries, in
             }
             hipLaunchKernelGGL(kq_lds, dim3((unsigned)((nq + 3) / 4)), dim3(256), smem, s->stream, s->x, s->xn2, s->dp, s->d, s->metric, s->n,
                                s->indptr, s->indices, s->hyper, s->offsets, s->children, s->tree_idx, s->n_nodes, dq, nq, k, epsilon,
-                               s->min_distance, s->n_neighbors, s->seed, di, dd, dov, (const int32_t *)nullptr, 0, (unsigned char *)nullptr, (size_t)0);
+                               s->min_distance, s->n_neighbors, s->seed, di, dd, dov, (const int32_t *)nullptr, 0, (unsigned char *)nullptr, (size_t)0,
+                               (const uint8_t *)s->codes, s->dcs, (const float *)s->lut, (const float *)s->cn2, k_out);
             if (hipGetLastError() != hipSuccess) { s->set_error("k_query launch failed"); rc = 1; break; }
             if (hipMemcpyAsync(hov.data(), dov, (size_t)nq, hipMemcpyDeviceToHost, s->stream) != hipSuccess || hipStreamSynchronize(s->stream) != hipSuccess) {
                 s->set_error("nnd_searcher_query: kernel or D2H failed: %s", hipGetErrorString(hipGetLastError())); rc = 1; break;
@@ -614,15 +770,16 @@ extern "C" int32_t nnd_searcher_query(nnd_searcher_t s, const float *queries, in
             if (hipMemcpyAsync(dlist, again.data(), sizeof(int32_t) * again.size(), hipMemcpyHostToDevice, s->stream) != hipSuccess) { s->set_error("H2D of the query list failed"); rc = 1; break; }
             for (size_t b0 = 0; b0 < again.size() && !rc; b0 += batch) {
                 const int nb = (int)(again.size() - b0 < batch ? again.size() - b0 : batch);
-                hipLaunchKernelGGL(kq_big, dim3((unsigned)((nb + 3) / 4)), dim3(256), 4 * per_wave_big, s->stream, s->x, s->xn2, s->dp, s->d, s->metric,
-                                   s->n, s->indptr, s->indices, s->hyper, s->offsets, s->children, s->tree_idx, s->n_nodes, dq, nq, k, epsilon,
-                                   s->min_distance, s->n_neighbors, s->seed, di, dd, (uint8_t *)nullptr, (const int32_t *)(dlist + b0), nb, scratch, stride);
+                hipLaunchKernelGGL(kq_big, dim3((unsigned)((nb + 3) / 4)), dim3(256), 4 * per_wave_big + lut_bytes, s->stream, s->x, s->xn2, s->dp, s->d,
+                                   s->metric, s->n, s->indptr, s->indices, s->hyper, s->offsets, s->children, s->tree_idx, s->n_nodes, dq, nq, k, epsilon,
+                                   s->min_distance, s->n_neighbors, s->seed, di, dd, (uint8_t *)nullptr, (const int32_t *)(dlist + b0), nb, scratch, stride,
+                                   (const uint8_t *)s->codes, s->dcs, (const float *)s->lut, (const float *)s->cn2, k_out);
                 if (hipGetLastError() != hipSuccess) { s->set_error("k_query (global-memory tier) launch failed"); rc = 1; }
             }
             if (rc) break;
         }
-        if (hipMemcpyAsync(out_idx, di, sizeof(int32_t) * (size_t)nq * k, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
-            hipMemcpyAsync(out_dist, dd, sizeof(float) * (size_t)nq * k, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
+        if (hipMemcpyAsync(out_idx, di, sizeof(int32_t) * (size_t)nq * k_out, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
+            hipMemcpyAsync(out_dist, dd, sizeof(float) * (size_t)nq * k_out, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
             hipStreamSynchronize(s->stream) != hipSuccess) { s->set_error("nnd_searcher_query: kernel or D2H failed: %s", hipGetErrorString(hipGetLastError())); rc = 1; break; }
     } while (0);
     if (dq) (void)hipFree(dq);
@@ -632,4 +789,93 @@ extern "C" int32_t nnd_searcher_query(nnd_searcher_t s, const float *queries, in
     if (dlist) (void)hipFree(dlist);
     if (scratch) (void)hipFree(scratch);
     return rc;
+}
+
+extern "C" int32_t nnd_searcher_query(nnd_searcher_t s, const float *queries, int64_t nq, int32_t k, float epsilon, int32_t *out_idx,
+                                      float *out_dist) {
+    if (!s) { snprintf(g_serr, sizeof(g_serr), "nnd_searcher_query: null searcher"); return 1; }
+    if (k < 1 || k > 256) { s->set_error("nnd_searcher_query: k must be in 1..256 (got %d)", k); return 1; }
+    return searcher_run(s, queries, nq, k, k, epsilon, false, out_idx, out_dist);
+}
+
+// ---- quantization="uint8" (pynndescent_.py:2191-2225, 2309-2364) ----
+// the two 256-entry tables: the walk's codebook (entries past n_values = the last value; the reference reads past its
+// array there, DESIGN.md "Quantized search") and the search table (+inf past n_values)
+static int quant_tables(nnd_searcher_s *s, const char *who, const float *values, int32_t n_values) {
+    if (s->metric != NND_METRIC_SQEUCLIDEAN && s->metric != NND_METRIC_ALT_COSINE && s->metric != NND_METRIC_ALT_DOT) {
+        s->set_error("%s: uint8 quantization supports the sqeuclidean, alternative cosine and alternative dot metrics (metric %d)", who, s->metric);
+        return 1;
+    }
+    if (!values || n_values < 1 || n_values > 256) { s->set_error("%s: the codebook must have 1..256 values (got %d)", who, n_values); return 1; }
+    S_HIP(hipSetDevice(s->device));
+    S_HIP(hipStreamSynchronize(s->stream));  // no kernel or copy of an earlier call still uses the tables
+    float *tab = s->tab_host;
+    for (int i = 0; i < 256; i++) {
+        tab[i] = values[i < n_values ? i : n_values - 1];
+        tab[256 + i] = i < n_values ? values[i] : INFINITY;
+    }
+    s->dcs = (s->d + 15) & ~15;
+    if (!s->lut) S_HIP(hipMalloc((void **)&s->lut, sizeof(float) * 512));
+    if (!s->codes) S_HIP(hipMalloc((void **)&s->codes, (size_t)s->n * s->dcs));
+    if (!s->cn2 && s->metric != NND_METRIC_SQEUCLIDEAN) S_HIP(hipMalloc((void **)&s->cn2, sizeof(float) * (size_t)s->n));
+    // queued on the searcher's stream, so the kernels that read the tables are ordered after it (the stream is
+    // non-blocking: it does not wait for copies on the null stream); tab_host outlives the copy (next call syncs first)
+    S_HIP(hipMemcpyAsync(s->lut, tab, sizeof(float) * 512, hipMemcpyHostToDevice, s->stream));
+    return 0;
+}
+
+static int quant_launch(nnd_searcher_s *s, const float *x, int64_t xstride) {
+    const int64_t blocks = (s->n + 3) / 4 < 4096 ? (s->n + 3) / 4 : 4096;
+    hipLaunchKernelGGL(k_quantize_u8, dim3((unsigned)blocks), dim3(256), 0, s->stream, x, xstride, s->n, s->d, s->dcs, (const float *)s->lut,
+                       (const float *)(s->lut + 256), s->codes, s->cn2);
+    S_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int32_t nnd_searcher_quantize_u8(nnd_searcher_t s, const float *rows, const float *values, int32_t n_values, uint8_t *codes_out) {
+    if (!s) { snprintf(g_serr, sizeof(g_serr), "nnd_searcher_quantize_u8: null searcher"); return 1; }
+    if (quant_tables(s, "nnd_searcher_quantize_u8", values, n_values)) return 1;
+    float *drows = nullptr;
+    if (rows) {
+        S_HIP(hipMalloc((void **)&drows, sizeof(float) * (size_t)s->n * s->d));
+        if (hipMemcpyAsync(drows, rows, sizeof(float) * (size_t)s->n * s->d, hipMemcpyHostToDevice, s->stream) != hipSuccess) {
+            (void)hipFree(drows);
+            s->set_error("nnd_searcher_quantize_u8: H2D of the rows failed");
+            return 1;
+        }
+    }
+    int rc = rows ? quant_launch(s, drows, s->d) : quant_launch(s, s->x, s->dp);
+    if (!rc && codes_out &&
+        hipMemcpy2DAsync(codes_out, (size_t)s->d, s->codes, (size_t)s->dcs, (size_t)s->d, (size_t)s->n, hipMemcpyDeviceToHost, s->stream) != hipSuccess) {
+        s->set_error("nnd_searcher_quantize_u8: D2H of the codes failed");
+        rc = 1;
+    }
+    if (hipStreamSynchronize(s->stream) != hipSuccess && !rc) {
+        s->set_error("nnd_searcher_quantize_u8: kernel failed: %s", hipGetErrorString(hipGetLastError()));
+        rc = 1;
+    }
+    if (drows) (void)hipFree(drows);
+    return rc;
+}
+
+extern "C" int32_t nnd_searcher_set_codes_u8(nnd_searcher_t s, const float *values, int32_t n_values, const uint8_t *codes) {
+    if (!s) { snprintf(g_serr, sizeof(g_serr), "nnd_searcher_set_codes_u8: null searcher"); return 1; }
+    if (!codes) { s->set_error("nnd_searcher_set_codes_u8: codes missing"); return 1; }
+    if (quant_tables(s, "nnd_searcher_set_codes_u8", values, n_values)) return 1;
+    S_HIP(hipMemsetAsync(s->codes, 0, (size_t)s->n * s->dcs, s->stream));
+    S_HIP(hipMemcpy2DAsync(s->codes, (size_t)s->dcs, codes, (size_t)s->d, (size_t)s->d, (size_t)s->n, hipMemcpyHostToDevice, s->stream));
+    if (s->cn2 && quant_launch(s, nullptr, 0)) return 1;
+    S_HIP(hipStreamSynchronize(s->stream));
+    return 0;
+}
+
+extern "C" int32_t nnd_searcher_query_proxy(nnd_searcher_t s, const float *queries, int64_t nq, int32_t k, int32_t search_k, float epsilon,
+                                            int32_t *out_idx, float *out_dist) {
+    if (!s) { snprintf(g_serr, sizeof(g_serr), "nnd_searcher_query_proxy: null searcher"); return 1; }
+    if (!s->codes) { s->set_error("nnd_searcher_query_proxy: the searcher has no codes (nnd_searcher_quantize_u8 first)"); return 1; }
+    if (search_k < 1 || search_k > 256 || k < 1 || k > search_k) {
+        s->set_error("nnd_searcher_query_proxy: need 1 <= k <= search_k <= 256 (got k %d, search_k %d)", k, search_k);
+        return 1;
+    }
+    return searcher_run(s, queries, nq, search_k, k, epsilon, true, out_idx, out_dist);
 }

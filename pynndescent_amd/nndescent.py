@@ -73,6 +73,36 @@ _DISTANCE_CORRECTIONS = {"euclidean": _capi.host_sqrt, "l2": _capi.host_sqrt, "s
                          "correlation": _capi.host_copy, "hellinger": correct_alternative_hellinger}
 
 
+# metrics with a uint8 proxy distance in the reference (distances.py:2250-2255 quantized_distances["uint8"])
+_UINT8_METRICS = ("euclidean", "l2", "cosine", "dot")
+
+
+def _check_quantization(quantization, metric):
+    """The quantization checks of the reference's ``prepare()`` (pynndescent_.py:2175-2263), host only."""
+    if quantization is None:
+        return
+    if quantization == "uint8":
+        if metric not in _UINT8_METRICS:
+            raise ValueError(f"Not uint8 quantization version of {metric}")
+        return
+    if quantization in ("uint4", "binary"):
+        raise NotImplementedError("quantized search with quantization=%r is out of scope for pynndescent_amd (\"uint8\" is "
+                                  "supported); use index.to_reference()" % (quantization,))
+    raise ValueError(f"Unrecognized quantization type {quantization}")
+
+
+def uint8_codebook(raw, random_state):
+    """The reference's uint8 codebook (pynndescent_.py:2193-2206) of the rows ``raw`` in their ORIGINAL order: a sample of
+    min(10000, n) rows drawn by ``check_random_state(random_state)``; its distinct values when there are at most 256,
+    else its quantiles at ``linspace(0, 1, 256)``; float32."""
+    rs = check_random_state(random_state)
+    sample = raw[rs.choice(raw.shape[0], min(10000, raw.shape[0]), replace=False)].ravel()
+    unique = np.unique(sample)
+    if len(unique) <= 256:
+        return unique.astype(np.float32)
+    return np.quantile(sample, np.linspace(0, 1, 256)).astype(np.float32)
+
+
 class _DeviceForestSentinel:
     """Stands in for ``_rp_forest``: downstream reference code only null-checks it
     (pynndescent_.py:1353) -- the build consumes nothing but the leaf array."""
@@ -494,29 +524,57 @@ class NNDescent:
             del self._neighbor_graph
 
     def prepare(self):
-        """``NNDescent.prepare`` (pynndescent_.py:2174-2273): build everything a query needs."""
-        if self.quantization is not None:
-            raise NotImplementedError("quantized search (quantization=%r) is out of scope for pynndescent_amd; use "
-                                      "index.to_reference()" % (self.quantization,))
-        if not hasattr(self, "_search_graph"):
+        """``NNDescent.prepare`` (pynndescent_.py:2174-2273): build everything a query needs.  quantization="uint8": the
+        codebook is drawn on the host from the rows in their original order, the device quantizes the searcher's rows, and
+        ``_quantized_data`` is kept on the host in the searcher's (tree) order, as the reference keeps it.  An index that
+        already has them (unpickled) reuses ``_quantized_values`` / ``_quantized_data``."""
+        _check_quantization(self.quantization, self.metric)
+        quantized = self.quantization == "uint8"
+        self._is_proxy_distance = quantized
+        fresh = not hasattr(self, "_search_graph")
+        if quantized and (fresh or getattr(self, "_quantized_values", None) is None):
+            raw = self._raw_data if fresh else self._raw_data[np.argsort(self._vertex_order)]
+            self._quantized_values = uint8_codebook(raw, self.random_state)
+            self._quantized_data = None  # derived by the device below, in the searcher's order
+        if fresh:
             self._init_search_graph()
         if getattr(self, "_searcher", None) is None:
             tree = self._search_forest[0] if self._search_forest else None
             self._searcher = _capi.Searcher(self._raw_data, self._search_graph, tree, _METRIC_CODES[self.metric],
                                             self._min_distance, self.n_neighbors, self.search_rng_state, device=self.device)
+        if quantized and not self._searcher.has_codes:
+            if getattr(self, "_quantized_data", None) is None:
+                # dot: the searcher's own copy is normalised once more on the device; the codes are those of _raw_data
+                rows = self._raw_data if self.metric == "dot" else None
+                self._quantized_data = self._searcher.quantize_u8(self._quantized_values, rows=rows)
+            else:
+                self._searcher.set_codes_u8(self._quantized_values, self._quantized_data)
 
     def query(self, query_data, k=10, epsilon=0.1, proxy_beam_size=4):
         """``NNDescent.query`` (pynndescent_.py:2275-2379) on the GPU: one wave per query (csrc/query.hip).
         Returns (indices (n_queries, k) in the ORIGINAL numbering, true distances (n_queries, k))."""
         if k > 256:
             raise NotImplementedError("pynndescent_amd answers queries with k <= 256; use index.to_reference() for k = %d" % k)
-        if not hasattr(self, "_search_graph") or getattr(self, "_searcher", None) is None:
+        _check_quantization(self.quantization, self.metric)
+        search_k = k
+        if self.quantization is not None:  # pynndescent_.py:2309-2312
+            search_k = proxy_beam_size * k
+            if search_k < k:
+                raise ValueError("proxy_beam_size must be at least 1 (got %r)" % (proxy_beam_size,))
+            if search_k > 256:
+                raise NotImplementedError("pynndescent_amd keeps proxy_beam_size * k <= 256 candidates per quantized query "
+                                          "(got %d); use index.to_reference()" % search_k)
+        if (not hasattr(self, "_search_graph") or getattr(self, "_searcher", None) is None
+                or (self.quantization is not None and not self._searcher.has_codes)):
             self.prepare()
         query_data = np.asarray(query_data).astype(np.float32, order="C")  # pynndescent_.py:2316
         if query_data.ndim != 2 or query_data.shape[1] != self._raw_data.shape[1]:
             raise ValueError("query_data must have shape (n_queries, %d)" % self._raw_data.shape[1])
         _raise_if_negative_host(query_data, self.metric)
-        indices, dists = self._searcher.query(query_data, k, epsilon)
+        if self.quantization is not None:  # the walk on the codes, the rerank in its epilogue (pynndescent_.py:2321-2322, 2363-2371)
+            indices, dists = self._searcher.query_proxy(query_data, k, search_k, epsilon + 1e-32)
+        else:
+            indices, dists = self._searcher.query(query_data, k, epsilon)
         found = indices >= 0
         indices = np.where(found, self._vertex_order[np.where(found, indices, 0)], -1).astype(np.int32)  # pynndescent_.py:2373
         if self._distance_correction is not None:  # pynndescent_.py:2375-2376
