@@ -15,7 +15,9 @@ Out of scope: sparse input, every other metric, ``n_neighbors`` above 256 or
 ``max_candidates`` above 128 (``query``: more than 256 results per query).  Those raise ``NotImplementedError`` naming the reference entry point to use
 instead; ``pynndescent_amd.make_index`` hands such inputs to ``pynndescent.NNDescent`` when it is importable.
 """
+import inspect
 import time
+from typing import Callable, NamedTuple
 from warnings import warn
 
 import numpy as np
@@ -25,11 +27,6 @@ from . import _capi
 
 INT32_MIN = np.iinfo(np.int32).min + 1  # pynndescent_.py:62
 INT32_MAX = np.iinfo(np.int32).max - 1  # pynndescent_.py:63
-
-_METRIC_CODES = _capi.METRIC_CODES
-# metrics whose trees are angular in the reference (pynndescent_.py:1075-1086)
-_ANGULAR_METRICS = ("cosine", "dot", "correlation", "dice", "jaccard", "hellinger", "hamming", "bit_hamming",
-                    "bit_jaccard")
 
 
 def ts():
@@ -65,16 +62,61 @@ def correct_alternative_hellinger(d):
     return np.sqrt(1.0 - np.power(2.0, -np.asarray(d, dtype=np.float64)))
 
 
-# (numpy.sqrt; large float32 arrays go through the library's threaded sqrtf -- the same bits, the fresh pages touched in parallel)
-# ("sqeuclidean": the reference applies no correction, pynndescent_.py:1271-1298; neighbor_graph still hands out a copy)
-# ("correlation": a true distance, no correction either, pynndescent_.py:1271-1298)
-_DISTANCE_CORRECTIONS = {"euclidean": _capi.host_sqrt, "l2": _capi.host_sqrt, "sqeuclidean": _capi.host_copy, "cosine": correct_alternative_cosine,
-                         "dot": correct_alternative_cosine, "inner_product": correct_alternative_inner_product,
-                         "correlation": _capi.host_copy, "hellinger": correct_alternative_hellinger}
+class _Metric(NamedTuple):
+    """What the host needs to know about one metric of the device path."""
+    code: int  # the kernels' metric (include/pynnd_amd.h NND_METRIC_*)
+    correction: Callable  # kernel distance -> the metric's own, always a new array (pynndescent_.py:1271-1298)
+    angular: bool = False  # angular trees in the reference (pynndescent_.py:1075-1086)
+    uint8: bool = False  # has a uint8 proxy distance (distances.py:2250-2255 quantized_distances["uint8"])
+    normalize: bool = False  # rows L2-normalised before anything else (pynndescent_.py:1101-1102)
+    nonnegative: bool = False  # hellinger takes sqrt(x): a negative entry is an error here, NaN distances in the reference
 
 
-# metrics with a uint8 proxy distance in the reference (distances.py:2250-2255 quantized_distances["uint8"])
-_UINT8_METRICS = ("euclidean", "l2", "cosine", "dot")
+# corrections: numpy.sqrt, large float32 arrays through the library's threaded sqrtf (the same bits, the fresh pages touched in
+# parallel); "sqeuclidean" and "correlation" are the kernels' own space, with no correction (pynndescent_.py:1271-1298) --
+# neighbor_graph still hands out a copy
+_METRICS = {
+    "euclidean": _Metric(_capi.METRIC_CODES["euclidean"], _capi.host_sqrt, uint8=True),
+    "l2": _Metric(_capi.METRIC_CODES["l2"], _capi.host_sqrt, uint8=True),
+    "sqeuclidean": _Metric(_capi.METRIC_CODES["sqeuclidean"], _capi.host_copy),
+    "cosine": _Metric(_capi.METRIC_CODES["cosine"], correct_alternative_cosine, angular=True, uint8=True),
+    "dot": _Metric(_capi.METRIC_CODES["dot"], correct_alternative_cosine, angular=True, uint8=True, normalize=True),
+    "inner_product": _Metric(_capi.METRIC_CODES["inner_product"], correct_alternative_inner_product),
+    "correlation": _Metric(_capi.METRIC_CODES["correlation"], _capi.host_copy, angular=True),
+    "hellinger": _Metric(_capi.METRIC_CODES["hellinger"], correct_alternative_hellinger, angular=True, nonnegative=True),
+}
+# views of the table by one field
+_DISTANCE_CORRECTIONS = {name: m.correction for name, m in _METRICS.items()}
+_ANGULAR_METRICS = frozenset(name for name, m in _METRICS.items() if m.angular)
+
+
+def _metric_record(metric, reference_fallback=True):
+    """The row of ``_METRICS``.  A metric off the device path raises the reference's ValueError (pynndescent_.py:1292), or
+    with ``reference_fallback`` NotImplementedError when the reference runs it (a callable, a name it knows): what
+    ``make_index`` hands to ``pynndescent.NNDescent``."""
+    if not callable(metric) and metric in _METRICS:
+        return _METRICS[metric]
+    if reference_fallback and (callable(metric) or metric in _KNOWN_REFERENCE_METRICS):
+        raise NotImplementedError(
+            "pynndescent_amd accelerates the dense euclidean / l2 / sqeuclidean / cosine / dot / inner_product / "
+            "correlation / hellinger build only; "
+            "use pynndescent.NNDescent for metric %r" % (metric,)
+        )
+    raise ValueError("Metric is neither callable, " + "nor a recognised string")
+
+
+def _reference_defaults(n, n_neighbors, n_trees=None, n_iters=None, leaf_size=None, max_candidates=None):
+    """The reference's derived defaults for what is None: (n_trees, n_iters, leaf_size, max_candidates) for ``n`` rows
+    (pynndescent_.py:1009-1012, 1135-1138; rp_trees.py:2845-2846)."""
+    if n_trees is None:
+        n_trees = max(3, min(12, int(round(2.0 * np.log10(n)))))
+    if n_iters is None:
+        n_iters = max(5, int(round(np.log2(n))))
+    if leaf_size is None:
+        leaf_size = max(60, min(256, 5 * int(n_neighbors)))
+    if max_candidates is None:
+        max_candidates = min(60, n_neighbors)
+    return n_trees, n_iters, leaf_size, max_candidates
 
 
 def _check_quantization(quantization, metric):
@@ -82,7 +124,7 @@ def _check_quantization(quantization, metric):
     if quantization is None:
         return
     if quantization == "uint8":
-        if metric not in _UINT8_METRICS:
+        if not _METRICS[metric].uint8:
             raise ValueError(f"Not uint8 quantization version of {metric}")
         return
     if quantization in ("uint4", "binary"):
@@ -157,10 +199,8 @@ class NNDescent:
         reference's analogue is ``n_jobs``, pynndescent_.py:1141-1143); ``devices`` lists their ordinals (default
         0..n_devices-1; a list that repeats an ordinal puts several ranks on one GPU).  Everything after the build
         (``prepare``, ``query``, ``update``) runs on ``device``."""
-        if n_trees is None:
-            n_trees = max(3, min(12, int(round(2.0 * np.log10(data.shape[0])))))  # pynndescent_.py:1009-1010
-        if n_iters is None:
-            n_iters = max(5, int(round(np.log2(data.shape[0]))))  # pynndescent_.py:1011-1012
+        n_trees, n_iters, eff_leaf_size, eff_max_candidates = _reference_defaults(
+            data.shape[0], n_neighbors, n_trees, n_iters, leaf_size, max_candidates)
 
         self.n_trees = n_trees
         self.angular_trees = angular_trees
@@ -194,14 +234,7 @@ class NNDescent:
         if self.n_devices < 1 or (self.devices is not None and len(self.devices) != self.n_devices):
             raise ValueError("n_devices must be >= 1 and match len(devices)")
 
-        if callable(metric) or metric not in _METRIC_CODES:
-            if callable(metric) or metric in _KNOWN_REFERENCE_METRICS:
-                raise NotImplementedError(
-                    "pynndescent_amd accelerates the dense euclidean / l2 / sqeuclidean / cosine / dot / inner_product / "
-                    "correlation / hellinger build only; "
-                    "use pynndescent.NNDescent for metric %r" % (metric,)
-                )
-            raise ValueError("Metric is neither callable, " + "nor a recognised string")  # pynndescent_.py:1292
+        m = _metric_record(metric)
         try:
             import scipy.sparse
 
@@ -220,54 +253,20 @@ class NNDescent:
         # into a copy; any other input has been copied by check_array already and is normalised in place
         copy_on_normalize = getattr(data, "dtype", None) == np.float32 and bool(getattr(getattr(data, "flags", None), "c_contiguous", False))
         data = _check_array_no_scan(data)
-        if metric == "dot":  # pynndescent_.py:1101-1102
-            from sklearn.preprocessing import normalize
-
-            data = normalize(data, norm="l2", copy=copy_on_normalize)
-        self._input_dtype = np.float32
-        self._raw_data = data
-
-        if not tree_init or n_trees == 0 or init_graph is not None:  # pynndescent_.py:1059-1062
-            self.tree_init = False
-        else:
-            self.tree_init = True
-
-        metric_kwds = metric_kwds or {}
-        self._dist_args = tuple(metric_kwds.values())
-        self.random_state = random_state
-        current_random_state = check_random_state(self.random_state)
-
-        self._distance_correction = _DISTANCE_CORRECTIONS[metric]
-        self._distance_func = None  # device kernels; see include/pynnd_amd.h NND_METRIC_*
-        self._angular_trees = metric in _ANGULAR_METRICS
-        self._bit_trees = False
-        self._is_sparse = False
-
-        # RandomState draw order of the reference: rng_state, search_rng_state, then the per-tree
-        # states inside make_forest (pynndescent_.py:1105-1113, rp_trees.py:2850)
-        self.rng_state = current_random_state.randint(INT32_MIN, INT32_MAX, 3).astype(np.int64)
-        self.search_rng_state = current_random_state.randint(INT32_MIN, INT32_MAX, 3).astype(np.int64)
-        for _ in range(10):
-            tau_rand_int(self.search_rng_state)
+        self.tree_init = not (not tree_init or n_trees == 0 or init_graph is not None)  # pynndescent_.py:1059-1062
+        self._dist_args = tuple((metric_kwds or {}).values())
+        current_random_state = self._set_up(data, m, random_state, copy_on_normalize)
+        data = self._raw_data
 
         n = data.shape[0]
         if self.tree_init:
             if verbose:
                 print(ts(), "Building RP forest with", str(n_trees), "trees")
-            eff_leaf_size = leaf_size
-            if eff_leaf_size is None:
-                eff_leaf_size = max(60, min(256, 5 * int(n_neighbors)))  # rp_trees.py:2845-2846
             tree_states = current_random_state.randint(INT32_MIN, INT32_MAX, size=(n_trees, 3)).astype(np.int64)
             eff_trees = n_trees
         else:
-            eff_leaf_size = max(60, min(256, 5 * int(n_neighbors))) if leaf_size is None else leaf_size
             tree_states = np.zeros((1, 3), np.int64)
             eff_trees = 0
-
-        if self.max_candidates is None:
-            effective_max_candidates = min(60, self.n_neighbors)  # pynndescent_.py:1135-1138
-        else:
-            effective_max_candidates = self.max_candidates
 
         if init_graph is not None:
             init_graph = np.asarray(init_graph)
@@ -276,12 +275,15 @@ class NNDescent:
             if init_dist is not None and init_graph.shape != np.asarray(init_dist).shape:
                 raise ValueError("The shapes of init graph and init distances do not match!")  # pynndescent_.py:1236
 
-        if self.n_devices > 1:  # (round 5: a build that starts from init_graph is sharded too -- nnd_build_multi_from_graph)
-            self._build_multi(data, metric, n_trees, eff_trees, eff_leaf_size, effective_max_candidates, n_iters, delta,
-                              max_rptree_depth, tree_states, verbose, init_graph, init_dist)
+        if self.n_devices > 1:  # (a build that starts from init_graph is sharded too -- nnd_build_multi_from_graph)
+            n_leaves = self._build_multi(data, eff_trees, eff_leaf_size, eff_max_candidates, tree_states[0], verbose,
+                                         init_graph=init_graph, init_dist=init_dist)
         else:
-            self._build_single(data, metric, n_trees, eff_trees, eff_leaf_size, effective_max_candidates, n_iters, delta,
-                               max_rptree_depth, tree_states, init_graph, init_dist, verbose, device)
+            self._neighbor_graph, self._build_stats, n_leaves = _build_graph(
+                data, m, n_neighbors, eff_trees, eff_leaf_size, max_rptree_depth, eff_max_candidates, n_iters, delta,
+                self.rng_state, tree_states[0], device, forest=self.tree_init, init_graph=init_graph, init_dist=init_dist,
+                random_fill=init_graph is None, check_finite=True, verbose=verbose, announce=verbose)
+        self._rp_forest = _DeviceForestSentinel(n_trees, n_leaves, eff_leaf_size) if self.tree_init else None
 
         # pynndescent_.py:1262-1267 `np.any(indices < 0)`: rows are ascending with the unfilled entries (-1, +inf) at the
         # tail, so the last column tells (1 M strided reads instead of a 15 M-element temporary)
@@ -292,69 +294,55 @@ class NNDescent:
                 " different parameters."
             )
 
-    def _build_multi(self, data, metric, n_trees, eff_trees, eff_leaf_size, effective_max_candidates, n_iters, delta,
-                     max_rptree_depth, tree_states, verbose, init_graph=None, init_dist=None):
-        """Row-sharded build over several GPUs, one call into the library (include/pynnd_amd.h nnd_build_multi)."""
+    def _set_up(self, data, m, random_state, copy):
+        """What the constructor and ``from_graph`` share (pynndescent_.py:1064-1113): the data the index holds (dot: rows
+        L2-normalised, into a new array when ``copy``), the metric's correction and tree flags, and ``rng_state`` /
+        ``search_rng_state`` drawn in the reference's order.  Returns the RandomState, whose next draws are the trees'."""
+        if m.normalize:  # pynndescent_.py:1101-1102
+            from sklearn.preprocessing import normalize
+
+            data = normalize(data, norm="l2", copy=copy)
+        self._input_dtype = np.float32
+        self._raw_data = data
+        self.random_state = random_state
+        current_random_state = check_random_state(random_state)
+        self._distance_correction = m.correction
+        self._distance_func = None  # device kernels; see include/pynnd_amd.h NND_METRIC_*
+        self._angular_trees = m.angular
+        self._bit_trees = False
+        self._is_sparse = False
+        # RandomState draw order of the reference: rng_state, search_rng_state, then the per-tree
+        # states inside make_forest (pynndescent_.py:1105-1113, rp_trees.py:2850)
+        self.rng_state = current_random_state.randint(INT32_MIN, INT32_MAX, 3).astype(np.int64)
+        self.search_rng_state = current_random_state.randint(INT32_MIN, INT32_MAX, 3).astype(np.int64)
+        for _ in range(10):
+            tau_rand_int(self.search_rng_state)
+        return current_random_state
+
+    def _build_multi(self, data, n_trees, leaf_size, max_candidates, tree_state, verbose, init_graph=None, init_dist=None,
+                     old_graph=None):
+        """Row-sharded build over several GPUs, one call into the library (include/pynnd_amd.h nnd_build_multi): from a
+        forest, from ``init_graph`` / ``init_dist``, or from a forest and ``old_graph`` (``update()``).  Sets the graph
+        and the stats; returns the forest's leaf count."""
         from sklearn.utils import assert_all_finite
 
         from . import sharded
 
         assert_all_finite(data)  # check_array's scan (pynndescent_.py:1054): the one-call multi-GPU build has no flag to read
-        _raise_if_negative_host(data, metric)
+        _raise_if_negative_host(data, _METRICS[self.metric])
         if verbose:
-            print(ts(), "NN descent for", str(n_iters), "iterations on", self.n_devices, "GPUs")
+            print(ts(), "NN descent for", str(self.n_iters), "iterations on", self.n_devices, "GPUs")
         idx, dst, st, info = sharded.build_multi(
-            data, self.n_devices, self.devices, metric, self.n_neighbors, eff_trees, eff_leaf_size, effective_max_candidates,
-            n_iters, delta, max_rptree_depth=max_rptree_depth, rng_state=self.rng_state, tree_state=tree_states[0],
-            init_graph=init_graph, init_dist=init_dist)
-        self._rp_forest = _DeviceForestSentinel(n_trees, st["n_leaves"], eff_leaf_size) if self.tree_init else None
+            data, self.n_devices, self.devices, self.metric, self.n_neighbors, n_trees, leaf_size, max_candidates,
+            self.n_iters, self.delta, max_rptree_depth=self.max_rptree_depth, rng_state=self.rng_state,
+            tree_state=tree_state, init_graph=init_graph, init_dist=init_dist, old_graph=old_graph)
         self._neighbor_graph = (idx, dst)
         self._build_stats = st
         self._shard_info = info
         if verbose:
             for it, c in enumerate(info["c"]):
-                print("\t", it + 1, " / ", n_iters, " c =", c)
-
-    def _build_single(self, data, metric, n_trees, eff_trees, eff_leaf_size, effective_max_candidates, n_iters, delta,
-                      max_rptree_depth, tree_states, init_graph, init_dist, verbose, device):
-        n, n_neighbors = data.shape[0], self.n_neighbors
-        builder = _capi.Builder(
-            n, data.shape[1], _METRIC_CODES[metric], n_neighbors, eff_trees, eff_leaf_size, max_rptree_depth,
-            effective_max_candidates, n_iters, delta, self.rng_state, tree_states[0], device=device,
-        )
-        try:
-            builder.set_data_host(data)
-            _raise_if_nonfinite(builder, data)
-            if metric == "hellinger" and builder.data_negative():
-                raise ValueError(_NEGATIVE_HELLINGER)
-            if self.tree_init:
-                builder.make_forest()
-                st = builder.stats()
-                self._rp_forest = _DeviceForestSentinel(n_trees, st["n_leaves"], eff_leaf_size)
-            else:
-                self._rp_forest = None
-            if verbose:
-                print(ts(), "NN descent for", str(n_iters), "iterations")
-            if init_graph is None:
-                if self.tree_init:
-                    builder.init_from_leaves()
-                builder.init_random()
-            else:
-                builder.init_from_graph(init_graph, init_dist)
-            if verbose:
-                # nn_descent_internal (pynndescent_.py:296-320), driven from here so that the output matches the reference's
-                for it in range(n_iters):
-                    print("\t", it + 1, " / ", n_iters)
-                    c = builder.descent_iter()
-                    if c <= delta * n_neighbors * n:
-                        print("\tStopping threshold met -- exiting after", it + 1, "iterations")
-                        break
-            else:
-                builder.descent()  # the same loop inside the library (nnd_descent): no host round trip per iteration
-            self._neighbor_graph = builder.finalize()
-            self._build_stats = builder.stats()
-        finally:
-            builder.close()
+                print("\t", it + 1, " / ", self.n_iters, " c =", c)
+        return st["n_leaves"]
 
     @property
     def neighbor_graph(self):
@@ -423,57 +411,28 @@ class NNDescent:
         self = object.__new__(cls)
         data = check_array(data, dtype=np.float32, order="C")
         n = data.shape[0]
-        n_trees = kwargs.pop("n_trees", None)
-        n_iters = kwargs.pop("n_iters", None)
-        if n_trees is None:
-            n_trees = max(3, min(12, int(round(2.0 * np.log10(n)))))
-        if n_iters is None:
-            n_iters = max(5, int(round(np.log2(n))))
-        defaults = dict(
-            angular_trees=False, metric_kwds=None, bit_metric=False, leaf_size=None, prune_degree_multiplier=1.5,
-            diversify_prob=1.0, diversify_method="standard", degree_prune_aggressiveness=1.0, n_search_trees=1,
-            search_tree_leaf_size=None, max_search_tree_depth=None, max_rptree_depth=200, max_candidates=None,
-            quantization=None, low_memory=True, delta=0.001, n_jobs=None, compressed=False,
-            parallel_batch_queries=False, verbose=False, device=0,
-        )
         if "pruning_degree_multiplier" in kwargs:  # the constructor's name for prune_degree_multiplier
             kwargs["prune_degree_multiplier"] = kwargs.pop("pruning_degree_multiplier")
-        unknown = set(kwargs) - set(defaults)
+        unknown = set(kwargs) - set(_FROM_GRAPH_DEFAULTS)
         if unknown:
             raise TypeError("unexpected arguments: %s" % sorted(unknown))
-        defaults.update(kwargs)
-        for name, value in defaults.items():
+        for name, value in dict(_FROM_GRAPH_DEFAULTS, **kwargs).items():
             setattr(self, name, value)
-        if metric not in _METRIC_CODES:
-            raise ValueError("Metric is neither callable, " + "nor a recognised string")
+        m = _metric_record(metric, reference_fallback=False)
         indices = np.ascontiguousarray(indices, np.int32)
         distances = np.ascontiguousarray(distances, np.float32)
         if indices.shape != distances.shape or indices.shape[0] != n:
             raise ValueError("Init graph size does not match dataset size!")
         _check_supported_sizes(indices.shape[1], self.max_candidates, None)
-        if metric == "dot":  # the data NNDescent would hold (pynndescent_.py:1101-1102)
-            from sklearn.preprocessing import normalize
-
-            data = normalize(data, norm="l2", copy=True)
-        _raise_if_negative_host(data, metric)
+        _raise_if_negative_host(data, m)
         self.metric, self.n_neighbors = metric, indices.shape[1]
-        self.n_trees, self.n_iters = n_trees, n_iters
-        self.n_trees_after_update = max(2, int(np.round(n_trees / 3)))
+        self.n_trees, self.n_iters, _, _ = _reference_defaults(n, self.n_neighbors, self.n_trees, self.n_iters)
+        self.n_trees_after_update = max(2, int(np.round(self.n_trees / 3)))
         self.dim = data.shape[1]
-        self._input_dtype, self._raw_data = np.float32, data
         self.tree_init = True
         self._dist_args = tuple((self.metric_kwds or {}).values())
-        self.random_state = random_state
-        rs = check_random_state(random_state)
-        self._distance_correction = _DISTANCE_CORRECTIONS[metric]
-        self._distance_func = None
-        self._angular_trees = metric in _ANGULAR_METRICS
-        self._bit_trees = self._is_sparse = False
-        self.rng_state = rs.randint(INT32_MIN, INT32_MAX, 3).astype(np.int64)
-        self.search_rng_state = rs.randint(INT32_MIN, INT32_MAX, 3).astype(np.int64)
-        for _ in range(10):
-            tau_rand_int(self.search_rng_state)
-        self._rp_forest = _DeviceForestSentinel(n_trees, 0, 0)
+        self._set_up(data, m, random_state, copy=True)  # (dot: the data NNDescent would hold, in a new array)
+        self._rp_forest = _DeviceForestSentinel(self.n_trees, 0, 0)
         self._neighbor_graph = (indices, distances)
         return self
 
@@ -540,12 +499,12 @@ class NNDescent:
             self._init_search_graph()
         if getattr(self, "_searcher", None) is None:
             tree = self._search_forest[0] if self._search_forest else None
-            self._searcher = _capi.Searcher(self._raw_data, self._search_graph, tree, _METRIC_CODES[self.metric],
+            self._searcher = _capi.Searcher(self._raw_data, self._search_graph, tree, _METRICS[self.metric].code,
                                             self._min_distance, self.n_neighbors, self.search_rng_state, device=self.device)
         if quantized and not self._searcher.has_codes:
             if getattr(self, "_quantized_data", None) is None:
                 # dot: the searcher's own copy is normalised once more on the device; the codes are those of _raw_data
-                rows = self._raw_data if self.metric == "dot" else None
+                rows = self._raw_data if _METRICS[self.metric].normalize else None
                 self._quantized_data = self._searcher.quantize_u8(self._quantized_values, rows=rows)
             else:
                 self._searcher.set_codes_u8(self._quantized_values, self._quantized_data)
@@ -570,7 +529,7 @@ class NNDescent:
         query_data = np.asarray(query_data).astype(np.float32, order="C")  # pynndescent_.py:2316
         if query_data.ndim != 2 or query_data.shape[1] != self._raw_data.shape[1]:
             raise ValueError("query_data must have shape (n_queries, %d)" % self._raw_data.shape[1])
-        _raise_if_negative_host(query_data, self.metric)
+        _raise_if_negative_host(query_data, _METRICS[self.metric])
         if self.quantization is not None:  # the walk on the codes, the rerank in its epilogue (pynndescent_.py:2321-2322, 2363-2371)
             indices, dists = self._searcher.query_proxy(query_data, k, search_k, epsilon + 1e-32)
         else:
@@ -597,7 +556,7 @@ class NNDescent:
         from .search_tree import FlatTree
 
         self.__dict__ = d
-        self._distance_correction = _DISTANCE_CORRECTIONS[self.metric]
+        self._distance_correction = _METRICS[self.metric].correction
         self._search_forest = [FlatTree(*t) for t in d["_search_forest"]]  # rp_trees.py:3072-3081 renumbaify_tree
         self._searcher = None
 
@@ -659,62 +618,18 @@ class NNDescent:
         pad_d[:n_old] = ds
 
         self.n_trees = self.n_trees_after_update  # pynndescent_.py:2498
-        eff_leaf_size = self.leaf_size
-        if eff_leaf_size is None:
-            eff_leaf_size = max(60, min(256, 5 * int(self.n_neighbors)))  # rp_trees.py:2845-2846
+        _, _, eff_leaf_size, eff_max_candidates = _reference_defaults(n, self.n_neighbors, self.n_trees, self.n_iters,
+                                                                      self.leaf_size, self.max_candidates)
         tree_states = current_random_state.randint(INT32_MIN, INT32_MAX, size=(self.n_trees, 3)).astype(np.int64)
-        if self.max_candidates is None:
-            effective_max_candidates = min(60, self.n_neighbors)
-        else:
-            effective_max_candidates = self.max_candidates
-        if getattr(self, "n_devices", 1) > 1:  # round 5: the rebuild is sharded like the build was (nnd_build_multi_update)
-            from sklearn.utils import assert_all_finite
-
-            from . import sharded
-
-            assert_all_finite(raw)
-            _raise_if_negative_host(raw, self.metric)
-            idx, dst, st, info = sharded.build_multi(
-                raw, self.n_devices, self.devices, self.metric, self.n_neighbors, self.n_trees, eff_leaf_size, effective_max_candidates,
-                self.n_iters, self.delta, max_rptree_depth=self.max_rptree_depth, rng_state=self.rng_state, tree_state=tree_states[0],
-                old_graph=(pad_i, pad_d))
-            self._rp_forest = _DeviceForestSentinel(self.n_trees, st["n_leaves"], eff_leaf_size)
-            self._neighbor_graph = (idx, dst)
-            self._build_stats = st
-            self._shard_info = info
-            self._raw_data = raw
-            if hasattr(self, "_search_graph"):
-                for name in ("_search_graph", "_search_forest", "_vertex_order", "_searcher"):
-                    if hasattr(self, name):
-                        delattr(self, name)
-                self.prepare()
-            return
-        builder = _capi.Builder(
-            n, raw.shape[1], _METRIC_CODES[self.metric], self.n_neighbors, self.n_trees, eff_leaf_size,
-            self.max_rptree_depth, effective_max_candidates, self.n_iters, self.delta, self.rng_state, tree_states[0],
-            device=self.device,
-        )
-        try:
-            builder.set_data_host(raw)
-            if self.metric == "hellinger" and builder.data_negative():
-                raise ValueError(_NEGATIVE_HELLINGER)
-            builder.make_forest()
-            self._rp_forest = _DeviceForestSentinel(self.n_trees, builder.stats()["n_leaves"], eff_leaf_size)
-            builder.reset_graph()
-            builder.init_from_neighbor_graph(pad_i, pad_d)  # pynndescent_.py:2512-2516
-            builder.init_from_leaves()                      # pynndescent_.py:2517
-            for it in range(self.n_iters):                  # nn_descent with init_graph: no random fill (P_:346-350)
-                if self.verbose:
-                    print("\t", it + 1, " / ", self.n_iters)
-                c = builder.descent_iter()
-                if c <= self.delta * self.n_neighbors * n:
-                    if self.verbose:
-                        print("\tStopping threshold met -- exiting after", it + 1, "iterations")
-                    break
-            self._neighbor_graph = builder.finalize()
-            self._build_stats = builder.stats()
-        finally:
-            builder.close()
+        if getattr(self, "n_devices", 1) > 1:  # the rebuild is sharded like the build was (nnd_build_multi_update)
+            n_leaves = self._build_multi(raw, self.n_trees, eff_leaf_size, eff_max_candidates, tree_states[0], False,
+                                         old_graph=(pad_i, pad_d))
+        else:  # pynndescent_.py:2512-2517: the old graph's entries as "old" edges, then the forest's; no random fill
+            self._neighbor_graph, self._build_stats, n_leaves = _build_graph(
+                raw, _METRICS[self.metric], self.n_neighbors, self.n_trees, eff_leaf_size, self.max_rptree_depth,
+                eff_max_candidates, self.n_iters, self.delta, self.rng_state, tree_states[0], self.device, forest=True,
+                old_graph=(pad_i, pad_d), verbose=self.verbose)
+        self._rp_forest = _DeviceForestSentinel(self.n_trees, n_leaves, eff_leaf_size)
         self._raw_data = raw
         if hasattr(self, "_search_graph"):  # pynndescent_.py:2538-2553: the derived structures are rebuilt
             for name in ("_search_graph", "_search_forest", "_vertex_order", "_searcher"):
@@ -723,20 +638,26 @@ class NNDescent:
             self.prepare()
 
 
+# from_graph's keywords and their defaults: the constructor's, minus what the graph fixes (the data, n_neighbors, the metric
+# and random_state are arguments of their own; the build's seeding and its devices do not apply)
+_FROM_GRAPH_DEFAULTS = {
+    ("prune_degree_multiplier" if name == "pruning_degree_multiplier" else name): p.default
+    for name, p in inspect.signature(NNDescent.__init__).parameters.items()
+    if name not in ("self", "data", "metric", "n_neighbors", "random_state", "tree_init", "init_graph", "init_dist",
+                    "n_devices", "devices")
+}
+
 EMPTY_GRAPH = (np.array([[-1]], dtype=np.int32), np.array([[np.inf]], dtype=np.float32),
                np.array([[0]], dtype=np.uint8))  # pynndescent_.py:64-68
 
-# distance arguments nn_descent understands: name (or __name__ of the reference's function) -> (kernel metric, correction)
-_ND_DISTS = {"squared_euclidean": (_capi.NND_METRIC_SQEUCLIDEAN, None), "sqeuclidean": (_capi.NND_METRIC_SQEUCLIDEAN, None),
-             "euclidean": (_capi.NND_METRIC_SQEUCLIDEAN, np.sqrt), "l2": (_capi.NND_METRIC_SQEUCLIDEAN, np.sqrt),
-             "alternative_cosine": (_capi.NND_METRIC_ALT_COSINE, None),
-             "cosine": (_capi.NND_METRIC_ALT_COSINE, correct_alternative_cosine),
-             "alternative_dot": (_capi.NND_METRIC_ALT_DOT, None), "dot": (_capi.NND_METRIC_ALT_DOT, correct_alternative_cosine),
-             "alternative_inner_product": (_capi.NND_METRIC_ALT_INNER_PRODUCT, None),
-             "inner_product": (_capi.NND_METRIC_ALT_INNER_PRODUCT, correct_alternative_inner_product),
-             "correlation": (_capi.NND_METRIC_CORRELATION, None),
-             "alternative_hellinger": (_capi.NND_METRIC_ALT_HELLINGER, None),
-             "hellinger": (_capi.NND_METRIC_ALT_HELLINGER, correct_alternative_hellinger)}
+# the reference's functions of the kernels' own spaces (pynndescent_.py:1247-1260) -> the metric whose kernels they name
+_ND_ALIASES = {"squared_euclidean": "sqeuclidean", "alternative_cosine": "cosine", "alternative_dot": "dot",
+               "alternative_inner_product": "inner_product", "alternative_hellinger": "hellinger"}
+# distance arguments nn_descent understands: name (or __name__ of the reference's function) -> (kernel metric, correction);
+# the eight metrics give true distances (the same kernels, corrected on return), the aliases none (a copy is no correction:
+# nn_descent returns the finished arrays themselves)
+_ND_DISTS = {name: (m.code, None if m.correction is _capi.host_copy else m.correction) for name, m in _METRICS.items()}
+_ND_DISTS.update((alt, (_METRICS[name].code, None)) for alt, name in _ND_ALIASES.items())
 
 
 def nn_descent(data, n_neighbors, rng_state, max_candidates=50, dist="squared_euclidean", n_iters=10, delta=0.001,
@@ -755,42 +676,80 @@ def nn_descent(data, n_neighbors, rng_state, max_candidates=50, dist="squared_eu
     name = dist if isinstance(dist, str) else getattr(dist, "__name__", None)
     if name not in _ND_DISTS:
         raise NotImplementedError("pynndescent_amd.nn_descent: dist must be one of %s (got %r)" % (sorted(_ND_DISTS), dist))
-    code, correction = _ND_DISTS[name]
+    m, correction = _METRICS[_ND_ALIASES.get(name, name)], _ND_DISTS[name][1]
     data = np.ascontiguousarray(data, dtype=np.float32)
     n = data.shape[0]
     _check_supported_sizes(n_neighbors, max_candidates, None)
     empty = init_graph[0].shape[0] == 1  # EMPTY_GRAPH
     if not empty and not (init_graph[0].shape[0] == n and init_graph[0].shape[1] == n_neighbors):
         raise ValueError("Invalid initial graph specified!")  # pynndescent_.py:352
-    builder = _capi.Builder(n, data.shape[1], code, n_neighbors, 0, max(60, min(256, 5 * int(n_neighbors))), 200,
-                            max_candidates, n_iters, delta, np.asarray(rng_state, np.int64), np.zeros(3, np.int64),
-                            device=device)
-    try:
-        builder.set_data_host(data)
-        if code == _capi.NND_METRIC_ALT_HELLINGER and builder.data_negative():
-            raise ValueError(_NEGATIVE_HELLINGER)
-        if empty:
-            if rp_tree_init:
-                if leaf_array is None:
-                    raise ValueError("rp_tree_init=True needs a leaf_array (rptree_leaf_array of a forest)")
-                builder.init_from_leaf_array(leaf_array)
-            builder.init_random()
-        else:  # a heap handed over: its entries, with their distances (flags restart as "new": they were never sampled here)
-            builder.init_from_graph(np.asarray(init_graph[0], np.int32), np.asarray(init_graph[1], np.float32))
-        for it in range(n_iters):  # nn_descent_internal (pynndescent_.py:296-320)
-            if verbose:
-                print("\t", it + 1, " / ", n_iters)
-            c = builder.descent_iter()
-            if c <= delta * n_neighbors * n:
-                if verbose:
-                    print("\tStopping threshold met -- exiting after", it + 1, "iterations")
-                break
-        idx, dst = builder.finalize()
-    finally:
-        builder.close()
+    if empty and rp_tree_init and leaf_array is None:
+        raise ValueError("rp_tree_init=True needs a leaf_array (rptree_leaf_array of a forest)")
+    leaf_size = _reference_defaults(n, n_neighbors, 0, n_iters, None, max_candidates)[2]
+    # (a heap handed over: its entries, with their distances; flags restart as "new": they were never sampled here)
+    (idx, dst), _, _ = _build_graph(
+        data, m, n_neighbors, 0, leaf_size, 200, max_candidates, n_iters, delta, np.asarray(rng_state, np.int64),
+        np.zeros(3, np.int64), device, leaf_array=leaf_array if empty and rp_tree_init else None,
+        init_graph=None if empty else np.asarray(init_graph[0], np.int32),
+        init_dist=None if empty else np.asarray(init_graph[1], np.float32), random_fill=empty, stats=False, verbose=verbose)
     if correction is not None:
         dst = correction(dst).astype(np.float32)
     return idx, dst
+
+
+def _build_graph(data, m, n_neighbors, n_trees, leaf_size, max_depth, max_candidates, n_iters, delta, rng_state, tree_rng,
+                 device, forest=False, leaf_array=None, init_graph=None, init_dist=None, old_graph=None, random_fill=False,
+                 check_finite=False, stats=True, verbose=False, announce=False):
+    """Every single-GPU build (``_capi.Builder``): the data in, its flags read (the NaN / inf one only when
+    ``check_finite``), ``forest`` built on the device, the graph seeded -- ``old_graph`` (ids, distances) as "old" edges,
+    then ``init_graph`` / ``init_dist``, the caller's ``leaf_array`` or the forest's leaves, then the random fill when
+    ``random_fill`` -- NN-descent to the stop rule, the graph out.  ``announce``: the constructor's verbose line.  Returns
+    ``((indices, distances), the stats (when ``stats``), the forest's leaf count)``."""
+    n = data.shape[0]
+    builder = _capi.Builder(n, data.shape[1], m.code, n_neighbors, n_trees, leaf_size, max_depth, max_candidates, n_iters,
+                            delta, rng_state, tree_rng, device=device)
+    try:
+        builder.set_data_host(data)
+        if check_finite:
+            _raise_if_nonfinite(builder, data)
+        if m.nonnegative and builder.data_negative():
+            raise ValueError(_NEGATIVE_HELLINGER)
+        n_leaves = None
+        if forest:
+            builder.make_forest()
+            n_leaves = builder.stats()["n_leaves"]
+        if announce:
+            print(ts(), "NN descent for", str(n_iters), "iterations")
+        if old_graph is not None:
+            builder.reset_graph()
+            builder.init_from_neighbor_graph(*old_graph)
+        if init_graph is not None:
+            builder.init_from_graph(init_graph, init_dist)
+        elif leaf_array is not None:
+            builder.init_from_leaf_array(leaf_array)
+        elif forest:
+            builder.init_from_leaves()
+        if random_fill:
+            builder.init_random()
+        _descend(builder, n, n_neighbors, n_iters, delta, verbose)
+        graph = builder.finalize()
+        return graph, builder.stats() if stats else None, n_leaves
+    finally:
+        builder.close()
+
+
+def _descend(builder, n, n_neighbors, n_iters, delta, verbose):
+    """nn_descent_internal (pynndescent_.py:296-320): the library's loop (nnd_descent, no host round trip per iteration),
+    or with ``verbose`` the same iterations and stop rule driven from here, so that the output matches the reference's."""
+    if not verbose:
+        builder.descent()
+        return
+    for it in range(n_iters):
+        print("\t", it + 1, " / ", n_iters)
+        c = builder.descent_iter()
+        if c <= delta * n_neighbors * n:
+            print("\tStopping threshold met -- exiting after", it + 1, "iterations")
+            break
 
 
 def _check_array_no_scan(data):
@@ -813,8 +772,8 @@ def _raise_if_nonfinite(builder, data):
 _NEGATIVE_HELLINGER = "the hellinger metric needs non-negative input: the data holds a negative entry"
 
 
-def _raise_if_negative_host(data, metric):
-    if metric == "hellinger" and data.size and data.min() < 0:
+def _raise_if_negative_host(data, m):
+    if m.nonnegative and data.size and data.min() < 0:
         raise ValueError(_NEGATIVE_HELLINGER)
 
 

@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _capi
+from .nndescent import _reference_defaults
 
 
 # ------------------------------------------------------------------------------------------------
@@ -214,9 +215,7 @@ def _global_params(n_total, dim, metric, n_neighbors, n_trees, leaf_size, max_ca
     """nnd_params of the GLOBAL build with the reference's derived defaults (pynndescent_.py:1009-1012, 1135-1138;
     rp_trees.py:2845) and its RandomState draw order (identical on every rank)."""
     k = int(n_neighbors)
-    n_iters = max(5, int(round(np.log2(n_total)))) if n_iters is None else int(n_iters)
-    leaf_size = max(60, min(256, 5 * k)) if leaf_size is None else int(leaf_size)
-    mc = min(60, k) if max_candidates is None else int(max_candidates)
+    _, n_iters, leaf_size, mc = (int(v) for v in _reference_defaults(n_total, k, n_trees, n_iters, leaf_size, max_candidates))
     rs = np.random.RandomState(seed)
     lim = np.iinfo(np.int32)
     rng_state = rs.randint(lim.min + 1, lim.max - 1, 3).astype(np.int64)
