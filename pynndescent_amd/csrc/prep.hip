@@ -90,9 +90,11 @@ __global__ void k_screen_scale(float *__restrict__ mean, int d, int dp, int metr
 }
 
 // per-row transform of the unit-row metrics before the normalisation: correlation subtracts the row mean mu, hellinger
-// takes the square root (a negative entry raises the negative-input flag; its NaN never reaches a distance the host hands out)
-__device__ __forceinline__ float prep_unit_transform(int metric, float v, float mu) {
-    if (metric == 4) return v - mu;
+// takes the square root (a negative entry raises the negative-input flag; its NaN never reaches a distance the host hands out).
+// The mean stays in float64 up to the subtraction: rounded to float32 first, a row on a large common offset (1e3 + N(0, 1e-2))
+// would lose half an ulp of the offset, a relative error of 3e-3 in its centred entries.
+__device__ __forceinline__ float prep_unit_transform(int metric, float v, double mu) {
+    if (metric == 4) return (float)((double)v - mu);
     if (metric == 5) return sqrtf(v);
     return v;
 }
@@ -134,11 +136,11 @@ __global__ __launch_bounds__(256) void k_prep_rows(const float *__restrict__ x, 
             if (xh) nr2[row] = make_float2(s, sqrtf(r2) * 1.000001f);
         }
     } else {
-        float mu = 0.0f;
+        double mu = 0.0;
         if (metric == 4) {  // the row mean in float64, as the reference's correlation does: a constant row centres to exact zeros
             double m = 0.0;
             for (int j = lane; j < d; j += 64) m += (double)src[j];
-            mu = (float)(nnd_wave_sum_f64(m) / (double)d);
+            mu = nnd_wave_sum_f64(m) / (double)d;
         }
         float s = 0.0f;
         for (int j = lane; j < d; j += 64) {
@@ -187,7 +189,8 @@ __global__ __launch_bounds__(256) void k_prep_rows_v4(const float *__restrict__ 
     float4 *dst = (float4 *)(xp + (on ? row : row_lo) * dp);
     uint2 *dsth = xh ? (uint2 *)(xh + (on ? row : row_lo) * dp) : nullptr;
     bool bad = false, neg = false;
-    float s = 0.0f, r2 = 0.0f, inv = 1.0f, mu = 0.0f;
+    float s = 0.0f, r2 = 0.0f, inv = 1.0f;
+    double mu = 0.0;
     const bool unit = nnd_metric_unit(metric);
     if (unit) {  // unit rows: the norm first (the row stays in L1 / L2 for the second pass)
         if (metric == 4) {  // correlation: the row mean first, in float64 (see k_prep_rows)
@@ -197,7 +200,7 @@ __global__ __launch_bounds__(256) void k_prep_rows_v4(const float *__restrict__ 
                 m += ((double)v.x + (double)v.y) + ((double)v.z + (double)v.w);
             }
             for (int o = lpr >> 1; o > 0; o >>= 1) m += __shfl_xor(m, o, 64);
-            mu = (float)(m / (double)d);
+            mu = m / (double)d;
         }
         for (int c = jl; c < ncd; c += lpr) {
             float4 v = on ? src[c] : make_float4(0, 0, 0, 0);

@@ -12,6 +12,11 @@
 // The COO/CSR conversions, the transpose, the element-wise maximum and the binarisation between them are
 // scipy calls in the reference (pynndescent_.py:1509-1611) and stay host glue (pynndescent_amd/search_graph.py).
 //
+// The row's own vertex as a comparison point (inner product keeps it at weight 1/|x|^2 > EPS; the csr passes meet it
+// whatever the metric): the reference compares d(x_j, x_i) with the stored d(i, j), the same function on the same operands,
+// bitwise equal there, so the test never prunes at factor 1.  A recomputation here sums in another order than the kernel
+// that stored d(i, j) and would prune at random on a one-ulp difference: every kernel below takes the stored value for it.
+//
 // All three are row-parallel: one wave per row, the row's entries in lanes, pair distances by wave-cooperative
 // dot products over the prepared rows (xp: centred for euclidean -- differences are unchanged -- or
 // L2-normalised for cosine), decisions broadcast with readlane.  The pruning rule is order dependent inside a
@@ -80,7 +85,7 @@ __global__ __launch_bounds__(256) void k_diversify_rows(const float *__restrict_
             const float dc = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_d), c));
             if (dc > PRUNE_EPS) {
                 const int32_t idc = __builtin_amdgcn_readlane(my_idx, c);
-                const float d = prune_pair_dist(xp, dp, nrm, metric, idj, idc);
+                const float d = idc == i ? dj : prune_pair_dist(xp, dp, nrm, metric, idj, idc);  // (the own vertex: see above)
                 if (d < lim && (AWARE || prune_coin(seed, (uint32_t)i, (uint32_t)j, (uint32_t)c, prob))) {  // pynndescent_.py:386-389
                     flag = false;
                     break;
@@ -153,11 +158,9 @@ __global__ __launch_bounds__(256) void k_diversify_csr(const float *__restrict__
                 if (AWARE || wl > PRUNE_EPS) {
                     // AWARE: the point at order[kk]; standard: storage position kk (reference quirk)
                     const int32_t idk = __builtin_amdgcn_readlane(my_idx, AWARE ? l : kk);
-                    // AWARE has no EPS guard: the row's own vertex (weight EPS) is a comparison point and d(x_i, x_j) is
-                    // compared with the stored d(i, j) = wj, the same quantity -- bitwise equal in the reference (same
-                    // function, same operands), so never pruned at factor >= 1.  Use the stored value, not a
-                    // recomputation that may differ by an ulp.
-                    const float d = (AWARE && wl <= PRUNE_EPS) ? wj : prune_pair_dist(xp, dp, nrm, metric, idj, idk);
+                    // the row's own vertex: the stored d(i, j) = wj (see above).  AWARE has no EPS guard, so a weight-EPS
+                    // entry (the own vertex at distance 0) is a comparison point too and takes the same rule.
+                    const float d = (idk == i || (AWARE && wl <= PRUNE_EPS)) ? wj : prune_pair_dist(xp, dp, nrm, metric, idj, idk);
                     if ((AWARE ? d * fj : d) < wj && prune_coin(seed, (uint32_t)i, (uint32_t)j, (uint32_t)kk, prob)) {
                         retained &= ~(1ull << j);
                         break;
@@ -215,7 +218,7 @@ __global__ __launch_bounds__(256) void k_diversify_rows_wide(const float *__rest
         for (int c = 0; c < j; c++) {
             if (!r.kept[c]) continue;
             if (r.w[c] > PRUNE_EPS) {
-                const float d = prune_pair_dist(xp, dp, nrm, metric, idj, r.idx[c]);
+                const float d = r.idx[c] == i ? dj : prune_pair_dist(xp, dp, nrm, metric, idj, r.idx[c]);
                 if (d < lim && (AWARE || prune_coin(seed, (uint32_t)i, (uint32_t)j, (uint32_t)c, prob))) {  // pynndescent_.py:386-389
                     flag = false;
                     break;
@@ -293,7 +296,7 @@ __global__ __launch_bounds__(256) void k_diversify_csr_wide(const float *__restr
             const float wl = r.w[l];
             if (AWARE || wl > PRUNE_EPS) {
                 const int32_t idk = r.idx[AWARE ? l : kk];  // AWARE: the point at order[kk]; standard: storage position kk (reference quirk)
-                const float d = (AWARE && wl <= PRUNE_EPS) ? wj : prune_pair_dist(xp, dp, nrm, metric, idj, idk);
+                const float d = (idk == i || (AWARE && wl <= PRUNE_EPS)) ? wj : prune_pair_dist(xp, dp, nrm, metric, idj, idk);
                 if ((AWARE ? d * fj : d) < wj && prune_coin(seed, (uint32_t)i, (uint32_t)j, (uint32_t)kk, prob)) {
                     if (lane == 0) r.kept[j] = 0;
                     break;

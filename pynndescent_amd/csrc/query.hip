@@ -375,16 +375,16 @@ __global__ __launch_bounds__(256) void k_query(const float *__restrict__ x, cons
             le = -children[2 * node + 1];
         }
         if (metric == 4 || metric == 5) {  // correlation / hellinger: the tree splits the raw rows (angular), the distances the prepared ones
-            float mu = 0.0f;
+            double mu = 0.0;
             if (metric == 4) {
                 double m = 0.0;
                 for (int j = lane; j < d; j += 64) m += (double)qs[j];
-                mu = (float)(nnd_wave_sum_f64(m) / (double)d);
+                mu = nnd_wave_sum_f64(m) / (double)d;
             }
             nnd_wave_lds_sync();
             float p2 = 0.0f;
             for (int j = lane; j < d; j += 64) {
-                const float v = metric == 4 ? qs[j] - mu : sqrtf(qs[j]);
+                const float v = metric == 4 ? (float)((double)qs[j] - mu) : sqrtf(qs[j]);
                 qs[j] = v;
                 p2 += v * v;
             }
@@ -539,15 +539,15 @@ __global__ void k_searcher_prep_rows(float *__restrict__ x, int64_t n, int d, in
     const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= n) return;
     float *row = x + r * dp;
-    float mu = 0.0f;
+    double mu = 0.0;  // (kept in float64 up to the subtraction, as prep.hip prep_unit_transform)
     if (metric == 4) {
         double m = 0.0;
         for (int j = lane; j < d; j += 64) m += (double)row[j];
-        mu = (float)(nnd_wave_sum_f64(m) / (double)d);
+        mu = nnd_wave_sum_f64(m) / (double)d;
     }
     float s = 0.0f;
     for (int j = lane; j < d; j += 64) {
-        const float v = metric == 4 ? row[j] - mu : (metric == 5 ? sqrtf(row[j]) : row[j]);
+        const float v = metric == 4 ? (float)((double)row[j] - mu) : (metric == 5 ? sqrtf(row[j]) : row[j]);
         row[j] = v;
         s += v * v;
     }

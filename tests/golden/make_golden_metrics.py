@@ -4,11 +4,17 @@ Run in the build container only (needs the reference tree, loaded un-jitted thro
 ``make_golden.py`` does):
 
     python tests/golden/make_golden_metrics.py [--only dot ...]
+    python tests/golden/make_golden_metrics.py --search-graph
+
 
 Per metric: the data (tests/metric_util.py metric_data: 2000 x 16 clustered, with zero / constant rows), three builds
 of the reference's ``NNDescent(metric=..., n_neighbors=10)`` -- its ``_neighbor_graph`` and corrected ``neighbor_graph``,
 recall@10 against float64 brute force, the share of rows whose first neighbour is the row itself -- and the answers of
 ``query(k=10)`` for 200 held-out queries after ``prepare()`` on the first build.
+
+``--search-graph`` writes metric_search_graph.npz instead and leaves the other fixtures alone: per metric, the reference's
+search graph after ``prepare()`` on the seed-3 build, its edges mapped back to original ids through ``_vertex_order``
+(``<metric>_rows`` / ``<metric>_cols``, sorted by (row, col)).
 
 ``corrected`` is the reference's own correction applied to the float64 view of the distances: the jitted reference's
 ``numba.vectorize`` corrections return float64; the un-jitted stub would keep float32 under NumPy 2.
@@ -65,6 +71,25 @@ def make(metric):
     print("wrote %s (%.1f KB)" % (path, os.path.getsize(path) / 1024.0))
 
 
+def make_search_graph(metrics):
+    pynndescent = ref_t0.load_reference()
+    out = {}
+    for metric in metrics:
+        t0 = time.time()
+        x, _ = MU.metric_data(metric)
+        index = pynndescent.NNDescent(x, metric=metric, n_neighbors=K, random_state=SEEDS[0])
+        index.prepare()
+        g = index._search_graph.tocoo()
+        order = np.asarray(index._vertex_order)
+        rows, cols = order[g.row].astype(np.int32), order[g.col].astype(np.int32)
+        keep = np.lexsort((cols, rows))
+        out[metric + "_rows"], out[metric + "_cols"] = rows[keep], cols[keep]
+        print("%s search graph: %d edges (%.1f s)" % (metric, rows.size, time.time() - t0))
+    path = os.path.join(HERE, "metric_search_graph.npz")
+    np.savez_compressed(path, **out)
+    print("wrote %s (%.1f KB)" % (path, os.path.getsize(path) / 1024.0))
+
+
 def _normalised(x):
     from sklearn.preprocessing import normalize
 
@@ -74,5 +99,10 @@ def _normalised(x):
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", nargs="*", default=list(MU.NEW_METRICS))
-    for m in ap.parse_args().only:
-        make(m)
+    ap.add_argument("--search-graph", action="store_true")
+    args = ap.parse_args()
+    if args.search_graph:
+        make_search_graph(args.only)
+    else:
+        for m in args.only:
+            make(m)

@@ -3,10 +3,14 @@ import numpy as np
 
 from oracle import oracle as O
 from pynndescent_amd import _capi
+from tests import metric_util as MU
 
 
 def alt_dist_matrix(x, rows_a, rows_b, metric):
-    """float64 alt-space distances (reference distances.py:63-91, 583-630)."""
+    """float64 alt-space distances (reference distances.py:63-91, 583-630; 680, 759, 1284, 1387 through
+    metric_util.alt_dist).  Dot expects the normalised rows the class hands to the build."""
+    if metric in MU.NEW_METRICS:
+        return MU.alt_dist(metric, x[rows_a], x[rows_b])
     a = x[rows_a].astype(np.float64)
     b = x[rows_b].astype(np.float64)
     if metric == "euclidean":
@@ -35,14 +39,63 @@ def make_builder(x, metric="euclidean", k=15, n_trees=8, leaf_size=None, mc=None
     return b
 
 
-def check_graph_invariants(x, metric, idx, dist, tol=2e-4, atol=1e-5, name=""):
-    """rows ascending, ids unique, stored alt distances match the true ones for the stored ids."""
+def self_dist(metric, x):
+    """d(x_i, x_i) as the join kernels store it (nnd_self_dist, reference utils.py:619 evaluates the pair): 0, FLT_MAX for
+    a zero row under dot, 1 / |x|^2 under inner product (FLT_MAX for a zero row)."""
+    x64 = np.asarray(x, np.float64)
+    n2 = (x64 * x64).sum(1)
+    if metric == "inner_product":
+        with np.errstate(divide="ignore"):
+            return np.where(n2 > 0, np.minimum(1.0 / n2, MU.FLT_MAX), MU.FLT_MAX)
+    if metric == "dot":
+        return np.where(n2 > 0, 0.0, MU.FLT_MAX)
+    return np.zeros(x64.shape[0])
+
+
+def tight_atol(d):
+    """the absolute part of the tight bound: 1e-6 at d <= 40 (the pairwise-Gram test's rows), growing with d beyond, as the
+    float32 accumulation error of a Gram value near 1 does (measured on an MI355X: 2.7e-6 at d = 127, 4.2e-6 at d = 256)."""
+    return 1e-6 * max(1.0, d / 40.0)
+
+
+def _check_metric_distances(x, metric, idx, dist, tight, loose, name):
+    """codes 2..5: stored float32 Gram-form distances against float64 truth, per pair: ``tight`` (rtol, atol) where the
+    transformed rows are not near-orthogonal (|cos| >= 0.05), ``loose`` where the similarity cancels -- the two bounds of
+    test_gpu_metrics.test_pairwise_gram_matches_reference_distance.  Self pairs follow ``self_dist``."""
+    n, k = idx.shape
+    valid = idx >= 0
+    nb = np.where(valid, idx, 0)
+    true, cos = MU.alt_dist_pairs(metric, x[:, None, :], x[nb])
+    own = valid & (idx == np.arange(n)[:, None])
+    true = np.where(own, self_dist(metric, x)[:, None], true)
+    big = true >= MU.FLT_MAX
+    assert np.array_equal(dist[valid] >= MU.FLT_MAX, big[valid]), name + ": FLT_MAX convention"
+    m = valid & ~big
+    d64 = dist.astype(np.float64)
+    err = np.abs(d64 - true)
+    good = m & ~(cos < 0.05) & ~own
+    for sel, (rt, at), what in ((good, tight, "well-conditioned"), (m, loose, "all")):
+        bad = sel & (err > rt * np.abs(true) + at)
+        assert not bad.any(), "%s: %s stored distances off at %d pairs, first row %d: got %r want %r" % (
+            name, what, int(bad.sum()), int(np.nonzero(bad)[0][0]), d64[bad][:4], true[bad][:4])
+    if metric != "inner_product":
+        assert np.array_equal(d64[own], true[own]), name + ": self pairs"
+    assert np.all(np.isinf(dist[~valid])), name + ": empty slots must be +inf"
+
+
+def check_graph_invariants(x, metric, idx, dist, tol=2e-4, atol=1e-5, name="", tight=None):
+    """rows ascending, ids unique, stored alt distances match the true ones for the stored ids (codes 2..5: the per-pair
+    bounds of ``_check_metric_distances``, ``tight`` and (tol, atol))."""
     n, k = idx.shape
     d64 = np.where(np.isfinite(dist), dist.astype(np.float64), 1e39)
     assert np.all(np.diff(d64, axis=1) >= 0), name + ": rows not ascending"
     for r in range(n):
         v = idx[r][idx[r] >= 0]
         assert len(v) == len(np.unique(v)), "%s: duplicate ids in row %d: %s" % (name, r, idx[r])
+    if metric in MU.NEW_METRICS:
+        tight = (1e-5, tight_atol(x.shape[1])) if tight is None else tight
+        _check_metric_distances(x, metric, idx, dist, tight, (tol, atol), name)
+        return
     rows = np.arange(n)
     valid = idx >= 0
     xi = x.astype(np.float64)

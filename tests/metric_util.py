@@ -51,6 +51,48 @@ def alt_dist(metric, a, b):
     raise ValueError(metric)
 
 
+def transformed(metric, a):
+    """float64 rows whose plain inner product the Gram kernels take: centred for correlation, square roots for hellinger
+    (dot's normalisation is the caller's: the rows come in as NNDescent hands them over)."""
+    a = np.asarray(a, np.float64)
+    if metric == "correlation":
+        return a - a.mean(-1, keepdims=True)
+    if metric == "hellinger":
+        return np.sqrt(a)
+    return a
+
+
+def abs_cos(metric, a, b):
+    """|cos| of every (a, b) pair in the metric's transformed space (nan for a zero row): where it is small, the float32
+    Gram value cancels and a stored distance carries a larger relative error."""
+    ta, tb = transformed(metric, a), transformed(metric, b)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.abs(ta @ tb.T) / np.outer(np.linalg.norm(ta, axis=1), np.linalg.norm(tb, axis=1))
+
+
+def alt_dist_pairs(metric, a, b):
+    """alt_dist of the pairs (a[i], b[i]) for any leading shape: (..., d) x (..., d) -> (...) float64, and their |cos|."""
+    a = np.asarray(a, np.float64)
+    b = np.asarray(b, np.float64)
+    ta, tb = transformed(metric, a), transformed(metric, b)
+    g = (ta * tb).sum(-1)
+    na, nb = (ta * ta).sum(-1), (tb * tb).sum(-1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        cos = np.abs(g) / np.sqrt(na * nb)
+        if metric in ("dot", "inner_product"):
+            r = -np.log2(g) if metric == "dot" else 1.0 / g
+            return np.where(g <= 0.0, FLT_MAX, r), cos
+        if metric == "correlation":
+            r = np.where(g == 0.0, 1.0, 1.0 - g / np.sqrt(na * nb))
+            return np.where((na == 0.0) & (nb == 0.0), 0.0, r), cos
+        if metric == "hellinger":
+            la, lb = a.sum(-1), b.sum(-1)
+            r = np.log2(np.sqrt(la * lb) / g)
+            one = (la == 0.0) | (lb == 0.0) | (g <= 0.0)
+            return np.where((la == 0.0) & (lb == 0.0), 0.0, np.where(one, FLT_MAX, r)), cos
+    raise ValueError(metric)
+
+
 def correct(metric, d):
     """The reference's correction of alt-space distances (float64)."""
     d = np.asarray(d, np.float64)

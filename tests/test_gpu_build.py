@@ -477,7 +477,7 @@ def test_nn_descent_function_with_reference_leaf_array(metric, dist):
     n, d, k = 20000, 32, 15
     x = clustered(n, d, 8, 60, seed=21)
     rng_state, _, ts = O.draw_rng_states(11, 6)
-    la = O.make_leaf_array(x, 6, O.default_leaf_size(k), ts, metric == "cosine")
+    la = O.make_leaf_array(x, 6, O.default_leaf_size(k), ts, O.ANGULAR[metric])
     n_iters = O.default_n_iters(n)
     gi, gd = pynndescent_amd.nn_descent(x, k, rng_state, max_candidates=k, dist=dist, n_iters=n_iters, delta=0.001,
                                         rp_tree_init=True, leaf_array=la)

@@ -46,7 +46,7 @@ def test_forest_partitions(metric, n, d, k, T):
     assert np.all((la >= 0) == (np.arange(ls)[None, :] < lens[:, None]))
     # same leaf statistics as the reference algorithm (oracle): mean fill within 15 %
     _, _, ts = O.draw_rng_states(1, T)
-    ola = O.make_leaf_array(x, T, ls, ts, metric == "cosine")
+    ola = O.make_leaf_array(x, T, ls, ts, O.ANGULAR[metric])
     ofill = (ola >= 0).sum(1).mean()
     assert abs(lens.mean() - ofill) <= 0.15 * ofill, (lens.mean(), ofill)
     # and the same locality: fraction of true 5-NN that share a leaf with their point
@@ -386,7 +386,7 @@ def test_forest_routing_pass(metric, n, d, k, T):
     for row, m in zip(la[::97], lens[::97]):
         assert np.all(np.diff(row[:m]) > 0)
     _, _, ts = O.draw_rng_states(1, T)
-    ola = O.make_leaf_array(x, T, ls, ts, metric == "cosine")
+    ola = O.make_leaf_array(x, T, ls, ts, O.ANGULAR[metric])
     ofill = (ola >= 0).sum(1).mean()
     assert abs(lens.mean() - ofill) <= 0.15 * ofill, (lens.mean(), ofill)
     # locality: fraction of true 5-NN of a sample of points that share a leaf with their point, vs the oracle's forest
@@ -540,7 +540,7 @@ def test_leaf_array_seam_matches_reference_init_rp_tree(metric, n, d, k, T):
     the reference's init_rp_tree leaves in its heaps on the SAME leaves -- compared exactly, row by row, as sets."""
     x = clustered(n, d, 6, 25, seed=n + k)
     _, _, ts = O.draw_rng_states(5, T)
-    la = O.make_leaf_array(x, T, O.default_leaf_size(k), ts, metric == "cosine")
+    la = O.make_leaf_array(x, T, O.default_leaf_size(k), ts, O.ANGULAR[metric])
     b = make_builder(x, metric, k=k, n_trees=0)  # no forest of its own
     b.init_from_leaf_array(la)
     idx, dist, flags = b.graph()
@@ -581,7 +581,7 @@ def test_leaf_init_recall_gpu_forest_vs_reference_forest(metric):
     b.init_from_leaves()
     g_idx, _, _ = b.graph()
     _, _, ts = O.draw_rng_states(1, T)
-    la = O.make_leaf_array(x, T, O.default_leaf_size(k), ts, metric == "cosine")
+    la = O.make_leaf_array(x, T, O.default_leaf_size(k), ts, O.ANGULAR[metric])
     b.reset_graph()
     b.init_from_leaf_array(la)
     o_idx, _, _ = b.graph()

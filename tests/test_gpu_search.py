@@ -60,7 +60,7 @@ def test_hub_tree_matches_oracle_at_size(metric, n, d, leaf):
     index = NNDescent(x, metric, n_neighbors=15, random_state=3)
     nbr = index._neighbor_graph[0]
     tree = make_hub_tree(x, nbr, metric, leaf_size=leaf, max_depth=200)
-    oh, oo, oc, oi, ol = O.make_hub_tree(x, nbr, index.rng_state, leaf, metric == "cosine", 200)
+    oh, oo, oc, oi, ol = O.make_hub_tree(x, nbr, index.rng_state, leaf, O.ANGULAR[metric], 200)
     assert tree.children.shape == oc.shape, (tree.children.shape, oc.shape)
     same_nodes = (tree.children == oc).all(1).mean()
     same_idx = (tree.indices == oi).mean()

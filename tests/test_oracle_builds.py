@@ -260,7 +260,7 @@ def test_hub_tree_matches_reference(golden_dir, metric):
     g = _g(golden_dir, "hub_tree")
     n, d, latent, ncl, seed = (int(v) for v in g[metric + "_gen"])
     x = clustered(n, d, latent, ncl, seed)
-    hyper, offs, children, indices, leaf = O.make_hub_tree(x, g[metric + "_idx"], g[metric + "_rng"], 30, metric == "cosine", 200)
+    hyper, offs, children, indices, leaf = O.make_hub_tree(x, g[metric + "_idx"], g[metric + "_rng"], 30, O.ANGULAR[metric], 200)
     np.testing.assert_array_equal(children, g[metric + "_children"])
     np.testing.assert_array_equal(indices, g[metric + "_indices"])
     assert leaf == int(g[metric + "_leaf_size"])
