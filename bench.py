@@ -1,6 +1,6 @@
 """bench.py -- index-build throughput of the MI355X NN-Descent builder (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 One "step" = one complete index build (prep -> RP forest -> leaf seeding -> random fill ->
 NN-descent to the reference's stop rule -> exact-distance finalize) over a synthetic point set that
@@ -15,9 +15,17 @@ Every N > 1 builds BASELINE configs[3] -- ONE 10 M x 128 set row-sharded over th
 "scaling": "strong", so that the curve over N = 2, 4, 8 is over the same work (`one_gpu_same_set` gives its one-GPU time);
 --points-per-gpu P selects weak scaling instead (P points per GPU, one global index of N * P points).
 
-Rank 0 prints ONE JSON line (contract in the task statement) carrying, besides the metric:
+Rank 0 prints ONE JSON line (contract in the task statement).  A plain run does only what the headline figure needs: set
+up, warm up, time the K steps, write --dump-outputs, print the line.  Besides the metric the line always carries what the
+timed steps report themselves (stage times, counts, iterations, the sharded build's exchange figures) and
   roofline             : dominant kernel's algorithmic HBM bytes / its HIP-event duration vs 8 TB/s, plus
                          roofline.mfma: MFMA flops issued (counted by the kernels) vs the f32 matrix peak
+  roofline.build       : whole-build algorithmic bytes (SURVEY 8d model with the measured counts) / wall time vs 8 TB/s
+--full adds everything that needs work of its own after the timed steps (null in a plain line); --no-cpu-baseline,
+--no-extras and --no-one-gpu leave parts of it out:
+  recall_at_10         : recall vs exact brute force on a sample of points (reference-test convention), with
+                         recall_at_10_strict_first10 and max_rel_dist_err
+  one_gpu_same_set     : N > 1: the same set built by one GPU (rank 0), and `speedup` over it
   cpu_baseline         : the CPU oracle (restatement of the reference algorithm, oracle/) timed on this
                          box's host cores on the same 1 M points
   value_host_inclusive : the same build through nnd_build (host buffers in, host buffers out: H2D + build + D2H)
@@ -26,8 +34,6 @@ Rank 0 prints ONE JSON line (contract in the task statement) carrying, besides t
   value_class_api      : wall time of the drop-in call itself, pynndescent_amd.NNDescent(x, ...).neighbor_graph (SURVEY 8d's metric)
   workload_k30         : the same points with the reference's default n_neighbors = 30 (+ oracle_recall_at_10, as above)
   workload_c3 / _c5    : BASELINE configs[2] / configs[4] stand-ins (+ oracle_recall_at_10; _c5: + the graph diversification / prune pass)
-  roofline.build       : whole-build algorithmic bytes (SURVEY 8d model with the measured counts) / wall time vs 8 TB/s
-  recall_at_10         : recall vs exact brute force on a sample of points (reference-test convention)
 
 --data FILE (.fvecs / .npy / .hdf5 with a "train" dataset): build THAT point set instead of the synthetic one (real SIFT-1M /
 GloVe / NYTimes when a file is on disk; there is none in this image), N = 1 only.
@@ -447,7 +453,7 @@ class Watchdog:
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--no-one-gpu", action="store_true", help="N > 1: skip the one-GPU build of the same set (one_gpu_same_set / speedup)")
+    ap.add_argument("--no-one-gpu", action="store_true", help="--full, N > 1: skip the one-GPU build of the same set (one_gpu_same_set / speedup)")
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--points-per-gpu", dest="n", type=int, default=None)
@@ -456,8 +462,12 @@ def main():
     ap.add_argument("--n-trees", type=int, default=None)
     ap.add_argument("--join-blocks", type=int, default=0, help="0 (default): the library's schedule, as the drop-in class runs it")
     ap.add_argument("--latent", type=int, default=16, help="latent dimension of the synthetic mixture (48 = the hard workload)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip value_host_inclusive, value_class_api, workload_hard, workload_k30")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed builds, also measure and check what needs work of its own: recall, the one-GPU build "
+                         "of the same set, the CPU baseline and the other workloads (module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline and the oracle legs")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="--full: skip value_host_inclusive, value_class_api, workload_hard, workload_k30, workload_c3, workload_c5")
     ap.add_argument("--data", default=None, help="build this point set (.fvecs / .npy / .hdf5 'train') instead of the synthetic one")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed builds, write the last one's neighbour graph (rank 0's rows) to DIR/*.npy")
@@ -635,7 +645,7 @@ def run(args, world, rank, local_rank, share_gpu, wd):
         n_join_launches += sum(st.get("join_substeps") or [args.join_blocks or 1] * st["n_iters_run"])
     barrier()
     elapsed = time.perf_counter() - t0
-    phase("recall / one-GPU build of the same set / extras", 1500)
+    phase("recall / one-GPU build of the same set / extras" if args.full else "result line", 1500)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
@@ -646,10 +656,10 @@ def run(args, world, rank, local_rank, share_gpu, wd):
     if args.dump_outputs is not None and rank == 0:  # outside the timed region, before the extras reuse the output buffers
         dumped = dump_outputs(args.dump_outputs, out_idx, out_dist)
 
-    # recall vs exact brute force on a sample of this rank's rows (outside the timed region)
-    x_all = gather_rows(x, world) if world > 1 else x
+    # --full: recall vs exact brute force on a sample of this rank's rows (outside the timed region)
+    x_all = gather_rows(x, world) if world > 1 and args.full else x
     one_gpu = None
-    if world > 1 and rank == 0 and not args.no_one_gpu:
+    if args.full and world > 1 and rank == 0 and not args.no_one_gpu:
         # the SAME set on one GPU (rank 0, outside the timed region): what the N-GPU time is a speed-up OVER
         b1 = _capi.Builder(n_total, d, _capi.NND_METRIC_SQEUCLIDEAN, k, n_trees, leaf_size, 200, min(60, k), n_iters, 0.001, rng_state,
                            tree_states[0], device=local_rank)
@@ -671,15 +681,17 @@ def run(args, world, rank, local_rank, share_gpu, wd):
         b1.close()
         del o1i, o1d
     if rank == 0:
-        rsmp = np.random.RandomState(0)
-        rows_np = rsmp.choice(n, size=min(2000, n), replace=False)
-        rows = torch.from_numpy(rows_np).to(device)  # rank 0 owns rows [0, n)
-        true_idx = exact_knn_sample(x_all, rows, 10)
-        rec_all = recall_at(true_idx, out_idx[rows], 10)
-        rec_strict = recall_at(true_idx, out_idx[rows], 10, cols=10)
-        nb = x_all[out_idx[rows].long()].double()
-        truth = ((x_all[rows].double()[:, None, :] - nb) ** 2).sum(-1)
-        rel = ((out_dist[rows].double() - truth).abs() / truth.clamp_min(1e-30))[truth > 0].max().item()
+        rec_all = rec_strict = rel = None
+        if args.full:
+            rsmp = np.random.RandomState(0)
+            rows_np = rsmp.choice(n, size=min(2000, n), replace=False)
+            rows = torch.from_numpy(rows_np).to(device)  # rank 0 owns rows [0, n)
+            true_idx = exact_knn_sample(x_all, rows, 10)
+            rec_all = recall_at(true_idx, out_idx[rows], 10)
+            rec_strict = recall_at(true_idx, out_idx[rows], 10, cols=10)
+            nb = x_all[out_idx[rows].long()].double()
+            truth = ((x_all[rows].double()[:, None, :] - nb) ** 2).sum(-1)
+            rel = ((out_dist[rows].double() - truth).abs() / truth.clamp_min(1e-30))[truth > 0].max().item()
 
         # roofline of the dominant kernel (by measured time).  Algorithmic bytes:
         #   k_local_join : C_i gathered candidate rows * dp*4 bytes per launch
@@ -753,7 +765,7 @@ def run(args, world, rank, local_rank, share_gpu, wd):
                                               "iters": round(b_iter / 1e9, 2), "final": round(b_final / 1e9, 2)}}
 
         cpu = host_incl = hard = cls_api = k30 = c3 = c5 = hard_leg = None
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             x_host = x.cpu().numpy()
             host_incl = host_inclusive(_capi, x_host, k, n_trees, leaf_size, n_iters, rng_state, tree_states[0], local_rank)
             cls_api = class_api(x_host, k, n_trees, local_rank)
@@ -815,7 +827,7 @@ def run(args, world, rank, local_rank, share_gpu, wd):
                                      "join": round(sum(sth["ms_join"]), 3), "sample": round(sum(sth["ms_sample"]), 3),
                                      "merge": round(sum(sth["ms_merge"]), 3), "finalize": round(sth["ms_finalize"], 3)}}
                 del xh
-        if world == 1 and not args.no_extras and args.latent == 16 and args.data is None:
+        if args.full and world == 1 and not args.no_extras and args.latent == 16 and args.data is None:
             builder.close()  # (its HBM is not needed any more; the other configurations get the GPU to themselves)
             _capi.load_library().nnd_release_pending()
             orc = None
@@ -824,7 +836,7 @@ def run(args, world, rank, local_rank, share_gpu, wd):
             othr = min(os.cpu_count() or 1, 256)
             c3 = other_config(_capi, "c3", device, local_rank, orc, othr)
             c5 = other_config(_capi, "c5", device, local_rank, orc, othr)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             from oracle import oracle as O  # test infrastructure: the cpu_baseline leg only
 
             x_np = x.cpu().numpy()
@@ -859,6 +871,7 @@ def run(args, world, rank, local_rank, share_gpu, wd):
             "vs_baseline": None,
             "dtype": "f32",
             "data": "synthetic" if data_name is None else "file:" + data_name,
+            "full": args.full,
             "config": {"workload": workload,
                        "parallelism": "1 GPU" if world == 1 else
                        "rows sharded over %d GPUs (one global index of %d points): point set all-gathered once (second channel, "
@@ -869,9 +882,9 @@ def run(args, world, rank, local_rank, share_gpu, wd):
                           {"rccl": "RCCL", "host": "HOST-staged over gloo (debug: two processes sharing one GPU)"}.get(comm.transport, comm.transport)),
                        "comm": None if world == 1 else comm.info(),
                        "join_blocks": args.join_blocks, "join_substeps_last_step": last.get("join_substeps")},
-            "recall_at_10": round(rec_all, 4),
-            "recall_at_10_strict_first10": round(rec_strict, 4),
-            "max_rel_dist_err": float("%.3g" % rel),
+            "recall_at_10": None if rec_all is None else round(rec_all, 4),
+            "recall_at_10_strict_first10": None if rec_strict is None else round(rec_strict, 4),
+            "max_rel_dist_err": None if rel is None else float("%.3g" % rel),
             "iters": last["n_iters_run"],
             "stage_ms_per_step": {sname: round(v / steps, 3) for sname, v in stage.items()},
             "last_step_iter_ms": {"sample": [round(v, 3) for v in last["ms_sample"]],

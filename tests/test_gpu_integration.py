@@ -93,7 +93,7 @@ def test_bench_two_processes_sharing_one_gpu():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--points-per-gpu", "60000",
-                          "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-extras"],
+                          "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extras"],
                          env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]
@@ -103,18 +103,35 @@ def test_bench_two_processes_sharing_one_gpu():
     assert sum(rec["exchanged_records_rank0"]) > 0
 
 
+def test_bench_plain_run_does_only_the_timed_builds():
+    """A plain `python bench.py --gpus 1` sets up, warms up, times its builds and prints the line: what needs work of its
+    own after the timed builds (recall, CPU baseline, the other workloads and figures) waits for --full and is null."""
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "PYNND_BENCH_SHARE_GPU"):
+        env.pop(k, None)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--points-per-gpu", "60000",
+                          "--steps", "2", "--warmup", "1"], env=env, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    rec = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+    assert rec["full"] is False and rec["n_gpus"] == 1 and rec["steps"] == 2 and rec["warmup"] == 1
+    assert rec["value"] > 0 and rec["ms_per_step"] > 0 and rec["iters"] > 0
+    for key in ("recall_at_10", "max_rel_dist_err", "one_gpu_same_set", "cpu_baseline", "value_host_inclusive",
+                "value_class_api", "workload_hard", "workload_k30", "workload_c3", "workload_c5"):
+        assert rec[key] is None, key
+
+
 def test_bench_four_processes_rehearsal_of_the_drivers_scaling_run():
     """What the driver runs for SCALE at N > 2 -- `bench.py --gpus N`, N processes, torch.distributed rendezvous, the
     by-cell forest, every exchange of the sharded build, the watchdog armed -- rehearsed on this one-GPU box: all ranks on
     GPU 0, the HOST transport over gloo (two RCCL ranks cannot share a GPU).  Four ranks: with this test process they are
     five processes holding the one GPU (the launching bench.py process does not open it when the GPU is shared).
     600 k points per rank, 2.4 M in all (the configs[3] run is 10 M; the eight thread-ranks of tests/test_gpu_sharded.py
-    cover eight ranks at that size in one process)."""
+    cover eight ranks at that size in one process).  With --full, so that the line carries recall as well."""
     env = dict(os.environ, PYNND_BENCH_SHARE_GPU="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--points-per-gpu", "600000", "--n-trees", "8",
-                          "--steps", "1", "--warmup", "1", "--no-one-gpu"], env=env, capture_output=True, text=True, timeout=900)
+                          "--steps", "1", "--warmup", "1", "--full", "--no-one-gpu"], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-2500:])
     rec = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
     assert "error" not in rec, rec

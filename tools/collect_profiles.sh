@@ -7,7 +7,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-( cd $R && timeout 600 python bench.py --steps 5 --warmup 2 > $O/${tag}_bench_1m.json.log 2>&1 )
+( cd $R && timeout 600 python bench.py --full --steps 5 --warmup 2 > $O/${tag}_bench_1m.json.log 2>&1 )
 rm -rf /tmp/p_tr /tmp/p_fe /tmp/p_wr /tmp/p_sq
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_tr -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras > /tmp/p_tr.log 2>&1
 python $R/tools/prof_summary.py /tmp/p_tr $O/${tag}_kernel_stats_bench1m.txt

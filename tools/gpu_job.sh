@@ -1,7 +1,7 @@
 #!/bin/bash
 # One parameterised GPU-box script (replaces the per-call gpu_r03?.sh files):  tools/gpu_job.sh <tag> <job> [<job> ...]
 # Every job writes gpurun_out/<tag>_<job>.log (and summaries next to it).  Jobs:
-#   tests[:expr]   pytest -m gpu (optionally -k expr)         bench[:args]   bench.py with args (default --steps 5 --warmup 2)
+#   tests[:expr]   pytest -m gpu (optionally -k expr)         bench[:args]   bench.py --full with args (default --steps 5 --warmup 2)
 #   trace          rocprofv3 kernel trace of a short bench    pmc            FETCH / WRITE / SQ counter passes (tools/collect_profiles.sh)
 #   critpath:G:N:T rank critical path, G ranks, N points, T trees          k30trace        kernel trace of the k = 30 workload
 #   onetree        kernel trace of one tree over 10 M points  py:<file>[:args]  python <file> args
@@ -16,7 +16,7 @@ for job in "$@"; do
       ( cd $R && timeout 1500 python -m pytest tests -m gpu -q -rP --maxfail=10 --durations=10 -p no:cacheprovider ${arg:+-k "$arg"} > $log 2>&1; echo "pytest rc=$?" >> $log )
       grep -c PASSED $log; tail -n 25 $log | cut -c1-200 ;;
     bench)
-      ( cd $R && timeout 900 python bench.py ${arg:---steps 5 --warmup 2} > $log 2>&1; echo "bench rc=$?" >> $log )
+      ( cd $R && timeout 900 python bench.py --full ${arg:---steps 5 --warmup 2} > $log 2>&1; echo "bench rc=$?" >> $log )
       tail -c 2500 $log ;;
     trace)
       rm -rf /tmp/p_tr; ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_tr -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras > $log 2>&1 )
