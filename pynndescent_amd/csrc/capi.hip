@@ -251,8 +251,8 @@ int nnd_create_impl(nnd_handle_t *out, const nnd_params *p, const int64_t *bound
         }
         if ((rc = dalloc(ctx, &ctx->counters, (size_t)CNT_COUNT * NND_CNT_STRIPES))) break;
         if ((rc = dalloc(ctx, &ctx->counters_sum, (size_t)CNT_COUNT))) break;
-        if (hipHostMalloc((void **)&ctx->h_pin, sizeof(long long) * 64, hipHostMallocDefault) != hipSuccess) { ctx->set_error("hipHostMalloc failed"); rc = 1; break; }
-        memset(ctx->h_pin, 0, sizeof(long long) * 64);
+        if (hipHostMalloc((void **)&ctx->h_pin, sizeof(nnd_pin_words), hipHostMallocDefault) != hipSuccess) { ctx->set_error("hipHostMalloc failed"); rc = 1; break; }
+        memset(ctx->h_pin, 0, sizeof(nnd_pin_words));
         if (hipHostGetDevicePointer((void **)&ctx->h_pin_dev, ctx->h_pin, 0) != hipSuccess) { (void)hipGetLastError(); ctx->h_pin_dev = nullptr; }
         if (p->n_trees > 0) {
             ctx->P = (int64_t)p->n_trees * ctx->n;
@@ -287,12 +287,12 @@ int nnd_create_impl(nnd_handle_t *out, const nnd_params *p, const int64_t *bound
                 if ((rc = dalloc(ctx, &ctx->node_child, (size_t)ctx->node_cap * 2))) break;
                 if ((rc = dalloc(ctx, &ctx->node_pack, (size_t)ctx->node_cap * (2 * ctx->dp + 16)))) break;
                 if ((rc = dalloc(ctx, &ctx->node_hfc, (size_t)ctx->node_cap * (ctx->dp + 4)))) break;
-                if ((rc = dalloc(ctx, &ctx->route_roots, (size_t)4096))) break;
+                if ((rc = dalloc(ctx, &ctx->route_roots, (size_t)NND_ROUTE_ROOTS_WORDS))) break;
                 if ((rc = dalloc(ctx, &ctx->s_leaf_depth, (size_t)Ps))) break;
                 if ((rc = dalloc(ctx, &ctx->cell_count, (size_t)ctx->cell_cap))) break;
                 if ((rc = dalloc(ctx, &ctx->cell_start, (size_t)ctx->cell_cap))) break;
                 if ((rc = dalloc(ctx, &ctx->cell_depth, (size_t)ctx->cell_cap))) break;
-                if ((rc = dalloc(ctx, &ctx->small_list, (size_t)ctx->cell_cap * 3))) break;
+                if ((rc = dalloc(ctx, &ctx->small_list, (size_t)ctx->cell_cap * NND_WORK_LIST_ROWS))) break;
             }
             const size_t S = (size_t)ctx->max_segs;
             for (int i = 0; i < 2 && !rc; i++) {
@@ -309,7 +309,7 @@ int nnd_create_impl(nnd_handle_t *out, const nnd_params *p, const int64_t *bound
             if ((rc = dalloc(ctx, &ctx->scan_out, P + 1))) break;
             if ((rc = dalloc(ctx, &ctx->scan_blk, P / 2048 + 2))) break;
             if ((rc = dalloc(ctx, &ctx->seg_nleft, S))) break;
-            if ((rc = dalloc(ctx, &ctx->seg_child, 5 * S))) break;  // child ids (2S) + finisher work list (3S)
+            if ((rc = dalloc(ctx, &ctx->seg_child, (NND_SEG_CHILD_WORDS + NND_WORK_LIST_ROWS) * S))) break;  // child ids + finisher work list (nnd_fin_list)
             if ((rc = dalloc(ctx, &ctx->hyper, S * (size_t)(ctx->dp + 4)))) break;
             if ((rc = dalloc(ctx, &ctx->hyper_h, S * (size_t)ctx->dp))) break;
             // (sized for any tree count: a shard finishes cells of ALL the build's trees, whatever its own allocation)
@@ -539,7 +539,7 @@ extern "C" int32_t nnd_data_nonfinite(nnd_handle_t ctx, int32_t *out) {
     if (need_data(ctx)) return 1;
     if (ctx->p.flags & NND_FLAG_NO_PREP) { *out = 0; return 0; }
     API_HIP(nnd_sync_spin(ctx));
-    *out = (ctx->h_pin[63] & 1) != 0 ? 1 : 0;
+    *out = (ctx->h_pin->data_flags & 1) != 0 ? 1 : 0;
     return 0;
 }
 // 1 when a hellinger point set held a negative entry (bit 1 of the prep kernel's flag word; bit 0 is the non-finite flag)
@@ -548,7 +548,7 @@ extern "C" int32_t nnd_data_negative(nnd_handle_t ctx, int32_t *out) {
     if (need_data(ctx)) return 1;
     if (ctx->p.flags & NND_FLAG_NO_PREP) { *out = 0; return 0; }
     API_HIP(nnd_sync_spin(ctx));
-    *out = (ctx->h_pin[63] & 2) != 0 ? 1 : 0;
+    *out = (ctx->h_pin->data_flags & 2) != 0 ? 1 : 0;
     return 0;
 }
 

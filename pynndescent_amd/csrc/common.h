@@ -240,11 +240,13 @@ __device__ __forceinline__ int nnd_owner_of(const int64_t *__restrict__ bounds, 
 }
 
 
-#define NND_HIP_CHECK(expr)                                                                         \
+// (text: the expression as written; ret: what the enclosing function returns for an error)
+#define NND_HIP_CHECK_AS(expr, text, ret)                                                           \
     do {                                                                                            \
         hipError_t _e = (expr);                                                                     \
         if (_e != hipSuccess) {                                                                     \
-            ctx->set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-            return 1;                                                                               \
+            ctx->set_error("%s failed: %s (%s:%d)", text, hipGetErrorString(_e), __FILE__, __LINE__); \
+            return ret;                                                                             \
         }                                                                                           \
     } while (0)
+#define NND_HIP_CHECK(expr) NND_HIP_CHECK_AS(expr, #expr, 1)

@@ -298,7 +298,7 @@ double *nnd_prep_partial_buffer(nnd_ctx *ctx, size_t doubles) {
 int nnd_prep_rows(nnd_ctx *ctx, const float *x_all, int64_t row_lo, int64_t row_hi, bool first) {
     const int d = ctx->d, dp = ctx->dp;
     const int64_t rows = row_hi - row_lo;
-    long long *flag = ctx->counters_sum + CNT_SCRATCH;  // a spare word of the reduced-counter block
+    long long *flag = ctx->counters_sum + CNT_PREP_FLAG;  // a spare word of the reduced-counter block
     if (first) NND_HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(long long), ctx->stream));
     if (rows <= 0) return 0;
     if ((d & 3) == 0 && ((uintptr_t)x_all & 15) == 0) {
@@ -328,8 +328,8 @@ int nnd_launch_prep(nnd_ctx *ctx) {
     }
     if (nnd_prep_mean_finish(ctx, partial, nblocks, n_s)) return 1;
     if (nnd_prep_rows(ctx, ctx->x_orig, 0, n, true)) return 1;
-    long long *flag = ctx->counters_sum + CNT_SCRATCH;
-    NND_HIP_CHECK(hipMemcpyAsync(ctx->h_pin + 63, flag, sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));  // read by nnd_data_nonfinite
+    long long *flag = ctx->counters_sum + CNT_PREP_FLAG;
+    NND_HIP_CHECK(hipMemcpyAsync(&ctx->h_pin->data_flags, flag, sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));  // read by nnd_data_nonfinite
     return 0;
 }
 
@@ -387,8 +387,8 @@ __global__ __launch_bounds__(256) void k_counters_reduce(const long long *__rest
 int nnd_read_counters(nnd_ctx *ctx) {
     hipLaunchKernelGGL(k_counters_reduce, dim3(1), dim3(256), 0, ctx->stream, ctx->counters, ctx->counters_sum);
     NND_HIP_CHECK(hipGetLastError());
-    NND_HIP_CHECK(hipMemcpyAsync(ctx->h_pin, ctx->counters_sum, sizeof(long long) * CNT_COUNT, hipMemcpyDeviceToHost, ctx->stream));
+    NND_HIP_CHECK(hipMemcpyAsync(ctx->h_pin->counters, ctx->counters_sum, sizeof(long long) * CNT_COUNT, hipMemcpyDeviceToHost, ctx->stream));
     NND_HIP_CHECK(nnd_sync_spin(ctx));
-    for (int c = 0; c < CNT_COUNT; c++) ctx->h_counters[c] = ctx->h_pin[c];
+    for (int c = 0; c < CNT_COUNT; c++) ctx->h_counters[c] = ctx->h_pin->counters[c];
     return 0;
 }

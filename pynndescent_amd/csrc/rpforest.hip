@@ -493,7 +493,7 @@ __global__ __launch_bounds__(256) void k_children(const int32_t *__restrict__ se
                                                   long long seq) {
     // host_words (optional): pinned HOST memory.  The host needs this level's segment count before it can launch the next
     // level; instead of a device-to-host copy behind the scatter kernel and a stream synchronisation (the GPU then idles
-    // for a launch latency per level), this workgroup writes the six words itself and raises a sequence number: the host,
+    // for a launch latency per level), this workgroup writes the six words (nnd_level_words) itself and raises a sequence number: the host,
     // spinning on it, queues the next level WHILE the scatter kernel runs.
     // node_child != nullptr (sample forest, see nnd_launch_forest): the tree itself is recorded -- node (node_base + s)
     // gets its two children: >= 0 the child's node id (next_base + its index in the next level; node_top - its index in
@@ -503,8 +503,8 @@ __global__ __launch_bounds__(256) void k_children(const int32_t *__restrict__ se
     // k_finish_subtrees (len <= fin_max: its whole subtree fits in one workgroup's LDS)
     __shared__ int part[256], partf[256];
     if (threadIdx.x == 0) {  // this launch's accumulators (single workgroup: ordered by the barrier below)
-        atomicExch((unsigned long long *)&counters[CNT_LEAVES], 0ull);  // atomics: ordered with the atomicAdd / atomicMax below at L2
-        atomicExch((unsigned long long *)&counters[CNT_SCRATCH + 3], 0ull);
+        atomicExch((unsigned long long *)&counters[CNT_ACTIVE_POS], 0ull);  // atomics: ordered with the atomicAdd / atomicMax below at L2
+        atomicExch((unsigned long long *)&counters[CNT_MAX_STAY], 0ull);
     }
     int chunk = (n_segs + 255) / 256;
     int s0 = threadIdx.x * chunk, s1 = s0 + chunk < n_segs ? s0 + chunk : n_segs;
@@ -524,13 +524,13 @@ __global__ __launch_bounds__(256) void k_children(const int32_t *__restrict__ se
     partf[threadIdx.x] = cntf;
     __syncthreads();
     if (threadIdx.x == 0) {
-        int run = 0, runf = (int)counters[CNT_SCRATCH + 1];  // finisher list grows across levels
+        int run = 0, runf = (int)counters[CNT_FIN_COUNT];  // finisher list grows across levels
         for (int i = 0; i < 256; i++) {
             int v = part[i]; part[i] = run; run += v;
             int vf = partf[i]; partf[i] = runf; runf += vf;
         }
         counters[CNT_ACTIVE_SEGS] = run;
-        counters[CNT_SCRATCH + 1] = runf;
+        counters[CNT_FIN_COUNT] = runf;
     }
     __syncthreads();
     int run = part[threadIdx.x], runf = partf[threadIdx.x];
@@ -569,16 +569,16 @@ __global__ __launch_bounds__(256) void k_children(const int32_t *__restrict__ se
             }
         }
     }
-    if (active_pos) atomicAdd((unsigned long long *)&counters[CNT_LEAVES], (unsigned long long)active_pos);  // positions still in the passes
-    if (max_stay) atomicMax((unsigned long long *)&counters[CNT_SCRATCH + 3], (unsigned long long)max_stay);  // longest of them
+    if (active_pos) atomicAdd((unsigned long long *)&counters[CNT_ACTIVE_POS], (unsigned long long)active_pos);  // positions still in the passes
+    if (max_stay) atomicMax((unsigned long long *)&counters[CNT_MAX_STAY], (unsigned long long)max_stay);  // longest of them
     if (host_words) {
         __syncthreads();  // (with its release / acquire fences: every thread's atomics above have been performed)
         if (threadIdx.x == 0) {
 #pragma unroll
-            for (int q = 0; q < 6; q++)
+            for (int q = 0; q < NND_LEVEL_WORDS; q++)  // nnd_level_flag (state.h): the words, then the sequence number
                 host_words[q] = __hip_atomic_load(&counters[CNT_ACTIVE_SEGS + q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __threadfence_system();
-            __hip_atomic_store(&host_words[6], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(&host_words[NND_LEVEL_WORDS], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
 }
@@ -1731,7 +1731,7 @@ __global__ void k_cell_lists(const int32_t *__restrict__ cell_count, const int32
                              int32_t *__restrict__ small_list, int32_t *__restrict__ fin_start, int32_t *__restrict__ fin_len,
                              int32_t *__restrict__ fin_depth, int32_t *__restrict__ big_start, int32_t *__restrict__ big_len,
                              int32_t *__restrict__ big_depth, int64_t list_stride,
-                             long long *__restrict__ counts /* [0] fin, [1] big, [2] small */) {
+                             long long *__restrict__ counts /* counters + CNT_FIN_COUNT: [0] fin, [1] big (CNT_BIG_COUNT), [2] small (CNT_SMALL_COUNT) */) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     const int len = c < n_cells ? cell_count[c] : 0;
     const int cls = len <= 0 ? -1 : (len <= fin_small ? 2 : (len <= fin_max ? 0 : 1));
@@ -1763,19 +1763,29 @@ __global__ void k_place(const int32_t *__restrict__ cell_of, const int32_t *__re
 }
 
 // -------------------------------------------------------------- host side --
-static int run_scan(nnd_ctx *ctx, int mode, const int32_t *pos_seg, uint8_t *bytes, int32_t *total_dev, int64_t P, int64_t n,
-                    const int32_t *perm = nullptr) {
+// What every static function of the forest returns: done, error (ctx->err is set), or "this form of the forest does not
+// apply here" -- the caller switches to one that does (the whole-set passes; in the sharded build, the split by tree).
+// The exported nnd_forest_* functions hand the same values on as int.
+enum forest_rc { FOREST_OK = 0, FOREST_ERROR = 1, FOREST_FALLBACK = 2 };
+static forest_rc forest_fallback(const char *reason) {
+    if (nnd_knob("NND_FOREST_DEBUG")) fprintf(stderr, "forest: fallback: %s\n", reason);
+    return FOREST_FALLBACK;
+}
+#define FOREST_HIP_CHECK(expr) NND_HIP_CHECK_AS(expr, #expr, FOREST_ERROR)
+
+static forest_rc run_scan(nnd_ctx *ctx, int mode, const int32_t *pos_seg, uint8_t *bytes, int32_t *total_dev, int64_t P, int64_t n,
+                          const int32_t *perm = nullptr) {
     int nb = (int)((P + SCAN_TILE - 1) / SCAN_TILE);
     hipLaunchKernelGGL(k_scan_reduce, dim3(nb), dim3(SCAN_BLOCK), 0, ctx->stream, mode, pos_seg, bytes, P, ctx->scan_blk, perm,
                        ctx->side_pt, n);
     hipLaunchKernelGGL(k_scan_apply<true>, dim3(nb), dim3(SCAN_BLOCK), 0, ctx->stream, mode == 2 ? 0 : mode, pos_seg, bytes, P,
                        ctx->scan_blk, ctx->scan_out, total_dev);
-    NND_HIP_CHECK(hipGetLastError());
-    return 0;
+    FOREST_HIP_CHECK(hipGetLastError());
+    return FOREST_OK;
 }
 
 // exclusive scan of data[0 .. n) in place, the grand total to total_dev[0] (ctx->scan_blk holds the tile sums)
-static int scan_i32_inplace(nnd_ctx *ctx, int32_t *data, int64_t n, int32_t *total_dev) {
+static forest_rc scan_i32_inplace(nnd_ctx *ctx, int32_t *data, int64_t n, int32_t *total_dev) {
     if (n <= SCAN_TILE) {
         hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(256), 0, ctx->stream, data, (int)n, total_dev);
     } else {
@@ -1784,8 +1794,16 @@ static int scan_i32_inplace(nnd_ctx *ctx, int32_t *data, int64_t n, int32_t *tot
         hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(256), 0, ctx->stream, ctx->scan_blk, nb, total_dev);
         hipLaunchKernelGGL(k_scan_i32_apply, dim3(nb), dim3(SCAN_BLOCK), 0, ctx->stream, data, n, ctx->scan_blk);
     }
-    NND_HIP_CHECK(hipGetLastError());
-    return 0;
+    FOREST_HIP_CHECK(hipGetLastError());
+    return FOREST_OK;
+}
+
+// the total of the leaf-mark scan that ran last (number of leaves / cells), on the host
+static forest_rc read_scan_total(nnd_ctx *ctx, int32_t *out) {
+    FOREST_HIP_CHECK(hipMemcpyAsync(&ctx->h_pin->scan_total, nnd_scan_total(ctx), sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    FOREST_HIP_CHECK(nnd_sync_spin(ctx));
+    *out = ctx->h_pin->scan_total;
+    return FOREST_OK;
 }
 
 static size_t fin_smem_bytes(int dp, int cap /* 0: ids in global memory */) {
@@ -1793,244 +1811,257 @@ static size_t fin_smem_bytes(int dp, int cap /* 0: ids in global memory */) {
     return (size_t)cap * 9 + tail;
 }
 
-// What the level-synchronous passes run on: the whole point set (small n), or the compact sample (recording the tree).
-struct forest_view {
+// The rows a pass or a finisher works on: the whole prepared point set, or the compact sample.
+struct forest_rows {
     const float *xp;
     const uint16_t *xh;
     const float2 *nr;  // per row: (|x|^2 -- 1 / 0 for normalised rows --, |x - bf16(x)|: the point's share of the screening band)
-    int64_t n, P;     // points per tree, n_trees * n
-    int leaf_size;    // split while len > leaf_size (rp_trees.py:2188)
+    int64_t n;         // points per tree
+    int leaf_size;     // split while len > leaf_size (rp_trees.py:2188)
+};
+static forest_rows whole_set_rows(const nnd_ctx *ctx) { return {ctx->xp, ctx->xh, ctx->nr2, ctx->n, ctx->p.leaf_size}; }
+
+// What the level-synchronous passes run on -- the whole point set (small n), or the sample (recording the tree) -- and the
+// state of their loop.
+struct forest_view {
+    forest_rows rows;
+    int64_t P;        // n_trees * rows.n
     int fin_max;      // children of <= fin_max points leave the passes for k_finish_subtrees (0: never)
     bool record;      // keep hyperplanes and children of every node (routing pass)
-    int cur = 0, depth = 0;
-    int64_t n_nodes = 0;
-    std::vector<int64_t> level_base;  // recording: first node id of every level (+ the total at the end)
-    int T = 0;                        // trees in the view (0: ctx->p.n_trees)
-    int tree_bias = 0;                // global number of the view's first tree (sharded build: tops split by tree)
-    int64_t n_low = 0, high_lo = 0;   // recording: node ids in use are [0, n_low) and [high_lo, node_cap) (k_pack_nodes compacts)
+    int T = 0;        // trees in the view (0: ctx->p.n_trees)
+    rp_tree_map tm;   // tm.tree_bias: global number of the view's first tree (sharded build: tops split by tree)
+    // loop state (levels_start .. the tails)
+    int cur = 0, depth = 0;            // ping-pong half that holds the current level, its depth
+    int64_t S = 0;                     // segments of the current level
+    long long active_pos = 0;          // positions in them
+    int64_t node_base = 0;             // nodes of the levels above (recording: this level's nodes are [node_base, node_base + S))
+    bool inv_live = true;              // inv[] is maintained while the point-major margin kernel is in use
+    nnd_level_flag *flag_dev = nullptr;  // where k_children hands the level's words over itself (nullptr: copy form, see level_handover)
+    std::vector<int64_t> level_base;   // recording: first node id of every level (+ the total at the end)
+    int64_t n_low = 0, high_lo = 0;    // recording: node ids in use are [0, n_low) and [high_lo, node_cap) (k_pack_nodes compacts)
 };
 
-// big list (global-memory variant; its nodes join the workgroup list as they shrink) -> workgroup list -> small list
-static int launch_finishers(nnd_ctx *ctx, int32_t *perm, int32_t *other, const int32_t *big_start, const int32_t *big_len,
-                            const int32_t *big_depth, int depth0, long long n_big, long long n_small = 0, rp_tree_map tm = rp_tree_map{}) {
-    const int dp = ctx->dp, angular = nnd_metric_unit(ctx->p.metric);
-    int32_t *fin_start = ctx->seg_child + 2 * ctx->max_segs;  // finisher work list lives behind seg_child
-    int32_t *fin_len = fin_start + ctx->max_segs;
-    int32_t *fin_depth = fin_len + ctx->max_segs;
-    long long *fin_count = ctx->counters + CNT_SCRATCH + 1;
-#define FIN_ARGS(st, ln, dpth, d0, cnt) ctx->xp, ctx->xh, ctx->nr2, ctx->p.metric, dp, ctx->n, perm, st, ln, dpth, d0, (int)(cnt), angular, \
-                 ctx->tree_seed, ctx->p.max_depth, ctx->p.leaf_size, ctx->leaf_flag
-    if (n_small > 0) {  // one wave per cell
-        const int32_t *sl = ctx->small_list;
-        hipLaunchKernelGGL((k_finish_subtrees<false, 64, FIN_SMALL>), dim3((unsigned)n_small), dim3(64), fin_smem_bytes(dp, FIN_SMALL),
-                           ctx->stream, FIN_ARGS(sl, sl + ctx->cell_cap, sl + 2 * ctx->cell_cap, 0, n_small), (int32_t *)nullptr,
-                           (uint8_t *)nullptr, FIN_MAX, fin_start, fin_len, fin_depth, fin_count, tm, ctx->mean + ctx->dp);
-        NND_HIP_CHECK(hipGetLastError());
-    }
-    if (n_big > 0) {
-        hipLaunchKernelGGL((k_finish_subtrees<true, 256, 0>), dim3((unsigned)n_big), dim3(256), fin_smem_bytes(dp, 0), ctx->stream,
-                           FIN_ARGS(big_start, big_len, big_depth, depth0, n_big), other, ctx->side, FIN_MAX, fin_start, fin_len,
-                           fin_depth, fin_count, tm, ctx->mean + ctx->dp);
-        NND_HIP_CHECK(hipGetLastError());
-    }
-    NND_HIP_CHECK(hipMemcpyAsync(ctx->h_pin + 34, fin_count, sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
-    NND_HIP_CHECK(nnd_sync_spin(ctx));
-    const long long nfin = ctx->h_pin[34];
-    if (nfin > ctx->max_segs) {
-        ctx->set_error("rp-forest: %lld finisher segments exceed the allocation of %lld", nfin, (long long)ctx->max_segs);
-        return 1;
-    }
-    if (nfin > 0) {
-        hipLaunchKernelGGL((k_finish_subtrees<false, 256, FIN_MAX>), dim3((unsigned)nfin), dim3(256), fin_smem_bytes(dp, FIN_MAX),
-                           ctx->stream, FIN_ARGS(fin_start, fin_len, fin_depth, 0, nfin), (int32_t *)nullptr, (uint8_t *)nullptr,
-                           FIN_MAX, fin_start, fin_len, fin_depth, fin_count, tm, ctx->mean + ctx->dp);
-        NND_HIP_CHECK(hipGetLastError());
-    }
-#undef FIN_ARGS
-    return 0;
+// One launch of k_finish_subtrees<BIG, NTHR, CAP, RECORD>, a workgroup per entry of `wl`: the rows the segments index, the
+// permutation they are finished in (BIG: `other` is the partition scratch), and for RECORD where the subtrees are recorded.
+// Nodes that a BIG launch has shrunk to FIN_MAX points join the finisher work list.
+template <bool BIG, int NTHR, int CAP, bool RECORD = false>
+static forest_rc launch_finisher(nnd_ctx *ctx, const forest_rows &r, int32_t *perm, int32_t *other, const nnd_work_list &wl, int depth0,
+                                 long long count, const rp_tree_map &tm, const rp_record &rec = rp_record{}) {
+    const nnd_work_list fin = nnd_fin_list(ctx);
+    hipLaunchKernelGGL((k_finish_subtrees<BIG, NTHR, CAP, RECORD>), dim3((unsigned)count), dim3(NTHR), fin_smem_bytes(ctx->dp, CAP), ctx->stream,
+                       r.xp, r.xh, r.nr, ctx->p.metric, ctx->dp, r.n, perm, wl.start, wl.len, wl.depth, depth0, (int)count,
+                       nnd_metric_unit(ctx->p.metric), ctx->tree_seed, ctx->p.max_depth, r.leaf_size, ctx->leaf_flag,
+                       BIG ? other : (int32_t *)nullptr, BIG ? ctx->side : (uint8_t *)nullptr, FIN_MAX, fin.start, fin.len, fin.depth,
+                       ctx->counters + CNT_FIN_COUNT, tm, ctx->mean + ctx->dp, rec);
+    FOREST_HIP_CHECK(hipGetLastError());
+    return FOREST_OK;
 }
 
-// The level-synchronous passes on `v`.  Returns 0, 1 (error) or 2 (recording ran out of node slots: caller falls back).
-static int forest_levels(nnd_ctx *ctx, forest_view &v) {
-    const int64_t n = v.n, P = v.P;
-    const int T = v.T > 0 ? v.T : ctx->p.n_trees, dp = ctx->dp, leaf_size = v.leaf_size, max_depth = ctx->p.max_depth;
-    const uint32_t pos_bias = (uint32_t)((int64_t)v.tree_bias * n);
-    rp_tree_map tm;
-    tm.tree_bias = v.tree_bias;
-    const int angular = nnd_metric_unit(ctx->p.metric);
-    const int hs = dp + 4;
-    int32_t *scan_total = (int32_t *)(ctx->counters + CNT_SCRATCH);  // device scratch word(s)
-    int splittable = (n > leaf_size && max_depth > 0) ? 1 : 0;
-    int cur = 0;
-    unsigned gridP = (unsigned)((P + 255) / 256);
-    hipLaunchKernelGGL(k_forest_init, dim3(gridP), dim3(256), 0, ctx->stream, ctx->perm[0], ctx->pos_seg[0],
-                       ctx->leaf_flag, ctx->inv, n, P, splittable);
+static forest_rc read_fin_count(nnd_ctx *ctx, long long *out) {
+    FOREST_HIP_CHECK(hipMemcpyAsync(&ctx->h_pin->fin_count, ctx->counters + CNT_FIN_COUNT, sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+    FOREST_HIP_CHECK(nnd_sync_spin(ctx));
+    *out = ctx->h_pin->fin_count;
+    return FOREST_OK;
+}
+
+// whole point set: one-wave list, then big list (global-memory variant; its nodes join the workgroup list as they shrink),
+// then the workgroup list
+static forest_rc launch_finishers(nnd_ctx *ctx, int32_t *perm, int32_t *other, const nnd_work_list &big, int depth0, long long n_big,
+                                  long long n_small, const rp_tree_map &tm) {
+    const forest_rows rows = whole_set_rows(ctx);
+    forest_rc rc;
+    if (n_small > 0 && (rc = launch_finisher<false, 64, FIN_SMALL>(ctx, rows, perm, other, nnd_small_list(ctx), 0, n_small, tm))) return rc;
+    if (n_big > 0 && (rc = launch_finisher<true, 256, 0>(ctx, rows, perm, other, big, depth0, n_big, tm))) return rc;
+    long long nfin = 0;
+    if ((rc = read_fin_count(ctx, &nfin))) return rc;
+    if (nfin > ctx->max_segs) {
+        ctx->set_error("rp-forest: %lld finisher segments exceed the allocation of %lld", nfin, (long long)ctx->max_segs);
+        return FOREST_ERROR;
+    }
+    if (nfin > 0) return launch_finisher<false, 256, FIN_MAX>(ctx, rows, perm, other, nnd_fin_list(ctx), 0, nfin, tm);
+    return FOREST_OK;
+}
+
+// Level loop, start: every tree one segment, the finisher work list empty.  Small point sets (whole-set mode): the roots go
+// straight to the finisher and no level runs.
+static forest_rc levels_start(nnd_ctx *ctx, forest_view &v) {
+    const int64_t n = v.rows.n;
+    if (v.T <= 0) v.T = ctx->p.n_trees;
+    const int T = v.T;
+    const int splittable = (n > v.rows.leaf_size && ctx->p.max_depth > 0) ? 1 : 0;
+    hipLaunchKernelGGL(k_forest_init, dim3((unsigned)((v.P + 255) / 256)), dim3(256), 0, ctx->stream, ctx->perm[0], ctx->pos_seg[0],
+                       ctx->leaf_flag, ctx->inv, n, v.P, splittable);
     hipLaunchKernelGGL(k_forest_init_segs, dim3((T + 63) / 64), dim3(64), 0, ctx->stream, ctx->seg_start[0],
                        ctx->seg_len[0], T, n);
-    int64_t S = splittable ? T : 0;
-    int depth = 0;
-    bool inv_live = true;  // inv[] is maintained while the point-major margin kernel is in use
-    long long active_pos = P;
-    const int fin_max = v.fin_max;
-    int32_t *fin_start = ctx->seg_child + 2 * ctx->max_segs;  // finisher work list lives behind seg_child
-    int32_t *fin_len = fin_start + ctx->max_segs;
-    int32_t *fin_depth = fin_len + ctx->max_segs;
-    int64_t node_base = 0;
+    v.cur = v.depth = 0;
+    v.S = splittable ? T : 0;
+    v.active_pos = v.P;
+    v.node_base = 0;
+    v.inv_live = true;
     // (a shard's host waits go through its communicator -- abort flag, timeout -- so it keeps the copy + wait form)
-    long long *flag_words = (ctx->h_pin_dev && !ctx->wait_hook && !nnd_knob("NND_NO_LEVEL_FLAG")) ? ctx->h_pin_dev + 40 : nullptr;
-    NND_HIP_CHECK(hipMemsetAsync(ctx->counters + CNT_SCRATCH + 1, 0, sizeof(long long), ctx->stream));
-    if (!v.record && S > 0 && n <= fin_max) {  // small point sets: the roots go straight to the finisher
+    v.flag_dev = (ctx->h_pin_dev && !ctx->wait_hook && !nnd_knob("NND_NO_LEVEL_FLAG")) ? &ctx->h_pin_dev->flag : nullptr;
+    long long *fin_count = ctx->counters + CNT_FIN_COUNT;
+    FOREST_HIP_CHECK(hipMemsetAsync(fin_count, 0, sizeof(long long), ctx->stream));
+    if (!v.record && v.S > 0 && n <= v.fin_max) {
+        const nnd_work_list fin = nnd_fin_list(ctx);
         std::vector<int32_t> h_s(T), h_l(T), h_d(T, 0);
         for (int t = 0; t < T; t++) { h_s[t] = (int32_t)(t * n); h_l[t] = (int32_t)n; }
-        NND_HIP_CHECK(hipMemcpyAsync(fin_start, h_s.data(), sizeof(int32_t) * T, hipMemcpyHostToDevice, ctx->stream));
-        NND_HIP_CHECK(hipMemcpyAsync(fin_len, h_l.data(), sizeof(int32_t) * T, hipMemcpyHostToDevice, ctx->stream));
-        NND_HIP_CHECK(hipMemcpyAsync(fin_depth, h_d.data(), sizeof(int32_t) * T, hipMemcpyHostToDevice, ctx->stream));
+        FOREST_HIP_CHECK(hipMemcpyAsync(fin.start, h_s.data(), sizeof(int32_t) * T, hipMemcpyHostToDevice, ctx->stream));
+        FOREST_HIP_CHECK(hipMemcpyAsync(fin.len, h_l.data(), sizeof(int32_t) * T, hipMemcpyHostToDevice, ctx->stream));
+        FOREST_HIP_CHECK(hipMemcpyAsync(fin.depth, h_d.data(), sizeof(int32_t) * T, hipMemcpyHostToDevice, ctx->stream));
         long long cntf = T;
-        NND_HIP_CHECK(hipMemcpyAsync(ctx->counters + CNT_SCRATCH + 1, &cntf, sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
-        NND_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        S = 0;
+        FOREST_HIP_CHECK(hipMemcpyAsync(fin_count, &cntf, sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
+        FOREST_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        v.S = 0;
     }
-    while (S > 0) {
-        if (S > ctx->max_segs) {
-            ctx->set_error("rp-forest: %lld segments exceed the allocation of %lld", (long long)S, (long long)ctx->max_segs);
-            return 1;
+    return FOREST_OK;
+}
+
+// One level's launches: hyperplanes, margins, scan, children, scatter.
+static forest_rc level_launch(nnd_ctx *ctx, forest_view &v) {
+    const forest_rows &r = v.rows;
+    const int64_t n = r.n, P = v.P, S = v.S, node_base = v.node_base;
+    const int dp = ctx->dp, hs = dp + 4, cur = v.cur, depth = v.depth;
+    const uint32_t pos_bias = (uint32_t)((int64_t)v.tm.tree_bias * n);
+    const unsigned gridP = (unsigned)((P + 255) / 256);
+    int32_t *scan_total = nnd_scan_total(ctx);
+    if (S > ctx->max_segs) {
+        ctx->set_error("rp-forest: %lld segments exceed the allocation of %lld", (long long)S, (long long)ctx->max_segs);
+        return FOREST_ERROR;
+    }
+    if (v.record && node_base + S > ctx->node_cap) return forest_fallback("a recorded level outgrows the node tables");
+    if (v.record) v.level_base.push_back(node_base);
+    // recording: this level's hyperplanes are written straight into the node tables at [node_base, node_base + S)
+    float *hyper = v.record ? ctx->node_hf + node_base * hs : ctx->hyper;
+    uint16_t *hyper_h = v.record ? ctx->node_hh + node_base * dp : ctx->hyper_h;
+    hipLaunchKernelGGL(k_hyperplane, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, ctx->stream, r.xp, dp,
+                       ctx->perm[cur], ctx->seg_start[cur], ctx->seg_len[cur], (int)S, nnd_metric_unit(ctx->p.metric), ctx->tree_seed, depth,
+                       hyper, hs, hyper_h, pos_bias, ctx->mean + ctx->dp);
+    // point-major pass: hyperplane table fits in L2 AND enough positions are still active to amortise
+    // streaming every row once (it costs n rows regardless of how many positions are active)
+    const bool fused = v.inv_live && (S * (int64_t)dp * 2 <= (int64_t)6 << 20) && (v.active_pos * 2 >= 3 * n);
+    if (fused) {
+        hipLaunchKernelGGL(k_margin_fused, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, ctx->stream, r.xp, r.xh, r.nr,
+                           ctx->p.metric, dp, n, v.T, ctx->inv, hyper, hs, hyper_h, ctx->tree_seed, depth, ctx->side_pt, pos_bias, ctx->mean + ctx->dp);
+    } else {
+        v.inv_live = false;
+        hipLaunchKernelGGL(k_margin, dim3((unsigned)((P + 63) / 64)), dim3(256), 0, ctx->stream, r.xp, r.xh, r.nr,
+                           ctx->p.metric, dp, ctx->perm[cur], ctx->pos_seg[cur], P, hyper, hs, hyper_h, ctx->tree_seed, depth,
+                           ctx->side, pos_bias, ctx->mean + ctx->dp);
+    }
+    if (run_scan(ctx, fused ? 2 : 0, ctx->pos_seg[cur], ctx->side, scan_total, P, n, ctx->perm[cur])) return FOREST_ERROR;
+    hipLaunchKernelGGL(k_seg_count, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, ctx->stream, ctx->seg_start[cur],
+                       ctx->seg_len[cur], (int)S, ctx->scan_out, scan_total, P, ctx->seg_nleft);
+    int child_can_split = (ctx->p.max_depth - (depth + 1)) > 0 ? 1 : 0;
+    // Recording: once only a few sample positions are still in splittable nodes the recorded tree stops: the
+    // children of this level all become cells, however long (a straggler level costs a full pass over the sample
+    // for a handful of nodes; an over-long cell just goes to a workgroup finisher instead of a single wave).
+    if (v.record && ctx->early_stop > 0 && v.active_pos * ctx->early_stop < P) child_can_split = 0;
+    const nnd_work_list fin = nnd_fin_list(ctx);
+    hipLaunchKernelGGL(k_children, dim3(1), dim3(256), 0, ctx->stream, ctx->seg_start[cur], ctx->seg_len[cur],
+                       ctx->seg_nleft, (int)S, r.leaf_size, child_can_split, v.fin_max, depth + 1, ctx->seg_start[1 - cur],
+                       ctx->seg_len[1 - cur], ctx->seg_child, ctx->leaf_flag, fin.start, fin.len, fin.depth, ctx->counters,
+                       v.record ? ctx->node_child : (int32_t *)nullptr, (int)node_base, (int)(node_base + S), ctx->s_leaf_depth,
+                       (int)ctx->node_cap - 1, (long long *)v.flag_dev, v.flag_dev ? ++ctx->flag_seq : 0);
+    hipLaunchKernelGGL(k_scatter, dim3(gridP), dim3(256), 0, ctx->stream, ctx->perm[cur], ctx->pos_seg[cur], ctx->side,
+                       ctx->scan_out, ctx->seg_start[cur], ctx->seg_nleft, ctx->seg_child, P, n, ctx->perm[1 - cur],
+                       ctx->pos_seg[1 - cur], v.inv_live ? ctx->inv : (int32_t *)nullptr);
+    FOREST_HIP_CHECK(hipGetLastError());
+    return FOREST_OK;
+}
+
+// One small hand-over per level: the host needs the number of segments that stay in the level passes before it can queue
+// the next level.  Flag form: k_children has written the words to pinned memory itself and raises the sequence number (see
+// there) -- no copy, no stream synchronisation.  Copy form otherwise.
+static forest_rc level_handover(nnd_ctx *ctx, const forest_view &v, nnd_level_words *next) {
+    if (!v.flag_dev) {
+        FOREST_HIP_CHECK(hipMemcpyAsync(&ctx->h_pin->level, ctx->counters + CNT_ACTIVE_SEGS, sizeof(nnd_level_words), hipMemcpyDeviceToHost,
+                                        ctx->stream));
+        FOREST_HIP_CHECK(nnd_sync_spin(ctx));
+        *next = ctx->h_pin->level;
+        return FOREST_OK;
+    }
+    volatile long long *seqw = &ctx->h_pin->flag.seq;
+    const auto t_spin = std::chrono::steady_clock::now();
+    unsigned spins = 0;
+    while (*seqw != ctx->flag_seq) {
+        if ((++spins & 0xFFFFu) == 0 && std::chrono::steady_clock::now() - t_spin > std::chrono::seconds(30)) {
+            ctx->set_error("rp-forest: the device did not hand over the segment count of level %d within 30 s", v.depth);
+            return FOREST_ERROR;
         }
-        if (v.record && node_base + S > ctx->node_cap) {
-            if (nnd_knob("NND_FOREST_DEBUG")) fprintf(stderr, "forest: fallback at line %d\n", __LINE__);
-            return 2;
-        }
-        if (v.record) v.level_base.push_back(node_base);
-        // recording: this level's hyperplanes are written straight into the node tables at [node_base, node_base + S)
-        float *hyper = v.record ? ctx->node_hf + node_base * hs : ctx->hyper;
-        uint16_t *hyper_h = v.record ? ctx->node_hh + node_base * dp : ctx->hyper_h;
-        hipLaunchKernelGGL(k_hyperplane, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, ctx->stream, v.xp, dp,
-                           ctx->perm[cur], ctx->seg_start[cur], ctx->seg_len[cur], (int)S, angular, ctx->tree_seed, depth,
-                           hyper, hs, hyper_h, pos_bias, ctx->mean + ctx->dp);
-        // point-major pass: hyperplane table fits in L2 AND enough positions are still active to amortise
-        // streaming every row once (it costs n rows regardless of how many positions are active)
-        const bool fused = inv_live && (S * (int64_t)dp * 2 <= (int64_t)6 << 20) && (active_pos * 2 >= 3 * n);
-        if (fused) {
-            hipLaunchKernelGGL(k_margin_fused, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, ctx->stream, v.xp, v.xh, v.nr,
-                               ctx->p.metric, dp, n, T, ctx->inv, hyper, hs, hyper_h, ctx->tree_seed, depth, ctx->side_pt, pos_bias, ctx->mean + ctx->dp);
-        } else {
-            inv_live = false;
-            hipLaunchKernelGGL(k_margin, dim3((unsigned)((P + 63) / 64)), dim3(256), 0, ctx->stream, v.xp, v.xh, v.nr,
-                               ctx->p.metric, dp, ctx->perm[cur], ctx->pos_seg[cur], P, hyper, hs, hyper_h, ctx->tree_seed, depth,
-                               ctx->side, pos_bias, ctx->mean + ctx->dp);
-        }
-        if (run_scan(ctx, fused ? 2 : 0, ctx->pos_seg[cur], ctx->side, scan_total, P, n, ctx->perm[cur])) return 1;
-        hipLaunchKernelGGL(k_seg_count, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, ctx->stream, ctx->seg_start[cur],
-                           ctx->seg_len[cur], (int)S, ctx->scan_out, scan_total, P, ctx->seg_nleft);
-        int child_can_split = (max_depth - (depth + 1)) > 0 ? 1 : 0;
-        // Recording: once only a few sample positions are still in splittable nodes the recorded tree stops: the
-        // children of this level all become cells, however long (a straggler level costs a full pass over the sample
-        // for a handful of nodes; an over-long cell just goes to a workgroup finisher instead of a single wave).
-        if (v.record && ctx->early_stop > 0 && active_pos * ctx->early_stop < P) child_can_split = 0;
-        hipLaunchKernelGGL(k_children, dim3(1), dim3(256), 0, ctx->stream, ctx->seg_start[cur], ctx->seg_len[cur],
-                           ctx->seg_nleft, (int)S, leaf_size, child_can_split, fin_max, depth + 1, ctx->seg_start[1 - cur],
-                           ctx->seg_len[1 - cur], ctx->seg_child, ctx->leaf_flag, fin_start, fin_len, fin_depth, ctx->counters,
-                           v.record ? ctx->node_child : (int32_t *)nullptr, (int)node_base, (int)(node_base + S), ctx->s_leaf_depth,
-                           (int)ctx->node_cap - 1, flag_words, flag_words ? ++ctx->flag_seq : 0);
-        hipLaunchKernelGGL(k_scatter, dim3(gridP), dim3(256), 0, ctx->stream, ctx->perm[cur], ctx->pos_seg[cur], ctx->side,
-                           ctx->scan_out, ctx->seg_start[cur], ctx->seg_nleft, ctx->seg_child, P, n, ctx->perm[1 - cur],
-                           ctx->pos_seg[1 - cur], inv_live ? ctx->inv : (int32_t *)nullptr);
-        NND_HIP_CHECK(hipGetLastError());
-        // one small hand-over per level: the number of segments that stay in the level-synchronous passes
-        static_assert(CNT_LEAVES == CNT_ACTIVE_SEGS + 1 && CNT_SCRATCH == CNT_LEAVES + 1, "counter layout");
-        long long *next = ctx->h_pin + 32;  // CNT_ACTIVE_SEGS, CNT_LEAVES, CNT_SCRATCH.. are adjacent; pinned words
-        if (flag_words) {  // written by k_children itself (see there): no copy, no stream synchronisation
-            next = ctx->h_pin + 40;
-            volatile long long *seqw = ctx->h_pin + 46;
-            const auto t_spin = std::chrono::steady_clock::now();
-            unsigned spins = 0;
-            while (*seqw != ctx->flag_seq) {
-                if ((++spins & 0xFFFFu) == 0 && std::chrono::steady_clock::now() - t_spin > std::chrono::seconds(30)) {
-                    ctx->set_error("rp-forest: the device did not hand over the segment count of level %d within 30 s", depth);
-                    return 1;
-                }
-            }
-            std::atomic_thread_fence(std::memory_order_acquire);
-        } else {
-            NND_HIP_CHECK(hipMemcpyAsync(next, ctx->counters + CNT_ACTIVE_SEGS, 6 * sizeof(long long), hipMemcpyDeviceToHost,
-                                         ctx->stream));
-            NND_HIP_CHECK(nnd_sync_spin(ctx));
-        }
-        node_base += S;
-        S = next[0];
-        active_pos = next[1];
-        cur = 1 - cur;
-        depth++;
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    *next = ctx->h_pin->flag.w;
+    return FOREST_OK;
+}
+
+// Recording tail: the subtrees that left the passes are recorded one workgroup each (k_finish_subtrees<.., RECORD>).
+static forest_rc record_subtrees(nnd_ctx *ctx, forest_view &v) {
+    const int64_t node_base = v.node_base;
+    v.level_base.push_back(node_base);
+    forest_rc rc;
+    long long nfin = 0;
+    if ((rc = read_fin_count(ctx, &nfin))) return rc;
+    if (nfin > ctx->max_segs || node_base + nfin + 1 >= ctx->node_cap) return forest_fallback("the subtrees to record outgrow the node tables");
+    v.n_low = node_base;
+    v.high_lo = ctx->node_cap;
+    if (nfin == 0) return FOREST_OK;
+    int *flags = (int *)(ctx->counters + CNT_REC_FLAGS);  // [0] id counter, [1] overflow
+    FOREST_HIP_CHECK(hipMemsetAsync(flags, 0, 2 * sizeof(int), ctx->stream));
+    rp_record rec{ctx->node_hf, ctx->node_hh, ctx->node_child, ctx->s_leaf_depth, ctx->dp + 4, (int)ctx->node_cap - 1,
+                  (int)(ctx->node_cap - 1 - nfin), (int)node_base, flags, flags + 1, 0, FIN_MAX};
+    // short subtrees: one wave each (a chain of dependent latencies wants concurrency, not width); the rest: a workgroup
+    rp_record rs = rec, rl = rec;
+    rs.min_len = 0; rs.max_len = FIN_SMALL;
+    rl.min_len = FIN_SMALL + 1; rl.max_len = FIN_MAX;
+    const nnd_work_list fin = nnd_fin_list(ctx);
+    if ((rc = launch_finisher<false, 64, FIN_SMALL, true>(ctx, v.rows, ctx->perm[v.cur], nullptr, fin, 0, nfin, v.tm, rs))) return rc;
+    if (v.fin_max > FIN_SMALL && (rc = launch_finisher<false, 256, FIN_MAX, true>(ctx, v.rows, ctx->perm[v.cur], nullptr, fin, 0, nfin, v.tm, rl)))
+        return rc;
+    FOREST_HIP_CHECK(hipMemcpyAsync(ctx->h_pin->rec_flags, flags, 2 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    FOREST_HIP_CHECK(nnd_sync_spin(ctx));
+    if (ctx->h_pin->rec_flags[1]) return forest_fallback("the recording finisher ran out of node slots");
+    // ids taken downwards: the segments' own (node_cap - nfin ..), then one per recorded split below them; the level passes'
+    // nodes were numbered upwards
+    v.high_lo = ctx->node_cap - nfin - ctx->h_pin->rec_flags[0];
+    return FOREST_OK;
+}
+
+// The level-synchronous passes on `v`, then what finishes its trees: the finishers (whole set), or the recording finisher.
+// FOREST_FALLBACK: recording ran out of node slots.
+static forest_rc forest_levels(nnd_ctx *ctx, forest_view &v) {
+    forest_rc rc = levels_start(ctx, v);
+    if (rc) return rc;
+    while (v.S > 0) {
+        nnd_level_words next;
+        if ((rc = level_launch(ctx, v)) || (rc = level_handover(ctx, v, &next))) return rc;
+        v.node_base += v.S;
+        v.S = next.segs;
+        v.active_pos = next.active_pos;
+        v.cur = 1 - v.cur;
+        v.depth++;
         // Tail of the level loop (whole-set mode): once most positions have been handed over, a level-synchronous pass
         // still costs P positions per kernel for a few hundred segments: the global-memory variant of the finisher
         // takes them (its nodes are split in place until they fit the LDS finisher, whose work list they join).
-        if (!v.record && S > 0 && (active_pos * 2 < 3 * n) && next[5] <= BIG_MAX) {  // next[5] = CNT_SCRATCH + 3: longest stayer
-            if (launch_finishers(ctx, ctx->perm[cur], ctx->perm[1 - cur], ctx->seg_start[cur], ctx->seg_len[cur], nullptr, depth, S, 0, tm)) return 1;
-            v.cur = cur;
-            v.depth = depth;
-            v.n_nodes = node_base;
-            return 0;  // both finishers have been launched
+        if (!v.record && v.S > 0 && (v.active_pos * 2 < 3 * v.rows.n) && next.max_stay <= BIG_MAX) {
+            const nnd_work_list stayers{ctx->seg_start[v.cur], ctx->seg_len[v.cur], nullptr};  // all at depth v.depth
+            return launch_finishers(ctx, ctx->perm[v.cur], ctx->perm[1 - v.cur], stayers, v.depth, v.S, 0, v.tm);
         }
     }
-    v.cur = cur;
-    v.depth = depth;
-    v.n_nodes = node_base;
-    if (v.record) {
-        v.level_base.push_back(node_base);
-        // the subtrees that left the passes are recorded one workgroup each (k_finish_subtrees<.., RECORD>)
-        NND_HIP_CHECK(hipMemcpyAsync(ctx->h_pin + 34, ctx->counters + CNT_SCRATCH + 1, sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
-        NND_HIP_CHECK(nnd_sync_spin(ctx));
-        const long long nfin = ctx->h_pin[34];
-        if (nfin > ctx->max_segs || node_base + nfin + 1 >= ctx->node_cap) {
-            if (nnd_knob("NND_FOREST_DEBUG")) fprintf(stderr, "forest: fallback at line %d\n", __LINE__);
-            return 2;
-        }
-        v.n_low = node_base;
-        v.high_lo = ctx->node_cap;
-        if (nfin > 0) {
-            int *flags = (int *)(ctx->counters + CNT_SCRATCH + 2);  // [0] id counter, [1] overflow
-            NND_HIP_CHECK(hipMemsetAsync(flags, 0, 2 * sizeof(int), ctx->stream));
-            rp_record rec{ctx->node_hf, ctx->node_hh, ctx->node_child, ctx->s_leaf_depth, hs, (int)ctx->node_cap - 1,
-                          (int)(ctx->node_cap - 1 - nfin), (int)node_base, flags, flags + 1, 0, FIN_MAX};
-            // short subtrees: one wave each (a chain of dependent latencies wants concurrency, not width); the rest: a workgroup
-            rp_record rs = rec, rl = rec;
-            rs.min_len = 0; rs.max_len = FIN_SMALL;
-            rl.min_len = FIN_SMALL + 1; rl.max_len = FIN_MAX;
-            hipLaunchKernelGGL((k_finish_subtrees<false, 64, FIN_SMALL, true>), dim3((unsigned)nfin), dim3(64), fin_smem_bytes(dp, FIN_SMALL),
-                               ctx->stream, v.xp, v.xh, v.nr, ctx->p.metric, dp, n, ctx->perm[cur], fin_start, fin_len, fin_depth, 0,
-                               (int)nfin, angular, ctx->tree_seed, max_depth, leaf_size, ctx->leaf_flag, (int32_t *)nullptr,
-                               (uint8_t *)nullptr, FIN_MAX, fin_start, fin_len, fin_depth, ctx->counters + CNT_SCRATCH + 1, tm, ctx->mean + ctx->dp, rs);
-            if (v.fin_max > FIN_SMALL)
-                hipLaunchKernelGGL((k_finish_subtrees<false, 256, FIN_MAX, true>), dim3((unsigned)nfin), dim3(256), fin_smem_bytes(dp, FIN_MAX),
-                                   ctx->stream, v.xp, v.xh, v.nr, ctx->p.metric, dp, n, ctx->perm[cur], fin_start, fin_len, fin_depth, 0,
-                                   (int)nfin, angular, ctx->tree_seed, max_depth, leaf_size, ctx->leaf_flag, (int32_t *)nullptr,
-                                   (uint8_t *)nullptr, FIN_MAX, fin_start, fin_len, fin_depth, ctx->counters + CNT_SCRATCH + 1, tm, ctx->mean + ctx->dp, rl);
-            NND_HIP_CHECK(hipGetLastError());
-            NND_HIP_CHECK(hipMemcpyAsync(ctx->h_pin + 38, flags, 2 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-            NND_HIP_CHECK(nnd_sync_spin(ctx));
-            if (((const int *)(ctx->h_pin + 38))[1]) {  // node tables exhausted
-                if (nnd_knob("NND_FOREST_DEBUG")) fprintf(stderr, "forest: fallback at line %d\n", __LINE__);
-                return 2;
-            }
-            // ids taken downwards: the segments' own (node_cap - nfin ..), then one per recorded split below them
-            v.high_lo = ctx->node_cap - nfin - ((const int *)(ctx->h_pin + 38))[0];
-        }
-        v.n_nodes = ctx->node_cap;  // ids are spread over the table: level-synchronous nodes upwards, recorded subtrees downwards
-        return 0;
-    }
-    if (launch_finishers(ctx, ctx->perm[cur], ctx->perm[1 - cur], nullptr, nullptr, nullptr, 0, 0, 0, tm)) return 1;
-    return 0;
+    if (v.record) return record_subtrees(ctx, v);
+    return launch_finishers(ctx, ctx->perm[v.cur], ctx->perm[1 - v.cur], nnd_work_list{}, 0, 0, 0, v.tm);
 }
 
-static int device_cus(nnd_ctx *ctx, int *out) {
+static forest_rc device_cus(nnd_ctx *ctx, int *out) {
     static int n_cu_dev[64] = {0};
     int &n_cu = n_cu_dev[ctx->p.device & 63];
     if (n_cu == 0) {
         hipDeviceProp_t prop;
-        NND_HIP_CHECK(hipGetDeviceProperties(&prop, ctx->p.device));
+        FOREST_HIP_CHECK(hipGetDeviceProperties(&prop, ctx->p.device));
         n_cu = prop.multiProcessorCount;
     }
     *out = n_cu;
-    return 0;
+    return FOREST_OK;
 }
 
 // What a routing pass reads and writes: packed trees (k_pack_nodes), the rows [row_lo, row_lo + nrows) of the prepared point
@@ -2047,26 +2078,26 @@ struct rp_route_io {
 };
 
 template <int NC, int TB>
-static int launch_route(nnd_ctx *ctx, const rp_route_io &io, int n_top, int l_top) {
+static forest_rc launch_route(nnd_ctx *ctx, const rp_route_io &io, int n_top, int l_top) {
     auto kern = k_route<NC, TB>;
     const size_t smem = (size_t)n_top * (2 * ctx->dp + 16);
     static bool attr_dev[64] = {false};
     if (!attr_dev[ctx->p.device & 63]) {
-        NND_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024));
+        FOREST_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024));
         attr_dev[ctx->p.device & 63] = true;
     }
     int n_cu = 0;
-    if (device_cus(ctx, &n_cu)) return 1;
+    if (device_cus(ctx, &n_cu)) return FOREST_ERROR;
     int64_t blocks = (ctx->n + 127) / 128;
     if (blocks > 2 * (int64_t)n_cu) blocks = 2 * (int64_t)n_cu;  // persistent: two 512-thread workgroups per CU
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(512), smem, ctx->stream, ctx->xp, ctx->nr2, ctx->p.metric, ctx->dp, ctx->n,
                        io.T, io.pack, io.hf, ctx->dp + 4, ctx->tree_seed, io.cell_count, io.cell_of, io.rank_of, n_top, l_top, ctx->mean + ctx->dp);
-    NND_HIP_CHECK(hipGetLastError());
-    return 0;
+    FOREST_HIP_CHECK(hipGetLastError());
+    return FOREST_OK;
 }
 
 // the plain walk (whole point set, the handle's own trees): kept for the comparison test and as the fallback
-static int route_plain(nnd_ctx *ctx, const rp_route_io &io, const forest_view &v) {
+static forest_rc route_plain(nnd_ctx *ctx, const rp_route_io &io, const forest_view &v) {
     const int dp = ctx->dp;
     // levels whose records fit the route kernel's LDS copy (<= 72 KB: two workgroups per CU)
     int l_top = 0;
@@ -2083,7 +2114,7 @@ static int route_plain(nnd_ctx *ctx, const rp_route_io &io, const forest_view &v
         case 8: return launch_route<8, 1>(ctx, io, n_top, l_top);
         default: break;  // wider rows: whole-set passes (nnd_create does not enable routing for them)
     }
-    return 2;
+    return FOREST_FALLBACK;
 }
 
 #ifndef NND_ROUTE_L1
@@ -2142,7 +2173,7 @@ static rp_route_geom route_geometry(int dp, int T, int64_t nrows, int64_t n_cell
 }
 
 template <int NC>
-static int launch_route_coherent(nnd_ctx *ctx, const rp_route_io &io, const rp_route_geom &g) {
+static forest_rc launch_route_coherent(nnd_ctx *ctx, const rp_route_io &io, const rp_route_geom &g) {
     const int dp = ctx->dp, rec = 2 * dp + 16, hs = dp + 4;
     unsigned char *ws = ctx->route_ws;
     unsigned char *top_rec = ws + g.o_top_rec;
@@ -2157,13 +2188,13 @@ static int launch_route_coherent(nnd_ctx *ctx, const rp_route_io &io, const rp_r
     auto kbkt = k_route_bucket<NC>;
     static bool attr_dev[64] = {false};
     if (!attr_dev[ctx->p.device & 63]) {
-        NND_HIP_CHECK(hipFuncSetAttribute((const void *)ktop, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        NND_HIP_CHECK(hipFuncSetAttribute((const void *)kbkt, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        FOREST_HIP_CHECK(hipFuncSetAttribute((const void *)ktop, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        FOREST_HIP_CHECK(hipFuncSetAttribute((const void *)kbkt, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_dev[ctx->p.device & 63] = true;
     }
     int n_cu = 0;
-    if (device_cus(ctx, &n_cu)) return 1;
-    NND_HIP_CHECK(hipMemsetAsync(bcount, 0, g.o_bstart - g.o_bcount, ctx->stream));  // counts and cursors
+    if (device_cus(ctx, &n_cu)) return FOREST_ERROR;
+    FOREST_HIP_CHECK(hipMemsetAsync(bcount, 0, g.o_bstart - g.o_bcount, ctx->stream));  // counts and cursors
     hipLaunchKernelGGL(k_top_heap, dim3((unsigned)io.T), dim3(256), 0, ctx->stream, io.pack, rec, dp, io.roots, g.L1, top_rec, top_node,
                        bucket_root);
     hipLaunchKernelGGL(k_bucket_tables, dim3((unsigned)g.nb), dim3(64), 0, ctx->stream, io.pack, rec, dp, bucket_root, g.R, bt_cnt, bt_node,
@@ -2182,27 +2213,27 @@ static int launch_route_coherent(nnd_ctx *ctx, const rp_route_io &io, const rp_r
                        io.nrows, io.row_lo, g.L1, bstart, bcursor, io.bucket_rows, ctx->nr2, ctx->p.metric, (uint32_t *)io.bucket_ab);
     const size_t smem2 = (size_t)g.R * rec + sizeof(int32_t) * 3 * (size_t)(g.R + 8) + sizeof(uint32_t) * (size_t)g.chunk;
     int per_cu = 0;
-    NND_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kbkt, 1024, smem2));
+    FOREST_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kbkt, 1024, smem2));
     if (per_cu < 1) per_cu = 1;
     int64_t blocks2 = (int64_t)n_cu * per_cu;
     if (blocks2 > g.max_items) blocks2 = g.max_items;
     hipLaunchKernelGGL(kbkt, dim3((unsigned)blocks2), dim3(1024), smem2, ctx->stream, ctx->xp, ctx->xh, ctx->nr2, ctx->p.metric, dp, ctx->n,
                        io.row_lo, io.nrows, g.L1, g.chunk, io.pack, io.hf, hs, items, n_items, bstart, io.bucket_rows, (const uint32_t *)io.bucket_ab, g.R, bt_cnt, bt_node,
                        bt_rec, bt_cell, ctx->tree_seed, io.cell_count, io.cell_of, io.rank_of, ctx->mean + ctx->dp);
-    NND_HIP_CHECK(hipGetLastError());
-    return 0;
+    FOREST_HIP_CHECK(hipGetLastError());
+    return FOREST_OK;
 }
 
-// pass 1 by bucket, pass 2 from LDS (see "coherent routing" above).  Returns 0 / 1 / 2 (not available for this geometry).
-static int route_coherent(nnd_ctx *ctx, const rp_route_io &io) {
+// pass 1 by bucket, pass 2 from LDS (see "coherent routing" above).  FOREST_FALLBACK: not available for this geometry.
+static forest_rc route_coherent(nnd_ctx *ctx, const rp_route_io &io) {
     const int dp = ctx->dp;
-    if (dp % 32 != 0 || dp > 256 || io.T < 1 || io.T > 4096) return 2;
+    if (dp % 32 != 0 || dp > 256 || io.T < 1 || io.T > NND_ROUTE_TREES_MAX) return FOREST_FALLBACK;
     const rp_route_geom g = route_geometry(dp, io.T, io.nrows, io.n_cells);
     if (g.total > ctx->route_ws_cap) {  // grow-only
-        NND_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        if (ctx->route_ws) { NND_HIP_CHECK(hipFree(ctx->route_ws)); ctx->route_ws = nullptr; }
+        FOREST_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        if (ctx->route_ws) { FOREST_HIP_CHECK(hipFree(ctx->route_ws)); ctx->route_ws = nullptr; }
         ctx->route_ws_cap = 0;
-        NND_HIP_CHECK(hipMalloc((void **)&ctx->route_ws, g.total + g.total / 4));
+        FOREST_HIP_CHECK(hipMalloc((void **)&ctx->route_ws, g.total + g.total / 4));
         ctx->route_ws_cap = g.total + g.total / 4;
     }
     switch (dp / 32) {
@@ -2216,7 +2247,7 @@ static int route_coherent(nnd_ctx *ctx, const rp_route_io &io) {
         case 8: return launch_route_coherent<8>(ctx, io, g);
         default: break;
     }
-    return 2;
+    return FOREST_FALLBACK;
 }
 
 __global__ void k_iota_i32(int32_t *__restrict__ out, int n, int base) {
@@ -2226,61 +2257,50 @@ __global__ void k_iota_i32(int32_t *__restrict__ out, int n, int base) {
 
 // The top of the view's trees from the sample (level passes + recording finisher), then the cells = leaves of the recorded
 // trees, numbered in position order (tree-major): ctx->scan_out[p] = cell number of the cell that starts at sample
-// position p, ctx->cell_depth filled.  Returns 0, 1, or 2 (fall back to the whole-set passes).
-static int forest_tops(nnd_ctx *ctx, forest_view &v, int32_t *n_cells_out) {
-    int32_t *scan_total = (int32_t *)(ctx->counters + CNT_SCRATCH);
-    const int rc = forest_levels(ctx, v);
+// position p, ctx->cell_depth filled.  FOREST_FALLBACK: to the whole-set passes.
+static forest_rc forest_tops(nnd_ctx *ctx, forest_view &v, int32_t *n_cells_out) {
+    forest_rc rc = forest_levels(ctx, v);
     if (rc) return rc;
-    if (run_scan(ctx, 1, nullptr, ctx->leaf_flag, scan_total, v.P, v.n)) return 1;
-    NND_HIP_CHECK(hipMemcpyAsync(ctx->h_pin + 35, scan_total, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    NND_HIP_CHECK(nnd_sync_spin(ctx));
-    const int32_t n_cells = *(const int32_t *)(ctx->h_pin + 35);
-    if (n_cells > ctx->cell_cap) {
-        if (nnd_knob("NND_FOREST_DEBUG")) fprintf(stderr, "forest: fallback at line %d\n", __LINE__);
-        return 2;
-    }
+    int32_t n_cells = 0;
+    if ((rc = run_scan(ctx, 1, nullptr, ctx->leaf_flag, nnd_scan_total(ctx), v.P, v.rows.n)) || (rc = read_scan_total(ctx, &n_cells))) return rc;
+    if (n_cells > ctx->cell_cap) return forest_fallback("the recorded trees have more cells than the cell tables hold");
     hipLaunchKernelGGL(k_cell_depths, dim3((unsigned)((v.P + 255) / 256)), dim3(256), 0, ctx->stream, ctx->leaf_flag, ctx->scan_out,
                        ctx->s_leaf_depth, v.P, ctx->cell_depth);
-    NND_HIP_CHECK(hipGetLastError());
+    FOREST_HIP_CHECK(hipGetLastError());
     *n_cells_out = n_cells;
-    return 0;
+    return FOREST_OK;
 }
 
 // cells (counts known) -> positions: cell_start = exclusive scan, work lists by size class, points placed, cells finished.
 // n_rows_routed rows x T trees were routed (cell_of / rank_of as rp_route_io lays them out); perm is written at
 // [0, sum of the counts).
-static int forest_place_finish(nnd_ctx *ctx, int32_t n_cells, int T, int64_t row_lo, int64_t nrows, const int32_t *cell_of,
-                               const int32_t *rank_of, int64_t P_used, rp_tree_map tm) {
-    int32_t *scan_total = (int32_t *)(ctx->counters + CNT_SCRATCH);
+static forest_rc forest_place_finish(nnd_ctx *ctx, int32_t n_cells, int T, int64_t row_lo, int64_t nrows, const int32_t *cell_of,
+                                     const int32_t *rank_of, int64_t P_used, rp_tree_map tm) {
     // cell_start = exclusive scan of the counts (k_scan_blocks scans in place: copy first)
-    NND_HIP_CHECK(hipMemcpyAsync(ctx->cell_start, ctx->cell_count, sizeof(int32_t) * (size_t)n_cells, hipMemcpyDeviceToDevice, ctx->stream));
-    if (scan_i32_inplace(ctx, ctx->cell_start, n_cells, scan_total)) return 1;
-    NND_HIP_CHECK(hipMemsetAsync(ctx->leaf_flag, 0, (size_t)P_used, ctx->stream));
-    long long *counts = ctx->counters + CNT_SCRATCH + 1;  // [0] workgroup list (what launch_finishers reads), [1] big, [2] small
-    NND_HIP_CHECK(hipMemsetAsync(counts, 0, 3 * sizeof(long long), ctx->stream));
-    int32_t *fin_start = ctx->seg_child + 2 * ctx->max_segs, *fin_len = fin_start + ctx->max_segs, *fin_depth = fin_len + ctx->max_segs;
-    int32_t *big_start = ctx->seg_start[0], *big_len = ctx->seg_len[0], *big_depth = ctx->seg_nleft;
+    FOREST_HIP_CHECK(hipMemcpyAsync(ctx->cell_start, ctx->cell_count, sizeof(int32_t) * (size_t)n_cells, hipMemcpyDeviceToDevice, ctx->stream));
+    if (scan_i32_inplace(ctx, ctx->cell_start, n_cells, nnd_scan_total(ctx))) return FOREST_ERROR;
+    FOREST_HIP_CHECK(hipMemsetAsync(ctx->leaf_flag, 0, (size_t)P_used, ctx->stream));
+    long long *counts = ctx->counters + CNT_FIN_COUNT;  // then CNT_BIG_COUNT, CNT_SMALL_COUNT: k_cell_lists counts its three classes
+    FOREST_HIP_CHECK(hipMemsetAsync(counts, 0, 3 * sizeof(long long), ctx->stream));
+    const nnd_work_list fin = nnd_fin_list(ctx), big = nnd_big_list(ctx), small = nnd_small_list(ctx);
     hipLaunchKernelGGL(k_cell_lists, dim3((unsigned)((n_cells + 255) / 256)), dim3(256), 0, ctx->stream, ctx->cell_count, ctx->cell_start,
-                       ctx->cell_depth, (int)n_cells, FIN_SMALL, FIN_MAX, ctx->small_list, fin_start, fin_len, fin_depth, big_start,
-                       big_len, big_depth, ctx->cell_cap, counts);
+                       ctx->cell_depth, (int)n_cells, FIN_SMALL, FIN_MAX, small.start, fin.start, fin.len, fin.depth, big.start,
+                       big.len, big.depth, small.len - small.start, counts);
     if (cell_of)
         hipLaunchKernelGGL(k_place, dim3((unsigned)((nrows + 255) / 256), (unsigned)T), dim3(256), 0, ctx->stream, cell_of, rank_of,
                            ctx->cell_start, nrows, row_lo, ctx->perm[0]);
-    NND_HIP_CHECK(hipGetLastError());
-    NND_HIP_CHECK(hipMemcpyAsync(ctx->h_pin + 36, counts + 1, 2 * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
-    NND_HIP_CHECK(nnd_sync_spin(ctx));
-    const long long n_big = ctx->h_pin[36], n_small = ctx->h_pin[37];
-    if (n_big > ctx->max_segs) {
-        if (nnd_knob("NND_FOREST_DEBUG")) fprintf(stderr, "forest: fallback at line %d\n", __LINE__);
-        return 2;
-    }
-    if (launch_finishers(ctx, ctx->perm[0], ctx->perm[1], big_start, big_len, big_depth, 0, n_big, n_small, tm)) return 1;
+    FOREST_HIP_CHECK(hipGetLastError());
+    FOREST_HIP_CHECK(hipMemcpyAsync(&ctx->h_pin->n_big, ctx->counters + CNT_BIG_COUNT, 2 * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+    FOREST_HIP_CHECK(nnd_sync_spin(ctx));
+    const long long n_big = ctx->h_pin->n_big, n_small = ctx->h_pin->n_small;
+    if (n_big > ctx->max_segs) return forest_fallback("more over-long cells than the big work list holds");
+    if (launch_finishers(ctx, ctx->perm[0], ctx->perm[1], big, 0, n_big, n_small, tm)) return FOREST_ERROR;
     ctx->cur = 0;
-    return 0;
+    return FOREST_OK;
 }
 
-// sample forest -> routing pass -> cells -> finishers.  Returns 0, 1, or 2 (fall back to the whole-set passes).
-static int forest_by_routing(nnd_ctx *ctx, int *levels_out) {
+// sample forest -> routing pass -> cells -> finishers.  FOREST_FALLBACK: to the whole-set passes.
+static forest_rc forest_by_routing(nnd_ctx *ctx, int *levels_out) {
     const int64_t n = ctx->n, P = ctx->P, M = ctx->s_m, Ps = (int64_t)ctx->p.n_trees * M;
     const int T = ctx->p.n_trees, dp = ctx->dp;
     hipLaunchKernelGGL(k_gather_sample, dim3((unsigned)((M + 15) / 16)), dim3(256), 0, ctx->stream, ctx->xp, ctx->xh, ctx->nr2,
@@ -2288,72 +2308,66 @@ static int forest_by_routing(nnd_ctx *ctx, int *levels_out) {
     // sample subtrees of <= 512 members leave the level-synchronous passes for the (one-wave) recording finisher;
     // 2048 (+ a workgroup class) means 4 fewer levels but a slower finisher: 6.9-7.2 ms vs 6.6 ms per forest at 1 M points
     static const int rec_fin = [] { const char *e = nnd_knob("NND_REC_FIN"); const int r = e ? atoi(e) : FIN_SMALL; return r <= FIN_SMALL ? FIN_SMALL : FIN_MAX; }();
-    forest_view v{ctx->xs, ctx->xsh, ctx->nr2s, M, Ps, ctx->cell_leaf, rec_fin, true};
+    forest_view v{{ctx->xs, ctx->xsh, ctx->nr2s, M, ctx->cell_leaf}, Ps, rec_fin, true};
     int32_t n_cells = 0;
-    int rc = forest_tops(ctx, v, &n_cells);
+    forest_rc rc = forest_tops(ctx, v, &n_cells);
     if (rc) return rc;
-    if (n_cells + P / (ctx->p.leaf_size + 1) > ctx->max_segs) {
-        if (nnd_knob("NND_FOREST_DEBUG")) fprintf(stderr, "forest: fallback at line %d\n", __LINE__);
-        return 2;
-    }
-    NND_HIP_CHECK(hipMemsetAsync(ctx->cell_count, 0, sizeof(int32_t) * (size_t)n_cells, ctx->stream));
+    if (n_cells + P / (ctx->p.leaf_size + 1) > ctx->max_segs) return forest_fallback("cells and leaves could outgrow the segment tables");
+    FOREST_HIP_CHECK(hipMemsetAsync(ctx->cell_count, 0, sizeof(int32_t) * (size_t)n_cells, ctx->stream));
     const int64_t n_packed = v.n_low + (ctx->node_cap - v.high_lo);
     rp_pack_map mp{v.n_low, v.high_lo, 0, 0, nullptr};
     hipLaunchKernelGGL(k_pack_nodes, dim3((unsigned)((n_packed + 15) / 16)), dim3(256), 0, ctx->stream, ctx->node_hh, ctx->node_hf,
                        dp + 4, ctx->node_child, ctx->scan_out, dp, n_packed, mp, ctx->node_pack, ctx->node_hfc);
-    int32_t *roots = ctx->route_roots;
+    int32_t *roots = ctx->route_roots;  // (T <= NND_ROUTE_TREES_MAX words, or route_coherent declines)
     hipLaunchKernelGGL(k_iota_i32, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, ctx->stream, roots, T, 0);
     // ctx->inv (segment table of the sample passes) and ctx->scan_out (the cell numbers: baked into the records by now)
     // are free: they hold the (tree, point) codes and the bucket-sorted point lists of the coherent form
     rp_route_io io{ctx->node_pack, ctx->node_hfc, roots, T, 0, n, n_cells, ctx->cell_count, ctx->pos_seg[0], ctx->pos_seg[1], ctx->inv, ctx->scan_out, ctx->perm[1]};
-    int rrc = 2;
-    if (!(ctx->p.flags & NND_FLAG_TEST_ROUTE_PLAIN)) rrc = route_coherent(ctx, io);
-    if (rrc == 2) rrc = route_plain(ctx, io, v);
-    if (rrc) return rrc;
+    rc = FOREST_FALLBACK;
+    if (!(ctx->p.flags & NND_FLAG_TEST_ROUTE_PLAIN)) rc = route_coherent(ctx, io);
+    if (rc == FOREST_FALLBACK) rc = route_plain(ctx, io, v);
+    if (rc) return rc;
     rc = forest_place_finish(ctx, n_cells, T, 0, n, ctx->pos_seg[0], ctx->pos_seg[1], P, rp_tree_map{});
     if (rc) return rc;
     *levels_out = v.depth;
     ctx->stats.n_cells = n_cells;
-    return 0;
+    return FOREST_OK;
 }
 
 // leaf tables of a finished position space [0, P): leaves = runs between leaf marks; tree t's leaves are those from
 // position t * n (tree_begin == nullptr) or tree_begin[t] on
-static int forest_leaf_tables(nnd_ctx *ctx, int64_t P, int T, const int32_t *tree_begin_dev) {
+static forest_rc forest_leaf_tables(nnd_ctx *ctx, int64_t P, int T, const int32_t *tree_begin_dev) {
     const int64_t n = ctx->n;
     const int leaf_size = ctx->p.leaf_size;
-    int32_t *scan_total = (int32_t *)(ctx->counters + CNT_SCRATCH);  // device scratch word(s)
     unsigned gridP = (unsigned)((P + 255) / 256);
-    if (run_scan(ctx, 1, nullptr, ctx->leaf_flag, scan_total, P, n)) return 1;
-    NND_HIP_CHECK(hipMemcpyAsync(ctx->h_pin + 35, scan_total, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    NND_HIP_CHECK(nnd_sync_spin(ctx));
-    const int32_t nl = *(const int32_t *)(ctx->h_pin + 35);
+    int32_t nl = 0;
+    if (run_scan(ctx, 1, nullptr, ctx->leaf_flag, nnd_scan_total(ctx), P, n) || read_scan_total(ctx, &nl)) return FOREST_ERROR;
     ctx->n_leaves = nl;
     if (nl + 1 > ctx->leaf_cap) {  // grow-only: repeated builds on one handle do not pay hipFree / hipMalloc (both synchronise)
-        if (ctx->leaf_start) { NND_HIP_CHECK(hipFree(ctx->leaf_start)); ctx->leaf_start = nullptr; }
-        if (ctx->leaf_len) { NND_HIP_CHECK(hipFree(ctx->leaf_len)); ctx->leaf_len = nullptr; }
+        if (ctx->leaf_start) { FOREST_HIP_CHECK(hipFree(ctx->leaf_start)); ctx->leaf_start = nullptr; }
+        if (ctx->leaf_len) { FOREST_HIP_CHECK(hipFree(ctx->leaf_len)); ctx->leaf_len = nullptr; }
         ctx->leaf_cap = (int64_t)(nl + 1) + (nl + 1) / 4;
-        NND_HIP_CHECK(hipMalloc((void **)&ctx->leaf_start, sizeof(int32_t) * (size_t)ctx->leaf_cap));
-        NND_HIP_CHECK(hipMalloc((void **)&ctx->leaf_len, sizeof(int32_t) * (size_t)ctx->leaf_cap));
+        FOREST_HIP_CHECK(hipMalloc((void **)&ctx->leaf_start, sizeof(int32_t) * (size_t)ctx->leaf_cap));
+        FOREST_HIP_CHECK(hipMalloc((void **)&ctx->leaf_len, sizeof(int32_t) * (size_t)ctx->leaf_cap));
     }
     hipLaunchKernelGGL(k_leaf_starts, dim3(gridP), dim3(256), 0, ctx->stream, ctx->leaf_flag, ctx->scan_out, P,
                        ctx->leaf_start);
     // leaf lengths, the longest leaf and the per-tree leaf offsets stay on the device; the host reads T + 1 words
     // (the full tables are fetched lazily, only when a leaf has to be cut or the caller asks for the leaf array)
-    int32_t *max_len_dev = (int32_t *)(ctx->counters + CNT_SCRATCH + 2);
-    NND_HIP_CHECK(hipMemsetAsync(max_len_dev, 0, sizeof(long long), ctx->stream));
+    int32_t *max_len_dev = (int32_t *)(ctx->counters + CNT_MAX_LEAF);
+    FOREST_HIP_CHECK(hipMemsetAsync(max_len_dev, 0, sizeof(long long), ctx->stream));
     // (every tree's first position starts a leaf, so a leaf never crosses a tree boundary; with tree_begin the clamp of
     // k_leaf_lens to t * n boundaries is switched off by handing it one "tree" of P positions)
     hipLaunchKernelGGL(k_leaf_lens, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, ctx->stream, ctx->leaf_start,
                        (int64_t)nl, tree_begin_dev ? P : n, P, ctx->leaf_len, max_len_dev);
     hipLaunchKernelGGL(k_tree_leaf_begin, dim3((T + 63) / 64), dim3(64), 0, ctx->stream, ctx->scan_out, T, n, tree_begin_dev, P, nl, ctx->tree_begin_dev);
-    NND_HIP_CHECK(hipGetLastError());
-    NND_HIP_CHECK(hipMemcpyAsync(ctx->h_tree_begin, ctx->tree_begin_dev, sizeof(long long) * T, hipMemcpyDeviceToHost, ctx->stream));
-    NND_HIP_CHECK(hipMemcpyAsync(ctx->h_pin + 36, max_len_dev, sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
-    NND_HIP_CHECK(nnd_sync_spin(ctx));
+    FOREST_HIP_CHECK(hipGetLastError());
+    FOREST_HIP_CHECK(hipMemcpyAsync(ctx->h_tree_begin, ctx->tree_begin_dev, sizeof(long long) * T, hipMemcpyDeviceToHost, ctx->stream));
+    FOREST_HIP_CHECK(hipMemcpyAsync(ctx->h_pin->max_leaf, max_len_dev, sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+    FOREST_HIP_CHECK(nnd_sync_spin(ctx));
     ctx->h_leaf_valid = false;
     int32_t mx = leaf_size;  // rp_trees.py:2548
-    const int32_t longest = *(const int32_t *)(ctx->h_pin + 36);
+    const int32_t longest = ctx->h_pin->max_leaf[0];
     if (longest > mx) mx = longest;
     ctx->tree_leaf_begin.assign(T + 1, nl);
     for (int t = 0; t < T; t++) ctx->tree_leaf_begin[t] = ctx->h_tree_begin[t];
@@ -2361,7 +2375,7 @@ static int forest_leaf_tables(nnd_ctx *ctx, int64_t P, int T, const int32_t *tre
     ctx->stats.n_leaves = nl;
     ctx->forest_built = true;
     ctx->forest_gen++;
-    return 0;
+    return FOREST_OK;
 }
 
 int nnd_launch_forest(nnd_ctx *ctx) {
@@ -2377,14 +2391,15 @@ int nnd_launch_forest(nnd_ctx *ctx) {
         ctx->set_error("n_trees * n = %lld exceeds the int32 position space", (long long)P);
         return 1;
     }
-    int levels = 0, rc = 2;
+    int levels = 0;
+    forest_rc rc = FOREST_FALLBACK;
     if (ctx->s_m > 0) rc = forest_by_routing(ctx, &levels);
     if (nnd_knob("NND_FOREST_DEBUG"))
         fprintf(stderr, "forest: n=%lld T=%d s_m=%lld routing rc=%d levels=%d node_cap=%lld cell_cap=%lld max_segs=%lld\n", (long long)n, T,
                 (long long)ctx->s_m, rc, levels, (long long)ctx->node_cap, (long long)ctx->cell_cap, (long long)ctx->max_segs);
-    if (rc == 1) return 1;
-    if (rc == 2) {  // small point set, very wide rows, or the recorded tree outgrew its tables: whole-set passes
-        forest_view v{ctx->xp, ctx->xh, ctx->nr2, n, P, leaf_size, FIN_MAX, false};
+    if (rc == FOREST_ERROR) return 1;
+    if (rc == FOREST_FALLBACK) {  // small point set, very wide rows, or the recorded tree outgrew its tables: whole-set passes
+        forest_view v{whole_set_rows(ctx), P, FIN_MAX, false};
         if (forest_levels(ctx, v)) return 1;
         ctx->cur = v.cur;
         levels = v.depth;
@@ -2397,7 +2412,7 @@ int nnd_launch_forest(nnd_ctx *ctx) {
 // ---------------------------------------------------------------------------------------------------------------------
 // The forest of the row-sharded build, sharded BY CELL (shard.hip drives the sequence; every rank runs it):
 //   tops      rank r builds the top of ITS trees (split by tree) on the GLOBAL sample -- hashes keyed by the global tree
-//             number and position (forest_view::tree_bias), so the forest does not depend on the number of ranks;
+//             number and position (forest_view::tm.tree_bias), so the forest does not depend on the number of ranks;
 //   pack      the recorded nodes, compacted and rebased, go into this rank's slice of the table of ALL trees
 //             (all-gathered by the caller), cells renumbered owner-major;
 //   route     every rank routes ITS rows through ALL trees (coherent passes);
@@ -2424,17 +2439,17 @@ int nnd_forest_tops(nnd_ctx *ctx, int T_loc, int tree_bias, nnd_tops_info *out) 
     out->n_low = out->high_lo = 0;
     if (T_loc <= 0) return 0;
     const int64_t M = ctx->s_m;
-    forest_view v{ctx->xs, ctx->xsh, ctx->nr2s, M, (int64_t)T_loc * M, ctx->cell_leaf, FIN_SMALL, true};
+    forest_view v{{ctx->xs, ctx->xsh, ctx->nr2s, M, ctx->cell_leaf}, (int64_t)T_loc * M, FIN_SMALL, true};
     v.T = T_loc;
-    v.tree_bias = tree_bias;
+    v.tm.tree_bias = tree_bias;
     int32_t n_cells = 0;
-    const int rc = forest_tops(ctx, v, &n_cells);
+    const forest_rc rc = forest_tops(ctx, v, &n_cells);
     // rc 2: NOT an error of the build -- the single-GPU forest falls back to the whole-set passes here (nnd_launch_forest); the
     // sharded build tells the other ranks and all of them switch to the forest split by tree (shard.hip)
-    if (rc == 2) { ctx->set_error("rp-forest (sharded): the recorded tree tops outgrew their tables"); return 2; }
+    if (rc == FOREST_FALLBACK) { ctx->set_error("rp-forest (sharded): the recorded tree tops outgrew their tables"); return FOREST_FALLBACK; }
     if (rc) return rc;
     // first cell of every local tree (cells are numbered tree-major): per-tree cell counts for the owner-major renumbering
-    int32_t *tcb = ctx->route_roots + 2048;  // scratch words behind the root table
+    int32_t *tcb = nnd_route_tree_cells(ctx);
     hipLaunchKernelGGL(k_tree_cell_begin, dim3((T_loc + 63) / 64), dim3(64), 0, ctx->stream, ctx->scan_out, T_loc, M, tcb);
     NND_HIP_CHECK(hipMemcpyAsync(ctx->h_tree_begin, tcb, sizeof(int32_t) * T_loc, hipMemcpyDeviceToHost, ctx->stream));
     NND_HIP_CHECK(nnd_sync_spin(ctx));
@@ -2463,8 +2478,8 @@ int nnd_forest_route_rows(nnd_ctx *ctx, const unsigned char *pack_all, const flo
     if (nrows <= 0 || T_all <= 0) return 0;
     if ((int64_t)T_all * nrows > ctx->P) { ctx->set_error("rp-forest (sharded): %d trees x %lld rows exceed the position space of %lld", T_all, (long long)nrows, (long long)ctx->P); return 1; }
     rp_route_io io{pack_all, hf_all, roots_dev, T_all, row_lo, nrows, n_cells_all, cell_count_all, ctx->pos_seg[0], ctx->pos_seg[1], ctx->inv, ctx->scan_out, ctx->perm[1]};
-    const int rc = route_coherent(ctx, io);
-    if (rc == 2) { ctx->set_error("rp-forest (sharded): the routing passes do not support this row width"); return 1; }
+    const forest_rc rc = route_coherent(ctx, io);
+    if (rc == FOREST_FALLBACK) { ctx->set_error("rp-forest (sharded): the routing passes do not support this row width"); return 1; }
     return rc;
 }
 
@@ -2491,7 +2506,7 @@ __global__ void k_dest_offsets(const int32_t *__restrict__ cell_scan, const int3
 int nnd_forest_route_records(nnd_ctx *ctx, int T_all, int64_t row_lo, int64_t nrows, int32_t n_cells_all, int32_t *cell_count_all /* in: counts, out: exclusive scan */,
                              int32_t *count_copy /* out: the counts (sent to the cells' owners) */,
                              const int32_t *dest_cell_dev, int G, int32_t *rec_cell, int32_t *rec_row, long long *dest_off_dev) {
-    int32_t *scan_total = (int32_t *)(ctx->counters + CNT_SCRATCH);
+    int32_t *scan_total = nnd_scan_total(ctx);
     NND_HIP_CHECK(hipMemcpyAsync(count_copy, cell_count_all, sizeof(int32_t) * (size_t)n_cells_all, hipMemcpyDeviceToDevice, ctx->stream));
     if (scan_i32_inplace(ctx, cell_count_all, n_cells_all, scan_total)) return 1;
     if (nrows > 0)
@@ -2544,7 +2559,7 @@ int nnd_forest_finish_owned(nnd_ctx *ctx, const int32_t *rec_cell, const int32_t
     if (n_rec > ctx->P || n_cells_own > ctx->cell_cap || n_cells_own + n_rec / (ctx->p.leaf_size + 1) > ctx->max_segs) {
         ctx->set_error("rp-forest (sharded): %lld point-trees / %d cells exceed this rank's forest tables (%lld positions)", (long long)n_rec, n_cells_own,
                        (long long)ctx->P);
-        return 2;  // (as above: the ranks agree to build this forest split by tree)
+        return FOREST_FALLBACK;  // (as above: the ranks agree to build this forest split by tree)
     }
     if (n_cells_own <= 0 || n_rec <= 0) {  // (a rank that owns no cell: nothing to seed from)
         ctx->forest_built = true;
@@ -2555,14 +2570,13 @@ int nnd_forest_finish_owned(nnd_ctx *ctx, const int32_t *rec_cell, const int32_t
                        ctx->cell_depth);
     // positions: cell_start = exclusive scan of the counts; rows placed through per-cell cursors (the order inside a cell is
     // immaterial: the finisher is order independent)
-    int32_t *scan_total = (int32_t *)(ctx->counters + CNT_SCRATCH);
     NND_HIP_CHECK(hipMemcpyAsync(ctx->cell_start, ctx->cell_count, sizeof(int32_t) * (size_t)n_cells_own, hipMemcpyDeviceToDevice, ctx->stream));
-    if (scan_i32_inplace(ctx, ctx->cell_start, n_cells_own, scan_total)) return 1;
-    int32_t *cursor = ctx->small_list;  // (free until k_cell_lists: 3 * cell_cap words)
+    if (scan_i32_inplace(ctx, ctx->cell_start, n_cells_own, nnd_scan_total(ctx))) return 1;
+    int32_t *cursor = nnd_small_list(ctx).start;  // placement cursor per own cell: the one-wave list is free until k_cell_lists fills it
     NND_HIP_CHECK(hipMemsetAsync(cursor, 0, sizeof(int32_t) * (size_t)n_cells_own, ctx->stream));
     hipLaunchKernelGGL(k_owner_place, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, ctx->stream, rec_cell, rec_row, n_rec, cell_base, ctx->cell_start,
                        cursor, ctx->perm[0]);
-    int32_t *tpb = ctx->route_roots + 2048 + 64;  // (T_all + 1) position of every tree's first own cell
+    int32_t *tpb = nnd_route_tree_pos(ctx);  // (T_all + 1) position of every tree's first own cell
     hipLaunchKernelGGL(k_tree_pos_begin, dim3((T_all + 64) / 64), dim3(64), 0, ctx->stream, ctx->cell_start, tree_first_cell_dev, T_all, n_cells_own,
                        (int32_t)n_rec, tpb);
     NND_HIP_CHECK(hipGetLastError());
@@ -2570,8 +2584,8 @@ int nnd_forest_finish_owned(nnd_ctx *ctx, const int32_t *rec_cell, const int32_t
     tm.tree_begin = tpb;
     tm.n_tree_begin = T_all;
     // (forest_place_finish scans the counts again: cheap, and it keeps one code path for the work lists)
-    const int rc = forest_place_finish(ctx, n_cells_own, T_all, 0, 0, nullptr, nullptr, n_rec, tm);
-    if (rc == 2) { ctx->set_error("rp-forest (sharded): too many over-long cells"); return 2; }
+    const forest_rc rc = forest_place_finish(ctx, n_cells_own, T_all, 0, 0, nullptr, nullptr, n_rec, tm);
+    if (rc == FOREST_FALLBACK) { ctx->set_error("rp-forest (sharded): too many over-long cells"); return FOREST_FALLBACK; }
     if (rc) return rc;
     ctx->stats.n_cells = n_cells_own;
     return forest_leaf_tables(ctx, n_rec, T_all, tpb);
@@ -2582,7 +2596,7 @@ int nnd_forest_finish_owned(nnd_ctx *ctx, const int32_t *rec_cell, const int32_t
 void nnd_forest_stable_partition(nnd_ctx *ctx, int64_t n, const int32_t *ord, const int32_t *pos, uint8_t *side, const int32_t *seg_start,
                                  const int32_t *seg_len, int n_segs, int32_t *nleft, const int32_t *seg_child, int32_t *ord_out,
                                  int32_t *pos_out) {
-    int32_t *scan_total = (int32_t *)(ctx->counters + CNT_SCRATCH);
+    int32_t *scan_total = nnd_scan_total(ctx);
     const int nb = (int)((n + SCAN_TILE - 1) / SCAN_TILE);
     hipLaunchKernelGGL(k_scan_reduce, dim3(nb), dim3(SCAN_BLOCK), 0, ctx->stream, 0, pos, side, n, ctx->scan_blk, (const int32_t *)nullptr,
                        (const uint8_t *)nullptr, n);

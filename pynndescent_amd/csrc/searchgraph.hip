@@ -299,12 +299,12 @@ int nnd_search_graph_impl(nnd_ctx *ctx, const int32_t *idx_src, const float *dis
     if (nnd_launch_diversify_csr(ctx, ptrF, f_ind, f_dat, (int *)(misc + 4), &orv, aware ? deg : nullptr)) return 1;
     // ---- union max(F', F'^T) without its diagonal: keyed edges, sorted, duplicates folded
     hipLaunchKernelGGL(k_sg_edge_keys, dim3(gn), dim3(256), 0, s, ptrF, f_ind, f_dat, n, keys, vals, misc);
-    NND_HIP_CHECK(hipMemcpyAsync(ctx->h_pin + 52, misc, 40, hipMemcpyDeviceToHost, s));
-    NND_HIP_CHECK(hipMemcpyAsync(ctx->h_pin + 57, ptrF + n, 4, hipMemcpyDeviceToHost, s));
+    NND_HIP_CHECK(hipMemcpyAsync(ctx->h_pin->sg_misc, misc, sizeof(ctx->h_pin->sg_misc), hipMemcpyDeviceToHost, s));
+    NND_HIP_CHECK(hipMemcpyAsync(&ctx->h_pin->sg_forward_nnz, ptrF + n, 4, hipMemcpyDeviceToHost, s));
     NND_HIP_CHECK(nnd_sync_spin(ctx));  // the host needs the edge counts to size the sort and the launches behind it
-    const int64_t m_live = (int64_t)ctx->h_pin[52], nnz_fp = (int64_t)ctx->h_pin[53];
-    const int64_t forward_nnz = (int64_t) * (const int32_t *)(ctx->h_pin + 57);
-    if ((int)ctx->h_pin[56] != 0) { ctx->set_error("nnd_search_graph: %d rows are longer than the pass handles", (int)ctx->h_pin[56]); return 1; }
+    const int64_t m_live = (int64_t)ctx->h_pin->sg_misc[0], nnz_fp = (int64_t)ctx->h_pin->sg_misc[1];
+    const int64_t forward_nnz = (int64_t)ctx->h_pin->sg_forward_nnz;
+    if ((int)ctx->h_pin->sg_misc[4] != 0) { ctx->set_error("nnd_search_graph: %d rows are longer than the pass handles", (int)ctx->h_pin->sg_misc[4]); return 1; }
     const int64_t n_keyed = 2 * forward_nnz;
     // key bits that matter: the 32 of the column + those of a row number < n, one to spare: the dead keys (all ones) then have
     // a "row" of all ones in the sorted bits, larger than any live row, and still sort last
@@ -321,11 +321,11 @@ int nnd_search_graph_impl(nnd_ctx *ctx, const int32_t *idx_src, const float *dis
         hipLaunchKernelGGL(k_sg_heads, dim3((unsigned)((m_live + 255) / 256)), dim3(256), 0, s, keys2, m_live, flag);
         if (sg_scan(ctx, flag, pos, m_live, bsum)) return 1;
         hipLaunchKernelGGL(k_sg_unique, dim3((unsigned)((m_live + 255) / 256)), dim3(256), 0, s, keys2, vals2, m_live, pos, u_ind, u_dat, cnt);
-        NND_HIP_CHECK(hipMemcpyAsync(ctx->h_pin + 58, pos + m_live, 4, hipMemcpyDeviceToHost, s));
+        NND_HIP_CHECK(hipMemcpyAsync(&ctx->h_pin->sg_union_nnz, pos + m_live, 4, hipMemcpyDeviceToHost, s));
     }
     if (sg_scan(ctx, cnt, uptr, n, bsum)) return 1;
     NND_HIP_CHECK(nnd_sync_spin(ctx));
-    if (m_live > 0) union_nnz = (int64_t) * (const int32_t *)(ctx->h_pin + 58);
+    if (m_live > 0) union_nnz = (int64_t)ctx->h_pin->sg_union_nnz;
     // ---- degree_prune (1606-1609) and the final compaction; (graph != 0) keeps the pattern only (1611)
     const int max_degree = (int)nearbyintf(multiplier * (float)n_neighbors);  // np.round: half to even
     if (union_nnz > 0) {
@@ -334,26 +334,26 @@ int nnd_search_graph_impl(nnd_ctx *ctx, const int32_t *idx_src, const float *dis
         if (sg_scan(ctx, flag, pos, union_nnz, bsum)) return 1;
         hipLaunchKernelGGL(k_sg_final, dim3((unsigned)((union_nnz + 255) / 256)), dim3(256), 0, s, u_ind, u_dat, union_nnz, pos, out_ind);
         hipLaunchKernelGGL(k_sg_final_ptr, dim3(gn1), dim3(256), 0, s, uptr, pos, n, out_ptr, (int32_t *)(misc + 3));
-        NND_HIP_CHECK(hipMemcpyAsync(ctx->h_pin + 59, pos + union_nnz, 4, hipMemcpyDeviceToHost, s));
+        NND_HIP_CHECK(hipMemcpyAsync(&ctx->h_pin->sg_final_nnz, pos + union_nnz, 4, hipMemcpyDeviceToHost, s));
     } else {
         NND_HIP_CHECK(hipMemsetAsync(out_ptr, 0, 4 * (size_t)(n + 1), s));
     }
-    NND_HIP_CHECK(hipMemcpyAsync(ctx->h_pin + 60, misc + 2, 16, hipMemcpyDeviceToHost, s));
+    NND_HIP_CHECK(hipMemcpyAsync(&ctx->h_pin->sg_tail, misc + 2, sizeof(nnd_sg_tail), hipMemcpyDeviceToHost, s));
     NND_HIP_CHECK(hipEventRecord(e1, s));
     NND_HIP_CHECK(nnd_sync_spin(ctx));
     NND_HIP_CHECK(hipGetLastError());
     g->out_ptr = out_ptr;
     g->out_ind = out_ind;
-    g->final_nnz = union_nnz > 0 ? (int64_t) * (const int32_t *)(ctx->h_pin + 59) : 0;
+    g->final_nnz = union_nnz > 0 ? (int64_t)ctx->h_pin->sg_final_nnz : 0;
     if (st) {
         memset(st, 0, sizeof(*st));
         st->forward_nnz = forward_nnz;
         st->reverse_nnz = nnz_fp;
         st->union_nnz = union_nnz;
         st->final_nnz = g->final_nnz;
-        const uint32_t mb = *(const uint32_t *)(ctx->h_pin + 60);
+        const uint32_t mb = ctx->h_pin->sg_tail.min_dist_bits;
         st->min_distance = forward_nnz > 0 && mb != 0xFFFFFFFFu ? __builtin_bit_cast(float, mb) : 0.0f;
-        st->max_degree_out = *(const int32_t *)(ctx->h_pin + 61);
+        st->max_degree_out = ctx->h_pin->sg_tail.max_degree_out;
         (void)hipEventElapsedTime(&st->ms_device, e0, e1);
     }
     return 0;

@@ -228,7 +228,7 @@ extern "C" int32_t nnd_shard_create(nnd_shard_t *out, const nnd_params *params, 
     // rank's share of ALL trees' cells (T n / G point-trees + 25 %) and the forest is the single-GPU forest, whatever G is
     // (global tree seeds).  Otherwise: split by tree, every rank drawing its own trees.
     const int t_loc_max = (params->n_trees + G - 1) / G;
-    s->by_cell = G > 1 && params->n_trees > 0 && params->n_trees <= 1024 && t_loc_max <= 64 && params->n >= 131072 && ((params->dim + 31) & ~31) <= 256 &&
+    s->by_cell = G > 1 && params->n_trees > 0 && params->n_trees <= NND_BY_CELL_TREES_MAX && t_loc_max <= NND_BY_CELL_RANK_TREES_MAX && params->n >= 131072 && ((params->dim + 31) & ~31) <= 256 &&
                  !(params->flags & NND_FLAG_TEST_FOREST_BY_TREE);
     if (s->by_cell) {
         const int share = (int)(((int64_t)params->n_trees * 5 + 4 * G - 1) / (4 * G)) + 1;  // ceil(1.25 T / G) + 1 trees' worth of positions
@@ -671,7 +671,7 @@ static int forest_by_cell(nnd_shard_s *s, const float *x_local_dev, hipEvent_t e
         S_CTX(nnd_forest_route_records(h, T, lo, n_own, cells_all, cell_count_all, count_copy, s->maps + o_dest, G, rec_cell, rec_row, s->cvec));
         if (s->own_order && n_own > 0) {  // the owned vertices in the order of their tree-0 cells (spatially coherent visiting order)
             hipLaunchKernelGGL(k_order_from_records, dim3(256), dim3(256), 0, st, rec_row, cell_count_all, s->maps + o_oseg, G, cells_all,
-                               (const int32_t *)(h->counters + CNT_SCRATCH), s->own_order);
+                               nnd_scan_total(h), s->own_order);
             h->own_order = s->own_order;
             h->forest_gen++;  // the buffer is rewritten in place: the sampler's inverse of the visiting order (rv_pos) is stale
         }
@@ -727,7 +727,7 @@ static int forest_by_cell(nnd_shard_s *s, const float *x_local_dev, hipEvent_t e
         h->x_orig = s->x_full;
         S_CTX(nnd_prep_rows(h, s->x_full, 0, lo, false));
         S_CTX(nnd_prep_rows(h, s->x_full, hi, n, false));
-        S_HIP(hipMemcpyAsync(h->h_pin + 63, h->counters_sum + CNT_SCRATCH, sizeof(long long), hipMemcpyDeviceToHost, st));  // non-finite flag (nnd_data_nonfinite)
+        S_HIP(hipMemcpyAsync(&h->h_pin->data_flags, h->counters_sum + CNT_PREP_FLAG, sizeof(long long), hipMemcpyDeviceToHost, st));  // non-finite flag (nnd_data_nonfinite)
         t_end(h, tp, &h->stats.ms_prep, true);
         // ---- (f) the cells this rank owns: rows placed, cells finished down to leaves, leaf tables ----
         const int tf = t_begin(h);
@@ -942,11 +942,11 @@ static int shard_build(nnd_shard_s *s, const float *x_local_dev, void *x_stream,
     // next host wait (no read-back of their own)
     auto harvest = [&](int it_done) {
         if (it_done < 0 || it_done >= 64) return;
-        h->stats.join_pairs[it_done] = h->h_pin[CNT_PAIRS];
-        h->stats.join_rows[it_done] = h->h_pin[CNT_ROWS];
-        h->stats.join_active[it_done] = h->h_pin[CNT_ACTIVE];
-        h->stats.proposals[it_done] = h->h_pin[CNT_PROPOSALS];
-        h->stats.join_mfma[it_done] = h->h_pin[CNT_MFMA];
+        h->stats.join_pairs[it_done] = h->h_pin->counters[CNT_PAIRS];
+        h->stats.join_rows[it_done] = h->h_pin->counters[CNT_ROWS];
+        h->stats.join_active[it_done] = h->h_pin->counters[CNT_ACTIVE];
+        h->stats.proposals[it_done] = h->h_pin->counters[CNT_PROPOSALS];
+        h->stats.join_mfma[it_done] = h->h_pin->counters[CNT_MFMA];
     };
     static float sink;
     const double stop_at = (double)s->gp.delta * s->k * (double)s->n_total;
@@ -1087,7 +1087,7 @@ static int shard_build(nnd_shard_s *s, const float *x_local_dev, void *x_stream,
             S_CTX(nnd_launch_merge(h));
             t_end(h, tm, ms_m, false);
             hipLaunchKernelGGL(k_counters_reduce_async, dim3(1), dim3(256), 0, st, h->counters, h->counters_sum);
-            S_HIP(hipMemcpyAsync(h->h_pin, h->counters_sum, sizeof(long long) * CNT_COUNT, hipMemcpyDeviceToHost, st));
+            S_HIP(hipMemcpyAsync(h->h_pin->counters, h->counters_sum, sizeof(long long) * CNT_COUNT, hipMemcpyDeviceToHost, st));
             sec.end();
         }
         h->iter++;

@@ -4,6 +4,7 @@
 #include <mutex>
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
 
@@ -34,10 +35,81 @@ enum {
     CNT_DEGENERATE,   // rp-forest: segments whose split left one side empty
     CNT_ACTIVE_SEGS,  // rp-forest: splittable segments for the next level
     CNT_LEAVES,
-    CNT_SCRATCH,      // + 1 .. + 3: forest scratch words
+    CNT_SCRATCH,      // first of the forest's four scratch words: use the names below
     CNT_MFMA = 12,    // v_mfma_f32_16x16x4_f32 instructions issued (2048 flop each) by the join / leaf kernels
     CNT_COUNT = 16
 };
+// The rp-forest's scratch words in stripe 0 of the counter block (rpforest.hip), one name per meaning.  Names that share a
+// word are never live together: the forest runs level loop -> [recording finisher] -> [cell lists] -> finishers -> leaf tables.
+enum {
+    CNT_ACTIVE_POS = CNT_LEAVES,       // level loop: positions still in the level passes (k_children; CNT_LEAVES is not used by the forest otherwise)
+    CNT_SCAN_TOTAL = CNT_SCRATCH,      // int32: grand total of the scan that ran last (run_scan, scan_i32_inplace, nnd_forest_stable_partition)
+    CNT_FIN_COUNT = CNT_SCRATCH + 1,   // entries of the finisher work list: grows across the levels (k_children), through k_cell_lists and the big finisher
+    CNT_BIG_COUNT = CNT_SCRATCH + 2,   // k_cell_lists: cells for the global-memory finisher ...
+    CNT_SMALL_COUNT = CNT_SCRATCH + 3, // ... and cells finished one wave each (k_cell_lists counts [fin, big, small] in three adjacent words)
+    CNT_REC_FLAGS = CNT_SCRATCH + 2,   // recording finisher (after the level loop, before any cell list): two ints, [0] node-id counter, [1] overflow flag
+    CNT_MAX_LEAF = CNT_SCRATCH + 2,    // leaf tables (after the finishers): int32, longest leaf
+    CNT_MAX_STAY = CNT_SCRATCH + 3,    // level loop: longest segment that stays in the level passes (k_children)
+    CNT_PREP_FLAG = CNT_SCRATCH        // in counters_SUM, not in the stripes: bit 0 non-finite / bit 1 negative input (prep.hip; read by shard.hip, capi.hip)
+};
+static_assert(CNT_SMALL_COUNT < CNT_MFMA && CNT_MAX_STAY < CNT_MFMA, "the forest's scratch words end below CNT_MFMA");
+static_assert(CNT_BIG_COUNT == CNT_FIN_COUNT + 1 && CNT_SMALL_COUNT == CNT_FIN_COUNT + 2, "k_cell_lists counts its three classes in adjacent words");
+// What the host learns after every level of the forest's level loop: the six adjacent counter words from CNT_ACTIVE_SEGS on
+// (copied, or written to pinned memory by k_children itself).
+constexpr int NND_LEVEL_WORDS = 6;
+struct nnd_level_words {
+    long long segs;        // CNT_ACTIVE_SEGS: segments of the next level
+    long long active_pos;  // CNT_ACTIVE_POS
+    long long scan_total, fin_count, rec_flags;  // (travel along; the host reads them elsewhere)
+    long long max_stay;    // CNT_MAX_STAY
+};
+static_assert(sizeof(nnd_level_words) == NND_LEVEL_WORDS * sizeof(long long), "hand-over layout");
+static_assert(CNT_ACTIVE_POS == CNT_ACTIVE_SEGS + 1 && CNT_SCAN_TOTAL == CNT_ACTIVE_SEGS + 2 && CNT_FIN_COUNT == CNT_ACTIVE_SEGS + 3 &&
+                  CNT_REC_FLAGS == CNT_ACTIVE_SEGS + 4 && CNT_MAX_STAY == CNT_ACTIVE_SEGS + NND_LEVEL_WORDS - 1,
+              "nnd_level_words mirrors the counter layout");
+// The words k_children writes to pinned memory itself: the level's words, then the sequence number the host spins on.
+struct nnd_level_flag {
+    nnd_level_words w;
+    long long seq;
+};
+static_assert(offsetof(nnd_level_flag, seq) == NND_LEVEL_WORDS * sizeof(long long), "k_children writes seq right behind the words");
+
+// The pinned host words of a handle (nnd_ctx::h_pin): every small latency-critical read-back has a field of its own, so no
+// two of them can collide whatever order the stages run in.
+struct nnd_sg_tail { uint32_t min_dist_bits, hi0; int32_t max_degree_out, hi1; };  // searchgraph.hip misc[2..3]: low halves of two 64-bit words
+struct nnd_pin_words {
+    long long counters[CNT_COUNT];   // mirror of counters_sum (prep.hip nnd_read_counters, shard.hip)
+    nnd_level_words level;           // rpforest.hip: a level's hand-over, copy form
+    long long fin_count;             // rpforest.hip: entries of the finisher work list
+    long long n_big, n_small;        // rpforest.hip: k_cell_lists' other two counts (adjacent: one copy)
+    int32_t rec_flags[2];            // rpforest.hip: recording finisher, [0] node ids taken, [1] node tables exhausted
+    int32_t max_leaf[2];             // rpforest.hip: [0] longest leaf (the copy brings the whole 64-bit device word)
+    int32_t scan_total;              // rpforest.hip: number of leaves / cells (total of a leaf-mark scan)
+    int32_t sg_forward_nnz, sg_union_nnz, sg_final_nnz;  // searchgraph.hip: totals of its scans
+    long long sg_misc[5];            // searchgraph.hip: [0] live keys, [1] reverse nnz, [4] rows longer than the pass handles
+    nnd_sg_tail sg_tail;             // searchgraph.hip: statistics read at the end of the pass
+    long long data_flags;            // CNT_PREP_FLAG of the last prep: bit 0 non-finite, bit 1 negative (prep.hip, shard.hip -> capi.hip)
+    alignas(64) nnd_level_flag flag; // rpforest.hip: a level's hand-over, written by k_children through h_pin_dev (a cache line of its own)
+    long long spare[17];
+};
+constexpr size_t NND_PIN_WORDS = 64;
+static_assert(sizeof(nnd_pin_words) == NND_PIN_WORDS * sizeof(long long), "the pinned block is 64 words");
+static_assert(offsetof(nnd_pin_words, n_small) == offsetof(nnd_pin_words, n_big) + sizeof(long long), "one copy brings both counts");
+
+// Work lists of the forest's finishers: (start, len, depth) per entry, carved out of buffers that are free at that time.
+struct nnd_work_list { int32_t *start, *len, *depth; };
+constexpr int NND_SEG_CHILD_WORDS = 2;  // seg_child: two child ids per segment, then the finisher work list (three rows of max_segs)
+constexpr int NND_WORK_LIST_ROWS = 3;
+// route_roots: the root of every routed tree on one GPU; a by-cell sharded build (its roots live in shard.hip's maps) keeps
+// two small per-tree tables in the upper half instead.  shard.hip enables the by-cell forest within these limits only.
+constexpr int NND_ROUTE_TREES_MAX = 4096;    // trees the routing passes take
+constexpr int NND_BY_CELL_TREES_MAX = 1024;  // trees of a by-cell sharded build
+constexpr int NND_BY_CELL_RANK_TREES_MAX = 64;  // ... and of one rank's share of the tops
+constexpr int NND_ROUTE_ROOTS_WORDS = 4096;
+constexpr int NND_RR_TREE_CELLS = 2048;                                       // (trees of this rank) first cell of every local tree
+constexpr int NND_RR_TREE_POS = NND_RR_TREE_CELLS + NND_BY_CELL_RANK_TREES_MAX;  // (all trees + 1) position of every tree's first own cell
+static_assert(NND_ROUTE_TREES_MAX <= NND_ROUTE_ROOTS_WORDS && NND_RR_TREE_POS + NND_BY_CELL_TREES_MAX + 1 <= NND_ROUTE_ROOTS_WORDS,
+              "the sub-tables of route_roots fit its allocation");
 // Hot kernels add to one of NND_CNT_STRIPES copies of the counter block (stripe = workgroup id), one
 // atomic per workgroup per counter: a single shared word saturates at ~12 ns per atomic on MI355X and
 // would serialise a million-wave launch.  nnd_read_counters sums the stripes.
@@ -136,12 +208,12 @@ struct nnd_handle_s {
     int32_t *node_child = nullptr;            // (node_cap, 2) child node id, or -2 - first sample position of a cell
     unsigned char *node_pack = nullptr;       // (node_cap, 2 * dp + 16) packed records read by the routing passes (compacted ids)
     float *node_hfc = nullptr;                // (node_cap, dp + 4) node_hf compacted like node_pack (exact rechecks of the routing passes)
-    int32_t *route_roots = nullptr;           // (4096) root node of every routed tree
+    int32_t *route_roots = nullptr;           // (NND_ROUTE_ROOTS_WORDS) root node of every routed tree | sub-tables of the by-cell build (nnd_route_tree_cells / _pos)
     unsigned char *route_ws = nullptr;        // workspace of the coherent routing passes (rpforest.hip route_geometry), grow-only
     size_t route_ws_cap = 0;
     int32_t *s_leaf_depth = nullptr;          // (n_trees * s_m) depth of the cell that starts at a sample position
     int32_t *cell_count = nullptr, *cell_start = nullptr, *cell_depth = nullptr;  // (cell_cap)
-    int32_t *small_list = nullptr;            // (3, cell_cap) start / len / depth of the cells finished one wave per cell
+    int32_t *small_list = nullptr;            // (NND_WORK_LIST_ROWS, cell_cap) work list of the cells finished one wave per cell (nnd_small_list)
     int32_t *leaf_start = nullptr, *leaf_len = nullptr; // (n_leaves) after the forest is done; grow-only buffers
     double *colsum_partial = nullptr;         // prep scratch (column sums per row block), grow-only
     size_t colsum_cap = 0;
@@ -183,9 +255,9 @@ struct nnd_handle_s {
     long long *counters = nullptr;      // device NND_CNT_STRIPES x CNT_COUNT (stripe 0 doubles as scratch for single-block kernels)
     long long h_counters[CNT_COUNT] = {0};
     long long *counters_sum = nullptr;        // (CNT_COUNT) device: stripes summed by k_counters_reduce
-    long long *h_pin = nullptr;               // pinned host words for the small latency-critical read-backs
-    long long *h_pin_dev = nullptr;           // the same words as the device sees them: a kernel can hand the host a few values itself
-    long long flag_seq = 0;                   // sequence number of the last such hand-over (rpforest.hip forest_levels)
+    nnd_pin_words *h_pin = nullptr;           // pinned host words for the small latency-critical read-backs
+    nnd_pin_words *h_pin_dev = nullptr;       // the same words as the device sees them: a kernel can hand the host a few values itself
+    long long flag_seq = 0;                   // sequence number of the last such hand-over (rpforest.hip level_handover)
 
     void set_error(const char *fmt, ...) {
         va_list ap;
@@ -195,6 +267,21 @@ struct nnd_handle_s {
     }
 };
 typedef nnd_handle_s nnd_ctx;
+
+static inline int32_t *nnd_scan_total(const nnd_ctx *ctx) { return (int32_t *)(ctx->counters + CNT_SCAN_TOTAL); }
+// The three work lists of the forest's finishers.  Finisher list: behind the child ids in seg_child.  One-wave list: small_list
+// (its rows also serve as the owner's placement cursors until k_cell_lists fills them).  Big list: the level passes' segment
+// tables of half 0 and seg_nleft, free once the level loop is over.
+static inline nnd_work_list nnd_fin_list(const nnd_ctx *ctx) {
+    int32_t *s = ctx->seg_child + NND_SEG_CHILD_WORDS * ctx->max_segs;
+    return {s, s + ctx->max_segs, s + 2 * ctx->max_segs};
+}
+static inline nnd_work_list nnd_small_list(const nnd_ctx *ctx) {
+    return {ctx->small_list, ctx->small_list + ctx->cell_cap, ctx->small_list + 2 * ctx->cell_cap};
+}
+static inline nnd_work_list nnd_big_list(const nnd_ctx *ctx) { return {ctx->seg_start[0], ctx->seg_len[0], ctx->seg_nleft}; }
+static inline int32_t *nnd_route_tree_cells(const nnd_ctx *ctx) { return &ctx->route_roots[NND_RR_TREE_CELLS]; }
+static inline int32_t *nnd_route_tree_pos(const nnd_ctx *ctx) { return &ctx->route_roots[NND_RR_TREE_POS]; }
 
 // capi.hip: nnd_create with the shard geometry known up front (bounds == nullptr: a plain handle)
 int nnd_create_impl(nnd_handle_t *out, const nnd_params *p, const int64_t *bounds_host, int n_ranks, int rank);
@@ -215,7 +302,7 @@ struct nnd_tops_info {
     int64_t n_packed = 0;        // packed node records of this rank's trees
     int64_t n_low = 0, high_lo = 0;
     int32_t n_cells = 0;         // cells of this rank's trees, numbered tree-major
-    int32_t tree_cells[64] = {0};  // ... per local tree
+    int32_t tree_cells[NND_BY_CELL_RANK_TREES_MAX] = {0};  // ... per local tree
     int levels = 0;
 };
 int nnd_forest_sample_gather(nnd_ctx *ctx, int64_t j_lo, int64_t j_hi);
