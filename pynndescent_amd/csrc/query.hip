@@ -257,7 +257,9 @@ __global__ __launch_bounds__(256) void k_query(const float *__restrict__ x, cons
     };
     auto update_bound = [&]() {
         const float wd = worst();
-        bound = wd + epsilon * (wd - min_distance);  // inf while the list is not full
+        // inf while the list is not full (not through the formula: with epsilon = 0 it gives 0 * inf = NaN there, and a NaN
+        // bound ends the search at the seeds)
+        bound = wd < INFINITY ? wd + epsilon * (wd - min_distance) : INFINITY;
     };
     // simple_heap_push (utils.py:352-406) on the sorted list: enters iff it beats the worst entry
     auto result_push = [&](float dc, int32_t vc) {

@@ -107,6 +107,15 @@ def test_prepare_against_reference_fixture(metric):
     r_gpu, r_ref = O.recall(ti, qi), O.recall(ti, g[metric + "_query_idx"])
     print("query recall@10: gpu %.4f reference %.4f" % (r_gpu, r_ref))
     assert abs(r_gpu - r_ref) <= 0.01  # (these queries come from another mixture: hard for both sides alike)
+    # ... and the very rows the reference returned, in order: every euclidean one, and every cosine one on which the
+    # step-exact reference walk (tests/search_reference.py) takes no decision within float32 error
+    from tests.test_search_reference_cpu import fixture_min_distance, fixture_walk
+    _, walk, _ = fixture_walk(metric, fixture_min_distance(g[metric + "_dist"]))
+    flagged = np.array([r.ambiguous for r in walk])
+    same = (qi == g[metric + "_query_idx"]).all(1)
+    print("query rows identical to the reference's: %d of %d (%d of the %d unflagged rows); min_distance %.8g" % (
+        same.sum(), len(same), same[~flagged].sum(), (~flagged).sum(), float(index._min_distance)))
+    assert same.all() if metric == "euclidean" else same[~flagged].all()
     # distances are the true metric's (corrected) values for the returned ids
     xi = x.astype(np.float64)
     if metric == "euclidean":
