@@ -37,10 +37,9 @@ extern "C" const char *nnd_last_error(nnd_handle_t h) { return h ? h->err : g_er
 void nnd_release_parked();
 template <typename T>
 static int dalloc(nnd_ctx *ctx, T **p, size_t count) {
-    if (hipMalloc((void **)p, sizeof(T) * (count ? count : 1)) != hipSuccess) {
-        (void)hipGetLastError();
+    if (!ctx->mem.alloc(p, count)) {
         nnd_release_parked();  // a parked handle (nnd_destroy) may hold what is missing
-        API_HIP(hipMalloc((void **)p, sizeof(T) * (count ? count : 1)));
+        if (!ctx->mem.alloc(p, count)) { ctx->set_error("out of device memory: allocation of %zu bytes failed", sizeof(T) * (count ? count : 1)); return 1; }
     }
     // debugging aid: fresh hipMalloc pages are usually zero, recycled ones are not -- NND_POISON=<byte> fills every buffer with
     // that byte (try 165: negative ints / tiny floats, and 1 or 127: positive ints) before the build initialises it
@@ -54,26 +53,6 @@ static int dalloc(nnd_ctx *ctx, T **p, size_t count) {
     return 0;
 }
 
-// Temporary device buffers of one API call: released on every return path.
-struct nnd_scratch {
-    std::vector<void *> ptrs;
-    ~nnd_scratch() {
-        for (void *p : ptrs)
-            if (p) (void)hipFree(p);
-    }
-    template <typename T>
-    T *get(nnd_ctx *ctx, size_t count) {
-        void *p = nullptr;
-        hipError_t e = hipMalloc(&p, sizeof(T) * (count ? count : 1));
-        if (e != hipSuccess) {
-            ctx->set_error("hipMalloc of %zu scratch bytes failed: %s", sizeof(T) * count, hipGetErrorString(e));
-            return nullptr;
-        }
-        ptrs.push_back(p);
-        return (T *)p;
-    }
-};
-
 std::recursive_mutex &nnd_lifecycle_mutex() {
 #ifdef NND_TEST_NO_LIFECYCLE_LOCK  // heap-check builds only (tools/gpu_asan.sh nolock): every thread gets its own mutex
     static thread_local std::recursive_mutex m;
@@ -83,29 +62,17 @@ std::recursive_mutex &nnd_lifecycle_mutex() {
     return m;
 }
 
+// Everything the handle holds.  Device memory has one owner (ctx->mem, devmem.h): whichever translation unit allocated a table,
+// it goes here; what is listed below is what is not device memory.
 static void free_all(nnd_ctx *ctx) {
-    auto F = [](void *p) {
-        if (p) (void)hipFree(p);
-    };
-    if (ctx->x_owned) F((void *)ctx->x_orig);
-    for (void *&a : ctx->slim_alloc) { F(a); a = nullptr; }  // cand / rbuf / active (the working pointers may be biased)
-    F(ctx->xp); F(ctx->nrm); F(ctx->nr2); F(ctx->xh); F(ctx->mean); F(ctx->knn_e); F(ctx->knn_d); F(ctx->th); F(ctx->pbuf_r);
-    F(ctx->pdirty); F(ctx->out_idx); F(ctx->out_dist);
-    F(ctx->rv_pos); F(ctx->rv_in_cursor); F(ctx->rv_in_rec); F(ctx->rv_ov);
-    for (int i = 0; i < 2; i++) { F(ctx->perm[i]); F(ctx->pos_seg[i]); F(ctx->seg_start[i]); F(ctx->seg_len[i]); }
-    F(ctx->inv); F(ctx->side); F(ctx->side_pt); F(ctx->leaf_flag); F(ctx->scan_out); F(ctx->scan_blk); F(ctx->seg_nleft); F(ctx->seg_child);
-    F(ctx->xs); F(ctx->xsh); F(ctx->nr2s); F(ctx->node_hf); F(ctx->node_hh); F(ctx->node_child); F(ctx->node_pack); F(ctx->node_hfc); F(ctx->route_roots); F(ctx->route_ws); F(ctx->s_leaf_depth);
-    F(ctx->cell_count); F(ctx->cell_start); F(ctx->cell_depth); F(ctx->small_list);
-    F(ctx->hyper); F(ctx->hyper_h); F(ctx->leaf_start); F(ctx->leaf_len); F(ctx->wl_start); F(ctx->wl_len); F(ctx->colsum_partial); F(ctx->counters_sum);
+    ctx->mem.release_all();
     if (ctx->h_pin) { (void)hipHostFree(ctx->h_pin); ctx->h_pin = nullptr; }
     if (ctx->h_tree_begin) { (void)hipHostFree(ctx->h_tree_begin); ctx->h_tree_begin = nullptr; }
-    F(ctx->tree_begin_dev); F(ctx->counters);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     if (ctx->ev_spin) (void)hipEventDestroy(ctx->ev_spin);
     for (hipEvent_t e : ctx->tev) if (e) (void)hipEventDestroy(e);
     ctx->tev.clear();
-    F(ctx->shard_bounds); F(ctx->shard_cursors);
     nnd_hub_tree_free(ctx);
     nnd_search_graph_free(ctx);
     if (ctx->stream && ctx->stream_owned) (void)hipStreamDestroy(ctx->stream);
@@ -126,6 +93,32 @@ static void jb_knobs(nnd_ctx *ctx) {  // experiments (KNOBS builds only): the sc
     if (const char *e = nnd_knob("NND_JB_FIRST")) ctx->jb_first = atoi(e) < 0 ? 0 : atoi(e);
 }
 static int auto_join_blocks(int k, int mc) { return (k <= 64 ? 1 : (k + 31) / 32) * (mc > 64 ? 2 : 1); }
+static uint32_t seed_of(const int64_t *s) { return nnd_mix32((uint32_t)s[0] ^ nnd_mix32((uint32_t)s[1] + 0x9E3779B9u) ^ nnd_mix32((uint32_t)s[2] + 0x7F4A7C15u)); }
+
+// Arm a handle for one build -- a new one (nnd_create_impl) or a parked one (take_parked): everything that is per build is
+// derived from the parameters or reset HERE, and nowhere else.  What is not touched survives parking on purpose: the grow-only
+// buffers and their capacities, rv_off, pbuf_clean / rbuf_clean, rv_pos_gen, forest_gen, cur, flag_seq.
+static void arm_for_build(nnd_ctx *ctx, const nnd_params *p) {
+    ctx->p = *p;
+    ctx->jb_auto = ctx->p.join_blocks < 1;
+    if (ctx->p.join_blocks < 1) ctx->p.join_blocks = auto_join_blocks(ctx->p.n_neighbors, ctx->p.max_candidates);
+    jb_knobs(ctx);
+    ctx->seed = seed_of(p->rng_state);
+    ctx->tree_seed = seed_of(p->tree_rng);
+    ctx->iter = 0;
+    ctx->stats = nnd_stats{};
+    ctx->err[0] = 0;
+    ctx->forest_built = false;
+    ctx->h_leaf_valid = false;
+    ctx->n_leaves = 0;
+    ctx->max_leaf = 0;
+    ctx->own_order = nullptr;
+    ctx->lists_replicated = false;
+    ctx->x_valid = false;
+    ctx->tlog.clear();
+    ctx->tev_used = 0;
+    nnd_hub_tree_free(ctx);
+}
 
 int nnd_create_impl(nnd_handle_t *out, const nnd_params *p, const int64_t *bounds_host, int n_ranks, int rank) {
     if (!out || !p) { gerr("nnd_create: null argument"); return 1; }
@@ -157,7 +150,7 @@ int nnd_create_impl(nnd_handle_t *out, const nnd_params *p, const int64_t *bound
 
     std::lock_guard<std::recursive_mutex> lifecycle(nnd_lifecycle_mutex());
     nnd_ctx *ctx = new nnd_ctx();
-    ctx->p = *p;
+    arm_for_build(ctx, p);
     ctx->n = p->n;
     ctx->own_lo = 0;
     ctx->own_hi = p->n;
@@ -193,13 +186,6 @@ int nnd_create_impl(nnd_handle_t *out, const nnd_params *p, const int64_t *bound
         const int r = atoi(pc_env);
         if (r == 16 || r == 32 || r == 64) ctx->pcap = r;
     }
-    ctx->jb_auto = ctx->p.join_blocks < 1;
-    if (ctx->p.join_blocks < 1) ctx->p.join_blocks = auto_join_blocks(ctx->p.n_neighbors, ctx->p.max_candidates);
-    jb_knobs(ctx);
-    ctx->seed = nnd_mix32((uint32_t)p->rng_state[0] ^ nnd_mix32((uint32_t)p->rng_state[1] + 0x9E3779B9u) ^
-                          nnd_mix32((uint32_t)p->rng_state[2] + 0x7F4A7C15u));
-    ctx->tree_seed = nnd_mix32((uint32_t)p->tree_rng[0] ^ nnd_mix32((uint32_t)p->tree_rng[1] + 0x9E3779B9u) ^
-                               nnd_mix32((uint32_t)p->tree_rng[2] + 0x7F4A7C15u));
     int rc = 0;
     do {
         if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) { ctx->set_error("hipStreamCreate failed"); rc = 1; break; }
@@ -224,18 +210,14 @@ int nnd_create_impl(nnd_handle_t *out, const nnd_params *p, const int64_t *bound
             uint32_t *a_rbuf = nullptr;
             uint8_t *a_active = nullptr;
             if ((rc = dalloc(ctx, &a_cand, rows * 2 * ctx->mcp))) break;
-            ctx->slim_alloc[0] = a_cand;
             if ((rc = dalloc(ctx, &a_rbuf, rows * 2 * ctx->rcap))) break;
-            ctx->slim_alloc[1] = a_rbuf;
             if ((rc = dalloc(ctx, &a_active, rows))) break;
-            ctx->slim_alloc[2] = a_active;
             // the working pointers are biased by -own_lo rows (0 on a plain handle): kernels index by global vertex id
             ctx->cand = a_cand - (size_t)ctx->own_lo * (ctx->slim ? 1 : 0) * 2 * ctx->mcp;
             ctx->rbuf = a_rbuf - (size_t)ctx->own_lo * (ctx->slim ? 1 : 0) * 2 * ctx->rcap;
             ctx->active = a_active - (size_t)ctx->own_lo * (ctx->slim ? 1 : 0);
             uint64_t *a_pbuf = nullptr;
             if ((rc = dalloc(ctx, &a_pbuf, rows * ctx->pcap))) break;
-            ctx->slim_alloc[3] = a_pbuf;
             ctx->pbuf = a_pbuf - (size_t)ctx->own_lo * (ctx->slim ? 1 : 0) * ctx->pcap;
             if (ctx->slim && (rc = dalloc(ctx, &ctx->pbuf_r, n * ctx->pcap_r))) break;
             if ((rc = dalloc(ctx, &ctx->pdirty, n))) break;
@@ -243,7 +225,7 @@ int nnd_create_impl(nnd_handle_t *out, const nnd_params *p, const int64_t *bound
             // default stream) and not with this handle's non-blocking stream -- it could clear the flags of a build in progress
             if (hipMemsetAsync(ctx->pdirty, 0, n, ctx->stream) != hipSuccess) { ctx->set_error("hipMemset failed"); rc = 1; break; }
             if (ctx->n_ranks > 0) {
-                if (hipMalloc((void **)&ctx->shard_bounds, sizeof(int64_t) * 65) != hipSuccess || hipMalloc((void **)&ctx->shard_cursors, sizeof(long long) * 66) != hipSuccess ||
+                if (!ctx->mem.alloc(&ctx->shard_bounds, 65) || !ctx->mem.alloc(&ctx->shard_cursors, 66) ||
                     hipMemcpy(ctx->shard_bounds, bounds_host, sizeof(int64_t) * (size_t)(n_ranks + 1), hipMemcpyHostToDevice) != hipSuccess) {
                     ctx->set_error("allocation of the shard tables failed"); rc = 1; break;
                 }
@@ -368,31 +350,13 @@ static nnd_ctx *take_parked(const nnd_params *p) {
     }
     if (!ctx) return nullptr;
     (void)hipSetDevice(p->device);
-    ctx->p = *p;
-    jb_knobs(ctx);
-    ctx->jb_auto = ctx->p.join_blocks < 1;
-    if (ctx->p.join_blocks < 1) ctx->p.join_blocks = auto_join_blocks(ctx->p.n_neighbors, ctx->p.max_candidates);
-    ctx->seed = nnd_mix32((uint32_t)p->rng_state[0] ^ nnd_mix32((uint32_t)p->rng_state[1] + 0x9E3779B9u) ^ nnd_mix32((uint32_t)p->rng_state[2] + 0x7F4A7C15u));
-    ctx->tree_seed = nnd_mix32((uint32_t)p->tree_rng[0] ^ nnd_mix32((uint32_t)p->tree_rng[1] + 0x9E3779B9u) ^ nnd_mix32((uint32_t)p->tree_rng[2] + 0x7F4A7C15u));
-    ctx->iter = 0;
-    ctx->stats = nnd_stats{};
-    ctx->err[0] = 0;
-    ctx->forest_built = false;
-    ctx->h_leaf_valid = false;
-    ctx->n_leaves = 0;
-    ctx->max_leaf = 0;
-    ctx->own_order = nullptr;
-    ctx->lists_replicated = false;
-    nnd_hub_tree_free(ctx);
+    arm_for_build(ctx, p);
     if (!ctx->stream_owned) {  // a borrowed stream must not outlive its lender
         ctx->stream = nullptr;
         if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) { destroy_now(ctx); return nullptr; }
         ctx->stream_owned = true;
     }
     if (!ctx->x_owned) ctx->x_orig = nullptr;  // a borrowed point set is gone; an owned copy's buffer is reused by nnd_set_data_host
-    ctx->x_valid = false;
-    ctx->tlog.clear();
-    ctx->tev_used = 0;
     return ctx;
 }
 
@@ -512,9 +476,7 @@ extern "C" int32_t nnd_set_data_host(nnd_handle_t ctx, const float *x) {
     ENTER(ctx);
     if (!x) { ctx->set_error("nnd_set_data_host: null data"); return 1; }
     if (!(ctx->x_owned && ctx->x_orig)) {  // the handle's own copy of the rows: allocated once, reused by later calls
-        float *dx = nullptr;
-        API_HIP(hipMalloc((void **)&dx, sizeof(float) * (size_t)ctx->n * ctx->d));
-        ctx->x_orig = dx;
+        if (!ctx->mem.alloc(&ctx->x_orig, (size_t)ctx->n * ctx->d)) { ctx->set_error("nnd_set_data_host: out of device memory for the handle's copy of the rows"); return 1; }
         ctx->x_owned = true;
     }
     if (h2d_parallel(ctx, (void *)ctx->x_orig, x, sizeof(float) * (size_t)ctx->n * ctx->d)) return 1;
@@ -525,7 +487,7 @@ extern "C" int32_t nnd_set_data_host(nnd_handle_t ctx, const float *x) {
 extern "C" int32_t nnd_set_data_device(nnd_handle_t ctx, const float *x_dev) {
     ENTER(ctx);
     if (!x_dev) { ctx->set_error("nnd_set_data_device: null data"); return 1; }
-    if (ctx->x_owned && ctx->x_orig) { API_HIP(hipFree((void *)ctx->x_orig)); }
+    if (ctx->x_owned) ctx->mem.free(&ctx->x_orig);
     ctx->x_orig = x_dev;
     ctx->x_owned = false;
     ctx->x_valid = true;
@@ -905,13 +867,7 @@ extern "C" int32_t nnd_host_sqrt_f32(float *dst, const float *src, int64_t count
 
 // grow-only device buffers for the finished graph of the host-buffer entry points (no hipMalloc / hipFree per call)
 static int out_buffers(nnd_ctx *ctx, size_t cnt) {
-    if (cnt <= ctx->out_cap) return 0;
-    if (ctx->out_idx) { API_HIP(hipFree(ctx->out_idx)); ctx->out_idx = nullptr; }
-    if (ctx->out_dist) { API_HIP(hipFree(ctx->out_dist)); ctx->out_dist = nullptr; }
-    ctx->out_cap = 0;
-    API_HIP(hipMalloc((void **)&ctx->out_idx, sizeof(int32_t) * cnt));
-    API_HIP(hipMalloc((void **)&ctx->out_dist, sizeof(float) * cnt));
-    ctx->out_cap = cnt;
+    if (!ctx->mem.grow2(&ctx->out_idx, &ctx->out_dist, &ctx->out_cap, cnt, cnt)) { ctx->set_error("out of device memory for the finished graph (%zu entries)", cnt); return 1; }
     return 0;
 }
 

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/pynnd_amd.h"
+#include "devmem.h"
 
 enum { NND_COMM_RCCL = 1, NND_COMM_LOCAL = 2, NND_COMM_HOST = 3 };
 #define NND_MAX_RANKS 64
@@ -71,6 +72,7 @@ struct nnd_comm_s {
     // RCCL
     void *nccl = nullptr;               // ncclComm_t
     long long *counts_all_dev = nullptr;  // (world, nv) gathered count vectors
+    nnd_devmem mem;                     // owner of this communicator's device memory (devmem.h)
     // LOCAL
     nnd_local_group *grp = nullptr;
     // HOST

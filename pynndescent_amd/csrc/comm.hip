@@ -123,10 +123,10 @@ static nnd_comm_s *make_rccl(const void *id_bytes, int32_t world, int32_t rank, 
     // (not under the lifecycle lock: ncclCommInitRank returns only when every rank of the world has called it)
     const ncclResult_t r = g_rccl.CommInitRank(&comm, world, id, rank);
     if (r != ncclSuccess || comm_common_init(c) ||
-        hipMalloc((void **)&c->counts_all_dev, sizeof(long long) * (size_t)world * (NND_MAX_RANKS + 8)) != hipSuccess) {
+        !c->mem.alloc(&c->counts_all_dev, (size_t)world * (NND_MAX_RANKS + 8))) {
         cgerr("nnd_comm_create_rccl: %s", r != ncclSuccess ? g_rccl.GetErrorString(r) : (c->err[0] ? c->err : "allocation failed"));
         if (comm) (void)g_rccl.CommAbort(comm);
-        if (c->counts_all_dev) (void)hipFree(c->counts_all_dev);
+        c->mem.release_all();
         if (c->h_counts) (void)hipHostFree(c->h_counts);
         if (c->ev) (void)hipEventDestroy(c->ev);
         delete c;
@@ -145,8 +145,9 @@ static nnd_comm_s *make_rccl(const void *id_bytes, int32_t world, int32_t rank, 
 static int comm_first_exchange(nnd_comm_s *c, hipStream_t st) {
     const int G = c->world, me = c->rank;
     if (G < 2) return 0;
-    int32_t *buf = nullptr;
-    C_HIP(hipMalloc((void **)&buf, sizeof(int32_t) * 2 * (size_t)G));
+    nnd_scratch tmp;  // released on return: every path below has waited for the exchange or failed
+    int32_t *buf = tmp.get<int32_t>(c, 2 * (size_t)G);
+    if (!buf) return 1;
     int32_t h[2 * NND_MAX_RANKS];
     for (int i = 0; i < 2 * G; i++) h[i] = -1;
     h[me] = me;  // [0, G): the word this rank sends (slot me); [G, 2 G): what the ranks sent
@@ -171,7 +172,6 @@ static int comm_first_exchange(nnd_comm_s *c, hipStream_t st) {
                 break;
             }
     if (rc && !c->err[0]) c->set_error("first exchange of a new communicator: a HIP call failed");
-    (void)hipFree(buf);
     c->bytes_sent = 0;
     return rc;
 }
@@ -333,7 +333,7 @@ extern "C" int32_t nnd_comm_destroy(nnd_comm_t c) {
     if (c->aux_stream) (void)hipStreamDestroy(c->aux_stream);
     // an aborted communicator was released by ncclCommAbort already
     if (c->kind == NND_COMM_RCCL && c->nccl && !c->dead && g_rccl.CommDestroy) (void)g_rccl.CommDestroy((ncclComm_t)c->nccl);
-    if (c->counts_all_dev) (void)hipFree(c->counts_all_dev);
+    c->mem.release_all();
     if (c->h_counts) (void)hipHostFree(c->h_counts);
     if (c->h_send) (void)hipHostFree(c->h_send);
     if (c->h_recv) (void)hipHostFree(c->h_recv);
@@ -451,8 +451,9 @@ static int host_stage_grow(nnd_comm_s *c, unsigned char **buf, size_t *cap, size
     if (need <= *cap) return 0;
     if (*buf) C_HIP(hipHostFree(*buf));
     *buf = nullptr;
+    *cap = 0;  // (published after the allocation, as nnd_devmem::grow does: a failed growth is tried again by the next call)
+    C_HIP(hipHostMalloc((void **)buf, need + need / 4 + 4096, hipHostMallocDefault));
     *cap = need + need / 4 + 4096;
-    C_HIP(hipHostMalloc((void **)buf, *cap, hipHostMallocDefault));
     return 0;
 }
 

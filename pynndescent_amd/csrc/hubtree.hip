@@ -294,11 +294,11 @@ int nnd_hub_tree_build_impl(nnd_ctx *ctx, const int32_t *rank_order_host, int le
     if (!ctx->perm[0] || ctx->P < n) { ctx->set_error("nnd_hub_tree_build: create the handle with n_trees >= 1 (it borrows the forest's scan / scatter buffers)"); return 1; }
     if (leaf_size < 1) leaf_size = 1;
     const int64_t S_max = 2 * (n / (leaf_size + 1) + 1) + 2;  // children of one level's splitting nodes
-    std::vector<void *> tmp;
+    nnd_scratch tmp;  // released on return, behind the synchronise at `done`
+    bool nomem = false;
     auto dev = [&](size_t bytes) -> void * {
-        void *p = nullptr;
-        if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) return nullptr;
-        tmp.push_back(p);
+        void *p = tmp.get<unsigned char>(ctx, bytes);
+        nomem = nomem || !p;
         return p;
     };
     int32_t *ord_rk[2] = {(int32_t *)dev(4 * n), (int32_t *)dev(4 * n)};
@@ -316,8 +316,7 @@ int nnd_hub_tree_build_impl(nnd_ctx *ctx, const int32_t *rank_order_host, int le
     nnd_hub_result *res = new nnd_hub_result();
     int32_t *ord_id[2] = {ctx->perm[0], ctx->perm[1]}, *pos_id[2] = {ctx->pos_seg[0], ctx->pos_seg[1]};
     int cur = 0, depth = 0, S = 1, n_split = 0;
-    for (void *p : tmp)
-        if (!p) { ctx->set_error("nnd_hub_tree_build: out of device memory"); rc = 1; goto done; }
+    if (nomem) { ctx->set_error("nnd_hub_tree_build: out of device memory"); rc = 1; goto done; }
     {
         const int splittable = (n > leaf_size && max_depth > 0) ? 1 : 0;
         const unsigned gridN = (unsigned)((n + 255) / 256);
@@ -433,8 +432,6 @@ int nnd_hub_tree_build_impl(nnd_ctx *ctx, const int32_t *rank_order_host, int le
     res = nullptr;
 done:
     (void)hipStreamSynchronize(ctx->stream);
-    for (void *p : tmp)
-        if (p) (void)hipFree(p);
     delete res;
     return rc;
 }

@@ -806,13 +806,7 @@ int nnd_launch_leaf_init(nnd_ctx *ctx) {
         tb[T] = (int64_t)ws.size();
         const int64_t nw = (int64_t)ws.size();
         if (nw == 0) return 0;
-        if (nw > ctx->wl_cap) {
-            if (ctx->wl_start) { NND_HIP_CHECK(hipFree(ctx->wl_start)); ctx->wl_start = nullptr; }
-            if (ctx->wl_len) { NND_HIP_CHECK(hipFree(ctx->wl_len)); ctx->wl_len = nullptr; }
-            ctx->wl_cap = nw + nw / 4;
-            NND_HIP_CHECK(hipMalloc((void **)&ctx->wl_start, sizeof(int32_t) * (size_t)ctx->wl_cap));
-            NND_HIP_CHECK(hipMalloc((void **)&ctx->wl_len, sizeof(int32_t) * (size_t)ctx->wl_cap));
-        }
+        if (!ctx->mem.grow2(&ctx->wl_start, &ctx->wl_len, &ctx->wl_cap, nw, nw + nw / 4)) { ctx->set_error("out of device memory for the leaf work list"); return 1; }
         NND_HIP_CHECK(hipMemcpyAsync(ctx->wl_start, ws.data(), sizeof(int32_t) * nw, hipMemcpyHostToDevice, ctx->stream));
         NND_HIP_CHECK(hipMemcpyAsync(ctx->wl_len, wl.data(), sizeof(int32_t) * nw, hipMemcpyHostToDevice, ctx->stream));
         NND_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // ws / wl are about to go out of scope
@@ -874,14 +868,10 @@ int nnd_launch_leaf_init_array(nnd_ctx *ctx, const int32_t *leaf_host, int64_t n
         ws[(size_t)at] = (int32_t)pc.off;
         wl[(size_t)at] = pc.len;
     }
-    int32_t *d_tab = nullptr, *d_ws = nullptr, *d_wl = nullptr;
     const size_t tab = (size_t)n_leaves * max_leaf_size, np = pieces.size();
-    int rc = 0;
-    if (hipMalloc((void **)&d_tab, sizeof(int32_t) * tab) != hipSuccess || hipMalloc((void **)&d_ws, sizeof(int32_t) * np) != hipSuccess ||
-        hipMalloc((void **)&d_wl, sizeof(int32_t) * np) != hipSuccess) {
-        ctx->set_error("nnd_init_from_leaf_array: out of device memory");
-        rc = 1;
-    }
+    nnd_scratch tmp;  // released on return, behind the synchronise below
+    int32_t *d_tab = tmp.get<int32_t>(ctx, tab), *d_ws = tmp.get<int32_t>(ctx, np), *d_wl = tmp.get<int32_t>(ctx, np);
+    int rc = !d_tab || !d_ws || !d_wl;
     if (!rc && (hipMemcpyAsync(d_tab, leaf_host, sizeof(int32_t) * tab, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
                 hipMemcpyAsync(d_ws, ws.data(), sizeof(int32_t) * np, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
                 hipMemcpyAsync(d_wl, wl.data(), sizeof(int32_t) * np, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)) {
@@ -890,9 +880,6 @@ int nnd_launch_leaf_init_array(nnd_ctx *ctx, const int32_t *leaf_host, int64_t n
     }
     if (!rc) rc = run_leaf_rounds(ctx, d_tab, d_ws, d_wl, tb, maxlen);  // ends with a counter read-back: the stream has drained
     (void)hipStreamSynchronize(ctx->stream);
-    if (d_tab) (void)hipFree(d_tab);
-    if (d_ws) (void)hipFree(d_ws);
-    if (d_wl) (void)hipFree(d_wl);
     if (!rc) ctx->stats.n_leaves = n_leaves;
     return rc;
 }

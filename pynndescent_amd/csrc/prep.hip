@@ -285,12 +285,8 @@ int nnd_prep_mean_finish(nnd_ctx *ctx, const double *partial, int nblocks, int64
 }
 int nnd_prep_partial_blocks(int64_t members) { return (int)((members + 127) / 128); }
 double *nnd_prep_partial_buffer(nnd_ctx *ctx, size_t doubles) {
-    if (doubles > ctx->colsum_cap) {  // grow-only scratch: no hipMalloc / hipFree (both synchronise) per build
-        if (ctx->colsum_partial) { (void)hipFree(ctx->colsum_partial); ctx->colsum_partial = nullptr; }
-        ctx->colsum_cap = 0;
-        if (hipMalloc((void **)&ctx->colsum_partial, sizeof(double) * doubles) != hipSuccess) { ctx->set_error("hipMalloc of the column-sum scratch failed"); return nullptr; }
-        ctx->colsum_cap = doubles;
-    }
+    // grow-only scratch: neither an allocation nor a free (both synchronise) per build
+    if (!ctx->mem.grow(&ctx->colsum_partial, &ctx->colsum_cap, doubles, doubles)) ctx->set_error("allocation of the column-sum scratch failed");
     return ctx->colsum_partial;
 }
 // pad + centre / normalise + norms + screening copy of rows [row_lo, row_hi); x_rows points at row 0 of the WHOLE set (a

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "common.h"
+#include "devmem.h"
 #include "../../include/pynnd_amd.h"
 
 #define Q_FRONTIER 512   // frontier entries per query (LDS tier)
@@ -66,6 +67,7 @@ struct nnd_searcher_s {
     hipStream_t stream = nullptr;
     int64_t last_spilled = 0;  // queries of the last call that ran on the global-memory tier
     bool force_big = false;    // nnd_searcher_set_tier(1): every query on the global-memory tier (tests)
+    nnd_devmem mem;            // owner of the device buffers above (devmem.h)
     char err[512] = {0};
     void set_error(const char *fmt, ...) {
         va_list ap;
@@ -619,9 +621,16 @@ __global__ __launch_bounds__(256) void k_quantize_u8(const float *__restrict__ x
             return 1;                                                                               \
         }                                                                                           \
     } while (0)
+#define S_ALLOC(p, count)                                                                      \
+    do {                                                                                       \
+        if (!s->mem.alloc(p, count)) {                                                         \
+            s->set_error("out of device memory: %s, %zu elements (%s:%d)", #p, (size_t)(count), __FILE__, __LINE__); \
+            return 1;                                                                          \
+        }                                                                                      \
+    } while (0)
 
 static int upload_padded(nnd_searcher_s *s, float **dst, const float *src, int64_t rows, int d, int dp) {
-    S_HIP(hipMalloc((void **)dst, sizeof(float) * (size_t)(rows ? rows : 1) * dp));
+    S_ALLOC(dst, (size_t)(rows ? rows : 1) * dp);
     if (rows == 0) return 0;
     if (d == dp) {
         S_HIP(hipMemcpy(*dst, src, sizeof(float) * (size_t)rows * d, hipMemcpyHostToDevice));
@@ -638,9 +647,7 @@ extern "C" int32_t nnd_searcher_destroy(nnd_searcher_t s) {
     if (!s) return 0;
     (void)hipSetDevice(s->device);
     if (s->stream) (void)hipStreamSynchronize(s->stream);
-    void *ptrs[] = {s->x, s->xn2, s->codes, s->cn2, s->lut, s->indptr, s->indices, s->hyper, s->offsets, s->children, s->tree_idx};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
+    s->mem.release_all();
     if (s->stream) (void)hipStreamDestroy(s->stream);
     delete s;
     return 0;
@@ -651,21 +658,21 @@ static int searcher_fill(nnd_searcher_s *s, const float *data, const int32_t *in
     S_HIP(hipSetDevice(s->device));
     S_HIP(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
     if (upload_padded(s, &s->x, data, s->n, s->d, s->dp)) return 1;
-    S_HIP(hipMalloc((void **)&s->xn2, sizeof(float) * (size_t)s->n));
+    S_ALLOC(&s->xn2, (size_t)s->n);
     if (s->metric == NND_METRIC_ALT_DOT || s->metric == NND_METRIC_CORRELATION || s->metric == NND_METRIC_ALT_HELLINGER)
         hipLaunchKernelGGL(k_searcher_prep_rows, dim3((unsigned)((s->n + 3) / 4)), dim3(256), 0, s->stream, s->x, s->n, s->d, s->dp, s->metric);
     hipLaunchKernelGGL(k_row_norm2, dim3((unsigned)((s->n + 3) / 4)), dim3(256), 0, s->stream, s->x, s->n, s->dp, s->xn2);
-    S_HIP(hipMalloc((void **)&s->indptr, sizeof(int32_t) * (size_t)(s->n + 1)));
+    S_ALLOC(&s->indptr, (size_t)(s->n + 1));
     S_HIP(hipMemcpy(s->indptr, indptr, sizeof(int32_t) * (size_t)(s->n + 1), hipMemcpyHostToDevice));
-    S_HIP(hipMalloc((void **)&s->indices, sizeof(int32_t) * (size_t)(s->nnz ? s->nnz : 1)));
+    S_ALLOC(&s->indices, (size_t)s->nnz);
     S_HIP(hipMemcpy(s->indices, indices, sizeof(int32_t) * (size_t)s->nnz, hipMemcpyHostToDevice));
     if (s->n_nodes > 0) {
         if (upload_padded(s, &s->hyper, hyperplanes, s->n_nodes, s->d, s->dp)) return 1;
-        S_HIP(hipMalloc((void **)&s->offsets, sizeof(float) * (size_t)s->n_nodes));
+        S_ALLOC(&s->offsets, (size_t)s->n_nodes);
         S_HIP(hipMemcpy(s->offsets, offsets, sizeof(float) * (size_t)s->n_nodes, hipMemcpyHostToDevice));
-        S_HIP(hipMalloc((void **)&s->children, sizeof(int32_t) * 2 * (size_t)s->n_nodes));
+        S_ALLOC(&s->children, 2 * (size_t)s->n_nodes);
         S_HIP(hipMemcpy(s->children, children, sizeof(int32_t) * 2 * (size_t)s->n_nodes, hipMemcpyHostToDevice));
-        S_HIP(hipMalloc((void **)&s->tree_idx, sizeof(int32_t) * (size_t)s->n));
+        S_ALLOC(&s->tree_idx, (size_t)s->n);
         S_HIP(hipMemcpy(s->tree_idx, tree_indices, sizeof(int32_t) * (size_t)s->n, hipMemcpyHostToDevice));
     }
     S_HIP(hipStreamSynchronize(s->stream));
@@ -729,9 +736,8 @@ static int searcher_run(nnd_searcher_s *s, const float *queries, int64_t nq, int
     if (nq <= 0) return 0;
     if (nq >= (int64_t)0x7FFFFFF0) { s->set_error("nnd_searcher_query: too many queries in one call"); return 1; }
     S_HIP(hipSetDevice(s->device));
-    float *dq = nullptr, *dd = nullptr;
-    int32_t *di = nullptr, *dlist = nullptr;
-    uint8_t *dov = nullptr;
+    nnd_scratch tmp;  // the buffers of this call
+    int32_t *dlist = nullptr;
     unsigned char *scratch = nullptr;
     int rc = 0;
     const size_t qp = q8 ? (size_t)s->dcs : (size_t)s->dp;  // query floats per wave in LDS (k_query's qp)
@@ -742,8 +748,10 @@ static int searcher_run(nnd_searcher_s *s, const float *queries, int64_t nq, int
     s->last_spilled = 0;
     std::vector<uint8_t> hov((size_t)nq, 1);
     do {
-        if (hipMalloc((void **)&dq, sizeof(float) * (size_t)nq * s->d) != hipSuccess || hipMalloc((void **)&di, sizeof(int32_t) * (size_t)nq * k_out) != hipSuccess ||
-            hipMalloc((void **)&dd, sizeof(float) * (size_t)nq * k_out) != hipSuccess || hipMalloc((void **)&dov, (size_t)nq) != hipSuccess) { s->set_error("nnd_searcher_query: out of device memory"); rc = 1; break; }
+        float *dq = tmp.get<float>(s, (size_t)nq * s->d), *dd = tmp.get<float>(s, (size_t)nq * k_out);
+        int32_t *di = tmp.get<int32_t>(s, (size_t)nq * k_out);
+        uint8_t *dov = tmp.get<uint8_t>(s, (size_t)nq);
+        if (!dq || !dd || !di || !dov) { s->set_error("nnd_searcher_query: out of device memory"); rc = 1; break; }
         if (hipMemcpyAsync(dq, queries, sizeof(float) * (size_t)nq * s->d, hipMemcpyHostToDevice, s->stream) != hipSuccess) { s->set_error("H2D of the queries failed"); rc = 1; break; }
         if (!s->force_big) {
             if (smem > 64 * 1024 && hipFuncSetAttribute((const void *)kq_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) {
@@ -766,7 +774,9 @@ static int searcher_run(nnd_searcher_s *s, const float *queries, int64_t nq, int
         if (!again.empty()) {
             const size_t stride = ((size_t)Q_BIG_FRONTIER * 8 + (size_t)((s->n + 31) / 32) * 4 + 255) & ~(size_t)255;
             const size_t batch = again.size() < Q_BIG_BATCH ? again.size() : (size_t)Q_BIG_BATCH;
-            if (hipMalloc((void **)&scratch, stride * batch) != hipSuccess || hipMalloc((void **)&dlist, sizeof(int32_t) * again.size()) != hipSuccess) {
+            scratch = tmp.get<unsigned char>(s, stride * batch);
+            dlist = tmp.get<int32_t>(s, again.size());
+            if (!scratch || !dlist) {
                 s->set_error("nnd_searcher_query: out of device memory for the global-memory tier (%zu bytes)", stride * batch); rc = 1; break;
             }
             if (hipMemcpyAsync(dlist, again.data(), sizeof(int32_t) * again.size(), hipMemcpyHostToDevice, s->stream) != hipSuccess) { s->set_error("H2D of the query list failed"); rc = 1; break; }
@@ -784,12 +794,6 @@ static int searcher_run(nnd_searcher_s *s, const float *queries, int64_t nq, int
             hipMemcpyAsync(out_dist, dd, sizeof(float) * (size_t)nq * k_out, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
             hipStreamSynchronize(s->stream) != hipSuccess) { s->set_error("nnd_searcher_query: kernel or D2H failed: %s", hipGetErrorString(hipGetLastError())); rc = 1; break; }
     } while (0);
-    if (dq) (void)hipFree(dq);
-    if (di) (void)hipFree(di);
-    if (dd) (void)hipFree(dd);
-    if (dov) (void)hipFree(dov);
-    if (dlist) (void)hipFree(dlist);
-    if (scratch) (void)hipFree(scratch);
     return rc;
 }
 
@@ -817,9 +821,9 @@ static int quant_tables(nnd_searcher_s *s, const char *who, const float *values,
         tab[256 + i] = i < n_values ? values[i] : INFINITY;
     }
     s->dcs = (s->d + 15) & ~15;
-    if (!s->lut) S_HIP(hipMalloc((void **)&s->lut, sizeof(float) * 512));
-    if (!s->codes) S_HIP(hipMalloc((void **)&s->codes, (size_t)s->n * s->dcs));
-    if (!s->cn2 && s->metric != NND_METRIC_SQEUCLIDEAN) S_HIP(hipMalloc((void **)&s->cn2, sizeof(float) * (size_t)s->n));
+    if (!s->lut) S_ALLOC(&s->lut, 512);
+    if (!s->codes) S_ALLOC(&s->codes, (size_t)s->n * s->dcs);
+    if (!s->cn2 && s->metric != NND_METRIC_SQEUCLIDEAN) S_ALLOC(&s->cn2, (size_t)s->n);
     // queued on the searcher's stream, so the kernels that read the tables are ordered after it (the stream is
     // non-blocking: it does not wait for copies on the null stream); tab_host outlives the copy (next call syncs first)
     S_HIP(hipMemcpyAsync(s->lut, tab, sizeof(float) * 512, hipMemcpyHostToDevice, s->stream));
@@ -837,11 +841,11 @@ static int quant_launch(nnd_searcher_s *s, const float *x, int64_t xstride) {
 extern "C" int32_t nnd_searcher_quantize_u8(nnd_searcher_t s, const float *rows, const float *values, int32_t n_values, uint8_t *codes_out) {
     if (!s) { snprintf(g_serr, sizeof(g_serr), "nnd_searcher_quantize_u8: null searcher"); return 1; }
     if (quant_tables(s, "nnd_searcher_quantize_u8", values, n_values)) return 1;
+    nnd_scratch tmp;  // released on return, behind the synchronise below
     float *drows = nullptr;
     if (rows) {
-        S_HIP(hipMalloc((void **)&drows, sizeof(float) * (size_t)s->n * s->d));
+        if (!(drows = tmp.get<float>(s, (size_t)s->n * s->d))) return 1;
         if (hipMemcpyAsync(drows, rows, sizeof(float) * (size_t)s->n * s->d, hipMemcpyHostToDevice, s->stream) != hipSuccess) {
-            (void)hipFree(drows);
             s->set_error("nnd_searcher_quantize_u8: H2D of the rows failed");
             return 1;
         }
@@ -856,7 +860,6 @@ extern "C" int32_t nnd_searcher_quantize_u8(nnd_searcher_t s, const float *rows,
         s->set_error("nnd_searcher_quantize_u8: kernel failed: %s", hipGetErrorString(hipGetLastError()));
         rc = 1;
     }
-    if (drows) (void)hipFree(drows);
     return rc;
 }
 

@@ -2231,10 +2231,7 @@ static forest_rc route_coherent(nnd_ctx *ctx, const rp_route_io &io) {
     const rp_route_geom g = route_geometry(dp, io.T, io.nrows, io.n_cells);
     if (g.total > ctx->route_ws_cap) {  // grow-only
         FOREST_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        if (ctx->route_ws) { FOREST_HIP_CHECK(hipFree(ctx->route_ws)); ctx->route_ws = nullptr; }
-        ctx->route_ws_cap = 0;
-        FOREST_HIP_CHECK(hipMalloc((void **)&ctx->route_ws, g.total + g.total / 4));
-        ctx->route_ws_cap = g.total + g.total / 4;
+        if (!ctx->mem.grow(&ctx->route_ws, &ctx->route_ws_cap, (size_t)g.total, (size_t)(g.total + g.total / 4))) { ctx->set_error("out of device memory for the routing workspace"); return FOREST_ERROR; }
     }
     switch (dp / 32) {
         case 1: return launch_route_coherent<1>(ctx, io, g);
@@ -2343,13 +2340,8 @@ static forest_rc forest_leaf_tables(nnd_ctx *ctx, int64_t P, int T, const int32_
     int32_t nl = 0;
     if (run_scan(ctx, 1, nullptr, ctx->leaf_flag, nnd_scan_total(ctx), P, n) || read_scan_total(ctx, &nl)) return FOREST_ERROR;
     ctx->n_leaves = nl;
-    if (nl + 1 > ctx->leaf_cap) {  // grow-only: repeated builds on one handle do not pay hipFree / hipMalloc (both synchronise)
-        if (ctx->leaf_start) { FOREST_HIP_CHECK(hipFree(ctx->leaf_start)); ctx->leaf_start = nullptr; }
-        if (ctx->leaf_len) { FOREST_HIP_CHECK(hipFree(ctx->leaf_len)); ctx->leaf_len = nullptr; }
-        ctx->leaf_cap = (int64_t)(nl + 1) + (nl + 1) / 4;
-        FOREST_HIP_CHECK(hipMalloc((void **)&ctx->leaf_start, sizeof(int32_t) * (size_t)ctx->leaf_cap));
-        FOREST_HIP_CHECK(hipMalloc((void **)&ctx->leaf_len, sizeof(int32_t) * (size_t)ctx->leaf_cap));
-    }
+    // grow-only: repeated builds on one handle pay neither a free nor an allocation (both synchronise)
+    if (!ctx->mem.grow2(&ctx->leaf_start, &ctx->leaf_len, &ctx->leaf_cap, (int64_t)nl + 1, (int64_t)(nl + 1) + (nl + 1) / 4)) { ctx->set_error("out of device memory for the leaf tables"); return FOREST_ERROR; }
     hipLaunchKernelGGL(k_leaf_starts, dim3(gridP), dim3(256), 0, ctx->stream, ctx->leaf_flag, ctx->scan_out, P,
                        ctx->leaf_start);
     // leaf lengths, the longest leaf and the per-tree leaf offsets stay on the device; the host reads T + 1 words

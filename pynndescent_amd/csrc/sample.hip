@@ -1100,18 +1100,7 @@ static void launch_select(nnd_ctx *ctx, uint32_t it_seed, bool wide) {
 }
 
 // grow-only tables of the bucketed reverse pass; the inverse of the visiting order once per forest.  An allocation that fails is
-// NOT a build error (returns false, nothing left behind): the caller falls back to the hashed slots, which need 8 * rcap bytes a row
-template <typename T>
-static bool rv_grow(T **p, size_t count) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    if (hipMalloc((void **)p, sizeof(T) * count) != hipSuccess) {
-        (void)hipGetLastError();  // (the error is handled here: do not let a later hipGetLastError() report it)
-        *p = nullptr;
-        return false;
-    }
-    return true;
-}
+// NOT a build error (nothing is left behind): the caller falls back to the hashed slots, which need 8 * rcap bytes a row
 // rows [row0, row0 + n_rows) are walked (all rows; a shard: the owned slice), `extra` records arrive from elsewhere.  The
 // record regions: nb buckets x 8 sub-regions x cap records of 8 bytes + the overflow list, sized for every offer.  cap = 4 x the
 // mean load of a sub-region when every offer of a bucket's vertices is counted (1024 at k = 15: 0.5 GB per million rows) for
@@ -1127,26 +1116,15 @@ static int rv_prepare(nnd_ctx *ctx, int logB, const int32_t *order, int64_t row0
     *cap_out = cap;
     const int64_t need = nb * 8 * cap;
     bool ok = !(ctx->p.flags & NND_FLAG_TEST_SAMPLE_NOMEM);  // test hook: behave as if the first allocation had failed
-    if (ok && (need > ctx->rv_cap_in || cap != ctx->rv_in_cap)) {
-        ctx->rv_cap_in = 0;  // (a failed allocation leaves no stale capacity behind)
-        ok = rv_grow(&ctx->rv_in_cursor, (size_t)nb * 8 + 8) && rv_grow(&ctx->rv_in_rec, (size_t)need);
-        if (ok) {
-            ctx->rv_cap_in = need;
-            ctx->rv_in_cap = cap;
-        }
+    if (ok) {
+        if (cap != ctx->rv_in_cap) ctx->rv_cap_in = 0;  // sub-regions of another size: the regions are allocated anew
+        ok = ctx->mem.grow2(&ctx->rv_in_cursor, (size_t)nb * 8 + 8, &ctx->rv_in_rec, (size_t)need, &ctx->rv_cap_in, need, need);
+        if (ok) ctx->rv_in_cap = cap;
     }
-    if (ok && nov > ctx->rv_cap_ov) {
-        const int64_t c = extra > 0 ? nov + nov / 4 : nov;  // (a shard's inbox varies from iteration to iteration: head room)
-        ctx->rv_cap_ov = 0;
-        ok = rv_grow(&ctx->rv_ov, (size_t)c);
-        if (ok) ctx->rv_cap_ov = c;
-    }
+    // (a shard's inbox varies from iteration to iteration: head room)
+    ok = ok && ctx->mem.grow(&ctx->rv_ov, &ctx->rv_cap_ov, nov, extra > 0 ? nov + nov / 4 : nov);
     if (ok && order && (!ctx->rv_pos || ctx->rv_pos_gen != ctx->forest_gen || ctx->rv_pos_of != order)) {
-        if (n_rows > ctx->rv_cap_pos) {
-            ctx->rv_cap_pos = 0;
-            ok = rv_grow(&ctx->rv_pos, (size_t)n_rows);
-            if (ok) ctx->rv_cap_pos = n_rows;
-        }
+        ok = ctx->mem.grow(&ctx->rv_pos, &ctx->rv_cap_pos, n_rows, n_rows);
         if (ok) {
             hipLaunchKernelGGL(k_rev_invert, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, ctx->stream, order, row0, n_rows, ctx->rv_pos);
             ctx->rv_pos_gen = ctx->forest_gen;
@@ -1156,9 +1134,9 @@ static int rv_prepare(nnd_ctx *ctx, int logB, const int32_t *order, int64_t row0
     if (!ok) {
         // give the memory back and switch this handle to the hashed-slot form of the pass for good: the banks (rbuf) exist on
         // every handle; they are re-armed here because the bucketed fill (k_rev_fill) leaves them in its own state
-        if (ctx->rv_in_cursor) { (void)hipFree(ctx->rv_in_cursor); ctx->rv_in_cursor = nullptr; }
-        if (ctx->rv_in_rec) { (void)hipFree(ctx->rv_in_rec); ctx->rv_in_rec = nullptr; }
-        if (ctx->rv_ov) { (void)hipFree(ctx->rv_ov); ctx->rv_ov = nullptr; }
+        ctx->mem.free(&ctx->rv_in_cursor);
+        ctx->mem.free(&ctx->rv_in_rec);
+        ctx->mem.free(&ctx->rv_ov);
         ctx->rv_cap_in = ctx->rv_cap_ov = 0;
         ctx->rv_in_cap = 0;
         ctx->rv_off = true;

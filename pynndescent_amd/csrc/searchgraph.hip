@@ -216,9 +216,7 @@ struct nnd_sg_state {
 };
 
 void nnd_search_graph_free(nnd_ctx *ctx) {
-    if (!ctx->sg) return;
-    if (ctx->sg->buf) (void)hipFree(ctx->sg->buf);
-    delete ctx->sg;
+    delete ctx->sg;  // (its workspace belongs to ctx->mem)
     ctx->sg = nullptr;
 }
 
@@ -245,13 +243,7 @@ int nnd_search_graph_impl(nnd_ctx *ctx, const int32_t *idx_src, const float *dis
     if (rocprim::radix_sort_pairs(nullptr, sort_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (float *)nullptr, (float *)nullptr, (size_t)(2 * nk), 0, 64, s) !=
         hipSuccess) { ctx->set_error("nnd_search_graph: rocprim::radix_sort_pairs (size query) failed"); return 1; }
     const size_t o_sort = take(sort_bytes + 256);
-    if (off > g->cap) {
-        if (g->buf) NND_HIP_CHECK(hipFree(g->buf));
-        g->buf = nullptr;
-        g->cap = 0;
-        NND_HIP_CHECK(hipMalloc((void **)&g->buf, off));
-        g->cap = off;
-    }
+    if (!ctx->mem.grow(&g->buf, &g->cap, off, off)) { ctx->set_error("nnd_search_graph: out of device memory for a workspace of %zu bytes", off); return 1; }
     unsigned char *B = g->buf;
     int32_t *di = (int32_t *)(B + o_di), *cnt = (int32_t *)(B + o_cnt), *ptrF = (int32_t *)(B + o_ptrF), *deg = (int32_t *)(B + o_deg),
             *f_ind = (int32_t *)(B + o_find), *flag = (int32_t *)(B + o_flag), *pos = (int32_t *)(B + o_pos), *u_ind = (int32_t *)(B + o_uind),

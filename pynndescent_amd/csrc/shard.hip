@@ -29,7 +29,7 @@ struct nnd_shard_s {
     int world = 1, rank = 0, k = 0, ks = 0, t0 = 0, t1 = 0;
     int64_t n_total = 0, lo = 0, hi = 0, max_range = 0;
     int64_t bounds[NND_MAX_RANKS + 1] = {0};
-    // device buffers
+    nnd_devmem mem;  // owner of the device buffers below (devmem.h); the handle `h` owns its own
     float *x_full = nullptr;                     // (n_total, d) replicated point set (world > 1)
     uint32_t *recv_e = nullptr;                  // (world - 1 sources) x (n_own, ks) partial k-list rows
     float *recv_d = nullptr;
@@ -162,10 +162,7 @@ __global__ __launch_bounds__(256) void k_compact_owned(const int32_t *__restrict
 static void shard_free(nnd_shard_s *s) {
     std::lock_guard<std::recursive_mutex> lifecycle(nnd_lifecycle_mutex());
     if (s->h) (void)hipSetDevice(s->h->p.device);
-    void *ptrs[] = {s->x_full, s->recv_e, s->recv_d, s->off_t, s->off_k, s->prop_t, s->prop_k, s->in_t, s->in_k, s->cvec, s->own_order, s->order_cursor,
-                    s->pack_all, s->hf_all, s->cells_i32, s->maps};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
+    s->mem.release_all();
     if (s->ev_x) (void)hipEventDestroy(s->ev_x);
     if (s->ev_g0) (void)hipEventDestroy(s->ev_g0);
     if (s->ev_g1) (void)hipEventDestroy(s->ev_g1);
@@ -251,12 +248,11 @@ extern "C" int32_t nnd_shard_create(nnd_shard_t *out, const nnd_params *params, 
     const int64_t n_own = s->hi - s->lo;
     std::lock_guard<std::recursive_mutex> lifecycle(nnd_lifecycle_mutex());
     bool ok = hipSetDevice(p.device) == hipSuccess;
-    ok = ok && hipMalloc((void **)&s->cvec, sizeof(long long) * (size_t)(NND_MAX_RANKS + 8)) == hipSuccess;
+    ok = ok && s->mem.alloc(&s->cvec, (size_t)(NND_MAX_RANKS + 8));
     ok = ok && hipEventCreateWithFlags(&s->ev_x, hipEventDisableTiming) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&s->ev_g0, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&s->ev_g1, hipEventDisableTiming) == hipSuccess;
     if (ok && G > 1 && p.n_trees > 0) {
-        ok = ok && hipMalloc((void **)&s->own_order, sizeof(int32_t) * (size_t)(n_own > 0 ? n_own : 1)) == hipSuccess;
-        ok = ok && hipMalloc((void **)&s->order_cursor, sizeof(int)) == hipSuccess;
+        ok = ok && s->mem.alloc(&s->own_order, (size_t)(n_own > 0 ? n_own : 1)) && s->mem.alloc(&s->order_cursor, 1);
     }
     if (ok && G > 1) {
         // offers: at most every owned edge goes to ONE other rank; proposals: 32 of a row's 64 slots may travel per
@@ -264,19 +260,15 @@ extern "C" int32_t nnd_shard_create(nnd_shard_t *out, const nnd_params *params, 
         s->cap_o = n_own * s->k > 0 ? n_own * s->k : 1;
         s->cap_p = s->max_range * 32 > 64 ? s->max_range * 32 : 64;
         if (params->flags & NND_FLAG_TEST_SMALL_REGIONS) s->cap_p = s->max_range > 64 ? s->max_range : 64;  // test hook: forces deferrals
-        ok = ok && hipMalloc((void **)&s->x_full, sizeof(float) * (size_t)s->n_total * params->dim) == hipSuccess;
+        ok = ok && s->mem.alloc(&s->x_full, (size_t)s->n_total * params->dim);
         if (params->n_trees > 0) {
             const size_t rows = (size_t)(G - 1) * (size_t)(n_own > 0 ? n_own : 1) * s->ks;
-            ok = ok && hipMalloc((void **)&s->recv_e, sizeof(uint32_t) * rows) == hipSuccess;
-            ok = ok && hipMalloc((void **)&s->recv_d, sizeof(float) * rows) == hipSuccess;
+            ok = ok && s->mem.alloc(&s->recv_e, rows) && s->mem.alloc(&s->recv_d, rows);
         }
-        ok = ok && hipMalloc((void **)&s->off_t, sizeof(int32_t) * (size_t)G * s->cap_o) == hipSuccess;
-        ok = ok && hipMalloc((void **)&s->off_k, sizeof(uint32_t) * (size_t)G * s->cap_o) == hipSuccess;
-        ok = ok && hipMalloc((void **)&s->prop_t, sizeof(int32_t) * (size_t)G * s->cap_p) == hipSuccess;
-        ok = ok && hipMalloc((void **)&s->prop_k, sizeof(uint64_t) * (size_t)G * s->cap_p) == hipSuccess;
-        s->in_cap = n_own * s->k + 1024;  // a typical iteration receives about as many offers as it sends; grows on demand
-        ok = ok && hipMalloc((void **)&s->in_t, sizeof(int32_t) * (size_t)s->in_cap) == hipSuccess;
-        ok = ok && hipMalloc((void **)&s->in_k, sizeof(uint64_t) * (size_t)s->in_cap) == hipSuccess;
+        ok = ok && s->mem.alloc(&s->off_t, (size_t)G * s->cap_o) && s->mem.alloc(&s->off_k, (size_t)G * s->cap_o);
+        ok = ok && s->mem.alloc(&s->prop_t, (size_t)G * s->cap_p) && s->mem.alloc(&s->prop_k, (size_t)G * s->cap_p);
+        const int64_t in0 = n_own * s->k + 1024;  // a typical iteration receives about as many offers as it sends; grows on demand
+        ok = ok && s->mem.grow2(&s->in_t, &s->in_k, &s->in_cap, in0, in0);
     }
     if (!ok) {
         snprintf(g_serr2, sizeof(g_serr2), "nnd_shard_create: out of device memory (rank %d of %d, %lld owned rows of %lld)", rank, G,
@@ -347,13 +339,7 @@ static void note_bytes(nnd_shard_s *s, int64_t before) {  // payload of the exch
 static int grow_inbox(nnd_shard_s *s, int64_t need) {
     if (need <= s->in_cap) return 0;
     S_COMM(comm_wait(s->comm, s->h->stream, "inbox growth"));
-    if (s->in_t) S_HIP(hipFree(s->in_t));
-    if (s->in_k) S_HIP(hipFree(s->in_k));
-    s->in_t = nullptr;
-    s->in_k = nullptr;
-    s->in_cap = need + need / 4;
-    S_HIP(hipMalloc((void **)&s->in_t, sizeof(int32_t) * (size_t)s->in_cap));
-    S_HIP(hipMalloc((void **)&s->in_k, sizeof(uint64_t) * (size_t)s->in_cap));
+    if (!s->mem.grow2(&s->in_t, &s->in_k, &s->in_cap, need, need + need / 4)) { s->set_error("out of device memory for an inbox of %lld records", (long long)need); return 1; }
     return 0;
 }
 
@@ -396,11 +382,7 @@ template <typename T>
 static int grow_dev(nnd_shard_s *s, T **buf, int64_t *cap, int64_t need) {
     if (need <= *cap) return 0;
     S_COMM(comm_wait(s->comm, s->h->stream, "buffer growth"));
-    if (*buf) S_HIP(hipFree(*buf));
-    *buf = nullptr;
-    *cap = 0;
-    S_HIP(hipMalloc((void **)buf, sizeof(T) * (size_t)(need + need / 8 + 64)));
-    *cap = need + need / 8 + 64;
+    if (!s->mem.grow(buf, cap, need, need + need / 8 + 64)) { s->set_error("out of device memory for a table of %lld entries", (long long)need); return 1; }
     return 0;
 }
 
@@ -615,15 +597,8 @@ static int forest_by_cell(nnd_shard_s *s, const float *x_local_dev, hipEvent_t e
     if (grow_dev(s, &s->cells_i32, &s->cells_cap, 3 * cpad + (int64_t)G * cells_own_max + 16)) return 1;
     if (nodes_all > s->nodes_cap) {
         S_COMM(comm_wait(c, st, "node tables"));
-        if (s->pack_all) S_HIP(hipFree(s->pack_all));
-        if (s->hf_all) S_HIP(hipFree(s->hf_all));
-        s->pack_all = nullptr;
-        s->hf_all = nullptr;
-        s->nodes_cap = 0;
         const int64_t cap = nodes_all + nodes_all / 8 + 64;
-        S_HIP(hipMalloc((void **)&s->pack_all, (size_t)cap * (2 * dp + 16)));
-        S_HIP(hipMalloc((void **)&s->hf_all, sizeof(float) * (size_t)cap * (dp + 4)));
-        s->nodes_cap = cap;
+        if (!s->mem.grow2(&s->pack_all, (size_t)cap * (2 * dp + 16), &s->hf_all, (size_t)cap * (dp + 4), &s->nodes_cap, (int64_t)nodes_all, cap)) { s->set_error("out of device memory for the node tables of %lld nodes", (long long)nodes_all); return 1; }
     }
     S_HIP(hipMemcpyAsync(s->maps, tab.data(), sizeof(int32_t) * tab.size(), hipMemcpyHostToDevice, st));
     int32_t *cell_count_all = s->cells_i32, *cell_depth_all = s->cells_i32 + cpad, *count_copy = s->cells_i32 + 2 * cpad, *cnt_recv = s->cells_i32 + 3 * cpad;
@@ -1277,20 +1252,15 @@ static int32_t build_multi_impl(const nnd_params *params_in, const float *x, int
         p.device = dev[r];
         nnd_shard_t sh = nullptr;
         const size_t nl = (size_t)sizes[r];
-        float *dx = nullptr;
-        int32_t *di = nullptr;
-        float *dd = nullptr;
-        int32_t *gi = nullptr;  // the owned rows of the init graph
-        float *gd = nullptr;
+        nnd_scratch tmp;  // this rank's staging buffers: released at (4) below
+        float *dx = nullptr, *dd = nullptr, *gd = nullptr;
+        int32_t *di = nullptr, *gi = nullptr;  // (gi, gd: the owned rows of the init graph)
         if (!rcs[r] && nnd_shard_create(&sh, &p, comms[r], sizes.data())) bail(nnd_shard_last_error(nullptr));
         if (!rcs[r]) {
-            bool ok = hipMalloc((void **)&dx, sizeof(float) * (nl ? nl : 1) * p.dim) == hipSuccess &&
-                      hipMalloc((void **)&di, sizeof(int32_t) * (nl ? nl : 1) * p.n_neighbors) == hipSuccess &&
-                      hipMalloc((void **)&dd, sizeof(float) * (nl ? nl : 1) * p.n_neighbors) == hipSuccess;
+            bool ok = tmp.alloc(&dx, (nl ? nl : 1) * p.dim) && tmp.alloc(&di, (nl ? nl : 1) * p.n_neighbors) && tmp.alloc(&dd, (nl ? nl : 1) * p.n_neighbors);
             if (ok && nl) ok = hipMemcpy(dx, x + (size_t)lo[r] * p.dim, sizeof(float) * nl * p.dim, hipMemcpyHostToDevice) == hipSuccess;
             if (ok && init_idx) {
-                ok = hipMalloc((void **)&gi, sizeof(int32_t) * (nl ? nl : 1) * init_width) == hipSuccess &&
-                     (!init_dist || hipMalloc((void **)&gd, sizeof(float) * (nl ? nl : 1) * init_width) == hipSuccess);
+                ok = tmp.alloc(&gi, (nl ? nl : 1) * init_width) && (!init_dist || tmp.alloc(&gd, (nl ? nl : 1) * init_width));
                 if (ok && nl) ok = hipMemcpy(gi, init_idx + (size_t)lo[r] * init_width, sizeof(int32_t) * nl * init_width, hipMemcpyHostToDevice) == hipSuccess;
                 if (ok && nl && init_dist) ok = hipMemcpy(gd, init_dist + (size_t)lo[r] * init_width, sizeof(float) * nl * init_width, hipMemcpyHostToDevice) == hipSuccess;
             }
@@ -1327,11 +1297,7 @@ static int32_t build_multi_impl(const nnd_params *params_in, const float *x, int
             (void)hipGetLastError();
         }
         bar.wait();  // (4) ... and everybody has drained before the first hipFree
-        if (dx) (void)hipFree(dx);
-        if (di) (void)hipFree(di);
-        if (dd) (void)hipFree(dd);
-        if (gi) (void)hipFree(gi);
-        if (gd) (void)hipFree(gd);
+        tmp.release_all();
         if (sh) (void)nnd_shard_destroy(sh);
     };
     std::vector<std::thread> th;

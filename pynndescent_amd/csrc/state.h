@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/pynnd_amd.h"
+#include "devmem.h"
 
 // Experiment / debugging knobs (NND_* environment variables: table sizes, kernel variants, NND_POISON, NND_FOREST_DEBUG)
 // exist only in a library built with `make KNOBS=1` (-DNND_EXPERIMENT_KNOBS): the product library reads no environment
@@ -122,6 +123,7 @@ struct nnd_handle_s {
     nnd_params p{};
     nnd_stats stats{};
     char err[512] = {0};
+    nnd_devmem mem;                // owner of every device buffer below, whichever translation unit allocates it (devmem.h)
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::vector<hipEvent_t> tev;   // event pool of the deferred stage timers (capi.hip t_begin / t_end / t_flush)
@@ -145,12 +147,11 @@ struct nnd_handle_s {
     int64_t *shard_bounds = nullptr;      // device (n_ranks + 1): first row of every rank, then n
     long long *shard_cursors = nullptr;   // device (66): per-destination record cursors, [64] dropped, [65] deferred
     bool stream_owned = true;             // false after nnd_set_stream: the caller's stream is borrowed
-    // A shard created by nnd_create_impl with bounds allocates the per-OWNED-row tables (cand, rbuf, active) for its own
-    // rows only; the pointers above are biased by -own_lo rows so that kernels keep indexing by global vertex id.
+    // A shard created by nnd_create_impl with bounds allocates the per-OWNED-row tables (cand, rbuf, active, pbuf) for its own
+    // rows only; those working pointers are biased by -own_lo rows so that kernels keep indexing by global vertex id (`mem` holds the bases).
     bool lists_replicated = false;        // shard: the neighbour ids of ALL rows are refreshed before every join (shard.hip): remote targets are tested too
     const int32_t *own_order = nullptr;   // shard: the owned vertices in a spatially coherent order (shard.hip), or nullptr
     bool slim = false;
-    void *slim_alloc[4] = {nullptr, nullptr, nullptr, nullptr};  // the allocations behind cand / rbuf / active / pbuf (always; biased or not)
     int64_t slim_rows() const { return slim ? own_hi - own_lo : n; }  // rows those three tables hold
     int64_t slim_row0() const { return slim ? own_lo : 0; }            // first of them
     uint32_t seed = 0, tree_seed = 0;

@@ -448,6 +448,37 @@ def test_repeated_builds_on_one_handle_are_identical():
     b.close()
 
 
+def test_handle_lifecycle_park_take_release_rebuilds_identically():
+    """Every device buffer of a handle has one owner (csrc/devmem.h), and one function arms a handle for a build: a build on
+    a handle taken from the park, and one on a fresh handle after the parked one was released (for another geometry, and by
+    nnd_release_pending), both reproduce the first build bit for bit."""
+    from pynndescent_amd import _capi
+
+    x = clustered(3000, 16, 4, 16, seed=1)
+
+    def build(rows):
+        b = make_builder(rows, "euclidean", k=10, n_trees=2)
+        b.make_forest()
+        b.init_from_leaves()
+        b.init_random()
+        b.descent()
+        idx, dist = b.finalize()
+        idx, dist = np.array(idx, copy=True), np.array(dist, copy=True)
+        b.close()  # parks the handle
+        return idx, dist
+
+    i0, d0 = build(x)
+    i1, d1 = build(x)  # same geometry, same seeds: the parked handle, re-armed
+    np.testing.assert_array_equal(i0, i1)
+    np.testing.assert_array_equal(d0, d1)
+    i2, d2 = build(x[:2000])  # another geometry: the parked handle is released, a fresh one allocated
+    check_graph_invariants(x[:2000], "euclidean", i2, d2, name="lifecycle n=2000")
+    assert _capi.load_library().nnd_release_pending() == 0
+    i3, d3 = build(x)  # nothing parked: fresh allocations
+    np.testing.assert_array_equal(i0, i3)
+    np.testing.assert_array_equal(d0, d3)
+
+
 @pytest.mark.parametrize("k,mc", [(15, 15), (10, 10), (30, 30), (20, 12)])
 def test_half_wave_select_equals_wave_select(k, mc):
     """k_sample_select_h (two vertices per wave) must produce exactly the lists and flag resets of k_sample_select."""
