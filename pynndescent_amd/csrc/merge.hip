@@ -4,7 +4,10 @@
 // thread scan ALL (p,q,d) updates and apply those whose endpoint it owns.  Here proposals were
 // already routed to their target by the join (join.hip), so one wave per target row that has
 // pending proposals merges them (merge.h) and re-arms the slots.  c (utils.py:725,731) is the
-// number of proposals that end up in a list.
+// number of pushes that succeed on the snapshot: the slot winners that beat the row's worst
+// distance as the merge found it and were not in the row yet (merge.h) -- also those that a
+// nearer winner of the same merge pushes beyond the k-th place, so it is NOT the number of
+// entries that end up in a list (tests/descent_reference.py restates it).
 //
 // k_random_init replaces init_random (pynndescent_.py:188-203); k_graph_init replaces
 // initalize_heap_from_graph_indices[_and_distances] (utils.py:836-860).  Both write their
