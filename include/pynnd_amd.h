@@ -121,6 +121,9 @@ typedef struct nnd_params {
  * build the same graph, entry for entry (tests/test_gpu_kernels.py) */
 #define NND_FLAG_TEST_JOIN_UNSTAGED 16384
 
+/* test hook: nnd_exact_knn_* answers every row through the float64 tier (tests/test_gpu_exact.py compares the two tiers) */
+#define NND_FLAG_TEST_EXACT_F64 32768
+
 /* Run-time statistics for measurement (bench.py roofline). */
 typedef struct nnd_stats {
     int64_t n_iters_run;
@@ -367,6 +370,29 @@ int32_t nnd_build_multi_from_graph(const nnd_params *params, const float *x, int
 int32_t nnd_build_multi_update(const nnd_params *params, const float *x, int32_t n_devices, const int32_t *devices, const int32_t *old_idx,
                                const float *old_dist, int32_t width, int32_t *out_idx, float *out_dist, nnd_stats *stats,
                                nnd_shard_info *info_rank0 /* nullable */, char *err, int32_t errlen);
+
+/* ---- exact k nearest neighbours by brute force (csrc/exact.hip; DESIGN.md "Exact search") ----
+ * The companion of the approximate index: ground truth, recall on the caller's own data, small point sets.  Works on any
+ * handle whose point set is resident and prepared (nnd_set_data_*): an NND_FLAG_NO_GRAPH handle (the natural one: no k-lists
+ * are allocated) or a build handle; fails on NND_FLAG_NO_PREP, for k < 1 and for k > min(n, 256).  Two tiers: an f32 MFMA
+ * Gram scan keeps the W >= k best candidates per row, their distances are recomputed from the original rows with float64
+ * accumulation (the formulas of nnd_finalize_*), and a row is answered from them only if a rounding-error bound proves that
+ * nothing the scan left out can belong to the top k; every other row is scanned again in float64.  The result is the exact
+ * top k by (float64 distance, id): rows ascending, ties to the smaller id, float32 alt-space distances. */
+typedef struct nnd_exact_stats {
+    int64_t n_rows, n_fallback;   /* rows answered / rows that were not certified and went through the float64 scan */
+    int64_t pairs, mfma;          /* pair distances and v_mfma_f32_16x16x4_f32 instructions of the scan */
+    float ms_scan, ms_refine, ms_fallback;
+} nnd_exact_stats;
+/* rows of the handle's own point set (host int64 ids, NULL = all n), self included */
+int32_t nnd_exact_knn_rows(nnd_handle_t h, const int64_t *rows, int64_t n_rows, int32_t k,
+                           int32_t *out_idx, float *out_dist, nnd_exact_stats *st /* may be NULL */);
+/* external queries, host float32 (n_q, dim): prepared with the point set's transform (code 0: the SET's column means) */
+int32_t nnd_exact_knn_queries(nnd_handle_t h, const float *q, int64_t n_q, int32_t k,
+                              int32_t *out_idx, float *out_dist, nnd_exact_stats *st);
+/* data slices the scan splits the point set into when n_rows query rows are asked for (a function of the shapes alone: few
+ * query blocks -> many slices, so that the chip is filled); tests */
+int32_t nnd_exact_slice_count(nnd_handle_t h, int64_t n_rows);
 
 /* Stream the handle runs on: the caller's HIP stream (e.g. the one that produces the point set) instead of the handle's
  * own, so the device-pointer entry points need no synchronisation with it.  NULL: the handle's own stream again. */

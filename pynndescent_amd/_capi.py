@@ -36,6 +36,7 @@ NND_FLAG_TEST_GATHER_INLINE = 8192  # test hook (sharded build): the id / thresh
 NND_FLAG_TEST_JOIN_UNSTAGED = 16384  # test hook: k_local_join_w with the membership lists read from global memory instead of staged in LDS
 NND_FLAG_TEST_SELECT_HALF = 4096  # test hook: the fused selection with 32 lanes per vertex where 16 would do (k <= 16, max_candidates <= 16)
 NND_FLAG_TEST_SAMPLE_NOMEM = 2048  # test hook: the sampler's record regions "cannot be allocated": the handle must fall back to the hashed slots
+NND_FLAG_TEST_EXACT_F64 = 32768  # test hook: the exact search answers every row through its float64 tier
 NND_FLAG_TEST_SAMPLE_ATOMIC = 256  # test hook: reverse offers by one global atomicMin per edge (rounds 1-4) instead of the bucketed transposition
 
 
@@ -151,6 +152,21 @@ HOST_EXCHANGE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_
                                C.POINTER(C.c_int64), C.POINTER(C.c_int64))
 
 
+class NNDExactStats(C.Structure):
+    _fields_ = [
+        ("n_rows", C.c_int64),
+        ("n_fallback", C.c_int64),
+        ("pairs", C.c_int64),
+        ("mfma", C.c_int64),
+        ("ms_scan", C.c_float),
+        ("ms_refine", C.c_float),
+        ("ms_fallback", C.c_float),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class NNDPruneOpts(C.Structure):
     _fields_ = [
         ("prune_probability", C.c_float),
@@ -202,6 +218,9 @@ _SIGNATURES = [
     ("nnd_get_candidates", C.c_int32, [_H, C.c_void_p, C.c_void_p]),
     ("nnd_sample_candidates", C.c_int32, [_H]),
     ("nnd_pairwise_gram", C.c_int32, [_H, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    ("nnd_exact_knn_rows", C.c_int32, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(NNDExactStats)]),
+    ("nnd_exact_knn_queries", C.c_int32, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(NNDExactStats)]),
+    ("nnd_exact_slice_count", C.c_int32, [_H, C.c_int64]),
     ("nnd_descent_sample", C.c_int32, [_H]),
     ("nnd_descent_join", C.c_int32, [_H]),
     ("nnd_set_stream", C.c_int32, [_H, C.c_void_p]),
@@ -522,6 +541,30 @@ class Builder:
         out = np.empty((a.shape[0], b.shape[0]), np.float32)
         self._check(self.lib.nnd_pairwise_gram(self._h, _ptr(a), a.shape[0], _ptr(b), b.shape[0], _ptr(out)))
         return out
+
+
+    # -- exact search (csrc/exact.hip) --------------------------------------------------------------
+    def _exact(self, call, arg, m, k):
+        idx = np.empty((m, int(k)), np.int32)
+        dist = np.empty((m, int(k)), np.float32)
+        st = NNDExactStats()
+        self._check(call(self._h, _ptr(arg), m, int(k), _ptr(idx), _ptr(dist), C.byref(st)))
+        stats = st.as_dict()
+        stats["slices"] = int(self.lib.nnd_exact_slice_count(self._h, m))
+        return idx, dist, stats
+
+    def exact_knn(self, rows=None, k=10):
+        """Exact k nearest neighbours (self included) of ``rows`` of the handle's point set (None: all of them): int32 ids and
+        float32 alt-space distances (m, k), rows ascending by (float64 distance, id), and the call's statistics."""
+        if rows is not None:
+            rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        return self._exact(self.lib.nnd_exact_knn_rows, rows, self.n if rows is None else rows.shape[0], k)
+
+    def exact_knn_queries(self, q, k):
+        """The same for external queries, float32 (m, dim), prepared with the point set's own transform."""
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        assert q.ndim == 2 and q.shape[1] == self.dim
+        return self._exact(self.lib.nnd_exact_knn_queries, q, q.shape[0], k)
 
 
 class Searcher:

@@ -1004,6 +1004,32 @@ extern "C" int32_t nnd_pairwise_gram(nnd_handle_t ctx, const int32_t *rows_a, in
     return 0;
 }
 
+// exact k nearest neighbours (exact.hip): rows of the point set / external queries
+static int exact_checks(nnd_ctx *ctx, const char *who, int64_t nq, int32_t k, const void *out_idx, const void *out_dist) {
+    if (ctx->p.flags & NND_FLAG_NO_PREP) { ctx->set_error("%s: this handle holds no prepared rows (NND_FLAG_NO_PREP)", who); return 1; }
+    if (need_data(ctx)) return 1;
+    if (k < 1 || k > NND_WIDE_K || (int64_t)k > ctx->n) { ctx->set_error("%s: k = %d is outside 1 .. min(n, %d) (n = %lld)", who, (int)k, NND_WIDE_K, (long long)ctx->n); return 1; }
+    if (nq < 0 || (nq > 0 && (!out_idx || !out_dist))) { ctx->set_error("%s: null output or negative row count", who); return 1; }
+    return 0;
+}
+extern "C" int32_t nnd_exact_knn_rows(nnd_handle_t ctx, const int64_t *rows, int64_t n_rows, int32_t k, int32_t *out_idx, float *out_dist, nnd_exact_stats *st) {
+    ENTER(ctx);
+    if (!rows) n_rows = ctx->n;
+    if (exact_checks(ctx, "nnd_exact_knn_rows", n_rows, k, out_idx, out_dist)) return 1;
+    return nnd_exact_knn_impl(ctx, rows, nullptr, n_rows, k, out_idx, out_dist, st);
+}
+extern "C" int32_t nnd_exact_knn_queries(nnd_handle_t ctx, const float *q, int64_t n_q, int32_t k, int32_t *out_idx, float *out_dist, nnd_exact_stats *st) {
+    ENTER(ctx);
+    if (exact_checks(ctx, "nnd_exact_knn_queries", n_q, k, out_idx, out_dist)) return 1;
+    if (!q && n_q > 0) { ctx->set_error("nnd_exact_knn_queries: null queries"); return 1; }
+    if (!q) { if (st) *st = nnd_exact_stats{}; return 0; }
+    return nnd_exact_knn_impl(ctx, nullptr, q, n_q, k, out_idx, out_dist, st);
+}
+extern "C" int32_t nnd_exact_slice_count(nnd_handle_t ctx, int64_t n_rows) {
+    if (!ctx) return 0;
+    return nnd_exact_slices_for(ctx->n, n_rows);  // (of the first batch: exact.hip takes at most EX_BATCH query rows per pass)
+}
+
 // Run on the caller's HIP stream (e.g. torch's current stream) instead of the handle's own: the library's kernels and the
 // caller's work are then ordered by the stream itself, no host synchronisation between them.  NULL: back to own.
 extern "C" int32_t nnd_set_stream(nnd_handle_t ctx, void *hip_stream) {

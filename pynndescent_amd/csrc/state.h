@@ -252,6 +252,8 @@ struct nnd_handle_s {
     size_t out_cap = 0;
     nnd_hub_result *hub = nullptr;
     struct nnd_sg_state *sg = nullptr;    // searchgraph.hip: workspace and result of the device pruning pass
+    unsigned char *exact_ws = nullptr;    // exact.hip: workspace of the exact search (query rows, partial lists, results), grow-only
+    size_t exact_ws_cap = 0;
 
     long long *counters = nullptr;      // device NND_CNT_STRIPES x CNT_COUNT (stripe 0 doubles as scratch for single-block kernels)
     long long h_counters[CNT_COUNT] = {0};
@@ -356,6 +358,10 @@ int nnd_search_graph_impl(nnd_ctx *ctx, const int32_t *idx_src, const float *dis
                           float diversify_prob, bool aware, float aggressiveness, uint32_t seed, int32_t *fwd_rows_host, float *fwd_dist_host,
                           nnd_search_graph_stats *st);
 int nnd_search_graph_fetch_impl(nnd_ctx *ctx, int32_t *indptr_host, int32_t *indices_host);
+// exact.hip: exact k nearest neighbours of `rows` of the point set (q == nullptr; rows == nullptr: all of them) or of the
+// external queries q (host (nq, d)); host outputs (nq, k)
+int nnd_exact_knn_impl(nnd_ctx *ctx, const int64_t *rows, const float *q, int64_t nq, int k, int32_t *out_idx, float *out_dist, nnd_exact_stats *st);
+int nnd_exact_slices_for(int64_t n, int64_t nq);  // data slices (gridDim.y) of the scan for nq query rows
 int nnd_read_counters(nnd_ctx *ctx);  // device -> ctx->h_counters (synchronises the stream)
 int nnd_zero_counters(nnd_ctx *ctx);
 

@@ -352,6 +352,28 @@ class NNDescent:
             return None
         return (_capi.host_copy(self._neighbor_graph[0]), self._distance_correction(self._neighbor_graph[1]))
 
+    @staticmethod
+    def _recall_rows(n, n_rows, random_state):
+        """The rows ``recall`` samples: ``RandomState(random_state).choice(n, min(n_rows, n), replace=False)``."""
+        return np.random.RandomState(random_state).choice(int(n), size=min(int(n_rows), int(n)), replace=False).astype(np.int64)
+
+    def recall(self, k=None, n_rows=1000, random_state=None):
+        """How good the graph is: the share of the true ``k`` nearest neighbours (self included; ``k`` defaults to
+        ``min(10, n_neighbors)``) that appear anywhere in the graph's row, averaged over ``min(n_rows, n)`` distinct rows
+        drawn by ``_recall_rows`` -- the convention of the reference's tests (tests/test_pynndescent_.py:27-31).  The truth
+        is the exact brute-force search of ``exact_knn`` over the index's data; only the data and the graph are read, so
+        every way of making the index (one or several devices, ``from_graph``, after ``update()``) is covered."""
+        graph_idx = self._neighbor_graph[0]
+        n = graph_idx.shape[0]
+        k = min(10, int(self.n_neighbors)) if k is None else int(k)
+        rows = self._recall_rows(n, n_rows, random_state)
+        data = self._raw_data
+        if hasattr(self, "_vertex_order"):  # prepare() keeps the rows in the search tree's leaf order; the graph keeps its numbering
+            data = data[np.argsort(self._vertex_order), :]
+        true_idx = exact_knn(data, k=k, metric=self.metric, rows=rows, device=getattr(self, "device", 0))[0]
+        hits = sum(int(np.isin(t, a).sum()) for t, a in zip(true_idx, graph_idx[rows]))
+        return hits / float(true_idx.shape[0] * k)
+
     def build_search_graph(self):
         """The pruning pass of ``_init_search_graph`` (pynndescent_.py:1451-1611: diversify, reverse diversify,
         degree prune) on the GPU alone; returns the CSR uint8 graph in the ORIGINAL vertex numbering (``prepare()``
@@ -695,6 +717,58 @@ def nn_descent(data, n_neighbors, rng_state, max_candidates=50, dist="squared_eu
     if correction is not None:
         dst = correction(dst).astype(np.float32)
     return idx, dst
+
+
+def exact_knn(data, queries=None, k=10, metric="euclidean", rows=None, device=0, return_stats=False):
+    """Exact ``k`` nearest neighbours by brute force on the GPU (csrc/exact.hip): of every row of ``data`` (self included), of the
+    rows ``rows`` of it, or of the external ``queries``.  Returns ``(indices int32 (m, k), distances float32-precision (m, k))``
+    in the metric's own space (the correction ``NNDescent.neighbor_graph`` applies), rows ascending, ties to the smaller id;
+    with ``return_stats`` also the call's statistics (rows that needed the float64 tier, kernel times).  The metrics and the
+    input rules are the class's: dot rows and queries are L2-normalised, hellinger takes no negative entry, NaN / inf raise
+    the reference's error.  ``k`` is at most 256 and at most the number of rows."""
+    if queries is not None and rows is not None:
+        raise ValueError("exact_knn takes `queries` (external points) or `rows` (ids of data rows), not both")
+    k = int(k)
+    if k > 256:
+        raise NotImplementedError("pynndescent_amd.exact_knn keeps at most k <= 256 neighbours per row (got k = %d)" % k)
+    m = _metric_record(metric)
+    data = _check_array_no_scan(data)
+    n = data.shape[0]
+    if k < 1 or k > n:
+        raise ValueError("k must be in 1 .. n = %d (got %d)" % (n, k))
+    _raise_if_negative_host(data, m)
+    if queries is not None:
+        from sklearn.utils import assert_all_finite
+
+        queries = _check_array_no_scan(queries)
+        if queries.shape[1] != data.shape[1]:
+            raise ValueError("queries must have shape (n_queries, %d)" % data.shape[1])
+        assert_all_finite(queries)
+        _raise_if_negative_host(queries, m)
+    if rows is not None:
+        rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        if rows.size and (rows.min() < 0 or rows.max() >= n):
+            raise ValueError("rows must be ids in [0, %d)" % n)
+    if m.normalize:  # pynndescent_.py:1101-1102, 2316-2318
+        from sklearn.preprocessing import normalize
+
+        data = normalize(data, norm="l2", copy=True)
+        if queries is not None:
+            queries = normalize(queries, norm="l2", copy=True)
+    # an auxiliary handle: the rows and their prepared copy, no k-lists
+    builder = _capi.Builder(n, data.shape[1], m.code, k, 0, 60, 200, min(60, k), 1, 0.001, [1, 2, 3], [4, 5, 6], device=device,
+                            flags=_capi.NND_FLAG_NO_GRAPH)
+    try:
+        builder.set_data_host(data)
+        _raise_if_nonfinite(builder, data)
+        if queries is not None:
+            idx, dist, stats = builder.exact_knn_queries(queries, k)
+        else:
+            idx, dist, stats = builder.exact_knn(rows, k)
+    finally:
+        builder.close()
+    dist = m.correction(dist)
+    return (idx, dist, stats) if return_stats else (idx, dist)
 
 
 def _build_graph(data, m, n_neighbors, n_trees, leaf_size, max_depth, max_candidates, n_iters, delta, rng_state, tree_rng,
