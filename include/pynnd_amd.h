@@ -22,8 +22,8 @@
  *     nnd_create fails.
  *   - "alt space": distances are squared-euclidean (metric 0),
  *     log2(|x||y|/<x,y>) (metric 1), -log2<x,y> of L2-normalised rows (2),
- *     1/<x,y> (3), 1 - Pearson correlation (4) or log2(sqrt(|x|_1|y|_1) /
- *     sum sqrt(x_i y_i)) (5), exactly what the reference keeps in
+ *     1/<x,y> (3), 1 - Pearson correlation (4), log2(sqrt(|x|_1|y|_1) /
+ *     sum sqrt(x_i y_i)) (5) or log2(|x||y|/<x,y>) + 1/sqrt<x,y> (6, a proxy: handed out as it is), exactly what the reference keeps in
  *     NNDescent._neighbor_graph (distances.py:63-91, 583-630, 680, 759, 1284, 1387);
  *     the caller applies sqrt / 1-2^-d / -1/d / sqrt(1-2^-d) itself
  *     (distances.py:2170-2173), as NNDescent.neighbor_graph does.
@@ -47,6 +47,13 @@ extern "C" {
 #define NND_METRIC_ALT_INNER_PRODUCT 3 /* reference distances.py:759 alternative_inner_product (rows as given) */
 #define NND_METRIC_CORRELATION 4 /* reference distances.py:1284 correlation (a true distance: no correction) */
 #define NND_METRIC_ALT_HELLINGER 5 /* reference distances.py:1387 alternative_hellinger (input must be >= 0) */
+/* Proxy metrics: a distance to build and walk on, with a true distance to rerank by (reference distances.py:2190 proxy_distances).
+ * They continue the numbering of the codes above; the six #define lines above stay the list of the alt-space metrics
+ * (tests/test_metrics_cpu.py holds that list), so this family is an enumeration of its own.
+ * NND_METRIC_PROXY_INNER_PRODUCT: reference distances.py:810 proxy_inner_product (rows as given), the build's and the walk's
+ * distance of metric="proxy_inner_product"; its true distance, the negative inner product, is what nnd_searcher_query_rerank
+ * returns.  <x,y> = 0 is FLT_MAX here, +inf in the reference. */
+enum { NND_METRIC_PROXY_INNER_PRODUCT = 6 };
 
 #define NND_ABI_VERSION 6 /* 6 (round 6): nnd_stats grew join_substeps[] and nnd_shard_info grew gather_bytes[] / gather_section[] at their ends; nnd_host_alloc / nnd_host_free; 5: nnd_search_graph / nnd_search_graph_fetch */
 
@@ -495,6 +502,13 @@ int32_t nnd_searcher_quantize_u8(nnd_searcher_t s, const float *rows /* may be N
 int32_t nnd_searcher_set_codes_u8(nnd_searcher_t s, const float *values, int32_t n_values, const uint8_t *codes /* (n, dim) */);
 int32_t nnd_searcher_query_proxy(nnd_searcher_t s, const float *queries /* (nq, dim) */, int64_t nq, int32_t k, int32_t search_k,
                                  float epsilon, int32_t *out_idx /* (nq, k) */, float *out_dist /* (nq, k) */);
+/* metric="proxy_inner_product" (reference query(), pynndescent_.py:2309-2312, 2363-2371; rerank 776-789).  Valid on a searcher
+ * whose metric has a true distance besides the one it walks on (NND_METRIC_PROXY_INNER_PRODUCT), an error on every other.  The
+ * walk on the float rows with the proxy distance keeps search_k results (1 <= k <= search_k <= 256); they are pushed in ascending
+ * proxy order, by the true distance -<q,x> of the raw query, into a list of k.  Output (nq, k): rows ascending in -<q,x> (float32
+ * accumulation, neither clamped nor corrected), unfilled slots (-1, +inf).  A zero query is searched like any other. */
+int32_t nnd_searcher_query_rerank(nnd_searcher_t s, const float *queries /* (nq, dim) */, int64_t nq, int32_t k, int32_t search_k,
+                                  float epsilon, int32_t *out_idx /* (nq, k) */, float *out_dist /* (nq, k) */);
 int32_t nnd_searcher_destroy(nnd_searcher_t s);
 const char *nnd_searcher_last_error(nnd_searcher_t s /* NULL: the error of a failed create */);
 

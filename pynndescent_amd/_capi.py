@@ -17,11 +17,13 @@ NND_METRIC_ALT_DOT = 2
 NND_METRIC_ALT_INNER_PRODUCT = 3
 NND_METRIC_CORRELATION = 4
 NND_METRIC_ALT_HELLINGER = 5
+NND_METRIC_PROXY_INNER_PRODUCT = 6
 # the reference's metric names on this path -> the space the kernels work in ("sqeuclidean" and "correlation" are that space
 # itself: no correction, distances.py named_distances / fast_distance_alternatives)
 METRIC_CODES = {"euclidean": NND_METRIC_SQEUCLIDEAN, "l2": NND_METRIC_SQEUCLIDEAN, "sqeuclidean": NND_METRIC_SQEUCLIDEAN,
                 "cosine": NND_METRIC_ALT_COSINE, "dot": NND_METRIC_ALT_DOT, "inner_product": NND_METRIC_ALT_INNER_PRODUCT,
-                "correlation": NND_METRIC_CORRELATION, "hellinger": NND_METRIC_ALT_HELLINGER}
+                "correlation": NND_METRIC_CORRELATION, "hellinger": NND_METRIC_ALT_HELLINGER,
+                "proxy_inner_product": NND_METRIC_PROXY_INNER_PRODUCT}
 NND_FLAG_NO_GRAPH = 1  # auxiliary handle: no k-lists / candidate / proposal tables (pruning pass, hub tree)
 NND_FLAG_NO_PREP = 2   # ... and no prepared copy of the rows (hub tree only)
 NND_FLAG_TEST_SELECT_WAVE = 4  # test hook: the one-wave-per-vertex selection kernel
@@ -269,6 +271,7 @@ _SIGNATURES = [
     ("nnd_searcher_quantize_u8", C.c_int32, [_H, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     ("nnd_searcher_set_codes_u8", C.c_int32, [_H, C.c_void_p, C.c_int32, C.c_void_p]),
     ("nnd_searcher_query_proxy", C.c_int32, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
+    ("nnd_searcher_query_rerank", C.c_int32, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
     ("nnd_searcher_destroy", C.c_int32, [_H]),
     ("nnd_searcher_last_error", C.c_char_p, [_H]),
 ]
@@ -634,6 +637,18 @@ class Searcher:
         dist = np.empty((q.shape[0], k), np.float32)
         if self.lib.nnd_searcher_query_proxy(self._h, _ptr(q), q.shape[0], int(k), int(search_k), float(epsilon), _ptr(idx),
                                              _ptr(dist)) != 0:
+            raise NNDError(self.lib.nnd_searcher_last_error(self._h).decode())
+        return idx, dist
+
+    def query_rerank(self, queries, k, search_k, epsilon):
+        """A metric with a true distance besides the one it walks on (proxy_inner_product): the walk on the float rows keeps
+        ``search_k`` results by the proxy distance, the rerank returns the best ``k`` by the true one (-<q,x>)."""
+        q = np.ascontiguousarray(queries, np.float32)
+        assert q.ndim == 2 and q.shape[1] == self.dim
+        idx = np.empty((q.shape[0], k), np.int32)
+        dist = np.empty((q.shape[0], k), np.float32)
+        if self.lib.nnd_searcher_query_rerank(self._h, _ptr(q), q.shape[0], int(k), int(search_k), float(epsilon), _ptr(idx),
+                                              _ptr(dist)) != 0:
             raise NNDError(self.lib.nnd_searcher_last_error(self._h).decode())
         return idx, dist
 

@@ -124,7 +124,7 @@ int nnd_create_impl(nnd_handle_t *out, const nnd_params *p, const int64_t *bound
     if (!out || !p) { gerr("nnd_create: null argument"); return 1; }
     *out = nullptr;
     if (p->n < 1 || p->dim < 1) { gerr("nnd_create: need n >= 1 and dim >= 1 (got n=%lld dim=%d)", (long long)p->n, p->dim); return 1; }
-    if (p->metric < NND_METRIC_SQEUCLIDEAN || p->metric > NND_METRIC_ALT_HELLINGER) { gerr("nnd_create: unknown metric %d", p->metric); return 1; }
+    if (p->metric < NND_METRIC_SQEUCLIDEAN || p->metric > NND_METRIC_PROXY_INNER_PRODUCT) { gerr("nnd_create: unknown metric %d", p->metric); return 1; }
     if (p->n_neighbors < 1 || p->n_neighbors > NND_WIDE_K) { gerr("nnd_create: n_neighbors must be in 1..%d (got %d)", NND_WIDE_K, p->n_neighbors); return 1; }
     if (p->max_candidates < 1 || p->max_candidates > 128) { gerr("nnd_create: max_candidates must be in 1..128 (got %d)", p->max_candidates); return 1; }
     if (p->n_trees < 0 || p->n_trees > 4096 || p->leaf_size < 1) { gerr("nnd_create: bad n_trees (0..4096) / leaf_size"); return 1; }
@@ -1007,6 +1007,7 @@ extern "C" int32_t nnd_pairwise_gram(nnd_handle_t ctx, const int32_t *rows_a, in
 // exact k nearest neighbours (exact.hip): rows of the point set / external queries
 static int exact_checks(nnd_ctx *ctx, const char *who, int64_t nq, int32_t k, const void *out_idx, const void *out_dist) {
     if (ctx->p.flags & NND_FLAG_NO_PREP) { ctx->set_error("%s: this handle holds no prepared rows (NND_FLAG_NO_PREP)", who); return 1; }
+    if (ctx->p.metric == NND_METRIC_PROXY_INNER_PRODUCT) { ctx->set_error("%s: the exact search has no certificate for the proxy inner product (metric 6)", who); return 1; }
     if (need_data(ctx)) return 1;
     if (k < 1 || k > NND_WIDE_K || (int64_t)k > ctx->n) { ctx->set_error("%s: k = %d is outside 1 .. min(n, %d) (n = %lld)", who, (int)k, NND_WIDE_K, (long long)ctx->n); return 1; }
     if (nq < 0 || (nq > 0 && (!out_idx || !out_dist))) { ctx->set_error("%s: null output or negative row count", who); return 1; }

@@ -5,7 +5,7 @@
 // (good enough to RANK); the distances handed back are recomputed from the ORIGINAL rows in the
 // reference's own formulas (distances.py:63-91 squared difference sum; distances.py:583-630
 // log2(sqrt(|x|^2|y|^2)/<x,y>); dot -log2<x,y> :680 on the rows as given (NNDescent normalises them on the host);
-// inner product 1/<x,y> :759; correlation :1284 with the row means first; hellinger :1387) with float64 accumulation,
+// inner product 1/<x,y> :759; its proxy :810; correlation :1284 with the row means first; hellinger :1387) with float64 accumulation,
 // then rows are re-sorted by that value.
 #include "common.h"
 #include "state.h"
@@ -17,7 +17,7 @@ __device__ __forceinline__ double fin_group16_sum_f64(double v) {
     return v;
 }
 
-// The metrics of codes 2..5 (include/pynnd_amd.h): one coordinate pair into the float64 accumulators (correlation: a and b
+// The metrics of codes 2..6 (include/pynnd_amd.h): one coordinate pair into the float64 accumulators (correlation: a and b
 // already centred), then the accumulated sums into the reference's distance.
 __device__ __forceinline__ void fin_acc_x(int metric, double a, double b, double &dot, double &nx, double &ny) {
     if (metric == 5) {
@@ -35,6 +35,11 @@ __device__ __forceinline__ float fin_value_x(int metric, double dt, double ax, d
         if (!(dt > 0.0)) return NND_FLT_MAX;
         const double r = metric == 2 ? -log2(dt) : 1.0 / dt;
         return r > 0.0 ? (float)fmin(r, (double)NND_FLT_MAX) : 0.0f;
+    }
+    if (metric == 6) {  // proxy_inner_product: FLT_MAX for a zero row or <x,y> <= 0 (common.h nnd_proxy_ip_dist)
+        if (ax == 0.0 || ay == 0.0 || !(dt > 0.0)) return NND_FLT_MAX;
+        const double c = -log2(dt / sqrt(ax * ay));
+        return (float)fmin((c > 0.0 ? c : 0.0) + 1.0 / sqrt(dt), (double)NND_FLT_MAX);
     }
     if (metric == 4) {  // correlation: 0 if both rows have zero variance, 1 if <x,y> = 0
         if (ax == 0.0 && ay == 0.0) return 0.0f;
@@ -58,7 +63,7 @@ __device__ __forceinline__ double fin_row_mean(const float *xr, int d, int l16) 
 // are accumulated side by side and up to 16 neighbour rows are in flight per wave (the gather is latency bound when
 // the rows are fetched one after another).
 // METRIC is a template parameter: the euclidean instance does not carry the cosine accumulators (146 -> far fewer
-// registers, i.e. more waves per SIMD for what is a gather-latency-bound kernel).  METRIC 2..5: the other metrics, one
+// registers, i.e. more waves per SIMD for what is a gather-latency-bound kernel).  METRIC 2..6: the other metrics, one
 // instance each (fin_acc_x / fin_value_x).
 template <int METRIC>
 __global__ __launch_bounds__(256, METRIC == 0 ? 6 : 4) void k_finalize(const float *__restrict__ x, int d, int64_t lo, int64_t n, int k, int ks,
@@ -259,6 +264,7 @@ int nnd_launch_finalize(nnd_ctx *ctx, int32_t *out_idx_dev, float *out_dist_dev)
         case 3: kern = k_finalize<3>; break;
         case 4: kern = k_finalize<4>; break;
         case 5: kern = k_finalize<5>; break;
+        case 6: kern = k_finalize<6>; break;
     }
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, ctx->stream, ctx->x_orig, ctx->d, ctx->own_lo, ctx->own_hi,
                        ctx->k, ctx->ks, ctx->knn_e, nnd_vertex_order(ctx), out_idx_dev, out_dist_dev);

@@ -54,7 +54,7 @@ __device__ __forceinline__ bool klist_has(const uint32_t *kl, uint32_t id) {
 #ifndef NND_J16_WAVES
 #define NND_J16_WAVES 3
 #endif
-template <int DC, int KS16, bool SHARD, bool XM = false>
+template <int DC, int KS16, bool SHARD, int XM = 0>
 __global__ __launch_bounds__(256, NND_J16_WAVES) void k_local_join16(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
                                                          int metric, const int32_t *__restrict__ cand,
                                                          const int32_t *__restrict__ order, int64_t v_begin,
@@ -392,7 +392,7 @@ static const int32_t *join_order(const nnd_ctx *ctx, int64_t &v_begin, int64_t &
     return order;
 }
 
-template <int DC, int KS16, bool SHARD, bool XM>
+template <int DC, int KS16, bool SHARD, int XM>
 static int launch_join16_t(nnd_ctx *ctx, int64_t v_begin, int64_t v_end) {
     constexpr int RV = 32, kls = KS16 * 16 + 4;
     constexpr int WAVE_BYTES = NND_J16_QCAP * 8 + 2 * RV * 4 + 4 * 4 + 5 * RV * 4 + RV * kls * 4 + 8;  // = the kernel's
@@ -429,7 +429,7 @@ static int launch_join16_t(nnd_ctx *ctx, int64_t v_begin, int64_t v_end) {
     return 0;
 }
 
-template <int DC, bool XM>
+template <int DC, int XM>
 static int launch_join16_ks(nnd_ctx *ctx, int64_t v_begin, int64_t v_end) {
     if (ctx->pbuf_r) {  // a shard of a row-sharded build: proposals for rows owned elsewhere go to the narrow table
         if (ctx->ks <= 16) return launch_join16_t<DC, 1, true, XM>(ctx, v_begin, v_end);
@@ -487,7 +487,7 @@ __device__ __forceinline__ void nnd_glds16(const void *src, void *lds_dst_wave_u
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(uintptr_t)src,
                                      (__attribute__((address_space(3))) void *)off, 16, 0, 0);
 }
-template <int MCP, int DC, bool SHARD, bool BLOCKED = false, bool SKIP_TRI = false, int ASEL = -1, bool KL = false, bool XM = false>
+template <int MCP, int DC, bool SHARD, bool BLOCKED = false, bool SKIP_TRI = false, int ASEL = -1, bool KL = false, int XM = 0>
 __global__ __launch_bounds__(256, MCP == 32 ? (ASEL >= 0 ? NND_JW_WAVES_SPLIT : NND_JW_WAVES) : 2) void k_local_join_w(const float *__restrict__ xp, int dp,
                                                                        const float *__restrict__ nrm, int metric,
                                                                        const int32_t *__restrict__ cand,
@@ -841,7 +841,7 @@ __global__ __launch_bounds__(256, MCP == 32 ? (ASEL >= 0 ? NND_JW_WAVES_SPLIT : 
     }
 }
 
-template <int MCP, int DC, bool SHARD, bool BLOCKED, bool SKIP_TRI, int ASEL, bool KL, bool XM>
+template <int MCP, int DC, bool SHARD, bool BLOCKED, bool SKIP_TRI, int ASEL, bool KL, int XM>
 static int launch_join_w_t(nnd_ctx *ctx, int64_t v_begin, int64_t v_end, int cstride = 0, int new_off = 0, int old_off = 0) {
     constexpr int RV = 2 * MCP;
     constexpr int WAVE_BYTES = join_w_lds<KL>::wave_bytes(RV);
@@ -875,7 +875,7 @@ static int launch_join_w_t(nnd_ctx *ctx, int64_t v_begin, int64_t v_end, int cst
     return 0;
 }
 
-template <int MCP, int DC, bool XM>
+template <int MCP, int DC, int XM>
 static int launch_join_w(nnd_ctx *ctx, int64_t v_begin, int64_t v_end) {
 #ifdef NND_JW_SPLIT  // two launches, one tile row of new candidates each (k_local_join_w, ASEL)
     if (MCP == 32) {
@@ -915,7 +915,7 @@ static int launch_join_w(nnd_ctx *ctx, int64_t v_begin, int64_t v_end) {
 // max_candidates 65..128: candidate lists [newA(64) newB(64) | oldA(64) oldB(64)] (filled from the front: the B blocks are empty
 // unless a class has more than 64 candidates, and a pass whose `new` block is empty does nothing).  Five passes of the 64-slot
 // kernel cover every pair once: A x A + A x oldA, A x oldB, B x B + B x oldA, B x oldB, A x B.
-template <bool SHARD, bool XM>
+template <bool SHARD, int XM>
 static int launch_join_blocked(nnd_ctx *ctx, int64_t v_begin, int64_t v_end) {
     if (launch_join_w_t<64, 32, SHARD, true, false, -1, false, XM>(ctx, v_begin, v_end, 256, 0, 128)) return 1;
     if (launch_join_w_t<64, 32, SHARD, true, true, -1, false, XM>(ctx, v_begin, v_end, 256, 0, 192)) return 1;
@@ -924,9 +924,11 @@ static int launch_join_blocked(nnd_ctx *ctx, int64_t v_begin, int64_t v_end) {
     return launch_join_w_t<64, 32, SHARD, true, true, -1, false, XM>(ctx, v_begin, v_end, 256, 0, 64);
 }
 
-// XM: the instances for the metrics of codes 2..5 (common.h nnd_gram_to_dist_t); the sqeuclidean / cosine instances do not
-// carry their conversions (a runtime branch among six metrics costs the k_local_join16<32, *, false> epilogue four registers)
-template <bool XM>
+// XM: 1 = the instances for the metrics of codes 2..5 (common.h nnd_gram_to_dist_t); the sqeuclidean / cosine instances (0) do not
+// carry their conversions (a runtime branch among six metrics costs the k_local_join16<32, *, 0> epilogue four registers), and
+// code 6 has instances of its own (2: its conversion alone, no branch on the metric) for the same reason: as one more branch of
+// the XM = 1 epilogue it took k_local_join16<64, 1, false, 1> from 127 to 131 registers, a wave per SIMD less for codes 2..5
+template <int XM>
 static int launch_join_xm(nnd_ctx *ctx, int64_t v_begin, int64_t v_end) {
     const bool wide = ctx->dp >= 128;
     switch (ctx->mcp) {
@@ -944,5 +946,6 @@ static int launch_join_xm(nnd_ctx *ctx, int64_t v_begin, int64_t v_end) {
 
 int nnd_launch_join(nnd_ctx *ctx, int64_t v_begin, int64_t v_end) {
     if (v_end <= v_begin) return 0;
-    return ctx->p.metric >= 2 ? launch_join_xm<true>(ctx, v_begin, v_end) : launch_join_xm<false>(ctx, v_begin, v_end);
+    if (ctx->p.metric == 6) return launch_join_xm<2>(ctx, v_begin, v_end);
+    return ctx->p.metric >= 2 ? launch_join_xm<1>(ctx, v_begin, v_end) : launch_join_xm<0>(ctx, v_begin, v_end);
 }

@@ -71,7 +71,7 @@ __global__ __launch_bounds__(256) void k_colsum_final(const double *__restrict__
 // sum (s x_i)(s h_i)).  A power of two that takes the largest prepared component to <= 2^11: a hyperplane is a difference of
 // two rows (<= 2^12 after scaling), far from the half-precision overflow at 65504 (a row beyond the sampled maximum by
 // more than 16x overflows to inf and is always rechecked exactly: correct, slower).  Unit-row metrics: bound 1; inner
-// product: rows as given, bound max |x|.
+// product and its proxy: rows as given, bound max |x|.
 __global__ void k_screen_scale(float *__restrict__ mean, int d, int dp, int metric) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     float bound = 1.0f;
@@ -79,7 +79,7 @@ __global__ void k_screen_scale(float *__restrict__ mean, int d, int dp, int metr
         float mm = 0.0f;
         for (int j = 0; j < d; j++) mm = fmaxf(mm, fabsf(mean[j]));
         bound = mean[dp + 2] + mm;  // |x_ij - mean_j| <= max |x| + max |mean|
-    } else if (metric == 3) {
+    } else if (metric == 3 || metric == 6) {
         bound = mean[dp + 2];
     }
     int e = 0;
@@ -255,9 +255,9 @@ __global__ __launch_bounds__(256) void k_prep_rows_v4(const float *__restrict__ 
 // computes the partial sums of the members among a rank's OWN rows (x_rows points at row `row0`), exchanges them, and
 // finishes the means from all of them in rank order (nnd_prep_mean_finish): the double-precision sums make the rounded
 // float means the same whatever the split.
-// the sampled column pass runs for sqeuclidean (the centre, and max |x| for the screening scale) and for inner product (max |x|
-// only: its rows are not centred and its column means are never read)
-bool nnd_prep_column_pass(int metric) { return metric == 0 || metric == 3; }
+// the sampled column pass runs for sqeuclidean (the centre, and max |x| for the screening scale) and for inner product and its
+// proxy (max |x| only: their rows are not centred and their column means are never read)
+bool nnd_prep_column_pass(int metric) { return metric == 0 || metric == 3 || metric == 6; }
 void nnd_prep_mean_geometry(int64_t n, int64_t *n_s, int64_t *stride) {
     *n_s = n < NND_MEAN_ROWS ? n : NND_MEAN_ROWS;
     *stride = *n_s > 0 ? n / *n_s : 1;

@@ -23,6 +23,9 @@
 //     the reference's proxy distances (q_quad_proxy) and keeps search_k = proxy_beam_size * k results; its epilogue is
 //     the reference's rerank (pynndescent_.py:776-789): exact distances of the RAW query to the float rows of those
 //     candidates, pushed in ascending proxy order into a list of k (DESIGN.md "Quantized search").
+//   * metric="proxy_inner_product" (RR instances without Q8, code 6): the walk runs on the float rows with the proxy
+//     -log2(cos) + 1 / sqrt<q,x> and keeps search_k results; the same epilogue reranks them by -<q,x> (DESIGN.md "Proxy
+//     distances").
 // Random choices (ties in the tree descent, random start vertices when the tree leaf holds fewer than
 // min(k, n_neighbors) points) come from the counter hash, keyed by the query's number.
 #include <stdarg.h>
@@ -100,7 +103,7 @@ __device__ __forceinline__ float q_quad_dist(const float *__restrict__ x, const 
     acc += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc), 0xB1, 0xF, 0xF, false));
     acc += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc), 0x4E, 0xF, 0xF, false));
     if (metric == 0) return acc;
-    if (metric != 1) return nnd_gram_to_dist(metric, acc, qn2, xn2[v]);  // prepared rows and query (codes 2..5)
+    if (metric != 1) return nnd_gram_to_dist_x<false>(metric, acc, qn2, xn2[v]);  // prepared rows and query (codes 2..5)
     // alternative_cosine (distances.py:600-630)
     const float nx = xn2[v];
     if (qn2 == 0.0f && nx == 0.0f) return 0.0f;
@@ -167,10 +170,29 @@ __device__ __forceinline__ float q_rerank_dist(const float *__restrict__ x, cons
     return acc > 0.0f ? -log2f(acc) : NND_FLT_MAX;
 }
 
+// quad-cooperative <q, x_v> of the query (LDS, dp floats) and the float row `v`: the rerank instances (code 6) take both of
+// their distances from it -- the walk's proxy nnd_proxy_ip_dist(<q,x>, |q|^2, |x|^2) (proxy_inner_product, distances.py:810-838)
+// and the rerank's true distance -<q,x> (inner_product, the reference's _true_distance_func), neither clamped nor corrected
+__device__ __forceinline__ float q_quad_dot(const float *__restrict__ x, int dp, const float *qs, int64_t v, int sub) {
+    const float4 *row = (const float4 *)(x + v * dp);
+    const float4 *q4 = (const float4 *)qs;
+    float acc = 0.0f;
+    for (int c = sub; c < (dp >> 2); c += 4) {
+        const float4 a = row[c], b = q4[c];
+        acc += a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w;
+    }
+    acc += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc), 0xB1, 0xF, 0xF, false));
+    acc += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc), 0x4E, 0xF, 0xF, false));
+    return acc;
+}
+
 // KU: result entries per lane -- entry u of lane j is position 64 u + j of the list (k <= 64 KU: 1, 2 or 4)
 // Q8: quantization="uint8" -- the walk on the code rows (k = search_k), the rerank to k_out in the epilogue; the codebook
-// (256 floats) sits in front of the waves' LDS.  The float instances (Q8 = false) never touch the last five arguments.
-template <bool BIG, int KU, bool Q8 = false>
+// (256 floats) sits in front of the waves' LDS.  The float instances (Q8 = false) never touch the codes, the codebook and cn2.
+// RR: the rerank epilogue (k = search_k, the k_out best by the true distance leave).  Three forms: the float walk without it,
+// the uint8 walk with it, and the float walk with it (Q8 = false, RR = true: metric code 6 and nothing else -- the walk on the
+// float rows by the proxy inner product, the rerank by -<q,x>; the query stays as given, a zero query is searched).
+template <bool BIG, int KU, bool Q8 = false, bool RR = Q8>
 __global__ __launch_bounds__(256) void k_query(const float *__restrict__ x, const float *__restrict__ xn2, int dp, int d, int metric,
                                                int64_t n, const int32_t *__restrict__ indptr, const int32_t *__restrict__ indices,
                                                const float *__restrict__ hyper, const float *__restrict__ offsets,
@@ -346,6 +368,7 @@ __global__ __launch_bounds__(256) void k_query(const float *__restrict__ x, cons
             const int64_t v = cl[c < nc ? c : 0];
             float dv;
             if constexpr (Q8) dv = q_quad_proxy(codes, cn2, dcs, d, metric, (const float *)qsm, qs, qn2, v, sub);
+            else if constexpr (RR) dv = nnd_proxy_ip_dist(q_quad_dot(x, dp, qs, v, sub), qn2, xn2[v]);
             else dv = q_quad_dist(x, xn2, dp, metric, qs, qn2, v, sub);
             if (sub == 0 && c < nc) cd[c] = dv;
         }
@@ -493,7 +516,7 @@ __global__ __launch_bounds__(256) void k_query(const float *__restrict__ x, cons
             }
         }
     }
-    if constexpr (Q8) {  // rerank (pynndescent_.py:776-789, 2364): the walk's search_k results -> the k_out best by exact distance
+    if constexpr (RR) {  // rerank (pynndescent_.py:776-789, 2364): the walk's search_k results -> the k_out best by exact distance
         const int ks = k;
         k = k_out;  // from here on the result list (worst(), result_push) and the output hold k_out entries
         if (!spilled && !dead) {
@@ -501,18 +524,22 @@ __global__ __launch_bounds__(256) void k_query(const float *__restrict__ x, cons
 #pragma unroll
             for (int u = 0; u < KU; u++)
                 if (64 * u + lane < ks) fv[64 * u + lane] = rv[u];  // candidates in ascending proxy order (the frontier is spent)
-            float p = 0.0f;  // the RAW query: the rerank takes query_data, not the normalised query
-            for (int j = lane; j < dp; j += 64) {
-                const float v = j < d ? queries[qi * d + j] : 0.0f;
-                qs[j] = v;
-                p += v * v;
-            }
-            qn2 = nnd_wave_sum_f32(p);
+            if constexpr (Q8) {  // the RAW query: the rerank takes query_data, not the normalised query
+                float p = 0.0f;
+                for (int j = lane; j < dp; j += 64) {
+                    const float v = j < d ? queries[qi * d + j] : 0.0f;
+                    qs[j] = v;
+                    p += v * v;
+                }
+                qn2 = nnd_wave_sum_f32(p);
+            }  // (the float walk of code 6 ran on the raw query: it is in place)
             nnd_wave_lds_sync();
             for (int c0 = 0; c0 < ks; c0 += 16) {
                 const int c = c0 + grp;
                 const int32_t vc = fv[c < ks ? c : 0];
-                const float dv = q_rerank_dist(x, xn2, dp, metric, qs, qn2, vc < 0 ? 0 : vc, sub);
+                float dv;
+                if constexpr (Q8) dv = q_rerank_dist(x, xn2, dp, metric, qs, qn2, vc < 0 ? 0 : vc, sub);
+                else dv = -q_quad_dot(x, dp, qs, vc < 0 ? 0 : vc, sub);
                 if (sub == 0 && c < ks) fd[c] = dv;
             }
             nnd_wave_lds_sync();
@@ -688,7 +715,7 @@ extern "C" int32_t nnd_searcher_create(nnd_searcher_t *out, int32_t device, int6
         return 1;
     };
     if (!out || !data || !indptr || !indices || n < 1 || dim < 1) return fail("bad arguments");
-    if (metric < NND_METRIC_SQEUCLIDEAN || metric > NND_METRIC_ALT_HELLINGER) return fail("unknown metric");
+    if (metric < NND_METRIC_SQEUCLIDEAN || metric > NND_METRIC_PROXY_INNER_PRODUCT) return fail("unknown metric");
     if (n_nodes > 0 && (!hyperplanes || !offsets || !children || !tree_indices)) return fail("tree arrays missing");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail("no HIP device visible (this library has no CPU path)");
@@ -724,15 +751,25 @@ extern "C" int32_t nnd_searcher_set_tier(nnd_searcher_t s, int32_t tier) {
     return 0;
 }
 
-// both query entry points: the walk keeps k results (the float rows) or k = search_k results and reranks them to k_out
-// (q8: the code rows); out_idx / out_dist are (nq, k_out)
-static int searcher_run(nnd_searcher_s *s, const float *queries, int64_t nq, int32_t k, int32_t k_out, float epsilon, bool q8,
-                        int32_t *out_idx, float *out_dist) {
+// the three forms of k_query (its Q8 / RR switches)
+enum q_form { Q_FORM_FLOAT, Q_FORM_U8, Q_FORM_RERANK };
+template <bool BIG>
+static auto query_kernel(q_form form, int k) -> decltype(&k_query<BIG, 1>) {
     // (k > 64, round 5: the result list as two or four entries per lane; the reference takes any k, pynndescent_.py:2275-2379)
-    auto kq_lds = q8 ? (k > 128 ? k_query<false, 4, true> : (k > 64 ? k_query<false, 2, true> : k_query<false, 1, true>))
-                     : (k > 128 ? k_query<false, 4> : (k > 64 ? k_query<false, 2> : k_query<false, 1>));
-    auto kq_big = q8 ? (k > 128 ? k_query<true, 4, true> : (k > 64 ? k_query<true, 2, true> : k_query<true, 1, true>))
-                     : (k > 128 ? k_query<true, 4> : (k > 64 ? k_query<true, 2> : k_query<true, 1>));
+    switch (form) {
+        case Q_FORM_U8: return k > 128 ? k_query<BIG, 4, true> : (k > 64 ? k_query<BIG, 2, true> : k_query<BIG, 1, true>);
+        case Q_FORM_RERANK: return k > 128 ? k_query<BIG, 4, false, true> : (k > 64 ? k_query<BIG, 2, false, true> : k_query<BIG, 1, false, true>);
+        default: return k > 128 ? k_query<BIG, 4> : (k > 64 ? k_query<BIG, 2> : k_query<BIG, 1>);
+    }
+}
+
+// every query entry point: the walk keeps k results (the float rows) or k = search_k results and reranks them to k_out
+// (Q_FORM_U8: the walk on the code rows; Q_FORM_RERANK: on the float rows); out_idx / out_dist are (nq, k_out)
+static int searcher_run(nnd_searcher_s *s, const float *queries, int64_t nq, int32_t k, int32_t k_out, float epsilon, q_form form,
+                        int32_t *out_idx, float *out_dist) {
+    const bool q8 = form == Q_FORM_U8;
+    auto kq_lds = query_kernel<false>(form, k);
+    auto kq_big = query_kernel<true>(form, k);
     if (nq <= 0) return 0;
     if (nq >= (int64_t)0x7FFFFFF0) { s->set_error("nnd_searcher_query: too many queries in one call"); return 1; }
     S_HIP(hipSetDevice(s->device));
@@ -801,7 +838,11 @@ extern "C" int32_t nnd_searcher_query(nnd_searcher_t s, const float *queries, in
                                       float *out_dist) {
     if (!s) { snprintf(g_serr, sizeof(g_serr), "nnd_searcher_query: null searcher"); return 1; }
     if (k < 1 || k > 256) { s->set_error("nnd_searcher_query: k must be in 1..256 (got %d)", k); return 1; }
-    return searcher_run(s, queries, nq, k, k, epsilon, false, out_idx, out_dist);
+    if (s->metric == NND_METRIC_PROXY_INNER_PRODUCT) {
+        s->set_error("nnd_searcher_query: metric %d is a proxy distance: its queries go through nnd_searcher_query_rerank", s->metric);
+        return 1;
+    }
+    return searcher_run(s, queries, nq, k, k, epsilon, Q_FORM_FLOAT, out_idx, out_dist);
 }
 
 // ---- quantization="uint8" (pynndescent_.py:2191-2225, 2309-2364) ----
@@ -882,5 +923,21 @@ extern "C" int32_t nnd_searcher_query_proxy(nnd_searcher_t s, const float *queri
         s->set_error("nnd_searcher_query_proxy: need 1 <= k <= search_k <= 256 (got k %d, search_k %d)", k, search_k);
         return 1;
     }
-    return searcher_run(s, queries, nq, search_k, k, epsilon, true, out_idx, out_dist);
+    return searcher_run(s, queries, nq, search_k, k, epsilon, Q_FORM_U8, out_idx, out_dist);
+}
+
+// ---- metric="proxy_inner_product" (pynndescent_.py:2309-2312, 2363-2371): the float walk with the rerank epilogue ----
+extern "C" int32_t nnd_searcher_query_rerank(nnd_searcher_t s, const float *queries, int64_t nq, int32_t k, int32_t search_k, float epsilon,
+                                             int32_t *out_idx, float *out_dist) {
+    if (!s) { snprintf(g_serr, sizeof(g_serr), "nnd_searcher_query_rerank: null searcher"); return 1; }
+    if (s->metric != NND_METRIC_PROXY_INNER_PRODUCT) {
+        s->set_error("nnd_searcher_query_rerank: metric %d has no true distance to rerank by (the proxy inner product, %d, has)", s->metric,
+                     NND_METRIC_PROXY_INNER_PRODUCT);
+        return 1;
+    }
+    if (search_k < 1 || search_k > 256 || k < 1 || k > search_k) {
+        s->set_error("nnd_searcher_query_rerank: need 1 <= k <= search_k <= 256 (got k %d, search_k %d)", k, search_k);
+        return 1;
+    }
+    return searcher_run(s, queries, nq, search_k, k, epsilon, Q_FORM_RERANK, out_idx, out_dist);
 }

@@ -10,7 +10,8 @@ if the HIP library or a gfx950 device is missing, construction raises.
 Also on the GPU: ``update`` (warm start, pynndescent_.py:2381-2553), ``build_search_graph`` (the pruning
 pass of ``_init_search_graph``, all diversify methods), ``prepare`` (hub search tree + reordering) and
 ``query``.  Metrics: euclidean / l2 / sqeuclidean / cosine / dot / inner_product / correlation / hellinger (hellinger input
-must be non-negative: a negative entry raises ``ValueError``, where the reference computes NaN distances without a word).
+must be non-negative: a negative entry raises ``ValueError``, where the reference computes NaN distances without a word) and
+proxy_inner_product (graph and walk on the reference's proxy distance, queries reranked by the true inner product).
 Out of scope: sparse input, every other metric, ``n_neighbors`` above 256 or
 ``max_candidates`` above 128 (``query``: more than 256 results per query).  Those raise ``NotImplementedError`` naming the reference entry point to use
 instead; ``pynndescent_amd.make_index`` hands such inputs to ``pynndescent.NNDescent`` when it is importable.
@@ -70,6 +71,9 @@ class _Metric(NamedTuple):
     uint8: bool = False  # has a uint8 proxy distance (distances.py:2250-2255 quantized_distances["uint8"])
     normalize: bool = False  # rows L2-normalised before anything else (pynndescent_.py:1101-1102)
     nonnegative: bool = False  # hellinger takes sqrt(x): a negative entry is an error here, NaN distances in the reference
+    # a proxy with a true distance (distances.py:2190 proxy_distances): the graph is built and walked on the kernel distance, which
+    # neighbor_graph hands out as it is; query() keeps proxy_beam_size * k candidates and the device reranks them by the true one
+    proxy: bool = False
 
 
 # corrections: numpy.sqrt, large float32 arrays through the library's threaded sqrtf (the same bits, the fresh pages touched in
@@ -84,6 +88,7 @@ _METRICS = {
     "inner_product": _Metric(_capi.METRIC_CODES["inner_product"], correct_alternative_inner_product),
     "correlation": _Metric(_capi.METRIC_CODES["correlation"], _capi.host_copy, angular=True),
     "hellinger": _Metric(_capi.METRIC_CODES["hellinger"], correct_alternative_hellinger, angular=True, nonnegative=True),
+    "proxy_inner_product": _Metric(_capi.METRIC_CODES["proxy_inner_product"], _capi.host_copy, proxy=True),
 }
 # views of the table by one field
 _DISTANCE_CORRECTIONS = {name: m.correction for name, m in _METRICS.items()}
@@ -99,7 +104,7 @@ def _metric_record(metric, reference_fallback=True):
     if reference_fallback and (callable(metric) or metric in _KNOWN_REFERENCE_METRICS):
         raise NotImplementedError(
             "pynndescent_amd accelerates the dense euclidean / l2 / sqeuclidean / cosine / dot / inner_product / "
-            "correlation / hellinger build only; "
+            "correlation / hellinger / proxy_inner_product build only; "
             "use pynndescent.NNDescent for metric %r" % (metric,)
         )
     raise ValueError("Metric is neither callable, " + "nor a recognised string")
@@ -117,6 +122,24 @@ def _reference_defaults(n, n_neighbors, n_trees=None, n_iters=None, leaf_size=No
     if max_candidates is None:
         max_candidates = min(60, n_neighbors)
     return n_trees, n_iters, leaf_size, max_candidates
+
+
+def _proxy_search_k(k, proxy_beam_size):
+    """``search_k`` of a query that is reranked (pynndescent_.py:2309-2312), within what the query kernel keeps."""
+    search_k = proxy_beam_size * k
+    if search_k < k:
+        raise ValueError("proxy_beam_size must be at least 1 (got %r)" % (proxy_beam_size,))
+    if search_k > 256:
+        raise NotImplementedError("pynndescent_amd keeps proxy_beam_size * k <= 256 candidates per quantized query "
+                                  "(got %d); use index.to_reference()" % search_k)
+    return search_k
+
+
+def _no_exact_for_proxy(metric, m, what):
+    """The exact search certifies its answers with a float64 bound per formula; it has none for a proxy distance."""
+    if m.proxy:
+        raise NotImplementedError("pynndescent_amd.%s does not cover metric %r (a proxy distance: the float64 certificate of the "
+                                  "exact search has no bound for it)" % (what, metric))
 
 
 def _check_quantization(quantization, metric):
@@ -308,6 +331,7 @@ class NNDescent:
         current_random_state = check_random_state(random_state)
         self._distance_correction = m.correction
         self._distance_func = None  # device kernels; see include/pynnd_amd.h NND_METRIC_*
+        self._is_proxy_distance = m.proxy  # pynndescent_.py:1272-1280 (the true distance: the rerank of csrc/query.hip)
         self._angular_trees = m.angular
         self._bit_trees = False
         self._is_sparse = False
@@ -363,6 +387,7 @@ class NNDescent:
         drawn by ``_recall_rows`` -- the convention of the reference's tests (tests/test_pynndescent_.py:27-31).  The truth
         is the exact brute-force search of ``exact_knn`` over the index's data; only the data and the graph are read, so
         every way of making the index (one or several devices, ``from_graph``, after ``update()``) is covered."""
+        _no_exact_for_proxy(self.metric, _METRICS[self.metric], "NNDescent.recall")
         graph_idx = self._neighbor_graph[0]
         n = graph_idx.shape[0]
         k = min(10, int(self.n_neighbors)) if k is None else int(k)
@@ -511,7 +536,7 @@ class NNDescent:
         already has them (unpickled) reuses ``_quantized_values`` / ``_quantized_data``."""
         _check_quantization(self.quantization, self.metric)
         quantized = self.quantization == "uint8"
-        self._is_proxy_distance = quantized
+        self._is_proxy_distance = quantized or _METRICS[self.metric].proxy
         fresh = not hasattr(self, "_search_graph")
         if quantized and (fresh or getattr(self, "_quantized_values", None) is None):
             raw = self._raw_data if fresh else self._raw_data[np.argsort(self._vertex_order)]
@@ -537,23 +562,21 @@ class NNDescent:
         if k > 256:
             raise NotImplementedError("pynndescent_amd answers queries with k <= 256; use index.to_reference() for k = %d" % k)
         _check_quantization(self.quantization, self.metric)
+        m = _METRICS[self.metric]
         search_k = k
-        if self.quantization is not None:  # pynndescent_.py:2309-2312
-            search_k = proxy_beam_size * k
-            if search_k < k:
-                raise ValueError("proxy_beam_size must be at least 1 (got %r)" % (proxy_beam_size,))
-            if search_k > 256:
-                raise NotImplementedError("pynndescent_amd keeps proxy_beam_size * k <= 256 candidates per quantized query "
-                                          "(got %d); use index.to_reference()" % search_k)
+        if self.quantization is not None or m.proxy:  # pynndescent_.py:2309-2312
+            search_k = _proxy_search_k(k, proxy_beam_size)
         if (not hasattr(self, "_search_graph") or getattr(self, "_searcher", None) is None
                 or (self.quantization is not None and not self._searcher.has_codes)):
             self.prepare()
         query_data = np.asarray(query_data).astype(np.float32, order="C")  # pynndescent_.py:2316
         if query_data.ndim != 2 or query_data.shape[1] != self._raw_data.shape[1]:
             raise ValueError("query_data must have shape (n_queries, %d)" % self._raw_data.shape[1])
-        _raise_if_negative_host(query_data, _METRICS[self.metric])
+        _raise_if_negative_host(query_data, m)
         if self.quantization is not None:  # the walk on the codes, the rerank in its epilogue (pynndescent_.py:2321-2322, 2363-2371)
             indices, dists = self._searcher.query_proxy(query_data, k, search_k, epsilon + 1e-32)
+        elif m.proxy:  # the walk on the proxy distance, the rerank by the true one; epsilon as given (pynndescent_.py:2321-2322)
+            indices, dists = self._searcher.query_rerank(query_data, k, search_k, epsilon)
         else:
             indices, dists = self._searcher.query(query_data, k, epsilon)
         found = indices >= 0
@@ -690,6 +713,7 @@ def nn_descent(data, n_neighbors, rng_state, max_candidates=50, dist="squared_eu
     data float32 (n, d); rng_state int64[3]; ``dist``: "squared_euclidean" / "alternative_cosine" / "alternative_dot" /
     "alternative_inner_product" / "correlation" / "alternative_hellinger" (what NNDescent passes, pynndescent_.py:1247-1260),
     "euclidean" / "cosine" / "dot" / "inner_product" / "hellinger" (true distances: the same kernels, corrected on return),
+    "proxy_inner_product" (the proxy distances themselves: it has no correction),
     or the reference function of one of those names (dot: the kernels rank by the L2-normalised rows, as NNDescent's
     normalised data gives; hand in normalised rows for the reference's ranking); ``init_graph``: EMPTY_GRAPH, or the heap triple ``(indices (n, k),
     distances (n, k), flags (n, k))`` the reference accepts (entries with index -1 are empty); ``leaf_array`` int32
@@ -732,6 +756,7 @@ def exact_knn(data, queries=None, k=10, metric="euclidean", rows=None, device=0,
     if k > 256:
         raise NotImplementedError("pynndescent_amd.exact_knn keeps at most k <= 256 neighbours per row (got k = %d)" % k)
     m = _metric_record(metric)
+    _no_exact_for_proxy(metric, m, "exact_knn")
     data = _check_array_no_scan(data)
     n = data.shape[0]
     if k < 1 or k > n:
@@ -866,7 +891,7 @@ def _check_supported_sizes(n_neighbors, max_candidates, init_graph):
 
 def make_index(data, *args, **kwargs):
     """``NNDescent(data, ...)`` on the GPU when the input is in scope (dense data, euclidean / l2 / sqeuclidean / cosine / dot /
-    inner_product / correlation / hellinger, k <= 256);
+    inner_product / correlation / hellinger / proxy_inner_product, k <= 256);
     otherwise -- and only then -- the reference ``pynndescent.NNDescent`` on the CPU when that package is importable
     (SURVEY.md section 8b), with a warning.  A missing HIP library or GPU is never papered over: that still raises."""
     device = kwargs.pop("device", 0)
@@ -881,7 +906,7 @@ def make_index(data, *args, **kwargs):
         return pynndescent.NNDescent(data, *args, **kwargs)
 
 
-# string metrics the reference recognises (distances.py:2103-2168 named_distances keys) -- used only to
+# string metrics the reference recognises (distances.py:2103-2168 named_distances keys, 2190-2239 proxy_distances keys) -- used only to
 # decide between NotImplementedError (valid in the reference, not accelerated) and the reference's ValueError.
 _KNOWN_REFERENCE_METRICS = frozenset(
     """euclidean l2 sqeuclidean manhattan taxicab l1 chebyshev linfinity linfty linf minkowski seuclidean
@@ -889,5 +914,8 @@ _KNOWN_REFERENCE_METRICS = frozenset(
     haversine braycurtis spearmanr tsss true_angular hellinger kantorovich wasserstein wasserstein_1d
     wasserstein-1d kantorovich-1d kantorovich_1d circular_kantorovich circular_wasserstein sinkhorn jensen-shannon
     jensen_shannon symmetric-kl symmetric_kl symmetric_kullback_liebler hamming jaccard dice matching kulsinski
-    rogerstanimoto russellrao sokalsneath sokalmichener yule bit_hamming bit_jaccard""".split()
+    rogerstanimoto russellrao sokalsneath sokalmichener yule bit_hamming bit_jaccard
+    proxy_inner_product proxy_wasserstein_1d proxy_wasserstein-1d proxy_kantorovich proxy_wasserstein
+    proxy_circular_kantorovich proxy_circular_wasserstein proxy_jensen_shannon proxy_jensen-shannon proxy_symmetric_kl
+    proxy_symmetric-kl proxy_sinkhorn""".split()
 )
