@@ -186,6 +186,33 @@ int32_t nnd_host_free(void *p);
  * (nnd_set_stream).  The prepared copy is made once per call, not once per build. */
 int32_t nnd_set_data_host(nnd_handle_t h, const float *x);
 int32_t nnd_set_data_device(nnd_handle_t h, const float *x_dev);
+/* Device arrays of other types (a caller whose embeddings live on the GPU, often in half precision).  dtype: */
+#define NND_DTYPE_FLOAT32 0
+#define NND_DTYPE_FLOAT16 1  /* IEEE binary16 */
+#define NND_DTYPE_BFLOAT16 2
+#define NND_DTYPE_FLOAT64 3
+/* nnd_set_data_device_typed: the point set as (n, dim) C-contiguous rows of `dtype` on the handle's device.  float32 is BORROWED
+ * exactly as nnd_set_data_device borrows it; the other types are converted on the handle's stream into the handle's OWN float32
+ * copy (binary16 / bfloat16 exactly, float64 rounded to nearest even, what numpy's astype(float32) does), and the caller's
+ * buffer is free again once the stream has passed the call.  NND_METRIC_ALT_DOT: rows of every type, float32 included, go into
+ * the own copy L2-normalised (x / sqrt(sum x^2), float32 accumulation, zero rows stay zero), which the host entry leaves to its
+ * caller (pynndescent_.py:1101-1102).  Then the prep kernel runs as for the other two entries; the stream rule is theirs. */
+int32_t nnd_set_data_device_typed(nnd_handle_t h, const void *x_dev, int32_t dtype);
+/* The same conversion without a handle, on `device` and `hip_stream` (NULL: the device's default stream): (n, dim) rows of
+ * `dtype` at src_dev -> float32 at dst_dev, L2-normalised when `normalize` is non-zero.  A query batch before a searcher sees
+ * it; dot's rows where the caller keeps the normalised copy itself.  Asynchronous: nothing is waited for. */
+int32_t nnd_device_rows_f32(int32_t device, void *hip_stream, const void *src_dev, int32_t dtype, int64_t n, int32_t dim,
+                            int32_t normalize, float *dst_dev);
+/* Corrections of the kernels' distances (the reference's distance_correction, pynndescent_.py:1271-1298) on the device, without
+ * a handle: a graph is corrected when NNDescent.neighbor_graph is read, long after its builder is gone.  `count` float32 values
+ * at in_dev -> out_dev, asynchronous on `hip_stream` of `device`.  Unfilled entries (+inf) come out as the host functions map
+ * them: sqrt +inf, cosine 1, inner product 0, hellinger 1. */
+#define NND_CORRECT_COPY 0              /* 32-bit words out, bit for bit (sqeuclidean, correlation, the proxies; the ids of a graph) */
+#define NND_CORRECT_SQRT 1              /* float32 out, correctly rounded: the bits of numpy.sqrt */
+#define NND_CORRECT_ALT_COSINE 2        /* float64 out: 1 - 2^-d */
+#define NND_CORRECT_ALT_INNER_PRODUCT 3 /* float64 out: d >= FLT_MAX ? 0 : -1 / d (an IEEE division: the host's bits) */
+#define NND_CORRECT_ALT_HELLINGER 4     /* float64 out: sqrt(1 - 2^-d) */
+int32_t nnd_device_correct(int32_t device, void *hip_stream, int32_t kind, const float *in_dev, void *out_dev, int64_t count);
 /* *out = 1 when the point set held a NaN or an infinity (seen by the prep kernel while it read the rows).  The reference
  * rejects such input in check_array (pynndescent_.py:1054) with a scan of its own; the host mirror raises the same
  * error from this flag instead of scanning 488 MB on one core (24 ms at 1 M x 128). */
@@ -509,6 +536,16 @@ int32_t nnd_searcher_query_proxy(nnd_searcher_t s, const float *queries /* (nq, 
  * accumulation, neither clamped nor corrected), unfilled slots (-1, +inf).  A zero query is searched like any other. */
 int32_t nnd_searcher_query_rerank(nnd_searcher_t s, const float *queries /* (nq, dim) */, int64_t nq, int32_t k, int32_t search_k,
                                   float epsilon, int32_t *out_idx /* (nq, k) */, float *out_dist /* (nq, k) */);
+/* The three query entries for a caller on the device: queries (float32, C-contiguous), out_idx and out_dist are DEVICE pointers
+ * on the searcher's device, neither copy is made, and the kernels run on `hip_stream` (NULL: the device's default stream) -- the
+ * stream that produced the queries, so that nothing has to be synchronised first.  The call returns when the stream has
+ * drained (the walk's overflow flags are read back in any case).  Everything else is as in the host forms. */
+int32_t nnd_searcher_query_device(nnd_searcher_t s, const float *queries_dev, int64_t nq, int32_t k, float epsilon,
+                                  int32_t *out_idx_dev, float *out_dist_dev, void *hip_stream);
+int32_t nnd_searcher_query_proxy_device(nnd_searcher_t s, const float *queries_dev, int64_t nq, int32_t k, int32_t search_k,
+                                        float epsilon, int32_t *out_idx_dev, float *out_dist_dev, void *hip_stream);
+int32_t nnd_searcher_query_rerank_device(nnd_searcher_t s, const float *queries_dev, int64_t nq, int32_t k, int32_t search_k,
+                                         float epsilon, int32_t *out_idx_dev, float *out_dist_dev, void *hip_stream);
 int32_t nnd_searcher_destroy(nnd_searcher_t s);
 const char *nnd_searcher_last_error(nnd_searcher_t s /* NULL: the error of a failed create */);
 

@@ -24,6 +24,9 @@ METRIC_CODES = {"euclidean": NND_METRIC_SQEUCLIDEAN, "l2": NND_METRIC_SQEUCLIDEA
                 "cosine": NND_METRIC_ALT_COSINE, "dot": NND_METRIC_ALT_DOT, "inner_product": NND_METRIC_ALT_INNER_PRODUCT,
                 "correlation": NND_METRIC_CORRELATION, "hellinger": NND_METRIC_ALT_HELLINGER,
                 "proxy_inner_product": NND_METRIC_PROXY_INNER_PRODUCT}
+# element types of a device array (include/pynnd_amd.h NND_DTYPE_*) and the corrections of nnd_device_correct (NND_CORRECT_*)
+NND_DTYPE_FLOAT32, NND_DTYPE_FLOAT16, NND_DTYPE_BFLOAT16, NND_DTYPE_FLOAT64 = 0, 1, 2, 3
+NND_CORRECT_COPY, NND_CORRECT_SQRT, NND_CORRECT_ALT_COSINE, NND_CORRECT_ALT_INNER_PRODUCT, NND_CORRECT_ALT_HELLINGER = 0, 1, 2, 3, 4
 NND_FLAG_NO_GRAPH = 1  # auxiliary handle: no k-lists / candidate / proposal tables (pruning pass, hub tree)
 NND_FLAG_NO_PREP = 2   # ... and no prepared copy of the rows (hub tree only)
 NND_FLAG_TEST_SELECT_WAVE = 4  # test hook: the one-wave-per-vertex selection kernel
@@ -191,6 +194,9 @@ _SIGNATURES = [
     ("nnd_destroy", C.c_int32, [_H]),
     ("nnd_set_data_host", C.c_int32, [_H, C.c_void_p]),
     ("nnd_set_data_device", C.c_int32, [_H, C.c_void_p]),
+    ("nnd_set_data_device_typed", C.c_int32, [_H, C.c_void_p, C.c_int32]),
+    ("nnd_device_rows_f32", C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
+    ("nnd_device_correct", C.c_int32, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64]),
     ("nnd_data_nonfinite", C.c_int32, [_H, C.POINTER(C.c_int32)]),
     ("nnd_data_negative", C.c_int32, [_H, C.POINTER(C.c_int32)]),
     ("nnd_release_pending", C.c_int32, []),
@@ -272,6 +278,11 @@ _SIGNATURES = [
     ("nnd_searcher_set_codes_u8", C.c_int32, [_H, C.c_void_p, C.c_int32, C.c_void_p]),
     ("nnd_searcher_query_proxy", C.c_int32, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
     ("nnd_searcher_query_rerank", C.c_int32, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
+    ("nnd_searcher_query_device", C.c_int32, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("nnd_searcher_query_proxy_device", C.c_int32, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p]),
+    ("nnd_searcher_query_rerank_device", C.c_int32, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p]),
     ("nnd_searcher_destroy", C.c_int32, [_H]),
     ("nnd_searcher_last_error", C.c_char_p, [_H]),
 ]
@@ -369,6 +380,13 @@ class Builder:
         (``torch.cuda.synchronize()`` / stream sync) unless the handle runs on the producing stream (``set_stream``)."""
         self._keepalive = keepalive
         self._check(self.lib.nnd_set_data_device(self._h, C.c_void_p(int(dev_ptr))))
+
+    def set_data_device_typed(self, dev_ptr, dtype, keepalive=None):
+        """dev_ptr: integer address of an (n, dim) C-contiguous device buffer of ``dtype`` (NND_DTYPE_*).  float32 is borrowed
+        like ``set_data_device``; the other types -- and every type under dot, whose rows are L2-normalised -- are converted
+        into the handle's own float32 copy.  The stream rule is ``set_data_device``'s."""
+        self._keepalive = keepalive
+        self._check(self.lib.nnd_set_data_device_typed(self._h, C.c_void_p(int(dev_ptr)), int(dtype)))
 
     # -- stages ---------------------------------------------------------------------------------
     def make_forest(self):
@@ -652,6 +670,21 @@ class Searcher:
             raise NNDError(self.lib.nnd_searcher_last_error(self._h).decode())
         return idx, dist
 
+    def query_device(self, form, q_ptr, nq, k, search_k, epsilon, idx_ptr, dist_ptr, stream_ptr):
+        """The three query forms (``form``: "float", "proxy", "rerank") on device buffers: float32 (nq, dim) queries at
+        ``q_ptr``, int32 / float32 (nq, k) results at ``idx_ptr`` / ``dist_ptr``, on the HIP stream ``stream_ptr`` (0: the
+        device's default stream).  Returns when the stream has drained."""
+        q, oi, od = C.c_void_p(int(q_ptr)), C.c_void_p(int(idx_ptr)), C.c_void_p(int(dist_ptr))
+        st = C.c_void_p(int(stream_ptr)) if stream_ptr else None
+        if form == "float":
+            rc = self.lib.nnd_searcher_query_device(self._h, q, int(nq), int(k), float(epsilon), oi, od, st)
+        elif form == "proxy":
+            rc = self.lib.nnd_searcher_query_proxy_device(self._h, q, int(nq), int(k), int(search_k), float(epsilon), oi, od, st)
+        else:
+            rc = self.lib.nnd_searcher_query_rerank_device(self._h, q, int(nq), int(k), int(search_k), float(epsilon), oi, od, st)
+        if rc != 0:
+            raise NNDError(self.lib.nnd_searcher_last_error(self._h).decode())
+
     def last_spilled(self):
         """Queries of the last call whose search outgrew the LDS structures and ran on the global-memory tier."""
         return int(self.lib.nnd_searcher_last_spilled(self._h))
@@ -760,3 +793,21 @@ def host_sqrt(a):
     if load_library().nnd_host_sqrt_f32(_ptr(out), _ptr(a), a.size) != 0:
         raise NNDError(load_library().nnd_last_global_error().decode())
     return out
+
+
+def device_rows_f32(device, stream_ptr, src_ptr, dtype, n, dim, normalize, dst_ptr):
+    """(n, dim) rows of ``dtype`` (NND_DTYPE_*) at the device address ``src_ptr`` -> float32 at ``dst_ptr``, L2-normalised when
+    ``normalize``; queued on the HIP stream ``stream_ptr`` (0: the default stream) of ``device``, nothing is waited for."""
+    lib = load_library()
+    if lib.nnd_device_rows_f32(int(device), C.c_void_p(int(stream_ptr)) if stream_ptr else None, C.c_void_p(int(src_ptr)), int(dtype),
+                               int(n), int(dim), 1 if normalize else 0, C.c_void_p(int(dst_ptr))) != 0:
+        raise NNDError(lib.nnd_last_global_error().decode())
+
+
+def device_correct(device, stream_ptr, kind, in_ptr, out_ptr, count):
+    """``count`` float32 kernel distances at ``in_ptr`` -> the metric's own at ``out_ptr`` (``kind``: NND_CORRECT_*; float32 out
+    for COPY and SQRT, float64 for the others), queued on ``stream_ptr`` of ``device``."""
+    lib = load_library()
+    if lib.nnd_device_correct(int(device), C.c_void_p(int(stream_ptr)) if stream_ptr else None, int(kind), C.c_void_p(int(in_ptr)),
+                              C.c_void_p(int(out_ptr)), int(count)) != 0:
+        raise NNDError(lib.nnd_last_global_error().decode())

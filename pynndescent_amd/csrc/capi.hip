@@ -22,6 +22,7 @@ static void gerr(const char *fmt, ...) {
 }
 
 extern "C" int32_t nnd_abi_version(void) { return NND_ABI_VERSION; }
+void nnd_set_global_error(const char *msg) { gerr("%s", msg); }  // the handle-free entries of devarray.hip
 extern "C" const char *nnd_last_global_error(void) { return g_err; }
 extern "C" const char *nnd_last_error(nnd_handle_t h) { return h ? h->err : g_err; }
 
@@ -490,6 +491,29 @@ extern "C" int32_t nnd_set_data_device(nnd_handle_t ctx, const float *x_dev) {
     if (ctx->x_owned) ctx->mem.free(&ctx->x_orig);
     ctx->x_orig = x_dev;
     ctx->x_owned = false;
+    ctx->x_valid = true;
+    return after_data(ctx);
+}
+
+// Rows of another type than float32 (and dot's rows of any type, which the reference normalises before anything else sees
+// them, pynndescent_.py:1101-1102): converted on the device into the handle's own float32 copy -- finalize.hip, exact.hip and
+// hubtree.hip read x_orig raw, so it stays float32 -- then prepared like any other point set.  float32 rows of the other
+// metrics are borrowed as nnd_set_data_device borrows them.
+extern "C" int32_t nnd_set_data_device_typed(nnd_handle_t ctx, const void *x_dev, int32_t dtype) {
+    ENTER(ctx);
+    if (!x_dev) { ctx->set_error("nnd_set_data_device_typed: null data"); return 1; }
+    if (dtype < NND_DTYPE_FLOAT32 || dtype > NND_DTYPE_FLOAT64) { ctx->set_error("nnd_set_data_device_typed: dtype %d is none of NND_DTYPE_*", (int)dtype); return 1; }
+    const bool normalize = ctx->p.metric == NND_METRIC_ALT_DOT;
+    if (dtype == NND_DTYPE_FLOAT32 && !normalize) return nnd_set_data_device(ctx, (const float *)x_dev);
+    if (!(ctx->x_owned && ctx->x_orig)) {
+        if (!ctx->mem.alloc(&ctx->x_orig, (size_t)ctx->n * ctx->d)) { ctx->set_error("nnd_set_data_device_typed: out of device memory for the handle's copy of the rows"); return 1; }
+        ctx->x_owned = true;
+    }
+    if (nnd_launch_rows_f32(ctx->stream, x_dev, dtype, ctx->n, ctx->d, normalize, (float *)ctx->x_orig)) {
+        (void)hipGetLastError();
+        ctx->set_error("nnd_set_data_device_typed: conversion kernel launch failed");
+        return 1;
+    }
     ctx->x_valid = true;
     return after_data(ctx);
 }

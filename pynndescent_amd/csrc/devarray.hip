@@ -1,0 +1,230 @@
+// devarray.hip -- what a caller whose arrays live on the device needs around the build and the search: typed rows (float16 /
+// bfloat16 / float64 / float32) -> the float32 rows every kernel reads, dot's row normalisation, and the corrections
+// NNDescent.neighbor_graph / query apply to the kernels' distances (pynndescent_.py:1271-1298), all without a host round trip.
+// The two exported entries take a device ordinal and a stream instead of a handle: a graph is corrected long after its builder
+// is gone, and a query batch is converted before any searcher sees it.
+#include <float.h>
+#include <stdio.h>
+
+#include "common.h"
+#include "convert_index.h"
+#include "state.h"
+
+// ---- typed rows -> float32 ----
+template <typename T>
+struct conv_traits;
+template <>
+struct conv_traits<float> {  // (dot on float32 rows: the copy that is normalised afterwards)
+    static constexpr int VEC = 4;
+    typedef float4 vec_t;
+    __device__ static __forceinline__ float one(float v) { return v; }
+    __device__ static __forceinline__ void many(const vec_t &v, float *o) { o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; }
+};
+struct conv_f16 { uint16_t bits; };
+struct conv_bf16 { uint16_t bits; };
+__device__ static __forceinline__ float conv_half_bits(uint32_t b) {
+    union { uint16_t u; _Float16 h; } c;
+    c.u = (uint16_t)b;
+    return (float)c.h;  // exact: every binary16 value (subnormals, inf, NaN) is a binary32 value
+}
+template <>
+struct conv_traits<conv_f16> {
+    static constexpr int VEC = 8;
+    typedef uint4 vec_t;
+    __device__ static __forceinline__ float one(conv_f16 v) { return conv_half_bits(v.bits); }
+    __device__ static __forceinline__ void many(const vec_t &v, float *o) {
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            o[2 * i] = conv_half_bits(w[i] & 0xFFFFu);
+            o[2 * i + 1] = conv_half_bits(w[i] >> 16);
+        }
+    }
+};
+template <>
+struct conv_traits<conv_bf16> {  // bfloat16 is the upper half of a binary32: exact
+    static constexpr int VEC = 8;
+    typedef uint4 vec_t;
+    __device__ static __forceinline__ float one(conv_bf16 v) { return __uint_as_float((uint32_t)v.bits << 16); }
+    __device__ static __forceinline__ void many(const vec_t &v, float *o) {
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            o[2 * i] = __uint_as_float(w[i] << 16);
+            o[2 * i + 1] = __uint_as_float(w[i] & 0xFFFF0000u);
+        }
+    }
+};
+struct conv_d4 { double2 a, b; };  // four doubles: two 16-byte loads of one 32-byte aligned group
+template <>
+struct conv_traits<double> {  // round to nearest even, what numpy's astype(float32) does
+    static constexpr int VEC = 4;
+    typedef conv_d4 vec_t;
+    __device__ static __forceinline__ float one(double v) { return __double2float_rn(v); }
+    __device__ static __forceinline__ void many(const vec_t &v, float *o) {
+        o[0] = __double2float_rn(v.a.x); o[1] = __double2float_rn(v.a.y);
+        o[2] = __double2float_rn(v.b.x); o[3] = __double2float_rn(v.b.y);
+    }
+};
+
+// one work item per thread (convert_index.h): a whole aligned vector of the source, or one element of the head / tail.  The
+// destination's vectors are stored whole when they are 16-byte aligned as well (dst_vec), element by element otherwise.
+template <typename T>
+__global__ __launch_bounds__(256) void k_rows_to_f32(const T *__restrict__ src, float *__restrict__ dst, nnd_conv_plan plan, int dst_vec) {
+    typedef conv_traits<T> tr;
+    const int64_t items = nnd_conv_items(plan);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (int64_t)gridDim.x * blockDim.x) {
+        int64_t first;
+        const int len = nnd_conv_item(plan, i, &first);
+        if (len == 1) {
+            dst[first] = tr::one(src[first]);
+            continue;
+        }
+        float o[tr::VEC];
+        tr::many(*(const typename tr::vec_t *)(src + first), o);
+        if (dst_vec) {
+#pragma unroll
+            for (int c = 0; c < tr::VEC; c += 4) *(float4 *)(dst + first + c) = make_float4(o[c], o[c + 1], o[c + 2], o[c + 3]);
+        } else {
+#pragma unroll
+            for (int c = 0; c < tr::VEC; c++) dst[first + c] = o[c];
+        }
+    }
+}
+
+// Correctly rounded float32 square root and quotient, whatever the compiler's float32 defaults are (__fsqrt_rn is the native,
+// approximate instruction here): the float64 operation is correctly rounded, and rounding a 53-bit square root or quotient of
+// 24-bit operands once more to 24 bits cannot differ from rounding the exact value (53 >= 2 * 24 + 2).
+__device__ __forceinline__ float sqrt_rn_f32(float v) { return (float)__dsqrt_rn((double)v); }
+__device__ __forceinline__ float div_rn_f32(float a, float b) { return (float)__ddiv_rn((double)a, (double)b); }
+
+// ---- dot: x / sqrt(sum x^2) in place, one wave per row (pynndescent_.py:1101-1102, sklearn.preprocessing.normalize) ----
+// float32 arithmetic like sklearn's row_norms, a correctly rounded square root and division like numpy's; a zero row stays zero.
+// The order of a plain float32 sum is the wave's here and the host's SIMD width there, and each order carries its own rounding
+// (up to about log2(d) / 2 ulp): two such sums put the rows up to 3 ulp apart (measured at d = 24).  So this side's sum carries
+// its rounding errors along -- every product with its exact error (fma), every addition with its exact error (two_sum), in float32
+// pairs -- and rounds once at the end: what is left between the two is the host's own rounding.
+__device__ __forceinline__ void two_sum(float a, float b, float *s, float *e) {
+#pragma clang fp contract(off)
+    const float t = a + b, bb = t - a;
+    *s = t;
+    *e = (a - (t - bb)) + (b - bb);
+}
+__global__ __launch_bounds__(256) void k_normalize_rows(float *__restrict__ x, int64_t n, int d) {
+    const int lane = nnd_lane();
+    const int64_t row = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (row >= n) return;
+    float *r = x + row * d;
+    float hi = 0.0f, lo = 0.0f;
+    for (int j = lane; j < d; j += 64) {
+#pragma clang fp contract(off)  // (p must be the rounded product: the fma below measures exactly that rounding)
+        const float v = r[j], p = v * v, pe = fmaf(v, v, -p);
+        float e;
+        two_sum(hi, p, &hi, &e);
+        lo += e + pe;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float oh = __shfl_xor(hi, o, 64), ol = __shfl_xor(lo, o, 64);
+        float e;
+        two_sum(hi, oh, &hi, &e);
+        lo = (lo + ol) + e;
+    }
+    const float s = hi + lo;
+    if (!(s > 0.0f) && !(s != s)) return;  // zero row (a NaN goes on: the prep kernel flags it)
+    const float nrm = sqrt_rn_f32(s);
+    for (int j = lane; j < d; j += 64) r[j] = div_rn_f32(r[j], nrm);
+}
+
+template <typename T>
+static int rows_launch(hipStream_t st, const void *src, int64_t count, float *dst) {
+    typedef conv_traits<T> tr;
+    const nnd_conv_plan plan = nnd_conv_make_plan((uint64_t)(uintptr_t)src, (int)sizeof(T), tr::VEC, count);
+    const int64_t items = nnd_conv_items(plan);
+    if (items <= 0) return 0;
+    const int dst_vec = (((uintptr_t)dst + sizeof(float) * (size_t)plan.head) & 15) == 0 ? 1 : 0;
+    int64_t blocks = (items + 255) / 256;
+    if (blocks > 262144) blocks = 262144;  // (the kernel strides over the rest)
+    hipLaunchKernelGGL(k_rows_to_f32<T>, dim3((unsigned)blocks), dim3(256), 0, st, (const T *)src, dst, plan, dst_vec);
+    return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
+// (n, d) rows of `dtype` at src -> float32 at dst (both on the current device), then dot's normalisation when asked for
+int nnd_launch_rows_f32(hipStream_t st, const void *src, int dtype, int64_t n, int d, bool normalize, float *dst) {
+    const int64_t count = n * (int64_t)d;
+    int rc = 1;
+    switch (dtype) {
+        case NND_DTYPE_FLOAT32:
+            if ((const void *)dst == src) rc = 0;
+            else rc = rows_launch<float>(st, src, count, dst);
+            break;
+        case NND_DTYPE_FLOAT16: rc = rows_launch<conv_f16>(st, src, count, dst); break;
+        case NND_DTYPE_BFLOAT16: rc = rows_launch<conv_bf16>(st, src, count, dst); break;
+        case NND_DTYPE_FLOAT64: rc = rows_launch<double>(st, src, count, dst); break;
+        default: return 1;
+    }
+    if (rc) return 1;
+    if (normalize && n > 0 && d > 0) {
+        hipLaunchKernelGGL(k_normalize_rows, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, dst, n, d);
+        if (hipGetLastError() != hipSuccess) return 1;
+    }
+    return 0;
+}
+
+// ---- corrections ----
+template <int KIND, typename OUT>
+__global__ __launch_bounds__(256) void k_correct(const float *__restrict__ in, OUT *__restrict__ out, int64_t count) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x) {
+        const float d = in[i];
+        if (KIND == NND_CORRECT_SQRT) out[i] = (OUT)sqrt_rn_f32(d);
+        else if (KIND == NND_CORRECT_ALT_COSINE) out[i] = (OUT)(1.0 - exp2(-(double)d));
+        else if (KIND == NND_CORRECT_ALT_INNER_PRODUCT) out[i] = (OUT)(d >= FLT_MAX ? 0.0 : __ddiv_rn(-1.0, (double)d));
+        else out[i] = (OUT)__dsqrt_rn(1.0 - exp2(-(double)d));
+    }
+}
+// the copy moves words, not floats: every bit pattern (the ids of a graph as well) arrives as it left
+__global__ __launch_bounds__(256) void k_copy_words(const uint32_t *__restrict__ in, uint32_t *__restrict__ out, int64_t count) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x) out[i] = in[i];
+}
+
+static thread_local char g_daerr[256] = {0};
+void nnd_set_global_error(const char *msg);  // capi.hip: what nnd_last_global_error returns
+
+static int da_fail(const char *msg) {
+    snprintf(g_daerr, sizeof(g_daerr), "%s", msg);
+    nnd_set_global_error(g_daerr);
+    return 1;
+}
+
+extern "C" int32_t nnd_device_rows_f32(int32_t device, void *hip_stream, const void *src_dev, int32_t dtype, int64_t n, int32_t dim,
+                                       int32_t normalize, float *dst_dev) {
+    if (n < 0 || dim < 0 || dtype < NND_DTYPE_FLOAT32 || dtype > NND_DTYPE_FLOAT64) return da_fail("nnd_device_rows_f32: bad shape or dtype");
+    if (n == 0 || dim == 0) return 0;
+    if (!src_dev || !dst_dev) return da_fail("nnd_device_rows_f32: null pointer");
+    if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return da_fail("nnd_device_rows_f32: no such device"); }
+    if (nnd_launch_rows_f32((hipStream_t)hip_stream, src_dev, dtype, n, dim, normalize != 0, dst_dev)) {
+        (void)hipGetLastError();
+        return da_fail("nnd_device_rows_f32: kernel launch failed");
+    }
+    return 0;
+}
+
+extern "C" int32_t nnd_device_correct(int32_t device, void *hip_stream, int32_t kind, const float *in_dev, void *out_dev, int64_t count) {
+    if (count < 0 || kind < NND_CORRECT_COPY || kind > NND_CORRECT_ALT_HELLINGER) return da_fail("nnd_device_correct: bad kind or count");
+    if (count == 0) return 0;
+    if (!in_dev || !out_dev) return da_fail("nnd_device_correct: null pointer");
+    if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return da_fail("nnd_device_correct: no such device"); }
+    hipStream_t st = (hipStream_t)hip_stream;
+    int64_t blocks = (count + 255) / 256;
+    if (blocks > 262144) blocks = 262144;
+    const dim3 g((unsigned)blocks), b(256);
+    switch (kind) {
+        case NND_CORRECT_COPY: hipLaunchKernelGGL(k_copy_words, g, b, 0, st, (const uint32_t *)in_dev, (uint32_t *)out_dev, count); break;
+        case NND_CORRECT_SQRT: hipLaunchKernelGGL((k_correct<NND_CORRECT_SQRT, float>), g, b, 0, st, in_dev, (float *)out_dev, count); break;
+        case NND_CORRECT_ALT_COSINE: hipLaunchKernelGGL((k_correct<NND_CORRECT_ALT_COSINE, double>), g, b, 0, st, in_dev, (double *)out_dev, count); break;
+        case NND_CORRECT_ALT_INNER_PRODUCT: hipLaunchKernelGGL((k_correct<NND_CORRECT_ALT_INNER_PRODUCT, double>), g, b, 0, st, in_dev, (double *)out_dev, count); break;
+        default: hipLaunchKernelGGL((k_correct<NND_CORRECT_ALT_HELLINGER, double>), g, b, 0, st, in_dev, (double *)out_dev, count); break;
+    }
+    if (hipGetLastError() != hipSuccess) return da_fail("nnd_device_correct: kernel launch failed");
+    return 0;
+}

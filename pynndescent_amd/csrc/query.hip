@@ -766,13 +766,14 @@ static auto query_kernel(q_form form, int k) -> decltype(&k_query<BIG, 1>) {
 // every query entry point: the walk keeps k results (the float rows) or k = search_k results and reranks them to k_out
 // (Q_FORM_U8: the walk on the code rows; Q_FORM_RERANK: on the float rows); out_idx / out_dist are (nq, k_out)
 static int searcher_run(nnd_searcher_s *s, const float *queries, int64_t nq, int32_t k, int32_t k_out, float epsilon, q_form form,
-                        int32_t *out_idx, float *out_dist) {
+                        int32_t *out_idx, float *out_dist, bool on_device = false, hipStream_t user_stream = nullptr) {
     const bool q8 = form == Q_FORM_U8;
     auto kq_lds = query_kernel<false>(form, k);
     auto kq_big = query_kernel<true>(form, k);
     if (nq <= 0) return 0;
     if (nq >= (int64_t)0x7FFFFFF0) { s->set_error("nnd_searcher_query: too many queries in one call"); return 1; }
     S_HIP(hipSetDevice(s->device));
+    hipStream_t st = on_device ? user_stream : s->stream;
     nnd_scratch tmp;  // the buffers of this call
     int32_t *dlist = nullptr;
     unsigned char *scratch = nullptr;
@@ -785,21 +786,22 @@ static int searcher_run(nnd_searcher_s *s, const float *queries, int64_t nq, int
     s->last_spilled = 0;
     std::vector<uint8_t> hov((size_t)nq, 1);
     do {
-        float *dq = tmp.get<float>(s, (size_t)nq * s->d), *dd = tmp.get<float>(s, (size_t)nq * k_out);
-        int32_t *di = tmp.get<int32_t>(s, (size_t)nq * k_out);
+        float *dq = on_device ? const_cast<float *>(queries) : tmp.get<float>(s, (size_t)nq * s->d);
+        float *dd = on_device ? out_dist : tmp.get<float>(s, (size_t)nq * k_out);
+        int32_t *di = on_device ? out_idx : tmp.get<int32_t>(s, (size_t)nq * k_out);
         uint8_t *dov = tmp.get<uint8_t>(s, (size_t)nq);
         if (!dq || !dd || !di || !dov) { s->set_error("nnd_searcher_query: out of device memory"); rc = 1; break; }
-        if (hipMemcpyAsync(dq, queries, sizeof(float) * (size_t)nq * s->d, hipMemcpyHostToDevice, s->stream) != hipSuccess) { s->set_error("H2D of the queries failed"); rc = 1; break; }
+        if (!on_device && hipMemcpyAsync(dq, queries, sizeof(float) * (size_t)nq * s->d, hipMemcpyHostToDevice, st) != hipSuccess) { s->set_error("H2D of the queries failed"); rc = 1; break; }
         if (!s->force_big) {
             if (smem > 64 * 1024 && hipFuncSetAttribute((const void *)kq_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) {
                 s->set_error("nnd_searcher_query: rows of %d floats need %zu bytes of LDS per workgroup", s->d, smem); rc = 1; break;
             }
-            hipLaunchKernelGGL(kq_lds, dim3((unsigned)((nq + 3) / 4)), dim3(256), smem, s->stream, s->x, s->xn2, s->dp, s->d, s->metric, s->n,
+            hipLaunchKernelGGL(kq_lds, dim3((unsigned)((nq + 3) / 4)), dim3(256), smem, st, s->x, s->xn2, s->dp, s->d, s->metric, s->n,
                                s->indptr, s->indices, s->hyper, s->offsets, s->children, s->tree_idx, s->n_nodes, dq, nq, k, epsilon,
                                s->min_distance, s->n_neighbors, s->seed, di, dd, dov, (const int32_t *)nullptr, 0, (unsigned char *)nullptr, (size_t)0,
                                (const uint8_t *)s->codes, s->dcs, (const float *)s->lut, (const float *)s->cn2, k_out);
             if (hipGetLastError() != hipSuccess) { s->set_error("k_query launch failed"); rc = 1; break; }
-            if (hipMemcpyAsync(hov.data(), dov, (size_t)nq, hipMemcpyDeviceToHost, s->stream) != hipSuccess || hipStreamSynchronize(s->stream) != hipSuccess) {
+            if (hipMemcpyAsync(hov.data(), dov, (size_t)nq, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
                 s->set_error("nnd_searcher_query: kernel or D2H failed: %s", hipGetErrorString(hipGetLastError())); rc = 1; break;
             }
         }
@@ -816,10 +818,10 @@ static int searcher_run(nnd_searcher_s *s, const float *queries, int64_t nq, int
             if (!scratch || !dlist) {
                 s->set_error("nnd_searcher_query: out of device memory for the global-memory tier (%zu bytes)", stride * batch); rc = 1; break;
             }
-            if (hipMemcpyAsync(dlist, again.data(), sizeof(int32_t) * again.size(), hipMemcpyHostToDevice, s->stream) != hipSuccess) { s->set_error("H2D of the query list failed"); rc = 1; break; }
+            if (hipMemcpyAsync(dlist, again.data(), sizeof(int32_t) * again.size(), hipMemcpyHostToDevice, st) != hipSuccess) { s->set_error("H2D of the query list failed"); rc = 1; break; }
             for (size_t b0 = 0; b0 < again.size() && !rc; b0 += batch) {
                 const int nb = (int)(again.size() - b0 < batch ? again.size() - b0 : batch);
-                hipLaunchKernelGGL(kq_big, dim3((unsigned)((nb + 3) / 4)), dim3(256), 4 * per_wave_big + lut_bytes, s->stream, s->x, s->xn2, s->dp, s->d,
+                hipLaunchKernelGGL(kq_big, dim3((unsigned)((nb + 3) / 4)), dim3(256), 4 * per_wave_big + lut_bytes, st, s->x, s->xn2, s->dp, s->d,
                                    s->metric, s->n, s->indptr, s->indices, s->hyper, s->offsets, s->children, s->tree_idx, s->n_nodes, dq, nq, k, epsilon,
                                    s->min_distance, s->n_neighbors, s->seed, di, dd, (uint8_t *)nullptr, (const int32_t *)(dlist + b0), nb, scratch, stride,
                                    (const uint8_t *)s->codes, s->dcs, (const float *)s->lut, (const float *)s->cn2, k_out);
@@ -827,9 +829,9 @@ static int searcher_run(nnd_searcher_s *s, const float *queries, int64_t nq, int
             }
             if (rc) break;
         }
-        if (hipMemcpyAsync(out_idx, di, sizeof(int32_t) * (size_t)nq * k_out, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
-            hipMemcpyAsync(out_dist, dd, sizeof(float) * (size_t)nq * k_out, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
-            hipStreamSynchronize(s->stream) != hipSuccess) { s->set_error("nnd_searcher_query: kernel or D2H failed: %s", hipGetErrorString(hipGetLastError())); rc = 1; break; }
+        if ((!on_device && (hipMemcpyAsync(out_idx, di, sizeof(int32_t) * (size_t)nq * k_out, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                            hipMemcpyAsync(out_dist, dd, sizeof(float) * (size_t)nq * k_out, hipMemcpyDeviceToHost, st) != hipSuccess)) ||
+            hipStreamSynchronize(st) != hipSuccess) { s->set_error("nnd_searcher_query: kernel or D2H failed: %s", hipGetErrorString(hipGetLastError())); rc = 1; break; }
     } while (0);
     return rc;
 }
@@ -940,4 +942,47 @@ extern "C" int32_t nnd_searcher_query_rerank(nnd_searcher_t s, const float *quer
         return 1;
     }
     return searcher_run(s, queries, nq, search_k, k, epsilon, Q_FORM_RERANK, out_idx, out_dist);
+}
+
+// ---- the same three entries for queries and results that live on the device (include/pynnd_amd.h) ----
+static int device_args(nnd_searcher_s *s, const char *who, const void *q, int64_t nq, const void *oi, const void *od) {
+    if (nq > 0 && (!q || !oi || !od)) { s->set_error("%s: null device pointer", who); return 1; }
+    return 0;
+}
+extern "C" int32_t nnd_searcher_query_device(nnd_searcher_t s, const float *queries_dev, int64_t nq, int32_t k, float epsilon,
+                                             int32_t *out_idx_dev, float *out_dist_dev, void *hip_stream) {
+    if (!s) { snprintf(g_serr, sizeof(g_serr), "nnd_searcher_query_device: null searcher"); return 1; }
+    if (k < 1 || k > 256) { s->set_error("nnd_searcher_query_device: k must be in 1..256 (got %d)", k); return 1; }
+    if (s->metric == NND_METRIC_PROXY_INNER_PRODUCT) {
+        s->set_error("nnd_searcher_query_device: metric %d is a proxy distance: its queries go through nnd_searcher_query_rerank_device", s->metric);
+        return 1;
+    }
+    if (device_args(s, "nnd_searcher_query_device", queries_dev, nq, out_idx_dev, out_dist_dev)) return 1;
+    return searcher_run(s, queries_dev, nq, k, k, epsilon, Q_FORM_FLOAT, out_idx_dev, out_dist_dev, true, (hipStream_t)hip_stream);
+}
+extern "C" int32_t nnd_searcher_query_proxy_device(nnd_searcher_t s, const float *queries_dev, int64_t nq, int32_t k, int32_t search_k,
+                                                   float epsilon, int32_t *out_idx_dev, float *out_dist_dev, void *hip_stream) {
+    if (!s) { snprintf(g_serr, sizeof(g_serr), "nnd_searcher_query_proxy_device: null searcher"); return 1; }
+    if (!s->codes) { s->set_error("nnd_searcher_query_proxy_device: the searcher has no codes (nnd_searcher_quantize_u8 first)"); return 1; }
+    if (search_k < 1 || search_k > 256 || k < 1 || k > search_k) {
+        s->set_error("nnd_searcher_query_proxy_device: need 1 <= k <= search_k <= 256 (got k %d, search_k %d)", k, search_k);
+        return 1;
+    }
+    if (device_args(s, "nnd_searcher_query_proxy_device", queries_dev, nq, out_idx_dev, out_dist_dev)) return 1;
+    return searcher_run(s, queries_dev, nq, search_k, k, epsilon, Q_FORM_U8, out_idx_dev, out_dist_dev, true, (hipStream_t)hip_stream);
+}
+extern "C" int32_t nnd_searcher_query_rerank_device(nnd_searcher_t s, const float *queries_dev, int64_t nq, int32_t k, int32_t search_k,
+                                                    float epsilon, int32_t *out_idx_dev, float *out_dist_dev, void *hip_stream) {
+    if (!s) { snprintf(g_serr, sizeof(g_serr), "nnd_searcher_query_rerank_device: null searcher"); return 1; }
+    if (s->metric != NND_METRIC_PROXY_INNER_PRODUCT) {
+        s->set_error("nnd_searcher_query_rerank_device: metric %d has no true distance to rerank by (the proxy inner product, %d, has)", s->metric,
+                     NND_METRIC_PROXY_INNER_PRODUCT);
+        return 1;
+    }
+    if (search_k < 1 || search_k > 256 || k < 1 || k > search_k) {
+        s->set_error("nnd_searcher_query_rerank_device: need 1 <= k <= search_k <= 256 (got k %d, search_k %d)", k, search_k);
+        return 1;
+    }
+    if (device_args(s, "nnd_searcher_query_rerank_device", queries_dev, nq, out_idx_dev, out_dist_dev)) return 1;
+    return searcher_run(s, queries_dev, nq, search_k, k, epsilon, Q_FORM_RERANK, out_idx_dev, out_dist_dev, true, (hipStream_t)hip_stream);
 }

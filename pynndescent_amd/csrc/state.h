@@ -336,6 +336,8 @@ int nnd_launch_proposal_export_regions(nnd_ctx *ctx, int64_t cap, int32_t *targe
 int nnd_launch_join(nnd_ctx *ctx, int64_t v_begin, int64_t v_end);
 int nnd_launch_merge(nnd_ctx *ctx);
 int nnd_launch_finalize(nnd_ctx *ctx, int32_t *out_idx_dev, float *out_dist_dev);
+// devarray.hip: (n, d) rows of NND_DTYPE_* `dtype` -> float32 at dst (current device, stream st), dot's normalisation on request
+int nnd_launch_rows_f32(hipStream_t st, const void *src, int dtype, int64_t n, int d, bool normalize, float *dst);
 int nnd_launch_pairwise(nnd_ctx *ctx, const int32_t *rows_a_dev, int na, const int32_t *rows_b_dev, int nb,
                         float *out_dev);
 int nnd_launch_import_proposals(nnd_ctx *ctx, const uint64_t *keys, const int32_t *targets, int64_t count);

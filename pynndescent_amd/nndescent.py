@@ -74,20 +74,25 @@ class _Metric(NamedTuple):
     # a proxy with a true distance (distances.py:2190 proxy_distances): the graph is built and walked on the kernel distance, which
     # neighbor_graph hands out as it is; query() keeps proxy_beam_size * k candidates and the device reranks them by the true one
     proxy: bool = False
+    device_kind: int = _capi.NND_CORRECT_COPY  # the same correction on a device tensor (include/pynnd_amd.h NND_CORRECT_*)
 
 
 # corrections: numpy.sqrt, large float32 arrays through the library's threaded sqrtf (the same bits, the fresh pages touched in
 # parallel); "sqeuclidean" and "correlation" are the kernels' own space, with no correction (pynndescent_.py:1271-1298) --
 # neighbor_graph still hands out a copy
 _METRICS = {
-    "euclidean": _Metric(_capi.METRIC_CODES["euclidean"], _capi.host_sqrt, uint8=True),
-    "l2": _Metric(_capi.METRIC_CODES["l2"], _capi.host_sqrt, uint8=True),
+    "euclidean": _Metric(_capi.METRIC_CODES["euclidean"], _capi.host_sqrt, uint8=True, device_kind=_capi.NND_CORRECT_SQRT),
+    "l2": _Metric(_capi.METRIC_CODES["l2"], _capi.host_sqrt, uint8=True, device_kind=_capi.NND_CORRECT_SQRT),
     "sqeuclidean": _Metric(_capi.METRIC_CODES["sqeuclidean"], _capi.host_copy),
-    "cosine": _Metric(_capi.METRIC_CODES["cosine"], correct_alternative_cosine, angular=True, uint8=True),
-    "dot": _Metric(_capi.METRIC_CODES["dot"], correct_alternative_cosine, angular=True, uint8=True, normalize=True),
-    "inner_product": _Metric(_capi.METRIC_CODES["inner_product"], correct_alternative_inner_product),
+    "cosine": _Metric(_capi.METRIC_CODES["cosine"], correct_alternative_cosine, angular=True, uint8=True,
+                      device_kind=_capi.NND_CORRECT_ALT_COSINE),
+    "dot": _Metric(_capi.METRIC_CODES["dot"], correct_alternative_cosine, angular=True, uint8=True, normalize=True,
+                   device_kind=_capi.NND_CORRECT_ALT_COSINE),
+    "inner_product": _Metric(_capi.METRIC_CODES["inner_product"], correct_alternative_inner_product,
+                             device_kind=_capi.NND_CORRECT_ALT_INNER_PRODUCT),
     "correlation": _Metric(_capi.METRIC_CODES["correlation"], _capi.host_copy, angular=True),
-    "hellinger": _Metric(_capi.METRIC_CODES["hellinger"], correct_alternative_hellinger, angular=True, nonnegative=True),
+    "hellinger": _Metric(_capi.METRIC_CODES["hellinger"], correct_alternative_hellinger, angular=True, nonnegative=True,
+                         device_kind=_capi.NND_CORRECT_ALT_HELLINGER),
     "proxy_inner_product": _Metric(_capi.METRIC_CODES["proxy_inner_product"], _capi.host_copy, proxy=True),
 }
 # views of the table by one field
@@ -168,6 +173,105 @@ def uint8_codebook(raw, random_state):
     return np.quantile(sample, np.linspace(0, 1, 256)).astype(np.float32)
 
 
+# ---- device arrays: input that lives on the GPU (in practice a torch.Tensor on a HIP device; torch is imported on this path only)
+_DEVICE_DTYPES = {"float32": _capi.NND_DTYPE_FLOAT32, "float16": _capi.NND_DTYPE_FLOAT16, "bfloat16": _capi.NND_DTYPE_BFLOAT16,
+                  "float64": _capi.NND_DTYPE_FLOAT64}
+
+
+def _is_device_array(a):
+    """A device array: ``is_cuda`` is true and there is a ``data_ptr()`` (with ``dtype``, ``shape``, ``device``, ``is_contiguous()``)."""
+    return getattr(a, "is_cuda", False) is True and callable(getattr(a, "data_ptr", None))
+
+
+def _check_device_array(a, device=0, what="data"):
+    """check_array for a device array: 2-D, float32 / float16 / bfloat16 / float64, on the GPU ``device`` names when that is not
+    0 (the default means "where the array is").  Returns ``(the array, contiguous -- a device copy when it was not --, its
+    NND_DTYPE_* code, its device ordinal)``; no device work besides that copy, no torch."""
+    name = str(a.dtype).rsplit(".", 1)[-1]
+    if name not in _DEVICE_DTYPES:
+        raise TypeError("pynndescent_amd takes device arrays of dtype float32, float16, bfloat16 or float64 (%s has dtype %s)"
+                        % (what, a.dtype))
+    if len(a.shape) != 2:
+        raise ValueError("Expected 2D array, got %dD array instead: %s has shape %s" % (len(a.shape), what, tuple(a.shape)))
+    ordinal = getattr(a.device, "index", None)
+    ordinal = 0 if ordinal is None else int(ordinal)
+    if device and int(device) != ordinal:
+        raise ValueError("device=%d, but %s is on device %d: the index runs where its data is" % (int(device), what, ordinal))
+    if not a.is_contiguous():
+        a = a.contiguous()
+    return a, _DEVICE_DTYPES[name], ordinal
+
+
+def _torch():
+    import torch  # (lazily: a host-only install never needs it)
+
+    return torch
+
+
+class _OnTorchStream:
+    """The HIP stream a library call runs on so that it is ordered with torch's work on ``ordinal``: torch's current stream.  The
+    default stream has no handle a builder could adopt (NULL means the builder's own, which does not wait for it), so there
+    the call runs on a side stream that waits for the default stream first and that the default stream waits for afterwards
+    -- on the device; the host waits for nothing."""
+
+    def __init__(self, torch, ordinal):
+        self.current = torch.cuda.current_stream(ordinal)
+        self.side = None
+        if not self.current.cuda_stream:
+            self.side = torch.cuda.Stream(device=ordinal)
+            self.side.wait_stream(self.current)
+        self.ptr = (self.side or self.current).cuda_stream
+
+    def done(self):
+        if self.side is not None:
+            self.current.wait_stream(self.side)
+
+
+class _DeviceInput:
+    """The device side of one single-GPU build (``_build_graph``): the caller's tensor in, the finished graph out as tensors."""
+
+    def __init__(self, tensor, dtype, ordinal, k):
+        self.torch = _torch()
+        self.tensor, self.dtype, self.ordinal, self.k = tensor, dtype, ordinal, int(k)
+        self.rows = tensor  # what the index keeps: the caller's own tensor, or dot's normalised float32 rows
+
+    def host_rows(self):
+        """The caller's rows on the host, float32: for sklearn's wording of the NaN / inf error, the one place that needs them."""
+        return np.ascontiguousarray(self.tensor.detach().float().cpu().numpy())
+
+    def set_data(self, builder, m):
+        torch, t = self.torch, self.tensor
+        self.stream = _OnTorchStream(torch, self.ordinal)
+        builder.set_stream(self.stream.ptr)
+        if m.normalize:  # pynndescent_.py:1101-1102: the index holds the normalised rows; the builder borrows them
+            self.rows = torch.empty(tuple(t.shape), dtype=torch.float32, device=t.device)
+            _capi.device_rows_f32(self.ordinal, self.stream.ptr, t.data_ptr(), self.dtype, t.shape[0], t.shape[1], True,
+                                  self.rows.data_ptr())
+            builder.set_data_device(self.rows.data_ptr(), keepalive=self.rows)
+        else:
+            builder.set_data_device_typed(t.data_ptr(), self.dtype, keepalive=t)
+
+    def finalize(self, builder):
+        torch, n = self.torch, self.tensor.shape[0]
+        idx = torch.empty((n, self.k), dtype=torch.int32, device=self.tensor.device)
+        dist = torch.empty((n, self.k), dtype=torch.float32, device=self.tensor.device)
+        builder.finalize_device(idx.data_ptr(), dist.data_ptr())
+        return idx, dist
+
+    def close(self):
+        if getattr(self, "stream", None) is not None:
+            self.stream.done()
+            self.stream = None
+
+
+def _device_corrected(torch, dist, m, ordinal):
+    """``m.correction`` of the float32 tensor ``dist``, on the device by the library (a new tensor; float64 where the host's is)."""
+    kind = m.device_kind
+    out = torch.empty_like(dist, dtype=torch.float32 if kind in (_capi.NND_CORRECT_COPY, _capi.NND_CORRECT_SQRT) else torch.float64)
+    _capi.device_correct(ordinal, torch.cuda.current_stream(ordinal).cuda_stream, kind, dist.data_ptr(), out.data_ptr(), dist.numel())
+    return out
+
+
 class _DeviceForestSentinel:
     """Stands in for ``_rp_forest``: downstream reference code only null-checks it
     (pynndescent_.py:1353) -- the build consumes nothing but the leaf array."""
@@ -221,7 +325,25 @@ class NNDescent:
         many GPUs of this node (``nnd_build_multi``: one host thread per GPU inside the library, RCCL over xGMI; the
         reference's analogue is ``n_jobs``, pynndescent_.py:1141-1143); ``devices`` lists their ordinals (default
         0..n_devices-1; a list that repeats an ordinal puts several ranks on one GPU).  Everything after the build
-        (``prepare``, ``query``, ``update``) runs on ``device``."""
+        (``prepare``, ``query``, ``update``) runs on ``device``.
+
+        ``data`` may be a device array -- a 2-D ``torch.Tensor`` on a HIP device, float32 / float16 / bfloat16 / float64 (half
+        precision and float64 are converted to float32 on the device; a float32 tensor is kept by reference, not copied).
+        The index then runs on the tensor's device and on torch's current stream: data queued on that stream needs no
+        synchronisation, and ``neighbor_graph`` / ``query(device array)`` return tensors there, corrected on the device.
+        ``_raw_data`` and ``_neighbor_graph`` are host mirrors fetched on first use; ``prepare``, ``update``, ``recall``,
+        ``build_search_graph``, pickling and ``to_reference`` work through them.  Out of scope: ``exact_knn`` / ``recall`` without
+        the host mirror; device ``init_graph`` / ``init_dist`` (converted with ``.cpu().numpy()``); a ``prepare()`` that stays off
+        the host; producers other than torch (``__cuda_array_interface__``, DLPack); and a sharded build from device memory --
+        with ``n_devices`` > 1 the rows are brought to the host first and the index is a host index, as for host input."""
+        dev_checked = None
+        if _is_device_array(data):  # dtype, shape and device first: before any device work, and before the shape is read
+            dev_checked = _check_device_array(data, device)
+            data, device = dev_checked[0], dev_checked[2]
+        if _is_device_array(init_graph):  # (out of scope on the device: they seed the build from the host)
+            init_graph = init_graph.detach().cpu().numpy()
+        if _is_device_array(init_dist):
+            init_dist = init_dist.detach().cpu().numpy()
         n_trees, n_iters, eff_leaf_size, eff_max_candidates = _reference_defaults(
             data.shape[0], n_neighbors, n_trees, n_iters, leaf_size, max_candidates)
 
@@ -274,12 +396,21 @@ class NNDescent:
         # lets sklearn produce the reference's own error
         # pynndescent_.py:1041-1046: a float32 C-contiguous input is the caller's own array after check_array -- normalised
         # into a copy; any other input has been copied by check_array already and is normalised in place
+        dev_in = None
+        if dev_checked is not None:
+            _, dtype_code, ordinal = dev_checked
+            if self.n_devices > 1:  # the sharded build takes its rows from the host, as for host input
+                data = np.ascontiguousarray(data.detach().float().cpu().numpy())
+            else:
+                dev_in = _DeviceInput(data, dtype_code, ordinal, n_neighbors)
         copy_on_normalize = getattr(data, "dtype", None) == np.float32 and bool(getattr(getattr(data, "flags", None), "c_contiguous", False))
-        data = _check_array_no_scan(data)
+        if dev_in is None:
+            data = _check_array_no_scan(data)
         self.tree_init = not (not tree_init or n_trees == 0 or init_graph is not None)  # pynndescent_.py:1059-1062
         self._dist_args = tuple((metric_kwds or {}).values())
-        current_random_state = self._set_up(data, m, random_state, copy_on_normalize)
-        data = self._raw_data
+        current_random_state = self._set_up(None if dev_in is not None else data, m, random_state, copy_on_normalize)
+        if dev_in is None:
+            data = self._raw_data
 
         n = data.shape[0]
         if self.tree_init:
@@ -302,15 +433,23 @@ class NNDescent:
             n_leaves = self._build_multi(data, eff_trees, eff_leaf_size, eff_max_candidates, tree_states[0], verbose,
                                          init_graph=init_graph, init_dist=init_dist)
         else:
-            self._neighbor_graph, self._build_stats, n_leaves = _build_graph(
+            graph, self._build_stats, n_leaves = _build_graph(
                 data, m, n_neighbors, eff_trees, eff_leaf_size, max_rptree_depth, eff_max_candidates, n_iters, delta,
                 self.rng_state, tree_states[0], device, forest=self.tree_init, init_graph=init_graph, init_dist=init_dist,
-                random_fill=init_graph is None, check_finite=True, verbose=verbose, announce=verbose)
+                random_fill=init_graph is None, check_finite=True, verbose=verbose, announce=verbose, dev_in=dev_in)
+            if dev_in is None:
+                self._neighbor_graph = graph
+            else:  # the graph and the rows stay on the device; _neighbor_graph / _raw_data are fetched when first read
+                self._device_graph, self._device_data = graph, dev_in.rows
         self._rp_forest = _DeviceForestSentinel(n_trees, n_leaves, eff_leaf_size) if self.tree_init else None
 
         # pynndescent_.py:1262-1267 `np.any(indices < 0)`: rows are ascending with the unfilled entries (-1, +inf) at the
-        # tail, so the last column tells (1 M strided reads instead of a 15 M-element temporary)
-        if self._neighbor_graph[0][:, -1].min() < 0:
+        # tail, so the last column tells (1 M strided reads instead of a 15 M-element temporary; on the device: one scalar back)
+        if dev_in is not None:
+            unfilled = bool((self._device_graph[0][:, -1].min() < 0).item())
+        else:
+            unfilled = self._neighbor_graph[0][:, -1].min() < 0
+        if unfilled:
             warn(
                 "Failed to correctly find n_neighbors for some samples."
                 " Results may be less than ideal. Try re-running with"
@@ -319,14 +458,15 @@ class NNDescent:
 
     def _set_up(self, data, m, random_state, copy):
         """What the constructor and ``from_graph`` share (pynndescent_.py:1064-1113): the data the index holds (dot: rows
-        L2-normalised, into a new array when ``copy``), the metric's correction and tree flags, and ``rng_state`` /
+        L2-normalised, into a new array when ``copy``; ``data`` None: the rows are on the device), the metric's correction and tree flags, and ``rng_state`` /
         ``search_rng_state`` drawn in the reference's order.  Returns the RandomState, whose next draws are the trees'."""
-        if m.normalize:  # pynndescent_.py:1101-1102
+        if data is not None and m.normalize:  # pynndescent_.py:1101-1102
             from sklearn.preprocessing import normalize
 
             data = normalize(data, norm="l2", copy=copy)
         self._input_dtype = np.float32
-        self._raw_data = data
+        if data is not None:  # (None: a device array -- _raw_data is its host mirror, fetched by __getattr__)
+            self._raw_data = data
         self.random_state = random_state
         current_random_state = check_random_state(random_state)
         self._distance_correction = m.correction
@@ -374,7 +514,31 @@ class NNDescent:
         if self.compressed and not hasattr(self, "_neighbor_graph"):
             warn("Compressed indexes do not have neighbor graph information.")
             return None
+        if "_device_graph" in self.__dict__:  # built from a device array: fresh tensors there, corrected by the library
+            torch = _torch()
+            idx, dist = self._device_graph
+            with torch.cuda.device(self.device):
+                return idx.clone(), _device_corrected(torch, dist, _METRICS[self.metric], self.device)
         return (_capi.host_copy(self._neighbor_graph[0]), self._distance_correction(self._neighbor_graph[1]))
+
+    def __getattr__(self, name):
+        """The host mirrors of an index built from a device array, fetched on first access and cached: ``_raw_data`` (float32
+        numpy rows; dot: the normalised rows the device computed) and ``_neighbor_graph`` (numpy int32 / float32).  Every line
+        that reads the two names finds them as on a host-built index, and ``hasattr`` keeps its meaning."""
+        d = self.__dict__
+        if name == "_raw_data" and "_device_data" in d:
+            value = np.ascontiguousarray(d["_device_data"].detach().float().cpu().numpy())
+        elif name == "_neighbor_graph" and "_device_graph" in d:
+            value = tuple(np.ascontiguousarray(t.cpu().numpy()) for t in d["_device_graph"])
+        else:
+            raise AttributeError("%r object has no attribute %r" % (type(self).__name__, name))
+        d[name] = value
+        return value
+
+    def _drop_device_copies(self):
+        """After the host mirrors have become the truth (``update()``), or for a pickle: the device tensors go."""
+        for name in ("_device_graph", "_device_data"):
+            self.__dict__.pop(name, None)
 
     @staticmethod
     def _recall_rows(n, n_rows, random_state):
@@ -528,6 +692,7 @@ class NNDescent:
             if hasattr(self, "_rp_forest"):
                 del self._rp_forest
             del self._neighbor_graph
+            self.__dict__.pop("_device_graph", None)
 
     def prepare(self):
         """``NNDescent.prepare`` (pynndescent_.py:2174-2273): build everything a query needs.  quantization="uint8": the
@@ -558,7 +723,10 @@ class NNDescent:
 
     def query(self, query_data, k=10, epsilon=0.1, proxy_beam_size=4):
         """``NNDescent.query`` (pynndescent_.py:2275-2379) on the GPU: one wave per query (csrc/query.hip).
-        Returns (indices (n_queries, k) in the ORIGINAL numbering, true distances (n_queries, k))."""
+        Returns (indices (n_queries, k) in the ORIGINAL numbering, true distances (n_queries, k)).  A device array
+        ``query_data`` (float32 / float16 / bfloat16 / float64, on the index's device) is answered with device tensors: the
+        queries are converted, the ids mapped back and the distances corrected on the device, on torch's current stream;
+        the index may have been built from host or device data alike, and a host ``query_data`` returns numpy on both."""
         if k > 256:
             raise NotImplementedError("pynndescent_amd answers queries with k <= 256; use index.to_reference() for k = %d" % k)
         _check_quantization(self.quantization, self.metric)
@@ -569,6 +737,8 @@ class NNDescent:
         if (not hasattr(self, "_search_graph") or getattr(self, "_searcher", None) is None
                 or (self.quantization is not None and not self._searcher.has_codes)):
             self.prepare()
+        if _is_device_array(query_data):
+            return self._query_device(query_data, m, k, search_k, epsilon)
         query_data = np.asarray(query_data).astype(np.float32, order="C")  # pynndescent_.py:2316
         if query_data.ndim != 2 or query_data.shape[1] != self._raw_data.shape[1]:
             raise ValueError("query_data must have shape (n_queries, %d)" % self._raw_data.shape[1])
@@ -585,12 +755,54 @@ class NNDescent:
             dists = self._distance_correction(dists)
         return indices, dists
 
+    def _query_device(self, q, m, k, search_k, epsilon):
+        """``query`` for a device array: the three forms on the device-pointer entries of the searcher."""
+        torch = _torch()
+        q, dtype, ordinal = _check_device_array(q, what="query_data")
+        if ordinal != int(self.device):
+            raise ValueError("query_data is on device %d, the index on device %d" % (ordinal, int(self.device)))
+        nq, dim = int(q.shape[0]), int(self._raw_data.shape[1])
+        if q.shape[1] != dim:
+            raise ValueError("query_data must have shape (n_queries, %d)" % dim)
+        with torch.cuda.device(ordinal):
+            stream = torch.cuda.current_stream(ordinal).cuda_stream
+            if dtype != _capi.NND_DTYPE_FLOAT32:  # pynndescent_.py:2316
+                q32 = torch.empty((nq, dim), dtype=torch.float32, device=q.device)
+                _capi.device_rows_f32(ordinal, stream, q.data_ptr(), dtype, nq, dim, False, q32.data_ptr())
+                q = q32
+            if m.nonnegative and nq and bool((q.min() < 0).item()):
+                raise ValueError(_NEGATIVE_HELLINGER)
+            indices = torch.empty((nq, k), dtype=torch.int32, device=q.device)
+            dists = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+            if self.quantization is not None:
+                form, eps = "proxy", epsilon + 1e-32
+            elif m.proxy:
+                form, eps = "rerank", epsilon
+            else:
+                form, eps = "float", epsilon
+            if nq:
+                self._searcher.query_device(form, q.data_ptr(), nq, k, search_k, eps, indices.data_ptr(), dists.data_ptr(), stream)
+            order = getattr(self._searcher, "vertex_order_device", None)  # lives and dies with the searcher
+            if order is None:
+                order = torch.from_numpy(np.ascontiguousarray(self._vertex_order, dtype=np.int32)).to(q.device)
+                self._searcher.vertex_order_device = order
+            found = indices >= 0
+            indices = torch.where(found, order[indices.clamp(min=0).long()], torch.full_like(indices, -1))  # pynndescent_.py:2373
+            if self._distance_correction is not None and m.device_kind != _capi.NND_CORRECT_COPY:  # pynndescent_.py:2375-2376
+                dists = _device_corrected(torch, dists, m, ordinal)
+        return indices, dists
+
     # ------------------------------------------------------------------------------------------------ pickling
     def __getstate__(self):
         """pynndescent_.py:1306-1320: a pickled index is a PREPARED index; device handles and the build forest stay behind."""
         if not hasattr(self, "_search_graph"):
             self._init_search_graph()
+        if "_device_data" in self.__dict__ or "_device_graph" in self.__dict__:  # the host mirrors travel, the tensors stay
+            self._raw_data
+            hasattr(self, "_neighbor_graph")
         state = self.__dict__.copy()
+        state.pop("_device_graph", None)
+        state.pop("_device_data", None)
         state.pop("_rp_forest", None)
         state.pop("_searcher", None)
         state["_search_forest"] = tuple(tuple(t) for t in self._search_forest)  # rp_trees.py:3060-3069 denumbaify_tree
@@ -648,6 +860,7 @@ class NNDescent:
         n_old = raw.shape[0]
         raw = np.ascontiguousarray(np.vstack([raw, xs_fresh]))
         ns, ds = (np.array(a, copy=True) for a in self._neighbor_graph)
+        self._drop_device_copies()  # (an index built from a device array: from here on its host arrays are the index)
         if updated_indices:
             hit = np.zeros(n_old, bool)
             hit[updated_indices] = True
@@ -798,19 +1011,23 @@ def exact_knn(data, queries=None, k=10, metric="euclidean", rows=None, device=0,
 
 def _build_graph(data, m, n_neighbors, n_trees, leaf_size, max_depth, max_candidates, n_iters, delta, rng_state, tree_rng,
                  device, forest=False, leaf_array=None, init_graph=None, init_dist=None, old_graph=None, random_fill=False,
-                 check_finite=False, stats=True, verbose=False, announce=False):
+                 check_finite=False, stats=True, verbose=False, announce=False, dev_in=None):
     """Every single-GPU build (``_capi.Builder``): the data in, its flags read (the NaN / inf one only when
     ``check_finite``), ``forest`` built on the device, the graph seeded -- ``old_graph`` (ids, distances) as "old" edges,
     then ``init_graph`` / ``init_dist``, the caller's ``leaf_array`` or the forest's leaves, then the random fill when
-    ``random_fill`` -- NN-descent to the stop rule, the graph out.  ``announce``: the constructor's verbose line.  Returns
+    ``random_fill`` -- NN-descent to the stop rule, the graph out.  ``announce``: the constructor's verbose line.  ``dev_in``
+    (a ``_DeviceInput``): the rows are a device array, read in place on torch's stream, and the graph comes out as tensors.  Returns
     ``((indices, distances), the stats (when ``stats``), the forest's leaf count)``."""
     n = data.shape[0]
     builder = _capi.Builder(n, data.shape[1], m.code, n_neighbors, n_trees, leaf_size, max_depth, max_candidates, n_iters,
                             delta, rng_state, tree_rng, device=device)
     try:
-        builder.set_data_host(data)
+        if dev_in is None:
+            builder.set_data_host(data)
+        else:
+            dev_in.set_data(builder, m)
         if check_finite:
-            _raise_if_nonfinite(builder, data)
+            _raise_if_nonfinite(builder, data if dev_in is None else dev_in.host_rows)
         if m.nonnegative and builder.data_negative():
             raise ValueError(_NEGATIVE_HELLINGER)
         n_leaves = None
@@ -831,10 +1048,12 @@ def _build_graph(data, m, n_neighbors, n_trees, leaf_size, max_depth, max_candid
         if random_fill:
             builder.init_random()
         _descend(builder, n, n_neighbors, n_iters, delta, verbose)
-        graph = builder.finalize()
+        graph = builder.finalize() if dev_in is None else dev_in.finalize(builder)
         return graph, builder.stats() if stats else None, n_leaves
     finally:
         builder.close()
+        if dev_in is not None:
+            dev_in.close()
 
 
 def _descend(builder, n, n_neighbors, n_iters, delta, verbose):
@@ -863,6 +1082,8 @@ def _raise_if_nonfinite(builder, data):
     if builder.data_nonfinite():
         from sklearn.utils import assert_all_finite
 
+        if callable(data):  # a device array: only this error path brings the rows to the host, for sklearn's wording
+            data = data()
         assert_all_finite(data)  # raises "Input contains NaN." / "... infinity or a value too large ..."
         raise ValueError("Input contains NaN or infinity.")  # (unreachable unless the two scans disagree)
 
