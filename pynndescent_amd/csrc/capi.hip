@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "common.h"
+#include "metric.h"
 #include "state.h"
 
 static thread_local char g_err[512] = {0};

@@ -10,7 +10,6 @@
 #define NND_IDX_MASK 0x7FFFFFFFu
 #define NND_EMPTY_KEY 0xFFFFFFFFFFFFFFFFull
 #define NND_EMPTY_SLOT 0xFFFFFFFFu  // an unarmed reverse-offer slot (sample.hip)
-#define NND_FLT_MAX 3.402823466e+38f
 // rows of more than 64 neighbours (n_neighbors up to NND_WIDE_K): a lane holds entries lane, 64 + lane, ...; merged through LDS (merge.h)
 #define NND_WIDE_K 256
 #define NND_WIDE_U (NND_WIDE_K / 64)
@@ -57,11 +56,6 @@ __device__ __forceinline__ int nnd_wave_sum_i32(int v) {
     return v;
 }
 __device__ __forceinline__ float nnd_wave_sum_f32(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ double nnd_wave_sum_f64(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
@@ -164,79 +158,6 @@ __device__ __forceinline__ uint16_t nnd_f32_to_h16(float v, float scale) {
 __device__ __forceinline__ float nnd_h16_to_f32(uint16_t b, float inv_scale) { return (float)__builtin_bit_cast(_Float16, b) * inv_scale; }
 
 __device__ __forceinline__ float nnd_clamp_dist(float d) { return d > 0.0f ? d : 0.0f; }
-
-// Metric codes (include/pynnd_amd.h NND_METRIC_*): 0 sqeuclidean, 1 alt cosine, 2 alt dot, 3 alt inner product,
-// 4 correlation, 5 alt hellinger, 6 proxy inner product.  The prep kernel turns every row into a "prepared" row whose inner products give the
-// distance (DESIGN.md "Metrics"):
-//   unit metrics (1, 2, 4, 5): rows L2-normalised after a per-metric transform (none / none / minus the row mean / sqrt);
-//     nrm = 1 (non-zero row) or 0 (zero row); the trees split angularly;
-//   norm metrics (0, 3, 6): rows centred on the column mean (0) or as given (3, 6); nrm = |x|^2; euclidean trees.
-__host__ __device__ __forceinline__ bool nnd_metric_unit(int metric) { return metric == 1 || metric == 2 || metric == 4 || metric == 5; }
-
-// Gram value -> alt-space distance.  Every value is >= 0: the k-lists order distances by their float bits.
-//   euclid:  |a|^2 + |b|^2 - 2<a,b>          (reference distances.py:63-91 in Gram form)
-//   cosine / hellinger: rows are pre-normalised, na/nb are 1 (non-zero row) or 0 (zero row):
-//            0 if both zero, FLT_MAX if one zero or <a,b> <= 0, else -log2(<a,b>) (distances.py:583-630, 1387-1417)
-//   dot:     FLT_MAX if either row is zero (both zero too) or <a,b> <= 0, else -log2(<a,b>) (distances.py:680-702)
-//   inner product: FLT_MAX if <a,b> <= 0, else 1 / <a,b> (distances.py:759-790)
-//   correlation: rows centred and normalised: 0 if both zero, else 1 - <a,b> clamped >= 0 (distances.py:1284-1313)
-//   proxy inner product: rows as given, na/nb = |a|^2, |b|^2: FLT_MAX if either row is zero or <a,b> <= 0, else
-//            max(-log2(<a,b> / sqrt(|a|^2 |b|^2)), 0) + 1 / sqrt(<a,b>) (distances.py:810-838; <a,b> = 0 is +inf there:
-//            DESIGN.md "Proxy distances")
-// Three transcendental instructions (two v_rsq_f32, one v_log_f32, 1 ulp each) instead of IEEE sqrt / divide sequences: the
-// conversion sits in the unrolled epilogues of the Gram kernels, where every instruction is paid per accumulator register.
-// The cosine is g * rsq(na) * rsq(nb) (no product of the norms: it cannot overflow where the cosine is finite).
-__device__ __forceinline__ float nnd_proxy_ip_dist(float g, float na, float nb) {
-    if (na == 0.0f || nb == 0.0f || !(g > 0.0f)) return NND_FLT_MAX;
-    const float cosv = g * __frsqrt_rn(na) * __frsqrt_rn(nb);
-    return fminf(nnd_clamp_dist(-__log2f(cosv)) + __frsqrt_rn(g), NND_FLT_MAX);
-}
-// PX = false: the codes 0..5 only -- the conversion as it was before code 6 existed, for the kernels that never see that
-// code (the query kernel's plain float walk, the joins' XM = 1 instances and the exact search: code 6 has instances of its
-// own in the first two and is refused by the third)
-template <bool PX>
-__device__ __forceinline__ float nnd_gram_to_dist_x(int metric, float g, float na, float nb) {
-    if (metric == 0) return nnd_clamp_dist(na + nb - 2.0f * g);
-    if (metric == 3) return g > 0.0f ? fminf(1.0f / g, NND_FLT_MAX) : NND_FLT_MAX;
-    if constexpr (PX)
-        if (metric == 6) return nnd_proxy_ip_dist(g, na, nb);
-    if (na == 0.0f && nb == 0.0f && metric != 2) return 0.0f;
-    if (metric == 4) return nnd_clamp_dist(1.0f - g);
-    if (na == 0.0f || nb == 0.0f || g <= 0.0f) return NND_FLT_MAX;
-    return nnd_clamp_dist(-__log2f(g));
-}
-__device__ __forceinline__ float nnd_gram_to_dist(int metric, float g, float na, float nb) { return nnd_gram_to_dist_x<true>(metric, g, na, nb); }
-// d(x, x) of a row with prepared norm value n (nrm): the join kernels set the self pair by this rule instead of the Gram
-// value.  The reference does evaluate the pair (utils.py:619 starts the inner loop at j): 0 for every metric whose
-// distance to itself is 0, FLT_MAX for a zero row under dot, 1 / |x|^2 under inner product, 1 / |x| under its proxy.
-template <bool PX>
-__device__ __forceinline__ float nnd_self_dist_x(int metric, float n) {
-    if (metric == 3) return n > 0.0f ? fminf(1.0f / n, NND_FLT_MAX) : NND_FLT_MAX;
-    if constexpr (PX)
-        if (metric == 6) return n > 0.0f ? fminf(__frsqrt_rn(n), NND_FLT_MAX) : NND_FLT_MAX;
-    if (metric == 2 && n == 0.0f) return NND_FLT_MAX;
-    return 0.0f;
-}
-__device__ __forceinline__ float nnd_self_dist(int metric, float n) { return nnd_self_dist_x<true>(metric, n); }
-
-// The same with the metric family fixed at compile time.  XM = 0: sqeuclidean / cosine only (the conversion of the kernels
-// before the other metrics existed, instruction for instruction); XM = 1: the codes 0..5, by a branch on the metric (the
-// conversion before code 6 existed: a bool converts to 0 / 1); XM = 2: code 6 alone, no branch.
-template <int XM>
-__device__ __forceinline__ float nnd_gram_to_dist_t(int metric, float g, float na, float nb) {
-    if constexpr (XM == 2) return nnd_proxy_ip_dist(g, na, nb);
-    if constexpr (XM == 1) return nnd_gram_to_dist_x<false>(metric, g, na, nb);
-    if (metric == 0) return nnd_clamp_dist(na + nb - 2.0f * g);
-    if (na == 0.0f && nb == 0.0f) return 0.0f;
-    if (na == 0.0f || nb == 0.0f || g <= 0.0f) return NND_FLT_MAX;
-    return nnd_clamp_dist(-__log2f(g));
-}
-template <int XM>
-__device__ __forceinline__ float nnd_self_dist_t(int metric, float n) {
-    if constexpr (XM == 2) return nnd_self_dist_x<true>(6, n);
-    if constexpr (XM == 1) return nnd_self_dist_x<false>(metric, n);
-    return 0.0f;
-}
 
 // Swizzled LDS addressing for row tiles read as MFMA operands.
 // A tile row holds DC floats = DC/4 16-byte chunks.  Chunk c of row r is stored at chunk position

@@ -2,18 +2,19 @@
 //
 // Two tiers, and a certificate that decides per row which one answers (DESIGN.md "Exact search"):
 //   k_exact_scan    streams the whole prepared point set past blocks of 64 query rows: f32 MFMA Gram tiles (gram.h), the
-//                   alt-space distance of every pair (nnd_gram_to_dist_t), the W >= k smallest kept per row by the leaf kernel's
+//                   alt-space distance of every pair (metric.h nnd_gram_to_dist), the W >= k smallest kept per row by the leaf kernel's
 //                   pattern (screen against the row's W-th distance, ballot + compact into an LDS queue, rank merge of a full
 //                   queue, merge.h).  It also keeps T, the smallest distance it did NOT keep.
 //   k_exact_merge   folds the partial lists when the point set was split over gridDim.y slices.
-//   k_exact_refine  recomputes the W candidates' distances from the ORIGINAL rows with float64 accumulation (the formulas of
-//                   finalize.hip), sorts by (float64 distance, id), keeps k -- and certifies the row iff the k-th exact distance
+//   k_exact_refine  recomputes the W candidates' distances from the ORIGINAL rows with float64 accumulation (metric.h
+//                   nnd_ref_acc / nnd_ref_dist, every term in float64), sorts by (float64 distance, id), keeps k -- and certifies the row iff the k-th exact distance
 //                   lies below T by more than the rounding-error band of the scan (exact_band.h): then nothing that was left
 //                   out can belong to the top k.
 //   k_exact_f64     the definition: all n original rows in float64, for exactly the rows that were not certified.
 // An f32 Gram ranking alone is NOT exact: on two far modes of tight points (|x| ~ 1e3, spread 1e-2) it misses a true neighbour
 // in every row however many candidates are refined; there the band exceeds every gap and the float64 tier answers.
 #include "common.h"
+#include "metric.h"
 #include "state.h"
 #include "gram.h"
 #include "merge.h"
@@ -78,12 +79,13 @@ __device__ __forceinline__ void ex_merge_into(uint64_t *scr, uint32_t *__restric
 // 16 w .. 16 w + 15: lane l holds, per accumulator tile J, the Gram values of rows 4 (l >> 4) + r, r = 0..3, and column
 // 16 J + (l & 15) -- so the threshold th[r], the reject minimum rej[r] and the queue fill fill[r] of those four rows live in
 // registers, the same in all 16 lanes of a group.  DC: floats of a row staged per K chunk (dp <= DC: the query rows are staged
-// once); XM: the metric family (common.h); WIDE: W > 64 (rows merged through LDS).
+// once); XM: the codes 2..5 (metric.h NND_CODES_0_5; code 6 is refused by the host), else 0 / 1; WIDE: W > 64 (rows merged through LDS).
 template <int DC, bool XM, bool WIDE>
 __global__ __launch_bounds__(256) void k_exact_scan(const float *__restrict__ xp, const float *__restrict__ nrm, int64_t n, int dp, int metric,
                                                     const float *__restrict__ qx, const float *__restrict__ qnrm, const int32_t *__restrict__ qids,
                                                     int self, int nq, int nq_pad, int W, int64_t rows_per_slice, uint32_t *__restrict__ list_e,
                                                     float *__restrict__ list_d, float *__restrict__ list_th, float *__restrict__ list_rej) {
+    constexpr int FAM = XM ? NND_CODES_0_5 : NND_CODES_01;
     extern __shared__ __align__(16) unsigned char ex_smem[];
     float *Xs = (float *)ex_smem;                              // (EX_QB + EX_TB) rows of DC floats, swizzled: queries, then the data tile
     float *snrm = Xs + (EX_QB + EX_TB) * DC;                   // (EX_TB) nrm of the data tile
@@ -178,8 +180,8 @@ __global__ __launch_bounds__(256) void k_exact_scan(const float *__restrict__ xp
             const float nb = snrm[col];
 #pragma unroll
             for (int r = 0; r < 4; r++) {
-                float val = nnd_gram_to_dist_t<XM>(metric, a[r], na[r], nb);
-                if ((int64_t)sid[r] == cid) val = nnd_self_dist_t<XM>(metric, na[r]);
+                float val = nnd_gram_to_dist<FAM>(metric, a[r], na[r], nb);
+                if ((int64_t)sid[r] == cid) val = nnd_self_dist<FAM>(metric, na[r]);
                 const bool ok = cv && qok[r] && val < th[r];
                 if (cv && !ok) rej[r] = fminf(rej[r], val);
                 const uint32_t m16 = (uint32_t)(__ballot(ok) >> (16 * g)) & 0xFFFFu;
@@ -226,83 +228,28 @@ __global__ __launch_bounds__(256) void k_exact_merge(int nq, int nq_pad, int W, 
     if (lane == 0) list_rej[q] = t;
 }
 
-// ---- float64 distances of the original rows, the reference's formulas (as finalize.hip computes them, hellinger's terms apart) ----
+// ---- float64 distances of the original rows: the reference's formulas of metric.h, hellinger's terms in float64 too ----
 struct ex_val {
     double r;   // alt-space distance, not yet rounded to float32 (FLT_MAX for the reference's "no similarity" cases)
     double g;   // the value the scan's Gram value approximates (codes 1, 5: cosine / coefficient; 2, 3: <a, b>), -inf if none
     double ax;  // codes 1..5: the query row's squared norm term
 };
-__device__ __forceinline__ double ex_group16_sum(double v) {
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ double ex_row_mean(const float *xr, int d, int l16) {
-    double m = 0.0;
-    for (int t = l16; t < d; t += 16) m += (double)xr[t];
-    return ex_group16_sum(m) / (double)d;
-}
 // the 16 lanes of a group on one pair; mua: the query row's mean (correlation)
 template <bool XM>
 __device__ __forceinline__ ex_val ex_pair_f64(int metric, const float *__restrict__ xa, const float *__restrict__ xb, int d, int l16, double mua) {
-    double s = 0.0, dot = 0.0, nx = 0.0, ny = 0.0;
-    if constexpr (XM) {
-        const double mub = metric == 4 ? ex_row_mean(xb, d, l16) : 0.0;
-        for (int t = l16; t < d; t += 16) {
-            const double a = (double)xa[t] - mua, b = (double)xb[t] - mub;
-            if (metric == 5) {  // alternative_hellinger: sum sqrt(x_i y_i), |x|_1, |y|_1 -- every term in float64 (finalize.hip keeps the
-                                // reference's float32 sqrtf terms: 1e-7 of a distance, enough to swap two near neighbours)
-                dot += sqrt(a * b);
-                nx += a;
-                ny += b;
-            } else {
-                dot += a * b;
-                nx += a * a;
-                ny += b * b;
-            }
-        }
-    } else {
-        for (int t = l16; t < d; t += 16) {
-            const double a = xa[t], b = xb[t];
-            if (metric == 0) s += (a - b) * (a - b);
-            else {
-                dot += a * b;
-                nx += a * a;
-                ny += b * b;
-            }
-        }
-    }
+    constexpr int FAM = XM ? NND_CODES_0_5 : NND_CODES_01;
+    double dot = 0.0, nx = 0.0, ny = 0.0;
+    const double ma = XM ? mua : 0.0, mb = XM && metric == 4 ? nnd_row_mean_f64<16>(xb, d, l16) : 0.0;
+    for (int t = l16; t < d; t += 16) nnd_ref_acc<FAM, NND_HELLINGER_F64>(metric, (double)xa[t] - ma, (double)xb[t] - mb, dot, nx, ny);
+    const double dt = nnd_group_sum_f64<16>(dot);
+    const double ax = metric == 0 ? 0.0 : nnd_group_sum_f64<16>(nx), ay = metric == 0 ? 0.0 : nnd_group_sum_f64<16>(ny);  // (code 0: dt is all)
     ex_val v;
+    v.r = nnd_ref_dist<NND_CODES_0_5>(metric, dt, ax, ay);  // (both instances carry the whole conversion: XM splits the loop above only)
     v.g = -INFINITY;
-    if (metric == 0) {
-        v.r = ex_group16_sum(s);
-        v.ax = 0.0;
-        return v;
-    }
-    const double dt = ex_group16_sum(dot), ax = ex_group16_sum(nx), ay = ex_group16_sum(ny);
     v.ax = ax;
-    if (metric == 2 || metric == 3) {  // alternative_dot / alternative_inner_product: FLT_MAX for <x,y> <= 0
-        if (!(dt > 0.0)) { v.r = (double)NND_FLT_MAX; return v; }
-        const double r = metric == 2 ? -log2(dt) : 1.0 / dt;
-        v.r = r > 0.0 ? fmin(r, (double)NND_FLT_MAX) : 0.0;
-        v.g = dt;
-        return v;
-    }
-    if (metric == 4) {  // correlation: 0 if both rows have zero variance, 1 if <x,y> = 0
-        if (ax == 0.0 && ay == 0.0) v.r = 0.0;
-        else if (dt == 0.0) v.r = 1.0;
-        else {
-            const double r = 1.0 - dt / sqrt(ax * ay);
-            v.r = r > 0.0 ? r : 0.0;
-        }
-        return v;
-    }
-    // alternative_cosine / alternative_hellinger
-    if (ax == 0.0 && ay == 0.0) v.r = 0.0;
-    else if (ax == 0.0 || ay == 0.0 || dt <= 0.0) v.r = (double)NND_FLT_MAX;
-    else {
-        const double r = log2(sqrt(ax * ay) / dt);
-        v.r = r > 0.0 ? r : 0.0;
+    if (metric == 2 || metric == 3) {
+        if (dt > 0.0) v.g = dt;
+    } else if (metric != 4 && ax != 0.0 && ay != 0.0 && !(dt <= 0.0)) {  // cosine / hellinger: nnd_ref_dist's finite case
         v.g = dt / sqrt(ax * ay);
     }
     return v;
@@ -340,7 +287,7 @@ __global__ __launch_bounds__(256) void k_exact_refine(const float *__restrict__ 
     nnd_wave_lds_sync();
     const int qid = qids[q];
     const float *xa = qraw + (int64_t)qid * d;  // (external queries: qid = q)
-    const double mua = metric == 4 ? ex_row_mean(xa, d, l16) : 0.0;
+    const double mua = metric == 4 ? nnd_row_mean_f64<16>(xa, d, l16) : 0.0;
     double axq = 0.0;
     for (int j0 = 0; j0 < W; j0 += 4) {
         const int j = j0 + grp;
@@ -390,7 +337,7 @@ __global__ __launch_bounds__(256) void k_exact_f64(const float *__restrict__ x, 
     const int lane = nnd_lane(), w = threadIdx.x >> 6, grp = lane >> 4, l16 = lane & 15;
     const int q = list[blockIdx.x];
     const float *xa = qraw + (int64_t)qids[q] * d;
-    const double mua = metric == 4 ? ex_row_mean(xa, d, l16) : 0.0;
+    const double mua = metric == 4 ? nnd_row_mean_f64<16>(xa, d, l16) : 0.0;
     int cnt = 0;
     double worst = INFINITY;
     for (int64_t b0 = 4 * w; b0 < n; b0 += 16) {
@@ -462,7 +409,7 @@ __global__ __launch_bounds__(256) void k_exact_nmax(const float *__restrict__ x,
         double v = 0.0;
         if (metric == 2) {
             for (int t = l16; t < d; t += 16) v += (double)x[row * d + t] * (double)x[row * d + t];
-            v = ex_group16_sum(v);
+            v = nnd_group_sum_f64<16>(v);
         } else {
             v = (double)nrm[row];
         }

@@ -12,7 +12,7 @@
 //         Rows wider than the LDS tile are contracted chunk after chunk into the same accumulators: t simply runs on.
 //         (The bounds below hold for ANY order of the chain; the order is stated so that the emulation matches bit for bit.)
 //   nrm = prep.hip's norm word: sum of squares of the prepared coordinates in f32 (codes 0, 3), 1 / 0 for the unit rows
-//   the distance by nnd_gram_to_dist (common.h)
+//   the distance by nnd_gram_to_dist (metric.h)
 // and what stands between a prepared coordinate and the original one: ONE f32 rounding for code 0 (raw - mean[j]), none for
 // code 3, and for the unit rows (codes 1, 2, 4, 5) the transform (none / none / minus the float64 row mean / sqrtf), the f32
 // sum of squares, 1 / sqrtf and one multiplication.

@@ -3,60 +3,23 @@
 // k_finalize replaces deheap_sort (reference utils.py:189-218): rows ascending by distance, empty
 // slots (-1, +inf) last.  The k-lists carry Gram-form f32 distances of centred / normalised rows
 // (good enough to RANK); the distances handed back are recomputed from the ORIGINAL rows in the
-// reference's own formulas (distances.py:63-91 squared difference sum; distances.py:583-630
-// log2(sqrt(|x|^2|y|^2)/<x,y>); dot -log2<x,y> :680 on the rows as given (NNDescent normalises them on the host);
-// inner product 1/<x,y> :759; its proxy :810; correlation :1284 with the row means first; hellinger :1387) with float64 accumulation,
-// then rows are re-sorted by that value.
+// reference's own formulas with float64 accumulation (metric.h nnd_ref_acc / nnd_ref_dist, hellinger's
+// terms in float32 as the reference's), then rows are re-sorted by that value.
 #include "common.h"
+#include "metric.h"
 #include "state.h"
 
-// sum over the 16 lanes of an aligned 16-lane group
-__device__ __forceinline__ double fin_group16_sum_f64(double v) {
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
+// one coordinate pair into the float64 sums, hellinger's terms as the reference takes them (metric.h)
+template <int FAM>
+__device__ __forceinline__ void fin_acc(int metric, double a, double b, double &dot, double &nx, double &ny) {
+    nnd_ref_acc<FAM, NND_HELLINGER_F32>(metric, a, b, dot, nx, ny);
 }
-
-// The metrics of codes 2..6 (include/pynnd_amd.h): one coordinate pair into the float64 accumulators (correlation: a and b
-// already centred), then the accumulated sums into the reference's distance.
-__device__ __forceinline__ void fin_acc_x(int metric, double a, double b, double &dot, double &nx, double &ny) {
-    if (metric == 5) {
-        dot += (double)sqrtf((float)a * (float)b);  // alternative_hellinger: sum sqrt(x_i y_i) (float32 terms, as the reference's), |x|_1, |y|_1
-        nx += a;
-        ny += b;
-    } else {
-        dot += a * b;
-        nx += a * a;
-        ny += b * b;
-    }
-}
-__device__ __forceinline__ float fin_value_x(int metric, double dt, double ax, double ay) {
-    if (metric == 2 || metric == 3) {  // alternative_dot / alternative_inner_product: FLT_MAX for <x,y> <= 0
-        if (!(dt > 0.0)) return NND_FLT_MAX;
-        const double r = metric == 2 ? -log2(dt) : 1.0 / dt;
-        return r > 0.0 ? (float)fmin(r, (double)NND_FLT_MAX) : 0.0f;
-    }
-    if (metric == 6) {  // proxy_inner_product: FLT_MAX for a zero row or <x,y> <= 0 (common.h nnd_proxy_ip_dist)
-        if (ax == 0.0 || ay == 0.0 || !(dt > 0.0)) return NND_FLT_MAX;
-        const double c = -log2(dt / sqrt(ax * ay));
-        return (float)fmin((c > 0.0 ? c : 0.0) + 1.0 / sqrt(dt), (double)NND_FLT_MAX);
-    }
-    if (metric == 4) {  // correlation: 0 if both rows have zero variance, 1 if <x,y> = 0
-        if (ax == 0.0 && ay == 0.0) return 0.0f;
-        if (dt == 0.0) return 1.0f;
-        const double r = 1.0 - dt / sqrt(ax * ay);
-        return r > 0.0 ? (float)r : 0.0f;
-    }
-    if (ax == 0.0 && ay == 0.0) return 0.0f;  // alternative_hellinger
-    if (ax == 0.0 || ay == 0.0 || dt <= 0.0) return NND_FLT_MAX;
-    const double r = log2(sqrt(ax * ay) / dt);
-    return r > 0.0 ? (float)r : 0.0f;
-}
-// correlation: the mean of row `xr` over the 16 lanes of a group (float64, as the reference's correlation)
-__device__ __forceinline__ double fin_row_mean(const float *xr, int d, int l16) {
-    double m = 0.0;
-    for (int t = l16; t < d; t += 16) m += (double)xr[t];
-    return fin_group16_sum_f64(m) / (double)d;
+// the 16 lanes' partial sums of one pair -> the distance handed back
+template <int FAM>
+__device__ __forceinline__ float fin_value(int metric, double dot, double nx, double ny) {
+    const double dt = nnd_group_sum_f64<16>(dot);
+    if (metric == 0) return (float)dt;
+    return (float)nnd_ref_dist<FAM>(metric, dt, nnd_group_sum_f64<16>(nx), nnd_group_sum_f64<16>(ny));
 }
 
 // One wave per row.  The 64 lanes work as 4 groups of 16: group g takes neighbours g, 4+g, 8+g, ... so four distances
@@ -64,7 +27,7 @@ __device__ __forceinline__ double fin_row_mean(const float *xr, int d, int l16) 
 // the rows are fetched one after another).
 // METRIC is a template parameter: the euclidean instance does not carry the cosine accumulators (146 -> far fewer
 // registers, i.e. more waves per SIMD for what is a gather-latency-bound kernel).  METRIC 2..6: the other metrics, one
-// instance each (fin_acc_x / fin_value_x).
+// instance each.
 template <int METRIC>
 __global__ __launch_bounds__(256, METRIC == 0 ? 6 : 4) void k_finalize(const float *__restrict__ x, int d, int64_t lo, int64_t n, int k, int ks,
                                                   const uint32_t *__restrict__ knn_e, const int32_t *__restrict__ order,
@@ -81,26 +44,26 @@ __global__ __launch_bounds__(256, METRIC == 0 ? 6 : 4) void k_finalize(const flo
     const float *xv = x + v * d;
     const int grp = lane >> 4, l16 = lane & 15;
     const bool vec = (d & 3) == 0;  // rows 16-byte aligned
-    constexpr int metric = METRIC;
+    constexpr int metric = METRIC, FAM = METRIC < 2 ? NND_CODES_01 : NND_CODES_ANY;
     float mine = INFINITY;
     const int nsteps = (k + 3) >> 2;
     for (int s0 = 0; s0 < nsteps; s0 += 4) {
         const float *xu[4];
         bool on[4];
-        double s[4], dot[4], nx[4], ny[4];
+        double dot[4], nx[4], ny[4];  // (sqeuclidean: the squared differences in dot)
 #pragma unroll
         for (int u = 0; u < 4; u++) {
             const int j = 4 * (s0 + u) + grp;
             const uint32_t ej = __shfl(e, j & 63, 64);
             on[u] = j < k && ej != NND_EMPTY_E;
             xu[u] = x + (int64_t)(on[u] ? (ej & NND_IDX_MASK) : 0) * d;
-            s[u] = dot[u] = nx[u] = ny[u] = 0.0;
+            dot[u] = nx[u] = ny[u] = 0.0;
         }
         double mua = 0.0, mub[4] = {0.0, 0.0, 0.0, 0.0};  // correlation: the row means
         if (metric == 4) {
-            mua = fin_row_mean(xv, d, l16);
+            mua = nnd_row_mean_f64<16>(xv, d, l16);
 #pragma unroll
-            for (int u = 0; u < 4; u++) mub[u] = fin_row_mean(xu[u], d, l16);
+            for (int u = 0; u < 4; u++) mub[u] = nnd_row_mean_f64<16>(xu[u], d, l16);
         }
         if (vec) {
             for (int t = 4 * l16; t < d; t += 64) {
@@ -112,17 +75,18 @@ __global__ __launch_bounds__(256, METRIC == 0 ? 6 : 4) void k_finalize(const flo
                 for (int u = 0; u < 4; u++) {
                     const double a0 = a.x, a1 = a.y, a2 = a.z, a3 = a.w;
                     const double b0 = q[u].x, b1 = q[u].y, b2 = q[u].z, b3 = q[u].w;
-                    if (metric == 0) {
-                        s[u] += (a0 - b0) * (a0 - b0) + (a1 - b1) * (a1 - b1) + (a2 - b2) * (a2 - b2) + (a3 - b3) * (a3 - b3);
+                    if (metric == 0) {  // codes 0 / 1: the four terms of a chunk are summed before they join the accumulator (the
+                                        // order every build since the first has summed in; nnd_ref_acc's terms, grouped)
+                        dot[u] += (a0 - b0) * (a0 - b0) + (a1 - b1) * (a1 - b1) + (a2 - b2) * (a2 - b2) + (a3 - b3) * (a3 - b3);
                     } else if (metric == 1) {
                         dot[u] += a0 * b0 + a1 * b1 + a2 * b2 + a3 * b3;
                         nx[u] += a0 * a0 + a1 * a1 + a2 * a2 + a3 * a3;
                         ny[u] += b0 * b0 + b1 * b1 + b2 * b2 + b3 * b3;
                     } else {
-                        fin_acc_x(metric, a0 - mua, b0 - mub[u], dot[u], nx[u], ny[u]);
-                        fin_acc_x(metric, a1 - mua, b1 - mub[u], dot[u], nx[u], ny[u]);
-                        fin_acc_x(metric, a2 - mua, b2 - mub[u], dot[u], nx[u], ny[u]);
-                        fin_acc_x(metric, a3 - mua, b3 - mub[u], dot[u], nx[u], ny[u]);
+                        fin_acc<FAM>(metric, a0 - mua, b0 - mub[u], dot[u], nx[u], ny[u]);
+                        fin_acc<FAM>(metric, a1 - mua, b1 - mub[u], dot[u], nx[u], ny[u]);
+                        fin_acc<FAM>(metric, a2 - mua, b2 - mub[u], dot[u], nx[u], ny[u]);
+                        fin_acc<FAM>(metric, a3 - mua, b3 - mub[u], dot[u], nx[u], ny[u]);
                     }
                 }
             }
@@ -131,35 +95,13 @@ __global__ __launch_bounds__(256, METRIC == 0 ? 6 : 4) void k_finalize(const flo
                 const double a0 = xv[t];
 #pragma unroll
                 for (int u = 0; u < 4; u++) {
-                    const double b0 = xu[u][t];
-                    if (metric == 0) s[u] += (a0 - b0) * (a0 - b0);
-                    else if (metric == 1) {
-                        dot[u] += a0 * b0;
-                        nx[u] += a0 * a0;
-                        ny[u] += b0 * b0;
-                    } else {
-                        fin_acc_x(metric, a0 - mua, b0 - mub[u], dot[u], nx[u], ny[u]);
-                    }
+                    fin_acc<FAM>(metric, a0 - mua, (double)xu[u][t] - mub[u], dot[u], nx[u], ny[u]);
                 }
             }
         }
 #pragma unroll
         for (int u = 0; u < 4; u++) {
-            float val;
-            if (metric == 0) {
-                val = (float)fin_group16_sum_f64(s[u]);
-            } else if (metric != 1) {
-                const double dt = fin_group16_sum_f64(dot[u]), ax = fin_group16_sum_f64(nx[u]), ay = fin_group16_sum_f64(ny[u]);
-                val = fin_value_x(metric, dt, ax, ay);
-            } else {
-                const double dt = fin_group16_sum_f64(dot[u]), ax = fin_group16_sum_f64(nx[u]), ay = fin_group16_sum_f64(ny[u]);
-                if (ax == 0.0 && ay == 0.0) val = 0.0f;
-                else if (ax == 0.0 || ay == 0.0 || dt <= 0.0) val = NND_FLT_MAX;
-                else {
-                    const double r = log2(sqrt(ax * ay) / dt);
-                    val = r > 0.0 ? (float)r : 0.0f;
-                }
-            }
+            float val = fin_value<FAM>(metric, dot[u], nx[u], ny[u]);
             if (!on[u]) val = INFINITY;
             // neighbour j = 4 * (s0 + u) + group: lane j takes it from (any lane of) group j & 3
             const float got = __shfl(val, 16 * (lane & 3), 64);
@@ -181,14 +123,15 @@ __global__ __launch_bounds__(256, METRIC == 0 ? 6 : 4) void k_finalize(const flo
 }
 
 // 64 < k <= NND_WIDE_K: one wave per row, ids / exact distances through LDS, four neighbours at a time (16 lanes each), ranks by
-// counting over the LDS copy.  Same arithmetic as k_finalize (float64 accumulation of the reference's formulas).  XM: the
-// instance for the metrics of codes 2..5 (the sqeuclidean / cosine instance does not carry their registers).
+// counting over the LDS copy.  Same arithmetic as k_finalize.  XM: the instance for the metrics of codes 2..6 (the
+// sqeuclidean / cosine instance does not carry their registers).
 template <bool XM>
 __global__ __launch_bounds__(256) void k_finalize_wide(const float *__restrict__ x, int d, int64_t lo, int64_t n, int k, int ks, int metric,
                                                        const uint32_t *__restrict__ knn_e, int32_t *__restrict__ out_idx,
                                                        float *__restrict__ out_dist) {
     __shared__ uint32_t sid[4][NND_WIDE_K];
     __shared__ float sdist[4][NND_WIDE_K];
+    constexpr int FAM = XM ? NND_CODES_ANY : NND_CODES_01;
     const int lane = nnd_lane(), w = threadIdx.x >> 6, grp = lane >> 4, l16 = lane & 15;
     const int64_t v = lo + (int64_t)blockIdx.x * 4 + w;
     if (v >= n) return;
@@ -200,35 +143,11 @@ __global__ __launch_bounds__(256) void k_finalize_wide(const float *__restrict__
         const uint32_t ej = j < k ? sid[w][j] : NND_EMPTY_E;
         const bool on = ej != NND_EMPTY_E;
         const float *xu = x + (int64_t)(on ? (ej & NND_IDX_MASK) : 0) * d;
-        double s = 0.0, dot = 0.0, nx = 0.0, ny = 0.0;
-        if constexpr (XM) {  // the metrics of codes 2..5 (fin_acc_x)
-            const double mua = metric == 4 ? fin_row_mean(xv, d, l16) : 0.0, mub = metric == 4 ? fin_row_mean(xu, d, l16) : 0.0;
-            for (int t = l16; t < d; t += 16) fin_acc_x(metric, (double)xv[t] - mua, (double)xu[t] - mub, dot, nx, ny);
-        } else {
-            for (int t = l16; t < d; t += 16) {
-                const double a0 = xv[t], b0 = xu[t];
-                if (metric == 0) s += (a0 - b0) * (a0 - b0);
-                else {
-                    dot += a0 * b0;
-                    nx += a0 * a0;
-                    ny += b0 * b0;
-                }
-            }
-        }
-        float val;
-        if (metric == 0) {
-            val = (float)fin_group16_sum_f64(s);
-        } else if (XM) {
-            val = fin_value_x(metric, fin_group16_sum_f64(dot), fin_group16_sum_f64(nx), fin_group16_sum_f64(ny));
-        } else {
-            const double dt = fin_group16_sum_f64(dot), ax = fin_group16_sum_f64(nx), ay = fin_group16_sum_f64(ny);
-            if (ax == 0.0 && ay == 0.0) val = 0.0f;
-            else if (ax == 0.0 || ay == 0.0 || dt <= 0.0) val = NND_FLT_MAX;
-            else {
-                const double r = log2(sqrt(ax * ay) / dt);
-                val = r > 0.0 ? (float)r : 0.0f;
-            }
-        }
+        double dot = 0.0, nx = 0.0, ny = 0.0;
+        const bool corr = XM && metric == 4;
+        const double mua = corr ? nnd_row_mean_f64<16>(xv, d, l16) : 0.0, mub = corr ? nnd_row_mean_f64<16>(xu, d, l16) : 0.0;
+        for (int t = l16; t < d; t += 16) fin_acc<FAM>(metric, (double)xv[t] - mua, (double)xu[t] - mub, dot, nx, ny);
+        float val = fin_value<FAM>(metric, dot, nx, ny);
         if (!on) val = INFINITY;
         if (l16 == 0 && j < k) sdist[w][j] = val;
     }
@@ -298,7 +217,7 @@ __global__ __launch_bounds__(64) void k_pairwise(const float *__restrict__ xp, i
     for (int r = 0; r < 4; r++) {
         int row = ta * 16 + 4 * g + r;
         int idr = row < na ? rows_a[row] : -1;
-        if (row < na && col < nb) out[(int64_t)row * nb + col] = nnd_gram_to_dist(metric, acc[r], idr >= 0 ? nrm[idr] : 0.0f, nbv);
+        if (row < na && col < nb) out[(int64_t)row * nb + col] = nnd_gram_to_dist<NND_CODES_ANY>(metric, acc[r], idr >= 0 ? nrm[idr] : 0.0f, nbv);
     }
 }
 

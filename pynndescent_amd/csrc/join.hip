@@ -26,6 +26,7 @@
 //     same source collapse into one slot, and a slot collision keeps the nearer source;
 //   * vertices are visited in the first tree's leaf order, one contiguous eighth per XCD.
 #include "common.h"
+#include "metric.h"
 #include "gram.h"
 #include "state.h"
 
@@ -54,6 +55,9 @@ __device__ __forceinline__ bool klist_has(const uint32_t *kl, uint32_t id) {
 #ifndef NND_J16_WAVES
 #define NND_J16_WAVES 3
 #endif
+// XM, the last template argument of both join kernels, is the metric family of the instance (metric.h nnd_metric_family); it
+// stays an int so that the kernels keep their names
+static_assert(NND_CODES_01 == 0 && NND_CODES_0_5 == 1 && NND_CODE_6 == 2, "launch_join_xm and the kernels' names count on these values");
 template <int DC, int KS16, bool SHARD, int XM = 0>
 __global__ __launch_bounds__(256, NND_J16_WAVES) void k_local_join16(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
                                                          int metric, const int32_t *__restrict__ cand,
@@ -63,6 +67,7 @@ __global__ __launch_bounds__(256, NND_J16_WAVES) void k_local_join16(const float
                                                          uint8_t *__restrict__ pdirty, int pcap, uint32_t slot_seed,
                                                          long long *__restrict__ counters, int64_t own_lo, int64_t own_hi,
                                                          uint64_t *__restrict__ pbuf_r, int pcap_r, int64_t rt_lo, int64_t rt_hi) {
+    constexpr nnd_metric_family FAM = (nnd_metric_family)XM;
     constexpr int MCP = 16, RV = 32;          // rows per vertex: [new(16) | old(16)]
     constexpr int NT = DC / 16;               // 16-byte chunks per lane, row and K block
     constexpr int KQ = KS16 * 4;              // uint4 chunks per neighbour-list row
@@ -334,7 +339,7 @@ __global__ __launch_bounds__(256, NND_J16_WAVES) void k_local_join16(const float
                     const bool valid = pid >= 0 && qid >= 0 && (jj >= MCP || jj >= i);
                     tot_pairs += valid ? 1 : 0;
                     const bool self = (pid == qid);
-                    const float d = self ? nnd_self_dist_t<XM>(metric, pn4[r]) : nnd_gram_to_dist_t<XM>(metric, acc[J][r], pn4[r], qn_);
+                    const float d = self ? nnd_self_dist<FAM>(metric, pn4[r]) : nnd_gram_to_dist<FAM>(metric, acc[J][r], pn4[r], qn_);
 #ifdef NND_JOIN_NOEPI
                     const bool need_p = valid && d == -12345.0f, need_q = false;
 #else
@@ -500,6 +505,7 @@ __global__ __launch_bounds__(256, MCP == 32 ? (ASEL >= 0 ? NND_JW_WAVES_SPLIT : 
                                                                        uint64_t *__restrict__ pbuf_r, int pcap_r, int64_t rt_lo, int64_t rt_hi,
                                                                        int cstride, int new_off, int old_off) {
     static_assert(!BLOCKED || MCP == 64, "the blocked passes run the 64-slot kernel");
+    constexpr nnd_metric_family FAM = (nnd_metric_family)XM;
     constexpr int NA = MCP / 16, NB = 2 * NA, RV = 2 * MCP;
     constexpr int NT = DC / 16;                       // 16-byte chunks per lane, row and K block
     constexpr int RPL = RV / 64;                      // candidate slots per lane (1 or 2)
@@ -794,7 +800,7 @@ __global__ __launch_bounds__(256, MCP == 32 ? (ASEL >= 0 ? NND_JW_WAVES_SPLIT : 
                         const bool valid = pid >= 0 && qid >= 0 && (jj >= MCP || jj >= i);
                         tot_pairs += valid ? 1 : 0;
                         const bool self = (pid == qid);
-                        const float d = self ? nnd_self_dist_t<XM>(metric, pn4[r]) : nnd_gram_to_dist_t<XM>(metric, acc[a][b][r], pn4[r], qn_);
+                        const float d = self ? nnd_self_dist<FAM>(metric, pn4[r]) : nnd_gram_to_dist<FAM>(metric, acc[a][b][r], pn4[r], qn_);
                         const bool need_p = valid && d < pth4[r], need_q = valid && !self && d < qth;
                         const unsigned long long pm = __ballot(need_p | need_q);
                         if (pm) {  // wave-uniform
@@ -924,7 +930,7 @@ static int launch_join_blocked(nnd_ctx *ctx, int64_t v_begin, int64_t v_end) {
     return launch_join_w_t<64, 32, SHARD, true, true, -1, false, XM>(ctx, v_begin, v_end, 256, 0, 64);
 }
 
-// XM: 1 = the instances for the metrics of codes 2..5 (common.h nnd_gram_to_dist_t); the sqeuclidean / cosine instances (0) do not
+// XM: the metric family (metric.h nnd_metric_family).  1 = the instances for the metrics of codes 2..5; the sqeuclidean / cosine instances (0) do not
 // carry their conversions (a runtime branch among six metrics costs the k_local_join16<32, *, 0> epilogue four registers), and
 // code 6 has instances of its own (2: its conversion alone, no branch on the metric) for the same reason: as one more branch of
 // the XM = 1 epilogue it took k_local_join16<64, 1, false, 1> from 127 to 131 registers, a wave per SIMD less for codes 2..5
@@ -946,6 +952,6 @@ static int launch_join_xm(nnd_ctx *ctx, int64_t v_begin, int64_t v_end) {
 
 int nnd_launch_join(nnd_ctx *ctx, int64_t v_begin, int64_t v_end) {
     if (v_end <= v_begin) return 0;
-    if (ctx->p.metric == 6) return launch_join_xm<2>(ctx, v_begin, v_end);
-    return ctx->p.metric >= 2 ? launch_join_xm<1>(ctx, v_begin, v_end) : launch_join_xm<0>(ctx, v_begin, v_end);
+    if (ctx->p.metric == 6) return launch_join_xm<NND_CODE_6>(ctx, v_begin, v_end);
+    return ctx->p.metric >= 2 ? launch_join_xm<NND_CODES_0_5>(ctx, v_begin, v_end) : launch_join_xm<NND_CODES_01>(ctx, v_begin, v_end);
 }

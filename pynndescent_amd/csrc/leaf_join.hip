@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "metric.h"
 #include "gram.h"
 #include "merge.h"
 #include "state.h"
@@ -237,7 +238,7 @@ __global__ __launch_bounds__(NW * 64, (NT <= 5 && NW == 8) ? 8 : (QW && NT <= 5 
 #pragma unroll
             for (int r = 0; r < 4; r++) {
                 const int il = I * 16 + 4 * g + r;
-                const float dv = nnd_gram_to_dist(metric, acct[q][r], nrs[il], nj);
+                const float dv = nnd_gram_to_dist<NND_CODES_ANY>(metric, acct[q][r], nrs[il], nj);
                 Dm[il * C::DSTRIDE + j] = dv;
                 if (I != J) Dm[j * C::DSTRIDE + il] = dv;  // the mirrored tile
             }
@@ -327,7 +328,7 @@ __global__ __launch_bounds__(NW * 64, (NT <= 5 && NW == 8) ? 8 : (QW && NT <= 5 
 #pragma unroll
                     for (int r = 0; r < 4; r++) {
                         const int il = 4 * g + r;
-                        Dw[il * C::DSTRIDE + j] = nnd_gram_to_dist(metric, acc[tr][J][r], nrs[I * 16 + il], nj);
+                        Dw[il * C::DSTRIDE + j] = nnd_gram_to_dist<NND_CODES_ANY>(metric, acc[tr][J][r], nrs[I * 16 + il], nj);
                     }
                 }
             }
@@ -472,7 +473,7 @@ __global__ __launch_bounds__(NW * 64, 2) void k_leaf_join_rb(const float *__rest
 #pragma unroll
         for (int r = 0; r < 4; r++) {
             const int il = tI[q] * 16 - r0 + 4 * g + r;
-            Dm[il * DSTRIDE + j] = nnd_gram_to_dist(metric, acc[q][r], nrs[r0 + il], nj);
+            Dm[il * DSTRIDE + j] = nnd_gram_to_dist<NND_CODES_ANY>(metric, acc[q][r], nrs[r0 + il], nj);
         }
     }
     __syncthreads();
@@ -635,7 +636,7 @@ __global__ __launch_bounds__(NW * 64, NT <= 6 ? NND_SYM_OCC_S : NND_SYM_OCC_L) v
         if (!tOn[q]) continue;
         const float nj = nrs[tJ[q] * 16 + r16];
 #pragma unroll
-        for (int r = 0; r < 4; r++) acc[q][r] = nnd_gram_to_dist(metric, acc[q][r], nrs[tI[q] * 16 + 4 * g + r], nj);
+        for (int r = 0; r < 4; r++) acc[q][r] = nnd_gram_to_dist<NND_CODES_ANY>(metric, acc[q][r], nrs[tI[q] * 16 + 4 * g + r], nj);
     }
     float *Dm = big;  // RB x DSTRIDE: row il = leaf row p0 + il
     int accepted = 0;

@@ -13,6 +13,7 @@
 // initalize_heap_from_graph_indices[_and_distances] (utils.py:836-860).  Both write their
 // candidates into the proposal slots and reuse k_merge.
 #include "common.h"
+#include "metric.h"
 #include "merge.h"
 #include "state.h"
 
@@ -201,20 +202,6 @@ int nnd_launch_merge(nnd_ctx *ctx) {
     return 0;
 }
 
-// wave-cooperative alt-space distance between prepared rows a and b (difference form for euclid)
-__device__ __forceinline__ float row_dist(const float *__restrict__ xp, int dp, const float *__restrict__ nrm, int metric,
-                                          int64_t a, int64_t b) {
-    const float *xa = xp + a * dp, *xb = xp + b * dp;
-    float s = 0.0f;
-    for (int j = nnd_lane(); j < dp; j += 64) {
-        float p = xa[j], q = xb[j];
-        s += metric == 0 ? (p - q) * (p - q) : p * q;
-    }
-    s = nnd_wave_sum_f32(s);
-    if (metric == 0) return nnd_clamp_dist(s);
-    return nnd_gram_to_dist(metric, s, nrm[a], nrm[b]);
-}
-
 // init_random (pynndescent_.py:188-203): rows that are not full get (k - filled) random candidates
 __global__ __launch_bounds__(256) void k_random_init(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
                                                      int metric, int64_t n, int64_t lo, int64_t hi, int k, int ks,
@@ -241,7 +228,7 @@ __global__ __launch_bounds__(256) void k_random_init(const float *__restrict__ x
         uint32_t id = __shfl(pick, j, 64);
         bool on = __shfl((int)mine, j, 64);
         if (!on) continue;
-        float d = row_dist(xp, dp, nrm, metric, v, (int64_t)id);
+        float d = nnd_row_pair_dist(xp, dp, nrm, metric, v, (int64_t)id);
         if (lane == 0) pbuf[v * pcap + j] = nnd_make_key(d, id);
     }
     if (lane == 0) pdirty[v] = 1;
@@ -281,7 +268,7 @@ __global__ __launch_bounds__(256) void k_graph_init(const float *__restrict__ xp
         int32_t q = __shfl(id, j, 64);
         bool on = __shfl((int)mine, j, 64);
         if (!on) continue;
-        float d = gdist ? nnd_clamp_dist(gdist[v * width + col0 + j]) : row_dist(xp, dp, nrm, metric, v, (int64_t)q);
+        float d = gdist ? nnd_clamp_dist(gdist[v * width + col0 + j]) : nnd_row_pair_dist(xp, dp, nrm, metric, v, (int64_t)q);
         if (lane == 0) pbuf[v * pcap + j] = nnd_make_key(d, (uint32_t)q);
     }
     if (lane == 0) pdirty[v] = 1;

@@ -7,10 +7,11 @@
 //       cosine rows are L2-normalised once (the reference recomputes both norms in every
 //       distance call, distances.py:617-620); zero rows stay zero and are flagged in nrm.
 //   nrm (n) float32: |xp_i|^2 for euclidean; 1 (non-zero row) / 0 (zero row) for cosine.
-// The other metrics (common.h nnd_metric_unit): dot rows are L2-normalised like cosine rows, correlation rows have their own
+// The other metrics (metric.h nnd_metric_unit): dot rows are L2-normalised like cosine rows, correlation rows have their own
 // mean subtracted first, hellinger rows are sqrt(x) first (|sqrt x|^2 = |x|_1), all with nrm 1 / 0; inner-product rows stay
 // as given (no column mean: the distance is not translation invariant) with nrm = |x|^2.
 #include "common.h"
+#include "metric.h"
 #include "state.h"
 
 // ---- column means, deterministic two-stage reduction (no float atomics) ----
@@ -89,16 +90,6 @@ __global__ void k_screen_scale(float *__restrict__ mean, int d, int dp, int metr
     mean[dp + 1] = exp2f((float)(-2 * e));
 }
 
-// per-row transform of the unit-row metrics before the normalisation: correlation subtracts the row mean mu, hellinger
-// takes the square root (a negative entry raises the negative-input flag; its NaN never reaches a distance the host hands out).
-// The mean stays in float64 up to the subtraction: rounded to float32 first, a row on a large common offset (1e3 + N(0, 1e-2))
-// would lose half an ulp of the offset, a relative error of 3e-3 in its centred entries.
-__device__ __forceinline__ float prep_unit_transform(int metric, float v, double mu) {
-    if (metric == 4) return (float)((double)v - mu);
-    if (metric == 5) return sqrtf(v);
-    return v;
-}
-
 // ---- one wave per row: pad + centre / normalise + norm ----
 // nr2[row] = (nrm[row], |xp_row - bf16(xp_row)| rounded up): the norm and how far the bf16 copy the forest screens with
 // is from the row, side by side (one 8-byte load per point in the margin kernels)
@@ -136,25 +127,20 @@ __global__ __launch_bounds__(256) void k_prep_rows(const float *__restrict__ x, 
             if (xh) nr2[row] = make_float2(s, sqrtf(r2) * 1.000001f);
         }
     } else {
-        double mu = 0.0;
-        if (metric == 4) {  // the row mean in float64, as the reference's correlation does: a constant row centres to exact zeros
-            double m = 0.0;
-            for (int j = lane; j < d; j += 64) m += (double)src[j];
-            mu = nnd_wave_sum_f64(m) / (double)d;
-        }
+        const double mu = metric == 4 ? nnd_row_mean_f64<64>(src, d, lane) : 0.0;  // (float64 up to the subtraction: metric.h)
         float s = 0.0f;
         for (int j = lane; j < d; j += 64) {
             const float raw = src[j];
             bad |= !isfinite(raw);
             neg |= metric == 5 && raw < 0.0f;
-            const float v = prep_unit_transform(metric, raw, mu);
+            const float v = nnd_unit_transform(metric, raw, mu);
             s += v * v;
         }
         s = nnd_wave_sum_f32(s);
         float inv = s > 0.0f ? 1.0f / sqrtf(s) : 0.0f;
         float r2 = 0.0f;
         for (int j = lane; j < dp; j += 64) {
-            const float v = j < d ? prep_unit_transform(metric, src[j], mu) * inv : 0.0f;
+            const float v = j < d ? nnd_unit_transform(metric, src[j], mu) * inv : 0.0f;
             dst[j] = v;
             if (xh) {
                 const uint16_t b = nnd_f32_to_h16(v, hsc);
@@ -193,7 +179,7 @@ __global__ __launch_bounds__(256) void k_prep_rows_v4(const float *__restrict__ 
     double mu = 0.0;
     const bool unit = nnd_metric_unit(metric);
     if (unit) {  // unit rows: the norm first (the row stays in L1 / L2 for the second pass)
-        if (metric == 4) {  // correlation: the row mean first, in float64 (see k_prep_rows)
+        if (metric == 4) {  // correlation: the row mean first, in float64 (nnd_row_mean_f64's rule on 16-byte loads and lpr lanes)
             double m = 0.0;
             for (int c = jl; c < ncd; c += lpr) {
                 const float4 v = on ? src[c] : make_float4(0, 0, 0, 0);
@@ -205,8 +191,8 @@ __global__ __launch_bounds__(256) void k_prep_rows_v4(const float *__restrict__ 
         for (int c = jl; c < ncd; c += lpr) {
             float4 v = on ? src[c] : make_float4(0, 0, 0, 0);
             neg |= metric == 5 && (v.x < 0.0f || v.y < 0.0f || v.z < 0.0f || v.w < 0.0f);
-            v.x = prep_unit_transform(metric, v.x, mu); v.y = prep_unit_transform(metric, v.y, mu);
-            v.z = prep_unit_transform(metric, v.z, mu); v.w = prep_unit_transform(metric, v.w, mu);
+            v.x = nnd_unit_transform(metric, v.x, mu); v.y = nnd_unit_transform(metric, v.y, mu);
+            v.z = nnd_unit_transform(metric, v.z, mu); v.w = nnd_unit_transform(metric, v.w, mu);
             s += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
         }
         for (int o = lpr >> 1; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
@@ -223,8 +209,8 @@ __global__ __launch_bounds__(256) void k_prep_rows_v4(const float *__restrict__ 
             }
         } else if (unit) {
             if (c < ncd) {  // (the padding stays zero: a centred zero is not)
-                v.x = prep_unit_transform(metric, v.x, mu); v.y = prep_unit_transform(metric, v.y, mu);
-                v.z = prep_unit_transform(metric, v.z, mu); v.w = prep_unit_transform(metric, v.w, mu);
+                v.x = nnd_unit_transform(metric, v.x, mu); v.y = nnd_unit_transform(metric, v.y, mu);
+                v.z = nnd_unit_transform(metric, v.z, mu); v.w = nnd_unit_transform(metric, v.w, mu);
             }
             v.x *= inv; v.y *= inv; v.z *= inv; v.w *= inv;
         }

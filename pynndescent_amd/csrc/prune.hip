@@ -17,29 +17,15 @@
 // bitwise equal there, so the test never prunes at factor 1.  A recomputation here sums in another order than the kernel
 // that stored d(i, j) and would prune at random on a one-ulp difference: every kernel below takes the stored value for it.
 //
-// All three are row-parallel: one wave per row, the row's entries in lanes, pair distances by wave-cooperative
-// dot products over the prepared rows (xp: centred for euclidean -- differences are unchanged -- or
-// L2-normalised for cosine), decisions broadcast with readlane.  The pruning rule is order dependent inside a
+// All three are row-parallel: one wave per row, the row's entries in lanes, pair distances of the prepared rows by
+// nnd_row_pair_dist (metric.h), decisions broadcast with readlane.  The pruning rule is order dependent inside a
 // row (an entry is tested against the entries KEPT so far), so a row is walked sequentially exactly like the
 // reference does; rows are independent.
 #include "common.h"
+#include "metric.h"
 #include "state.h"
 
 #define PRUNE_EPS 1.1920929e-07f  // np.finfo(np.float32).eps (pynndescent_.py:65)
-
-// alt-space distance between prepared rows a and b (all 64 lanes participate)
-__device__ __forceinline__ float prune_pair_dist(const float *__restrict__ xp, int dp, const float *__restrict__ nrm, int metric,
-                                                 int64_t a, int64_t b) {
-    const float *xa = xp + a * dp, *xb = xp + b * dp;
-    float s = 0.0f;
-    for (int j = nnd_lane(); j < dp; j += 64) {
-        const float p = xa[j], q = xb[j];
-        s += metric == 0 ? (p - q) * (p - q) : p * q;
-    }
-    s = nnd_wave_sum_f32(s);
-    if (metric == 0) return nnd_clamp_dist(s);
-    return nnd_gram_to_dist(metric, s, nrm[a], nrm[b]);
-}
 
 // u in [0,1): the coin of one pruning test (reference: tau_rand(rng_state) < prune_probability)
 __device__ __forceinline__ bool prune_coin(uint32_t seed, uint32_t row, uint32_t a, uint32_t b, float prob) {
@@ -85,7 +71,7 @@ __global__ __launch_bounds__(256) void k_diversify_rows(const float *__restrict_
             const float dc = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_d), c));
             if (dc > PRUNE_EPS) {
                 const int32_t idc = __builtin_amdgcn_readlane(my_idx, c);
-                const float d = idc == i ? dj : prune_pair_dist(xp, dp, nrm, metric, idj, idc);  // (the own vertex: see above)
+                const float d = idc == i ? dj : nnd_row_pair_dist(xp, dp, nrm, metric, idj, idc);  // (the own vertex: see above)
                 if (d < lim && (AWARE || prune_coin(seed, (uint32_t)i, (uint32_t)j, (uint32_t)c, prob))) {  // pynndescent_.py:386-389
                     flag = false;
                     break;
@@ -160,7 +146,7 @@ __global__ __launch_bounds__(256) void k_diversify_csr(const float *__restrict__
                     const int32_t idk = __builtin_amdgcn_readlane(my_idx, AWARE ? l : kk);
                     // the row's own vertex: the stored d(i, j) = wj (see above).  AWARE has no EPS guard, so a weight-EPS
                     // entry (the own vertex at distance 0) is a comparison point too and takes the same rule.
-                    const float d = (idk == i || (AWARE && wl <= PRUNE_EPS)) ? wj : prune_pair_dist(xp, dp, nrm, metric, idj, idk);
+                    const float d = (idk == i || (AWARE && wl <= PRUNE_EPS)) ? wj : nnd_row_pair_dist(xp, dp, nrm, metric, idj, idk);
                     if ((AWARE ? d * fj : d) < wj && prune_coin(seed, (uint32_t)i, (uint32_t)j, (uint32_t)kk, prob)) {
                         retained &= ~(1ull << j);
                         break;
@@ -218,7 +204,7 @@ __global__ __launch_bounds__(256) void k_diversify_rows_wide(const float *__rest
         for (int c = 0; c < j; c++) {
             if (!r.kept[c]) continue;
             if (r.w[c] > PRUNE_EPS) {
-                const float d = r.idx[c] == i ? dj : prune_pair_dist(xp, dp, nrm, metric, idj, r.idx[c]);
+                const float d = r.idx[c] == i ? dj : nnd_row_pair_dist(xp, dp, nrm, metric, idj, r.idx[c]);
                 if (d < lim && (AWARE || prune_coin(seed, (uint32_t)i, (uint32_t)j, (uint32_t)c, prob))) {  // pynndescent_.py:386-389
                     flag = false;
                     break;
@@ -296,7 +282,7 @@ __global__ __launch_bounds__(256) void k_diversify_csr_wide(const float *__restr
             const float wl = r.w[l];
             if (AWARE || wl > PRUNE_EPS) {
                 const int32_t idk = r.idx[AWARE ? l : kk];  // AWARE: the point at order[kk]; standard: storage position kk (reference quirk)
-                const float d = (idk == i || (AWARE && wl <= PRUNE_EPS)) ? wj : prune_pair_dist(xp, dp, nrm, metric, idj, idk);
+                const float d = (idk == i || (AWARE && wl <= PRUNE_EPS)) ? wj : nnd_row_pair_dist(xp, dp, nrm, metric, idj, idk);
                 if ((AWARE ? d * fj : d) < wj && prune_coin(seed, (uint32_t)i, (uint32_t)j, (uint32_t)kk, prob)) {
                     if (lane == 0) r.kept[j] = 0;
                     break;

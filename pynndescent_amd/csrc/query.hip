@@ -14,7 +14,7 @@
 //   * distances: a quad (4 lanes) per candidate, 16 candidates of an adjacency row per step, rows gathered from HBM,
 //     the query vector in LDS; float32 in the reference's formulas (distances.py:63-91, 583-630) on the RAW rows --
 //     cosine queries are normalised first (pynndescent_.py:1808-1815), data rows are not.  The other metrics (codes 2..5)
-//     work on prepared rows, as the build does (common.h nnd_gram_to_dist): the searcher's copy of the data gets the
+//     work on prepared rows, as the build does (metric.h nnd_gram_to_dist): the searcher's copy of the data gets the
 //     metric's transform once (k_searcher_prep_rows), each query gets it in the kernel (dot: normalised, a zero query is
 //     skipped as for cosine; correlation: centred, then normalised; hellinger: sqrt, then normalised; inner product: raw);
 //   * stop rule: the nearest unexpanded frontier vertex is farther than
@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "common.h"
+#include "metric.h"
 #include "devmem.h"
 #include "../../include/pynnd_amd.h"
 
@@ -82,29 +83,40 @@ struct nnd_searcher_s {
 
 static thread_local char g_serr[512] = {0};
 
-// quad-cooperative alt-space distance between the query (LDS, dp floats, |q|^2 = qn2) and row `v`
-__device__ __forceinline__ float q_quad_dist(const float *__restrict__ x, const float *__restrict__ xn2, int dp, int metric,
-                                             const float *qs, float qn2, int64_t v, int sub) {
+// sum over the four lanes of a quad, in every one of them (two DPP quad permutes)
+__device__ __forceinline__ float q_quad_sum(float acc) {
+    acc += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc), 0xB1, 0xF, 0xF, false));
+    acc += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc), 0x4E, 0xF, 0xF, false));
+    return acc;
+}
+// quad-cooperative <q, x_v> of the query (LDS, dp floats) and the float row `v`, lane `sub` of the quad taking every fourth
+// 16-byte chunk; SQDIFF: its sibling |q - x_v|^2 (code 0).  Every float distance below starts from it; the rerank instances of
+// code 6 take both of theirs from the plain product -- the walk's proxy nnd_gram_to_dist<NND_CODE_6>(<q,x>, |q|^2, |x|^2) and
+// the rerank's true distance -<q,x> (inner_product, the reference's _true_distance_func), neither clamped nor corrected
+template <bool SQDIFF = false>
+__device__ __forceinline__ float q_quad_dot(const float *__restrict__ x, int dp, const float *qs, int64_t v, int sub) {
     const float4 *row = (const float4 *)(x + v * dp);
     const float4 *q4 = (const float4 *)qs;
     float acc = 0.0f;
-    if (metric == 0) {
-        for (int c = sub; c < (dp >> 2); c += 4) {
-            const float4 a = row[c], b = q4[c];
+    for (int c = sub; c < (dp >> 2); c += 4) {
+        const float4 a = row[c], b = q4[c];
+        if constexpr (SQDIFF) {
             const float d0 = b.x - a.x, d1 = b.y - a.y, d2 = b.z - a.z, d3 = b.w - a.w;
             acc += d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3;
-        }
-    } else {
-        for (int c = sub; c < (dp >> 2); c += 4) {
-            const float4 a = row[c], b = q4[c];
+        } else {
             acc += a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w;
         }
     }
-    acc += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc), 0xB1, 0xF, 0xF, false));
-    acc += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc), 0x4E, 0xF, 0xF, false));
-    if (metric == 0) return acc;
-    if (metric != 1) return nnd_gram_to_dist_x<false>(metric, acc, qn2, xn2[v]);  // prepared rows and query (codes 2..5)
-    // alternative_cosine (distances.py:600-630)
+    return q_quad_sum(acc);
+}
+
+// quad-cooperative alt-space distance between the query (LDS, dp floats, |q|^2 = qn2) and row `v`
+__device__ __forceinline__ float q_quad_dist(const float *__restrict__ x, const float *__restrict__ xn2, int dp, int metric,
+                                             const float *qs, float qn2, int64_t v, int sub) {
+    if (metric == 0) return q_quad_dot<true>(x, dp, qs, v, sub);
+    const float acc = q_quad_dot(x, dp, qs, v, sub);
+    if (metric != 1) return nnd_gram_to_dist<NND_CODES_0_5>(metric, acc, qn2, xn2[v]);  // prepared rows and query (codes 2..5)
+    // alternative_cosine (distances.py:600-630) on the raw rows
     const float nx = xn2[v];
     if (qn2 == 0.0f && nx == 0.0f) return 0.0f;
     if (qn2 == 0.0f || nx == 0.0f || acc <= 0.0f) return NND_FLT_MAX;
@@ -143,8 +155,7 @@ __device__ __forceinline__ float q_quad_proxy(const uint8_t *__restrict__ codes,
     const int full = d >> 4;
     for (int c = sub; c < full; c += 4) chunk(c, 16);
     if ((d & 15) && sub == (full & 3)) chunk(full, d & 15);
-    acc += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc), 0xB1, 0xF, 0xF, false));
-    acc += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc), 0x4E, 0xF, 0xF, false));
+    acc = q_quad_sum(acc);
     if (metric == 0) return acc;
     const float ny = cn2[v];
     if (metric == 2) return acc > 0.0f ? -log2f(acc / sqrtf(ny)) : NND_FLT_MAX;  // distances.py:1948-1966
@@ -158,32 +169,8 @@ __device__ __forceinline__ float q_quad_proxy(const uint8_t *__restrict__ codes,
 __device__ __forceinline__ float q_rerank_dist(const float *__restrict__ x, const float *__restrict__ xn2, int dp, int metric,
                                                const float *qs, float qn2, int64_t v, int sub) {
     if (metric != 2) return q_quad_dist(x, xn2, dp, metric, qs, qn2, v, sub);
-    const float4 *row = (const float4 *)(x + v * dp);
-    const float4 *q4 = (const float4 *)qs;
-    float acc = 0.0f;
-    for (int c = sub; c < (dp >> 2); c += 4) {
-        const float4 a = row[c], b = q4[c];
-        acc += a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w;
-    }
-    acc += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc), 0xB1, 0xF, 0xF, false));
-    acc += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc), 0x4E, 0xF, 0xF, false));
+    const float acc = q_quad_dot(x, dp, qs, v, sub);
     return acc > 0.0f ? -log2f(acc) : NND_FLT_MAX;
-}
-
-// quad-cooperative <q, x_v> of the query (LDS, dp floats) and the float row `v`: the rerank instances (code 6) take both of
-// their distances from it -- the walk's proxy nnd_proxy_ip_dist(<q,x>, |q|^2, |x|^2) (proxy_inner_product, distances.py:810-838)
-// and the rerank's true distance -<q,x> (inner_product, the reference's _true_distance_func), neither clamped nor corrected
-__device__ __forceinline__ float q_quad_dot(const float *__restrict__ x, int dp, const float *qs, int64_t v, int sub) {
-    const float4 *row = (const float4 *)(x + v * dp);
-    const float4 *q4 = (const float4 *)qs;
-    float acc = 0.0f;
-    for (int c = sub; c < (dp >> 2); c += 4) {
-        const float4 a = row[c], b = q4[c];
-        acc += a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w;
-    }
-    acc += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc), 0xB1, 0xF, 0xF, false));
-    acc += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc), 0x4E, 0xF, 0xF, false));
-    return acc;
 }
 
 // KU: result entries per lane -- entry u of lane j is position 64 u + j of the list (k <= 64 KU: 1, 2 or 4)
@@ -368,7 +355,7 @@ __global__ __launch_bounds__(256) void k_query(const float *__restrict__ x, cons
             const int64_t v = cl[c < nc ? c : 0];
             float dv;
             if constexpr (Q8) dv = q_quad_proxy(codes, cn2, dcs, d, metric, (const float *)qsm, qs, qn2, v, sub);
-            else if constexpr (RR) dv = nnd_proxy_ip_dist(q_quad_dot(x, dp, qs, v, sub), qn2, xn2[v]);
+            else if constexpr (RR) dv = nnd_gram_to_dist<NND_CODE_6>(metric, q_quad_dot(x, dp, qs, v, sub), qn2, xn2[v]);
             else dv = q_quad_dist(x, xn2, dp, metric, qs, qn2, v, sub);
             if (sub == 0 && c < nc) cd[c] = dv;
         }
@@ -402,16 +389,11 @@ __global__ __launch_bounds__(256) void k_query(const float *__restrict__ x, cons
             le = -children[2 * node + 1];
         }
         if (metric == 4 || metric == 5) {  // correlation / hellinger: the tree splits the raw rows (angular), the distances the prepared ones
-            double mu = 0.0;
-            if (metric == 4) {
-                double m = 0.0;
-                for (int j = lane; j < d; j += 64) m += (double)qs[j];
-                mu = nnd_wave_sum_f64(m) / (double)d;
-            }
+            const double mu = metric == 4 ? nnd_row_mean_f64<64>(qs, d, lane) : 0.0;
             nnd_wave_lds_sync();
             float p2 = 0.0f;
             for (int j = lane; j < d; j += 64) {
-                const float v = metric == 4 ? (float)((double)qs[j] - mu) : sqrtf(qs[j]);
+                const float v = nnd_unit_transform(metric == 4 ? 4 : 5, qs[j], mu);  // (this block: the codes 4 / 5 only)
                 qs[j] = v;
                 p2 += v * v;
             }
@@ -563,22 +545,17 @@ __global__ __launch_bounds__(256) void k_query(const float *__restrict__ x, cons
         }
 }
 
-// the searcher's copy of the rows for the codes 2..5: the build's row transform (prep.hip), one wave per row, in place --
+// the searcher's copy of the rows for the codes 2..5: the build's row transform (metric.h), one wave per row, in place --
 // dot: L2-normalised; correlation: minus the row mean (float64), then normalised; hellinger: sqrt, then normalised
 __global__ void k_searcher_prep_rows(float *__restrict__ x, int64_t n, int d, int dp, int metric) {
     const int lane = nnd_lane();
     const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= n) return;
     float *row = x + r * dp;
-    double mu = 0.0;  // (kept in float64 up to the subtraction, as prep.hip prep_unit_transform)
-    if (metric == 4) {
-        double m = 0.0;
-        for (int j = lane; j < d; j += 64) m += (double)row[j];
-        mu = nnd_wave_sum_f64(m) / (double)d;
-    }
+    const double mu = metric == 4 ? nnd_row_mean_f64<64>(row, d, lane) : 0.0;
     float s = 0.0f;
     for (int j = lane; j < d; j += 64) {
-        const float v = metric == 4 ? (float)((double)row[j] - mu) : (metric == 5 ? sqrtf(row[j]) : row[j]);
+        const float v = nnd_unit_transform(metric, row[j], mu);
         row[j] = v;
         s += v * v;
     }

@@ -30,6 +30,7 @@
 #include <chrono>
 
 #include "common.h"
+#include "metric.h"
 #include "state.h"
 
 #define RP_EPS 1e-8f  // rp_trees.py:23

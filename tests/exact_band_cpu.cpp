@@ -3,7 +3,7 @@
 //
 //   exact_band_cpu <metric code> <n> <d> <n_query_rows> <file of n * d float32>
 //
-// Emulated, as prep.hip / gram.h / common.h compute it: the float32 preparation of the rows (code 0: minus the column mean;
+// Emulated, as prep.hip / gram.h / metric.h compute it: the float32 preparation of the rows (code 0: minus the column mean;
 // codes 1, 2, 4, 5: transform, f32 sum of squares, 1 / sqrtf, product; code 3: as given), the nrm word, the Gram value as ONE
 // fmaf chain in the kernel's K order (exact_band.h), nnd_gram_to_dist's combination.  Compared with the float64 value of the
 // ORIGINAL rows.  Prints the largest error / band ratio; exit status 1 if any pair exceeds its band.

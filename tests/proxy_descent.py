@@ -14,7 +14,7 @@ from tests import proxy_util as PU
 
 
 class ProxyPrepared(DR.Prepared):
-    """Rows as given and nrm = |x|^2, like inner product (csrc/prep.hip); distances by common.h nnd_proxy_ip_dist."""
+    """Rows as given and nrm = |x|^2, like inner product (csrc/prep.hip); distances by metric.h nnd_proxy_ip_dist."""
 
     def __init__(self, data, exact=False):
         assert not exact, "the proxy has a log2 and two roots: no lattice makes it exact"
