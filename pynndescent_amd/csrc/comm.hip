@@ -1,5 +1,6 @@
 // comm.hip -- the three transports of comm.h.
 #include "comm.h"
+#include "state.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>  // types and prototypes only: librccl is opened with dlopen (load_rccl)
@@ -7,8 +8,6 @@
 
 #include <chrono>
 #include <string>
-
-std::recursive_mutex &nnd_lifecycle_mutex();  // capi.hip (state.h): creation / tear-down of handles is serialised
 
 static thread_local char g_cerr[512] = {0};
 static void cgerr(const char *fmt, ...) {

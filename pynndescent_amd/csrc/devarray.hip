@@ -188,7 +188,7 @@ __global__ __launch_bounds__(256) void k_copy_words(const uint32_t *__restrict__
 }
 
 static thread_local char g_daerr[256] = {0};
-void nnd_set_global_error(const char *msg);  // capi.hip: what nnd_last_global_error returns
+void nnd_set_global_error(const char *msg);  // handle.hip: what nnd_last_global_error returns
 
 static int da_fail(const char *msg) {
     snprintf(g_daerr, sizeof(g_daerr), "%s", msg);

@@ -20,6 +20,7 @@
 
 #include "comm.h"
 #include "common.h"
+#include "plan.h"
 #include "state.h"
 
 struct nnd_shard_s {
@@ -174,7 +175,7 @@ static void shard_free(nnd_shard_s *s) {
 // handle was created for ceil(1.25 T / G) + 1 trees' worth of positions, which holds the (t1 - t0) whole trees of the split by
 // tree; only the tree count, the position space and the tree seed change (every rank draws its own trees from a seed derived
 // from the global one and its first tree's number, as nnd_shard_create does for a by-tree shard).  Called on EVERY rank or on
-// none: at creation (the routing forest is not available on this geometry) or when the ranks have agreed that the by-cell
+// none: at creation (the handle's plan has no routing forest after all) or when the ranks have agreed that the by-cell
 // forest cannot be built on this data (forest_by_cell returns 2: tops / cell tables outgrown on some rank).
 static void shard_switch_to_by_tree(nnd_shard_s *s) {
     nnd_ctx *h = s->h;
@@ -183,7 +184,7 @@ static void shard_switch_to_by_tree(nnd_shard_s *s) {
     h->p.n_trees = s->t1 - s->t0;
     h->P = (int64_t)h->p.n_trees * h->n;
     h->p.tree_rng[1] = (int64_t)((uint64_t)s->gp.tree_rng[1] + 0x9E3779B97F4A7C15ull * (uint64_t)(s->t0 + 1));
-    h->tree_seed = nnd_mix32((uint32_t)h->p.tree_rng[0] ^ nnd_mix32((uint32_t)h->p.tree_rng[1] + 0x9E3779B9u) ^ nnd_mix32((uint32_t)h->p.tree_rng[2] + 0x7F4A7C15u));
+    h->tree_seed = nnd_seed_of(h->p.tree_rng);
     h->own_order = nullptr;
     h->forest_built = false;
 }
@@ -220,13 +221,13 @@ extern "C" int32_t nnd_shard_create(nnd_shard_t *out, const nnd_params *params, 
     nnd_params p = *params;
     p.n_trees = s->t1 - s->t0;
     p.device = comm->device;
-    // Forest sharded BY CELL (forest_by_cell): when the routing forest applies (as in nnd_create: n >= 131072, rows of
+    // Forest sharded BY CELL (forest_by_cell): when the routing forest applies (plan.h nnd_plan_routes: n >= 131072, rows of
     // <= 256 floats) and the tree counts fit the exchange vectors.  The handle's forest tables are then sized for this
     // rank's share of ALL trees' cells (T n / G point-trees + 25 %) and the forest is the single-GPU forest, whatever G is
     // (global tree seeds).  Otherwise: split by tree, every rank drawing its own trees.
     const int t_loc_max = (params->n_trees + G - 1) / G;
-    s->by_cell = G > 1 && params->n_trees > 0 && params->n_trees <= NND_BY_CELL_TREES_MAX && t_loc_max <= NND_BY_CELL_RANK_TREES_MAX && params->n >= 131072 && ((params->dim + 31) & ~31) <= 256 &&
-                 !(params->flags & NND_FLAG_TEST_FOREST_BY_TREE);
+    s->by_cell = G > 1 && params->n_trees > 0 && params->n_trees <= NND_BY_CELL_TREES_MAX && t_loc_max <= NND_BY_CELL_RANK_TREES_MAX &&
+                 nnd_plan_routes(params->n, params->dim, params->flags) && !(params->flags & NND_FLAG_TEST_FOREST_BY_TREE);
     if (s->by_cell) {
         const int share = (int)(((int64_t)params->n_trees * 5 + 4 * G - 1) / (4 * G)) + 1;  // ceil(1.25 T / G) + 1 trees' worth of positions
         s->t_alloc = share > t_loc_max ? share : t_loc_max;
@@ -242,8 +243,8 @@ extern "C" int32_t nnd_shard_create(nnd_shard_t *out, const nnd_params *params, 
     }
     s->k = s->h->k;
     s->ks = s->h->ks;
-    // (the same on every rank: a function of the parameters) the handle has no routing forest after all -- a library built with
-    // the experiment knobs and NND_FOREST_WHOLE=1, or a future change of the condition in nnd_create_impl
+    // (the same on every rank: a function of the parameters) the predicate holds but the plan has no sample: a library built with
+    // the experiment knobs and NND_SAMPLE_STRIDE > n
     if (s->by_cell && !(s->h->s_m > 0 && s->h->s_stride > 0)) shard_switch_to_by_tree(s);
     const int64_t n_own = s->hi - s->lo;
     std::lock_guard<std::recursive_mutex> lifecycle(nnd_lifecycle_mutex());
@@ -1024,7 +1025,7 @@ static int shard_build(nnd_shard_s *s, const float *x_local_dev, void *x_stream,
             section_timer sec(s);
             // (3) local join of the owned vertices
             S_CTX(nnd_zero_counters(h));
-            // (rows of more than 64 neighbours: join_blocks sub-steps as in the one-GPU build, capi.hip auto_join_blocks -- the
+            // (rows of more than 64 neighbours: join_blocks sub-steps as in the one-GPU build, plan.h nnd_auto_join_blocks -- the
             // owned rows are merged between the sub-steps, the proposals for rows owned elsewhere keep collecting in their narrow
             // table and travel once, below)
             const int tj = t_begin(h);

@@ -12,19 +12,7 @@
 
 #include "../../include/pynnd_amd.h"
 #include "devmem.h"
-
-// Experiment / debugging knobs (NND_* environment variables: table sizes, kernel variants, NND_POISON, NND_FOREST_DEBUG)
-// exist only in a library built with `make KNOBS=1` (-DNND_EXPERIMENT_KNOBS): the product library reads no environment
-// variable -- an environment leftover must not be able to change what a build computes.
-#include <stdlib.h>
-static inline const char *nnd_knob(const char *name) {
-#ifdef NND_EXPERIMENT_KNOBS
-    return getenv(name);
-#else
-    (void)name;
-    return nullptr;
-#endif
-}
+#include "knob.h"
 
 // device-side counters (one int64 each), reset per phase
 enum {
@@ -51,7 +39,7 @@ enum {
     CNT_REC_FLAGS = CNT_SCRATCH + 2,   // recording finisher (after the level loop, before any cell list): two ints, [0] node-id counter, [1] overflow flag
     CNT_MAX_LEAF = CNT_SCRATCH + 2,    // leaf tables (after the finishers): int32, longest leaf
     CNT_MAX_STAY = CNT_SCRATCH + 3,    // level loop: longest segment that stays in the level passes (k_children)
-    CNT_PREP_FLAG = CNT_SCRATCH        // in counters_SUM, not in the stripes: bit 0 non-finite / bit 1 negative input (prep.hip; read by shard.hip, capi.hip)
+    CNT_PREP_FLAG = CNT_SCRATCH        // in counters_SUM, not in the stripes: bit 0 non-finite / bit 1 negative input (prep.hip; read by shard.hip, capi.hip data_flag)
 };
 static_assert(CNT_SMALL_COUNT < CNT_MFMA && CNT_MAX_STAY < CNT_MFMA, "the forest's scratch words end below CNT_MFMA");
 static_assert(CNT_BIG_COUNT == CNT_FIN_COUNT + 1 && CNT_SMALL_COUNT == CNT_FIN_COUNT + 2, "k_cell_lists counts its three classes in adjacent words");
@@ -126,7 +114,7 @@ struct nnd_handle_s {
     nnd_devmem mem;                // owner of every device buffer below, whichever translation unit allocates it (devmem.h)
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    std::vector<hipEvent_t> tev;   // event pool of the deferred stage timers (capi.hip t_begin / t_end / t_flush)
+    std::vector<hipEvent_t> tev;   // event pool of the deferred stage timers (t_begin / t_end / t_flush below)
     int tev_used = 0;
     std::vector<nnd_tlog> tlog;
     hipEvent_t ev_spin = nullptr;  // nnd_sync_spin: busy-polled completion of small read-backs (lower wake-up latency)
@@ -286,8 +274,12 @@ static inline nnd_work_list nnd_big_list(const nnd_ctx *ctx) { return {ctx->seg_
 static inline int32_t *nnd_route_tree_cells(const nnd_ctx *ctx) { return &ctx->route_roots[NND_RR_TREE_CELLS]; }
 static inline int32_t *nnd_route_tree_pos(const nnd_ctx *ctx) { return &ctx->route_roots[NND_RR_TREE_POS]; }
 
-// capi.hip: nnd_create with the shard geometry known up front (bounds == nullptr: a plain handle)
+// handle.hip: nnd_create with the shard geometry known up front (bounds == nullptr: a plain handle)
 int nnd_create_impl(nnd_handle_t *out, const nnd_params *p, const int64_t *bounds_host, int n_ranks, int rank);
+void nnd_set_global_error(const char *msg);  // handle.hip: what nnd_last_global_error returns (the entries that have no handle)
+// transfer.hip: pageable host memory <-> device through pinned staging buffers (small or pinned: one plain copy); d2h returns drained
+int nnd_h2d_parallel(nnd_ctx *ctx, void *dst_dev, const void *src, size_t bytes);
+int nnd_d2h_parallel(nnd_ctx *ctx, void *dst, const void *src, size_t bytes, int parts);
 // ---- implemented in the kernel translation units; each returns 0 / sets ctx->err ----
 int nnd_launch_prep(nnd_ctx *ctx);
 // the pieces of nnd_launch_prep (prep.hip), for the sharded build: a rank preps its own rows first, the others once they arrive
@@ -327,7 +319,7 @@ int nnd_launch_init_from_graph(nnd_ctx *ctx, const int32_t *idx_dev, const float
 int nnd_launch_sample(nnd_ctx *ctx);
 // One process-wide lock around the creation and the tear-down of handles (hipMalloc / hipFree storms, stream and event
 // creation / destruction): ranks that live as threads of one process (LOCAL transport, nnd_build_multi) create and destroy
-// their state at the same moment; none of it is on a timed path, so it is simply serialised.
+// their state at the same moment; none of it is on a timed path, so it is simply serialised.  (handle.hip)
 std::recursive_mutex &nnd_lifecycle_mutex();
 
 int nnd_launch_sample_begin(nnd_ctx *ctx, int64_t cap, int32_t *targets_dev, uint32_t *sources_dev, long long *counts_dev);

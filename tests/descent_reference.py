@@ -1,7 +1,7 @@
 """A step-exact restatement of one NN-descent iteration (local join + proposal merge) in float64 numpy: test infrastructure.
 
 What is restated, and from where:
-  * csrc/capi.hip descent_iter (:656-697): ``join_blocks`` sub-steps, sub-step b joins the vertices [n b / nb, n (b + 1) / nb)
+  * csrc/capi.hip descent_iter: ``join_blocks`` sub-steps, sub-step b joins the vertices [n b / nb, n (b + 1) / nb)
     of the visiting order and is followed by a merge of EVERY row that has pending proposals; counters are zeroed once per
     iteration and read at its end.  The visiting order is the first tree's, so sub-steps are modelled for builders without a
     forest only (position = id).
@@ -180,7 +180,7 @@ def reference_iter(data, metric, idx0, dist0, fl0, new, old, k, rng_state, it, j
     d_rad = np.zeros((n, k))
     flags = np.where(ids >= 0, post_sampling_flags(idx0, fl0, new), 0).astype(np.uint8)
     new, old = np.asarray(new, np.int64), np.asarray(old, np.int64)
-    slot_seed = hash2(searcher_seed(rng_state) ^ 0x2545F491, int(it))  # join.hip :422 (capi.hip seed_of = searcher_seed)
+    slot_seed = hash2(searcher_seed(rng_state) ^ 0x2545F491, int(it))  # join.hip :422 (common.h nnd_seed_of = searcher_seed)
     slot_of = np.array([hash2(slot_seed, s) & 63 for s in range(n)], np.int64) if slots is not None else None
     assert slots in (None, 64)
     amb = np.zeros(n, np.uint8)

@@ -31,7 +31,7 @@ What is restated, and from where (rpforest.hip unless said otherwise):
     finisher list with its depth.  Tail: after a level, once active_pos * 2 < 3 n and the longest stayer is <= BIG_MAX = 8192 the
     stayers go to the global-memory finisher (same rules; it hands nodes of <= FIN_MAX on to the LDS form).  active_pos counts the
     stayers of ALL trees, so the passes are modelled level by level over all trees.
-  * routing mode (capi.hip :252-259; n >= 131072, dp <= 256): sample member j is row 16 j + hash2(seed ^ 0x7F4A7C15, j) % 16,
+  * routing mode (csrc/plan.h nnd_plan_routes: n >= 131072, dp <= 256): sample member j is row 16 j + hash2(seed ^ 0x7F4A7C15, j) % 16,
     M = n / 16 (k_gather_sample :1061).  The sample forest is the same machinery on the sample rows: leaf_size 24, fin_max 512,
     ids = sample indices, positions in T * M, recording finisher (one-wave form) with tree = position / M (forest_by_routing
     :2307-2308, record_subtrees :1999-2028).  Its leaves are the cells, in position order, each with its depth (:562-568, :979-983).
@@ -81,7 +81,7 @@ from tests.search_reference import METRIC_CODE, U24, _unit_rows, searcher_seed
 
 EPS = 1e-8
 FIN_MAX, BIG_MAX, FIN_SMALL = 2048, 8192, 512   # rpforest.hip :634-642
-ROUTE_MIN_N, ROUTE_MAX_DP, SAMPLE_STRIDE, CELL_LEAF = 131072, 256, 16, 24   # capi.hip :252-259
+ROUTE_MIN_N, ROUTE_MAX_DP, SAMPLE_STRIDE, CELL_LEAF = 131072, 256, 16, 24   # csrc/plan.h nnd_plan_routes, nnd_make_plan
 COIN = 0x5bd1e995
 M32 = 0xFFFFFFFF
 METRIC_NAME = {0: "euclidean", 1: "cosine", 2: "dot", 3: "inner_product", 4: "correlation", 5: "hellinger"}
@@ -182,7 +182,7 @@ class Prepared:
 
 
 def tree_seed_of(tree_rng):
-    """capi.hip :97, :108: the forest's 32-bit seed from the first tree's int64[3] state (``seed_of`` = searcher_seed)."""
+    """csrc/common.h nnd_seed_of (handle.hip arm_for_build): the forest's 32-bit seed from the first tree's int64[3] state (= searcher_seed)."""
     return searcher_seed(tree_rng)
 
 

@@ -1,8 +1,8 @@
 """dot / inner_product / correlation / hellinger (codes 2..5) on every kernel instance that serves them, on a real MI355X,
 against float64 truth and the CPU oracle (the reference algorithm, pinned by tests/test_oracle_metrics_cpu.py).
 
-Which instance a case selects (parameter ids name it).  dp = d rounded up to 32 (capi.hip, nnd_create); ks = k rounded
-up to 16; the padded max_candidates mcp is 16 / 32 / 64 / 128 (capi.hip, nnd_create: 32 at least when ks > 64).
+Which instance a case selects (parameter ids name it).  dp = d rounded up to 32 (csrc/plan.h nnd_make_plan); ks = k rounded
+up to 16; the padded max_candidates mcp is 16 / 32 / 64 / 128 (the same function: 32 at least when ks > 64).
   prep.hip nnd_prep_rows:        d % 4 != 0 -> k_prep_rows (scalar); else k_prep_rows_v4, lpr = the power of two >= dp/4
                                  (max 64): d 4 -> 1 .. d 256 / 260 -> 64
   join.hip launch_join_xm:       mcp 16 -> k_local_join16 (DC 32 at dp < 128, 64 at dp >= 128); mcp 32 -> k_local_join_w<32>

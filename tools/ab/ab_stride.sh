@@ -1,6 +1,6 @@
 #!/bin/bash
 # sample stride / cell size of the routing forest, sharded critical path + per-tree cost on one GPU:
-#   tools/ab/ab_stride.sh <tag> <variant> "<ENV=.. ENV=..>" ["<...>" ...]     (variant: a KNOBS build of capi.hip)
+#   tools/ab/ab_stride.sh <tag> <variant> "<ENV=.. ENV=..>" ["<...>" ...]     (variant: a KNOBS build of the library, tools/build_variant.sh)
 tag=$1; v=$2; shift; shift
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; mkdir -p $O
 lib=$R/pynndescent_amd/_exp/lib_$v.so

@@ -57,7 +57,7 @@ if "--curves" in sys.argv:
         print(json.dumps({"forced_iters": it, "gpu": gpu(1, n_iters=it, delta=0.0)[0], "oracle": orc(1, n_iters=it, delta=0.0)[0] if it > 0 else None}), flush=True)
 for jb in (2, 4, 12):
     print(json.dumps({"join_blocks": jb, "gpu": gpu(1, join_blocks=jb)}), flush=True)
-# join_blocks = 0: the library's schedule (sub-steps follow the update volume); under a KNOBS build of capi.hip
+# join_blocks = 0: the library's schedule (sub-steps follow the update volume); under a KNOBS build of the library
 # (PYNND_AMD_LIB=pynndescent_amd/_exp/lib_kn.so) the schedule's parameters can be swept
 for env in ({}, {"NND_JB_MAX": "1"}, {"NND_JB_DIV": "1"}, {"NND_JB_MAX": "16", "NND_JB_DIV": "1", "NND_JB_FIRST": "16"}, {"NND_JB_MAX": "16", "NND_JB_DIV": "1", "NND_JB_FIRST": "8"}):
     for kk in ("NND_JB_MAX", "NND_JB_DIV", "NND_JB_FIRST"):

@@ -1,5 +1,5 @@
 """Recall@10 of the GPU build under experiment knobs, several seeds each, on MANY sample rows (sigma of one number ~ 0.00025),
-next to the CPU oracle on the same rows.  Needs a KNOBS build of capi.hip (PYNND_AMD_LIB=pynndescent_amd/_exp/lib_kn.so).
+next to the CPU oracle on the same rows.  Needs a KNOBS build of the library (csrc/knob.h; PYNND_AMD_LIB=pynndescent_amd/_exp/lib_kn.so).
 usage: python tools/recall_study.py [c3|c2] [n_rows] [oracle seeds] [gpu seeds]"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
