@@ -41,6 +41,9 @@ __host__ __device__ __forceinline__ uint32_t nnd_hash2(uint32_t seed, uint32_t a
 __host__ __device__ __forceinline__ uint32_t nnd_hash3(uint32_t seed, uint32_t a, uint32_t b) {
     return nnd_mix32(nnd_hash2(seed, a) ^ nnd_mix32(b * 0x85EBCA6Bu + 0xC2B2AE35u));
 }
+// the word that stands for (entry a, compared entry b) in the coin hash of a pruning test (prune.hip): positions in a row of at
+// most NND_WIDE_K entries, a different word for every pair -- every test of a row has a coin of its own
+__host__ __device__ __forceinline__ uint32_t nnd_prune_coin_word(uint32_t a, uint32_t b) { return a * (uint32_t)NND_WIDE_K + b; }
 // the 32-bit seed of a build (or of its forest) from the caller's int64[3] generator state (nnd_params rng_state / tree_rng)
 static inline uint32_t nnd_seed_of(const int64_t *s) { return nnd_mix32((uint32_t)s[0] ^ nnd_mix32((uint32_t)s[1] + 0x9E3779B9u) ^ nnd_mix32((uint32_t)s[2] + 0x7F4A7C15u)); }
 

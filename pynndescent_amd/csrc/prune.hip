@@ -27,10 +27,10 @@
 
 #define PRUNE_EPS 1.1920929e-07f  // np.finfo(np.float32).eps (pynndescent_.py:65)
 
-// u in [0,1): the coin of one pruning test (reference: tau_rand(rng_state) < prune_probability)
+// u in [0,1): the coin of one pruning test (reference: tau_rand(rng_state) < prune_probability); a, b: positions in the row
 __device__ __forceinline__ bool prune_coin(uint32_t seed, uint32_t row, uint32_t a, uint32_t b, float prob) {
     if (prob >= 1.0f) return true;
-    const uint32_t h = nnd_hash3(seed, row, a * 64u + b);
+    const uint32_t h = nnd_hash3(seed, row, nnd_prune_coin_word(a, b));
     return (float)(h >> 8) * (1.0f / 16777216.0f) < prob;
 }
 

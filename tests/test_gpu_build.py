@@ -289,6 +289,12 @@ def test_search_graph_pruning_pass_vs_reference_fixture(metric):
     agree = (st["forward_rows"] == fr).mean()
     print("forward diversify agreement %.5f; nnz %d -> %d -> %d" % (agree, st["forward_nnz"], st["union_nnz"], st["final_nnz"]))
     assert agree > 0.995
+    # tightened by the step-exact model (tests/prune_reference.py): every forward row the model can pin IS the reference's
+    from tests import prune_reference as PR
+
+    model = PR.diversify_rows(PR.Prepared(x, metric), g[metric + "_idx"], g[metric + "_dist"])
+    off = np.nonzero((st["forward_rows"] != fr).any(1) & (model.flags == 0))[0]
+    assert not len(off), (off[:5], int((model.flags != 0).sum()))
     a = set(zip(np.repeat(np.arange(n), np.diff(sg.indptr)).tolist(), sg.indices.tolist()))
     b = set(zip(np.repeat(np.arange(n), np.diff(g[metric + "_indptr"])).tolist(), g[metric + "_indices"].tolist()))
     assert len(a ^ b) <= 0.01 * len(b), (len(a ^ b), len(b))
