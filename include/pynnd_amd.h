@@ -496,6 +496,35 @@ int32_t nnd_hub_tree_build(nnd_handle_t h, const int32_t *rank_order_host, int32
 int32_t nnd_hub_tree_fetch(nnd_handle_t h, float *hyperplanes, float *offsets, int32_t *children, int32_t *indices,
                            int32_t *max_leaf_size);
 
+/* ---- prepare() of an index whose rows and graph live on the device (csrc/prepare.hip; DESIGN.md "Device arrays") ----
+ * The glue between the hub tree, the pruning pass and the searcher, so that neither the rows nor the graph visit the host.
+ * The entries without a handle take a device ordinal and a HIP stream (NULL: the device's default stream), queue their kernels
+ * there and return when the stream has drained (their scratch buffers are released on return).
+ *
+ * nnd_rank_order_device: the hub tree's rank order from a device graph.  idx_dev: int32 (n, k) neighbour ids; ids < 0 and
+ * ids >= n are skipped (compute_global_degrees, rp_trees.py:714-744).  rank_order_dev (n): the point ids sorted by
+ * (-in-degree, id) -- numpy.argsort(-degree, kind="stable") entry for entry: one radix sort of the packed keys
+ * (0xFFFFFFFF - degree) << 32 | id. */
+int32_t nnd_rank_order_device(int32_t device, void *hip_stream, const int32_t *idx_dev, int64_t n, int32_t k, int32_t *rank_order_dev);
+/* nnd_hub_tree_build with the rank order on the handle's device (read on the handle's stream); everything else as there */
+int32_t nnd_hub_tree_build_device(nnd_handle_t h, const int32_t *rank_order_dev, int32_t leaf_size, int32_t max_depth,
+                                  int64_t *n_nodes_out);
+/* The finished search graph of the last nnd_search_graph call where it lies: device addresses of indptr (n + 1) and indices
+ * (final_nnz) in the handle's workspace, valid until the next pass on the handle or its nnd_destroy.  No copy is made. */
+int32_t nnd_search_graph_device(nnd_handle_t h, const int32_t **indptr_dev, const int32_t **indices_dev, int64_t *nnz);
+/* The tail of _init_search_graph (pynndescent_.py:1629-1651) for the graph: rows and columns of a CSR pattern (indptr (n + 1),
+ * indices (nnz), rows of at most 384 entries, columns in [0, n)) in the order `order_dev` (n, a permutation of [0, n): new row i
+ * is old row order[i], column j becomes the position of j in `order`), columns ascending within a row -- scipy's
+ * g[order, :].tocsc()[:, order].tocsr() with sort_indices().  order_dev NULL: the identity, the graph is copied as it is.
+ * Outputs: indptr_out_dev (n + 1), indices_out_dev (nnz).  One wave per row. */
+int32_t nnd_reorder_csr_device(int32_t device, void *hip_stream, const int32_t *order_dev, int64_t n, const int32_t *indptr_dev,
+                               const int32_t *indices_dev, int64_t nnz, int32_t *indptr_out_dev, int32_t *indices_out_dev);
+/* The same, and the rows' gather, on host arrays staged through the device (tests: row shapes no small index produces).
+ * x: float32 (n, dim); x_out: (n, dp) with dp = (dim + 3) & ~3, row i = x[order[i]] followed by dp - dim zeros -- the
+ * searcher's padded layout.  order NULL: the identity. */
+int32_t nnd_reorder_host(int32_t device, int64_t n, int32_t dim, const int32_t *order, const int32_t *indptr, const int32_t *indices,
+                         int64_t nnz, const float *x, int32_t *indptr_out, int32_t *indices_out, float *x_out);
+
 /* ---- batched queries against a prepared index (reference NNDescent.query, pynndescent_.py:2275-2379: the search
  * closure of _init_search_function 1793-1883, select_side / search_flat_tree rp_trees.py:2662-2741, deheap_sort) ----
  * The searcher owns device copies of what the reference's closure captures: the (reordered) raw data, the CSR search
@@ -507,6 +536,17 @@ int32_t nnd_searcher_create(nnd_searcher_t *out, int32_t device, int64_t n, int3
                             const int32_t *indptr, const int32_t *indices, int64_t nnz, const float *hyperplanes,
                             const float *offsets, const int32_t *children, const int32_t *tree_indices, int64_t n_nodes,
                             float min_distance, int32_t n_neighbors, const int64_t *search_rng_state /* 3 */);
+/* The same searcher filled from device memory, on `hip_stream` (NULL: the device's default stream) of `device`.  rows_dev: the
+ * point set, (n, dim) rows of `dtype` (NND_DTYPE_*) in their ORIGINAL order; order_dev (n, device; NULL: the identity): row i of
+ * the searcher is row order[i] of rows_dev, converted to float32 and written straight into the padded layout (dp floats, zero
+ * fill).  indptr_dev / indices_dev: the CSR graph in the searcher's numbering (nnd_reorder_csr_device), copied device to
+ * device.  The tree tables are HOST pointers as above (tree_indices in the searcher's numbering).  The caller's buffers are
+ * free again when the call returns (the stream has drained). */
+int32_t nnd_searcher_create_device(nnd_searcher_t *out, int32_t device, int64_t n, int32_t dim, int32_t metric, const void *rows_dev,
+                                   int32_t dtype, const int32_t *order_dev, const int32_t *indptr_dev, const int32_t *indices_dev,
+                                   int64_t nnz, const float *hyperplanes, const float *offsets, const int32_t *children,
+                                   const int32_t *tree_indices, int64_t n_nodes, float min_distance, int32_t n_neighbors,
+                                   const int64_t *search_rng_state /* 3 */, void *hip_stream);
 int32_t nnd_searcher_query(nnd_searcher_t s, const float *queries /* (nq, dim) */, int64_t nq, int32_t k, float epsilon,
                            int32_t *out_idx /* (nq, k) */, float *out_dist /* (nq, k) */);
 /* The search runs in two tiers: per-query LDS structures (3400 visited vertices, 512 frontier entries) and, for exactly

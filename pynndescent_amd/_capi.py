@@ -271,6 +271,16 @@ _SIGNATURES = [
     ("nnd_searcher_create", C.c_int32, [C.POINTER(_H), C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_int32,
                                         C.c_void_p]),
+    ("nnd_rank_order_device", C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
+    ("nnd_hub_tree_build_device", C.c_int32, [_H, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    ("nnd_search_graph_device", C.c_int32, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
+    ("nnd_reorder_csr_device", C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                           C.c_void_p]),
+    ("nnd_reorder_host", C.c_int32, [C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p]),
+    ("nnd_searcher_create_device", C.c_int32, [C.POINTER(_H), C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                               C.c_float, C.c_int32, C.c_void_p, C.c_void_p]),
     ("nnd_searcher_query", C.c_int32, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
     ("nnd_searcher_last_spilled", C.c_int64, [_H]),
     ("nnd_searcher_set_tier", C.c_int32, [_H, C.c_int32]),
@@ -536,6 +546,20 @@ class Builder:
         out = (indptr, indices[: int(st.final_nnz)], stats)
         return out + (fr, fd) if want_forward else out
 
+    def search_graph_device(self, idx_ptr, dist_ptr, n_neighbors, pruning_degree_multiplier=1.5, diversify_prob=1.0, degree_aware=False,
+                            degree_prune_aggressiveness=1.0, seed=0):
+        """The pass on a graph at the device addresses ``idx_ptr`` / ``dist_ptr``, its result left where it lies: returns (device
+        address of indptr (n + 1), of indices (nnz), nnz, stats dict).  The addresses are the handle's: valid until its next pass
+        or ``close()``; the reorder of ``reorder_csr_device`` reads them in place."""
+        st = NNDSearchGraphStats()
+        self._check(self.lib.nnd_search_graph(self._h, C.c_void_p(int(idx_ptr)), C.c_void_p(int(dist_ptr)), 1, int(n_neighbors),
+                                              float(pruning_degree_multiplier), float(diversify_prob), 1 if degree_aware else 0,
+                                              float(degree_prune_aggressiveness), int(seed) & 0xFFFFFFFF, None, None, C.byref(st)))
+        indptr, indices, nnz = C.c_void_p(), C.c_void_p(), C.c_int64()
+        self._check(self.lib.nnd_search_graph_device(self._h, C.byref(indptr), C.byref(indices), C.byref(nnz)))
+        stats = {f: getattr(st, f) for f, _ in NNDSearchGraphStats._fields_ if f != "reserved"}
+        return int(indptr.value or 0), int(indices.value or 0), int(nnz.value), stats
+
     def degree_prune(self, indptr, data, max_degree):
         indptr = np.ascontiguousarray(indptr, np.int32)
         data = np.ascontiguousarray(data, np.float32).copy()
@@ -548,13 +572,22 @@ class Builder:
         assert ro.shape == (self.n,)
         nn = C.c_int64()
         self._check(self.lib.nnd_hub_tree_build(self._h, _ptr(ro), int(leaf_size), int(max_depth), C.byref(nn)))
-        hyper = np.empty((nn.value, self.dim), np.float32)
-        offs = np.empty((nn.value,), np.float32)
-        children = np.empty((nn.value, 2), np.int32)
+        return self._hub_tree_fetch(nn.value)
+
+    def _hub_tree_fetch(self, n_nodes):
+        hyper = np.empty((n_nodes, self.dim), np.float32)
+        offs = np.empty((n_nodes,), np.float32)
+        children = np.empty((n_nodes, 2), np.int32)
         indices = np.empty((self.n,), np.int32)
         ml = C.c_int32()
         self._check(self.lib.nnd_hub_tree_fetch(self._h, _ptr(hyper), _ptr(offs), _ptr(children), _ptr(indices), C.byref(ml)))
         return hyper, offs, children, indices, int(ml.value)
+
+    def hub_tree_device(self, rank_order_ptr, leaf_size, max_depth):
+        """``hub_tree`` with the rank order at a device address (int32 (n), e.g. what ``rank_order_device`` wrote)."""
+        nn = C.c_int64()
+        self._check(self.lib.nnd_hub_tree_build_device(self._h, C.c_void_p(int(rank_order_ptr)), int(leaf_size), int(max_depth), C.byref(nn)))
+        return self._hub_tree_fetch(nn.value)
 
     def pairwise_gram(self, rows_a, rows_b):
         a = np.ascontiguousarray(rows_a, np.int32)
@@ -614,6 +647,36 @@ class Searcher:
                                           int(n_nodes), float(min_distance), int(n_neighbors), _ptr(rng))
         if rc != 0:
             raise NNDError(self.lib.nnd_searcher_last_error(None).decode())
+
+    @classmethod
+    def from_device(cls, rows_ptr, dtype, n, dim, order_ptr, indptr_ptr, indices_ptr, nnz, tree, metric, min_distance, n_neighbors,
+                    search_rng_state, device=0, stream_ptr=0):
+        """The searcher filled from device memory (``nnd_searcher_create_device``): (n, dim) rows of ``dtype`` (NND_DTYPE_*) at
+        ``rows_ptr`` in their original order, gathered by the int32 permutation at ``order_ptr`` (0: identity); the CSR graph in the
+        searcher's numbering at ``indptr_ptr`` / ``indices_ptr``; ``tree``: host FlatTree or None; on the HIP stream ``stream_ptr``."""
+        self = object.__new__(cls)
+        self.lib = load_library()
+        self.n, self.dim = int(n), int(dim)
+        if tree is not None:
+            hyper = np.ascontiguousarray(tree.hyperplanes, np.float32)
+            offs = np.ascontiguousarray(tree.offsets, np.float32)
+            children = np.ascontiguousarray(tree.children, np.int32)
+            tidx = np.ascontiguousarray(tree.indices, np.int32)
+            n_nodes = hyper.shape[0]
+        else:
+            hyper = offs = children = tidx = None
+            n_nodes = 0
+        rng = np.ascontiguousarray(search_rng_state, np.int64)
+        self.has_codes = False
+        self._h = _H()
+        dev = lambda p: C.c_void_p(int(p)) if p else None  # noqa: E731
+        rc = self.lib.nnd_searcher_create_device(C.byref(self._h), int(device), self.n, self.dim, int(metric), dev(rows_ptr), int(dtype),
+                                                 dev(order_ptr), dev(indptr_ptr), dev(indices_ptr), int(nnz), _ptr(hyper), _ptr(offs),
+                                                 _ptr(children), _ptr(tidx), int(n_nodes), float(min_distance), int(n_neighbors), _ptr(rng),
+                                                 dev(stream_ptr))
+        if rc != 0:
+            raise NNDError(self.lib.nnd_searcher_last_error(None).decode())
+        return self
 
     def query(self, queries, k, epsilon):
         q = np.ascontiguousarray(queries, np.float32)
@@ -811,3 +874,43 @@ def device_correct(device, stream_ptr, kind, in_ptr, out_ptr, count):
     if lib.nnd_device_correct(int(device), C.c_void_p(int(stream_ptr)) if stream_ptr else None, int(kind), C.c_void_p(int(in_ptr)),
                               C.c_void_p(int(out_ptr)), int(count)) != 0:
         raise NNDError(lib.nnd_last_global_error().decode())
+
+
+def rank_order_device(device, stream_ptr, idx_ptr, n, k, out_ptr):
+    """The hub tree's rank order of the int32 (n, k) graph at the device address ``idx_ptr``: the ids by (-in-degree, id), int32
+    (n) at ``out_ptr`` -- ``numpy.argsort(-bincount, kind="stable")``; on ``stream_ptr`` of ``device``, drained on return."""
+    lib = load_library()
+    if lib.nnd_rank_order_device(int(device), C.c_void_p(int(stream_ptr)) if stream_ptr else None, C.c_void_p(int(idx_ptr)), int(n), int(k),
+                                 C.c_void_p(int(out_ptr))) != 0:
+        raise NNDError(lib.nnd_last_global_error().decode())
+
+
+def reorder_csr_device(device, stream_ptr, order_ptr, n, indptr_ptr, indices_ptr, nnz, indptr_out_ptr, indices_out_ptr):
+    """Rows and columns of the CSR pattern at the device addresses ``indptr_ptr`` / ``indices_ptr`` in the order of the int32
+    permutation at ``order_ptr`` (0: the identity, a copy), columns ascending, into ``indptr_out_ptr`` / ``indices_out_ptr``."""
+    lib = load_library()
+    dev = lambda p: C.c_void_p(int(p)) if p else None  # noqa: E731
+    if lib.nnd_reorder_csr_device(int(device), dev(stream_ptr), dev(order_ptr), int(n), dev(indptr_ptr), dev(indices_ptr), int(nnz),
+                                  dev(indptr_out_ptr), dev(indices_out_ptr)) != 0:
+        raise NNDError(lib.nnd_last_global_error().decode())
+
+
+def reorder_host(order, indptr, indices, x, device=0):
+    """``search_tree.reorder_by_tree`` by the device kernels on host arrays (the test entry): returns (indptr, indices, rows) --
+    the CSR pattern and the float32 rows ``x`` in the order ``order`` (None: identity), the rows in the searcher's layout, (n, dp)
+    with dp = (dim + 3) & ~3 and zeros past dim."""
+    lib = load_library()
+    x = np.ascontiguousarray(x, np.float32)
+    n, dim = x.shape
+    indptr = np.ascontiguousarray(indptr, np.int32)
+    indices = np.ascontiguousarray(indices, np.int32)
+    order = None if order is None else np.ascontiguousarray(order, np.int32)
+    assert indptr.shape == (n + 1,) and (order is None or order.shape == (n,))
+    nnz = int(indices.shape[0])
+    out_ptr = np.empty(n + 1, np.int32)
+    out_ind = np.empty(max(nnz, 1), np.int32)
+    out_x = np.empty((n, (dim + 3) & ~3), np.float32)
+    if lib.nnd_reorder_host(int(device), n, dim, _ptr(order), _ptr(indptr), _ptr(indices), nnz, _ptr(x), _ptr(out_ptr), _ptr(out_ind),
+                            _ptr(out_x)) != 0:
+        raise NNDError(lib.nnd_last_global_error().decode())
+    return out_ptr, out_ind[:nnz], out_x

@@ -563,13 +563,26 @@ extern "C" int32_t nnd_search_graph_fetch(nnd_handle_t ctx, int32_t *indptr_host
     if (!indptr_host) { ctx->set_error("nnd_search_graph_fetch: null argument"); return 1; }
     return nnd_search_graph_fetch_impl(ctx, indptr_host, indices_host);
 }
+extern "C" int32_t nnd_search_graph_device(nnd_handle_t ctx, const int32_t **indptr_dev, const int32_t **indices_dev, int64_t *nnz) {
+    ENTER(ctx, 0);
+    if (!indptr_dev || !indices_dev || !nnz) { ctx->set_error("nnd_search_graph_device: null argument"); return 1; }
+    return nnd_search_graph_device_impl(ctx, indptr_dev, indices_dev, nnz);
+}
 
 // ---- hub search tree of NNDescent.prepare() (reference rp_trees.py:714-1312, 2926-3049; host glue: search_tree.py) ----
 extern "C" int32_t nnd_hub_tree_build(nnd_handle_t ctx, const int32_t *rank_order /* host (n): ids by (-in-degree, id) */,
                                       int32_t leaf_size, int32_t max_depth, int64_t *n_nodes_out) {
     ENTER(ctx, NEED_DATA);
     if (!rank_order) { ctx->set_error("nnd_hub_tree_build: null rank order"); return 1; }
-    if (nnd_hub_tree_build_impl(ctx, rank_order, leaf_size, max_depth, nnd_metric_unit(ctx->p.metric))) return 1;
+    if (nnd_hub_tree_build_impl(ctx, rank_order, false, leaf_size, max_depth, nnd_metric_unit(ctx->p.metric))) return 1;
+    if (n_nodes_out) *n_nodes_out = nnd_hub_tree_nodes(ctx);
+    return 0;
+}
+extern "C" int32_t nnd_hub_tree_build_device(nnd_handle_t ctx, const int32_t *rank_order_dev /* device (n) */, int32_t leaf_size, int32_t max_depth,
+                                             int64_t *n_nodes_out) {
+    ENTER(ctx, NEED_DATA);
+    if (!rank_order_dev) { ctx->set_error("nnd_hub_tree_build_device: null rank order"); return 1; }
+    if (nnd_hub_tree_build_impl(ctx, rank_order_dev, true, leaf_size, max_depth, nnd_metric_unit(ctx->p.metric))) return 1;
     if (n_nodes_out) *n_nodes_out = nnd_hub_tree_nodes(ctx);
     return 0;
 }

@@ -1,5 +1,6 @@
 // devarray.hip -- what a caller whose arrays live on the device needs around the build and the search: typed rows (float16 /
-// bfloat16 / float64 / float32) -> the float32 rows every kernel reads, dot's row normalisation, and the corrections
+// bfloat16 / float64 / float32) -> the float32 rows every kernel reads (in place of the rows, or gathered by a permutation into
+// the searcher's padded layout: prepare() of a device-built index), dot's row normalisation, and the corrections
 // NNDescent.neighbor_graph / query apply to the kernels' distances (pynndescent_.py:1271-1298), all without a host round trip.
 // The two exported entries take a device ordinal and a stream instead of a handle: a graph is corrected long after its builder
 // is gone, and a query batch is converted before any searcher sees it.
@@ -169,6 +170,63 @@ int nnd_launch_rows_f32(hipStream_t st, const void *src, int dtype, int64_t n, i
         if (hipGetLastError() != hipSuccess) return 1;
     }
     return 0;
+}
+
+// ---- gather: dst row i = float32 of src row order[i], in rows of dp >= d floats with zero fill (the searcher's layout) ----
+// 2^lpr_log2 lanes share a row (a whole wave for 256 floats and more, part of one below: 32 lanes at d = 128); a lane takes
+// every 2^lpr_log2-th chunk of the row.  VECSRC (d a multiple of the type's vector, base aligned): one aligned vector load of the
+// source per chunk, 16 bytes for float32 / binary16 / bfloat16; otherwise up to four element loads, the columns past d read as
+// zero.  The destination's 16-byte chunks are always aligned (dp is a multiple of 4 floats) and stored whole.  An entry of
+// `order` outside [0, n) (a caller's error) leaves its row unwritten: nothing is read out of bounds.
+template <typename T, bool VECSRC>
+__global__ __launch_bounds__(256) void k_gather_rows(const T *__restrict__ src, const int32_t *__restrict__ order, int64_t n, int d, int dp,
+                                                     int lpr_log2, float *__restrict__ dst) {
+    typedef conv_traits<T> tr;
+    constexpr int CH = VECSRC ? tr::VEC : 4;
+    const int lpr = 1 << lpr_log2, sub = (int)threadIdx.x & (lpr - 1);
+    const int64_t step = (int64_t)gridDim.x * (256 >> lpr_log2);
+    for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> lpr_log2; i < n; i += step) {
+        const int64_t r = order ? (int64_t)order[i] : i;
+        if (r < 0 || r >= n) continue;
+        const T *s = src + r * d;
+        float *o = dst + i * dp;
+        for (int c = sub; c * CH < dp; c += lpr) {
+            float v[CH];
+            if constexpr (VECSRC) {
+                tr::many(*(const typename tr::vec_t *)(s + c * CH), v);
+            } else {
+#pragma unroll
+                for (int q = 0; q < 4; q++) v[q] = c * 4 + q < d ? tr::one(s[c * 4 + q]) : 0.0f;
+            }
+#pragma unroll
+            for (int q = 0; q < CH; q += 4) *(float4 *)(o + c * CH + q) = make_float4(v[q], v[q + 1], v[q + 2], v[q + 3]);
+        }
+    }
+}
+template <typename T>
+static int gather_launch(hipStream_t st, const void *src, const int32_t *order, int64_t n, int d, int dp, float *dst) {
+    typedef conv_traits<T> tr;
+    const bool vec = d % tr::VEC == 0 && ((uintptr_t)src & 15) == 0;  // (then dp == d: every vector is 4 or 8 floats)
+    const int chunks = vec ? d / tr::VEC : dp / 4;
+    int lpr_log2 = 0;
+    while (lpr_log2 < 6 && (1 << lpr_log2) < chunks) lpr_log2++;
+    const int64_t rows_per_block = 256 >> lpr_log2;
+    int64_t blocks = (n + rows_per_block - 1) / rows_per_block;
+    if (blocks > 8192) blocks = 8192;  // (the kernel strides over the rest)
+    if (vec) hipLaunchKernelGGL((k_gather_rows<T, true>), dim3((unsigned)blocks), dim3(256), 0, st, (const T *)src, order, n, d, dp, lpr_log2, dst);
+    else hipLaunchKernelGGL((k_gather_rows<T, false>), dim3((unsigned)blocks), dim3(256), 0, st, (const T *)src, order, n, d, dp, lpr_log2, dst);
+    return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+int nnd_launch_gather_rows(hipStream_t st, const void *src, int dtype, const int32_t *order, int64_t n, int d, int dp, float *dst) {
+    if (n <= 0 || d <= 0) return 0;
+    if (dp < d || (dp & 3) || ((uintptr_t)dst & 15)) return 1;
+    switch (dtype) {
+        case NND_DTYPE_FLOAT32: return gather_launch<float>(st, src, order, n, d, dp, dst);
+        case NND_DTYPE_FLOAT16: return gather_launch<conv_f16>(st, src, order, n, d, dp, dst);
+        case NND_DTYPE_BFLOAT16: return gather_launch<conv_bf16>(st, src, order, n, d, dp, dst);
+        case NND_DTYPE_FLOAT64: return gather_launch<double>(st, src, order, n, d, dp, dst);
+        default: return 1;
+    }
 }
 
 // ---- corrections ----

@@ -287,7 +287,7 @@ struct nnd_hub_result {
         }                                                                                            \
     } while (0)
 
-int nnd_hub_tree_build_impl(nnd_ctx *ctx, const int32_t *rank_order_host, int leaf_size, int max_depth, int angular) {
+int nnd_hub_tree_build_impl(nnd_ctx *ctx, const int32_t *rank_order, bool rank_on_device, int leaf_size, int max_depth, int angular) {
     const int64_t n = ctx->n;
     const int d = ctx->d;
     int rc = 0;
@@ -321,7 +321,7 @@ int nnd_hub_tree_build_impl(nnd_ctx *ctx, const int32_t *rank_order_host, int le
         const int splittable = (n > leaf_size && max_depth > 0) ? 1 : 0;
         const unsigned gridN = (unsigned)((n + 255) / 256);
         hipLaunchKernelGGL(k_hub_init, dim3(gridN), dim3(256), 0, ctx->stream, ord_id[0], pos_id[0], pos_rk[0], n, splittable);
-        HUB_HIP(hipMemcpyAsync(ord_rk[0], rank_order_host, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+        HUB_HIP(hipMemcpyAsync(ord_rk[0], rank_order, sizeof(int32_t) * (size_t)n, rank_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
         const int32_t h0[2] = {0, (int32_t)n};
         const uint8_t hs = (uint8_t)splittable;
         HUB_HIP(hipMemcpyAsync(sst[0], &h0[0], 4, hipMemcpyHostToDevice, ctx->stream));

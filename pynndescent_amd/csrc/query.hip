@@ -39,6 +39,9 @@
 #include "devmem.h"
 #include "../../include/pynnd_amd.h"
 
+// devarray.hip: rows of NND_DTYPE_* `dtype` gathered by `order` (nullptr: identity) into float32 rows of dp floats, zero padded
+int nnd_launch_gather_rows(hipStream_t st, const void *src, int dtype, const int32_t *order, int64_t n, int d, int dp, float *dst);
+
 #define Q_FRONTIER 512   // frontier entries per query (LDS tier)
 #define Q_VISITED 4096   // visited-set slots per query (power of two; LDS tier)
 #define Q_VISITED_MAX 3400  // entries after which the LDS set counts as full
@@ -683,17 +686,50 @@ static int searcher_fill(nnd_searcher_s *s, const float *data, const int32_t *in
     return 0;
 }
 
-extern "C" int32_t nnd_searcher_create(nnd_searcher_t *out, int32_t device, int64_t n, int32_t dim, int32_t metric, const float *data,
-                                       const int32_t *indptr, const int32_t *indices, int64_t nnz, const float *hyperplanes,
-                                       const float *offsets, const int32_t *children, const int32_t *tree_indices, int64_t n_nodes,
-                                       float min_distance, int32_t n_neighbors, const int64_t *rng_state) {
-    auto fail = [&](const char *msg) {
-        snprintf(g_serr, sizeof(g_serr), "nnd_searcher_create: %s", msg);
+// the same state from device memory, on the caller's stream: rows gathered by `order` straight into the padded layout
+// (devarray.hip), the CSR copied device to device; the tree tables come from the host as above
+static int searcher_fill_device(nnd_searcher_s *s, const void *rows, int dtype, const int32_t *order, const int32_t *indptr, const int32_t *indices,
+                                const float *hyperplanes, const float *offsets, const int32_t *children, const int32_t *tree_indices, hipStream_t st) {
+    S_HIP(hipSetDevice(s->device));
+    S_HIP(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+    S_ALLOC(&s->x, (size_t)s->n * s->dp);
+    S_ALLOC(&s->xn2, (size_t)s->n);
+    S_ALLOC(&s->indptr, (size_t)(s->n + 1));
+    S_ALLOC(&s->indices, (size_t)s->nnz);
+    if (nnd_launch_gather_rows(st, rows, dtype, order, s->n, s->d, s->dp, s->x)) {
+        (void)hipGetLastError();
+        s->set_error("the rows' gather could not be launched (dtype %d)", dtype);
         return 1;
+    }
+    if (s->metric == NND_METRIC_ALT_DOT || s->metric == NND_METRIC_CORRELATION || s->metric == NND_METRIC_ALT_HELLINGER)
+        hipLaunchKernelGGL(k_searcher_prep_rows, dim3((unsigned)((s->n + 3) / 4)), dim3(256), 0, st, s->x, s->n, s->d, s->dp, s->metric);
+    hipLaunchKernelGGL(k_row_norm2, dim3((unsigned)((s->n + 3) / 4)), dim3(256), 0, st, s->x, s->n, s->dp, s->xn2);
+    S_HIP(hipGetLastError());
+    S_HIP(hipMemcpyAsync(s->indptr, indptr, sizeof(int32_t) * (size_t)(s->n + 1), hipMemcpyDeviceToDevice, st));
+    if (s->nnz > 0) S_HIP(hipMemcpyAsync(s->indices, indices, sizeof(int32_t) * (size_t)s->nnz, hipMemcpyDeviceToDevice, st));
+    if (s->n_nodes > 0) {
+        if (upload_padded(s, &s->hyper, hyperplanes, s->n_nodes, s->d, s->dp)) return 1;
+        S_ALLOC(&s->offsets, (size_t)s->n_nodes);
+        S_HIP(hipMemcpy(s->offsets, offsets, sizeof(float) * (size_t)s->n_nodes, hipMemcpyHostToDevice));
+        S_ALLOC(&s->children, 2 * (size_t)s->n_nodes);
+        S_HIP(hipMemcpy(s->children, children, sizeof(int32_t) * 2 * (size_t)s->n_nodes, hipMemcpyHostToDevice));
+        S_ALLOC(&s->tree_idx, (size_t)s->n);
+        S_HIP(hipMemcpy(s->tree_idx, tree_indices, sizeof(int32_t) * (size_t)s->n, hipMemcpyHostToDevice));
+    }
+    S_HIP(hipStreamSynchronize(st));  // the caller's buffers are free again, and the searcher's own stream may read what was written
+    return 0;
+}
+
+// what the two create entries share: the argument and device checks, and the searcher with its scalars set (nullptr: g_serr says why)
+static nnd_searcher_s *searcher_new(const char *who, bool args_ok, int32_t device, int64_t n, int32_t dim, int32_t metric, int64_t nnz,
+                                    bool tree_ok, int64_t n_nodes, float min_distance, int32_t n_neighbors, const int64_t *rng_state) {
+    auto fail = [&](const char *msg) -> nnd_searcher_s * {
+        snprintf(g_serr, sizeof(g_serr), "%s: %s", who, msg);
+        return nullptr;
     };
-    if (!out || !data || !indptr || !indices || n < 1 || dim < 1) return fail("bad arguments");
+    if (!args_ok || n < 1 || dim < 1 || nnz < 0) return fail("bad arguments");
     if (metric < NND_METRIC_SQEUCLIDEAN || metric > NND_METRIC_PROXY_INNER_PRODUCT) return fail("unknown metric");
-    if (n_nodes > 0 && (!hyperplanes || !offsets || !children || !tree_indices)) return fail("tree arrays missing");
+    if (n_nodes > 0 && !tree_ok) return fail("tree arrays missing");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail("no HIP device visible (this library has no CPU path)");
     if (device < 0 || device >= ndev) return fail("device out of range");
@@ -711,13 +747,40 @@ extern "C" int32_t nnd_searcher_create(nnd_searcher_t *out, int32_t device, int6
     s->n_neighbors = n_neighbors;
     s->min_distance = min_distance;
     s->seed = rng_state ? nnd_mix32((uint32_t)rng_state[0] ^ nnd_mix32((uint32_t)rng_state[1] + 0x9E3779B9u) ^ nnd_mix32((uint32_t)rng_state[2] + 0x7F4A7C15u)) : 1u;
-    if (searcher_fill(s, data, indptr, indices, hyperplanes, offsets, children, tree_indices)) {
-        snprintf(g_serr, sizeof(g_serr), "nnd_searcher_create: %s", s->err);
+    return s;
+}
+static int searcher_filled(const char *who, nnd_searcher_s *s, int rc, nnd_searcher_t *out) {
+    if (rc) {
+        snprintf(g_serr, sizeof(g_serr), "%s: %s", who, s->err);
         nnd_searcher_destroy(s);
         return 1;
     }
     *out = s;
     return 0;
+}
+
+extern "C" int32_t nnd_searcher_create(nnd_searcher_t *out, int32_t device, int64_t n, int32_t dim, int32_t metric, const float *data,
+                                       const int32_t *indptr, const int32_t *indices, int64_t nnz, const float *hyperplanes,
+                                       const float *offsets, const int32_t *children, const int32_t *tree_indices, int64_t n_nodes,
+                                       float min_distance, int32_t n_neighbors, const int64_t *rng_state) {
+    nnd_searcher_s *s = searcher_new("nnd_searcher_create", out && data && indptr && indices, device, n, dim, metric, nnz,
+                                     hyperplanes && offsets && children && tree_indices, n_nodes, min_distance, n_neighbors, rng_state);
+    if (!s) return 1;
+    return searcher_filled("nnd_searcher_create", s, searcher_fill(s, data, indptr, indices, hyperplanes, offsets, children, tree_indices), out);
+}
+
+extern "C" int32_t nnd_searcher_create_device(nnd_searcher_t *out, int32_t device, int64_t n, int32_t dim, int32_t metric, const void *rows_dev,
+                                              int32_t dtype, const int32_t *order_dev, const int32_t *indptr_dev, const int32_t *indices_dev,
+                                              int64_t nnz, const float *hyperplanes, const float *offsets, const int32_t *children,
+                                              const int32_t *tree_indices, int64_t n_nodes, float min_distance, int32_t n_neighbors,
+                                              const int64_t *rng_state, void *hip_stream) {
+    const bool args_ok = out && rows_dev && indptr_dev && (indices_dev || nnz == 0) && dtype >= NND_DTYPE_FLOAT32 && dtype <= NND_DTYPE_FLOAT64;
+    nnd_searcher_s *s = searcher_new("nnd_searcher_create_device", args_ok, device, n, dim, metric, nnz,
+                                     hyperplanes && offsets && children && tree_indices, n_nodes, min_distance, n_neighbors, rng_state);
+    if (!s) return 1;
+    return searcher_filled("nnd_searcher_create_device", s,
+                           searcher_fill_device(s, rows_dev, dtype, order_dev, indptr_dev, indices_dev, hyperplanes, offsets, children, tree_indices,
+                                                (hipStream_t)hip_stream), out);
 }
 
 extern "C" int64_t nnd_searcher_last_spilled(nnd_searcher_t s) { return s ? s->last_spilled : -1; }

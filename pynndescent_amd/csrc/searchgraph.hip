@@ -359,3 +359,12 @@ int nnd_search_graph_fetch_impl(nnd_ctx *ctx, int32_t *indptr_host, int32_t *ind
     NND_HIP_CHECK(nnd_sync_spin(ctx));
     return 0;
 }
+
+// the result where it lies (prepare() of a device-built index: the reorder kernels of prepare.hip read it in place)
+int nnd_search_graph_device_impl(nnd_ctx *ctx, const int32_t **indptr_dev, const int32_t **indices_dev, int64_t *nnz) {
+    if (!ctx->sg || !ctx->sg->out_ptr) { ctx->set_error("nnd_search_graph_device: no search graph has been built on this handle"); return 1; }
+    *indptr_dev = ctx->sg->out_ptr;
+    *indices_dev = ctx->sg->out_ind;
+    *nnz = ctx->sg->final_nnz;
+    return 0;
+}

@@ -343,7 +343,7 @@ int nnd_launch_degree_prune(nnd_ctx *ctx, const int32_t *indptr_dev, float *data
 void nnd_forest_stable_partition(nnd_ctx *ctx, int64_t n, const int32_t *ord, const int32_t *pos, uint8_t *side, const int32_t *seg_start,
                                  const int32_t *seg_len, int n_segs, int32_t *nleft, const int32_t *seg_child, int32_t *ord_out,
                                  int32_t *pos_out);
-int nnd_hub_tree_build_impl(nnd_ctx *ctx, const int32_t *rank_order_host, int leaf_size, int max_depth, int angular);
+int nnd_hub_tree_build_impl(nnd_ctx *ctx, const int32_t *rank_order, bool rank_on_device, int leaf_size, int max_depth, int angular);
 int nnd_hub_tree_fetch_impl(nnd_ctx *ctx, float *hyperplanes, float *offsets, int32_t *children, int32_t *indices, int32_t *max_leaf);
 int64_t nnd_hub_tree_nodes(const nnd_ctx *ctx);
 void nnd_hub_tree_free(nnd_ctx *ctx);
@@ -352,6 +352,10 @@ int nnd_search_graph_impl(nnd_ctx *ctx, const int32_t *idx_src, const float *dis
                           float diversify_prob, bool aware, float aggressiveness, uint32_t seed, int32_t *fwd_rows_host, float *fwd_dist_host,
                           nnd_search_graph_stats *st);
 int nnd_search_graph_fetch_impl(nnd_ctx *ctx, int32_t *indptr_host, int32_t *indices_host);
+int nnd_search_graph_device_impl(nnd_ctx *ctx, const int32_t **indptr_dev, const int32_t **indices_dev, int64_t *nnz);
+// prepare.hip: rows of NND_DTYPE_* `dtype` gathered by `order` (nullptr: identity) into float32 rows of dp >= d floats, zero
+// padded (current device, stream st): dst row i = src row order[i]
+int nnd_launch_gather_rows(hipStream_t st, const void *src, int dtype, const int32_t *order, int64_t n, int d, int dp, float *dst);
 // exact.hip: exact k nearest neighbours of `rows` of the point set (q == nullptr; rows == nullptr: all of them) or of the
 // external queries q (host (nq, d)); host outputs (nq, k)
 int nnd_exact_knn_impl(nnd_ctx *ctx, const int64_t *rows, const float *q, int64_t nq, int k, int32_t *out_idx, float *out_dist, nnd_exact_stats *st);

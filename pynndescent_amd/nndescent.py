@@ -227,6 +227,18 @@ class _OnTorchStream:
             self.current.wait_stream(self.side)
 
 
+def _stream_ms(torch, stream, fn):
+    """``fn()`` between two events on the stream of an ``_OnTorchStream``: (its result, the stream time in ms).  For calls that
+    return with the stream drained (the entries of csrc/prepare.hip, the searcher's fill): reading the time waits for nothing."""
+    on = stream.side or stream.current
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record(on)
+    out = fn()
+    e1.record(on)
+    e1.synchronize()
+    return out, float(e0.elapsed_time(e1))
+
+
 class _DeviceInput:
     """The device side of one single-GPU build (``_build_graph``): the caller's tensor in, the finished graph out as tensors."""
 
@@ -272,6 +284,37 @@ def _device_corrected(torch, dist, m, ordinal):
     return out
 
 
+class _DeviceRowsView:
+    """The rows of a device tensor for ``uint8_codebook``: its shape, and ``view[rows]`` -- the sample, gathered on the device with
+    torch indexing and brought to the host as float32 (at most 10 000 rows cross the bus, in the order asked for)."""
+
+    def __init__(self, tensor):
+        self.tensor, self.shape = tensor, tuple(tensor.shape)
+
+    def __getitem__(self, rows):
+        torch = _torch()
+        at = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int64)).to(self.tensor.device)
+        return np.ascontiguousarray(self.tensor.detach()[at].float().cpu().numpy())
+
+
+def _prepares_on_device(index):
+    """Whether ``prepare()`` of ``index`` runs from its device tensors (``NNDescent._init_search_graph_device``): an index built
+    from a device array on one GPU that still holds its rows and its graph there, a graph within the device pass's edge
+    positions, and no reason to go through the host -- the ``_host_prepare`` switch, or dot with uint8 codes (they are the codes
+    of rows other than the searcher's own copy).  Reads ``__dict__`` only: no host mirror is fetched by asking."""
+    from .search_graph import DEVICE_PASS_MAX_EDGES
+
+    d = index.__dict__
+    if d.get("_host_prepare", getattr(type(index), "_host_prepare", False)):
+        return False
+    if "_device_data" not in d or "_device_graph" not in d or int(d.get("n_devices", 1)) != 1:
+        return False
+    if d.get("quantization") == "uint8" and _METRICS[d["metric"]].normalize:
+        return False
+    n, k = (int(v) for v in d["_device_graph"][0].shape)
+    return 2 * n * k < DEVICE_PASS_MAX_EDGES
+
+
 class _DeviceForestSentinel:
     """Stands in for ``_rp_forest``: downstream reference code only null-checks it
     (pynndescent_.py:1353) -- the build consumes nothing but the leaf array."""
@@ -285,6 +328,11 @@ class _DeviceForestSentinel:
 
 class NNDescent:
     """See ``pynndescent.NNDescent``; constructor signature identical (pynndescent_.py:976-1007)."""
+
+    # the host-path switch of prepare(): set ``index._host_prepare = True`` on an index built from a device array and its
+    # prepare() takes the path of a host-built index (mirrors fetched, scipy reorder, three uploads) -- tests and
+    # tools/ab/device_prepare_timing.py compare the two paths on one and the same graph with it
+    _host_prepare = False
 
     def __init__(
         self,
@@ -331,11 +379,14 @@ class NNDescent:
         precision and float64 are converted to float32 on the device; a float32 tensor is kept by reference, not copied).
         The index then runs on the tensor's device and on torch's current stream: data queued on that stream needs no
         synchronisation, and ``neighbor_graph`` / ``query(device array)`` return tensors there, corrected on the device.
-        ``_raw_data`` and ``_neighbor_graph`` are host mirrors fetched on first use; ``prepare``, ``update``, ``recall``,
-        ``build_search_graph``, pickling and ``to_reference`` work through them.  Out of scope: ``exact_knn`` / ``recall`` without
-        the host mirror; device ``init_graph`` / ``init_dist`` (converted with ``.cpu().numpy()``); a ``prepare()`` that stays off
-        the host; producers other than torch (``__cuda_array_interface__``, DLPack); and a sharded build from device memory --
-        with ``n_devices`` > 1 the rows are brought to the host first and the index is a host index, as for host input."""
+        ``prepare()`` -- and so the first ``query()`` -- runs from those tensors too (hub rank, tree, pruning pass, reorder and
+        the searcher's fill on the device: only the tree's tables, ``_vertex_order`` and scalars cross the bus; dot with
+        ``quantization="uint8"`` takes the host path).  ``_raw_data``, ``_neighbor_graph``, ``_search_graph`` and
+        ``_quantized_data`` are host mirrors fetched on first use; ``update``, ``recall``, ``build_search_graph``, pickling and
+        ``to_reference`` work through them.  Out of scope: ``exact_knn`` / ``recall`` without the host mirror; device
+        ``init_graph`` / ``init_dist`` (converted with ``.cpu().numpy()``); the hub tree's FlatTree assembly on the device;
+        producers other than torch (``__cuda_array_interface__``, DLPack); and a sharded build from device memory -- with
+        ``n_devices`` > 1 the rows are brought to the host first and the index is a host index, as for host input."""
         dev_checked = None
         if _is_device_array(data):  # dtype, shape and device first: before any device work, and before the shape is read
             dev_checked = _check_device_array(data, device)
@@ -523,13 +574,28 @@ class NNDescent:
 
     def __getattr__(self, name):
         """The host mirrors of an index built from a device array, fetched on first access and cached: ``_raw_data`` (float32
-        numpy rows; dot: the normalised rows the device computed) and ``_neighbor_graph`` (numpy int32 / float32).  Every line
-        that reads the two names finds them as on a host-built index, and ``hasattr`` keeps its meaning."""
+        numpy rows; dot: the normalised rows the device computed; after a device prepare: in the search tree's leaf order, as
+        the host path leaves them) and ``_neighbor_graph`` (numpy int32 / float32); after a device prepare also ``_search_graph``
+        (scipy CSR uint8, sorted indices) and ``_quantized_data`` (the searcher's uint8 codes).  Every line that reads the names
+        finds them as on a host-built index, and ``hasattr`` keeps its meaning."""
         d = self.__dict__
         if name == "_raw_data" and "_device_data" in d:
-            value = np.ascontiguousarray(d["_device_data"].detach().float().cpu().numpy())
+            rows = d["_device_data"].detach()
+            if "_device_order" in d:  # x_new[i] = x[order[i]]: the gather the searcher's fill makes
+                rows = rows[d["_device_order"].long()]
+            value = np.ascontiguousarray(rows.float().cpu().numpy())
         elif name == "_neighbor_graph" and "_device_graph" in d:
             value = tuple(np.ascontiguousarray(t.cpu().numpy()) for t in d["_device_graph"])
+        elif name == "_search_graph" and "_device_search_graph" in d:
+            import scipy.sparse as sp
+
+            indptr, indices = (np.ascontiguousarray(t.cpu().numpy()) for t in d["_device_search_graph"])
+            n = indptr.shape[0] - 1
+            value = sp.csr_array((np.ones(indices.shape[0], np.uint8), indices, indptr), shape=(n, n))
+            value.has_sorted_indices = True
+        elif (name == "_quantized_data" and "_device_search_graph" in d and d.get("_searcher") is not None
+              and d["_searcher"].has_codes):  # the codes the searcher derived from its own rows, deterministic: derived again
+            value = d["_searcher"].quantize_u8(d["_quantized_values"], rows=None)
         else:
             raise AttributeError("%r object has no attribute %r" % (type(self).__name__, name))
         d[name] = value
@@ -537,8 +603,14 @@ class NNDescent:
 
     def _drop_device_copies(self):
         """After the host mirrors have become the truth (``update()``), or for a pickle: the device tensors go."""
-        for name in ("_device_graph", "_device_data"):
+        for name in ("_device_graph", "_device_data", "_device_order", "_device_search_graph", "_device_prepare_stats"):
             self.__dict__.pop(name, None)
+
+    @property
+    def _prepared(self):
+        """Whether ``_init_search_graph`` has run (``_vertex_order`` is set eagerly on both paths).  Looks at ``__dict__``: asking
+        fetches no host mirror."""
+        return "_vertex_order" in self.__dict__
 
     @staticmethod
     def _recall_rows(n, n_rows, random_state):
@@ -569,7 +641,7 @@ class NNDescent:
         runs the same pass and then re-indexes everything by the hub search tree's leaf order)."""
         from .search_graph import build_search_graph
 
-        if hasattr(self, "_vertex_order"):
+        if self._prepared:
             raise RuntimeError("the index is prepared already: its search graph is index._search_graph (in leaf order)")
         self._pruned_graph = build_search_graph(
             self._raw_data, self._neighbor_graph[0], self._neighbor_graph[1], self.metric, self.n_neighbors,
@@ -659,6 +731,13 @@ class NNDescent:
                             else (self.leaf_size if self.leaf_size is not None else 30))  # pynndescent_.py:1341-1345
         search_tree_depth = (self.max_search_tree_depth if self.max_search_tree_depth is not None
                              else self.max_rptree_depth)                                   # pynndescent_.py:1346-1350
+        if _prepares_on_device(self):
+            try:
+                return self._init_search_graph_device(search_leaf_size, search_tree_depth)
+            except _capi.NNDError as e:
+                if "memory" not in str(e).lower():
+                    raise
+                warn("the search-graph pass does not fit the device (%s): preparing through the host" % e)
         if not hasattr(self, "_search_forest"):
             if getattr(self, "_rp_forest", None) is None and not self.tree_init:
                 self._search_forest = []  # pynndescent_.py:1377-1378: no tree, queries start from random vertices
@@ -694,6 +773,100 @@ class NNDescent:
             del self._neighbor_graph
             self.__dict__.pop("_device_graph", None)
 
+    def _init_search_graph_device(self, search_leaf_size, search_tree_depth):
+        """``_init_search_graph`` from the device tensors of an index built from a device array, on torch's current stream
+        (``_OnTorchStream``): the in-degrees and the hub rank (csrc/prepare.hip), the hub tree and the pruning pass on handles
+        bound to the tensor, the graph re-indexed by the tree's leaf order where the pass left it.  The rows and the graphs
+        never visit the host and no host mirror is made; what crosses the bus: the FlatTree tables, ``_vertex_order`` (4 bytes
+        per point, down and up again) and scalars.  The rows are gathered when the searcher is filled (``prepare``);
+        ``_device_data`` stays the caller's tensor in its original order."""
+        from .search_tree import FlatTree
+
+        if self.diversify_method not in ("standard", "degree_aware"):
+            raise ValueError("diversify_method must be 'standard' or 'degree_aware'")
+        torch, d, m = _torch(), self.__dict__, _METRICS[self.metric]
+        data, (gidx, gdist) = d["_device_data"], d["_device_graph"]
+        n, dim, k = int(data.shape[0]), int(data.shape[1]), int(gidx.shape[1])
+        dtype, ordinal = _DEVICE_DTYPES[str(data.dtype).rsplit(".", 1)[-1]], int(self.device)
+        seed = int(self.rng_state[0])
+        ms = {}  # stream time of every stage (tools/ab/device_prepare_timing.py reads them)
+
+        def bound(builder, stream):  # dot: _device_data is the normalised float32 copy already, borrowed as it is
+            builder.set_stream(stream.ptr)
+            if m.normalize:
+                builder.set_data_device(data.data_ptr(), keepalive=data)
+            else:
+                builder.set_data_device_typed(data.data_ptr(), dtype, keepalive=data)
+            return builder
+
+        with torch.cuda.device(ordinal):
+            if "_search_forest" not in d:
+                if getattr(self, "_rp_forest", None) is None and not self.tree_init:
+                    self._search_forest = []  # pynndescent_.py:1377-1378: no tree, queries start from random vertices
+                else:
+                    if self.verbose:
+                        print(ts(), "Building hub-based search tree")
+                    stream = _OnTorchStream(torch, ordinal)
+                    b = None
+                    try:
+                        rank = torch.empty((n,), dtype=torch.int32, device=data.device)
+                        _, ms["ms_rank"] = _stream_ms(torch, stream, lambda: _capi.rank_order_device(
+                            ordinal, stream.ptr, gidx.data_ptr(), n, k, rank.data_ptr()))
+                        b = _capi.Builder(n, dim, m.code, 1, 1, max(int(search_leaf_size), 1), search_tree_depth, 1, 1, 0.001,
+                                          [seed & 0x7FFFFFFF, 2, 3], [4, 5, 6], device=ordinal,
+                                          flags=_capi.NND_FLAG_NO_GRAPH | _capi.NND_FLAG_NO_PREP)
+                        tables, ms["ms_hub_tree"] = _stream_ms(torch, stream, lambda: bound(b, stream).hub_tree_device(
+                            rank.data_ptr(), search_leaf_size, search_tree_depth))
+                        self._search_forest = [FlatTree(*tables)]
+                    finally:
+                        if b is not None:
+                            b.close()
+                        stream.done()
+                    self._rp_forest = None  # the reference deletes it here (pynndescent_.py:1444)
+            order = None
+            if self._search_forest:  # the leaf order goes up once; the queries' id mapping reads the same tensor
+                tree = self._search_forest[0]
+                vertex_order = np.asarray(tree.indices)
+                order = torch.from_numpy(np.ascontiguousarray(vertex_order, dtype=np.int32)).to(data.device)
+            if self.verbose:
+                print(ts(), "Diversifying and pruning the search graph")
+            stream = _OnTorchStream(torch, ordinal)  # (made after the upload: a side stream waits for it)
+            b = None
+            try:
+                b = bound(_capi.Builder(n, dim, m.code, k, 0, 60, 200, min(60, k), 1, 0.001, [1, 2, 3], [4, 5, 6], device=ordinal,
+                                        flags=_capi.NND_FLAG_NO_GRAPH), stream)
+                indptr_at, indices_at, nnz, st = b.search_graph_device(
+                    gidx.data_ptr(), gdist.data_ptr(), self.n_neighbors, self.prune_degree_multiplier, self.diversify_prob,
+                    self.diversify_method == "degree_aware", self.degree_prune_aggressiveness, seed & 0xFFFFFFFF)
+                if self.verbose:
+                    print(ts(), "Resorting data and graph based on tree order")
+                indptr = torch.empty((n + 1,), dtype=torch.int32, device=data.device)
+                indices = torch.empty((nnz,), dtype=torch.int32, device=data.device)
+                _, ms["ms_reorder"] = _stream_ms(torch, stream, lambda: _capi.reorder_csr_device(
+                    ordinal, stream.ptr, 0 if order is None else order.data_ptr(), n, indptr_at, indices_at, nnz, indptr.data_ptr(),
+                    indices.data_ptr() if nnz else 0))
+            finally:
+                if b is not None:
+                    b.close()
+                stream.done()
+        self._min_distance = np.float32(float(st["min_distance"]))                  # pynndescent_.py:1539
+        self._visited = np.zeros((n // 8) + 1, dtype=np.uint8, order="C")           # pynndescent_.py:1624-1626
+        if order is not None:
+            self._vertex_order = vertex_order
+            self._device_order = order
+            new_tree = FlatTree(tree.hyperplanes, tree.offsets, tree.children, np.arange(n, dtype=np.int32), tree.leaf_size)
+            self._search_forest = [new_tree] + list(self._search_forest[1: self.n_search_trees])
+        else:
+            self._vertex_order = np.arange(n)
+        d.pop("_raw_data", None)  # (a mirror fetched before: the rows in their original order; the next read gathers them)
+        self._device_search_graph = (indptr, indices)
+        self._device_prepare_stats = dict(ms, ms_search_graph=float(st["ms_device"]), final_nnz=int(nnz))
+        self._searcher = None
+        if self.compressed:  # pynndescent_.py:1653-1658
+            d.pop("_rp_forest", None)
+            d.pop("_neighbor_graph", None)
+            d.pop("_device_graph", None)
+
     def prepare(self):
         """``NNDescent.prepare`` (pynndescent_.py:2174-2273): build everything a query needs.  quantization="uint8": the
         codebook is drawn on the host from the rows in their original order, the device quantizes the searcher's rows, and
@@ -702,24 +875,57 @@ class NNDescent:
         _check_quantization(self.quantization, self.metric)
         quantized = self.quantization == "uint8"
         self._is_proxy_distance = quantized or _METRICS[self.metric].proxy
-        fresh = not hasattr(self, "_search_graph")
-        if quantized and (fresh or getattr(self, "_quantized_values", None) is None):
-            raw = self._raw_data if fresh else self._raw_data[np.argsort(self._vertex_order)]
+        d = self.__dict__
+        fresh = not self._prepared
+        if quantized and (fresh or d.get("_quantized_values") is None):
+            if "_device_search_graph" in d or (fresh and _prepares_on_device(self)):  # the sample is gathered on the device
+                raw = _DeviceRowsView(d["_device_data"])
+            else:
+                raw = self._raw_data if fresh else self._raw_data[np.argsort(self._vertex_order)]
             self._quantized_values = uint8_codebook(raw, self.random_state)
             self._quantized_data = None  # derived by the device below, in the searcher's order
         if fresh:
             self._init_search_graph()
-        if getattr(self, "_searcher", None) is None:
+        on_device = "_device_search_graph" in d and "_device_data" in d
+        if d.get("_searcher") is None:
             tree = self._search_forest[0] if self._search_forest else None
-            self._searcher = _capi.Searcher(self._raw_data, self._search_graph, tree, _METRICS[self.metric].code,
-                                            self._min_distance, self.n_neighbors, self.search_rng_state, device=self.device)
+            if on_device:
+                self._searcher = self._searcher_from_device(tree)
+            else:
+                self._searcher = _capi.Searcher(self._raw_data, self._search_graph, tree, _METRICS[self.metric].code,
+                                                self._min_distance, self.n_neighbors, self.search_rng_state, device=self.device)
         if quantized and not self._searcher.has_codes:
-            if getattr(self, "_quantized_data", None) is None:
+            if d.get("_quantized_data") is None:
                 # dot: the searcher's own copy is normalised once more on the device; the codes are those of _raw_data
                 rows = self._raw_data if _METRICS[self.metric].normalize else None
-                self._quantized_data = self._searcher.quantize_u8(self._quantized_values, rows=rows)
+                if on_device and rows is None:  # the codes stay with the searcher; _quantized_data is their mirror, fetched when read
+                    self._searcher.quantize_u8(self._quantized_values, rows=None, fetch=False)
+                    d.pop("_quantized_data", None)
+                else:
+                    self._quantized_data = self._searcher.quantize_u8(self._quantized_values, rows=rows)
             else:
                 self._searcher.set_codes_u8(self._quantized_values, self._quantized_data)
+
+    def _searcher_from_device(self, tree):
+        """The searcher of a device-prepared index, filled on torch's current stream from the caller's tensor (its rows gathered by
+        the leaf order straight into the searcher's layout), the reordered device graph and the host tree tables."""
+        torch, d = _torch(), self.__dict__
+        data, (indptr, indices), order = d["_device_data"], d["_device_search_graph"], d.get("_device_order")
+        ordinal = int(self.device)
+        with torch.cuda.device(ordinal):
+            stream = _OnTorchStream(torch, ordinal)
+            try:
+                searcher, ms = _stream_ms(torch, stream, lambda: _capi.Searcher.from_device(
+                    data.data_ptr(), _DEVICE_DTYPES[str(data.dtype).rsplit(".", 1)[-1]], data.shape[0], data.shape[1],
+                    0 if order is None else order.data_ptr(), indptr.data_ptr(), indices.data_ptr() if indices.numel() else 0,
+                    indices.numel(), tree, _METRICS[self.metric].code, self._min_distance, self.n_neighbors, self.search_rng_state,
+                    device=ordinal, stream_ptr=stream.ptr))
+                d.setdefault("_device_prepare_stats", {})["ms_searcher_fill"] = ms
+            finally:
+                stream.done()
+        if order is not None:
+            searcher.vertex_order_device = order  # what _query_device maps the answers' ids through
+        return searcher
 
     def query(self, query_data, k=10, epsilon=0.1, proxy_beam_size=4):
         """``NNDescent.query`` (pynndescent_.py:2275-2379) on the GPU: one wave per query (csrc/query.hip).
@@ -734,14 +940,14 @@ class NNDescent:
         search_k = k
         if self.quantization is not None or m.proxy:  # pynndescent_.py:2309-2312
             search_k = _proxy_search_k(k, proxy_beam_size)
-        if (not hasattr(self, "_search_graph") or getattr(self, "_searcher", None) is None
+        if (not self._prepared or getattr(self, "_searcher", None) is None
                 or (self.quantization is not None and not self._searcher.has_codes)):
             self.prepare()
         if _is_device_array(query_data):
             return self._query_device(query_data, m, k, search_k, epsilon)
         query_data = np.asarray(query_data).astype(np.float32, order="C")  # pynndescent_.py:2316
-        if query_data.ndim != 2 or query_data.shape[1] != self._raw_data.shape[1]:
-            raise ValueError("query_data must have shape (n_queries, %d)" % self._raw_data.shape[1])
+        if query_data.ndim != 2 or query_data.shape[1] != self.dim:
+            raise ValueError("query_data must have shape (n_queries, %d)" % self.dim)
         _raise_if_negative_host(query_data, m)
         if self.quantization is not None:  # the walk on the codes, the rerank in its epilogue (pynndescent_.py:2321-2322, 2363-2371)
             indices, dists = self._searcher.query_proxy(query_data, k, search_k, epsilon + 1e-32)
@@ -761,7 +967,7 @@ class NNDescent:
         q, dtype, ordinal = _check_device_array(q, what="query_data")
         if ordinal != int(self.device):
             raise ValueError("query_data is on device %d, the index on device %d" % (ordinal, int(self.device)))
-        nq, dim = int(q.shape[0]), int(self._raw_data.shape[1])
+        nq, dim = int(q.shape[0]), int(self.dim)
         if q.shape[1] != dim:
             raise ValueError("query_data must have shape (n_queries, %d)" % dim)
         with torch.cuda.device(ordinal):
@@ -795,14 +1001,15 @@ class NNDescent:
     # ------------------------------------------------------------------------------------------------ pickling
     def __getstate__(self):
         """pynndescent_.py:1306-1320: a pickled index is a PREPARED index; device handles and the build forest stay behind."""
-        if not hasattr(self, "_search_graph"):
+        if not self._prepared:
             self._init_search_graph()
         if "_device_data" in self.__dict__ or "_device_graph" in self.__dict__:  # the host mirrors travel, the tensors stay
             self._raw_data
-            hasattr(self, "_neighbor_graph")
+            for name in ("_neighbor_graph", "_search_graph", "_quantized_data"):
+                hasattr(self, name)
         state = self.__dict__.copy()
-        state.pop("_device_graph", None)
-        state.pop("_device_data", None)
+        for name in ("_device_graph", "_device_data", "_device_order", "_device_search_graph", "_device_prepare_stats"):
+            state.pop(name, None)
         state.pop("_rp_forest", None)
         state.pop("_searcher", None)
         state["_search_forest"] = tuple(tuple(t) for t in self._search_forest)  # rp_trees.py:3060-3069 denumbaify_tree
@@ -889,10 +1096,9 @@ class NNDescent:
                 old_graph=(pad_i, pad_d), verbose=self.verbose)
         self._rp_forest = _DeviceForestSentinel(self.n_trees, n_leaves, eff_leaf_size)
         self._raw_data = raw
-        if hasattr(self, "_search_graph"):  # pynndescent_.py:2538-2553: the derived structures are rebuilt
+        if self._prepared:  # pynndescent_.py:2538-2553: the derived structures are rebuilt
             for name in ("_search_graph", "_search_forest", "_vertex_order", "_searcher"):
-                if hasattr(self, name):
-                    delattr(self, name)
+                self.__dict__.pop(name, None)
             self.prepare()
 
 

@@ -4,6 +4,9 @@ Mirrors ``make_hub_tree`` + ``convert_tree_format`` (reference rp_trees.py:714-1
 ``_init_search_graph`` (pynndescent_.py:1436-1449, 1629-1651).  The tree is built on the GPU (csrc/hubtree.hip, entry
 points ``nnd_hub_tree_build`` / ``nnd_hub_tree_fetch``); what stays on the host is what the reference does with
 numpy / scipy too: the in-degree bincount, the (-degree, id) order, fancy-indexing the data and the CSR graph.
+An index built from a device array does not come through here: its rank order, reorder and gather run on the device
+(csrc/prepare.hip, ``NNDescent._init_search_graph_device``) and give the same arrays; ``reorder_by_tree`` is their reference in
+tests/test_gpu_device_prepare.py.
 """
 from collections import namedtuple
 
