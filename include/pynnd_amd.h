@@ -213,6 +213,35 @@ int32_t nnd_device_rows_f32(int32_t device, void *hip_stream, const void *src_de
 #define NND_CORRECT_ALT_INNER_PRODUCT 3 /* float64 out: d >= FLT_MAX ? 0 : -1 / d (an IEEE division: the host's bits) */
 #define NND_CORRECT_ALT_HELLINGER 4     /* float64 out: sqrt(1 - 2^-d) */
 int32_t nnd_device_correct(int32_t device, void *hip_stream, int32_t kind, const float *in_dev, void *out_dev, int64_t count);
+/* ---- NNDescent.update() / recall() of an index whose rows and graph live on the device (csrc/devarray.hip, csrc/update.hip;
+ * DESIGN.md "Device arrays") ----  Like the two entries above: a device ordinal and a HIP stream (NULL: the device's default
+ * stream) instead of a handle, everything is queued there and nothing is waited for; every array is the caller's and must stay
+ * valid until the stream has passed the call.
+ *
+ * nnd_device_update_rows: the grown point set (pynndescent_.py:2461-2476).  out_dev: (n_old + n_fresh, dim) rows of out_dtype,
+ * 16-byte aligned.  Rows [0, n_old) = old_dev, rows [n_old, ..) = fresh_dev, then row upd_ids_dev[i] = row upd_rows_dev[i] of
+ * upd_dev ((n_upd, dim)) for the n_pairs pairs; the ids of the pairs must be distinct and in [0, n_old) (the host resolves
+ * duplicates and negative ids first; a pair out of range is skipped).  Each of the three inputs has an NND_DTYPE_* of its own
+ * (ignored where its count is 0).  out_dtype is either the one type all inputs share -- then no value is converted -- or
+ * NND_DTYPE_FLOAT32: binary16 / bfloat16 widen exactly, float64 rounds to nearest even (nnd_set_data_device_typed's conversion).
+ * Nothing is normalised. */
+int32_t nnd_device_update_rows(int32_t device, void *hip_stream, int32_t dim, const void *old_dev, int32_t old_dtype, int64_t n_old,
+                               const void *fresh_dev, int32_t fresh_dtype, int64_t n_fresh, const void *upd_dev, int32_t upd_dtype,
+                               int64_t n_upd, const int32_t *upd_rows_dev, const int32_t *upd_ids_dev, int64_t n_pairs, void *out_dev,
+                               int32_t out_dtype);
+/* nnd_device_update_graph: the invalidated, padded graph of the warm start (pynndescent_.py:2478-2493).  idx_dev / dist_dev: the
+ * old (n_old, k) graph; upd_ids_dev: the n_upd ids of the updated points (in [0, n_old); repeats allowed); map_dev: n_old bytes
+ * of scratch (the "is updated" lookup, written here).  out_idx_dev / out_dist_dev, (n_new, k) with n_new >= n_old: the rows of
+ * updated points, every entry that points at one (cleared in place) and the rows from n_old on are (-1, +inf); every other entry
+ * is copied. */
+int32_t nnd_device_update_graph(int32_t device, void *hip_stream, const int32_t *idx_dev, const float *dist_dev, int64_t n_old, int32_t k,
+                                const int32_t *upd_ids_dev, int64_t n_upd, int64_t n_new, uint8_t *map_dev, int32_t *out_idx_dev,
+                                float *out_dist_dev);
+/* nnd_device_recall_hits: *hits_dev (one int64 on the device, zeroed here) = the number of entries of true_idx_dev ((m, k),
+ * k <= 256) that appear in row rows_dev[i] of graph_idx_dev ((n, width), width <= 256) -- sum(isin(true[i], graph[rows[i]])).
+ * One wave per sampled row. */
+int32_t nnd_device_recall_hits(int32_t device, void *hip_stream, const int32_t *true_idx_dev, int64_t m, int32_t k, const int32_t *graph_idx_dev,
+                               int64_t n, int32_t width, const int32_t *rows_dev, int64_t *hits_dev);
 /* *out = 1 when the point set held a NaN or an infinity (seen by the prep kernel while it read the rows).  The reference
  * rejects such input in check_array (pynndescent_.py:1054) with a scan of its own; the host mirror raises the same
  * error from this flag instead of scanning 488 MB on one core (24 ms at 1 M x 128). */
@@ -246,6 +275,13 @@ int32_t nnd_init_from_graph(nnd_handle_t h, const int32_t *init_idx, const float
  * (pynndescent_.py:2512-2517): the entries of an existing graph -- host (n, width) indices (-1 = none) and
  * alt-space distances (required) -- are inserted with flag 0 ("old").  Call after nnd_reset_graph. */
 int32_t nnd_init_from_neighbor_graph(nnd_handle_t h, const int32_t *init_idx, const float *init_dist, int32_t width);
+/* The two entries above for a graph on the handle's device: DEVICE pointers to the full (n, width) int32 ids and float32
+ * distances (init_dist_dev nullable for nnd_init_from_graph_device, required for the neighbour-graph form), read in place on the
+ * handle's stream (nnd_set_stream: the caller's), nothing is staged.  The arrays stay the caller's and must remain valid until
+ * the stream has passed the call; nnd_init_from_graph_device returns without waiting, nnd_init_from_neighbor_graph_device
+ * returns with the stream drained, as its host form does. */
+int32_t nnd_init_from_graph_device(nnd_handle_t h, const int32_t *init_idx_dev, const float *init_dist_dev, int32_t width);
+int32_t nnd_init_from_neighbor_graph_device(nnd_handle_t h, const int32_t *init_idx_dev, const float *init_dist_dev, int32_t width);
 
 /* One iteration of nn_descent_internal (pynndescent_.py:296-320):
  * new_build_candidates (utils.py:221-320) + generate_graph_update_array (utils.py:536-658)
@@ -424,6 +460,16 @@ int32_t nnd_exact_knn_rows(nnd_handle_t h, const int64_t *rows, int64_t n_rows, 
 /* external queries, host float32 (n_q, dim): prepared with the point set's transform (code 0: the SET's column means) */
 int32_t nnd_exact_knn_queries(nnd_handle_t h, const float *q, int64_t n_q, int32_t k,
                               int32_t *out_idx, float *out_dist, nnd_exact_stats *st);
+/* The two entries above for a caller on the handle's device, on the handle's stream (nnd_set_stream: the caller's).  rows_dev:
+ * int32 ids on the device (NULL = all n; an id outside [0, n) is an error, found on the device as the ids enter their batch and reported with that batch).  q_dev: (n_q, dim)
+ * queries of `dtype` (NND_DTYPE_*), converted into each batch's own float32 copy (NND_METRIC_ALT_DOT: and L2-normalised, as
+ * nnd_set_data_device_typed normalises the rows).  out_idx_dev / out_dist_dev: DEVICE (m, k) arrays, written device to device.
+ * All arrays stay the caller's; the call returns with the stream drained (one scalar per batch, the count of uncertified rows,
+ * crosses the bus in any case). */
+int32_t nnd_exact_knn_rows_device(nnd_handle_t h, const int32_t *rows_dev, int64_t n_rows, int32_t k,
+                                  int32_t *out_idx_dev, float *out_dist_dev, nnd_exact_stats *st /* may be NULL */);
+int32_t nnd_exact_knn_queries_device(nnd_handle_t h, const void *q_dev, int32_t dtype, int64_t n_q, int32_t k,
+                                     int32_t *out_idx_dev, float *out_dist_dev, nnd_exact_stats *st);
 /* data slices the scan splits the point set into when n_rows query rows are asked for (a function of the shapes alone: few
  * query blocks -> many slices, so that the chip is filled); tests */
 int32_t nnd_exact_slice_count(nnd_handle_t h, int64_t n_rows);

@@ -197,6 +197,12 @@ _SIGNATURES = [
     ("nnd_set_data_device_typed", C.c_int32, [_H, C.c_void_p, C.c_int32]),
     ("nnd_device_rows_f32", C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
     ("nnd_device_correct", C.c_int32, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64]),
+    ("nnd_device_update_rows", C.c_int32, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int64,
+                                           C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32]),
+    ("nnd_device_update_graph", C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int64,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("nnd_device_recall_hits", C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
+                                           C.c_void_p]),
     ("nnd_data_nonfinite", C.c_int32, [_H, C.POINTER(C.c_int32)]),
     ("nnd_data_negative", C.c_int32, [_H, C.POINTER(C.c_int32)]),
     ("nnd_release_pending", C.c_int32, []),
@@ -213,6 +219,8 @@ _SIGNATURES = [
     ("nnd_init_random", C.c_int32, [_H]),
     ("nnd_init_from_graph", C.c_int32, [_H, C.c_void_p, C.c_void_p, C.c_int32]),
     ("nnd_init_from_neighbor_graph", C.c_int32, [_H, C.c_void_p, C.c_void_p, C.c_int32]),
+    ("nnd_init_from_graph_device", C.c_int32, [_H, C.c_void_p, C.c_void_p, C.c_int32]),
+    ("nnd_init_from_neighbor_graph_device", C.c_int32, [_H, C.c_void_p, C.c_void_p, C.c_int32]),
     ("nnd_descent_iter", C.c_int32, [_H, C.POINTER(C.c_int64)]),
     ("nnd_descent", C.c_int32, [_H]),
     ("nnd_finalize_host", C.c_int32, [_H, C.c_void_p, C.c_void_p]),
@@ -228,6 +236,9 @@ _SIGNATURES = [
     ("nnd_pairwise_gram", C.c_int32, [_H, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     ("nnd_exact_knn_rows", C.c_int32, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(NNDExactStats)]),
     ("nnd_exact_knn_queries", C.c_int32, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(NNDExactStats)]),
+    ("nnd_exact_knn_rows_device", C.c_int32, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(NNDExactStats)]),
+    ("nnd_exact_knn_queries_device", C.c_int32, [_H, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+                                                 C.POINTER(NNDExactStats)]),
     ("nnd_exact_slice_count", C.c_int32, [_H, C.c_int64]),
     ("nnd_descent_sample", C.c_int32, [_H]),
     ("nnd_descent_join", C.c_int32, [_H]),
@@ -434,6 +445,16 @@ class Builder:
         dist = np.ascontiguousarray(dist, np.float32)
         self._check(self.lib.nnd_init_from_neighbor_graph(self._h, _ptr(idx), _ptr(dist), idx.shape[1]))
 
+    def init_from_graph_device(self, idx_ptr, dist_ptr, width):
+        """``init_from_graph`` on the device addresses of an int32 / float32 (n, width) graph (``dist_ptr`` 0: distances are
+        computed), read in place on the handle's stream; nothing is waited for."""
+        self._check(self.lib.nnd_init_from_graph_device(self._h, C.c_void_p(int(idx_ptr)), C.c_void_p(int(dist_ptr)) if dist_ptr else None,
+                                                        int(width)))
+
+    def init_from_neighbor_graph_device(self, idx_ptr, dist_ptr, width):
+        """``init_from_neighbor_graph`` on device addresses; returns with the handle's stream drained."""
+        self._check(self.lib.nnd_init_from_neighbor_graph_device(self._h, C.c_void_p(int(idx_ptr)), C.c_void_p(int(dist_ptr)), int(width)))
+
     def descent_iter(self):
         c = C.c_int64()
         self._check(self.lib.nnd_descent_iter(self._h, C.byref(c)))
@@ -619,6 +640,24 @@ class Builder:
         q = np.ascontiguousarray(q, dtype=np.float32)
         assert q.ndim == 2 and q.shape[1] == self.dim
         return self._exact(self.lib.nnd_exact_knn_queries, q, q.shape[0], k)
+
+
+    def exact_knn_device(self, k, idx_ptr, dist_ptr, rows_ptr=0, n_rows=None, q_ptr=0, q_dtype=NND_DTYPE_FLOAT32, n_q=0):
+        """The exact search with every array on the handle's device, on the handle's stream: of the int32 row ids at ``rows_ptr``
+        (0: all rows), or of the (n_q, dim) queries of ``q_dtype`` at ``q_ptr``; int32 / float32 (m, k) answers written at
+        ``idx_ptr`` / ``dist_ptr``.  Returns the call's statistics."""
+        st = NNDExactStats()
+        dev = lambda p: C.c_void_p(int(p)) if p else None  # noqa: E731
+        if q_ptr:
+            m = int(n_q)
+            self._check(self.lib.nnd_exact_knn_queries_device(self._h, dev(q_ptr), int(q_dtype), m, int(k), dev(idx_ptr), dev(dist_ptr),
+                                                              C.byref(st)))
+        else:
+            m = self.n if not rows_ptr else int(n_rows)
+            self._check(self.lib.nnd_exact_knn_rows_device(self._h, dev(rows_ptr), m, int(k), dev(idx_ptr), dev(dist_ptr), C.byref(st)))
+        stats = st.as_dict()
+        stats["slices"] = int(self.lib.nnd_exact_slice_count(self._h, m))
+        return stats
 
 
 class Searcher:
@@ -873,6 +912,38 @@ def device_correct(device, stream_ptr, kind, in_ptr, out_ptr, count):
     lib = load_library()
     if lib.nnd_device_correct(int(device), C.c_void_p(int(stream_ptr)) if stream_ptr else None, int(kind), C.c_void_p(int(in_ptr)),
                               C.c_void_p(int(out_ptr)), int(count)) != 0:
+        raise NNDError(lib.nnd_last_global_error().decode())
+
+
+def device_update_rows(device, stream_ptr, dim, old, fresh, updated, pairs, out_ptr, out_dtype):
+    """The grown point set of ``update()`` at ``out_ptr`` (``nnd_device_update_rows``).  ``old`` / ``fresh`` / ``updated``:
+    ``(device address, NND_DTYPE_*, rows)`` each (rows 0: absent); ``pairs``: ``(address of the int32 source rows, address of the
+    int32 destination ids, count)``; queued on ``stream_ptr`` of ``device``."""
+    lib = load_library()
+    dev = lambda p: C.c_void_p(int(p)) if p else None  # noqa: E731
+    if lib.nnd_device_update_rows(int(device), dev(stream_ptr), int(dim), dev(old[0]), int(old[1]), int(old[2]), dev(fresh[0]), int(fresh[1]),
+                                  int(fresh[2]), dev(updated[0]), int(updated[1]), int(updated[2]), dev(pairs[0]), dev(pairs[1]), int(pairs[2]),
+                                  dev(out_ptr), int(out_dtype)) != 0:
+        raise NNDError(lib.nnd_last_global_error().decode())
+
+
+def device_update_graph(device, stream_ptr, idx_ptr, dist_ptr, n_old, k, ids_ptr, n_upd, n_new, map_ptr, out_idx_ptr, out_dist_ptr):
+    """The old (n_old, k) graph at ``idx_ptr`` / ``dist_ptr`` invalidated for the ``n_upd`` updated ids at ``ids_ptr`` and padded
+    to ``n_new`` rows, into ``out_idx_ptr`` / ``out_dist_ptr``; ``map_ptr``: n_old bytes of scratch."""
+    lib = load_library()
+    dev = lambda p: C.c_void_p(int(p)) if p else None  # noqa: E731
+    if lib.nnd_device_update_graph(int(device), dev(stream_ptr), dev(idx_ptr), dev(dist_ptr), int(n_old), int(k), dev(ids_ptr), int(n_upd),
+                                   int(n_new), dev(map_ptr), dev(out_idx_ptr), dev(out_dist_ptr)) != 0:
+        raise NNDError(lib.nnd_last_global_error().decode())
+
+
+def device_recall_hits(device, stream_ptr, true_ptr, m, k, graph_ptr, n, width, rows_ptr, hits_ptr):
+    """The int64 at ``hits_ptr`` = how many of the (m, k) true ids at ``true_ptr`` appear in the rows ``rows_ptr`` (int32 (m)) of the
+    int32 (n, width) graph at ``graph_ptr``; queued on ``stream_ptr`` of ``device``."""
+    lib = load_library()
+    dev = lambda p: C.c_void_p(int(p)) if p else None  # noqa: E731
+    if lib.nnd_device_recall_hits(int(device), dev(stream_ptr), dev(true_ptr), int(m), int(k), dev(graph_ptr), int(n), int(width), dev(rows_ptr),
+                                  dev(hits_ptr)) != 0:
         raise NNDError(lib.nnd_last_global_error().decode())
 
 

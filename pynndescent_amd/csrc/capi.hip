@@ -215,6 +215,25 @@ extern "C" int32_t nnd_init_from_neighbor_graph(nnd_handle_t ctx, const int32_t 
     return 0;
 }
 
+// The two entries above for a graph that lives on the handle's device: the full (n, width) arrays are read in place on the
+// handle's stream (a shard's handle reads its own rows of them).  Nothing is staged, so nothing has to be waited for before
+// the return: the arrays must stay valid until the stream has passed the call.
+extern "C" int32_t nnd_init_from_graph_device(nnd_handle_t ctx, const int32_t *init_idx_dev, const float *init_dist_dev, int32_t width) {
+    ENTER(ctx, NEED_GRAPH | NEED_DATA);
+    if (!init_idx_dev || width < 1 || width > NND_WIDE_K) { ctx->set_error("nnd_init_from_graph_device: width must be in 1..%d", NND_WIDE_K); return 1; }
+    const size_t off = (size_t)ctx->own_lo * width;
+    return nnd_launch_init_from_graph(ctx, init_idx_dev + off, init_dist_dev ? init_dist_dev + off : nullptr, width);
+}
+extern "C" int32_t nnd_init_from_neighbor_graph_device(nnd_handle_t ctx, const int32_t *init_idx_dev, const float *init_dist_dev, int32_t width) {
+    if (!ctx) return 1;
+    if (!init_dist_dev) { ENTER(ctx, 0); ctx->set_error("nnd_init_from_neighbor_graph_device: distances are required"); return 1; }
+    if (nnd_init_from_graph_device(ctx, init_idx_dev, init_dist_dev, width)) return 1;
+    if (nnd_launch_clear_new_flags(ctx)) return 1;
+    ctx->all_new = false;
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) { ctx->set_error("nnd_init_from_neighbor_graph_device: synchronize failed"); return 1; }
+    return 0;
+}
+
 extern "C" int32_t nnd_sample_candidates(nnd_handle_t ctx) {
     ENTER(ctx, NEED_GRAPH);
     return nnd_launch_sample(ctx);
@@ -453,6 +472,25 @@ extern "C" int32_t nnd_exact_knn_queries(nnd_handle_t ctx, const float *q, int64
     if (!q && n_q > 0) { ctx->set_error("nnd_exact_knn_queries: null queries"); return 1; }
     if (!q) { if (st) *st = nnd_exact_stats{}; return 0; }
     return nnd_exact_knn_impl(ctx, nullptr, q, n_q, k, out_idx, out_dist, st);
+}
+// ... with the caller's arrays on the handle's device (exact.hip: the batch copies become device to device)
+extern "C" int32_t nnd_exact_knn_rows_device(nnd_handle_t ctx, const int32_t *rows_dev, int64_t n_rows, int32_t k, int32_t *out_idx_dev, float *out_dist_dev,
+                                             nnd_exact_stats *st) {
+    ENTER(ctx, NEED_PREP);
+    if (!rows_dev) n_rows = ctx->n;
+    if (exact_checks(ctx, "nnd_exact_knn_rows_device", n_rows, k, out_idx_dev, out_dist_dev)) return 1;
+    const nnd_exact_dev dev{rows_dev, nullptr, NND_DTYPE_FLOAT32};
+    return nnd_exact_knn_impl(ctx, nullptr, nullptr, n_rows, k, out_idx_dev, out_dist_dev, st, &dev);
+}
+extern "C" int32_t nnd_exact_knn_queries_device(nnd_handle_t ctx, const void *q_dev, int32_t dtype, int64_t n_q, int32_t k, int32_t *out_idx_dev,
+                                                float *out_dist_dev, nnd_exact_stats *st) {
+    ENTER(ctx, NEED_PREP);
+    if (exact_checks(ctx, "nnd_exact_knn_queries_device", n_q, k, out_idx_dev, out_dist_dev)) return 1;
+    if (dtype < NND_DTYPE_FLOAT32 || dtype > NND_DTYPE_FLOAT64) { ctx->set_error("nnd_exact_knn_queries_device: dtype %d is none of NND_DTYPE_*", (int)dtype); return 1; }
+    if (!q_dev && n_q > 0) { ctx->set_error("nnd_exact_knn_queries_device: null queries"); return 1; }
+    if (!q_dev) { if (st) *st = nnd_exact_stats{}; return 0; }
+    const nnd_exact_dev dev{nullptr, q_dev, dtype};
+    return nnd_exact_knn_impl(ctx, nullptr, nullptr, n_q, k, out_idx_dev, out_dist_dev, st, &dev);
 }
 extern "C" int32_t nnd_exact_slice_count(nnd_handle_t ctx, int64_t n_rows) {
     if (!ctx) return 0;

@@ -229,6 +229,105 @@ int nnd_launch_gather_rows(hipStream_t st, const void *src, int dtype, const int
     }
 }
 
+// ---- update(): the grown point set assembled on the device (NNDescent.update of a device-built index) ----
+// The new (n_old + n_fresh, d) tensor takes the old rows, the fresh rows behind them and the updated rows at their ids.  When
+// every array has the tensor's own type nothing is converted: the elements move as words of their size (k_rows_copy, with the
+// work split of k_rows_to_f32: aligned 16-byte loads of the source, 16-byte stores when the destination is aligned as well).
+// Otherwise the tensor is float32 and the rows go through k_rows_to_f32.
+template <typename U>
+__global__ __launch_bounds__(256) void k_rows_copy(const U *__restrict__ src, U *__restrict__ dst, nnd_conv_plan plan, int dst_vec) {
+    constexpr int VEC = 16 / (int)sizeof(U);
+    const int64_t items = nnd_conv_items(plan);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (int64_t)gridDim.x * blockDim.x) {
+        int64_t first;
+        const int len = nnd_conv_item(plan, i, &first);
+        if (len == 1) {
+            dst[first] = src[first];
+            continue;
+        }
+        union { uint4 v; U e[VEC]; } w;
+        w.v = *(const uint4 *)(src + first);
+        if (dst_vec) {
+            *(uint4 *)(dst + first) = w.v;
+        } else {
+#pragma unroll
+            for (int c = 0; c < VEC; c++) dst[first + c] = w.e[c];
+        }
+    }
+}
+template <typename U>
+static int copy_launch(hipStream_t st, const void *src, int64_t count, void *dst) {
+    const nnd_conv_plan plan = nnd_conv_make_plan((uint64_t)(uintptr_t)src, (int)sizeof(U), 16 / (int)sizeof(U), count);
+    const int64_t items = nnd_conv_items(plan);
+    if (items <= 0) return 0;
+    const int dst_vec = (((uintptr_t)dst + sizeof(U) * (size_t)plan.head) & 15) == 0 ? 1 : 0;
+    int64_t blocks = (items + 255) / 256;
+    if (blocks > 262144) blocks = 262144;  // (the kernel strides over the rest)
+    hipLaunchKernelGGL(k_rows_copy<U>, dim3((unsigned)blocks), dim3(256), 0, st, (const U *)src, (U *)dst, plan, dst_vec);
+    return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+static size_t dtype_size(int dtype) { return dtype == NND_DTYPE_FLOAT64 ? 8 : dtype == NND_DTYPE_FLOAT32 ? 4 : 2; }
+// `count` elements of `dtype` at src -> dst: as they are when out_dtype is the same type, as float32 otherwise
+static int rows_into(hipStream_t st, const void *src, int dtype, int64_t count, void *dst, int out_dtype) {
+    if (count <= 0) return 0;
+    if (dtype != out_dtype) return nnd_launch_rows_f32(st, src, dtype, count, 1, false, (float *)dst);
+    switch (dtype_size(dtype)) {
+        case 2: return copy_launch<uint16_t>(st, src, count, dst);
+        case 4: return copy_launch<uint32_t>(st, src, count, dst);
+        default: return copy_launch<uint64_t>(st, src, count, dst);
+    }
+}
+
+// The typed row scatter: row ids[i] of dst = row rows[i] of src, 2^lpr_log2 lanes per pair, a lane every 2^lpr_log2-th element.
+// The pairs' ids are distinct (the host resolves duplicates: the last one wins there), so no two groups write one row; a pair
+// that names a row outside either array (a caller's error) is skipped: nothing is read or written out of bounds.
+// RAW: both arrays hold the same type, moved as words of its size (T == OUT: uint16_t / uint32_t / uint64_t)
+template <typename T, typename OUT, bool RAW>
+__global__ __launch_bounds__(256) void k_scatter_rows(const T *__restrict__ src, int64_t n_src, const int32_t *__restrict__ rows, const int32_t *__restrict__ ids,
+                                                      int64_t n_pairs, int d, int lpr_log2, OUT *__restrict__ dst, int64_t n_dst) {
+    const int lpr = 1 << lpr_log2, sub = (int)threadIdx.x & (lpr - 1);
+    const int64_t step = (int64_t)gridDim.x * (256 >> lpr_log2);
+    for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> lpr_log2; i < n_pairs; i += step) {
+        const int64_t s = rows[i], r = ids[i];
+        if (s < 0 || s >= n_src || r < 0 || r >= n_dst) continue;
+        const T *from = src + s * d;
+        OUT *to = dst + r * d;
+        for (int c = sub; c < d; c += lpr) {
+            if constexpr (RAW) to[c] = from[c];
+            else to[c] = conv_traits<T>::one(from[c]);
+        }
+    }
+}
+template <typename T, typename OUT, bool RAW>
+static int scatter_launch(hipStream_t st, const void *src, int64_t n_src, const int32_t *rows, const int32_t *ids, int64_t n_pairs, int d, void *dst,
+                          int64_t n_dst) {
+    int lpr_log2 = 0;
+    while (lpr_log2 < 6 && (1 << lpr_log2) < d) lpr_log2++;
+    const int64_t per_block = 256 >> lpr_log2;
+    int64_t blocks = (n_pairs + per_block - 1) / per_block;
+    if (blocks > 8192) blocks = 8192;  // (the kernel strides over the rest)
+    hipLaunchKernelGGL((k_scatter_rows<T, OUT, RAW>), dim3((unsigned)blocks), dim3(256), 0, st, (const T *)src, n_src, rows, ids, n_pairs, d, lpr_log2, (OUT *)dst,
+                       n_dst);
+    return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+static int scatter_into(hipStream_t st, const void *src, int dtype, int64_t n_src, const int32_t *rows, const int32_t *ids, int64_t n_pairs, int d, void *dst,
+                        int out_dtype, int64_t n_dst) {
+    if (n_pairs <= 0) return 0;
+    if (dtype == out_dtype) {
+        switch (dtype_size(dtype)) {
+            case 2: return scatter_launch<uint16_t, uint16_t, true>(st, src, n_src, rows, ids, n_pairs, d, dst, n_dst);
+            case 4: return scatter_launch<uint32_t, uint32_t, true>(st, src, n_src, rows, ids, n_pairs, d, dst, n_dst);
+            default: return scatter_launch<uint64_t, uint64_t, true>(st, src, n_src, rows, ids, n_pairs, d, dst, n_dst);
+        }
+    }
+    switch (dtype) {
+        case NND_DTYPE_FLOAT32: return scatter_launch<float, float, false>(st, src, n_src, rows, ids, n_pairs, d, dst, n_dst);
+        case NND_DTYPE_FLOAT16: return scatter_launch<conv_f16, float, false>(st, src, n_src, rows, ids, n_pairs, d, dst, n_dst);
+        case NND_DTYPE_BFLOAT16: return scatter_launch<conv_bf16, float, false>(st, src, n_src, rows, ids, n_pairs, d, dst, n_dst);
+        default: return scatter_launch<double, float, false>(st, src, n_src, rows, ids, n_pairs, d, dst, n_dst);
+    }
+}
+
 // ---- corrections ----
 template <int KIND, typename OUT>
 __global__ __launch_bounds__(256) void k_correct(const float *__restrict__ in, OUT *__restrict__ out, int64_t count) {
@@ -284,5 +383,33 @@ extern "C" int32_t nnd_device_correct(int32_t device, void *hip_stream, int32_t 
         default: hipLaunchKernelGGL((k_correct<NND_CORRECT_ALT_HELLINGER, double>), g, b, 0, st, in_dev, (double *)out_dev, count); break;
     }
     if (hipGetLastError() != hipSuccess) return da_fail("nnd_device_correct: kernel launch failed");
+    return 0;
+}
+
+static bool dtype_ok(int32_t t) { return t >= NND_DTYPE_FLOAT32 && t <= NND_DTYPE_FLOAT64; }
+
+extern "C" int32_t nnd_device_update_rows(int32_t device, void *hip_stream, int32_t dim, const void *old_dev, int32_t old_dtype, int64_t n_old,
+                                          const void *fresh_dev, int32_t fresh_dtype, int64_t n_fresh, const void *upd_dev, int32_t upd_dtype,
+                                          int64_t n_upd, const int32_t *upd_rows_dev, const int32_t *upd_ids_dev, int64_t n_pairs, void *out_dev,
+                                          int32_t out_dtype) {
+    if (dim < 1 || n_old < 0 || n_fresh < 0 || n_upd < 0 || n_pairs < 0 || !dtype_ok(out_dtype)) return da_fail("nnd_device_update_rows: bad shape or dtype");
+    const bool has_old = n_old > 0, has_fresh = n_fresh > 0, has_upd = n_pairs > 0;
+    if ((has_old && !dtype_ok(old_dtype)) || (has_fresh && !dtype_ok(fresh_dtype)) || (has_upd && !dtype_ok(upd_dtype)))
+        return da_fail("nnd_device_update_rows: bad shape or dtype");
+    // the dtype rule: one shared type is kept, anything else meets in float32
+    if (out_dtype != NND_DTYPE_FLOAT32 && ((has_old && old_dtype != out_dtype) || (has_fresh && fresh_dtype != out_dtype) || (has_upd && upd_dtype != out_dtype)))
+        return da_fail("nnd_device_update_rows: arrays of different types are assembled as float32");
+    if ((has_old && !old_dev) || (has_fresh && !fresh_dev) || (has_upd && (!upd_dev || !upd_rows_dev || !upd_ids_dev)) || ((has_old || has_fresh) && !out_dev))
+        return da_fail("nnd_device_update_rows: null pointer");
+    if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return da_fail("nnd_device_update_rows: no such device"); }
+    hipStream_t st = (hipStream_t)hip_stream;
+    char *out = (char *)out_dev;
+    const size_t esz = dtype_size(out_dtype);
+    if (rows_into(st, old_dev, old_dtype, n_old * (int64_t)dim, out, out_dtype) ||
+        rows_into(st, fresh_dev, fresh_dtype, n_fresh * (int64_t)dim, out + esz * (size_t)n_old * dim, out_dtype) ||
+        scatter_into(st, upd_dev, upd_dtype, n_upd, upd_rows_dev, upd_ids_dev, n_pairs, dim, out, out_dtype, n_old)) {
+        (void)hipGetLastError();
+        return da_fail("nnd_device_update_rows: kernel launch failed");
+    }
     return 0;
 }

@@ -424,6 +424,16 @@ __global__ void k_exact_iota(int32_t *__restrict__ p, int n, int base) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) p[i] = base + i;
 }
+// row ids that arrive on the device are checked there, on their way into the batch: an id outside [0, n) is counted and replaced
+// by 0 (the scan would read that row), and the count comes back with the batch's answers
+__global__ __launch_bounds__(256) void k_exact_take_ids(const int32_t *__restrict__ ids, int count, int64_t n, int32_t *__restrict__ out, int32_t *__restrict__ n_bad) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const int32_t id = ids[i];
+    const bool bad = id < 0 || (int64_t)id >= n;
+    out[i] = bad ? 0 : id;
+    if (bad) atomicAdd(n_bad, 1);
+}
 
 // ---- host side ----
 int nnd_exact_slices_for(int64_t n, int64_t nq) {
@@ -460,16 +470,23 @@ static int ex_launch_scan(nnd_ctx *ctx, bool xm, bool wide, dim3 grid, const flo
     return 0;
 }
 
-int nnd_exact_knn_impl(nnd_ctx *ctx, const int64_t *rows, const float *q, int64_t nq_all, int k, int32_t *out_idx, float *out_dist, nnd_exact_stats *st) {
+static size_t ex_dtype_size(int dtype) { return dtype == NND_DTYPE_FLOAT64 ? 8 : dtype == NND_DTYPE_FLOAT32 ? 4 : 2; }
+
+// `dev` (the device entries): row ids / queries are read from, and the answers written to, memory of the handle's device -- every
+// copy below becomes device to device on the handle's stream; only the per-batch scalars cross the bus
+int nnd_exact_knn_impl(nnd_ctx *ctx, const int64_t *rows, const float *q, int64_t nq_all, int k, int32_t *out_idx, float *out_dist, nnd_exact_stats *st,
+                       const nnd_exact_dev *dev) {
     const int64_t n = ctx->n;
     const int d = ctx->d, dp = ctx->dp, metric = ctx->p.metric;
-    const bool self = q == nullptr, xm = metric >= 2, force_f64 = (ctx->p.flags & NND_FLAG_TEST_EXACT_F64) != 0;
+    const bool self = dev ? dev->q_dev == nullptr : q == nullptr, xm = metric >= 2, force_f64 = (ctx->p.flags & NND_FLAG_TEST_EXACT_F64) != 0;
+    const bool some_rows = dev ? dev->rows_dev != nullptr : rows != nullptr;
+    const hipMemcpyKind out_kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     if (n > (int64_t)NND_IDX_MASK) { ctx->set_error("exact search: more than 2^31 - 1 points"); return 1; }
     const int W = ex_list_width(k);
     const bool wide = W > 64;
     nnd_exact_stats s{};
     std::vector<int32_t> ids;
-    if (self && rows) {
+    if (self && rows && !dev) {
         ids.resize((size_t)nq_all);
         for (int64_t i = 0; i < nq_all; i++) {
             if (rows[i] < 0 || rows[i] >= n) { ctx->set_error("exact search: row id %lld is outside [0, %lld)", (long long)rows[i], (long long)n); return 1; }
@@ -498,7 +515,7 @@ int nnd_exact_knn_impl(nnd_ctx *ctx, const int64_t *rows, const float *q, int64_
           *lrej = (float *)(ws + o_rej), *od = (float *)(ws + o_od);
     uint32_t *le = (uint32_t *)(ws + o_le);
     double *nmax = (double *)(ws + o_misc);
-    int32_t *n_unc = (int32_t *)(ws + o_misc + 8);
+    int32_t *n_unc = (int32_t *)(ws + o_misc + 8), *n_bad = (int32_t *)(ws + o_misc + 12);
 
     NND_HIP_CHECK(hipMemsetAsync(nmax, 0, 16, ctx->stream));
     if (!force_f64 && (metric == 0 || metric == 2 || metric == 3)) {
@@ -510,8 +527,12 @@ int nnd_exact_knn_impl(nnd_ctx *ctx, const int64_t *rows, const float *q, int64_
     for (int64_t b0 = 0; b0 < nq_all; b0 += EX_BATCH) {
         const int nq = (int)(nq_all - b0 < EX_BATCH ? nq_all - b0 : EX_BATCH);
         const int nq_pad = (nq + EX_QB - 1) / EX_QB * EX_QB;
-        if (self && rows) NND_HIP_CHECK(hipMemcpyAsync(qids, ids.data() + b0, sizeof(int32_t) * nq, hipMemcpyHostToDevice, ctx->stream));
-        else {  // all rows: ids b0 ..; external queries: their index in the batch's own prepared copy
+        if (self && some_rows) {
+            if (dev) {
+                hipLaunchKernelGGL(k_exact_take_ids, dim3((nq + 255) / 256), dim3(256), 0, ctx->stream, dev->rows_dev + b0, nq, n, qids, n_bad);
+                NND_HIP_CHECK(hipGetLastError());
+            } else NND_HIP_CHECK(hipMemcpyAsync(qids, ids.data() + b0, sizeof(int32_t) * nq, hipMemcpyHostToDevice, ctx->stream));
+        } else {  // all rows: ids b0 ..; external queries: their index in the batch's own prepared copy
             hipLaunchKernelGGL(k_exact_iota, dim3((nq + 255) / 256), dim3(256), 0, ctx->stream, qids, nq, self ? (int)b0 : 0);
             NND_HIP_CHECK(hipGetLastError());
         }
@@ -519,7 +540,16 @@ int nnd_exact_knn_impl(nnd_ctx *ctx, const int64_t *rows, const float *q, int64_
         if (!self) {
             // the queries through the point set's own preparation (code 0: the SET's column means): the prep kernels write where
             // the handle's prepared-row pointers point
-            NND_HIP_CHECK(hipMemcpyAsync(qraw_own, q + b0 * d, sizeof(float) * (size_t)nq * d, hipMemcpyHostToDevice, ctx->stream));
+            if (dev) {  // typed device queries: converted (dot: and L2-normalised, as the typed data entry does) into the same copy
+                const char *src = (const char *)dev->q_dev + (size_t)b0 * d * ex_dtype_size(dev->q_dtype);
+                if (nnd_launch_rows_f32(ctx->stream, src, dev->q_dtype, nq, d, metric == NND_METRIC_ALT_DOT, qraw_own)) {
+                    (void)hipGetLastError();
+                    ctx->set_error("exact search: conversion kernel launch failed");
+                    return 1;
+                }
+            } else {
+                NND_HIP_CHECK(hipMemcpyAsync(qraw_own, q + b0 * d, sizeof(float) * (size_t)nq * d, hipMemcpyHostToDevice, ctx->stream));
+            }
             float *xp0 = ctx->xp, *nrm0 = ctx->nrm;
             uint16_t *xh0 = ctx->xh;
             float2 *nr20 = ctx->nr2;
@@ -568,10 +598,16 @@ int nnd_exact_knn_impl(nnd_ctx *ctx, const int64_t *rows, const float *q, int64_
             NND_HIP_CHECK(hipGetLastError());
             t_end(ctx, t_fb, &s.ms_fallback, true);
         }
-        NND_HIP_CHECK(hipMemcpyAsync(out_idx + b0 * k, oi, sizeof(int32_t) * (size_t)nq * k, hipMemcpyDeviceToHost, ctx->stream));
-        NND_HIP_CHECK(hipMemcpyAsync(out_dist + b0 * k, od, sizeof(float) * (size_t)nq * k, hipMemcpyDeviceToHost, ctx->stream));
+        NND_HIP_CHECK(hipMemcpyAsync(out_idx + b0 * k, oi, sizeof(int32_t) * (size_t)nq * k, out_kind, ctx->stream));
+        NND_HIP_CHECK(hipMemcpyAsync(out_dist + b0 * k, od, sizeof(float) * (size_t)nq * k, out_kind, ctx->stream));
+        const bool ids_checked = dev && self && some_rows;
+        if (ids_checked) NND_HIP_CHECK(hipMemcpyAsync(&ctx->h_pin->spare[1], n_bad, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
         t_flush(ctx);
         NND_HIP_CHECK(nnd_sync_spin(ctx));
+        if (ids_checked && *(const int32_t *)&ctx->h_pin->spare[1]) {
+            ctx->set_error("exact search: %d row ids are outside [0, %lld)", (int)*(const int32_t *)&ctx->h_pin->spare[1], (long long)n);
+            return 1;
+        }
         s.n_rows += nq;
         s.n_fallback += n_fallback;
     }

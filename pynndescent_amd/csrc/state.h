@@ -357,8 +357,15 @@ int nnd_search_graph_device_impl(nnd_ctx *ctx, const int32_t **indptr_dev, const
 // padded (current device, stream st): dst row i = src row order[i]
 int nnd_launch_gather_rows(hipStream_t st, const void *src, int dtype, const int32_t *order, int64_t n, int d, int dp, float *dst);
 // exact.hip: exact k nearest neighbours of `rows` of the point set (q == nullptr; rows == nullptr: all of them) or of the
-// external queries q (host (nq, d)); host outputs (nq, k)
-int nnd_exact_knn_impl(nnd_ctx *ctx, const int64_t *rows, const float *q, int64_t nq, int k, int32_t *out_idx, float *out_dist, nnd_exact_stats *st);
+// external queries q (host (nq, d)); host outputs (nq, k).  With `dev` the caller's arrays are on the handle's device instead:
+// int32 row ids (nullptr: all rows) or (nq, d) queries of an NND_DTYPE_* type (nullptr: rows of the point set), device outputs
+struct nnd_exact_dev {
+    const int32_t *rows_dev;
+    const void *q_dev;
+    int q_dtype;
+};
+int nnd_exact_knn_impl(nnd_ctx *ctx, const int64_t *rows, const float *q, int64_t nq, int k, int32_t *out_idx, float *out_dist, nnd_exact_stats *st,
+                       const nnd_exact_dev *dev = nullptr);
 int nnd_exact_slices_for(int64_t n, int64_t nq);  // data slices (gridDim.y) of the scan for nq query rows
 int nnd_read_counters(nnd_ctx *ctx);  // device -> ctx->h_counters (synchronises the stream)
 int nnd_zero_counters(nnd_ctx *ctx);

@@ -208,6 +208,55 @@ def _torch():
     return torch
 
 
+def _dtype_name(a):
+    """``float32`` of ``torch.float32``: the key of ``_DEVICE_DTYPES`` and the attribute of torch."""
+    return str(a.dtype).rsplit(".", 1)[-1]
+
+
+def _shape_of(a):
+    """The shape of a host array-like or a device array, without bringing either anywhere."""
+    return tuple(a.shape) if hasattr(a, "shape") else np.shape(a)
+
+
+def _rows_to_host(a):
+    """A device array as the float32 host rows ``check_array`` would make of its values (a host array: as it is)."""
+    return np.ascontiguousarray(a.detach().float().cpu().numpy()) if _is_device_array(a) else a
+
+
+def _ids_to_host(a):
+    """Row ids given as a device array, on the host (they are few); everything else as it is."""
+    return a.detach().cpu().numpy() if _is_device_array(a) else a
+
+
+def _updates_on_device(index, xs_fresh, xs_updated):
+    """Whether ``update()`` of ``index`` stays on the device (``NNDescent._update_device``): the index holds its rows and its graph
+    on one GPU, and at least one of the incoming arrays is a device array.  Reads ``__dict__`` only."""
+    d = index.__dict__
+    if "_device_data" not in d or "_device_graph" not in d or int(d.get("n_devices", 1)) != 1:
+        return False
+    return _is_device_array(xs_fresh) or _is_device_array(xs_updated)
+
+
+def _resolve_updated_indices(updated_indices, n_old):
+    """``updated_indices`` as the host loop ``raw[i] = x`` reads them (pynndescent_.py:2467-2469), resolved to distinct pairs:
+    ``(row ids, source rows)``, int32, ids ascending -- a negative id wraps, of several entries that name one row the last one
+    wins, an id outside ``[-n_old, n_old)`` raises numpy's ``IndexError``.  No two pairs write one row."""
+    ids = np.asarray(updated_indices, dtype=np.int64).reshape(-1)
+    outside = (ids < -n_old) | (ids >= n_old)
+    if outside.any():
+        raise IndexError("index %d is out of bounds for axis 0 with size %d" % (int(ids[outside][0]), n_old))
+    ids = np.where(ids < 0, ids + n_old, ids)
+    unique, first_from_the_end = np.unique(ids[::-1], return_index=True)
+    return unique.astype(np.int32), (ids.shape[0] - 1 - first_from_the_end).astype(np.int32)
+
+
+def _update_dtype(names):
+    """The dtype rule of the device ``update()``: ``names`` -- the dtype names of the index's tensor and of every incoming array
+    (a host array counts as float32, what ``check_array`` makes of it) -- share one dtype: it is kept; otherwise float32."""
+    names = list(names)
+    return names[0] if all(name == names[0] for name in names) else "float32"
+
+
 class _OnTorchStream:
     """The HIP stream a library call runs on so that it is ordered with torch's work on ``ordinal``: torch's current stream.  The
     default stream has no handle a builder could adopt (NULL means the builder's own, which does not wait for it), so there
@@ -242,10 +291,11 @@ def _stream_ms(torch, stream, fn):
 class _DeviceInput:
     """The device side of one single-GPU build (``_build_graph``): the caller's tensor in, the finished graph out as tensors."""
 
-    def __init__(self, tensor, dtype, ordinal, k):
+    def __init__(self, tensor, dtype, ordinal, k, as_given=False):
         self.torch = _torch()
         self.tensor, self.dtype, self.ordinal, self.k = tensor, dtype, ordinal, int(k)
         self.rows = tensor  # what the index keeps: the caller's own tensor, or dot's normalised float32 rows
+        self.as_given = as_given  # update(): dot's rows enter as they are (float32, pynndescent_.py:2461-2476 normalises nothing)
 
     def host_rows(self):
         """The caller's rows on the host, float32: for sklearn's wording of the NaN / inf error, the one place that needs them."""
@@ -255,7 +305,9 @@ class _DeviceInput:
         torch, t = self.torch, self.tensor
         self.stream = _OnTorchStream(torch, self.ordinal)
         builder.set_stream(self.stream.ptr)
-        if m.normalize:  # pynndescent_.py:1101-1102: the index holds the normalised rows; the builder borrows them
+        if m.normalize and self.as_given:  # (the typed entry would normalise every dot input)
+            builder.set_data_device(t.data_ptr(), keepalive=t)
+        elif m.normalize:  # pynndescent_.py:1101-1102: the index holds the normalised rows; the builder borrows them
             self.rows = torch.empty(tuple(t.shape), dtype=torch.float32, device=t.device)
             _capi.device_rows_f32(self.ordinal, self.stream.ptr, t.data_ptr(), self.dtype, t.shape[0], t.shape[1], True,
                                   self.rows.data_ptr())
@@ -382,19 +434,27 @@ class NNDescent:
         ``prepare()`` -- and so the first ``query()`` -- runs from those tensors too (hub rank, tree, pruning pass, reorder and
         the searcher's fill on the device: only the tree's tables, ``_vertex_order`` and scalars cross the bus; dot with
         ``quantization="uint8"`` takes the host path).  ``_raw_data``, ``_neighbor_graph``, ``_search_graph`` and
-        ``_quantized_data`` are host mirrors fetched on first use; ``update``, ``recall``, ``build_search_graph``, pickling and
-        ``to_reference`` work through them.  Out of scope: ``exact_knn`` / ``recall`` without the host mirror; device
-        ``init_graph`` / ``init_dist`` (converted with ``.cpu().numpy()``); the hub tree's FlatTree assembly on the device;
-        producers other than torch (``__cuda_array_interface__``, DLPack); and a sharded build from device memory -- with
-        ``n_devices`` > 1 the rows are brought to the host first and the index is a host index, as for host input."""
+        ``_quantized_data`` are host mirrors fetched on first use; ``build_search_graph``, pickling and ``to_reference`` work
+        through them.  ``update()`` with a tensor and ``recall()`` stay on the device (``_update_device``, ``_recall_device``);
+        ``update()`` with host arrays alone makes the index a host index.  ``init_graph`` / ``init_dist`` may be tensors as well:
+        with device ``data`` on one GPU they are cast to int32 / float32 on the device and seed the build where they are
+        (``nnd_init_from_graph_device``); in every other combination they are brought to the host.  Out of scope: the hub
+        tree's FlatTree assembly on the device; producers other than torch (``__cuda_array_interface__``, DLPack); and a sharded
+        build from device memory -- with ``n_devices`` > 1 the rows are brought to the host first and the index is a host index,
+        as for host input."""
         dev_checked = None
         if _is_device_array(data):  # dtype, shape and device first: before any device work, and before the shape is read
             dev_checked = _check_device_array(data, device)
             data, device = dev_checked[0], dev_checked[2]
-        if _is_device_array(init_graph):  # (out of scope on the device: they seed the build from the host)
-            init_graph = init_graph.detach().cpu().numpy()
-        if _is_device_array(init_dist):
-            init_dist = init_dist.detach().cpu().numpy()
+        # init_graph / init_dist tensors seed a device build where they are (cast on torch's stream here, before the builder's
+        # stream is taken from it); every other combination meets on the host
+        if dev_checked is not None and int(n_devices) == 1 and _is_device_array(init_graph) and (init_dist is None or _is_device_array(init_dist)):
+            torch = _torch()
+            init_graph = init_graph.detach().to(device=data.device, dtype=torch.int32).contiguous()
+            if init_dist is not None:
+                init_dist = init_dist.detach().to(device=data.device, dtype=torch.float32).contiguous()
+        else:
+            init_graph, init_dist = _ids_to_host(init_graph), _ids_to_host(init_dist)
         n_trees, n_iters, eff_leaf_size, eff_max_candidates = _reference_defaults(
             data.shape[0], n_neighbors, n_trees, n_iters, leaf_size, max_candidates)
 
@@ -474,10 +534,11 @@ class NNDescent:
             eff_trees = 0
 
         if init_graph is not None:
-            init_graph = np.asarray(init_graph)
+            if not _is_device_array(init_graph):
+                init_graph = np.asarray(init_graph)
             if init_graph.shape[0] != n:
                 raise ValueError("Init graph size does not match dataset size!")  # pynndescent_.py:1229
-            if init_dist is not None and init_graph.shape != np.asarray(init_dist).shape:
+            if init_dist is not None and tuple(init_graph.shape) != _shape_of(init_dist):
                 raise ValueError("The shapes of init graph and init distances do not match!")  # pynndescent_.py:1236
 
         if self.n_devices > 1:  # (a build that starts from init_graph is sharded too -- nnd_build_multi_from_graph)
@@ -622,8 +683,15 @@ class NNDescent:
         ``min(10, n_neighbors)``) that appear anywhere in the graph's row, averaged over ``min(n_rows, n)`` distinct rows
         drawn by ``_recall_rows`` -- the convention of the reference's tests (tests/test_pynndescent_.py:27-31).  The truth
         is the exact brute-force search of ``exact_knn`` over the index's data; only the data and the graph are read, so
-        every way of making the index (one or several devices, ``from_graph``, after ``update()``) is covered."""
+        every way of making the index (one or several devices, ``from_graph``, after ``update()``) is covered.  An index built
+        from a device array on one GPU is measured where it is: the exact search and the count run on its tensors, the sampled
+        row ids go up and one integer comes back (the same value, and no host mirror is fetched).  dot: the truth is searched
+        on rows normalised once more -- by the device there, by sklearn on the host path -- which agree within rounding only,
+        so the two paths may differ where two true neighbours are that close; every other metric gives the same value."""
         _no_exact_for_proxy(self.metric, _METRICS[self.metric], "NNDescent.recall")
+        d = self.__dict__
+        if "_device_data" in d and "_device_graph" in d and int(d.get("n_devices", 1)) == 1:
+            return self._recall_device(k, n_rows, random_state)
         graph_idx = self._neighbor_graph[0]
         n = graph_idx.shape[0]
         k = min(10, int(self.n_neighbors)) if k is None else int(k)
@@ -634,6 +702,23 @@ class NNDescent:
         true_idx = exact_knn(data, k=k, metric=self.metric, rows=rows, device=getattr(self, "device", 0))[0]
         hits = sum(int(np.isin(t, a).sum()) for t, a in zip(true_idx, graph_idx[rows]))
         return hits / float(true_idx.shape[0] * k)
+
+    def _recall_device(self, k, n_rows, random_state):
+        """``recall`` of an index that holds its rows and its graph on the device: the sampled ids go up, the exact search runs on
+        the tensors (``_device_data`` keeps the original order through ``prepare()``), one wave per sampled row counts the true ids
+        found in the graph's row, and one integer comes back.  No host mirror is read or made."""
+        torch, d = _torch(), self.__dict__
+        data, gidx = d["_device_data"], d["_device_graph"][0]
+        n, ordinal = int(gidx.shape[0]), int(self.device)
+        k = min(10, int(self.n_neighbors)) if k is None else int(k)
+        rows = self._recall_rows(n, n_rows, random_state)
+        with torch.cuda.device(ordinal):
+            rows_dev = torch.from_numpy(rows.astype(np.int32)).to(data.device)
+            true_idx = _exact_knn_device(data, None, k, self.metric, _METRICS[self.metric], rows_dev, ordinal, False)[0]
+            hits = torch.empty((1,), dtype=torch.int64, device=data.device)
+            _capi.device_recall_hits(ordinal, torch.cuda.current_stream(ordinal).cuda_stream, true_idx.data_ptr(), true_idx.shape[0], k,
+                                     gidx.data_ptr(), n, gidx.shape[1], rows_dev.data_ptr(), hits.data_ptr())
+            return int(hits.item()) / float(true_idx.shape[0] * k)
 
     def build_search_graph(self):
         """The pruning pass of ``_init_search_graph`` (pynndescent_.py:1451-1611: diversify, reverse diversify,
@@ -1028,12 +1113,33 @@ class NNDescent:
         """``pynndescent.NNDescent.update`` (pynndescent_.py:2381-2553) on the GPU: fresh rows are appended, updated
         rows replaced (their graph rows and every edge pointing at them are dropped), then the graph is rebuilt from
         a warm start -- the old graph inserted as "old" edges (init_from_neighbor_graph, flag 0), a forest of
-        ``n_trees_after_update`` trees seeding "new" edges, no random fill -- and NN-descent runs to the stop rule."""
+        ``n_trees_after_update`` trees seeding "new" edges, no random fill -- and NN-descent runs to the stop rule.
+
+        An index built from a device array on one GPU stays there when ``xs_fresh`` or ``xs_updated`` is a device array (a host
+        array given alongside is uploaded): the new rows and the invalidated graph are assembled on the device
+        (``_update_device``), ``neighbor_graph`` keeps returning tensors and a prepared index is prepared again on the device.
+        With host arrays alone such an index becomes a host index, as before; a device array given to a host index, or to one
+        built on several GPUs, is brought to the host.  ``updated_indices`` may be a tensor; the ids are read on the host."""
+        on_device = _updates_on_device(self, xs_fresh, xs_updated)
+        if not on_device:  # a tensor on an index that cannot stay on the device: its values, through the host path
+            xs_fresh, xs_updated = _rows_to_host(xs_fresh), _rows_to_host(xs_updated)
+        updated_indices = _ids_to_host(updated_indices)  # (a tensor of ids: they are few, and they stay a host list)
+
+        def checked(rows, what):  # check_array; a device array of the device path: its validator, nothing is read
+            if not _is_device_array(rows):
+                return check_array(rows, dtype=self._input_dtype, order="C")
+            rows, _, ordinal = _check_device_array(rows, what=what)
+            if ordinal != int(self.device):
+                raise ValueError("%s is on device %d, the index on device %d" % (what, ordinal, int(self.device)))
+            if rows.shape[1] != self.dim:
+                raise ValueError("%s must have shape (n_rows, %d), got %s" % (what, self.dim, tuple(rows.shape)))
+            return rows
+
         current_random_state = check_random_state(self.random_state)
         # drawn and handed to make_forest by the reference (pynndescent_.py:2408-2411); kept for the stream position
         current_random_state.randint(INT32_MIN, INT32_MAX, 3)
         if xs_updated is not None:
-            xs_updated = check_array(xs_updated, dtype=self._input_dtype, order="C")
+            xs_updated = checked(xs_updated, "xs_updated")
             if updated_indices is None:
                 raise ValueError("If xs_updated are provided, updated_indices must also be provided!")
             try:
@@ -1049,6 +1155,9 @@ class NNDescent:
             if updated_indices is not None:
                 warn("xs_updated not provided, while update_indices provided. " "They will be ignored.")
             updated_indices = None
+        if on_device:
+            return self._update_device(None if xs_fresh is None else checked(xs_fresh, "xs_fresh"), xs_updated, updated_indices or [],
+                                       current_random_state)
         if updated_indices is None:
             xs_updated = np.zeros((0, self._raw_data.shape[1]), self._input_dtype)
             updated_indices = []
@@ -1099,6 +1208,64 @@ class NNDescent:
         if self._prepared:  # pynndescent_.py:2538-2553: the derived structures are rebuilt
             for name in ("_search_graph", "_search_forest", "_vertex_order", "_searcher"):
                 self.__dict__.pop(name, None)
+            self.prepare()
+
+
+    def _update_device(self, xs_fresh, xs_updated, updated_indices, current_random_state):
+        """``update`` of an index that holds its rows and its graph on the device, entry for entry what the host path computes
+        from the mirrors -- on torch's current stream (``_OnTorchStream``), with no host leg: the new ``(n_old + n_fresh, d)``
+        tensor (old rows, fresh rows, updated rows scattered to their ids; the dtype all arrays share, else float32) and the
+        invalidated, padded graph are written by the library (``nnd_device_update_rows`` / ``nnd_device_update_graph``), the
+        rebuild binds the new rows as they are (dot: not normalised again, as on the host path) and reads the old graph in place.
+        What crosses the bus: the resolved ``(row id, source row)`` pairs, host arrays given alongside, and the build's scalars."""
+        d, m = self.__dict__, _METRICS[self.metric]
+        data, (gidx, gdist) = d["_device_data"], d["_device_graph"]
+        n_old, dim, k, ordinal = int(data.shape[0]), int(data.shape[1]), int(gidx.shape[1]), int(self.device)
+        ids, sources = _resolve_updated_indices(updated_indices, n_old)  # (IndexError: before any device work)
+        torch = _torch()
+        n_fresh = 0 if xs_fresh is None else int(xs_fresh.shape[0])
+        n = n_old + n_fresh
+        n_trees = self.n_trees_after_update  # pynndescent_.py:2498 (assigned with the new tensors: a rebuild that raises changes nothing)
+        _, _, eff_leaf_size, eff_max_candidates = _reference_defaults(n, self.n_neighbors, n_trees, self.n_iters,
+                                                                      self.leaf_size, self.max_candidates)
+        tree_states = current_random_state.randint(INT32_MIN, INT32_MAX, size=(n_trees, 3)).astype(np.int64)
+        with torch.cuda.device(ordinal):
+            def on_device(rows):  # a host array given alongside goes up (float32: what check_array made of it)
+                return rows if rows is None or _is_device_array(rows) else torch.from_numpy(rows).to(data.device)
+
+            def described(rows):  # (address, NND_DTYPE_*, rows) of an array that may be absent
+                return (0, 0, 0) if rows is None or rows.shape[0] == 0 else (rows.data_ptr(), _DEVICE_DTYPES[_dtype_name(rows)], rows.shape[0])
+
+            xs_fresh, xs_updated = on_device(xs_fresh), on_device(xs_updated)
+            out_name = _update_dtype([_dtype_name(data)] + [_dtype_name(a) for a in (xs_fresh, xs_updated) if a is not None])
+            new_data = torch.empty((n, dim), dtype=getattr(torch, out_name), device=data.device)
+            pad_i = torch.empty((n, k), dtype=torch.int32, device=data.device)
+            pad_d = torch.empty((n, k), dtype=torch.float32, device=data.device)
+            updated_map = torch.empty((n_old,), dtype=torch.uint8, device=data.device)
+            pairs = torch.from_numpy(np.stack([ids, sources])).to(data.device) if ids.shape[0] else None
+            stream = _OnTorchStream(torch, ordinal)  # (made after the uploads: a side stream waits for them)
+            try:
+                ids_ptr, sources_ptr = (pairs[0].data_ptr(), pairs[1].data_ptr()) if pairs is not None else (0, 0)
+                _capi.device_update_rows(ordinal, stream.ptr, dim, described(data), described(xs_fresh), described(xs_updated),
+                                         (sources_ptr, ids_ptr, ids.shape[0]), new_data.data_ptr(), _DEVICE_DTYPES[out_name])
+                _capi.device_update_graph(ordinal, stream.ptr, gidx.data_ptr(), gdist.data_ptr(), n_old, k, ids_ptr, ids.shape[0], n,
+                                          updated_map.data_ptr(), pad_i.data_ptr(), pad_d.data_ptr())
+            finally:
+                stream.done()
+            # pynndescent_.py:2512-2517: the old graph's entries as "old" edges, then the forest's; no random fill
+            dev_in = _DeviceInput(new_data, _DEVICE_DTYPES[out_name], ordinal, self.n_neighbors, as_given=True)
+            graph, build_stats, n_leaves = _build_graph(
+                new_data, m, self.n_neighbors, n_trees, eff_leaf_size, self.max_rptree_depth, eff_max_candidates, self.n_iters,
+                self.delta, self.rng_state, tree_states[0], ordinal, forest=True, old_graph=(pad_i, pad_d), check_finite=True,
+                verbose=self.verbose, dev_in=dev_in)
+        self.n_trees, self._build_stats = n_trees, build_stats
+        self._rp_forest = _DeviceForestSentinel(n_trees, n_leaves, eff_leaf_size)
+        was_prepared = self._prepared
+        for name in ("_device_order", "_device_search_graph", "_device_prepare_stats", "_raw_data", "_neighbor_graph", "_search_graph",
+                     "_quantized_data", "_searcher", "_search_forest", "_vertex_order"):
+            d.pop(name, None)
+        self._device_data, self._device_graph = new_data, graph  # (the caller's original tensor is released)
+        if was_prepared:  # pynndescent_.py:2538-2553: the derived structures are rebuilt, from the tensors when _prepares_on_device
             self.prepare()
 
 
@@ -1168,7 +1335,13 @@ def exact_knn(data, queries=None, k=10, metric="euclidean", rows=None, device=0,
     in the metric's own space (the correction ``NNDescent.neighbor_graph`` applies), rows ascending, ties to the smaller id;
     with ``return_stats`` also the call's statistics (rows that needed the float64 tier, kernel times).  The metrics and the
     input rules are the class's: dot rows and queries are L2-normalised, hellinger takes no negative entry, NaN / inf raise
-    the reference's error.  ``k`` is at most 256 and at most the number of rows."""
+    the reference's error.  ``k`` is at most 256 and at most the number of rows.
+
+    ``data`` may be a device array (a 2-D ``torch.Tensor`` on a HIP device, float32 / float16 / bfloat16 / float64): the search
+    then runs on the tensor where it is, on torch's current stream, and the answers are tensors on that device -- int32 ids, and
+    the distances corrected on the device (float32 or float64, as ``NNDescent.neighbor_graph`` returns them for the metric; dot
+    normalises on the device, within rounding of the host's rows).  ``queries`` on the other side are moved to where ``data`` is;
+    ``rows`` may be a host array or a tensor (the ids are range-checked on the host)."""
     if queries is not None and rows is not None:
         raise ValueError("exact_knn takes `queries` (external points) or `rows` (ids of data rows), not both")
     k = int(k)
@@ -1176,6 +1349,9 @@ def exact_knn(data, queries=None, k=10, metric="euclidean", rows=None, device=0,
         raise NotImplementedError("pynndescent_amd.exact_knn keeps at most k <= 256 neighbours per row (got k = %d)" % k)
     m = _metric_record(metric)
     _no_exact_for_proxy(metric, m, "exact_knn")
+    if _is_device_array(data):
+        return _exact_knn_device(data, queries, k, metric, m, rows, device, return_stats)
+    queries, rows = _rows_to_host(queries), _ids_to_host(rows)  # (the results live where the data lives)
     data = _check_array_no_scan(data)
     n = data.shape[0]
     if k < 1 or k > n:
@@ -1215,6 +1391,69 @@ def exact_knn(data, queries=None, k=10, metric="euclidean", rows=None, device=0,
     return (idx, dist, stats) if return_stats else (idx, dist)
 
 
+def _exact_knn_device(data, queries, k, metric, m, rows, device, return_stats):
+    """``exact_knn`` for a device array ``data`` (``k``, the metric and queries-or-rows are checked already): an auxiliary handle
+    bound to the tensor on torch's current stream, the device entries of csrc/exact.hip, the answers corrected on the device.
+    ``rows``: a host array or a tensor of ids (range-checked on the host), or an int32 tensor on the data's device that the
+    caller has checked (``NNDescent._recall_device``).  What crosses the bus: the row ids, host queries, and scalars."""
+    data, dtype, ordinal = _check_device_array(data, device)
+    n, dim = int(data.shape[0]), int(data.shape[1])
+    if k < 1 or k > n:
+        raise ValueError("k must be in 1 .. n = %d (got %d)" % (n, k))
+    torch = _torch()
+    with torch.cuda.device(ordinal):
+        q = q_dtype = None
+        if queries is not None:
+            if _is_device_array(queries):
+                q, q_dtype, q_ordinal = _check_device_array(queries, what="queries")
+                if q_ordinal != ordinal:
+                    q = q.to(data.device)
+            else:
+                q, q_dtype = torch.from_numpy(_check_array_no_scan(queries)).to(data.device), _capi.NND_DTYPE_FLOAT32
+            if q.shape[1] != dim:
+                raise ValueError("queries must have shape (n_queries, %d)" % dim)
+            if q.shape[0] and not bool(torch.isfinite(q).all().item()):  # one scalar; only the error path brings the queries down
+                from sklearn.utils import assert_all_finite
+
+                assert_all_finite(_rows_to_host(q))
+            if m.nonnegative and q.shape[0] and bool((q.min() < 0).item()):
+                raise ValueError(_NEGATIVE_HELLINGER)
+        rows_dev = None
+        if rows is not None:
+            if _is_device_array(rows) and _dtype_name(rows) == "int32" and len(rows.shape) == 1 and rows.device == data.device:
+                rows_dev = rows
+            else:
+                rows = np.ascontiguousarray(_ids_to_host(rows), dtype=np.int64).reshape(-1)
+                if rows.size and (rows.min() < 0 or rows.max() >= n):
+                    raise ValueError("rows must be ids in [0, %d)" % n)
+                rows_dev = torch.from_numpy(rows.astype(np.int32)).to(data.device)
+        n_out = int(q.shape[0]) if q is not None else (n if rows_dev is None else int(rows_dev.shape[0]))
+        idx = torch.empty((n_out, k), dtype=torch.int32, device=data.device)
+        dist = torch.empty((n_out, k), dtype=torch.float32, device=data.device)
+        stream = _OnTorchStream(torch, ordinal)  # (made after the uploads: a side stream waits for them)
+        # an auxiliary handle: the rows and their prepared copy, no k-lists
+        builder = _capi.Builder(n, dim, m.code, k, 0, 60, 200, min(60, k), 1, 0.001, [1, 2, 3], [4, 5, 6], device=ordinal,
+                                flags=_capi.NND_FLAG_NO_GRAPH)
+        try:
+            builder.set_stream(stream.ptr)
+            builder.set_data_device_typed(data.data_ptr(), dtype, keepalive=data)  # (dot: normalised there, as the class does)
+            _raise_if_nonfinite(builder, lambda: _rows_to_host(data))
+            if m.nonnegative and builder.data_negative():
+                raise ValueError(_NEGATIVE_HELLINGER)
+            if n_out == 0:  # (nothing asked for: an empty tensor has no address to hand over)
+                stats = dict(_capi.NNDExactStats().as_dict(), slices=0)
+            elif q is not None:
+                stats = builder.exact_knn_device(k, idx.data_ptr(), dist.data_ptr(), q_ptr=q.data_ptr(), q_dtype=q_dtype, n_q=n_out)
+            else:
+                stats = builder.exact_knn_device(k, idx.data_ptr(), dist.data_ptr(), rows_ptr=0 if rows_dev is None else rows_dev.data_ptr(),
+                                                 n_rows=n_out)
+        finally:
+            builder.close()
+            stream.done()
+        dist = _device_corrected(torch, dist, m, ordinal)
+    return (idx, dist, stats) if return_stats else (idx, dist)
+
+
 def _build_graph(data, m, n_neighbors, n_trees, leaf_size, max_depth, max_candidates, n_iters, delta, rng_state, tree_rng,
                  device, forest=False, leaf_array=None, init_graph=None, init_dist=None, old_graph=None, random_fill=False,
                  check_finite=False, stats=True, verbose=False, announce=False, dev_in=None):
@@ -1222,7 +1461,8 @@ def _build_graph(data, m, n_neighbors, n_trees, leaf_size, max_depth, max_candid
     ``check_finite``), ``forest`` built on the device, the graph seeded -- ``old_graph`` (ids, distances) as "old" edges,
     then ``init_graph`` / ``init_dist``, the caller's ``leaf_array`` or the forest's leaves, then the random fill when
     ``random_fill`` -- NN-descent to the stop rule, the graph out.  ``announce``: the constructor's verbose line.  ``dev_in``
-    (a ``_DeviceInput``): the rows are a device array, read in place on torch's stream, and the graph comes out as tensors.  Returns
+    (a ``_DeviceInput``): the rows are a device array, read in place on torch's stream, and the graph comes out as tensors;
+    ``old_graph`` and ``init_graph`` / ``init_dist`` may then be tensors as well (int32 / float32, read in place).  Returns
     ``((indices, distances), the stats (when ``stats``), the forest's leaf count)``."""
     n = data.shape[0]
     builder = _capi.Builder(n, data.shape[1], m.code, n_neighbors, n_trees, leaf_size, max_depth, max_candidates, n_iters,
@@ -1244,8 +1484,13 @@ def _build_graph(data, m, n_neighbors, n_trees, leaf_size, max_depth, max_candid
             print(ts(), "NN descent for", str(n_iters), "iterations")
         if old_graph is not None:
             builder.reset_graph()
-            builder.init_from_neighbor_graph(*old_graph)
-        if init_graph is not None:
+            if _is_device_array(old_graph[0]):  # (update() of a device-built index: the invalidated graph is a pair of tensors)
+                builder.init_from_neighbor_graph_device(old_graph[0].data_ptr(), old_graph[1].data_ptr(), old_graph[0].shape[1])
+            else:
+                builder.init_from_neighbor_graph(*old_graph)
+        if init_graph is not None and _is_device_array(init_graph):  # int32 / float32, contiguous, on the data's device
+            builder.init_from_graph_device(init_graph.data_ptr(), 0 if init_dist is None else init_dist.data_ptr(), init_graph.shape[1])
+        elif init_graph is not None:
             builder.init_from_graph(init_graph, init_dist)
         elif leaf_array is not None:
             builder.init_from_leaf_array(leaf_array)
@@ -1311,9 +1556,9 @@ def _check_supported_sizes(n_neighbors, max_candidates, init_graph):
         raise NotImplementedError(
             "pynndescent_amd supports n_neighbors <= 256 and max_candidates <= 128 (got n_neighbors=%s, max_candidates=%s); "
             "use pynndescent.NNDescent (or pynndescent_amd.make_index) for wider graphs" % (n_neighbors, max_candidates))
-    if init_graph is not None and np.ndim(init_graph) == 2 and np.shape(init_graph)[1] > 256:
+    if init_graph is not None and len(_shape_of(init_graph)) == 2 and _shape_of(init_graph)[1] > 256:
         raise NotImplementedError("pynndescent_amd supports init_graph with at most 256 columns (got %d); use "
-                                  "pynndescent.NNDescent" % np.shape(init_graph)[1])
+                                  "pynndescent.NNDescent" % _shape_of(init_graph)[1])
 
 
 def make_index(data, *args, **kwargs):
