@@ -17,12 +17,19 @@
 //     entries of its rank-ordered segment -- no per-node search at all;
 //   * level-synchronous: one pass over all positions per level computes the three margins of every member of every
 //     splittable node (thread per member, float32 multiply-then-add in dimension order -- the arithmetic of the
-//     reference's loops, rp_trees.py:865-869, 990-993; no FMA contraction -- so the sides and with them the tree
-//     match the un-jitted reference run bit for bit), one pass picks the winner per node, the stable partition reuses
-//     the scan / scatter kernels of the RP forest (rpforest.hip);
+//     reference's loops, rp_trees.py:865-869, 990-993 -- so the sides and with them the tree match the un-jitted
+//     reference run bit for bit), one pass picks the winner per node, the stable partition reuses the scan / scatter
+//     kernels of the RP forest (rpforest.hip).  "Multiply-then-add" is a property of the compiled code, not of the
+//     spelling: the compiler's default fuses a * b + c into one FMA wherever both operations may contract, and the
+//     __fmul_rn / __fadd_rn intrinsics are plain operators to it.  Every float operation of this file is therefore
+//     one of the hub_* helpers below, compiled under "#pragma clang fp contract(off)"; division and square root are
+//     the correctly rounded ones.  tests/hubtree_reference.py restates this arithmetic (mode exact32) and
+//     tests/test_gpu_hubtree_exact.py holds the tree to it byte for byte;
 //   * the host assembles the per-level tables into the pre-order FlatTree (nnd_hub_tree_fetch).
-// Only the all-candidates-invalid fallback differs: the reference re-draws every member's side from the sequential
-// Tausworthe stream (rp_trees.py:902-910, in recursion order); here it is the counter hash of (seed, id, depth).
+// The tree does not depend on the handle's seed.  When every candidate of a node is one-sided the reference re-draws
+// every member's side from its Tausworthe stream (rp_trees.py:902-910) but returns best_balance = 0, so the caller
+// makes that node a leaf (rp_trees.py:1091-1096) and the drawn sides are never used.  k_hub_margins still records a
+// coin per member (bit 3 of sidebits, the counter hash of (seed, id, depth)), but k_hub_choose never selects it.
 #include <algorithm>
 #include <vector>
 
@@ -30,7 +37,15 @@
 #include "state.h"
 
 #define HUB_EPS 1e-8f             // rp_trees.py:23
-#define HUB_MIN_BALANCE 0.1f      // rp_trees.py:803 MIN_SPLIT_BALANCE
+#define HUB_MIN_BALANCE 0.1f      // rp_trees.py:798 MIN_SPLIT_BALANCE
+
+// One correctly rounded float32 operation each, never fused with a neighbour (see the header).
+#pragma clang fp contract(off)
+static __device__ __forceinline__ float hub_add(float a, float b) { return a + b; }
+static __device__ __forceinline__ float hub_sub(float a, float b) { return a - b; }
+static __device__ __forceinline__ float hub_mul(float a, float b) { return a * b; }
+static __device__ __forceinline__ float hub_div(float a, float b) { return __fdiv_rn(a, b); }
+static __device__ __forceinline__ float hub_sqrt(float a) { return __fsqrt_rn(a); }
 
 // ------------------------------------------------------------------ kernels --
 __global__ void k_hub_init(int32_t *__restrict__ ord_id, int32_t *__restrict__ pos_id, int32_t *__restrict__ pos_rk, int64_t n,
@@ -65,30 +80,30 @@ __global__ void k_hub_planes(const float *__restrict__ x, int d, const int32_t *
     if (!angular) {
         float o = 0.0f;
         for (int j = 0; j < d; j++) {
-            const float v = __fsub_rn(xl[j], xr[j]);
+            const float v = hub_sub(xl[j], xr[j]);
             h[j] = v;
-            o = __fsub_rn(o, __fmul_rn(__fmul_rn(v, __fadd_rn(xl[j], xr[j])), 0.5f));
+            o = hub_sub(o, hub_mul(hub_mul(v, hub_add(xl[j], xr[j])), 0.5f));
         }
         off[s * 4 + c] = o;
     } else {
         float ln = 0.0f, rn = 0.0f;
         for (int j = 0; j < d; j++) {
-            ln = __fadd_rn(ln, __fmul_rn(xl[j], xl[j]));  // utils.py:86-91 norm()
-            rn = __fadd_rn(rn, __fmul_rn(xr[j], xr[j]));
+            ln = hub_add(ln, hub_mul(xl[j], xl[j]));  // utils.py:86-91 norm()
+            rn = hub_add(rn, hub_mul(xr[j], xr[j]));
         }
-        ln = __fsqrt_rn(ln);
-        rn = __fsqrt_rn(rn);
+        ln = hub_sqrt(ln);
+        rn = hub_sqrt(rn);
         if (fabsf(ln) < HUB_EPS) ln = 1.0f;
         if (fabsf(rn) < HUB_EPS) rn = 1.0f;
         float hn = 0.0f;
         for (int j = 0; j < d; j++) {
-            const float v = __fsub_rn(__fdiv_rn(xl[j], ln), __fdiv_rn(xr[j], rn));
+            const float v = hub_sub(hub_div(xl[j], ln), hub_div(xr[j], rn));
             h[j] = v;
-            hn = __fadd_rn(hn, __fmul_rn(v, v));
+            hn = hub_add(hn, hub_mul(v, v));
         }
-        hn = __fsqrt_rn(hn);
+        hn = hub_sqrt(hn);
         if (fabsf(hn) < HUB_EPS) hn = 1.0f;
-        for (int j = 0; j < d; j++) h[j] = __fdiv_rn(h[j], hn);
+        for (int j = 0; j < d; j++) h[j] = hub_div(h[j], hn);
         off[s * 4 + c] = 0.0f;
     }
 }
@@ -113,10 +128,10 @@ __global__ __launch_bounds__(256) void k_hub_margins(const float *__restrict__ x
         float m0 = off[s * 4 + 0], m1 = off[s * 4 + 1], m2 = off[s * 4 + 2];
         for (int j = 0; j < d; j++) {  // rp_trees.py:866-869 / 991-993: margin += hyperplane_vector[d] * data[indices[i], d]
             const float xv = xr[j];
-            m0 = __fadd_rn(m0, __fmul_rn(h0[j], xv));
+            m0 = hub_add(m0, hub_mul(h0[j], xv));
             if (ncand == 3) {
-                m1 = __fadd_rn(m1, __fmul_rn(h1[j], xv));
-                m2 = __fadd_rn(m2, __fmul_rn(h2[j], xv));
+                m1 = hub_add(m1, hub_mul(h1[j], xv));
+                m2 = hub_add(m2, hub_mul(h2[j], xv));
             }
         }
         const float mm[3] = {m0, m1, m2};
@@ -164,7 +179,7 @@ __global__ void k_hub_choose(const int32_t *__restrict__ seg_len, const uint8_t 
     for (int c = 0; c < ncand; c++) {
         const int nl = nleft4[s * 4 + c], nr = len - nl;
         if (nl == 0 || nr == 0) continue;
-        const float bal = __fdiv_rn((float)(nl < nr ? nl : nr), (float)len);
+        const float bal = hub_div((float)(nl < nr ? nl : nr), (float)len);
         if (bal > best) {
             best = bal;
             bc = c;

@@ -512,6 +512,21 @@ def gen_hub_tree(ref):
     save("hub_tree", **out)
 
 
+def gen_hub_tree_edges(ref):
+    """The reference's own make_hub_tree + convert_tree_format, un-jitted, on every case of tests/hubtree_cases.py with at most
+    1000 points: the five FlatTree tables only (the inputs are rebuilt from the cases' seeds).  tests/test_hubtree_reference_cpu.py
+    pins the host model of csrc/hubtree.hip to them on machines without the reference."""
+    from tests import hubtree_cases as HC
+
+    out = {}
+    for name in HC.small():
+        hyper, offs, children, indices, leaf = HC.reference_tables(HC.case(name))
+        print("hub tree edges", name, "nodes", children.shape[0], "leaf_size", leaf)
+        out.update({name + "/hyperplanes": hyper, name + "/offsets": offs, name + "/children": children, name + "/indices": indices,
+                    name + "/leaf_size": np.int32(leaf)})
+    save("hub_tree_edges", **out)
+
+
 def gen_update(ref):
     """NNDescent.update (pynndescent_.py:2381-2553): fresh rows appended + some rows replaced, warm start from the
     old graph (flag 0) + a smaller forest, no random init."""
@@ -551,6 +566,7 @@ GENERATORS = {
     "search_graph": gen_search_graph,
     "search_graph_modes": gen_search_graph_modes,
     "hub_tree": gen_hub_tree,
+    "hub_tree_edges": gen_hub_tree_edges,
     "update": gen_update,
 }
 
