@@ -130,6 +130,9 @@ typedef struct nnd_params {
 
 /* test hook: nnd_exact_knn_* answers every row through the float64 tier (tests/test_gpu_exact.py compares the two tiers) */
 #define NND_FLAG_TEST_EXACT_F64 32768
+/* test hook: nnd_init_random launches one wave per row (the earlier form) where it would let one wave screen 64 rows and work on
+ * those that are not full: the two forms must leave identical k-lists (tests/test_gpu_random_init.py) */
+#define NND_FLAG_TEST_RANDOM_INIT_ROWWISE 65536
 
 /* Run-time statistics for measurement (bench.py roofline). */
 typedef struct nnd_stats {

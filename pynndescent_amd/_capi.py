@@ -42,6 +42,7 @@ NND_FLAG_TEST_JOIN_UNSTAGED = 16384  # test hook: k_local_join_w with the member
 NND_FLAG_TEST_SELECT_HALF = 4096  # test hook: the fused selection with 32 lanes per vertex where 16 would do (k <= 16, max_candidates <= 16)
 NND_FLAG_TEST_SAMPLE_NOMEM = 2048  # test hook: the sampler's record regions "cannot be allocated": the handle must fall back to the hashed slots
 NND_FLAG_TEST_EXACT_F64 = 32768  # test hook: the exact search answers every row through its float64 tier
+NND_FLAG_TEST_RANDOM_INIT_ROWWISE = 65536  # test hook: init_random with one wave per row instead of one screening wave per 64 rows
 NND_FLAG_TEST_SAMPLE_ATOMIC = 256  # test hook: reverse offers by one global atomicMin per edge (rounds 1-4) instead of the bucketed transposition
 
 

@@ -5,9 +5,47 @@
 // (good enough to RANK); the distances handed back are recomputed from the ORIGINAL rows in the
 // reference's own formulas with float64 accumulation (metric.h nnd_ref_acc / nnd_ref_dist, hellinger's
 // terms in float32 as the reference's), then rows are re-sorted by that value.
+//
+// The float64 arithmetic of the codes 0 / 1 on rows of whole 16-byte chunks (d % 4 == 0, k <= 64) is spelled operation by
+// operation, so that the bits handed back are a property of this text and not of the compiler's choice of what to fuse:
+//   * the 16 lanes of a group split a row by chunks: lane l takes the chunks t = 4 l + 64 i, i = 0, 1, ..;
+//   * a chunk's four terms p0..p3 (code 0: p = (a - b)^2 on the float64 difference; code 1: a b, a a and b b, three sums)
+//     join as s = p1, s = fma(., ., s) for p0, p2, p3 in that order, then the lane's sum takes s by one addition;
+//   * the 16 lanes' sums join by the xor butterfly 8, 4, 2, 1 (v += partner's v; every lane ends on the same bits);
+//   * the value is (float) of that sum (code 1: of nnd_ref_dist on the three sums).
+// fin_* below are the only float64 operations of that path, compiled with contraction off; tests/finalize_reference.py restates
+// them and tests/test_gpu_finalize_exact.py holds the kernels to it bit for bit.  The codes 2..6, rows with d % 4 != 0 and
+// k_finalize_wide sum as nnd_ref_acc does.
 #include "common.h"
+#include "merge.h"
 #include "metric.h"
 #include "state.h"
+
+__device__ __forceinline__ double fin_sub(double a, double b) {
+#pragma clang fp contract(off)
+    return a - b;
+}
+__device__ __forceinline__ double fin_add(double a, double b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+// one chunk of <a, b>: p1 first, then p0, p2, p3 by fused multiply-add
+__device__ __forceinline__ double fin_chunk(double a0, double a1, double a2, double a3, double b0, double b1, double b2, double b3) {
+#pragma clang fp contract(off)
+    double s = a1 * b1;
+    s = __builtin_fma(a0, b0, s);
+    s = __builtin_fma(a2, b2, s);
+    return __builtin_fma(a3, b3, s);
+}
+// code 0: the chunk's squared differences
+__device__ __forceinline__ double fin_chunk_sq(const float4 a, const float4 b) {
+    const double d0 = fin_sub((double)a.x, (double)b.x), d1 = fin_sub((double)a.y, (double)b.y);
+    const double d2 = fin_sub((double)a.z, (double)b.z), d3 = fin_sub((double)a.w, (double)b.w);
+    return fin_chunk(d0, d1, d2, d3, d0, d1, d2, d3);
+}
+__device__ __forceinline__ double fin_chunk_dot(const float4 a, const float4 b) {
+    return fin_chunk((double)a.x, (double)a.y, (double)a.z, (double)a.w, (double)b.x, (double)b.y, (double)b.z, (double)b.w);
+}
 
 // one coordinate pair into the float64 sums, hellinger's terms as the reference takes them (metric.h)
 template <int FAM>
@@ -73,16 +111,15 @@ __global__ __launch_bounds__(256, METRIC == 0 ? 6 : 4) void k_finalize(const flo
                 for (int u = 0; u < 4; u++) q[u] = *(const float4 *)(xu[u] + t);
 #pragma unroll
                 for (int u = 0; u < 4; u++) {
-                    const double a0 = a.x, a1 = a.y, a2 = a.z, a3 = a.w;
-                    const double b0 = q[u].x, b1 = q[u].y, b2 = q[u].z, b3 = q[u].w;
-                    if (metric == 0) {  // codes 0 / 1: the four terms of a chunk are summed before they join the accumulator (the
-                                        // order every build since the first has summed in; nnd_ref_acc's terms, grouped)
-                        dot[u] += (a0 - b0) * (a0 - b0) + (a1 - b1) * (a1 - b1) + (a2 - b2) * (a2 - b2) + (a3 - b3) * (a3 - b3);
+                    if (metric == 0) {  // codes 0 / 1: a chunk's four terms are summed before they join the accumulator (file header)
+                        dot[u] = fin_add(dot[u], fin_chunk_sq(a, q[u]));
                     } else if (metric == 1) {
-                        dot[u] += a0 * b0 + a1 * b1 + a2 * b2 + a3 * b3;
-                        nx[u] += a0 * a0 + a1 * a1 + a2 * a2 + a3 * a3;
-                        ny[u] += b0 * b0 + b1 * b1 + b2 * b2 + b3 * b3;
+                        dot[u] = fin_add(dot[u], fin_chunk_dot(a, q[u]));
+                        nx[u] = fin_add(nx[u], fin_chunk_dot(a, a));
+                        ny[u] = fin_add(ny[u], fin_chunk_dot(q[u], q[u]));
                     } else {
+                        const double a0 = a.x, a1 = a.y, a2 = a.z, a3 = a.w;
+                        const double b0 = q[u].x, b1 = q[u].y, b2 = q[u].z, b3 = q[u].w;
                         fin_acc<FAM>(metric, a0 - mua, b0 - mub[u], dot[u], nx[u], ny[u]);
                         fin_acc<FAM>(metric, a1 - mua, b1 - mub[u], dot[u], nx[u], ny[u]);
                         fin_acc<FAM>(metric, a2 - mua, b2 - mub[u], dot[u], nx[u], ny[u]);
@@ -117,6 +154,124 @@ __global__ __launch_bounds__(256, METRIC == 0 ? 6 : 4) void k_finalize(const flo
         r += (kj < mykey || (kj == mykey && j < lane)) ? 1 : 0;
     }
     if (lane < k) {
+        out_idx[(v - lo) * k + r] = e == NND_EMPTY_E ? -1 : (int32_t)(e & NND_IDX_MASK);
+        out_dist[(v - lo) * k + r] = mine;
+    }
+}
+
+// k <= 16, codes 0 / 1, d % 4 == 0: one row per 16-lane group, four rows per wave.  Everything a row needs stays inside its
+// DPP row, so nothing goes through the LDS pipe and the per-wave bookkeeping is shared by four rows:
+//   * every lane of a group reads the row's 16 entries itself (four 16-byte loads of one address per group);
+//   * the group takes its neighbours four at a time (16 neighbour rows in flight per wave, as in k_finalize);
+//   * the butterfly's partners come by DPP moves.  No single pattern reaches lane l ^ 4, so lane p of the group plays chunk
+//     lane c = p ^ 3 for p & 4, p otherwise: then c ^ 8, c ^ 4, c ^ 2, c ^ 1 sit at p ror 8, the half-row mirror 7 - (p & 7),
+//     p ^ 2, p ^ 1 -- the pairs and their order are the file header's, only the lane that holds a chunk differs;
+//   * the four sums of a round join in one butterfly: at the first step a lane keeps two of the four sums and hands the other
+//     two to its partner, at the second it keeps one of two, so a lane's four additions per step become 2, 1, 1, 1 -- each still
+//     v[c] + v[c ^ o] of the same two lanes.  Quad q of the row ends on the sum of the round's neighbour q;
+//   * lane p therefore keeps neighbour 4 (p & 3) + (p >> 2); the rank is a count over the 15 row rotations of the (distance,
+//     index) keys.
+template <int CTRL>
+__device__ __forceinline__ double fin_dpp_f64(double v) {
+    const uint64_t b = (uint64_t)__double_as_longlong(v);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)b, CTRL, 0xF, 0xF, true);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(b >> 32), CTRL, 0xF, 0xF, true);
+    return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
+}
+__device__ __forceinline__ double fin_row_sum_f64(double v) {  // all 16 lanes of the row active
+    v = fin_add(v, fin_dpp_f64<NND_DPP_ROW_ROR(8)>(v));
+    v = fin_add(v, fin_dpp_f64<NND_DPP_ROW_HALF_MIRROR>(v));
+    v = fin_add(v, fin_dpp_f64<NND_DPP_QUAD_XOR2>(v));
+    return fin_add(v, fin_dpp_f64<NND_DPP_QUAD_XOR1>(v));
+}
+// four sums per lane -> quad q of the row holds the 16-lane sum of v[q] (on every one of its lanes)
+__device__ __forceinline__ double fin_row_sum4_f64(const double (&v)[4], int p16) {
+    const bool lo8 = (p16 & 8) == 0, lo4 = (p16 & 4) == 0;
+    const double a = fin_add(lo8 ? v[0] : v[2], fin_dpp_f64<NND_DPP_ROW_ROR(8)>(lo8 ? v[2] : v[0]));
+    const double b = fin_add(lo8 ? v[1] : v[3], fin_dpp_f64<NND_DPP_ROW_ROR(8)>(lo8 ? v[3] : v[1]));
+    double s = fin_add(lo4 ? a : b, fin_dpp_f64<NND_DPP_ROW_HALF_MIRROR>(lo4 ? b : a));
+    s = fin_add(s, fin_dpp_f64<NND_DPP_QUAD_XOR2>(s));
+    return fin_add(s, fin_dpp_f64<NND_DPP_QUAD_XOR1>(s));
+}
+// keys of the row that sort before mine: rotation T brings lane p the key of lane (p - T) & 15, which wins a tie iff p >= T
+template <int T>
+__device__ __forceinline__ int fin_row_rank(uint32_t klo, uint32_t khi, int p16) {
+    if constexpr (T == 0) return 0;
+    else {
+        const uint32_t olo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)klo, NND_DPP_ROW_ROR(T), 0xF, 0xF, true);
+        const uint32_t ohi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)khi, NND_DPP_ROW_ROR(T), 0xF, 0xF, true);
+        const uint64_t other = ((uint64_t)ohi << 32) | olo, mine = ((uint64_t)khi << 32) | klo;
+        return (((other < mine) | ((other == mine) & (p16 >= T))) ? 1 : 0) + fin_row_rank<T - 1>(klo, khi, p16);
+    }
+}
+
+template <int METRIC>
+__global__ __launch_bounds__(256, METRIC == 0 ? 6 : 4) void k_finalize16(const float *__restrict__ x, int d, int64_t lo, int64_t n, int k, int ks,
+                                                    const uint32_t *__restrict__ knn_e, const int32_t *__restrict__ order,
+                                                    int32_t *__restrict__ out_idx, float *__restrict__ out_dist) {
+    static_assert(METRIC == 0 || METRIC == 1, "the other codes go through k_finalize");
+    const int lane = nnd_lane(), w = threadIdx.x >> 6, grp = lane >> 4, p16 = lane & 15;
+    const int c16 = (p16 & 4) ? (p16 ^ 3) : p16;  // the chunk lane this lane plays
+    // rows in `order`, one contiguous eighth per XCD (see k_finalize)
+    int64_t b = blockIdx.x;
+    if ((gridDim.x & 7) == 0) b = (b & 7) * (gridDim.x >> 3) + (b >> 3);
+    const int64_t g0 = lo + (b * 4 + w) * 4;
+    if (g0 >= n) return;
+    // a group past the end works on the last row again and stores nothing: every lane of the wave stays active for the DPP moves
+    const bool row_on = g0 + grp < n;
+    const int64_t g = row_on ? g0 + grp : n - 1;
+    const int64_t v = order ? (int64_t)order[g] : g;
+    const uint32_t *er = knn_e + v * ks;  // (ks = 16: a 64-byte row)
+    const int j16 = 4 * (p16 & 3) + (p16 >> 2);  // the neighbour whose value ends on this lane
+    const uint32_t e = j16 < k ? er[j16] : NND_EMPTY_E;
+    u32x4 eb[4];
+#pragma unroll
+    for (int bt = 0; bt < 4; bt++) eb[bt] = *(const u32x4 *)(er + 4 * bt);
+    const uint32_t row_bytes = (uint32_t)d * 4u;  // (one 64-bit multiply-add per row address)
+    const char *xc = (const char *)(x + 4 * c16);
+    const float *xv = (const float *)(xc + (uint64_t)v * row_bytes);
+    float mine = INFINITY;
+#pragma unroll
+    for (int bt = 0; bt < 4; bt++) {
+        if (4 * bt >= k) break;
+        const float *xu[4];
+        double dot[4], ny[4], nx = 0.0;
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const uint32_t ej = eb[bt][u];
+            const bool on = 4 * bt + u < k && ej != NND_EMPTY_E;  // (an empty slot reads row 0; its lane hands back +inf)
+            xu[u] = (const float *)(xc + (uint64_t)(on ? (ej & NND_IDX_MASK) : 0u) * row_bytes);
+            dot[u] = ny[u] = 0.0;
+        }
+        for (int t = 4 * c16; t < d; t += 64) {
+            const int o = t - 4 * c16;
+            const float4 a = *(const float4 *)(xv + o);
+            float4 q[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) q[u] = *(const float4 *)(xu[u] + o);
+            if (METRIC == 1) nx = fin_add(nx, fin_chunk_dot(a, a));
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                if (METRIC == 0) {
+                    dot[u] = fin_add(dot[u], fin_chunk_sq(a, q[u]));
+                } else {
+                    dot[u] = fin_add(dot[u], fin_chunk_dot(a, q[u]));
+                    ny[u] = fin_add(ny[u], fin_chunk_dot(q[u], q[u]));
+                }
+            }
+        }
+        const double dt = fin_row_sum4_f64(dot, p16);  // neighbour 4 bt + (p16 >> 2)
+        float val;
+        if (METRIC == 0) val = (float)dt;
+        else val = (float)nnd_ref_dist<NND_CODES_01>(1, dt, fin_row_sum_f64(nx), fin_row_sum4_f64(ny, p16));
+        if ((p16 & 3) == bt) mine = val;
+    }
+    if (e == NND_EMPTY_E) mine = INFINITY;
+    // rank by (distance, index); empty entries are (+inf, 0x7FFFFFFF) and land at the tail, lanes past k behind every key
+    const uint32_t myidx = e == NND_EMPTY_E ? NND_IDX_MASK : (e & NND_IDX_MASK);
+    const uint32_t klo = j16 < k ? myidx : 0xFFFFFFFFu, khi = j16 < k ? __float_as_uint(mine) : 0xFFFFFFFFu;
+    const int r = fin_row_rank<15>(klo, khi, p16);
+    if (row_on && j16 < k) {
         out_idx[(v - lo) * k + r] = e == NND_EMPTY_E ? -1 : (int32_t)(e & NND_IDX_MASK);
         out_dist[(v - lo) * k + r] = mine;
     }
@@ -172,6 +327,13 @@ int nnd_launch_finalize(nnd_ctx *ctx, int32_t *out_idx_dev, float *out_dist_dev)
     if (ctx->k > 64) {
         hipLaunchKernelGGL(ctx->p.metric >= 2 ? k_finalize_wide<true> : k_finalize_wide<false>, dim3(grid), dim3(256), 0, ctx->stream, ctx->x_orig, ctx->d, ctx->own_lo, ctx->own_hi, ctx->k, ctx->ks,
                            ctx->p.metric, ctx->knn_e, out_idx_dev, out_dist_dev);
+        NND_HIP_CHECK(hipGetLastError());
+        return 0;
+    }
+    if (ctx->k <= 16 && ctx->p.metric <= 1 && (ctx->d & 3) == 0) {  // four rows per wave
+        grid = ((unsigned)((ctx->own_hi - ctx->own_lo + 15) / 16) + 7u) & ~7u;
+        hipLaunchKernelGGL(ctx->p.metric == 0 ? k_finalize16<0> : k_finalize16<1>, dim3(grid), dim3(256), 0, ctx->stream, ctx->x_orig, ctx->d,
+                           ctx->own_lo, ctx->own_hi, ctx->k, ctx->ks, ctx->knn_e, nnd_vertex_order(ctx), out_idx_dev, out_dist_dev);
         NND_HIP_CHECK(hipGetLastError());
         return 0;
     }

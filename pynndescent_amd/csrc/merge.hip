@@ -202,14 +202,11 @@ int nnd_launch_merge(nnd_ctx *ctx) {
     return 0;
 }
 
-// init_random (pynndescent_.py:188-203): rows that are not full get (k - filled) random candidates
-__global__ __launch_bounds__(256) void k_random_init(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
-                                                     int metric, int64_t n, int64_t lo, int64_t hi, int k, int ks,
-                                                     const uint32_t *__restrict__ knn_e, uint32_t seed,
-                                                     uint64_t *__restrict__ pbuf, uint8_t *__restrict__ pdirty, int pcap) {
-    const int lane = nnd_lane(), w = threadIdx.x >> 6;
-    const int64_t v = lo + (int64_t)blockIdx.x * 4 + w;
-    if (v >= hi) return;
+// init_random (pynndescent_.py:188-203): rows that are not full get (k - filled) random candidates.  One row, the whole wave:
+__device__ __forceinline__ void random_init_row(const float *__restrict__ xp, int dp, const float *__restrict__ nrm, int metric, int64_t n,
+                                                int64_t v, int k, int ks, const uint32_t *__restrict__ knn_e, uint32_t seed,
+                                                uint64_t *__restrict__ pbuf, uint8_t *__restrict__ pdirty, int pcap) {
+    const int lane = nnd_lane();
     int filled = 0;
     for (int j0 = 0; j0 < k; j0 += 64) {  // (wide rows: several entries per lane)
         const uint32_t e = j0 + lane < k ? knn_e[v * ks + j0 + lane] : NND_EMPTY_E;
@@ -233,13 +230,51 @@ __global__ __launch_bounds__(256) void k_random_init(const float *__restrict__ x
     }
     if (lane == 0) pdirty[v] = 1;
 }
+// A wave screens 64 rows first, one row per lane: the lane counts the filled ones of its row's first k slots (wherever they sit in
+// the row; rows are ks = 16 m words, read 16 bytes at a time), and the wave then works through the rows that are not full.  After
+// leaf seeding that is next to none of them: a full row costs its 64 bytes and no wave of its own.
+__global__ __launch_bounds__(256) void k_random_init(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
+                                                     int metric, int64_t n, int64_t lo, int64_t hi, int k, int ks,
+                                                     const uint32_t *__restrict__ knn_e, uint32_t seed,
+                                                     uint64_t *__restrict__ pbuf, uint8_t *__restrict__ pdirty, int pcap) {
+    const int lane = nnd_lane(), w = threadIdx.x >> 6;
+    const int64_t base = lo + ((int64_t)blockIdx.x * 4 + w) * 64;
+    if (base >= hi) return;
+    int filled = k;  // (lanes past the last row: nothing to do)
+    if (base + lane < hi) {
+        filled = 0;
+        const u32x4 *row = (const u32x4 *)(knn_e + (base + lane) * ks);
+        for (int c = 0; 4 * c < k; c++) {
+            const u32x4 e = row[c];
+#pragma unroll
+            for (int q = 0; q < 4; q++) filled += (4 * c + q < k && e[q] != NND_EMPTY_E) ? 1 : 0;
+        }
+    }
+    unsigned long long m = __ballot(filled < k);
+    while (m) {
+        const int64_t v = base + __builtin_ctzll(m);
+        m &= m - 1;
+        random_init_row(xp, dp, nrm, metric, n, v, k, ks, knn_e, seed, pbuf, pdirty, pcap);
+    }
+}
+// one wave per row (NND_FLAG_TEST_RANDOM_INIT_ROWWISE: the form the screening kernel is compared with)
+__global__ __launch_bounds__(256) void k_random_init_rowwise(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
+                                                             int metric, int64_t n, int64_t lo, int64_t hi, int k, int ks,
+                                                             const uint32_t *__restrict__ knn_e, uint32_t seed,
+                                                             uint64_t *__restrict__ pbuf, uint8_t *__restrict__ pdirty, int pcap) {
+    const int64_t v = lo + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (v >= hi) return;
+    random_init_row(xp, dp, nrm, metric, n, v, k, ks, knn_e, seed, pbuf, pdirty, pcap);
+}
 
 int nnd_launch_random_init(nnd_ctx *ctx) {
+    const bool rowwise = (ctx->p.flags & NND_FLAG_TEST_RANDOM_INIT_ROWWISE) != 0;
+    const int64_t rows = ctx->own_hi - ctx->own_lo;
     for (int pass = 0; pass < (ctx->k + 63) / 64; pass++) {
         ctx->pbuf_clean = false;
-        hipLaunchKernelGGL(k_random_init, dim3((unsigned)((ctx->own_hi - ctx->own_lo + 3) / 4)), dim3(256), 0, ctx->stream, ctx->xp,
-                           ctx->dp, ctx->nrm, ctx->p.metric, ctx->n, ctx->own_lo, ctx->own_hi, ctx->k, ctx->ks, ctx->knn_e,
-                           ctx->seed ^ 0x3C6EF372u ^ (uint32_t)(pass * 0x9E3779B9u), ctx->pbuf, ctx->pdirty, ctx->pcap);
+        hipLaunchKernelGGL(rowwise ? k_random_init_rowwise : k_random_init, dim3((unsigned)(rowwise ? (rows + 3) / 4 : (rows + 255) / 256)),
+                           dim3(256), 0, ctx->stream, ctx->xp, ctx->dp, ctx->nrm, ctx->p.metric, ctx->n, ctx->own_lo, ctx->own_hi, ctx->k,
+                           ctx->ks, ctx->knn_e, ctx->seed ^ 0x3C6EF372u ^ (uint32_t)(pass * 0x9E3779B9u), ctx->pbuf, ctx->pdirty, ctx->pcap);
         NND_HIP_CHECK(hipGetLastError());
         if (nnd_launch_merge(ctx)) return 1;
     }

@@ -350,24 +350,18 @@ int nnd_zero_counters(nnd_ctx *ctx) {
     NND_HIP_CHECK(hipMemsetAsync(ctx->counters, 0, sizeof(long long) * CNT_COUNT * NND_CNT_STRIPES, ctx->stream));
     return 0;
 }
-// stripes -> one value per counter, on the device (the host then reads CNT_COUNT words, not CNT_COUNT * 512)
-__global__ __launch_bounds__(256) void k_counters_reduce(const long long *__restrict__ counters, long long *__restrict__ out) {
-    __shared__ long long red[256];
-    for (int c = 0; c < CNT_COUNT; c++) {
-        long long s = 0;
-        for (int i = threadIdx.x; i < NND_CNT_STRIPES; i += 256) s += counters[(size_t)i * CNT_COUNT + c];
-        red[threadIdx.x] = s;
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) {
-            if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) out[c] = red[0];
-        __syncthreads();
-    }
+// stripes -> one value per counter, on the device (the host then reads CNT_COUNT words, not CNT_COUNT * 512): one wave per counter,
+// every lane sums its share of the stripes, the wave's lanes join by shuffles (integer sums: exact in any order)
+__global__ __launch_bounds__(64 * CNT_COUNT) void k_counters_reduce(const long long *__restrict__ counters, long long *__restrict__ out) {
+    const int lane = nnd_lane(), c = threadIdx.x >> 6;
+    long long s = 0;
+    for (int i = lane; i < NND_CNT_STRIPES; i += 64) s += counters[(size_t)i * CNT_COUNT + c];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if (lane == 0) out[c] = s;
 }
 int nnd_read_counters(nnd_ctx *ctx) {
-    hipLaunchKernelGGL(k_counters_reduce, dim3(1), dim3(256), 0, ctx->stream, ctx->counters, ctx->counters_sum);
+    hipLaunchKernelGGL(k_counters_reduce, dim3(1), dim3(64 * CNT_COUNT), 0, ctx->stream, ctx->counters, ctx->counters_sum);
     NND_HIP_CHECK(hipGetLastError());
     NND_HIP_CHECK(hipMemcpyAsync(ctx->h_pin->counters, ctx->counters_sum, sizeof(long long) * CNT_COUNT, hipMemcpyDeviceToHost, ctx->stream));
     NND_HIP_CHECK(nnd_sync_spin(ctx));
