@@ -38,8 +38,12 @@ __host__ __device__ __forceinline__ uint32_t nnd_unmix32(uint32_t x) {
 __host__ __device__ __forceinline__ uint32_t nnd_hash2(uint32_t seed, uint32_t a) {
     return nnd_mix32(seed ^ nnd_mix32(a + 0x9E3779B9u));
 }
+// nnd_hash3(seed, a, b) from h = nnd_hash2(seed, a): for callers that hash many b under one (seed, a)
+__host__ __device__ __forceinline__ uint32_t nnd_hash3_from(uint32_t h, uint32_t b) {
+    return nnd_mix32(h ^ nnd_mix32(b * 0x85EBCA6Bu + 0xC2B2AE35u));
+}
 __host__ __device__ __forceinline__ uint32_t nnd_hash3(uint32_t seed, uint32_t a, uint32_t b) {
-    return nnd_mix32(nnd_hash2(seed, a) ^ nnd_mix32(b * 0x85EBCA6Bu + 0xC2B2AE35u));
+    return nnd_hash3_from(nnd_hash2(seed, a), b);
 }
 // the word that stands for (entry a, compared entry b) in the coin hash of a pruning test (prune.hip): positions in a row of at
 // most NND_WIDE_K entries, a different word for every pair -- every test of a row has a coin of its own

@@ -450,12 +450,32 @@ __device__ __forceinline__ void nnd_select_half(uint32_t *__restrict__ knn_e, in
 // up to 47 (79) LDS broadcasts with a 64-bit compare per item: 400 of the 500 us of k_rev_select
 // (profiles/r06_sample_select_floor.log).  Only the max_candidates smallest keys matter, and the keys' priority words are
 // uniform 32-bit hashes: the items whose priority lies under a threshold tau -- chosen so that ~max_candidates + 10 pass -- are
-// compacted (at most two per lane), the reverse offers among THEM are screened against the forward ids, and only they are
-// ranked.  An item's rank among the survivors is its rank among all items (every smaller key passed too), so the lists are the
-// ones the full ranking writes, entry for entry (tests/test_gpu_kernels.py: exact-sample test, half-wave = wave test).  tau
-// moves (bisection) in the few per cent of the cases where fewer than max_candidates or more than 2 LW items pass.
-//   F = list[0 .. LW): the class's forward keys (the ids the duplicate screen reads); C = list[LW .. 3 LW): the survivors.
+// compacted (at most two per lane) and only they are ranked.  An item's rank among the survivors is its rank among all items
+// (every smaller key passed too), so the lists are the ones the full ranking writes, entry for entry, whatever tau was
+// (tests/test_gpu_select_lean.py, tests/test_gpu_kernels.py: exact-sample test, half-wave = wave test).  tau moves (bisection)
+// in the < 1 % of the cases where fewer than max_candidates or more than 2 LW items pass.
+//
+// The lean form (profiles/select_trim_ab.txt).  The kernel is limited by vector issue, and a trip of the round-6 form spent
+// ~343 VALU wave-instructions: 37 forming keys, 30 on counts and a float division for tau, 48 compacting, 70 in the duplicate
+// screen, 110 ranking (20 survivors), 48 storing.  Now ~222 (173 when every group of the wave has <= LW survivors):
+//   keys      26  the vertex's salt and its half of the forward hash come from LDS (k_rev_select forms them once per vertex);
+//   screen    34  BEFORE the compaction, straight-line: the row's forward ids are broadcast from LDS (4 x ds_read_b128) and every
+//                 reverse offer is compared with all 16 -- no trip count, no per-step predicate, no second pass over survivors;
+//                 the counts below are then exact, and nothing has to be taken out of C again;
+//   tau       17  a reciprocal and a multiply (any estimate is correct, the bisection repairs a bad one);
+//   compact   40  the masks of the valid items are taken once, a round's ballots are the compares' own results;
+//   rank   45..94 C is padded with empty keys, which rank behind every key: four keys per step (2 x ds_read_b128), a 64-bit
+//                 compare and an add-with-carry per (key, survivor), 11 + 2.1 / 4.1 VALU per survivor with one / two keys per
+//                 lane -- the floor of rank counting on this ISA;
+//   stores    11  the ids go to their rank's place of an LDS row pre-set to -1, the row leaves in ONE 64-byte store.
+// Priced and not built: ranks and screen by DPP row rotations (a rotation costs a VALU move per dword, 4 per 64-bit key and
+// step against 0 for the LDS broadcast, which the LDS pipe carries: 12 against 4.1 VALU per survivor); a tighter tau target
+// (mc + 8: 177.0 against 178.0 VALU per wave trip for rank + compaction -- the trip count of a wave is set by its groups with
+// <= 2 mc + 4 items, which are ranked whole; mc + 4: 180.2, 9 % of the waves take a second round).
+//   F = list[0 .. LW / 2): the class's forward ids, lane order; O = list[LW / 2 .. LW): the candidate row;
+//   C = list[LW .. 3 LW): the survivors.
 // Returns the rank of this lane's forward item (1 << 30: not sampled).
+typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
 template <int LW>
 __device__ __forceinline__ int nnd_group_max(int v) {  // the largest v over the wave's groups (v is uniform inside a group)
     int m = __builtin_amdgcn_readlane(v, 0);
@@ -469,71 +489,69 @@ __device__ __forceinline__ int nnd_group_max(int v) {  // the largest v over the
 template <int LW, int NR>
 __device__ __forceinline__ int nnd_select_class(bool act, bool fvalid, uint64_t fkey, const bool (&rvalid)[NR], const uint64_t (&rkey)[NR], int mc,
                                                 int mcp, int32_t *dst, uint64_t *list, int j, int gb) {
-    constexpr uint32_t GM = LW == 32 ? 0xFFFFFFFFu : ((1u << (LW & 31)) - 1u);
+    static_assert(LW == 16, "the lean form: one 16-lane row per vertex, a candidate row of LW entries (mcp == LW)");
+    constexpr uint32_t GM = (1u << LW) - 1u;
     constexpr int CAP = 2 * LW;
-    uint64_t *F = list, *C = list + LW;
+    uint32_t *F = (uint32_t *)list;     // LW forward ids, lane order
+    int32_t *O = (int32_t *)list + LW;  // the class's candidate row
+    uint64_t *C = list + LW;
     const uint32_t below = (1u << j) - 1u;
-    const uint32_t fmask = (uint32_t)(__ballot(fvalid) >> gb) & GM;
-    const int nf = __popc(fmask);
-    if (fvalid) F[__popc(fmask & below)] = fkey;
-    int M = nf;
+    // utils.py:427-430: an id already in the list is not pushed again (a reverse offer that repeats a forward edge of the class).
+    // The row's forward ids are broadcast from LDS, 16 straight-line compares per reverse offer; an empty lane holds ~0, no id.
+    F[j] = fvalid ? (uint32_t)fkey : 0xFFFFFFFFu;
+    O[j] = -1;
+    nnd_wave_lds_sync();
+    bool rv[NR];
 #pragma unroll
-    for (int i = 0; i < NR; i++) M += __popc((uint32_t)(__ballot(rvalid[i]) >> gb) & GM);
+    for (int i = 0; i < NR; i++) rv[i] = rvalid[i];
+#pragma unroll
+    for (int q = 0; q < LW; q += 4) {
+        const u32x4 f = *(const u32x4 *)(F + q);
+#pragma unroll
+        for (int i = 0; i < NR; i++) {
+            const uint32_t s = (uint32_t)rkey[i];
+            rv[i] = rv[i] && f[0] != s && f[1] != s && f[2] != s && f[3] != s;
+        }
+    }
+    // (the masks of the valid items are taken once: inside the loop a ballot is then the compare's own result and one scalar AND)
+    const unsigned long long bf = __ballot(fvalid);
+    unsigned long long br[NR];
+    int M = __popc((uint32_t)(bf >> gb) & GM);
+#pragma unroll
+    for (int i = 0; i < NR; i++) {
+        br[i] = __ballot(rv[i]);
+        M += __popc((uint32_t)(br[i] >> gb) & GM);
+    }
     const uint32_t fp = (uint32_t)(fkey >> 32);
     uint32_t rp[NR];
 #pragma unroll
     for (int i = 0; i < NR; i++) rp[i] = (uint32_t)(rkey[i] >> 32);
     uint32_t tau = 0xFFFFFFFFu, lo = 0u, hi = 0xFFFFFFFFu;
     if (M > CAP || M > 2 * mc + 4) {  // (a list that is not much longer than what is kept is ranked whole: nothing to gain from a threshold)
-        const float t = (float)(mc + 10) * 4294967296.0f / (float)M;
+        const float t = (float)(mc + 10) * 4294967296.0f * __builtin_amdgcn_rcpf((float)M);  // any estimate is correct: see above
         tau = t >= 4294967040.0f ? 0xFFFFFFFFu : (uint32_t)t;
     }
-    const int nfm = nnd_group_max<LW>(nf);  // wave-uniform trip count of the screen
-    int count = 0, cv = 0, tpos = -1, cn = 0;
-    uint64_t key0 = NND_EMPTY_KEY, key1 = NND_EMPTY_KEY;
-    bool dup0 = false, dup1 = false;
+    int count = 0, tpos = -1;
 #pragma unroll 1
     for (int iter = 0; iter < 30; iter++) {
-        nnd_wave_lds_sync();  // F is written / the previous round's reads of C are done
+        nnd_wave_lds_sync();  // the previous reads of C are done
+        C[j] = NND_EMPTY_KEY;  // what no survivor overwrites ranks behind every key: the rank loop needs no bound per group
+        C[LW + j] = NND_EMPTY_KEY;
         const bool fpass = fvalid && fp <= tau;
-        const uint32_t pm = (uint32_t)(__ballot(fpass) >> gb) & GM;
-        const int npf = __popc(pm);
+        const uint32_t pm = (uint32_t)((__ballot(fp <= tau) & bf) >> gb) & GM;
         tpos = fpass ? __popc(pm & below) : -1;
-        if (fpass) C[tpos] = fkey;  // (npf <= nf <= LW)
-        int pos = npf;
+        if (fpass) C[tpos] = fkey;  // (at most LW forward items)
+        int pos = __popc(pm);
 #pragma unroll
         for (int i = 0; i < NR; i++) {
-            const bool rpass = rvalid[i] && rp[i] <= tau;
-            const uint32_t m = (uint32_t)(__ballot(rpass) >> gb) & GM;
+            const bool rpass = rv[i] && rp[i] <= tau;
+            const uint32_t m = (uint32_t)((__ballot(rp[i] <= tau) & br[i]) >> gb) & GM;
             const int p = pos + __popc(m & below);
             if (rpass && p < CAP) C[p] = rkey[i];
             pos += __popc(m);
         }
         count = pos;
-        nnd_wave_lds_sync();
-        cn = count < CAP ? count : CAP;
-        const bool two = nnd_group_max<LW>(cn) > LW;  // wave-uniform: some group holds a second survivor per lane
-        key0 = j < cn ? C[j] : NND_EMPTY_KEY;
-        key1 = (two && LW + j < cn) ? C[LW + j] : NND_EMPTY_KEY;
-        // utils.py:427-430: an id already in the list is not pushed again (a reverse offer that repeats a forward edge of the class)
-        const bool rev0 = j >= npf && j < cn, rev1 = two && LW + j < cn;  // (survivors LW .. are reverse offers: npf <= LW)
-        dup0 = dup1 = false;
-        if (__ballot(rev0 || rev1)) {
-            const uint32_t s0 = (uint32_t)key0, s1 = (uint32_t)key1;
-            if (two) {
-#pragma unroll 4
-                for (int q = 0; q < nfm; q++) {
-                    const uint32_t f = (uint32_t)F[q];
-                    dup0 = dup0 || (rev0 && q < nf && f == s0);
-                    dup1 = dup1 || (rev1 && q < nf && f == s1);
-                }
-            } else {
-#pragma unroll 4
-                for (int q = 0; q < nfm; q++) dup0 = dup0 || (rev0 && q < nf && (uint32_t)F[q] == s0);
-            }
-        }
-        cv = cn - __popc((uint32_t)(__ballot(dup0) >> gb) & GM) - __popc((uint32_t)(__ballot(dup1) >> gb) & GM);
-        const bool ok = count <= CAP && (cv >= mc || tau == 0xFFFFFFFFu);
+        const bool ok = count <= CAP && (count >= mc || tau == 0xFFFFFFFFu);
         if (!__ballot(!ok)) break;  // every vertex of the wave is settled
         if (!ok) {
             if (count > CAP) {
@@ -546,32 +564,32 @@ __device__ __forceinline__ int nnd_select_class(bool act, bool fvalid, uint64_t 
             }
         }
     }
-    if (dup0) key0 = NND_EMPTY_KEY;
-    if (dup1) key1 = NND_EMPTY_KEY;
-    const int cmax = nnd_group_max<LW>(cn);  // wave-uniform trip count
-    nnd_wave_lds_sync();  // every lane holds its survivors: C is rewritten with the screened keys
-    C[j] = key0;
-    if (cmax > LW) C[LW + j] = key1;
     nnd_wave_lds_sync();
-    int r0 = 0, r1 = 0;
-    if (cmax > LW) {
-#pragma unroll 4
-        for (int q = 0; q < cmax; q++) {
-            const uint64_t kq = C[q];
-            const bool in = q < cn;
-            r0 += (in && kq < key0) ? 1 : 0;
-            r1 += (in && kq < key1) ? 1 : 0;
+    const int cn = count < CAP ? count : CAP;
+    const int cmax = nnd_group_max<LW>(cn);  // wave-uniform trip count, taken in steps of four keys (C holds 2 LW)
+    const int filled = cn < mc ? cn : mc;
+    const uint64_t key0 = C[j];
+    int r0 = 0;
+    if (cmax > LW) {  // some group holds a second survivor per lane
+        const uint64_t key1 = C[LW + j];
+        int r1 = 0;
+#pragma unroll 2
+        for (int q = 0; q < cmax; q += 4) {
+            const u64x2 a = *(const u64x2 *)(C + q), b = *(const u64x2 *)(C + q + 2);
+            r0 += (a[0] < key0 ? 1 : 0) + (a[1] < key0 ? 1 : 0) + (b[0] < key0 ? 1 : 0) + (b[1] < key0 ? 1 : 0);
+            r1 += (a[0] < key1 ? 1 : 0) + (a[1] < key1 ? 1 : 0) + (b[0] < key1 ? 1 : 0) + (b[1] < key1 ? 1 : 0);
         }
+        if (r1 < filled) O[r1] = (int32_t)(uint32_t)key1;  // (an empty key's rank is cn >= filled)
     } else {
-#pragma unroll 4
-        for (int q = 0; q < cmax; q++) r0 += (q < cn && C[q] < key0) ? 1 : 0;
+#pragma unroll 2
+        for (int q = 0; q < cmax; q += 4) {
+            const u64x2 a = *(const u64x2 *)(C + q), b = *(const u64x2 *)(C + q + 2);
+            r0 += (a[0] < key0 ? 1 : 0) + (a[1] < key0 ? 1 : 0) + (b[0] < key0 ? 1 : 0) + (b[1] < key0 ? 1 : 0);
+        }
     }
-    if (act) {
-        if (key0 != NND_EMPTY_KEY && r0 < mc) dst[r0] = (int32_t)(uint32_t)key0;
-        if (key1 != NND_EMPTY_KEY && r1 < mc) dst[r1] = (int32_t)(uint32_t)key1;
-        const int filled = cv < mc ? cv : mc;
-        for (int q = filled + j; q < mcp; q += LW) dst[q] = -1;
-    }
+    if (r0 < filled) O[r0] = (int32_t)(uint32_t)key0;
+    nnd_wave_lds_sync();
+    if (act) dst[j] = O[j];  // the whole row in one store: ids in rank order, -1 behind them
     const int got = __builtin_amdgcn_ds_bpermute((gb + (tpos >= 0 ? tpos : 0)) << 2, r0);
     return tpos >= 0 ? got : (1 << 30);
 }
@@ -580,15 +598,17 @@ __device__ __forceinline__ int nnd_select_class(bool act, bool fvalid, uint64_t 
 // words per class (rwo: old-class bank, rwn: new-class bank; slot i * LW + j) however the caller obtained them -- from rbuf
 // (k_sample_select_h) or from the LDS banks of the bucketed reverse pass (k_rev_select).  `list`: 3 LW keys of LDS per group.
 // WIDE (the first pass of a build: every edge new, both banks hold new-class offers, nnd_offer_addr): one class.
+// The vertex's two hashes come from the caller, which forms them once per vertex and not once per lane:
+// vh.x = nnd_offer_salt(it_seed, vv), vh.y = nnd_hash2(it_seed, vv), the vertex's half of the forward priorities.
 template <bool WIDE, int LW, int NRC>
-__device__ __forceinline__ void nnd_select_group(uint32_t *__restrict__ knn_e, int k, int ks, int mc, int mcp, uint32_t it_seed,
+__device__ __forceinline__ void nnd_select_group(uint32_t *__restrict__ knn_e, int k, int ks, int mc, int mcp, uint2 vh,
                                                  int32_t *__restrict__ cand, int64_t vv, bool act, uint32_t e, const uint32_t (&rwo)[NRC],
                                                  const uint32_t (&rwn)[NRC], uint64_t *list, int j, int gb) {
-    const uint32_t salt = nnd_offer_salt(it_seed, (uint32_t)vv);
+    const uint32_t salt = vh.x;
     const bool valid = e != NND_EMPTY_E;
     const uint32_t u = e & NND_IDX_MASK;
     const uint32_t cls = e >> 31;
-    const uint64_t fkey = ((uint64_t)nnd_hash3(it_seed, (uint32_t)vv, u) << 32) | u;
+    const uint64_t fkey = ((uint64_t)nnd_hash3_from(vh.y, u) << 32) | u;
     int32_t *out = cand + vv * 2 * mcp;  // layout [new | old]
     int my_rank;  // rank of this lane's forward new edge among the new offers
     if constexpr (WIDE) {
@@ -959,6 +979,8 @@ __global__ __launch_bounds__(1024) void k_rev_fill(rv_inbox ib, int64_t row0, in
 // runs the selection (nnd_select_half) for 8 of the bucket's targets in turn, the next one's k-list row requested while the
 // current one is ranked.  LDS: 32 KB banks + 16 KB selection lists: three workgroups = 24 waves per CU (measured against 1024
 // threads -- 4 targets per half-wave, 32 KB of lists, two workgroups = 32 waves per CU: 0.52 instead of 0.41 ms per launch).
+// LW = 16 (four targets per wave, nnd_select_group): the 32 groups take the bucket's ACTIVE vertices in bucket order, up to four
+// each, and the inactive ones get their empty new lists in one pass of the whole workgroup (profiles/select_trim_ab.txt).
 template <bool WIDE, int LW>
 __global__ __launch_bounds__(RV_SEL_THREADS) void k_rev_select(rv_inbox ib, int64_t row0, int64_t n, const int32_t *__restrict__ order,
                                                     const uint8_t *__restrict__ active,
@@ -970,9 +992,13 @@ __global__ __launch_bounds__(RV_SEL_THREADS) void k_rev_select(rv_inbox ib, int6
     constexpr int NBANK = WIDE ? NB : 2 * NB;
     __shared__ uint32_t bank[NB * ROW];
     __shared__ uint32_t cnt[NBANK];
-    __shared__ uint64_t skey[NG][LW == 32 ? 128 : 3 * LW];  // LW = 32: the two 64-item class lists of nnd_select_half
+    __shared__ __attribute__((aligned(16))) uint64_t skey[NG][LW == 32 ? 128 : 3 * LW];  // LW = 32: the two 64-item class lists of nnd_select_half
     __shared__ int32_t vtx[NB];
+    __shared__ uint2 vhash[LW == 16 ? NB : 1];  // LW = 16: (offer salt, nnd_hash2(it_seed, v)) of every active vertex of the bucket
+    __shared__ uint8_t alist[2][LW == 16 ? 64 : 1];
+    __shared__ int acnt[2], icnt[2];  // active / inactive vertices in each of the two lists' halves of the bucket
     __shared__ int any_ovf;
+    static_assert(NB == 128, "the active lists: one per wave of the first NB threads");
     const int tid = threadIdx.x, lane = tid & 63, grp = tid / LW, j = lane & (LW - 1), gb = lane & (64 - LW);
     const int64_t b = blockIdx.x;
     // the bucket's vertices: v >= 0 active, -2 - v inactive, -1 beyond the last vertex
@@ -984,6 +1010,18 @@ __global__ __launch_bounds__(RV_SEL_THREADS) void k_rev_select(rv_inbox ib, int6
             if (!active[v]) v = -2 - v;
         }
         vtx[tid] = v;
+        if constexpr (LW == 16) {  // once per vertex here, not once per lane in the target loop
+            const uint32_t vid = v >= 0 ? (uint32_t)v : 0u;
+            vhash[tid] = make_uint2(nnd_offer_salt(it_seed, vid), nnd_hash2(it_seed, vid));
+            // ... and the bucket's ACTIVE vertices in bucket order, one list per wave of this block (NB = two waves)
+            const unsigned long long am = __ballot(v >= 0);
+            if (v >= 0) alist[tid >> 6][nnd_prefix_popc(am)] = (uint8_t)tid;
+            const unsigned long long im = __ballot(v <= -2);
+            if (lane == 0) {
+                acnt[tid >> 6] = __popcll(am);
+                icnt[tid >> 6] = __popcll(im);
+            }
+        }
     }
     for (int i = tid; i < NB * ROW; i += NT) bank[i] = NND_EMPTY_SLOT;
     for (int i = tid; i < NBANK; i += NT) cnt[i] = 0;
@@ -991,9 +1029,30 @@ __global__ __launch_bounds__(RV_SEL_THREADS) void k_rev_select(rv_inbox ib, int6
     __syncthreads();
     // the k-list row of this group's first target is requested now and lands during the fill phase; the next target's
     // row is requested while the current one is ranked
+    // LW = 16: a group's r-th target is the (r * NG + grp)-th ACTIVE vertex of the bucket, so that late iterations -- a fifth of
+    // the vertices active, scattered over the bucket -- run one or two full rounds instead of PER rounds of mostly idle groups
+    // (what is written for a vertex does not depend on which group writes it, or when).  LW = 32: target r * NG + grp, as ever.
+    int nact = NB, rounds = PER;
+    uint32_t tpk = 0;  // LW = 16: the group's targets of rounds 0 .. PER - 1, one byte each
+    if constexpr (LW == 16) {
+        static_assert(PER <= 4 && NB <= 256, "a byte per target, a word per group");
+        const int c0 = acnt[0];
+        nact = c0 + acnt[1];
+        rounds = (nact + NG - 1) / NG;
+#pragma unroll
+        for (int r = 0; r < PER; r++) {
+            const int idx = r * NG + grp;
+            if (idx < nact) tpk |= (uint32_t)(idx < c0 ? alist[0][idx] : alist[1][idx - c0]) << (8 * r);
+        }
+    }
+    auto has_target = [&](int r) -> bool { return LW == 32 || r * NG + grp < nact; };
+    auto target_of = [&](int r) -> int {  // bucket index of the group's target of round r (0 where it has none)
+        if constexpr (LW == 16) return (int)((tpk >> (8 * r)) & 0xFFu);
+        return r * NG + grp;
+    };
     uint32_t pre_e = NND_EMPTY_E;
-    {
-        const int32_t v0 = vtx[grp];
+    if (rounds > 0) {
+        const int32_t v0 = has_target(0) ? vtx[target_of(0)] : -1;
         if (v0 >= 0 && j < k) pre_e = knn_e[(int64_t)v0 * ks + j];
     }
     rv_each_record(ib, b, tid, NT, [&](uint32_t w, uint32_t m) {
@@ -1016,25 +1075,34 @@ __global__ __launch_bounds__(RV_SEL_THREADS) void k_rev_select(rv_inbox ib, int6
         __syncthreads();
     }
     uint64_t *sk = skey[grp];
+    if constexpr (LW == 16) {  // no new candidate can reach an inactive vertex: empty new list (its old list is never read)
+        const int todo = icnt[0] + icnt[1] ? NB * LW : 0;  // (workgroup-uniform: none in the first pass of a build)
+        for (int i = tid; i < todo; i += NT) {
+            const int32_t v = vtx[i / LW];
+            if (v <= -2)
+                for (int q = i % LW; q < mcp; q += LW) cand[(int64_t)(-2 - v) * 2 * mcp + q] = -1;
+        }
+    }
 #pragma unroll 1
-    for (int r = 0; r < PER; r++) {
-        const int tl = r * NG + grp;
-        const int32_t v = vtx[tl];
+    for (int r = 0; r < rounds; r++) {
+        const int tl = target_of(r);
+        const int32_t v = has_target(r) ? vtx[tl] : -1;
         const bool act = v >= 0;
         const uint32_t e = pre_e;
         pre_e = NND_EMPTY_E;
-        if (r + 1 < PER) {
-            const int32_t vn = vtx[tl + NG];
+        if (r + 1 < rounds) {
+            const int32_t vn = has_target(r + 1) ? vtx[target_of(r + 1)] : -1;
             if (vn >= 0 && j < k) pre_e = knn_e[(int64_t)vn * ks + j];
         }
-        if (v <= -2)  // no new candidate can reach the vertex: empty new list (its old list is never read)
+        if (LW == 32 && v <= -2)  // (as above)
             for (int q = j; q < mcp; q += LW) cand[(int64_t)(-2 - v) * 2 * mcp + q] = -1;
         if (!__ballot(act)) continue;  // wave-uniform
+        const int tb = tl;  // (a group without a target: 0, and act is false)
         uint32_t rwo[NRC], rwn[NRC];
 #pragma unroll
         for (int i = 0; i < NRC; i++) {
-            rwo[i] = act ? bank[tl * ROW + i * LW + j] : NND_EMPTY_SLOT;
-            rwn[i] = act ? bank[tl * ROW + RCAP + i * LW + j] : NND_EMPTY_SLOT;
+            rwo[i] = act ? bank[tb * ROW + i * LW + j] : NND_EMPTY_SLOT;
+            rwn[i] = act ? bank[tb * ROW + RCAP + i * LW + j] : NND_EMPTY_SLOT;
         }
         nnd_wave_lds_sync();  // the previous target's lists are done with
 #ifdef NND_RV_NOSELECT  // timing experiments only: the kernel without the per-target selection
@@ -1044,7 +1112,7 @@ __global__ __launch_bounds__(RV_SEL_THREADS) void k_rev_select(rv_inbox ib, int6
         if constexpr (LW == 32)
             nnd_select_half<WIDE>(knn_e, k, ks, mc, mcp, it_seed, cand, act ? (int64_t)v : 0, act, e, rwo[0], rwn[0], (uint64_t(*)[64])sk, j, gb);
         else
-            nnd_select_group<WIDE, LW, NRC>(knn_e, k, ks, mc, mcp, it_seed, cand, act ? (int64_t)v : 0, act, e, rwo, rwn, sk, j, gb);
+            nnd_select_group<WIDE, LW, NRC>(knn_e, k, ks, mc, mcp, vhash[tb], cand, act ? (int64_t)v : 0, act, e, rwo, rwn, sk, j, gb);
     }
 }
 
@@ -1197,7 +1265,7 @@ static int launch_sample_bucketed(nnd_ctx *ctx, uint32_t it_seed, bool wide, con
     ib.ov = ctx->rv_ov;
     ib.ov_count = ov_count;
     if (fused) {
-        const bool q16 = ctx->ks == 16 && ctx->mc <= 16 && !(ctx->p.flags & NND_FLAG_TEST_SELECT_HALF);  // four targets per wave
+        const bool q16 = ctx->ks == 16 && ctx->mc <= 16 && ctx->mcp == 16 && !(ctx->p.flags & NND_FLAG_TEST_SELECT_HALF);  // four targets per wave
         auto kern = q16 ? (wide ? k_rev_select<true, 16> : k_rev_select<false, 16>) : (wide ? k_rev_select<true, 32> : k_rev_select<false, 32>);
         hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(RV_SEL_THREADS), 0, st, ib, row0, n_rows, order, ctx->active, ctx->knn_e, ctx->k, ctx->ks, ctx->mc, ctx->mcp,
                            it_seed, ctx->cand);
