@@ -216,6 +216,21 @@ int32_t nnd_device_rows_f32(int32_t device, void *hip_stream, const void *src_de
 #define NND_CORRECT_ALT_INNER_PRODUCT 3 /* float64 out: d >= FLT_MAX ? 0 : -1 / d (an IEEE division: the host's bits) */
 #define NND_CORRECT_ALT_HELLINGER 4     /* float64 out: sqrt(1 - 2^-d) */
 int32_t nnd_device_correct(int32_t device, void *hip_stream, int32_t kind, const float *in_dev, void *out_dev, int64_t count);
+/* ---- metrics with a fixed linear map (csrc/linear.hip; DESIGN.md "Metrics"): seuclidean, wminkowski with p = 2, mahalanobis ----
+ * They are NND_METRIC_SQEUCLIDEAN after y = A (x - c): the caller transforms every row that enters the library (training
+ * rows, update() rows, queries) with one of the two entries below and hands the float32 result to the entry points of metric
+ * code 0, unchanged.  kind: */
+#define NND_LINEAR_DIAGONAL 0 /* map: dim floats, y_j = map[j] (x_j - shift_j): V^-1/2 of seuclidean, sqrt(w) of wminkowski */
+#define NND_LINEAR_DENSE 1    /* map: (dim, dim) row-major, y_j = sum_k map[j, k] (x_k - shift_k): a factor of mahalanobis' VI */
+/* (n, dim) float32 rows at x -> (n, dim) float32 rows at y (x == y is not allowed for the dense kind).  A row's result
+ * depends on that row alone, bit for bit: not on n, on its position, on the other rows of the call, or on the run.
+ * nnd_device_linear_rows: every pointer is a device pointer on `device`; queued on `hip_stream` (NULL: the default stream),
+ * nothing is waited for, nothing is allocated.  nnd_linear_rows_host: every pointer is a host pointer; the rows go up, the
+ * result comes down, and the call returns when it is there (its device buffers are one nnd_scratch, released on return). */
+int32_t nnd_device_linear_rows(int32_t device, void *hip_stream, int32_t kind, int32_t dim, const float *map_dev, const float *shift_dev,
+                               const float *x_dev, int64_t n, float *y_dev);
+int32_t nnd_linear_rows_host(int32_t device, int32_t kind, int32_t dim, const float *map, const float *shift, const float *x, int64_t n,
+                             float *y);
 /* ---- NNDescent.update() / recall() of an index whose rows and graph live on the device (csrc/devarray.hip, csrc/update.hip;
  * DESIGN.md "Device arrays") ----  Like the two entries above: a device ordinal and a HIP stream (NULL: the device's default
  * stream) instead of a handle, everything is queued there and nothing is waited for; every array is the caller's and must stay

@@ -27,6 +27,7 @@ METRIC_CODES = {"euclidean": NND_METRIC_SQEUCLIDEAN, "l2": NND_METRIC_SQEUCLIDEA
 # element types of a device array (include/pynnd_amd.h NND_DTYPE_*) and the corrections of nnd_device_correct (NND_CORRECT_*)
 NND_DTYPE_FLOAT32, NND_DTYPE_FLOAT16, NND_DTYPE_BFLOAT16, NND_DTYPE_FLOAT64 = 0, 1, 2, 3
 NND_CORRECT_COPY, NND_CORRECT_SQRT, NND_CORRECT_ALT_COSINE, NND_CORRECT_ALT_INNER_PRODUCT, NND_CORRECT_ALT_HELLINGER = 0, 1, 2, 3, 4
+NND_LINEAR_DIAGONAL, NND_LINEAR_DENSE = 0, 1  # the kinds of a metric's linear map (include/pynnd_amd.h NND_LINEAR_*, csrc/linear.hip)
 NND_FLAG_NO_GRAPH = 1  # auxiliary handle: no k-lists / candidate / proposal tables (pruning pass, hub tree)
 NND_FLAG_NO_PREP = 2   # ... and no prepared copy of the rows (hub tree only)
 NND_FLAG_TEST_SELECT_WAVE = 4  # test hook: the one-wave-per-vertex selection kernel
@@ -198,6 +199,8 @@ _SIGNATURES = [
     ("nnd_set_data_device_typed", C.c_int32, [_H, C.c_void_p, C.c_int32]),
     ("nnd_device_rows_f32", C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
     ("nnd_device_correct", C.c_int32, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64]),
+    ("nnd_device_linear_rows", C.c_int32, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    ("nnd_linear_rows_host", C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     ("nnd_device_update_rows", C.c_int32, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int64,
                                            C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32]),
     ("nnd_device_update_graph", C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int64,
@@ -905,6 +908,29 @@ def device_rows_f32(device, stream_ptr, src_ptr, dtype, n, dim, normalize, dst_p
     if lib.nnd_device_rows_f32(int(device), C.c_void_p(int(stream_ptr)) if stream_ptr else None, C.c_void_p(int(src_ptr)), int(dtype),
                                int(n), int(dim), 1 if normalize else 0, C.c_void_p(int(dst_ptr))) != 0:
         raise NNDError(lib.nnd_last_global_error().decode())
+
+
+def device_linear_rows(device, stream_ptr, kind, dim, map_ptr, shift_ptr, x_ptr, n, y_ptr):
+    """``y = A (x - c)`` for the (n, dim) float32 rows at the device address ``x_ptr`` into ``y_ptr`` (``kind``: NND_LINEAR_*;
+    ``map_ptr``: dim floats or (dim, dim); ``shift_ptr``: dim floats); queued on ``stream_ptr`` of ``device``."""
+    lib = load_library()
+    dev = lambda p: C.c_void_p(int(p)) if p else None  # noqa: E731
+    if lib.nnd_device_linear_rows(int(device), dev(stream_ptr), int(kind), int(dim), dev(map_ptr), dev(shift_ptr), dev(x_ptr), int(n),
+                                  dev(y_ptr)) != 0:
+        raise NNDError(lib.nnd_last_global_error().decode())
+
+
+def linear_rows_host(kind, a, shift, x, device=0):
+    """``y = A (x - c)`` of the float32 host rows ``x`` by the device kernel (``nnd_linear_rows_host``): a new float32 array."""
+    lib = load_library()
+    x = np.ascontiguousarray(x, np.float32)
+    a, shift = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(shift, np.float32)
+    n, dim = x.shape
+    assert shift.shape == (dim,) and a.shape == ((dim, dim) if kind == NND_LINEAR_DENSE else (dim,))
+    y = np.empty((n, dim), np.float32)
+    if lib.nnd_linear_rows_host(int(device), int(kind), dim, _ptr(a), _ptr(shift), _ptr(x), n, _ptr(y)) != 0:
+        raise NNDError(lib.nnd_last_global_error().decode())
+    return y
 
 
 def device_correct(device, stream_ptr, kind, in_ptr, out_ptr, count):

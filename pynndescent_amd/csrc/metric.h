@@ -8,6 +8,8 @@
 //   unit metrics (1, 2, 4, 5): rows L2-normalised after a per-metric transform (none / none / minus the row mean / sqrt);
 //     nrm = 1 (non-zero row) or 0 (zero row); the trees split angularly;
 //   norm metrics (0, 3, 6): rows centred on the column mean (0) or as given (3, 6); nrm = |x|^2; euclidean trees.
+// The metrics with a fixed linear map (seuclidean, wminkowski with p = 2, mahalanobis) have no code and no formula here: they
+// are code 0 on rows that k_linear_rows (linear.hip) transformed once, y = A (x - c), before any kernel of this header sees them.
 // Four pieces, and which kernel takes which (DESIGN.md "Metrics" has the table):
 //   1. nnd_gram_to_dist / nnd_self_dist   float32 Gram value of two prepared rows -> distance (every kernel that ranks)
 //   2. nnd_ref_acc / nnd_ref_dist         float64 reference formula on the rows AS GIVEN (the distances handed back)

@@ -11,7 +11,10 @@ Also on the GPU: ``update`` (warm start, pynndescent_.py:2381-2553), ``build_sea
 pass of ``_init_search_graph``, all diversify methods), ``prepare`` (hub search tree + reordering) and
 ``query``.  Metrics: euclidean / l2 / sqeuclidean / cosine / dot / inner_product / correlation / hellinger (hellinger input
 must be non-negative: a negative entry raises ``ValueError``, where the reference computes NaN distances without a word) and
-proxy_inner_product (graph and walk on the reference's proxy distance, queries reranked by the true inner product).
+proxy_inner_product (graph and walk on the reference's proxy distance, queries reranked by the true inner product); and the
+metrics that are euclidean after a fixed linear map of the rows, with ``metric_kwds`` read positionally as the reference reads
+it: seuclidean / standardised_euclidean ``(V,)``, wminkowski / weighted_minkowski ``(w,)`` or ``(w, 2)``, mahalanobis ``(VI,)``
+and minkowski ``()`` or ``(2,)`` (linear_map.py; the device transforms every row once, csrc/linear.hip).
 Out of scope: sparse input, every other metric, ``n_neighbors`` above 256 or
 ``max_candidates`` above 128 (``query``: more than 256 results per query).  Those raise ``NotImplementedError`` naming the reference entry point to use
 instead; ``pynndescent_amd.make_index`` hands such inputs to ``pynndescent.NNDescent`` when it is importable.
@@ -24,7 +27,7 @@ from warnings import warn
 import numpy as np
 from sklearn.utils import check_array, check_random_state
 
-from . import _capi
+from . import _capi, linear_map
 
 INT32_MIN = np.iinfo(np.int32).min + 1  # pynndescent_.py:62
 INT32_MAX = np.iinfo(np.int32).max - 1  # pynndescent_.py:63
@@ -75,6 +78,9 @@ class _Metric(NamedTuple):
     # neighbor_graph hands out as it is; query() keeps proxy_beam_size * k candidates and the device reranks them by the true one
     proxy: bool = False
     device_kind: int = _capi.NND_CORRECT_COPY  # the same correction on a device tensor (include/pynnd_amd.h NND_CORRECT_*)
+    # carries a fixed linear map from metric_kwds (linear_map.py): the device works on y = A (x - c), a transformed float32 copy
+    # of the rows, with the kernels of ``code`` unchanged; _raw_data stays the caller's rows
+    linear: bool = False
 
 
 # corrections: numpy.sqrt, large float32 arrays through the library's threaded sqrtf (the same bits, the fresh pages touched in
@@ -95,9 +101,19 @@ _METRICS = {
                          device_kind=_capi.NND_CORRECT_ALT_HELLINGER),
     "proxy_inner_product": _Metric(_capi.METRIC_CODES["proxy_inner_product"], _capi.host_copy, proxy=True),
 }
+# euclidean distance after a fixed linear map of the rows (seuclidean, wminkowski with p = 2, mahalanobis; minkowski with p = 2
+# has no map and is the euclidean path itself): code 0 and euclidean's correction on the transformed rows.  A table of its own:
+# these names take metric_kwds, the nine above ignore it
+_LINEAR_METRICS = {name: _Metric(_capi.METRIC_CODES["euclidean"], _capi.host_sqrt, device_kind=_capi.NND_CORRECT_SQRT, linear=True)
+                   for name in linear_map.LINEAR_METRICS}
 # views of the table by one field
 _DISTANCE_CORRECTIONS = {name: m.correction for name, m in _METRICS.items()}
 _ANGULAR_METRICS = frozenset(name for name, m in _METRICS.items() if m.angular)
+
+
+def _metric_of(name):
+    """The record of a metric an index already has (its name was accepted by ``_metric_record``)."""
+    return _METRICS[name] if name in _METRICS else _LINEAR_METRICS[name]
 
 
 def _metric_record(metric, reference_fallback=True):
@@ -106,10 +122,13 @@ def _metric_record(metric, reference_fallback=True):
     ``make_index`` hands to ``pynndescent.NNDescent``."""
     if not callable(metric) and metric in _METRICS:
         return _METRICS[metric]
+    if not callable(metric) and metric in _LINEAR_METRICS:
+        return _LINEAR_METRICS[metric]
     if reference_fallback and (callable(metric) or metric in _KNOWN_REFERENCE_METRICS):
         raise NotImplementedError(
             "pynndescent_amd accelerates the dense euclidean / l2 / sqeuclidean / cosine / dot / inner_product / "
-            "correlation / hellinger / proxy_inner_product build only; "
+            "correlation / hellinger / proxy_inner_product / seuclidean / standardised_euclidean / mahalanobis build and the "
+            "p = 2 form of minkowski / wminkowski / weighted_minkowski only; "
             "use pynndescent.NNDescent for metric %r" % (metric,)
         )
     raise ValueError("Metric is neither callable, " + "nor a recognised string")
@@ -152,7 +171,7 @@ def _check_quantization(quantization, metric):
     if quantization is None:
         return
     if quantization == "uint8":
-        if not _METRICS[metric].uint8:
+        if not _metric_record(metric, reference_fallback=False).uint8:
             raise ValueError(f"Not uint8 quantization version of {metric}")
         return
     if quantization in ("uint4", "binary"):
@@ -291,11 +310,13 @@ def _stream_ms(torch, stream, fn):
 class _DeviceInput:
     """The device side of one single-GPU build (``_build_graph``): the caller's tensor in, the finished graph out as tensors."""
 
-    def __init__(self, tensor, dtype, ordinal, k, as_given=False):
+    def __init__(self, tensor, dtype, ordinal, k, as_given=False, linear=None):
         self.torch = _torch()
         self.tensor, self.dtype, self.ordinal, self.k = tensor, dtype, ordinal, int(k)
-        self.rows = tensor  # what the index keeps: the caller's own tensor, or dot's normalised float32 rows
+        # what the device works on: the caller's own tensor, dot's normalised float32 rows, or the rows a linear map transformed
+        self.rows = tensor
         self.as_given = as_given  # update(): dot's rows enter as they are (float32, pynndescent_.py:2461-2476 normalises nothing)
+        self.linear = linear  # a _DeviceLinear: the metric's map on this device (None: the metric has none)
 
     def host_rows(self):
         """The caller's rows on the host, float32: for sklearn's wording of the NaN / inf error, the one place that needs them."""
@@ -305,7 +326,10 @@ class _DeviceInput:
         torch, t = self.torch, self.tensor
         self.stream = _OnTorchStream(torch, self.ordinal)
         builder.set_stream(self.stream.ptr)
-        if m.normalize and self.as_given:  # (the typed entry would normalise every dot input)
+        if self.linear is not None:  # the builder borrows the transformed copy, and the index keeps it next to the caller's rows
+            self.rows = self.linear.rows(t, self.dtype, self.stream.ptr)
+            builder.set_data_device(self.rows.data_ptr(), keepalive=self.rows)
+        elif m.normalize and self.as_given:  # (the typed entry would normalise every dot input)
             builder.set_data_device(t.data_ptr(), keepalive=t)
         elif m.normalize:  # pynndescent_.py:1101-1102: the index holds the normalised rows; the builder borrows them
             self.rows = torch.empty(tuple(t.shape), dtype=torch.float32, device=t.device)
@@ -326,6 +350,50 @@ class _DeviceInput:
         if getattr(self, "stream", None) is not None:
             self.stream.done()
             self.stream = None
+
+
+class _DeviceLinear:
+    """A metric's linear map (``linear_map.LinearMap``) on one device: ``a`` and ``shift`` as float32 tensors there (uploaded
+    here, on torch's current stream: make it before the ``_OnTorchStream`` of the call that uses it)."""
+
+    def __init__(self, lin, device, ordinal):
+        torch = _torch()
+        self.kind, self.ordinal = int(lin.kind), int(ordinal)
+        self.a = torch.from_numpy(np.ascontiguousarray(lin.a, dtype=np.float32)).to(device)
+        self.shift = torch.from_numpy(np.ascontiguousarray(lin.shift, dtype=np.float32)).to(device)
+
+    def rows(self, t, dtype, stream_ptr):
+        """``A (x - shift)`` of the contiguous (n, d) tensor ``t`` (``dtype``: its NND_DTYPE_*): a new float32 tensor, queued on
+        ``stream_ptr``.  The existing conversion to float32 runs first (csrc/devarray.hip), then csrc/linear.hip."""
+        torch = _torch()
+        n, dim = int(t.shape[0]), int(t.shape[1])
+        out = torch.empty((n, dim), dtype=torch.float32, device=t.device)
+        if n == 0:
+            return out
+        if dtype != _capi.NND_DTYPE_FLOAT32:
+            x32 = torch.empty((n, dim), dtype=torch.float32, device=t.device)
+            _capi.device_rows_f32(self.ordinal, stream_ptr, t.data_ptr(), dtype, n, dim, False, x32.data_ptr())
+            t = x32
+        _capi.device_linear_rows(self.ordinal, stream_ptr, self.kind, dim, self.a.data_ptr(), self.shift.data_ptr(), t.data_ptr(), n,
+                                 out.data_ptr())
+        return out
+
+
+def _linear_map_of(metric, m, metric_kwds, dim):
+    """The ``LinearMap`` (without its shift) of a metric that carries one; None for every other metric -- ``metric_kwds`` stays
+    unread for those -- and for minkowski with p = 2.  Raises what ``linear_map.parse_metric_kwds`` raises."""
+    return linear_map.parse_metric_kwds(metric, metric_kwds, dim) if m.linear else None
+
+
+def _refuse_with_linear(metric, m, quantization, n_devices):
+    """What the metrics with a linear map do not combine with, reported before any device work."""
+    if not m.linear:
+        return
+    if quantization == "uint8":
+        _check_quantization(quantization, metric)  # the reference's ValueError("Not uint8 quantization version of ...")
+    if int(n_devices) > 1:
+        raise NotImplementedError("pynndescent_amd builds metric %r on one GPU (n_devices = %d): the row-sharded build has no "
+                                  "linear map; use n_devices=1" % (metric, int(n_devices)))
 
 
 def _device_corrected(torch, dist, m, ordinal):
@@ -361,7 +429,7 @@ def _prepares_on_device(index):
         return False
     if "_device_data" not in d or "_device_graph" not in d or int(d.get("n_devices", 1)) != 1:
         return False
-    if d.get("quantization") == "uint8" and _METRICS[d["metric"]].normalize:
+    if d.get("quantization") == "uint8" and _metric_of(d["metric"]).normalize:
         return False
     n, k = (int(v) for v in d["_device_graph"][0].shape)
     return 2 * n * k < DEVICE_PASS_MAX_EDGES
@@ -491,6 +559,8 @@ class NNDescent:
             raise ValueError("n_devices must be >= 1 and match len(devices)")
 
         m = _metric_record(metric)
+        lin = _linear_map_of(metric, m, metric_kwds, data.shape[1])  # (host only: every error of metric_kwds comes first)
+        _refuse_with_linear(metric, m, quantization, self.n_devices)
         try:
             import scipy.sparse
 
@@ -522,6 +592,13 @@ class NNDescent:
         current_random_state = self._set_up(None if dev_in is not None else data, m, random_state, copy_on_normalize)
         if dev_in is None:
             data = self._raw_data
+        self._linear_map = None
+        if lin is not None:  # the shift is fixed here, once; the device builds on the transformed copy, _raw_data stays the caller's
+            self._linear_map = lin = lin._replace(shift=linear_map.shift_of(data if dev_in is None else _DeviceRowsView(data)))
+            if dev_in is None:
+                data = self._lin_data = _capi.linear_rows_host(lin.kind, lin.a, lin.shift, data, device=device)
+            else:
+                dev_in.linear = self._linear_on_device(data.device)
 
         n = data.shape[0]
         if self.tree_init:
@@ -553,6 +630,8 @@ class NNDescent:
                 self._neighbor_graph = graph
             else:  # the graph and the rows stay on the device; _neighbor_graph / _raw_data are fetched when first read
                 self._device_graph, self._device_data = graph, dev_in.rows
+                if dev_in.linear is not None:  # _device_data: the transformed rows the device works on; the caller's tensor stays
+                    self._device_raw = dev_in.tensor
         self._rp_forest = _DeviceForestSentinel(n_trees, n_leaves, eff_leaf_size) if self.tree_init else None
 
         # pynndescent_.py:1262-1267 `np.any(indices < 0)`: rows are ascending with the unfilled entries (-1, +inf) at the
@@ -605,7 +684,7 @@ class NNDescent:
         from . import sharded
 
         assert_all_finite(data)  # check_array's scan (pynndescent_.py:1054): the one-call multi-GPU build has no flag to read
-        _raise_if_negative_host(data, _METRICS[self.metric])
+        _raise_if_negative_host(data, _metric_of(self.metric))
         if verbose:
             print(ts(), "NN descent for", str(self.n_iters), "iterations on", self.n_devices, "GPUs")
         idx, dst, st, info = sharded.build_multi(
@@ -630,7 +709,7 @@ class NNDescent:
             torch = _torch()
             idx, dist = self._device_graph
             with torch.cuda.device(self.device):
-                return idx.clone(), _device_corrected(torch, dist, _METRICS[self.metric], self.device)
+                return idx.clone(), _device_corrected(torch, dist, _metric_of(self.metric), self.device)
         return (_capi.host_copy(self._neighbor_graph[0]), self._distance_correction(self._neighbor_graph[1]))
 
     def __getattr__(self, name):
@@ -640,11 +719,17 @@ class NNDescent:
         (scipy CSR uint8, sorted indices) and ``_quantized_data`` (the searcher's uint8 codes).  Every line that reads the names
         finds them as on a host-built index, and ``hasattr`` keeps its meaning."""
         d = self.__dict__
-        if name == "_raw_data" and "_device_data" in d:
-            rows = d["_device_data"].detach()
+        if name in ("_raw_data", "_lin_data") and "_device_data" in d and (name == "_raw_data" or d.get("_linear_map") is not None):
+            # (a metric with a linear map: _device_data holds the transformed rows, _device_raw the caller's)
+            rows = d["_device_raw" if name == "_raw_data" and "_device_raw" in d else "_device_data"].detach()
             if "_device_order" in d:  # x_new[i] = x[order[i]]: the gather the searcher's fill makes
                 rows = rows[d["_device_order"].long()]
             value = np.ascontiguousarray(rows.float().cpu().numpy())
+        elif name == "_lin_data" and d.get("_linear_map") is not None:
+            # the transformed rows of a host index that has none at hand (unpickled, from_graph): a row's transform depends on
+            # the row alone, so transforming _raw_data again gives the bits the index was built on, in _raw_data's order
+            lin = d["_linear_map"]
+            value = _capi.linear_rows_host(lin.kind, lin.a, lin.shift, self._raw_data, device=self.device)
         elif name == "_neighbor_graph" and "_device_graph" in d:
             value = tuple(np.ascontiguousarray(t.cpu().numpy()) for t in d["_device_graph"])
         elif name == "_search_graph" and "_device_search_graph" in d:
@@ -664,8 +749,24 @@ class NNDescent:
 
     def _drop_device_copies(self):
         """After the host mirrors have become the truth (``update()``), or for a pickle: the device tensors go."""
-        for name in ("_device_graph", "_device_data", "_device_order", "_device_search_graph", "_device_prepare_stats"):
+        for name in ("_device_graph", "_device_data", "_device_raw", "_device_order", "_device_search_graph", "_device_prepare_stats"):
             self.__dict__.pop(name, None)
+
+    def _kernel_metric(self):
+        """The metric name the kernels run: the index's own, or euclidean on the transformed rows of a linear map."""
+        return "euclidean" if _metric_of(self.metric).linear else self.metric
+
+    def _work_rows(self):
+        """The host rows the device works on: ``_raw_data``, or its transformed copy ``_lin_data`` for a metric with a linear map."""
+        return self._lin_data if self.__dict__.get("_linear_map") is not None else self._raw_data
+
+    def _linear_on_device(self, device):
+        """The index's linear map as tensors on ``device`` (a ``_DeviceLinear``), uploaded once."""
+        d = self.__dict__
+        if d.get("_device_linear") is None:
+            ordinal = getattr(device, "index", None)
+            d["_device_linear"] = _DeviceLinear(d["_linear_map"], device, int(self.device) if ordinal is None else ordinal)
+        return d["_device_linear"]
 
     @property
     def _prepared(self):
@@ -688,7 +789,7 @@ class NNDescent:
         row ids go up and one integer comes back (the same value, and no host mirror is fetched).  dot: the truth is searched
         on rows normalised once more -- by the device there, by sklearn on the host path -- which agree within rounding only,
         so the two paths may differ where two true neighbours are that close; every other metric gives the same value."""
-        _no_exact_for_proxy(self.metric, _METRICS[self.metric], "NNDescent.recall")
+        _no_exact_for_proxy(self.metric, _metric_of(self.metric), "NNDescent.recall")
         d = self.__dict__
         if "_device_data" in d and "_device_graph" in d and int(d.get("n_devices", 1)) == 1:
             return self._recall_device(k, n_rows, random_state)
@@ -696,10 +797,10 @@ class NNDescent:
         n = graph_idx.shape[0]
         k = min(10, int(self.n_neighbors)) if k is None else int(k)
         rows = self._recall_rows(n, n_rows, random_state)
-        data = self._raw_data
+        data = self._work_rows()  # (a metric with a linear map: the truth is euclidean on the transformed rows)
         if hasattr(self, "_vertex_order"):  # prepare() keeps the rows in the search tree's leaf order; the graph keeps its numbering
             data = data[np.argsort(self._vertex_order), :]
-        true_idx = exact_knn(data, k=k, metric=self.metric, rows=rows, device=getattr(self, "device", 0))[0]
+        true_idx = exact_knn(data, k=k, metric=self._kernel_metric(), rows=rows, device=getattr(self, "device", 0))[0]
         hits = sum(int(np.isin(t, a).sum()) for t, a in zip(true_idx, graph_idx[rows]))
         return hits / float(true_idx.shape[0] * k)
 
@@ -714,7 +815,7 @@ class NNDescent:
         rows = self._recall_rows(n, n_rows, random_state)
         with torch.cuda.device(ordinal):
             rows_dev = torch.from_numpy(rows.astype(np.int32)).to(data.device)
-            true_idx = _exact_knn_device(data, None, k, self.metric, _METRICS[self.metric], rows_dev, ordinal, False)[0]
+            true_idx = _exact_knn_device(data, None, k, self.metric, _metric_of(self.metric), rows_dev, ordinal, False)[0]
             hits = torch.empty((1,), dtype=torch.int64, device=data.device)
             _capi.device_recall_hits(ordinal, torch.cuda.current_stream(ordinal).cuda_stream, true_idx.data_ptr(), true_idx.shape[0], k,
                                      gidx.data_ptr(), n, gidx.shape[1], rows_dev.data_ptr(), hits.data_ptr())
@@ -729,7 +830,7 @@ class NNDescent:
         if self._prepared:
             raise RuntimeError("the index is prepared already: its search graph is index._search_graph (in leaf order)")
         self._pruned_graph = build_search_graph(
-            self._raw_data, self._neighbor_graph[0], self._neighbor_graph[1], self.metric, self.n_neighbors,
+            self._work_rows(), self._neighbor_graph[0], self._neighbor_graph[1], self._kernel_metric(), self.n_neighbors,
             self.prune_degree_multiplier, self.diversify_prob, self.diversify_method,
             degree_prune_aggressiveness=self.degree_prune_aggressiveness,
             seed=int(self.rng_state[0]) & 0xFFFFFFFF, device=self.device)
@@ -749,18 +850,27 @@ class NNDescent:
         """Hand the GPU-built index to ``pynndescent.NNDescent`` (must be importable) WITHOUT rebuilding: the returned
         object carries this index's data, graph and parameters, so the reference's own ``prepare()`` (hub search tree,
         pruned + reordered search graph) and ``query()`` run on it unchanged.  The reference only null-checks
-        ``_rp_forest`` before building its hub tree from the graph (pynndescent_.py:1353-1437)."""
+        ``_rp_forest`` before building its hub tree from the graph (pynndescent_.py:1353-1437).
+
+        seuclidean / wminkowski / mahalanobis / minkowski: the reference keeps no squared space for them, so the graph handed
+        over holds true distances, and the search structures of a prepared index are LEFT OUT of the hand-over (its tree's
+        hyperplanes split the transformed space, the reference's tree descent takes raw queries): the rows go back to their
+        original order and the reference's own ``prepare()`` rebuilds tree and search graph from the graph."""
         import pynndescent
 
+        linear = _metric_of(self.metric).linear
         ref = object.__new__(pynndescent.NNDescent)
         for name in self._HANDOVER:
             if hasattr(self, name):
                 setattr(ref, name, getattr(self, name))
+        if linear and self._prepared:
+            ref._raw_data = np.ascontiguousarray(self._raw_data[np.argsort(self._vertex_order), :])
         if hasattr(self, "_neighbor_graph"):
-            ref._neighbor_graph = (self._neighbor_graph[0].copy(), self._neighbor_graph[1].copy())
+            dist = self._neighbor_graph[1]
+            ref._neighbor_graph = (self._neighbor_graph[0].copy(), np.sqrt(dist) if linear else dist.copy())
         ref._distance_correction = None
         ref._set_distance_func()  # pynndescent_.py:1271-1298: numba distance, correction, proxy flags
-        if hasattr(self, "_search_graph"):  # prepared on the GPU: the reference's prepare() has nothing left to build
+        if hasattr(self, "_search_graph") and not linear:  # prepared on the GPU: the reference's prepare() has nothing left to build
             from pynndescent.rp_trees import FlatTree as RefFlatTree
 
             ref._search_graph = self._search_graph.copy()
@@ -799,7 +909,11 @@ class NNDescent:
         self.dim = data.shape[1]
         self.tree_init = True
         self._dist_args = tuple((self.metric_kwds or {}).values())
+        lin = _linear_map_of(metric, m, self.metric_kwds, data.shape[1])
+        _refuse_with_linear(metric, m, self.quantization, 1)
         self._set_up(data, m, random_state, copy=True)  # (dot: the data NNDescent would hold, in a new array)
+        # (``distances`` of a metric with a linear map: squared, of the rows transformed with this shift -- what the build keeps)
+        self._linear_map = None if lin is None else lin._replace(shift=linear_map.shift_of(self._raw_data))
         self._rp_forest = _DeviceForestSentinel(self.n_trees, 0, 0)
         self._neighbor_graph = (indices, distances)
         return self
@@ -829,14 +943,14 @@ class NNDescent:
             else:
                 if self.verbose:
                     print(ts(), "Building hub-based search tree")
-                self._search_forest = [make_hub_tree(self._raw_data, self._neighbor_graph[0], self.metric, search_leaf_size,
+                self._search_forest = [make_hub_tree(self._work_rows(), self._neighbor_graph[0], self._kernel_metric(), search_leaf_size,
                                                      search_tree_depth, device=self.device,
                                                      seed=int(self.rng_state[0]) & 0x7FFFFFFF)]
                 self._rp_forest = None  # the reference deletes it here (pynndescent_.py:1444)
         if self.verbose:
             print(ts(), "Diversifying and pruning the search graph")
         graph, stages = build_search_graph(
-            self._raw_data, self._neighbor_graph[0], self._neighbor_graph[1], self.metric, self.n_neighbors,
+            self._work_rows(), self._neighbor_graph[0], self._neighbor_graph[1], self._kernel_metric(), self.n_neighbors,
             self.prune_degree_multiplier, self.diversify_prob, self.diversify_method,
             degree_prune_aggressiveness=self.degree_prune_aggressiveness, seed=int(self.rng_state[0]) & 0xFFFFFFFF,
             device=self.device, return_stages=True)
@@ -845,8 +959,11 @@ class NNDescent:
         if self.verbose:
             print(ts(), "Resorting data and graph based on tree order")
         if self._search_forest:
-            graph, data, self._vertex_order, tree = reorder_by_tree(graph, self._raw_data, self._search_forest[0])
-            self._raw_data = data
+            graph, data, self._vertex_order, tree = reorder_by_tree(graph, self._work_rows(), self._search_forest[0])
+            if self.__dict__.get("_linear_map") is not None:  # both copies in the leaf order
+                self._lin_data, self._raw_data = data, np.ascontiguousarray(self._raw_data[self._vertex_order, :])
+            else:
+                self._raw_data = data
             self._search_forest = [tree] + list(self._search_forest[1: self.n_search_trees])
         else:
             self._vertex_order = np.arange(self._raw_data.shape[0])
@@ -869,7 +986,7 @@ class NNDescent:
 
         if self.diversify_method not in ("standard", "degree_aware"):
             raise ValueError("diversify_method must be 'standard' or 'degree_aware'")
-        torch, d, m = _torch(), self.__dict__, _METRICS[self.metric]
+        torch, d, m = _torch(), self.__dict__, _metric_of(self.metric)
         data, (gidx, gdist) = d["_device_data"], d["_device_graph"]
         n, dim, k = int(data.shape[0]), int(data.shape[1]), int(gidx.shape[1])
         dtype, ordinal = _DEVICE_DTYPES[str(data.dtype).rsplit(".", 1)[-1]], int(self.device)
@@ -944,6 +1061,7 @@ class NNDescent:
         else:
             self._vertex_order = np.arange(n)
         d.pop("_raw_data", None)  # (a mirror fetched before: the rows in their original order; the next read gathers them)
+        d.pop("_lin_data", None)
         self._device_search_graph = (indptr, indices)
         self._device_prepare_stats = dict(ms, ms_search_graph=float(st["ms_device"]), final_nnz=int(nnz))
         self._searcher = None
@@ -959,7 +1077,7 @@ class NNDescent:
         already has them (unpickled) reuses ``_quantized_values`` / ``_quantized_data``."""
         _check_quantization(self.quantization, self.metric)
         quantized = self.quantization == "uint8"
-        self._is_proxy_distance = quantized or _METRICS[self.metric].proxy
+        self._is_proxy_distance = quantized or _metric_of(self.metric).proxy
         d = self.__dict__
         fresh = not self._prepared
         if quantized and (fresh or d.get("_quantized_values") is None):
@@ -977,12 +1095,12 @@ class NNDescent:
             if on_device:
                 self._searcher = self._searcher_from_device(tree)
             else:
-                self._searcher = _capi.Searcher(self._raw_data, self._search_graph, tree, _METRICS[self.metric].code,
+                self._searcher = _capi.Searcher(self._work_rows(), self._search_graph, tree, _metric_of(self.metric).code,
                                                 self._min_distance, self.n_neighbors, self.search_rng_state, device=self.device)
         if quantized and not self._searcher.has_codes:
             if d.get("_quantized_data") is None:
                 # dot: the searcher's own copy is normalised once more on the device; the codes are those of _raw_data
-                rows = self._raw_data if _METRICS[self.metric].normalize else None
+                rows = self._raw_data if _metric_of(self.metric).normalize else None
                 if on_device and rows is None:  # the codes stay with the searcher; _quantized_data is their mirror, fetched when read
                     self._searcher.quantize_u8(self._quantized_values, rows=None, fetch=False)
                     d.pop("_quantized_data", None)
@@ -1003,7 +1121,7 @@ class NNDescent:
                 searcher, ms = _stream_ms(torch, stream, lambda: _capi.Searcher.from_device(
                     data.data_ptr(), _DEVICE_DTYPES[str(data.dtype).rsplit(".", 1)[-1]], data.shape[0], data.shape[1],
                     0 if order is None else order.data_ptr(), indptr.data_ptr(), indices.data_ptr() if indices.numel() else 0,
-                    indices.numel(), tree, _METRICS[self.metric].code, self._min_distance, self.n_neighbors, self.search_rng_state,
+                    indices.numel(), tree, _metric_of(self.metric).code, self._min_distance, self.n_neighbors, self.search_rng_state,
                     device=ordinal, stream_ptr=stream.ptr))
                 d.setdefault("_device_prepare_stats", {})["ms_searcher_fill"] = ms
             finally:
@@ -1021,7 +1139,7 @@ class NNDescent:
         if k > 256:
             raise NotImplementedError("pynndescent_amd answers queries with k <= 256; use index.to_reference() for k = %d" % k)
         _check_quantization(self.quantization, self.metric)
-        m = _METRICS[self.metric]
+        m = _metric_of(self.metric)
         search_k = k
         if self.quantization is not None or m.proxy:  # pynndescent_.py:2309-2312
             search_k = _proxy_search_k(k, proxy_beam_size)
@@ -1034,6 +1152,9 @@ class NNDescent:
         if query_data.ndim != 2 or query_data.shape[1] != self.dim:
             raise ValueError("query_data must have shape (n_queries, %d)" % self.dim)
         _raise_if_negative_host(query_data, m)
+        lin = self.__dict__.get("_linear_map")
+        if lin is not None:  # the queries through the index's own (A, c), by the kernel that transformed its rows
+            query_data = _capi.linear_rows_host(lin.kind, lin.a, lin.shift, query_data, device=self.device)
         if self.quantization is not None:  # the walk on the codes, the rerank in its epilogue (pynndescent_.py:2321-2322, 2363-2371)
             indices, dists = self._searcher.query_proxy(query_data, k, search_k, epsilon + 1e-32)
         elif m.proxy:  # the walk on the proxy distance, the rerank by the true one; epsilon as given (pynndescent_.py:2321-2322)
@@ -1057,7 +1178,9 @@ class NNDescent:
             raise ValueError("query_data must have shape (n_queries, %d)" % dim)
         with torch.cuda.device(ordinal):
             stream = torch.cuda.current_stream(ordinal).cuda_stream
-            if dtype != _capi.NND_DTYPE_FLOAT32:  # pynndescent_.py:2316
+            if self.__dict__.get("_linear_map") is not None:  # converted, then through the index's own (A, c)
+                q = self._linear_on_device(q.device).rows(q, dtype, stream)
+            elif dtype != _capi.NND_DTYPE_FLOAT32:  # pynndescent_.py:2316
                 q32 = torch.empty((nq, dim), dtype=torch.float32, device=q.device)
                 _capi.device_rows_f32(ordinal, stream, q.data_ptr(), dtype, nq, dim, False, q32.data_ptr())
                 q = q32
@@ -1095,6 +1218,9 @@ class NNDescent:
         state = self.__dict__.copy()
         for name in ("_device_graph", "_device_data", "_device_order", "_device_search_graph", "_device_prepare_stats"):
             state.pop(name, None)
+        # a linear map travels as _linear_map (kind, A, c: float32); the transformed rows are derived again from _raw_data
+        for name in ("_device_raw", "_device_linear", "_lin_data"):
+            state.pop(name, None)
         state.pop("_rp_forest", None)
         state.pop("_searcher", None)
         state["_search_forest"] = tuple(tuple(t) for t in self._search_forest)  # rp_trees.py:3060-3069 denumbaify_tree
@@ -1105,7 +1231,7 @@ class NNDescent:
         from .search_tree import FlatTree
 
         self.__dict__ = d
-        self._distance_correction = _METRICS[self.metric].correction
+        self._distance_correction = _metric_of(self.metric).correction
         self._search_forest = [FlatTree(*t) for t in d["_search_forest"]]  # rp_trees.py:3072-3081 renumbaify_tree
         self._searcher = None
 
@@ -1199,8 +1325,12 @@ class NNDescent:
             n_leaves = self._build_multi(raw, self.n_trees, eff_leaf_size, eff_max_candidates, tree_states[0], False,
                                          old_graph=(pad_i, pad_d))
         else:  # pynndescent_.py:2512-2517: the old graph's entries as "old" edges, then the forest's; no random fill
+            lin, work = self.__dict__.get("_linear_map"), raw
+            self.__dict__.pop("_lin_data", None)
+            if lin is not None:  # old, updated and fresh rows through the index's own (A, c): old rows come out as they were
+                work = self._lin_data = _capi.linear_rows_host(lin.kind, lin.a, lin.shift, raw, device=self.device)
             self._neighbor_graph, self._build_stats, n_leaves = _build_graph(
-                raw, _METRICS[self.metric], self.n_neighbors, self.n_trees, eff_leaf_size, self.max_rptree_depth,
+                work, _metric_of(self.metric), self.n_neighbors, self.n_trees, eff_leaf_size, self.max_rptree_depth,
                 eff_max_candidates, self.n_iters, self.delta, self.rng_state, tree_states[0], self.device, forest=True,
                 old_graph=(pad_i, pad_d), verbose=self.verbose)
         self._rp_forest = _DeviceForestSentinel(self.n_trees, n_leaves, eff_leaf_size)
@@ -1218,8 +1348,10 @@ class NNDescent:
         invalidated, padded graph are written by the library (``nnd_device_update_rows`` / ``nnd_device_update_graph``), the
         rebuild binds the new rows as they are (dot: not normalised again, as on the host path) and reads the old graph in place.
         What crosses the bus: the resolved ``(row id, source row)`` pairs, host arrays given alongside, and the build's scalars."""
-        d, m = self.__dict__, _METRICS[self.metric]
-        data, (gidx, gdist) = d["_device_data"], d["_device_graph"]
+        d, m = self.__dict__, _metric_of(self.metric)
+        # (a metric with a linear map: the new tensor is assembled from the caller's rows, and transformed as a whole below)
+        data, (gidx, gdist) = d.get("_device_raw", d["_device_data"]), d["_device_graph"]
+        linear = self._linear_on_device(data.device) if d.get("_linear_map") is not None else None
         n_old, dim, k, ordinal = int(data.shape[0]), int(data.shape[1]), int(gidx.shape[1]), int(self.device)
         ids, sources = _resolve_updated_indices(updated_indices, n_old)  # (IndexError: before any device work)
         torch = _torch()
@@ -1253,7 +1385,7 @@ class NNDescent:
             finally:
                 stream.done()
             # pynndescent_.py:2512-2517: the old graph's entries as "old" edges, then the forest's; no random fill
-            dev_in = _DeviceInput(new_data, _DEVICE_DTYPES[out_name], ordinal, self.n_neighbors, as_given=True)
+            dev_in = _DeviceInput(new_data, _DEVICE_DTYPES[out_name], ordinal, self.n_neighbors, as_given=True, linear=linear)
             graph, build_stats, n_leaves = _build_graph(
                 new_data, m, self.n_neighbors, n_trees, eff_leaf_size, self.max_rptree_depth, eff_max_candidates, self.n_iters,
                 self.delta, self.rng_state, tree_states[0], ordinal, forest=True, old_graph=(pad_i, pad_d), check_finite=True,
@@ -1261,10 +1393,12 @@ class NNDescent:
         self.n_trees, self._build_stats = n_trees, build_stats
         self._rp_forest = _DeviceForestSentinel(n_trees, n_leaves, eff_leaf_size)
         was_prepared = self._prepared
-        for name in ("_device_order", "_device_search_graph", "_device_prepare_stats", "_raw_data", "_neighbor_graph", "_search_graph",
-                     "_quantized_data", "_searcher", "_search_forest", "_vertex_order"):
+        for name in ("_device_order", "_device_search_graph", "_device_prepare_stats", "_raw_data", "_lin_data", "_neighbor_graph",
+                     "_search_graph", "_quantized_data", "_searcher", "_search_forest", "_vertex_order"):
             d.pop(name, None)
-        self._device_data, self._device_graph = new_data, graph  # (the caller's original tensor is released)
+        self._device_data, self._device_graph = dev_in.rows, graph  # (the caller's original tensor is released)
+        if linear is not None:
+            self._device_raw = new_data
         if was_prepared:  # pynndescent_.py:2538-2553: the derived structures are rebuilt, from the tensors when _prepares_on_device
             self.prepare()
 
@@ -1329,7 +1463,42 @@ def nn_descent(data, n_neighbors, rng_state, max_candidates=50, dist="squared_eu
     return idx, dst
 
 
-def exact_knn(data, queries=None, k=10, metric="euclidean", rows=None, device=0, return_stats=False):
+def _exact_linear_rows(metric, m, metric_kwds, data, queries, device):
+    """``exact_knn`` of a metric with a linear map: ``(data, queries)`` transformed by the device (float32; tensors stay tensors),
+    on which the search is euclidean.  The shift is the one an index of ``data`` would fix; distances do not depend on it."""
+    if _is_device_array(data):
+        data, dtype, ordinal = _check_device_array(data, device)
+        lin = _linear_map_of(metric, m, metric_kwds, data.shape[1])
+        if lin is None:
+            return data, queries
+        torch = _torch()
+        with torch.cuda.device(ordinal):
+            dl = _DeviceLinear(lin._replace(shift=linear_map.shift_of(_DeviceRowsView(data))), data.device, ordinal)
+            stream = torch.cuda.current_stream(ordinal).cuda_stream
+            if queries is not None:
+                if _is_device_array(queries):
+                    queries, q_dtype, _ = _check_device_array(queries, what="queries")
+                    queries = queries.to(data.device)
+                else:
+                    queries, q_dtype = torch.from_numpy(_check_array_no_scan(queries)).to(data.device), _capi.NND_DTYPE_FLOAT32
+                if queries.shape[1] != data.shape[1]:
+                    raise ValueError("queries must have shape (n_queries, %d)" % data.shape[1])
+                queries = dl.rows(queries, q_dtype, stream)
+            return dl.rows(data, dtype, stream), queries
+    data = _check_array_no_scan(data)
+    lin = _linear_map_of(metric, m, metric_kwds, data.shape[1])
+    if lin is None:
+        return data, queries
+    lin = lin._replace(shift=linear_map.shift_of(data))
+    if queries is not None:
+        queries = _check_array_no_scan(_rows_to_host(queries))
+        if queries.shape[1] != data.shape[1]:
+            raise ValueError("queries must have shape (n_queries, %d)" % data.shape[1])
+        queries = _capi.linear_rows_host(lin.kind, lin.a, lin.shift, queries, device=device)
+    return _capi.linear_rows_host(lin.kind, lin.a, lin.shift, data, device=device), queries
+
+
+def exact_knn(data, queries=None, k=10, metric="euclidean", rows=None, device=0, return_stats=False, metric_kwds=None):
     """Exact ``k`` nearest neighbours by brute force on the GPU (csrc/exact.hip): of every row of ``data`` (self included), of the
     rows ``rows`` of it, or of the external ``queries``.  Returns ``(indices int32 (m, k), distances float32-precision (m, k))``
     in the metric's own space (the correction ``NNDescent.neighbor_graph`` applies), rows ascending, ties to the smaller id;
@@ -1341,7 +1510,12 @@ def exact_knn(data, queries=None, k=10, metric="euclidean", rows=None, device=0,
     then runs on the tensor where it is, on torch's current stream, and the answers are tensors on that device -- int32 ids, and
     the distances corrected on the device (float32 or float64, as ``NNDescent.neighbor_graph`` returns them for the metric; dot
     normalises on the device, within rounding of the host's rows).  ``queries`` on the other side are moved to where ``data`` is;
-    ``rows`` may be a host array or a tensor (the ids are range-checked on the host)."""
+    ``rows`` may be a host array or a tensor (the ids are range-checked on the host).
+
+    ``metric_kwds``: the arguments of seuclidean / wminkowski (p = 2) / mahalanobis / minkowski (p = 2), read positionally as by
+    ``NNDescent``; every other metric ignores it.  For these metrics the answers are exact in this sense: (float64 distance, id)
+    on the float32 transformed rows -- the rows ``A (x - c)`` the device computes once (csrc/linear.hip), on which the search is
+    the euclidean one."""
     if queries is not None and rows is not None:
         raise ValueError("exact_knn takes `queries` (external points) or `rows` (ids of data rows), not both")
     k = int(k)
@@ -1349,6 +1523,9 @@ def exact_knn(data, queries=None, k=10, metric="euclidean", rows=None, device=0,
         raise NotImplementedError("pynndescent_amd.exact_knn keeps at most k <= 256 neighbours per row (got k = %d)" % k)
     m = _metric_record(metric)
     _no_exact_for_proxy(metric, m, "exact_knn")
+    if m.linear:  # (metric_kwds is validated in there, before any device work)
+        data, queries = _exact_linear_rows(metric, m, metric_kwds, data, queries, device)
+        metric, m = "euclidean", _METRICS["euclidean"]
     if _is_device_array(data):
         return _exact_knn_device(data, queries, k, metric, m, rows, device, return_stats)
     queries, rows = _rows_to_host(queries), _ids_to_host(rows)  # (the results live where the data lives)
@@ -1563,7 +1740,8 @@ def _check_supported_sizes(n_neighbors, max_candidates, init_graph):
 
 def make_index(data, *args, **kwargs):
     """``NNDescent(data, ...)`` on the GPU when the input is in scope (dense data, euclidean / l2 / sqeuclidean / cosine / dot /
-    inner_product / correlation / hellinger / proxy_inner_product, k <= 256);
+    inner_product / correlation / hellinger / proxy_inner_product / seuclidean / mahalanobis / minkowski and wminkowski with p = 2,
+    k <= 256);
     otherwise -- and only then -- the reference ``pynndescent.NNDescent`` on the CPU when that package is importable
     (SURVEY.md section 8b), with a warning.  A missing HIP library or GPU is never papered over: that still raises."""
     device = kwargs.pop("device", 0)
