@@ -54,6 +54,24 @@ extern "C" {
  * distance of metric="proxy_inner_product"; its true distance, the negative inner product, is what nnd_searcher_query_rerank
  * returns.  <x,y> = 0 is FLT_MAX here, +inf in the reference. */
 enum { NND_METRIC_PROXY_INNER_PRODUCT = 6 };
+/* Boolean metrics (reference distances.py:259-552): functions of the counts of the indicator rows b_x = (x != 0) --
+ * c = <b_x, b_y> = n_TT, a = nnz(x), b = nnz(y), ne = a + b - 2c, and the column count d.  The kernels build and walk on
+ * indicator rows (x != 0 -> 1, else 0); the distances handed back are the float64 formulas on the counts of the rows as given.
+ * NND_METRIC_JACCARD is alternative_jaccard, -log2(c / (c + ne)) (the caller applies 1 - 2^-v; c = 0 on a non-empty union is
+ * FLT_MAX here, +inf in the reference); the other eight are the reference's distances as they are.  dim must be below 2^23.  7 is no code
+ * (nnd_create has always refused it, and a test pins that refusal).
+ * An enumeration of its own, like the proxy family: the six #define lines above stay the list of the alt-space metrics. */
+enum {
+    NND_METRIC_JACCARD = 8,         /* alternative_jaccard :303 */
+    NND_METRIC_DICE = 9,            /* ne / (2c + ne) :360 */
+    NND_METRIC_SOKALSNEATH = 10,     /* ne / (0.5c + ne) :479 */
+    NND_METRIC_MATCHING = 11,       /* ne / d :340 */
+    NND_METRIC_ROGERSTANIMOTO = 12, /* 2ne / (d + ne) :414 */
+    NND_METRIC_SOKALMICHENER = 13,  /* the same :458 */
+    NND_METRIC_KULSINSKI = 14,      /* (ne - c + d) / (ne + d) :386 */
+    NND_METRIC_RUSSELLRAO = 15,     /* (d - c) / d :435 */
+    NND_METRIC_YULE = 16            /* 2 n_TF n_FT / (c n_FF + n_TF n_FT) :525 */
+};
 
 #define NND_ABI_VERSION 6 /* 6 (round 6): nnd_stats grew join_substeps[] and nnd_shard_info grew gather_bytes[] / gather_section[] at their ends; nnd_host_alloc / nnd_host_free; 5: nnd_search_graph / nnd_search_graph_fetch */
 

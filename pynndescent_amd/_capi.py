@@ -24,6 +24,18 @@ METRIC_CODES = {"euclidean": NND_METRIC_SQEUCLIDEAN, "l2": NND_METRIC_SQEUCLIDEA
                 "cosine": NND_METRIC_ALT_COSINE, "dot": NND_METRIC_ALT_DOT, "inner_product": NND_METRIC_ALT_INNER_PRODUCT,
                 "correlation": NND_METRIC_CORRELATION, "hellinger": NND_METRIC_ALT_HELLINGER,
                 "proxy_inner_product": NND_METRIC_PROXY_INNER_PRODUCT}
+# the boolean family (include/pynnd_amd.h: an enumeration of its own): name -> code, in the header's order
+(NND_METRIC_JACCARD, NND_METRIC_DICE, NND_METRIC_SOKALSNEATH, NND_METRIC_MATCHING, NND_METRIC_ROGERSTANIMOTO,
+ NND_METRIC_SOKALMICHENER, NND_METRIC_KULSINSKI, NND_METRIC_RUSSELLRAO, NND_METRIC_YULE) = range(8, 17)
+BOOLEAN_METRIC_CODES = {"jaccard": NND_METRIC_JACCARD, "dice": NND_METRIC_DICE, "sokalsneath": NND_METRIC_SOKALSNEATH,
+                        "matching": NND_METRIC_MATCHING, "rogerstanimoto": NND_METRIC_ROGERSTANIMOTO,
+                        "sokalmichener": NND_METRIC_SOKALMICHENER, "kulsinski": NND_METRIC_KULSINSKI,
+                        "russellrao": NND_METRIC_RUSSELLRAO, "yule": NND_METRIC_YULE}
+
+
+def metric_code(name):
+    """The kernels' code of a metric name of either table."""
+    return METRIC_CODES[name] if name in METRIC_CODES else BOOLEAN_METRIC_CODES[name]
 # element types of a device array (include/pynnd_amd.h NND_DTYPE_*) and the corrections of nnd_device_correct (NND_CORRECT_*)
 NND_DTYPE_FLOAT32, NND_DTYPE_FLOAT16, NND_DTYPE_BFLOAT16, NND_DTYPE_FLOAT64 = 0, 1, 2, 3
 NND_CORRECT_COPY, NND_CORRECT_SQRT, NND_CORRECT_ALT_COSINE, NND_CORRECT_ALT_INNER_PRODUCT, NND_CORRECT_ALT_HELLINGER = 0, 1, 2, 3, 4

@@ -607,12 +607,15 @@ extern "C" int32_t nnd_search_graph_device(nnd_handle_t ctx, const int32_t **ind
     return nnd_search_graph_device_impl(ctx, indptr_dev, indices_dev, nnz);
 }
 
+// the hub tree splits the rows AS GIVEN, angularly where the reference's search tree is angular (pynndescent_.py:1075-1086): the
+// unit-row metrics, and jaccard / dice of the boolean family
+static bool hub_tree_angular(int metric) { return nnd_metric_unit(metric) || metric == NND_METRIC_JACCARD || metric == NND_METRIC_DICE; }
 // ---- hub search tree of NNDescent.prepare() (reference rp_trees.py:714-1312, 2926-3049; host glue: search_tree.py) ----
 extern "C" int32_t nnd_hub_tree_build(nnd_handle_t ctx, const int32_t *rank_order /* host (n): ids by (-in-degree, id) */,
                                       int32_t leaf_size, int32_t max_depth, int64_t *n_nodes_out) {
     ENTER(ctx, NEED_DATA);
     if (!rank_order) { ctx->set_error("nnd_hub_tree_build: null rank order"); return 1; }
-    if (nnd_hub_tree_build_impl(ctx, rank_order, false, leaf_size, max_depth, nnd_metric_unit(ctx->p.metric))) return 1;
+    if (nnd_hub_tree_build_impl(ctx, rank_order, false, leaf_size, max_depth, hub_tree_angular(ctx->p.metric))) return 1;
     if (n_nodes_out) *n_nodes_out = nnd_hub_tree_nodes(ctx);
     return 0;
 }
@@ -620,7 +623,7 @@ extern "C" int32_t nnd_hub_tree_build_device(nnd_handle_t ctx, const int32_t *ra
                                              int64_t *n_nodes_out) {
     ENTER(ctx, NEED_DATA);
     if (!rank_order_dev) { ctx->set_error("nnd_hub_tree_build_device: null rank order"); return 1; }
-    if (nnd_hub_tree_build_impl(ctx, rank_order_dev, true, leaf_size, max_depth, nnd_metric_unit(ctx->p.metric))) return 1;
+    if (nnd_hub_tree_build_impl(ctx, rank_order_dev, true, leaf_size, max_depth, hub_tree_angular(ctx->p.metric))) return 1;
     if (n_nodes_out) *n_nodes_out = nnd_hub_tree_nodes(ctx);
     return 0;
 }

@@ -80,12 +80,13 @@ __device__ __forceinline__ void ex_merge_into(uint64_t *scr, uint32_t *__restric
 // 16 J + (l & 15) -- so the threshold th[r], the reject minimum rej[r] and the queue fill fill[r] of those four rows live in
 // registers, the same in all 16 lanes of a group.  DC: floats of a row staged per K chunk (dp <= DC: the query rows are staged
 // once); XM: the codes 2..5 (metric.h NND_CODES_0_5; code 6 is refused by the host), else 0 / 1; WIDE: W > 64 (rows merged through LDS).
-template <int DC, bool XM, bool WIDE>
-__global__ __launch_bounds__(256) void k_exact_scan(const float *__restrict__ xp, const float *__restrict__ nrm, int64_t n, int dp, int metric,
+// The body is shared by the kernels' instances: k_exact_scan (XM as above) and k_exact_scan_bool, the boolean family's (FAM =
+// NND_CODES_BOOL: `metric` carries the column count, metric.h nnd_kernel_metric).
+template <int DC, int FAM, bool WIDE>
+__device__ __forceinline__ void ex_scan_body(const float *__restrict__ xp, const float *__restrict__ nrm, int64_t n, int dp, int metric,
                                                     const float *__restrict__ qx, const float *__restrict__ qnrm, const int32_t *__restrict__ qids,
                                                     int self, int nq, int nq_pad, int W, int64_t rows_per_slice, uint32_t *__restrict__ list_e,
                                                     float *__restrict__ list_d, float *__restrict__ list_th, float *__restrict__ list_rej) {
-    constexpr int FAM = XM ? NND_CODES_0_5 : NND_CODES_01;
     extern __shared__ __align__(16) unsigned char ex_smem[];
     float *Xs = (float *)ex_smem;                              // (EX_QB + EX_TB) rows of DC floats, swizzled: queries, then the data tile
     float *snrm = Xs + (EX_QB + EX_TB) * DC;                   // (EX_TB) nrm of the data tile
@@ -200,6 +201,21 @@ __global__ __launch_bounds__(256) void k_exact_scan(const float *__restrict__ xp
         if (c16 == 0) list_rej[lbase + 4 * g + r] = v;
     }
 }
+template <int DC, bool XM, bool WIDE>
+__global__ __launch_bounds__(256) void k_exact_scan(const float *__restrict__ xp, const float *__restrict__ nrm, int64_t n, int dp, int metric,
+                                                    const float *__restrict__ qx, const float *__restrict__ qnrm, const int32_t *__restrict__ qids,
+                                                    int self, int nq, int nq_pad, int W, int64_t rows_per_slice, uint32_t *__restrict__ list_e,
+                                                    float *__restrict__ list_d, float *__restrict__ list_th, float *__restrict__ list_rej) {
+    ex_scan_body<DC, XM ? NND_CODES_0_5 : NND_CODES_01, WIDE>(xp, nrm, n, dp, metric, qx, qnrm, qids, self, nq, nq_pad, W, rows_per_slice, list_e, list_d, list_th, list_rej);
+}
+template <int DC, bool WIDE>
+__global__ __launch_bounds__(256) void k_exact_scan_bool(const float *__restrict__ xp, const float *__restrict__ nrm, int64_t n, int dp, int metric,
+                                                    const float *__restrict__ qx, const float *__restrict__ qnrm, const int32_t *__restrict__ qids,
+                                                    int self, int nq, int nq_pad, int W, int64_t rows_per_slice, uint32_t *__restrict__ list_e,
+                                                    float *__restrict__ list_d, float *__restrict__ list_th, float *__restrict__ list_rej) {
+    ex_scan_body<DC, NND_CODES_BOOL, WIDE>(xp, nrm, n, dp, metric, qx, qnrm, qids, self, nq, nq_pad, W, rows_per_slice, list_e, list_d, list_th, list_rej);
+}
+
 
 // ---- the slices' lists folded into slice 0's, one wave per query row ----
 template <bool WIDE>
@@ -235,15 +251,22 @@ struct ex_val {
     double ax;  // codes 1..5: the query row's squared norm term
 };
 // the 16 lanes of a group on one pair; mua: the query row's mean (correlation)
-template <bool XM>
+// FAM: NND_CODES_01, NND_CODES_0_5 (the codes 2..5) or NND_CODES_BOOL (the counts, then the float64 twin on them and d)
+template <int FAM>
 __device__ __forceinline__ ex_val ex_pair_f64(int metric, const float *__restrict__ xa, const float *__restrict__ xb, int d, int l16, double mua) {
-    constexpr int FAM = XM ? NND_CODES_0_5 : NND_CODES_01;
+    constexpr bool XM = FAM != NND_CODES_01;
     double dot = 0.0, nx = 0.0, ny = 0.0;
     const double ma = XM ? mua : 0.0, mb = XM && metric == 4 ? nnd_row_mean_f64<16>(xb, d, l16) : 0.0;
     for (int t = l16; t < d; t += 16) nnd_ref_acc<FAM, NND_HELLINGER_F64>(metric, (double)xa[t] - ma, (double)xb[t] - mb, dot, nx, ny);
     const double dt = nnd_group_sum_f64<16>(dot);
     const double ax = metric == 0 ? 0.0 : nnd_group_sum_f64<16>(nx), ay = metric == 0 ? 0.0 : nnd_group_sum_f64<16>(ny);  // (code 0: dt is all)
     ex_val v;
+    if constexpr (FAM == NND_CODES_BOOL) {  // certified in distance space (ex_certified): no Gram value
+        v.r = nnd_ref_dist<NND_CODES_BOOL>(metric, dt, ax, ay, (double)d);
+        v.g = -INFINITY;
+        v.ax = ax;
+        return v;
+    }
     v.r = nnd_ref_dist<NND_CODES_0_5>(metric, dt, ax, ay);  // (both instances carry the whole conversion: XM splits the loop above only)
     v.g = -INFINITY;
     v.ax = ax;
@@ -257,8 +280,13 @@ __device__ __forceinline__ ex_val ex_pair_f64(int metric, const float *__restric
 
 // Is the row's top k final?  rk / gk / ax: the k-th candidate's exact values; t: the smallest kernel distance the scan left
 // out; na: the query's nrm word; nmax: the largest nrm of the point set (code 2: the largest |x|^2 of the raw rows).
+template <int FAM>
 __device__ __forceinline__ bool ex_certified(int metric, int d, int dp, double rk, double gk, double ax, float t, float na, double nmax) {
     if (t == INFINITY) return true;  // nothing was left out
+    if constexpr (FAM == NND_CODES_BOOL) {  // the scan's values are exact functions of exact counts: the conversion's band alone
+        if (metric == NND_BOOL_FIRST) return rk < (double)t - nnd_exact_band_jaccard((double)t);
+        return rk < (double)t - nnd_exact_band_bool_rational((double)t);
+    }
     if (metric == 0) return rk < (double)t - nnd_exact_band_sqeuclid(dp, (double)na, nmax);
     if (metric == 4) return rk < (double)t - nnd_exact_band_correlation(d, dp);
     if (!(gk > -INFINITY)) return false;
@@ -271,8 +299,8 @@ __device__ __forceinline__ bool ex_certified(int metric, int d, int dp, double r
 }
 
 // ---- refinement and certificate: one wave per query row ----
-template <bool XM>
-__global__ __launch_bounds__(256) void k_exact_refine(const float *__restrict__ x, int d, int dp, int metric, const float *__restrict__ qraw,
+template <int FAM>
+__device__ __forceinline__ void ex_refine_body(const float *__restrict__ x, int d, int dp, int metric, const float *__restrict__ qraw,
                                                       const int32_t *__restrict__ qids, const float *__restrict__ qnrm, int nq, int k, int W,
                                                       const uint32_t *__restrict__ list_e, const float *__restrict__ list_rej,
                                                       const double *__restrict__ nmax, int32_t *__restrict__ out_idx, float *__restrict__ out_dist,
@@ -293,7 +321,7 @@ __global__ __launch_bounds__(256) void k_exact_refine(const float *__restrict__ 
         const int j = j0 + grp;
         const uint32_t e = j < W ? sid[w][j] : NND_EMPTY_E;
         const bool on = e != NND_EMPTY_E;
-        const ex_val v = ex_pair_f64<XM>(metric, xa, x + (int64_t)(on ? (e & NND_IDX_MASK) : 0) * d, d, l16, mua);
+        const ex_val v = ex_pair_f64<FAM>(metric, xa, x + (int64_t)(on ? (e & NND_IDX_MASK) : 0) * d, d, l16, mua);
         axq = v.ax;
         if (l16 == 0 && j < W) {
             sr[w][j] = on ? v.r : INFINITY;
@@ -320,15 +348,30 @@ __global__ __launch_bounds__(256) void k_exact_refine(const float *__restrict__ 
         }
     }
     nnd_wave_lds_sync();
-    if (lane == 0 && !ex_certified(metric, d, dp, kth[w][0], kth[w][1], axq, list_rej[q], qnrm[qid], *nmax)) uncert[atomicAdd(n_uncert, 1)] = q;
+    if (lane == 0 && !ex_certified<FAM>(metric, d, dp, kth[w][0], kth[w][1], axq, list_rej[q], qnrm[qid], *nmax)) uncert[atomicAdd(n_uncert, 1)] = q;
+}
+template <bool XM>
+__global__ __launch_bounds__(256) void k_exact_refine(const float *__restrict__ x, int d, int dp, int metric, const float *__restrict__ qraw,
+                                                      const int32_t *__restrict__ qids, const float *__restrict__ qnrm, int nq, int k, int W,
+                                                      const uint32_t *__restrict__ list_e, const float *__restrict__ list_rej,
+                                                      const double *__restrict__ nmax, int32_t *__restrict__ out_idx, float *__restrict__ out_dist,
+                                                      int32_t *__restrict__ uncert, int32_t *__restrict__ n_uncert) {
+    ex_refine_body<XM ? NND_CODES_0_5 : NND_CODES_01>(x, d, dp, metric, qraw, qids, qnrm, nq, k, W, list_e, list_rej, nmax, out_idx, out_dist, uncert, n_uncert);
+}
+__global__ __launch_bounds__(256) void k_exact_refine_bool(const float *__restrict__ x, int d, int dp, int metric, const float *__restrict__ qraw,
+                                                      const int32_t *__restrict__ qids, const float *__restrict__ qnrm, int nq, int k, int W,
+                                                      const uint32_t *__restrict__ list_e, const float *__restrict__ list_rej,
+                                                      const double *__restrict__ nmax, int32_t *__restrict__ out_idx, float *__restrict__ out_dist,
+                                                      int32_t *__restrict__ uncert, int32_t *__restrict__ n_uncert) {
+    ex_refine_body<NND_CODES_BOOL>(x, d, dp, metric, qraw, qids, qnrm, nq, k, W, list_e, list_rej, nmax, out_idx, out_dist, uncert, n_uncert);
 }
 
 // ---- tier 2: all n original rows in float64, one workgroup per listed query row ----
 // Wave w takes data rows 16 i + 4 w + (0..3), four at a time (16 lanes each), in ascending order, and keeps its k best in an LDS
 // list sorted by (distance, id): a row enters only if it is strictly closer than the list's last (its id is larger than every
 // id the wave has seen).  The four lists are then ranked against each other.
-template <bool XM>
-__global__ __launch_bounds__(256) void k_exact_f64(const float *__restrict__ x, int64_t n, int d, int metric, const float *__restrict__ qraw,
+template <int FAM>
+__device__ __forceinline__ void ex_f64_body(const float *__restrict__ x, int64_t n, int d, int metric, const float *__restrict__ qraw,
                                                    const int32_t *__restrict__ qids, int k, const int32_t *__restrict__ list,
                                                    int32_t *__restrict__ out_idx, float *__restrict__ out_dist) {
     __shared__ double ld[4][NND_WIDE_K];
@@ -342,7 +385,7 @@ __global__ __launch_bounds__(256) void k_exact_f64(const float *__restrict__ x, 
     double worst = INFINITY;
     for (int64_t b0 = 4 * w; b0 < n; b0 += 16) {
         const int64_t jb = b0 + grp;
-        const ex_val v = ex_pair_f64<XM>(metric, xa, x + (jb < n ? jb : 0) * d, d, l16, mua);
+        const ex_val v = ex_pair_f64<FAM>(metric, xa, x + (jb < n ? jb : 0) * d, d, l16, mua);
 #pragma unroll 1
         for (int u = 0; u < 4; u++) {
             const double ru = __longlong_as_double((long long)nnd_readlane_u64((uint64_t)__double_as_longlong(v.r), 16 * u));
@@ -399,6 +442,18 @@ __global__ __launch_bounds__(256) void k_exact_f64(const float *__restrict__ x, 
         }
     }
 }
+template <bool XM>
+__global__ __launch_bounds__(256) void k_exact_f64(const float *__restrict__ x, int64_t n, int d, int metric, const float *__restrict__ qraw,
+                                                   const int32_t *__restrict__ qids, int k, const int32_t *__restrict__ list,
+                                                   int32_t *__restrict__ out_idx, float *__restrict__ out_dist) {
+    ex_f64_body<XM ? NND_CODES_0_5 : NND_CODES_01>(x, n, d, metric, qraw, qids, k, list, out_idx, out_dist);
+}
+__global__ __launch_bounds__(256) void k_exact_f64_bool(const float *__restrict__ x, int64_t n, int d, int metric, const float *__restrict__ qraw,
+                                                   const int32_t *__restrict__ qids, int k, const int32_t *__restrict__ list,
+                                                   int32_t *__restrict__ out_idx, float *__restrict__ out_dist) {
+    ex_f64_body<NND_CODES_BOOL>(x, n, d, metric, qraw, qids, k, list, out_idx, out_dist);
+}
+
 
 // the largest nrm of the point set (codes 0, 3), or the largest |x|^2 of the rows as given (code 2), as a double; 16 lanes per row
 __global__ __launch_bounds__(256) void k_exact_nmax(const float *__restrict__ x, const float *__restrict__ nrm, int64_t n, int d, int metric,
@@ -463,8 +518,9 @@ static int ex_launch_scan(nnd_ctx *ctx, bool xm, bool wide, dim3 grid, const flo
     const size_t lds = sizeof(float) * ((EX_QB + EX_TB) * DC + EX_TB) + sizeof(int32_t) * EX_QB + sizeof(uint2) * EX_QB * EX_PC +
                        (wide ? sizeof(uint64_t) * 4 * NND_WIDE_SCRATCH_WORDS : 0);
     auto kern = xm ? (wide ? k_exact_scan<DC, true, true> : k_exact_scan<DC, true, false>) : (wide ? k_exact_scan<DC, false, true> : k_exact_scan<DC, false, false>);
+    if (nnd_metric_bool(ctx->p.metric)) kern = wide ? k_exact_scan_bool<DC, true> : k_exact_scan_bool<DC, false>;
     if (lds > 48 * 1024) NND_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, ctx->stream, ctx->xp, ctx->nrm, ctx->n, ctx->dp, ctx->p.metric, qx, qnrm, qids, self, nq, nq_pad, W, rows_per_slice,
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, ctx->stream, ctx->xp, ctx->nrm, ctx->n, ctx->dp, nnd_kmetric(ctx), qx, qnrm, qids, self, nq, nq_pad, W, rows_per_slice,
                        le, ld, lth, lrej);
     NND_HIP_CHECK(hipGetLastError());
     return 0;
@@ -478,7 +534,7 @@ int nnd_exact_knn_impl(nnd_ctx *ctx, const int64_t *rows, const float *q, int64_
                        const nnd_exact_dev *dev) {
     const int64_t n = ctx->n;
     const int d = ctx->d, dp = ctx->dp, metric = ctx->p.metric;
-    const bool self = dev ? dev->q_dev == nullptr : q == nullptr, xm = metric >= 2, force_f64 = (ctx->p.flags & NND_FLAG_TEST_EXACT_F64) != 0;
+    const bool self = dev ? dev->q_dev == nullptr : q == nullptr, xm = metric >= 2, bm = nnd_metric_bool(metric), force_f64 = (ctx->p.flags & NND_FLAG_TEST_EXACT_F64) != 0;
     const bool some_rows = dev ? dev->rows_dev != nullptr : rows != nullptr;
     const hipMemcpyKind out_kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     if (n > (int64_t)NND_IDX_MASK) { ctx->set_error("exact search: more than 2^31 - 1 points"); return 1; }
@@ -577,7 +633,7 @@ int nnd_exact_knn_impl(nnd_ctx *ctx, const int64_t *rows, const float *q, int64_
             }
             t_end(ctx, t_scan, &s.ms_scan, true);
             const int t_ref = t_begin(ctx);
-            hipLaunchKernelGGL(xm ? k_exact_refine<true> : k_exact_refine<false>, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, ctx->stream, ctx->x_orig, d, dp, metric, qraw,
+            hipLaunchKernelGGL(bm ? k_exact_refine_bool : (xm ? k_exact_refine<true> : k_exact_refine<false>), dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, ctx->stream, ctx->x_orig, d, dp, metric, qraw,
                                qids, qnrm, nq, k, W, le, lrej, nmax, oi, od, unc, n_unc);
             NND_HIP_CHECK(hipGetLastError());
             t_end(ctx, t_ref, &s.ms_refine, true);
@@ -593,7 +649,7 @@ int nnd_exact_knn_impl(nnd_ctx *ctx, const int64_t *rows, const float *q, int64_
         }
         if (n_fallback > 0) {
             const int t_fb = t_begin(ctx);
-            hipLaunchKernelGGL(xm ? k_exact_f64<true> : k_exact_f64<false>, dim3((unsigned)n_fallback), dim3(256), 0, ctx->stream, ctx->x_orig, n, d, metric, qraw, qids,
+            hipLaunchKernelGGL(bm ? k_exact_f64_bool : (xm ? k_exact_f64<true> : k_exact_f64<false>), dim3((unsigned)n_fallback), dim3(256), 0, ctx->stream, ctx->x_orig, n, d, metric, qraw, qids,
                                k, unc, oi, od);
             NND_HIP_CHECK(hipGetLastError());
             t_end(ctx, t_fb, &s.ms_fallback, true);

@@ -62,3 +62,17 @@ NND_BAND_FN double nnd_exact_gram_of_log_dist(double t) {
 }
 // ... and under 1 / g >= T (one division, rounded once) at most this:
 NND_BAND_FN double nnd_exact_gram_of_inverse_dist(double t) { return (1.0 + 4.0 * NND_EXACT_U) / t; }
+// The boolean family (codes 8..16), DISTANCE space.  The scan's Gram value and both norm words are counts of indicator rows:
+// integers below 2^24, exact in float32 in any summation order.  So the band is that of the conversion alone (metric.h
+// nnd_bool_dist).  The eight rational formulas are quotients of two sums of non-negative terms, every difference in them one of
+// integers that float32 holds exactly: at most three roundings in the denominator (yule: two products and a sum; below 2^24,
+// as at every d below 2^12, none at all) and one in the numerator, then ONE correctly rounded division -- (1 + u)^5 relative,
+// taken as 8 u of the value.  (With exact operands the correctly rounded quotient is monotone in the exact one, and the band
+// is needed only to decide ties strictly; a row whose k-th exact distance EQUALS what the scan left out goes to the float64 tier.)
+NND_BAND_FN double nnd_exact_band_bool_rational(double t) { return 8.0 * NND_EXACT_U * t; }
+// jaccard is -log2f of one correctly rounded quotient in (0, 1]: the quotient's rounding moves the logarithm by at most
+// u / ln 2 < 2 u, and the hardware logarithm is trusted as above, 2^-20 max(1, |log2 x|).  FLT_MAX (no common column) is exact.
+NND_BAND_FN double nnd_exact_band_jaccard(double t) {
+    if (t >= 3.0e38) return 0.0;
+    return 9.5367431640625e-07 * (t > 1.0 ? t : 1.0) + 2.0 * NND_EXACT_U;
+}

@@ -54,9 +54,11 @@ __device__ __forceinline__ void fin_acc(int metric, double a, double b, double &
 }
 // the 16 lanes' partial sums of one pair -> the distance handed back
 template <int FAM>
-__device__ __forceinline__ float fin_value(int metric, double dot, double nx, double ny) {
+__device__ __forceinline__ float fin_value(int metric, double dot, double nx, double ny, int d) {
     const double dt = nnd_group_sum_f64<16>(dot);
     if (metric == 0) return (float)dt;
+    if constexpr (FAM == NND_CODES_BOOL)  // the three counts and the column count (the only family that reads d)
+        return (float)nnd_ref_dist<FAM>(metric, dt, nnd_group_sum_f64<16>(nx), nnd_group_sum_f64<16>(ny), (double)d);
     return (float)nnd_ref_dist<FAM>(metric, dt, nnd_group_sum_f64<16>(nx), nnd_group_sum_f64<16>(ny));
 }
 
@@ -65,7 +67,7 @@ __device__ __forceinline__ float fin_value(int metric, double dot, double nx, do
 // the rows are fetched one after another).
 // METRIC is a template parameter: the euclidean instance does not carry the cosine accumulators (146 -> far fewer
 // registers, i.e. more waves per SIMD for what is a gather-latency-bound kernel).  METRIC 2..6: the other metrics, one
-// instance each.
+// instance each; METRIC 8..16: the boolean family, one instance each (the counts of the rows as given, then the float64 twin).
 template <int METRIC>
 __global__ __launch_bounds__(256, METRIC == 0 ? 6 : 4) void k_finalize(const float *__restrict__ x, int d, int64_t lo, int64_t n, int k, int ks,
                                                   const uint32_t *__restrict__ knn_e, const int32_t *__restrict__ order,
@@ -82,7 +84,7 @@ __global__ __launch_bounds__(256, METRIC == 0 ? 6 : 4) void k_finalize(const flo
     const float *xv = x + v * d;
     const int grp = lane >> 4, l16 = lane & 15;
     const bool vec = (d & 3) == 0;  // rows 16-byte aligned
-    constexpr int metric = METRIC, FAM = METRIC < 2 ? NND_CODES_01 : NND_CODES_ANY;
+    constexpr int metric = METRIC, FAM = METRIC < 2 ? NND_CODES_01 : (METRIC >= NND_BOOL_FIRST ? NND_CODES_BOOL : NND_CODES_ANY);
     float mine = INFINITY;
     const int nsteps = (k + 3) >> 2;
     for (int s0 = 0; s0 < nsteps; s0 += 4) {
@@ -138,7 +140,7 @@ __global__ __launch_bounds__(256, METRIC == 0 ? 6 : 4) void k_finalize(const flo
         }
 #pragma unroll
         for (int u = 0; u < 4; u++) {
-            float val = fin_value<FAM>(metric, dot[u], nx[u], ny[u]);
+            float val = fin_value<FAM>(metric, dot[u], nx[u], ny[u], d);
             if (!on[u]) val = INFINITY;
             // neighbour j = 4 * (s0 + u) + group: lane j takes it from (any lane of) group j & 3
             const float got = __shfl(val, 16 * (lane & 3), 64);
@@ -280,13 +282,14 @@ __global__ __launch_bounds__(256, METRIC == 0 ? 6 : 4) void k_finalize16(const f
 // 64 < k <= NND_WIDE_K: one wave per row, ids / exact distances through LDS, four neighbours at a time (16 lanes each), ranks by
 // counting over the LDS copy.  Same arithmetic as k_finalize.  XM: the instance for the metrics of codes 2..6 (the
 // sqeuclidean / cosine instance does not carry their registers).
-template <bool XM>
-__global__ __launch_bounds__(256) void k_finalize_wide(const float *__restrict__ x, int d, int64_t lo, int64_t n, int k, int ks, int metric,
-                                                       const uint32_t *__restrict__ knn_e, int32_t *__restrict__ out_idx,
-                                                       float *__restrict__ out_dist) {
+// The body is shared with k_finalize_wide_bool, the boolean family's instance (FAM = NND_CODES_BOOL).
+template <int FAM>
+__device__ __forceinline__ void fin_wide_body(const float *__restrict__ x, int d, int64_t lo, int64_t n, int k, int ks, int metric,
+                                              const uint32_t *__restrict__ knn_e, int32_t *__restrict__ out_idx,
+                                              float *__restrict__ out_dist) {
     __shared__ uint32_t sid[4][NND_WIDE_K];
     __shared__ float sdist[4][NND_WIDE_K];
-    constexpr int FAM = XM ? NND_CODES_ANY : NND_CODES_01;
+    constexpr bool XM = FAM != NND_CODES_01;
     const int lane = nnd_lane(), w = threadIdx.x >> 6, grp = lane >> 4, l16 = lane & 15;
     const int64_t v = lo + (int64_t)blockIdx.x * 4 + w;
     if (v >= n) return;
@@ -299,10 +302,10 @@ __global__ __launch_bounds__(256) void k_finalize_wide(const float *__restrict__
         const bool on = ej != NND_EMPTY_E;
         const float *xu = x + (int64_t)(on ? (ej & NND_IDX_MASK) : 0) * d;
         double dot = 0.0, nx = 0.0, ny = 0.0;
-        const bool corr = XM && metric == 4;
+        const bool corr = XM && FAM != NND_CODES_BOOL && metric == 4;
         const double mua = corr ? nnd_row_mean_f64<16>(xv, d, l16) : 0.0, mub = corr ? nnd_row_mean_f64<16>(xu, d, l16) : 0.0;
         for (int t = l16; t < d; t += 16) fin_acc<FAM>(metric, (double)xv[t] - mua, (double)xu[t] - mub, dot, nx, ny);
-        float val = fin_value<FAM>(metric, dot, nx, ny);
+        float val = fin_value<FAM>(metric, dot, nx, ny, d);
         if (!on) val = INFINITY;
         if (l16 == 0 && j < k) sdist[w][j] = val;
     }
@@ -321,11 +324,22 @@ __global__ __launch_bounds__(256) void k_finalize_wide(const float *__restrict__
         out_dist[(v - lo) * k + r] = sdist[w][j];
     }
 }
+template <bool XM>
+__global__ __launch_bounds__(256) void k_finalize_wide(const float *__restrict__ x, int d, int64_t lo, int64_t n, int k, int ks, int metric,
+                                                       const uint32_t *__restrict__ knn_e, int32_t *__restrict__ out_idx,
+                                                       float *__restrict__ out_dist) {
+    fin_wide_body<XM ? NND_CODES_ANY : NND_CODES_01>(x, d, lo, n, k, ks, metric, knn_e, out_idx, out_dist);
+}
+__global__ __launch_bounds__(256) void k_finalize_wide_bool(const float *__restrict__ x, int d, int64_t lo, int64_t n, int k, int ks, int metric,
+                                                            const uint32_t *__restrict__ knn_e, int32_t *__restrict__ out_idx,
+                                                            float *__restrict__ out_dist) {
+    fin_wide_body<NND_CODES_BOOL>(x, d, lo, n, k, ks, metric, knn_e, out_idx, out_dist);
+}
 
 int nnd_launch_finalize(nnd_ctx *ctx, int32_t *out_idx_dev, float *out_dist_dev) {
     unsigned grid = (unsigned)((ctx->own_hi - ctx->own_lo + 3) / 4);
     if (ctx->k > 64) {
-        hipLaunchKernelGGL(ctx->p.metric >= 2 ? k_finalize_wide<true> : k_finalize_wide<false>, dim3(grid), dim3(256), 0, ctx->stream, ctx->x_orig, ctx->d, ctx->own_lo, ctx->own_hi, ctx->k, ctx->ks,
+        hipLaunchKernelGGL(ctx->p.metric >= NND_BOOL_FIRST ? k_finalize_wide_bool : (ctx->p.metric >= 2 ? k_finalize_wide<true> : k_finalize_wide<false>), dim3(grid), dim3(256), 0, ctx->stream, ctx->x_orig, ctx->d, ctx->own_lo, ctx->own_hi, ctx->k, ctx->ks,
                            ctx->p.metric, ctx->knn_e, out_idx_dev, out_dist_dev);
         NND_HIP_CHECK(hipGetLastError());
         return 0;
@@ -346,6 +360,15 @@ int nnd_launch_finalize(nnd_ctx *ctx, int32_t *out_idx_dev, float *out_dist_dev)
         case 4: kern = k_finalize<4>; break;
         case 5: kern = k_finalize<5>; break;
         case 6: kern = k_finalize<6>; break;
+        case 8: kern = k_finalize<8>; break;
+        case 9: kern = k_finalize<9>; break;
+        case 10: kern = k_finalize<10>; break;
+        case 11: kern = k_finalize<11>; break;
+        case 12: kern = k_finalize<12>; break;
+        case 13: kern = k_finalize<13>; break;
+        case 14: kern = k_finalize<14>; break;
+        case 15: kern = k_finalize<15>; break;
+        case 16: kern = k_finalize<16>; break;
     }
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, ctx->stream, ctx->x_orig, ctx->d, ctx->own_lo, ctx->own_hi,
                        ctx->k, ctx->ks, ctx->knn_e, nnd_vertex_order(ctx), out_idx_dev, out_dist_dev);
@@ -356,7 +379,9 @@ int nnd_launch_finalize(nnd_ctx *ctx, int32_t *out_idx_dev, float *out_dist_dev)
 // ---- debug / parity: the MFMA Gram tile on arbitrary row lists (tests/test_gpu_kernels.py) ----
 // one wave per 16x16 output tile; operands come straight from global memory with the same K mapping
 // as gram.h (chunk c of a row feeds lane group c & 3).
-__global__ __launch_bounds__(64) void k_pairwise(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
+// (the body of k_pairwise and of k_pairwise_bool, the instance of the boolean family: metric.h nnd_metric_family)
+template <int FAM>
+__device__ __forceinline__ void fin_pairwise_body(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
                                                  int metric, const int32_t *__restrict__ rows_a, int na,
                                                  const int32_t *__restrict__ rows_b, int nb, float *__restrict__ out) {
     const int lane = nnd_lane(), r16 = lane & 15, g = lane >> 4;
@@ -379,13 +404,23 @@ __global__ __launch_bounds__(64) void k_pairwise(const float *__restrict__ xp, i
     for (int r = 0; r < 4; r++) {
         int row = ta * 16 + 4 * g + r;
         int idr = row < na ? rows_a[row] : -1;
-        if (row < na && col < nb) out[(int64_t)row * nb + col] = nnd_gram_to_dist<NND_CODES_ANY>(metric, acc[r], idr >= 0 ? nrm[idr] : 0.0f, nbv);
+        if (row < na && col < nb) out[(int64_t)row * nb + col] = nnd_gram_to_dist<FAM>(metric, acc[r], idr >= 0 ? nrm[idr] : 0.0f, nbv);
     }
+}
+__global__ __launch_bounds__(64) void k_pairwise(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
+                                                 int metric, const int32_t *__restrict__ rows_a, int na,
+                                                 const int32_t *__restrict__ rows_b, int nb, float *__restrict__ out) {
+    fin_pairwise_body<NND_CODES_ANY>(xp, dp, nrm, metric, rows_a, na, rows_b, nb, out);
+}
+__global__ __launch_bounds__(64) void k_pairwise_bool(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
+                                                 int metric, const int32_t *__restrict__ rows_a, int na,
+                                                 const int32_t *__restrict__ rows_b, int nb, float *__restrict__ out) {
+    fin_pairwise_body<NND_CODES_BOOL>(xp, dp, nrm, metric, rows_a, na, rows_b, nb, out);
 }
 
 int nnd_launch_pairwise(nnd_ctx *ctx, const int32_t *rows_a_dev, int na, const int32_t *rows_b_dev, int nb, float *out_dev) {
     dim3 grid((nb + 15) / 16, (na + 15) / 16);
-    hipLaunchKernelGGL(k_pairwise, grid, dim3(64), 0, ctx->stream, ctx->xp, ctx->dp, ctx->nrm, ctx->p.metric, rows_a_dev, na,
+    hipLaunchKernelGGL(nnd_metric_bool(ctx->p.metric) ? k_pairwise_bool : k_pairwise, grid, dim3(64), 0, ctx->stream, ctx->xp, ctx->dp, ctx->nrm, nnd_kmetric(ctx), rows_a_dev, na,
                        rows_b_dev, nb, out_dev);
     NND_HIP_CHECK(hipGetLastError());
     return 0;

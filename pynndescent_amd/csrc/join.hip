@@ -57,7 +57,7 @@ __device__ __forceinline__ bool klist_has(const uint32_t *kl, uint32_t id) {
 #endif
 // XM, the last template argument of both join kernels, is the metric family of the instance (metric.h nnd_metric_family); it
 // stays an int so that the kernels keep their names
-static_assert(NND_CODES_01 == 0 && NND_CODES_0_5 == 1 && NND_CODE_6 == 2, "launch_join_xm and the kernels' names count on these values");
+static_assert(NND_CODES_01 == 0 && NND_CODES_0_5 == 1 && NND_CODE_6 == 2 && NND_CODES_BOOL == 3, "launch_join_xm and the kernels' names count on these values");
 template <int DC, int KS16, bool SHARD, int XM = 0>
 __global__ __launch_bounds__(256, NND_J16_WAVES) void k_local_join16(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
                                                          int metric, const int32_t *__restrict__ cand,
@@ -427,7 +427,7 @@ static int launch_join16_t(nnd_ctx *ctx, int64_t v_begin, int64_t v_end) {
     uint32_t slot_seed = nnd_hash2(ctx->seed ^ 0x2545F491u, (uint32_t)ctx->iter);
     ctx->pbuf_clean = false;
     const int32_t *order = join_order(ctx, v_begin, v_end);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, ctx->stream, ctx->xp, ctx->dp, ctx->nrm, ctx->p.metric, ctx->cand,
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, ctx->stream, ctx->xp, ctx->dp, ctx->nrm, nnd_kmetric(ctx), ctx->cand,
                        order, v_begin, v_end, ctx->k, ctx->ks, ctx->knn_e, ctx->th, ctx->pbuf, ctx->pdirty, ctx->pcap, slot_seed,
                        ctx->counters, nnd_list_lo(ctx), nnd_list_hi(ctx), ctx->pbuf_r, ctx->pcap_r, ctx->own_lo, ctx->own_hi);
     NND_HIP_CHECK(hipGetLastError());
@@ -873,7 +873,7 @@ static int launch_join_w_t(nnd_ctx *ctx, int64_t v_begin, int64_t v_end, int cst
     uint32_t slot_seed = nnd_hash2(ctx->seed ^ 0x2545F491u, (uint32_t)ctx->iter);
     ctx->pbuf_clean = false;
     const int32_t *order = join_order(ctx, v_begin, v_end);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, ctx->stream, ctx->xp, ctx->dp, ctx->nrm, ctx->p.metric, ctx->cand,
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, ctx->stream, ctx->xp, ctx->dp, ctx->nrm, nnd_kmetric(ctx), ctx->cand,
                        order, v_begin, v_end, ctx->k, ctx->ks, ctx->knn_e, ctx->th, ctx->pbuf, ctx->pdirty,
                        ctx->pcap, slot_seed, ctx->counters, nnd_list_lo(ctx), nnd_list_hi(ctx), ctx->pbuf_r, ctx->pcap_r, ctx->own_lo, ctx->own_hi,
                        cstride, new_off, old_off);
@@ -934,6 +934,7 @@ static int launch_join_blocked(nnd_ctx *ctx, int64_t v_begin, int64_t v_end) {
 // carry their conversions (a runtime branch among six metrics costs the k_local_join16<32, *, 0> epilogue four registers), and
 // code 6 has instances of its own (2: its conversion alone, no branch on the metric) for the same reason: as one more branch of
 // the XM = 1 epilogue it took k_local_join16<64, 1, false, 1> from 127 to 131 registers, a wave per SIMD less for codes 2..5
+// The boolean family (3) has instances of its own likewise: the branch among its nine formulas is paid by nobody else.
 template <int XM>
 static int launch_join_xm(nnd_ctx *ctx, int64_t v_begin, int64_t v_end) {
     const bool wide = ctx->dp >= 128;
@@ -953,5 +954,6 @@ static int launch_join_xm(nnd_ctx *ctx, int64_t v_begin, int64_t v_end) {
 int nnd_launch_join(nnd_ctx *ctx, int64_t v_begin, int64_t v_end) {
     if (v_end <= v_begin) return 0;
     if (ctx->p.metric == 6) return launch_join_xm<NND_CODE_6>(ctx, v_begin, v_end);
+    if (ctx->p.metric >= NND_BOOL_FIRST) return launch_join_xm<NND_CODES_BOOL>(ctx, v_begin, v_end);  // (`metric` carries d: nnd_kmetric)
     return ctx->p.metric >= 2 ? launch_join_xm<NND_CODES_0_5>(ctx, v_begin, v_end) : launch_join_xm<NND_CODES_01>(ctx, v_begin, v_end);
 }

@@ -45,8 +45,9 @@ struct leaf_cfg {
 };
 
 // QW (host: k <= 16 and the whole distance block in LDS): quarter-wave merges, four rows per wave (merge.h)
-template <int NT, int NW, int DC, bool QW = false>
-__global__ __launch_bounds__(NW * 64, (NT <= 5 && NW == 8) ? 8 : (QW && NT <= 5 && NW == 4) ? NND_LEAF_QW_OCC : 1) void k_leaf_join(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
+// (the body of k_leaf_join and of k_leaf_join_bool, the instance of the boolean family: metric.h nnd_metric_family)
+template <int FAM, int NT, int NW, int DC, bool QW = false>
+__device__ __forceinline__ void lf_leaf_join_body(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
                                                        int metric, const int32_t *__restrict__ perm,
                                                        const int32_t *__restrict__ wl_start,
                                                        const int32_t *__restrict__ wl_len, int64_t leaf0,
@@ -238,7 +239,7 @@ __global__ __launch_bounds__(NW * 64, (NT <= 5 && NW == 8) ? 8 : (QW && NT <= 5 
 #pragma unroll
             for (int r = 0; r < 4; r++) {
                 const int il = I * 16 + 4 * g + r;
-                const float dv = nnd_gram_to_dist<NND_CODES_ANY>(metric, acct[q][r], nrs[il], nj);
+                const float dv = nnd_gram_to_dist<FAM>(metric, acct[q][r], nrs[il], nj);
                 Dm[il * C::DSTRIDE + j] = dv;
                 if (I != J) Dm[j * C::DSTRIDE + il] = dv;  // the mirrored tile
             }
@@ -328,7 +329,7 @@ __global__ __launch_bounds__(NW * 64, (NT <= 5 && NW == 8) ? 8 : (QW && NT <= 5 
 #pragma unroll
                     for (int r = 0; r < 4; r++) {
                         const int il = 4 * g + r;
-                        Dw[il * C::DSTRIDE + j] = nnd_gram_to_dist<NND_CODES_ANY>(metric, acc[tr][J][r], nrs[I * 16 + il], nj);
+                        Dw[il * C::DSTRIDE + j] = nnd_gram_to_dist<FAM>(metric, acc[tr][J][r], nrs[I * 16 + il], nj);
                     }
                 }
             }
@@ -373,6 +374,26 @@ __global__ __launch_bounds__(NW * 64, (NT <= 5 && NW == 8) ? 8 : (QW && NT <= 5 
         nnd_count(counters, CNT_MFMA, (long long)(C::FULLD ? nt * (nt + 1) / 2 : nt * nt) * (dp >> 2));
     }
 }
+template <int NT, int NW, int DC, bool QW = false>
+__global__ __launch_bounds__(NW * 64, (NT <= 5 && NW == 8) ? 8 : (QW && NT <= 5 && NW == 4) ? NND_LEAF_QW_OCC : 1) void k_leaf_join(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
+                                                       int metric, const int32_t *__restrict__ perm,
+                                                       const int32_t *__restrict__ wl_start,
+                                                       const int32_t *__restrict__ wl_len, int64_t leaf0,
+                                                       int64_t n_leaves, int k, int ks, uint32_t *__restrict__ knn_e,
+                                                       float *__restrict__ knn_d, float *__restrict__ th,
+                                                       long long *__restrict__ counters, int m_lo) {
+    lf_leaf_join_body<NND_CODES_ANY, NT, NW, DC, QW>(xp, dp, nrm, metric, perm, wl_start, wl_len, leaf0, n_leaves, k, ks, knn_e, knn_d, th, counters, m_lo);
+}
+template <int NT, int NW, int DC, bool QW = false>
+__global__ __launch_bounds__(NW * 64, (NT <= 5 && NW == 8) ? 8 : (QW && NT <= 5 && NW == 4) ? NND_LEAF_QW_OCC : 1) void k_leaf_join_bool(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
+                                                       int metric, const int32_t *__restrict__ perm,
+                                                       const int32_t *__restrict__ wl_start,
+                                                       const int32_t *__restrict__ wl_len, int64_t leaf0,
+                                                       int64_t n_leaves, int k, int ks, uint32_t *__restrict__ knn_e,
+                                                       float *__restrict__ knn_d, float *__restrict__ th,
+                                                       long long *__restrict__ counters, int m_lo) {
+    lf_leaf_join_body<NND_CODES_BOOL, NT, NW, DC, QW>(xp, dp, nrm, metric, perm, wl_start, wl_len, leaf0, n_leaves, k, ks, knn_e, knn_d, th, counters, m_lo);
+}
 
 // Leaves of more than 96 points (k = 30, the reference's default, gives leaf_size 150).  The one-workgroup-per-leaf kernel
 // above then keeps 16 rows of the distance block per wave, needs 82 KB of LDS (ONE workgroup of 8 waves per CU) and deals
@@ -383,8 +404,9 @@ __global__ __launch_bounds__(NW * 64, (NT <= 5 && NW == 8) ? 8 : (QW && NT <= 5 
 // same share of the merges; the leaf's Gram block is computed twice (no symmetry across workgroups) and its rows are
 // staged once per block (the reason for 64-row blocks: 32-row blocks staged every leaf five times).  Rows of one leaf
 // are owned by exactly one workgroup: no atomics.
-template <int NT, int NW = 8, bool WIDE = false>
-__global__ __launch_bounds__(NW * 64, 2) void k_leaf_join_rb(const float *__restrict__ xp, int dp, const float *__restrict__ nrm, int metric,
+// (the body of k_leaf_join_rb and of k_leaf_join_rb_bool, the instance of the boolean family: metric.h nnd_metric_family)
+template <int FAM, int NT, int NW = 8, bool WIDE = false>
+__device__ __forceinline__ void lf_leaf_join_rb_body(const float *__restrict__ xp, int dp, const float *__restrict__ nrm, int metric,
                                                          const int32_t *__restrict__ perm, const int32_t *__restrict__ wl_start,
                                                          const int32_t *__restrict__ wl_len, int64_t leaf0, int64_t n_leaves, int k, int ks,
                                                          uint32_t *__restrict__ knn_e, float *__restrict__ knn_d, float *__restrict__ th,
@@ -473,7 +495,7 @@ __global__ __launch_bounds__(NW * 64, 2) void k_leaf_join_rb(const float *__rest
 #pragma unroll
         for (int r = 0; r < 4; r++) {
             const int il = tI[q] * 16 - r0 + 4 * g + r;
-            Dm[il * DSTRIDE + j] = nnd_gram_to_dist<NND_CODES_ANY>(metric, acc[q][r], nrs[r0 + il], nj);
+            Dm[il * DSTRIDE + j] = nnd_gram_to_dist<FAM>(metric, acc[q][r], nrs[r0 + il], nj);
         }
     }
     __syncthreads();
@@ -534,6 +556,22 @@ __global__ __launch_bounds__(NW * 64, 2) void k_leaf_join_rb(const float *__rest
         nnd_count(counters, CNT_MFMA, (long long)trows * nt * (dp >> 2));
     }
 }
+template <int NT, int NW = 8, bool WIDE = false>
+__global__ __launch_bounds__(NW * 64, 2) void k_leaf_join_rb(const float *__restrict__ xp, int dp, const float *__restrict__ nrm, int metric,
+                                                         const int32_t *__restrict__ perm, const int32_t *__restrict__ wl_start,
+                                                         const int32_t *__restrict__ wl_len, int64_t leaf0, int64_t n_leaves, int k, int ks,
+                                                         uint32_t *__restrict__ knn_e, float *__restrict__ knn_d, float *__restrict__ th,
+                                                         long long *__restrict__ counters) {
+    lf_leaf_join_rb_body<NND_CODES_ANY, NT, NW, WIDE>(xp, dp, nrm, metric, perm, wl_start, wl_len, leaf0, n_leaves, k, ks, knn_e, knn_d, th, counters);
+}
+template <int NT, int NW = 8, bool WIDE = false>
+__global__ __launch_bounds__(NW * 64, 2) void k_leaf_join_rb_bool(const float *__restrict__ xp, int dp, const float *__restrict__ nrm, int metric,
+                                                         const int32_t *__restrict__ perm, const int32_t *__restrict__ wl_start,
+                                                         const int32_t *__restrict__ wl_len, int64_t leaf0, int64_t n_leaves, int k, int ks,
+                                                         uint32_t *__restrict__ knn_e, float *__restrict__ knn_d, float *__restrict__ th,
+                                                         long long *__restrict__ counters) {
+    lf_leaf_join_rb_body<NND_CODES_BOOL, NT, NW, WIDE>(xp, dp, nrm, metric, perm, wl_start, wl_len, leaf0, n_leaves, k, ks, knn_e, knn_d, th, counters);
+}
 
 // Rows of 17 .. 32 neighbours (k = 30, the reference's default, with leaves of up to 150 points), round 6.  k_leaf_join_rb above
 // gives every 64-row block of a leaf its own workgroup: the leaf's rows are staged once per block (three times at 150 points),
@@ -550,8 +588,9 @@ __global__ __launch_bounds__(NW * 64, 2) void k_leaf_join_rb(const float *__rest
 #ifndef NND_SYM_OCC_L
 #define NND_SYM_OCC_L 3
 #endif
-template <int NT, int NW = 8>
-__global__ __launch_bounds__(NW * 64, NT <= 6 ? NND_SYM_OCC_S : NND_SYM_OCC_L) void k_leaf_join_sym(const float *__restrict__ xp, int dp, const float *__restrict__ nrm, int metric,
+// (the body of k_leaf_join_sym and of k_leaf_join_sym_bool, the instance of the boolean family: metric.h nnd_metric_family)
+template <int FAM, int NT, int NW = 8>
+__device__ __forceinline__ void lf_leaf_join_sym_body(const float *__restrict__ xp, int dp, const float *__restrict__ nrm, int metric,
                                                           const int32_t *__restrict__ perm, const int32_t *__restrict__ wl_start,
                                                           const int32_t *__restrict__ wl_len, int64_t leaf0, int64_t n_leaves, int k, int ks,
                                                           uint32_t *__restrict__ knn_e, float *__restrict__ knn_d, float *__restrict__ th,
@@ -636,7 +675,7 @@ __global__ __launch_bounds__(NW * 64, NT <= 6 ? NND_SYM_OCC_S : NND_SYM_OCC_L) v
         if (!tOn[q]) continue;
         const float nj = nrs[tJ[q] * 16 + r16];
 #pragma unroll
-        for (int r = 0; r < 4; r++) acc[q][r] = nnd_gram_to_dist<NND_CODES_ANY>(metric, acc[q][r], nrs[tI[q] * 16 + 4 * g + r], nj);
+        for (int r = 0; r < 4; r++) acc[q][r] = nnd_gram_to_dist<FAM>(metric, acc[q][r], nrs[tI[q] * 16 + 4 * g + r], nj);
     }
     float *Dm = big;  // RB x DSTRIDE: row il = leaf row p0 + il
     int accepted = 0;
@@ -698,6 +737,22 @@ __global__ __launch_bounds__(NW * 64, NT <= 6 ? NND_SYM_OCC_S : NND_SYM_OCC_L) v
         nnd_count(counters, CNT_MFMA, (long long)(nt * (nt + 1) / 2) * (dp >> 2));
     }
 }
+template <int NT, int NW = 8>
+__global__ __launch_bounds__(NW * 64, NT <= 6 ? NND_SYM_OCC_S : NND_SYM_OCC_L) void k_leaf_join_sym(const float *__restrict__ xp, int dp, const float *__restrict__ nrm, int metric,
+                                                          const int32_t *__restrict__ perm, const int32_t *__restrict__ wl_start,
+                                                          const int32_t *__restrict__ wl_len, int64_t leaf0, int64_t n_leaves, int k, int ks,
+                                                          uint32_t *__restrict__ knn_e, float *__restrict__ knn_d, float *__restrict__ th,
+                                                          long long *__restrict__ counters, int m_lo) {
+    lf_leaf_join_sym_body<NND_CODES_ANY, NT, NW>(xp, dp, nrm, metric, perm, wl_start, wl_len, leaf0, n_leaves, k, ks, knn_e, knn_d, th, counters, m_lo);
+}
+template <int NT, int NW = 8>
+__global__ __launch_bounds__(NW * 64, NT <= 6 ? NND_SYM_OCC_S : NND_SYM_OCC_L) void k_leaf_join_sym_bool(const float *__restrict__ xp, int dp, const float *__restrict__ nrm, int metric,
+                                                          const int32_t *__restrict__ perm, const int32_t *__restrict__ wl_start,
+                                                          const int32_t *__restrict__ wl_len, int64_t leaf0, int64_t n_leaves, int k, int ks,
+                                                          uint32_t *__restrict__ knn_e, float *__restrict__ knn_d, float *__restrict__ th,
+                                                          long long *__restrict__ counters, int m_lo) {
+    lf_leaf_join_sym_body<NND_CODES_BOOL, NT, NW>(xp, dp, nrm, metric, perm, wl_start, wl_len, leaf0, n_leaves, k, ks, knn_e, knn_d, th, counters, m_lo);
+}
 
 // Work list: leaves longer than 256 points (possible only when max_depth cuts the recursion short,
 // rp_trees.py:2188) are cut into runs of <= 256 consecutive positions for seeding purposes.
@@ -709,62 +764,63 @@ static constexpr int LEAF_MAX = 256;
 static int run_leaf_rounds(nnd_ctx *ctx, const int32_t *perm, const int32_t *d_ws, const int32_t *d_wl,
                            const std::vector<int64_t> &tb, int maxlen) {
     if (nnd_zero_counters(ctx)) return 1;
+    const bool bm = nnd_metric_bool(ctx->p.metric);  // the boolean family's instances (metric.h NND_CODES_BOOL)
     const int T = (int)tb.size() - 1;
     for (int t = 0; t < T; t++) {
         int64_t cnt = tb[t + 1] - tb[t];
         if (cnt <= 0) continue;
         dim3 grid((unsigned)cnt);
-#define LEAF_ARGS ctx->xp, ctx->dp, ctx->nrm, ctx->p.metric, perm, d_ws, d_wl, tb[t], tb[t + 1], ctx->k, ctx->ks, \
+#define LEAF_ARGS ctx->xp, ctx->dp, ctx->nrm, nnd_kmetric(ctx), perm, d_ws, d_wl, tb[t], tb[t + 1], ctx->k, ctx->ks, \
                   ctx->knn_e, ctx->knn_d, ctx->th, ctx->counters
         const bool qw = ctx->k <= 16;
         if (ctx->k > NND_MAX_K) {  // wide rows: the row-block kernel with LDS merges, whatever the leaf size
             if (maxlen <= 128)
-                hipLaunchKernelGGL((k_leaf_join_rb<8, 8, true>), dim3((unsigned)cnt, 2), dim3(512), 0, ctx->stream, LEAF_ARGS);
+                hipLaunchKernelGGL((bm ? k_leaf_join_rb_bool<8, 8, true> : k_leaf_join_rb<8, 8, true>), dim3((unsigned)cnt, 2), dim3(512), 0, ctx->stream, LEAF_ARGS);
             else if (maxlen <= 160)
-                hipLaunchKernelGGL((k_leaf_join_rb<10, 8, true>), dim3((unsigned)cnt, 3), dim3(512), 0, ctx->stream, LEAF_ARGS);
+                hipLaunchKernelGGL((bm ? k_leaf_join_rb_bool<10, 8, true> : k_leaf_join_rb<10, 8, true>), dim3((unsigned)cnt, 3), dim3(512), 0, ctx->stream, LEAF_ARGS);
             else
-                hipLaunchKernelGGL((k_leaf_join_rb<16, 8, true>), dim3((unsigned)cnt, 4), dim3(512), 0, ctx->stream, LEAF_ARGS);
+                hipLaunchKernelGGL((bm ? k_leaf_join_rb_bool<16, 8, true> : k_leaf_join_rb<16, 8, true>), dim3((unsigned)cnt, 4), dim3(512), 0, ctx->stream, LEAF_ARGS);
         }
 #ifndef NND_LEAF_OLD_K32
         else if (!qw && ctx->k <= 32 && maxlen <= 160) {  // k = 17 .. 32: one workgroup per leaf, two rows per wave (k_leaf_join_sym)
-            hipLaunchKernelGGL((k_leaf_join_sym<6, 8>), grid, dim3(512), 0, ctx->stream, LEAF_ARGS, 0);
-            if (maxlen > 96) hipLaunchKernelGGL((k_leaf_join_sym<10, 8>), grid, dim3(512), 0, ctx->stream, LEAF_ARGS, 96);
+            hipLaunchKernelGGL((bm ? k_leaf_join_sym_bool<6, 8> : k_leaf_join_sym<6, 8>), grid, dim3(512), 0, ctx->stream, LEAF_ARGS, 0);
+            if (maxlen > 96) hipLaunchKernelGGL((bm ? k_leaf_join_sym_bool<10, 8> : k_leaf_join_sym<10, 8>), grid, dim3(512), 0, ctx->stream, LEAF_ARGS, 96);
         }
 #endif
         else if (maxlen <= 64 && qw)
-            hipLaunchKernelGGL((k_leaf_join<4, 8, 64, true>), grid, dim3(512), 0, ctx->stream, LEAF_ARGS, 0);
+            hipLaunchKernelGGL((bm ? k_leaf_join_bool<4, 8, 64, true> : k_leaf_join<4, 8, 64, true>), grid, dim3(512), 0, ctx->stream, LEAF_ARGS, 0);
         else if (maxlen <= 64)
-            hipLaunchKernelGGL((k_leaf_join<4, 8, 64>), grid, dim3(512), 0, ctx->stream, LEAF_ARGS, 0);
+            hipLaunchKernelGGL((bm ? k_leaf_join_bool<4, 8, 64> : k_leaf_join<4, 8, 64>), grid, dim3(512), 0, ctx->stream, LEAF_ARGS, 0);
         else if (maxlen <= 80 && qw) {  // the default leaf_size (<= 75 points) with k <= 16
             // Two size classes, two launches over the tree's leaf table (a workgroup whose leaf belongs to the other class
             // leaves at once): leaves of <= 64 points -- 85 % of the leaves, 3/4 of the points -- get FOUR waves and 21 KB of LDS,
             // so that 6 of them are in flight per CU instead of 4.  The kernel is bound by exposed latency, not by a pipe
             // (profiles/r06_leaf_occupancy.log: 375 / 425 / 535 us per tree with 4 / 3 / 2 workgroups per CU).
 #ifdef NND_LEAF_ONE_CLASS
-            hipLaunchKernelGGL((k_leaf_join<5, 8, 64, true>), grid, dim3(512), 0, ctx->stream, LEAF_ARGS, 0);
+            hipLaunchKernelGGL((bm ? k_leaf_join_bool<5, 8, 64, true> : k_leaf_join<5, 8, 64, true>), grid, dim3(512), 0, ctx->stream, LEAF_ARGS, 0);
 #else
-            hipLaunchKernelGGL((k_leaf_join<4, 4, 64, true>), grid, dim3(256), 0, ctx->stream, LEAF_ARGS, 0);
+            hipLaunchKernelGGL((bm ? k_leaf_join_bool<4, 4, 64, true> : k_leaf_join<4, 4, 64, true>), grid, dim3(256), 0, ctx->stream, LEAF_ARGS, 0);
 #ifdef NND_LEAF_EMPTY_L  // timing experiment: what do the workgroups that leave at once cost?
-            hipLaunchKernelGGL((k_leaf_join<5, 8, 64, true>), grid, dim3(512), 0, ctx->stream, LEAF_ARGS, 1000);
+            hipLaunchKernelGGL((bm ? k_leaf_join_bool<5, 8, 64, true> : k_leaf_join<5, 8, 64, true>), grid, dim3(512), 0, ctx->stream, LEAF_ARGS, 1000);
 #elif defined(NND_LEAF_L_NW4)  // experiment: the large class with four waves too
-            hipLaunchKernelGGL((k_leaf_join<5, 4, 64, true>), grid, dim3(256), 0, ctx->stream, LEAF_ARGS, 64);
+            hipLaunchKernelGGL((bm ? k_leaf_join_bool<5, 4, 64, true> : k_leaf_join<5, 4, 64, true>), grid, dim3(256), 0, ctx->stream, LEAF_ARGS, 64);
 #else
-            hipLaunchKernelGGL((k_leaf_join<5, 8, 64, true>), grid, dim3(512), 0, ctx->stream, LEAF_ARGS, 64);
+            hipLaunchKernelGGL((bm ? k_leaf_join_bool<5, 8, 64, true> : k_leaf_join<5, 8, 64, true>), grid, dim3(512), 0, ctx->stream, LEAF_ARGS, 64);
 #endif
 #endif
         }
         else if (maxlen <= 80)
-            hipLaunchKernelGGL((k_leaf_join<5, 8, 64>), grid, dim3(512), 0, ctx->stream, LEAF_ARGS, 0);
+            hipLaunchKernelGGL((bm ? k_leaf_join_bool<5, 8, 64> : k_leaf_join<5, 8, 64>), grid, dim3(512), 0, ctx->stream, LEAF_ARGS, 0);
         else if (maxlen <= 96 && qw)
-            hipLaunchKernelGGL((k_leaf_join<6, 8, 64, true>), grid, dim3(512), 0, ctx->stream, LEAF_ARGS, 0);
+            hipLaunchKernelGGL((bm ? k_leaf_join_bool<6, 8, 64, true> : k_leaf_join<6, 8, 64, true>), grid, dim3(512), 0, ctx->stream, LEAF_ARGS, 0);
         else if (maxlen <= 96)
-            hipLaunchKernelGGL((k_leaf_join<6, 8, 64>), grid, dim3(512), 0, ctx->stream, LEAF_ARGS, 0);
+            hipLaunchKernelGGL((bm ? k_leaf_join_bool<6, 8, 64> : k_leaf_join<6, 8, 64>), grid, dim3(512), 0, ctx->stream, LEAF_ARGS, 0);
         else if (maxlen <= 128)  // larger leaves: a workgroup per block of 32 rows (k_leaf_join_rb)
-            hipLaunchKernelGGL((k_leaf_join_rb<8, 8>), dim3((unsigned)cnt, 2), dim3(512), 0, ctx->stream, LEAF_ARGS);
+            hipLaunchKernelGGL((bm ? k_leaf_join_rb_bool<8, 8> : k_leaf_join_rb<8, 8>), dim3((unsigned)cnt, 2), dim3(512), 0, ctx->stream, LEAF_ARGS);
         else if (maxlen <= 160)  // k = 30 (leaf_size 150)
-            hipLaunchKernelGGL((k_leaf_join_rb<10, 8>), dim3((unsigned)cnt, 3), dim3(512), 0, ctx->stream, LEAF_ARGS);
+            hipLaunchKernelGGL((bm ? k_leaf_join_rb_bool<10, 8> : k_leaf_join_rb<10, 8>), dim3((unsigned)cnt, 3), dim3(512), 0, ctx->stream, LEAF_ARGS);
         else
-            hipLaunchKernelGGL((k_leaf_join_rb<16, 8>), dim3((unsigned)cnt, 4), dim3(512), 0, ctx->stream, LEAF_ARGS);
+            hipLaunchKernelGGL((bm ? k_leaf_join_rb_bool<16, 8> : k_leaf_join_rb<16, 8>), dim3((unsigned)cnt, 4), dim3(512), 0, ctx->stream, LEAF_ARGS);
 #undef LEAF_ARGS
     }
     NND_HIP_CHECK(hipGetLastError());

@@ -3,11 +3,12 @@
 // the cosine of q_quad_dist, the uint8 proxies of q_quad_proxy and the rerank's un-clamped dot.)
 //
 // Metric codes (include/pynnd_amd.h NND_METRIC_*): 0 sqeuclidean, 1 alt cosine, 2 alt dot, 3 alt inner product,
-// 4 correlation, 5 alt hellinger, 6 proxy inner product.  The prep kernel turns every row into a "prepared" row whose inner
+// 4 correlation, 5 alt hellinger, 6 proxy inner product, 8..16 the boolean family (below).  The prep kernel turns every row into a "prepared" row whose inner
 // products give the distance (DESIGN.md "Metrics"):
 //   unit metrics (1, 2, 4, 5): rows L2-normalised after a per-metric transform (none / none / minus the row mean / sqrt);
 //     nrm = 1 (non-zero row) or 0 (zero row); the trees split angularly;
-//   norm metrics (0, 3, 6): rows centred on the column mean (0) or as given (3, 6); nrm = |x|^2; euclidean trees.
+//   norm metrics (0, 3, 6): rows centred on the column mean (0) or as given (3, 6); nrm = |x|^2; euclidean trees;
+//   boolean metrics (8..16): indicator rows (x != 0 -> 1.0f, else 0.0f), norm metrics too: nrm = nnz(x); euclidean trees.
 // The metrics with a fixed linear map (seuclidean, wminkowski with p = 2, mahalanobis) have no code and no formula here: they
 // are code 0 on rows that k_linear_rows (linear.hip) transformed once, y = A (x - c), before any kernel of this header sees them.
 // Four pieces, and which kernel takes which (DESIGN.md "Metrics" has the table):
@@ -31,6 +32,18 @@
 
 NND_HD_INLINE bool nnd_metric_unit(int metric) { return metric == 1 || metric == 2 || metric == 4 || metric == 5; }
 
+// The boolean family (include/pynnd_amd.h NND_METRIC_JACCARD .. NND_METRIC_YULE): 8 jaccard (alternative_jaccard), 9 dice,
+// 10 sokalsneath, 11 matching, 12 rogerstanimoto, 13 sokalmichener, 14 kulsinski, 15 russellrao, 16 yule (7 is no code:
+// tests/test_plan_cpu.py pins its refusal).  Six of the formulas
+// need the true column count d, and the ranking kernels receive only dp.  d travels INSIDE the kernels' `metric` argument:
+// for these codes a launcher hands over nnd_kernel_metric(code, d) = code | d << 8, so no kernel's argument block grows and
+// the instances of the other codes see the value they always saw (DESIGN.md "Boolean metrics").  nnd_create refuses
+// d >= 2^23 for the family: the counts stay exact float32 integers and the packed value an int.
+#define NND_BOOL_FIRST 8
+#define NND_BOOL_LAST 16
+NND_HD_INLINE bool nnd_metric_bool(int code) { return code >= NND_BOOL_FIRST && code <= NND_BOOL_LAST; }
+NND_HD_INLINE int nnd_kernel_metric(int code, int d) { return nnd_metric_bool(code) ? code | (d << 8) : code; }
+
 // The codes a kernel instance can meet, fixed at compile time: a conversion carries the branches of its family's codes and no
 // others (in the unrolled epilogues of the Gram kernels every branch is paid per accumulator register: the six-way branch cost
 // k_local_join16<32, 1|2, false> four VGPRs, DESIGN.md "Metrics").  A new kernel takes the narrowest family its launcher
@@ -40,7 +53,9 @@ enum nnd_metric_family {
     NND_CODES_01 = 0,   // sqeuclidean / cosine
     NND_CODES_0_5 = 1,  // every code but 6 (kernels where code 6 has an instance of its own, or is refused by the host)
     NND_CODE_6 = 2,     // proxy inner product alone: no branch on the code
-    NND_CODES_ANY = 3,  // 0..6, by a branch on the code
+    NND_CODES_BOOL = 3, // the boolean family alone (8..16, `metric` packed by nnd_kernel_metric): the branch among its nine formulas
+    NND_CODES_ANY = 4,  // 0..6, by a branch on the code (no kernel is named by this value); the boolean family is never part of
+                        // a branch: every kernel that ranks has instances of its own for it (NND_CODES_BOOL)
 };
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -65,7 +80,40 @@ enum nnd_metric_family {
 // The hellinger term sqrt(x_i y_i) is the one place where the two users differ, on purpose: finalize takes it as the reference
 // does, sqrtf of the float32 product, so that the distances handed back are the reference's; exact search takes it in float64
 // (the float32 terms move a distance by 1e-7, enough to swap two near neighbours of a ranking that claims to be exact).
+//    The boolean family (8..16) counts: dot += (a != 0 && b != 0), nx += (a != 0), ny += (b != 0) on the rows as given, then
+//    nnd_bool_dist_f64 on the three counts and the column count d, which nnd_ref_dist takes as a fourth value.
 enum nnd_hellinger_terms { NND_HELLINGER_F32, NND_HELLINGER_F64 };
+
+// The boolean family's conversion in float64, the twin of the device's nnd_bool_dist below: (code, c, na, nb, d) -> distance
+// for c = n_TT, na = nnz(x), nb = nnz(y) (reference distances.py:259-552; ne = n_TF + n_FT = na + nb - 2c).
+//   jaccard        0 if the union is empty, FLT_MAX if c = 0 (+inf in the reference), else -log2(c / (c + ne))
+//   dice           0 if ne = 0, else ne / (2c + ne)              sokalsneath  the same with 0.5c
+//   matching       ne / d                                        rogerstanimoto, sokalmichener  2ne / (d + ne)
+//   kulsinski      0 if ne = 0, else (ne - c + d) / (ne + d)     russellrao   0 if c = na = nb, else (d - c) / d
+//   yule           0 if n_TF = 0 or n_FT = 0, else 2 n_TF n_FT / (c n_FF + n_TF n_FT)
+NND_HD_INLINE double nnd_bool_dist_f64(int code, double c, double na, double nb, double d) {
+    const double ne = na + nb - 2.0 * c;
+    switch (code) {
+        case 8: {
+            if (c + ne == 0.0) return 0.0;
+            if (c == 0.0) return (double)NND_FLT_MAX;
+            const double r = -log2(c / (c + ne));
+            return r > 0.0 ? r : 0.0;
+        }
+        case 9: return ne == 0.0 ? 0.0 : ne / (2.0 * c + ne);
+        case 10: return ne == 0.0 ? 0.0 : ne / (0.5 * c + ne);
+        case 11: return ne / d;
+        case 12:
+        case 13: return (2.0 * ne) / (d + ne);
+        case 14: return ne == 0.0 ? 0.0 : (ne - c + d) / (ne + d);
+        case 15: return (c == na && c == nb) ? 0.0 : (d - c) / d;
+        default: {
+            const double tf = na - c, ft = nb - c, ff = d - na - nb + c;
+            if (tf == 0.0 || ft == 0.0) return 0.0;
+            return (2.0 * tf * ft) / (c * ff + tf * ft);
+        }
+    }
+}
 
 template <int FAM, int HELL>
 NND_HD_INLINE void nnd_ref_acc(int metric, double a, double b, double &dot, double &nx, double &ny) {
@@ -77,6 +125,10 @@ NND_HD_INLINE void nnd_ref_acc(int metric, double a, double b, double &dot, doub
             ny = fma(b, b, ny);
             dot = fma(a, b, dot);
         }
+    } else if constexpr (FAM == NND_CODES_BOOL) {  // the counts n_TT, nnz(x), nnz(y)
+        dot += (a != 0.0 && b != 0.0) ? 1.0 : 0.0;
+        nx += a != 0.0 ? 1.0 : 0.0;
+        ny += b != 0.0 ? 1.0 : 0.0;
     } else if (metric == 5) {  // sum sqrt(x_i y_i), |x|_1, |y|_1
         if constexpr (HELL == NND_HELLINGER_F32) dot += (double)sqrtf((float)a * (float)b);
         else dot += sqrt(a * b);
@@ -91,7 +143,8 @@ NND_HD_INLINE void nnd_ref_acc(int metric, double a, double b, double &dot, doub
 // The distance as a double: 0, 1 and FLT_MAX come out exactly, so a cast to float32 keeps them; every value is >= 0.
 // No intrinsics: the same text runs on the host.
 template <int FAM>
-NND_HD_INLINE double nnd_ref_dist(int metric, double dt, double ax, double ay) {
+NND_HD_INLINE double nnd_ref_dist(int metric, double dt, double ax, double ay, double d = 0.0) {
+    if constexpr (FAM == NND_CODES_BOOL) return nnd_bool_dist_f64(metric & 0xff, dt, ax, ay, d);
     constexpr bool m01 = FAM == NND_CODES_01, m6 = FAM == NND_CODE_6 || FAM == NND_CODES_ANY;
     if (metric == 0) return dt;
     if (!m01 && (metric == 2 || metric == 3)) {  // alternative_dot / alternative_inner_product: FLT_MAX for <x,y> <= 0
@@ -150,10 +203,43 @@ __device__ __forceinline__ float nnd_proxy_ip_dist(float g, float na, float nb) 
     const float cosv = g * __frsqrt_rn(na) * __frsqrt_rn(nb);
     return fminf(nnd_clamp_dist(-__log2f(cosv)) + __frsqrt_rn(g), NND_FLT_MAX);
 }
+// The boolean family: the ONE conversion of every ranking site (the joins' XM = 3 instances, the leaf kernels, k_pairwise,
+// nnd_row_pair_dist, k_query, the exact scan), so that two kernels cannot disagree on a pair.  c, na, nb are Gram values of
+// indicator rows: integers below 2^24, exact in float32 whatever the summation order, so the result is a function of four
+// integers.  Every operation is one IEEE float32 operation, never fused (contraction is off in the body: yule's c n_FF +
+// n_TF n_FT is the one place where a fused multiply-add would round differently) and the division is the correctly rounded one,
+// not v_rcp_f32: tests/boolean_util.py restates the expressions in float32 numpy and the GPU tests hold the eight rational
+// formulas to them bit for bit.  jaccard's -log2 is the hardware's (v_log_f32, 1 ulp), as cosine's.
+__device__ __forceinline__ float nnd_bool_dist(int code, float c, float na, float nb, float d) {
+#pragma clang fp contract(off)
+    const float ne = na + nb - (c + c);
+    switch (code) {
+        case 8: {
+            const float u = c + ne;
+            if (u == 0.0f) return 0.0f;
+            if (c == 0.0f) return NND_FLT_MAX;
+            return nnd_clamp_dist(-__log2f(__fdiv_rn(c, u)));
+        }
+        case 9: return ne == 0.0f ? 0.0f : __fdiv_rn(ne, 2.0f * c + ne);
+        case 10: return ne == 0.0f ? 0.0f : __fdiv_rn(ne, 0.5f * c + ne);
+        case 11: return __fdiv_rn(ne, d);
+        case 12:
+        case 13: return __fdiv_rn(ne + ne, d + ne);
+        case 14: return ne == 0.0f ? 0.0f : __fdiv_rn(ne - c + d, ne + d);
+        case 15: return (c == na && c == nb) ? 0.0f : __fdiv_rn(d - c, d);
+        default: {
+            const float tf = na - c, ft = nb - c, ff = d - na - nb + c;
+            if (tf == 0.0f || ft == 0.0f) return 0.0f;
+            const float p = tf * ft;
+            return __fdiv_rn(p + p, c * ff + p);
+        }
+    }
+}
 template <int FAM>
 __device__ __forceinline__ float nnd_gram_to_dist(int metric, float g, float na, float nb) {
     constexpr bool m01 = FAM == NND_CODES_01;
     if constexpr (FAM == NND_CODE_6) return nnd_proxy_ip_dist(g, na, nb);
+    if constexpr (FAM == NND_CODES_BOOL) return nnd_bool_dist(metric & 0xff, g, na, nb, (float)(metric >> 8));
     if (metric == 0) return nnd_clamp_dist(na + nb - 2.0f * g);
     if (!m01 && metric == 3) return g > 0.0f ? fminf(1.0f / g, NND_FLT_MAX) : NND_FLT_MAX;
     if constexpr (FAM == NND_CODES_ANY)
@@ -169,7 +255,7 @@ __device__ __forceinline__ float nnd_gram_to_dist(int metric, float g, float na,
 template <int FAM>
 __device__ __forceinline__ float nnd_self_dist(int metric, float n) {
     constexpr bool only6 = FAM == NND_CODE_6;
-    if constexpr (FAM == NND_CODES_01) return 0.0f;
+    if constexpr (FAM == NND_CODES_01 || FAM == NND_CODES_BOOL) return 0.0f;  // (the boolean family: 0 for all nine)
     if (!only6 && metric == 3) return n > 0.0f ? fminf(1.0f / n, NND_FLT_MAX) : NND_FLT_MAX;
     if (only6 || (FAM == NND_CODES_ANY && metric == 6)) return n > 0.0f ? fminf(__frsqrt_rn(n), NND_FLT_MAX) : NND_FLT_MAX;
     if (metric == 2 && n == 0.0f) return NND_FLT_MAX;
@@ -180,6 +266,7 @@ __device__ __forceinline__ float nnd_self_dist(int metric, float n) {
 // 3. Alt-space distance of the prepared rows a and b, one wave per pair (all 64 lanes take part): lane-strided partial sums,
 // then nnd_wave_sum_f32; the difference form for sqeuclidean.  merge.hip (random init, proposals without a stored distance)
 // and prune.hip (the pruning passes).
+template <int FAM = NND_CODES_ANY>
 __device__ __forceinline__ float nnd_row_pair_dist(const float *__restrict__ xp, int dp, const float *__restrict__ nrm, int metric,
                                                    int64_t a, int64_t b) {
     const float *xa = xp + a * dp, *xb = xp + b * dp;
@@ -189,6 +276,7 @@ __device__ __forceinline__ float nnd_row_pair_dist(const float *__restrict__ xp,
         s += metric == 0 ? (p - q) * (p - q) : p * q;
     }
     s = nnd_wave_sum_f32(s);
+    if constexpr (FAM == NND_CODES_BOOL) return nnd_gram_to_dist<FAM>(metric, s, nrm[a], nrm[b]);  // (0 / 1 products: s is a count)
     if (metric == 0) return nnd_clamp_dist(s);
     return nnd_gram_to_dist<NND_CODES_ANY>(metric, s, nrm[a], nrm[b]);
 }

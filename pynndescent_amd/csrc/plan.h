@@ -13,7 +13,8 @@ constexpr int NND_PLAN_MAX_K = 256;  // = NND_WIDE_K (common.h; handle.hip asser
 
 static inline int nnd_check_params(const nnd_params *p, char *err, size_t errlen) {
     if (p->n < 1 || p->dim < 1) { snprintf(err, errlen, "nnd_create: need n >= 1 and dim >= 1 (got n=%lld dim=%d)", (long long)p->n, p->dim); return 1; }
-    if (p->metric < NND_METRIC_SQEUCLIDEAN || p->metric > NND_METRIC_PROXY_INNER_PRODUCT) { snprintf(err, errlen, "nnd_create: unknown metric %d", p->metric); return 1; }
+    if (p->metric < NND_METRIC_SQEUCLIDEAN || p->metric > NND_METRIC_YULE || p->metric == NND_METRIC_PROXY_INNER_PRODUCT + 1 /* 7 is no code */) { snprintf(err, errlen, "nnd_create: unknown metric %d", p->metric); return 1; }
+    if (p->metric >= NND_METRIC_JACCARD && p->dim >= (1 << 23)) { snprintf(err, errlen, "nnd_create: the boolean metrics need dim < 2^23 (got %d)", p->dim); return 1; }
     if (p->n_neighbors < 1 || p->n_neighbors > NND_PLAN_MAX_K) { snprintf(err, errlen, "nnd_create: n_neighbors must be in 1..%d (got %d)", NND_PLAN_MAX_K, p->n_neighbors); return 1; }
     if (p->max_candidates < 1 || p->max_candidates > 128) { snprintf(err, errlen, "nnd_create: max_candidates must be in 1..128 (got %d)", p->max_candidates); return 1; }
     if (p->n_trees < 0 || p->n_trees > 4096 || p->leaf_size < 1) { snprintf(err, errlen, "nnd_create: bad n_trees (0..4096) / leaf_size"); return 1; }

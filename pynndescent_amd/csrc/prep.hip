@@ -111,6 +111,7 @@ __global__ __launch_bounds__(256) void k_prep_rows(const float *__restrict__ x, 
             const float raw = j < d ? src[j] : 0.0f;
             bad |= !isfinite(raw);
             float v = j < d ? (metric == 0 ? raw - mean[j] : raw) : 0.0f;
+            if (metric >= NND_BOOL_FIRST) v = v != 0.0f ? 1.0f : 0.0f;  // the boolean family: indicator rows, nrm = nnz(x)
             dst[j] = v;
             if (xh) {
                 const uint16_t b = nnd_f32_to_h16(v, hsc);
@@ -207,6 +208,9 @@ __global__ __launch_bounds__(256) void k_prep_rows_v4(const float *__restrict__ 
                 const float4 m = ((const float4 *)mean)[c];
                 v.x -= m.x; v.y -= m.y; v.z -= m.z; v.w -= m.w;
             }
+        } else if (metric >= NND_BOOL_FIRST) {  // the boolean family: indicator rows (the padding stays zero), nrm = nnz(x)
+            v.x = v.x != 0.0f ? 1.0f : 0.0f; v.y = v.y != 0.0f ? 1.0f : 0.0f;
+            v.z = v.z != 0.0f ? 1.0f : 0.0f; v.w = v.w != 0.0f ? 1.0f : 0.0f;
         } else if (unit) {
             if (c < ncd) {  // (the padding stays zero: a centred zero is not)
                 v.x = nnd_unit_transform(metric, v.x, mu); v.y = nnd_unit_transform(metric, v.y, mu);

@@ -38,8 +38,9 @@ __device__ __forceinline__ bool prune_coin(uint32_t seed, uint32_t row, uint32_t
 // (-1, +inf); kept entries stay in order.  AWARE: an entry u whose undirected degree exceeds max_degree is pruned
 // against d(i,u) * threshold_factor * alpha (pynndescent_.py:506-531); there is no coin in that variant (the
 // reference call site hands diversify_prob to `alpha`, pynndescent_.py:1486-1497 -- the host passes it the same way).
-template <bool AWARE>
-__global__ __launch_bounds__(256) void k_diversify_rows(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
+// (the body of k_diversify_rows and of k_diversify_rows_bool, the instance of the boolean family: metric.h nnd_metric_family)
+template <int FAM, bool AWARE>
+__device__ __forceinline__ void pr_diversify_rows_body(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
                                                         int metric, int64_t n, int k, int32_t *__restrict__ idx,
                                                         float *__restrict__ dist, float prob, uint32_t seed,
                                                         const int32_t *__restrict__ degree, int max_degree,
@@ -71,7 +72,7 @@ __global__ __launch_bounds__(256) void k_diversify_rows(const float *__restrict_
             const float dc = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_d), c));
             if (dc > PRUNE_EPS) {
                 const int32_t idc = __builtin_amdgcn_readlane(my_idx, c);
-                const float d = idc == i ? dj : nnd_row_pair_dist(xp, dp, nrm, metric, idj, idc);  // (the own vertex: see above)
+                const float d = idc == i ? dj : nnd_row_pair_dist<FAM>(xp, dp, nrm, metric, idj, idc);  // (the own vertex: see above)
                 if (d < lim && (AWARE || prune_coin(seed, (uint32_t)i, (uint32_t)j, (uint32_t)c, prob))) {  // pynndescent_.py:386-389
                     flag = false;
                     break;
@@ -92,6 +93,22 @@ __global__ __launch_bounds__(256) void k_diversify_rows(const float *__restrict_
         dist[i * k + lane] = lane < nk ? out_d : INFINITY;
     }
 }
+template <bool AWARE>
+__global__ __launch_bounds__(256) void k_diversify_rows(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
+                                                        int metric, int64_t n, int k, int32_t *__restrict__ idx,
+                                                        float *__restrict__ dist, float prob, uint32_t seed,
+                                                        const int32_t *__restrict__ degree, int max_degree,
+                                                        float base_rate, float alpha) {
+    pr_diversify_rows_body<NND_CODES_ANY, AWARE>(xp, dp, nrm, metric, n, k, idx, dist, prob, seed, degree, max_degree, base_rate, alpha);
+}
+template <bool AWARE>
+__global__ __launch_bounds__(256) void k_diversify_rows_bool(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
+                                                        int metric, int64_t n, int k, int32_t *__restrict__ idx,
+                                                        float *__restrict__ dist, float prob, uint32_t seed,
+                                                        const int32_t *__restrict__ degree, int max_degree,
+                                                        float base_rate, float alpha) {
+    pr_diversify_rows_body<NND_CODES_BOOL, AWARE>(xp, dp, nrm, metric, n, k, idx, dist, prob, seed, degree, max_degree, base_rate, alpha);
+}
 
 // pynndescent_.py:549-588 (AWARE = false) / 625-726 (AWARE = true) on CSR rows of length <= 64 (rows of a diversified
 // k-NN graph have <= k entries).  Entries are walked in ascending weight order (ties by position).
@@ -100,8 +117,9 @@ __global__ __launch_bounds__(256) void k_diversify_rows(const float *__restrict_
 // AWARE = true (pynndescent_.py:682-719): the walk starts at the first entry, skips weight-0 entries, compares with
 // the point at order[k], has no FLOAT32_EPS guard, and prunes when d * threshold_factor(degree of entry j) < w_j.
 // Pruned entries get weight 0.
-template <bool AWARE>
-__global__ __launch_bounds__(256) void k_diversify_csr(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
+// (the body of k_diversify_csr and of k_diversify_csr_bool, the instance of the boolean family: metric.h nnd_metric_family)
+template <int FAM, bool AWARE>
+__device__ __forceinline__ void pr_diversify_csr_body(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
                                                        int metric, int64_t n_rows, const int32_t *__restrict__ indptr,
                                                        const int32_t *__restrict__ indices, float *__restrict__ data,
                                                        int *__restrict__ too_long, float prob, uint32_t seed,
@@ -146,7 +164,7 @@ __global__ __launch_bounds__(256) void k_diversify_csr(const float *__restrict__
                     const int32_t idk = __builtin_amdgcn_readlane(my_idx, AWARE ? l : kk);
                     // the row's own vertex: the stored d(i, j) = wj (see above).  AWARE has no EPS guard, so a weight-EPS
                     // entry (the own vertex at distance 0) is a comparison point too and takes the same rule.
-                    const float d = (idk == i || (AWARE && wl <= PRUNE_EPS)) ? wj : nnd_row_pair_dist(xp, dp, nrm, metric, idj, idk);
+                    const float d = (idk == i || (AWARE && wl <= PRUNE_EPS)) ? wj : nnd_row_pair_dist<FAM>(xp, dp, nrm, metric, idj, idk);
                     if ((AWARE ? d * fj : d) < wj && prune_coin(seed, (uint32_t)i, (uint32_t)j, (uint32_t)kk, prob)) {
                         retained &= ~(1ull << j);
                         break;
@@ -156,6 +174,24 @@ __global__ __launch_bounds__(256) void k_diversify_csr(const float *__restrict__
         }
     }
     if (lane < len && !((retained >> lane) & 1ull)) data[a + lane] = 0.0f;
+}
+template <bool AWARE>
+__global__ __launch_bounds__(256) void k_diversify_csr(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
+                                                       int metric, int64_t n_rows, const int32_t *__restrict__ indptr,
+                                                       const int32_t *__restrict__ indices, float *__restrict__ data,
+                                                       int *__restrict__ too_long, float prob, uint32_t seed,
+                                                       const int32_t *__restrict__ degree, int max_degree,
+                                                       float aggressiveness) {
+    pr_diversify_csr_body<NND_CODES_ANY, AWARE>(xp, dp, nrm, metric, n_rows, indptr, indices, data, too_long, prob, seed, degree, max_degree, aggressiveness);
+}
+template <bool AWARE>
+__global__ __launch_bounds__(256) void k_diversify_csr_bool(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
+                                                       int metric, int64_t n_rows, const int32_t *__restrict__ indptr,
+                                                       const int32_t *__restrict__ indices, float *__restrict__ data,
+                                                       int *__restrict__ too_long, float prob, uint32_t seed,
+                                                       const int32_t *__restrict__ degree, int max_degree,
+                                                       float aggressiveness) {
+    pr_diversify_csr_body<NND_CODES_BOOL, AWARE>(xp, dp, nrm, metric, n_rows, indptr, indices, data, too_long, prob, seed, degree, max_degree, aggressiveness);
 }
 
 
@@ -171,8 +207,9 @@ struct prune_wide_row {
     uint8_t kept[PRUNE_WIDE];
 };
 
-template <bool AWARE>
-__global__ __launch_bounds__(256) void k_diversify_rows_wide(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
+// (the body of k_diversify_rows_wide and of k_diversify_rows_wide_bool, the instance of the boolean family: metric.h nnd_metric_family)
+template <int FAM, bool AWARE>
+__device__ __forceinline__ void pr_diversify_rows_wide_body(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
                                                              int metric, int64_t n, int k, int32_t *__restrict__ idx,
                                                              float *__restrict__ dist, float prob, uint32_t seed,
                                                              const int32_t *__restrict__ degree, int max_degree,
@@ -204,7 +241,7 @@ __global__ __launch_bounds__(256) void k_diversify_rows_wide(const float *__rest
         for (int c = 0; c < j; c++) {
             if (!r.kept[c]) continue;
             if (r.w[c] > PRUNE_EPS) {
-                const float d = r.idx[c] == i ? dj : nnd_row_pair_dist(xp, dp, nrm, metric, idj, r.idx[c]);
+                const float d = r.idx[c] == i ? dj : nnd_row_pair_dist<FAM>(xp, dp, nrm, metric, idj, r.idx[c]);
                 if (d < lim && (AWARE || prune_coin(seed, (uint32_t)i, (uint32_t)j, (uint32_t)c, prob))) {  // pynndescent_.py:386-389
                     flag = false;
                     break;
@@ -229,9 +266,26 @@ __global__ __launch_bounds__(256) void k_diversify_rows_wide(const float *__rest
         dist[i * k + j] = INFINITY;
     }
 }
-
 template <bool AWARE>
-__global__ __launch_bounds__(256) void k_diversify_csr_wide(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
+__global__ __launch_bounds__(256) void k_diversify_rows_wide(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
+                                                             int metric, int64_t n, int k, int32_t *__restrict__ idx,
+                                                             float *__restrict__ dist, float prob, uint32_t seed,
+                                                             const int32_t *__restrict__ degree, int max_degree,
+                                                             float base_rate, float alpha) {
+    pr_diversify_rows_wide_body<NND_CODES_ANY, AWARE>(xp, dp, nrm, metric, n, k, idx, dist, prob, seed, degree, max_degree, base_rate, alpha);
+}
+template <bool AWARE>
+__global__ __launch_bounds__(256) void k_diversify_rows_wide_bool(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
+                                                             int metric, int64_t n, int k, int32_t *__restrict__ idx,
+                                                             float *__restrict__ dist, float prob, uint32_t seed,
+                                                             const int32_t *__restrict__ degree, int max_degree,
+                                                             float base_rate, float alpha) {
+    pr_diversify_rows_wide_body<NND_CODES_BOOL, AWARE>(xp, dp, nrm, metric, n, k, idx, dist, prob, seed, degree, max_degree, base_rate, alpha);
+}
+
+// (the body of k_diversify_csr_wide and of k_diversify_csr_wide_bool, the instance of the boolean family: metric.h nnd_metric_family)
+template <int FAM, bool AWARE>
+__device__ __forceinline__ void pr_diversify_csr_wide_body(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
                                                             int metric, int64_t n_rows, const int32_t *__restrict__ indptr,
                                                             const int32_t *__restrict__ indices, float *__restrict__ data,
                                                             int *__restrict__ too_long, float prob, uint32_t seed,
@@ -282,7 +336,7 @@ __global__ __launch_bounds__(256) void k_diversify_csr_wide(const float *__restr
             const float wl = r.w[l];
             if (AWARE || wl > PRUNE_EPS) {
                 const int32_t idk = r.idx[AWARE ? l : kk];  // AWARE: the point at order[kk]; standard: storage position kk (reference quirk)
-                const float d = (idk == i || (AWARE && wl <= PRUNE_EPS)) ? wj : nnd_row_pair_dist(xp, dp, nrm, metric, idj, idk);
+                const float d = (idk == i || (AWARE && wl <= PRUNE_EPS)) ? wj : nnd_row_pair_dist<FAM>(xp, dp, nrm, metric, idj, idk);
                 if ((AWARE ? d * fj : d) < wj && prune_coin(seed, (uint32_t)i, (uint32_t)j, (uint32_t)kk, prob)) {
                     if (lane == 0) r.kept[j] = 0;
                     break;
@@ -293,6 +347,24 @@ __global__ __launch_bounds__(256) void k_diversify_csr_wide(const float *__restr
     }
     for (int j = lane; j < len; j += 64)
         if (!r.kept[j]) data[a + j] = 0.0f;
+}
+template <bool AWARE>
+__global__ __launch_bounds__(256) void k_diversify_csr_wide(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
+                                                            int metric, int64_t n_rows, const int32_t *__restrict__ indptr,
+                                                            const int32_t *__restrict__ indices, float *__restrict__ data,
+                                                            int *__restrict__ too_long, float prob, uint32_t seed,
+                                                            const int32_t *__restrict__ degree, int max_degree,
+                                                            float aggressiveness) {
+    pr_diversify_csr_wide_body<NND_CODES_ANY, AWARE>(xp, dp, nrm, metric, n_rows, indptr, indices, data, too_long, prob, seed, degree, max_degree, aggressiveness);
+}
+template <bool AWARE>
+__global__ __launch_bounds__(256) void k_diversify_csr_wide_bool(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
+                                                            int metric, int64_t n_rows, const int32_t *__restrict__ indptr,
+                                                            const int32_t *__restrict__ indices, float *__restrict__ data,
+                                                            int *__restrict__ too_long, float prob, uint32_t seed,
+                                                            const int32_t *__restrict__ degree, int max_degree,
+                                                            float aggressiveness) {
+    pr_diversify_csr_wide_body<NND_CODES_BOOL, AWARE>(xp, dp, nrm, metric, n_rows, indptr, indices, data, too_long, prob, seed, degree, max_degree, aggressiveness);
 }
 
 // pynndescent_.py:728-738: rows longer than max_degree keep the entries <= sorted(row)[max_degree]
@@ -326,25 +398,26 @@ __global__ __launch_bounds__(256) void k_degree_prune(int64_t n_rows, const int3
 }
 
 int nnd_launch_diversify_rows(nnd_ctx *ctx, int32_t *idx_dev, float *dist_dev, const nnd_prune_opts *o, const int32_t *degree_dev) {
+    const bool bm = nnd_metric_bool(ctx->p.metric);  // the boolean family's instances (metric.h NND_CODES_BOOL)
     const dim3 grid((unsigned)((ctx->n + 3) / 4));
     if (ctx->k > PRUNE_WIDE) { ctx->set_error("the pruning pass handles rows of at most %d neighbours", PRUNE_WIDE); return 1; }
     if (ctx->k > 64) {  // rows that do not fit one entry per lane: the LDS variants
         const float base_rate = 0.04f * fmaxf(0.0f, o->aggressiveness);
         if (o->degree_aware)
-            hipLaunchKernelGGL(k_diversify_rows_wide<true>, grid, dim3(256), 0, ctx->stream, ctx->xp, ctx->dp, ctx->nrm, ctx->p.metric, ctx->n, ctx->k,
+            hipLaunchKernelGGL(bm ? k_diversify_rows_wide_bool<true> : k_diversify_rows_wide<true>, grid, dim3(256), 0, ctx->stream, ctx->xp, ctx->dp, ctx->nrm, nnd_kmetric(ctx), ctx->n, ctx->k,
                                idx_dev, dist_dev, 1.0f, o->seed, degree_dev, o->max_degree, base_rate, o->alpha);
         else
-            hipLaunchKernelGGL(k_diversify_rows_wide<false>, grid, dim3(256), 0, ctx->stream, ctx->xp, ctx->dp, ctx->nrm, ctx->p.metric, ctx->n, ctx->k,
+            hipLaunchKernelGGL(bm ? k_diversify_rows_wide_bool<false> : k_diversify_rows_wide<false>, grid, dim3(256), 0, ctx->stream, ctx->xp, ctx->dp, ctx->nrm, nnd_kmetric(ctx), ctx->n, ctx->k,
                                idx_dev, dist_dev, o->prune_probability, o->seed, (const int32_t *)nullptr, 1, 0.0f, 1.0f);
         NND_HIP_CHECK(hipGetLastError());
         return 0;
     }
     if (o->degree_aware) {
         const float base_rate = 0.04f * fmaxf(0.0f, o->aggressiveness);  // pynndescent_.py:487-488
-        hipLaunchKernelGGL(k_diversify_rows<true>, grid, dim3(256), 0, ctx->stream, ctx->xp, ctx->dp, ctx->nrm, ctx->p.metric,
+        hipLaunchKernelGGL(bm ? k_diversify_rows_bool<true> : k_diversify_rows<true>, grid, dim3(256), 0, ctx->stream, ctx->xp, ctx->dp, ctx->nrm, nnd_kmetric(ctx),
                            ctx->n, ctx->k, idx_dev, dist_dev, 1.0f, o->seed, degree_dev, o->max_degree, base_rate, o->alpha);
     } else {
-        hipLaunchKernelGGL(k_diversify_rows<false>, grid, dim3(256), 0, ctx->stream, ctx->xp, ctx->dp, ctx->nrm, ctx->p.metric,
+        hipLaunchKernelGGL(bm ? k_diversify_rows_bool<false> : k_diversify_rows<false>, grid, dim3(256), 0, ctx->stream, ctx->xp, ctx->dp, ctx->nrm, nnd_kmetric(ctx),
                            ctx->n, ctx->k, idx_dev, dist_dev, o->prune_probability, o->seed, (const int32_t *)nullptr, 1, 0.0f, 1.0f);
     }
     NND_HIP_CHECK(hipGetLastError());
@@ -352,23 +425,24 @@ int nnd_launch_diversify_rows(nnd_ctx *ctx, int32_t *idx_dev, float *dist_dev, c
 }
 int nnd_launch_diversify_csr(nnd_ctx *ctx, const int32_t *indptr_dev, const int32_t *indices_dev, float *data_dev,
                              int *too_long_dev, const nnd_prune_opts *o, const int32_t *degree_dev) {
+    const bool bm = nnd_metric_bool(ctx->p.metric);  // the boolean family's instances (metric.h NND_CODES_BOOL)
     const dim3 grid((unsigned)((ctx->n + 3) / 4));
     if (ctx->k > 64) {  // rows of up to PRUNE_WIDE entries: the LDS variants
         if (o->degree_aware)
-            hipLaunchKernelGGL(k_diversify_csr_wide<true>, grid, dim3(256), 0, ctx->stream, ctx->xp, ctx->dp, ctx->nrm, ctx->p.metric, ctx->n, indptr_dev,
+            hipLaunchKernelGGL(bm ? k_diversify_csr_wide_bool<true> : k_diversify_csr_wide<true>, grid, dim3(256), 0, ctx->stream, ctx->xp, ctx->dp, ctx->nrm, nnd_kmetric(ctx), ctx->n, indptr_dev,
                                indices_dev, data_dev, too_long_dev, o->prune_probability, o->seed ^ 0x51ED270Bu, degree_dev, o->max_degree, o->aggressiveness);
         else
-            hipLaunchKernelGGL(k_diversify_csr_wide<false>, grid, dim3(256), 0, ctx->stream, ctx->xp, ctx->dp, ctx->nrm, ctx->p.metric, ctx->n, indptr_dev,
+            hipLaunchKernelGGL(bm ? k_diversify_csr_wide_bool<false> : k_diversify_csr_wide<false>, grid, dim3(256), 0, ctx->stream, ctx->xp, ctx->dp, ctx->nrm, nnd_kmetric(ctx), ctx->n, indptr_dev,
                                indices_dev, data_dev, too_long_dev, o->prune_probability, o->seed ^ 0x51ED270Bu, (const int32_t *)nullptr, 1, 0.0f);
         NND_HIP_CHECK(hipGetLastError());
         return 0;
     }
     if (o->degree_aware)
-        hipLaunchKernelGGL(k_diversify_csr<true>, grid, dim3(256), 0, ctx->stream, ctx->xp, ctx->dp, ctx->nrm, ctx->p.metric,
+        hipLaunchKernelGGL(bm ? k_diversify_csr_bool<true> : k_diversify_csr<true>, grid, dim3(256), 0, ctx->stream, ctx->xp, ctx->dp, ctx->nrm, nnd_kmetric(ctx),
                            ctx->n, indptr_dev, indices_dev, data_dev, too_long_dev, o->prune_probability, o->seed ^ 0x51ED270Bu,
                            degree_dev, o->max_degree, o->aggressiveness);
     else
-        hipLaunchKernelGGL(k_diversify_csr<false>, grid, dim3(256), 0, ctx->stream, ctx->xp, ctx->dp, ctx->nrm, ctx->p.metric,
+        hipLaunchKernelGGL(bm ? k_diversify_csr_bool<false> : k_diversify_csr<false>, grid, dim3(256), 0, ctx->stream, ctx->xp, ctx->dp, ctx->nrm, nnd_kmetric(ctx),
                            ctx->n, indptr_dev, indices_dev, data_dev, too_long_dev, o->prune_probability, o->seed ^ 0x51ED270Bu,
                            (const int32_t *)nullptr, 1, 0.0f);
     NND_HIP_CHECK(hipGetLastError());

@@ -182,8 +182,11 @@ __device__ __forceinline__ float q_rerank_dist(const float *__restrict__ x, cons
 // RR: the rerank epilogue (k = search_k, the k_out best by the true distance leave).  Three forms: the float walk without it,
 // the uint8 walk with it, and the float walk with it (Q8 = false, RR = true: metric code 6 and nothing else -- the walk on the
 // float rows by the proxy inner product, the rerank by -<q,x>; the query stays as given, a zero query is searched).
-template <bool BIG, int KU, bool Q8 = false, bool RR = Q8>
-__global__ __launch_bounds__(256) void k_query(const float *__restrict__ x, const float *__restrict__ xn2, int dp, int d, int metric,
+// BM: the boolean family (codes 8..16, the instances of k_query_bool): the tree is descended with the query as given, then the
+// query becomes its indicator row and the walk's distances are metric.h nnd_bool_dist on exact counts.
+// The body is shared by the kernels k_query (BM = false) and k_query_bool below.
+template <bool BIG, int KU, bool Q8, bool RR, bool BM>
+__device__ __forceinline__ void q_body(const float *__restrict__ x, const float *__restrict__ xn2, int dp, int d, int metric,
                                                int64_t n, const int32_t *__restrict__ indptr, const int32_t *__restrict__ indices,
                                                const float *__restrict__ hyper, const float *__restrict__ offsets,
                                                const int32_t *__restrict__ children, const int32_t *__restrict__ tree_idx,
@@ -359,6 +362,7 @@ __global__ __launch_bounds__(256) void k_query(const float *__restrict__ x, cons
             float dv;
             if constexpr (Q8) dv = q_quad_proxy(codes, cn2, dcs, d, metric, (const float *)qsm, qs, qn2, v, sub);
             else if constexpr (RR) dv = nnd_gram_to_dist<NND_CODE_6>(metric, q_quad_dot(x, dp, qs, v, sub), qn2, xn2[v]);
+            else if constexpr (BM) dv = nnd_gram_to_dist<NND_CODES_BOOL>(nnd_kernel_metric(metric, d), q_quad_dot(x, dp, qs, v, sub), qn2, xn2[v]);
             else dv = q_quad_dist(x, xn2, dp, metric, qs, qn2, v, sub);
             if (sub == 0 && c < nc) cd[c] = dv;
         }
@@ -390,6 +394,16 @@ __global__ __launch_bounds__(256) void k_query(const float *__restrict__ x, cons
             }
             ls = -children[2 * node];
             le = -children[2 * node + 1];
+        }
+        if constexpr (BM) {  // the tree splits the rows as given, the distances take the indicator rows: qn2 = nnz(q)
+            float p2 = 0.0f;
+            for (int j = lane; j < d; j += 64) {
+                const float v = qs[j] != 0.0f ? 1.0f : 0.0f;
+                qs[j] = v;
+                p2 += v;
+            }
+            qn2 = nnd_wave_sum_f32(p2);
+            nnd_wave_lds_sync();
         }
         if (metric == 4 || metric == 5) {  // correlation / hellinger: the tree splits the raw rows (angular), the distances the prepared ones
             const double mu = metric == 4 ? nnd_row_mean_f64<64>(qs, d, lane) : 0.0;
@@ -547,6 +561,37 @@ __global__ __launch_bounds__(256) void k_query(const float *__restrict__ x, cons
             out_dist[qi * k + 64 * u + lane] = rd[u];
         }
 }
+template <bool BIG, int KU, bool Q8 = false, bool RR = Q8>
+__global__ __launch_bounds__(256) void k_query(const float *__restrict__ x, const float *__restrict__ xn2, int dp, int d, int metric,
+                                               int64_t n, const int32_t *__restrict__ indptr, const int32_t *__restrict__ indices,
+                                               const float *__restrict__ hyper, const float *__restrict__ offsets,
+                                               const int32_t *__restrict__ children, const int32_t *__restrict__ tree_idx,
+                                               int64_t n_nodes, const float *__restrict__ queries, int64_t nq, int k, float epsilon,
+                                               float min_distance, int n_neighbors, uint32_t seed, int32_t *__restrict__ out_idx,
+                                               float *__restrict__ out_dist, uint8_t *__restrict__ overflow /* (nq) LDS tier: set when the query needs the big tier */,
+                                               const int32_t *__restrict__ qlist /* BIG: the queries of this batch */,
+                                               int n_list, unsigned char *__restrict__ scratch, size_t scratch_stride,
+                                               const uint8_t *__restrict__ codes, int dcs, const float *__restrict__ lut,
+                                               const float *__restrict__ cn2, int k_out) {
+    q_body<BIG, KU, Q8, RR, false>(x, xn2, dp, d, metric, n, indptr, indices, hyper, offsets, children, tree_idx, n_nodes, queries, nq, k, epsilon, min_distance,
+                               n_neighbors, seed, out_idx, out_dist, overflow, qlist, n_list, scratch, scratch_stride, codes, dcs, lut, cn2, k_out);
+}
+template <bool BIG, int KU>
+__global__ __launch_bounds__(256) void k_query_bool(const float *__restrict__ x, const float *__restrict__ xn2, int dp, int d, int metric,
+                                               int64_t n, const int32_t *__restrict__ indptr, const int32_t *__restrict__ indices,
+                                               const float *__restrict__ hyper, const float *__restrict__ offsets,
+                                               const int32_t *__restrict__ children, const int32_t *__restrict__ tree_idx,
+                                               int64_t n_nodes, const float *__restrict__ queries, int64_t nq, int k, float epsilon,
+                                               float min_distance, int n_neighbors, uint32_t seed, int32_t *__restrict__ out_idx,
+                                               float *__restrict__ out_dist, uint8_t *__restrict__ overflow /* (nq) LDS tier: set when the query needs the big tier */,
+                                               const int32_t *__restrict__ qlist /* BIG: the queries of this batch */,
+                                               int n_list, unsigned char *__restrict__ scratch, size_t scratch_stride,
+                                               const uint8_t *__restrict__ codes, int dcs, const float *__restrict__ lut,
+                                               const float *__restrict__ cn2, int k_out) {
+    q_body<BIG, KU, false, false, true>(x, xn2, dp, d, metric, n, indptr, indices, hyper, offsets, children, tree_idx, n_nodes, queries, nq, k, epsilon, min_distance,
+                               n_neighbors, seed, out_idx, out_dist, overflow, qlist, n_list, scratch, scratch_stride, codes, dcs, lut, cn2, k_out);
+}
+
 
 // the searcher's copy of the rows for the codes 2..5: the build's row transform (metric.h), one wave per row, in place --
 // dot: L2-normalised; correlation: minus the row mean (float64), then normalised; hellinger: sqrt, then normalised
@@ -565,6 +610,17 @@ __global__ void k_searcher_prep_rows(float *__restrict__ x, int64_t n, int d, in
     s = nnd_wave_sum_f32(s);
     const float inv = s > 0.0f ? 1.0f / sqrtf(s) : 0.0f;
     for (int j = lane; j < d; j += 64) row[j] *= inv;
+}
+
+// the boolean family: the searcher's rows become indicator rows in place (x != 0 -> 1, else 0; the padding stays 0), so that
+// k_row_norm2 gives nnz(x) and every product of the walk is a count
+__global__ void k_searcher_indicator_rows(float *__restrict__ x, int64_t n, int dp) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n * dp) x[i] = x[i] != 0.0f ? 1.0f : 0.0f;
+}
+static void searcher_indicator_rows(nnd_searcher_s *s, hipStream_t st) {
+    const int64_t total = s->n * s->dp;
+    hipLaunchKernelGGL(k_searcher_indicator_rows, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, s->x, s->n, s->dp);
 }
 
 // squared norms of the padded rows (alternative_cosine recomputes them per call, distances.py:617-620)
@@ -668,6 +724,7 @@ static int searcher_fill(nnd_searcher_s *s, const float *data, const int32_t *in
     S_ALLOC(&s->xn2, (size_t)s->n);
     if (s->metric == NND_METRIC_ALT_DOT || s->metric == NND_METRIC_CORRELATION || s->metric == NND_METRIC_ALT_HELLINGER)
         hipLaunchKernelGGL(k_searcher_prep_rows, dim3((unsigned)((s->n + 3) / 4)), dim3(256), 0, s->stream, s->x, s->n, s->d, s->dp, s->metric);
+    if (nnd_metric_bool(s->metric)) searcher_indicator_rows(s, s->stream);
     hipLaunchKernelGGL(k_row_norm2, dim3((unsigned)((s->n + 3) / 4)), dim3(256), 0, s->stream, s->x, s->n, s->dp, s->xn2);
     S_ALLOC(&s->indptr, (size_t)(s->n + 1));
     S_HIP(hipMemcpy(s->indptr, indptr, sizeof(int32_t) * (size_t)(s->n + 1), hipMemcpyHostToDevice));
@@ -703,6 +760,7 @@ static int searcher_fill_device(nnd_searcher_s *s, const void *rows, int dtype, 
     }
     if (s->metric == NND_METRIC_ALT_DOT || s->metric == NND_METRIC_CORRELATION || s->metric == NND_METRIC_ALT_HELLINGER)
         hipLaunchKernelGGL(k_searcher_prep_rows, dim3((unsigned)((s->n + 3) / 4)), dim3(256), 0, st, s->x, s->n, s->d, s->dp, s->metric);
+    if (nnd_metric_bool(s->metric)) searcher_indicator_rows(s, st);
     hipLaunchKernelGGL(k_row_norm2, dim3((unsigned)((s->n + 3) / 4)), dim3(256), 0, st, s->x, s->n, s->dp, s->xn2);
     S_HIP(hipGetLastError());
     S_HIP(hipMemcpyAsync(s->indptr, indptr, sizeof(int32_t) * (size_t)(s->n + 1), hipMemcpyDeviceToDevice, st));
@@ -728,7 +786,8 @@ static nnd_searcher_s *searcher_new(const char *who, bool args_ok, int32_t devic
         return nullptr;
     };
     if (!args_ok || n < 1 || dim < 1 || nnz < 0) return fail("bad arguments");
-    if (metric < NND_METRIC_SQEUCLIDEAN || metric > NND_METRIC_PROXY_INNER_PRODUCT) return fail("unknown metric");
+    if (metric < NND_METRIC_SQEUCLIDEAN || metric > NND_METRIC_YULE || metric == NND_METRIC_PROXY_INNER_PRODUCT + 1) return fail("unknown metric");
+    if (nnd_metric_bool(metric) && dim >= (1 << 23)) return fail("the boolean metrics need dim < 2^23");
     if (n_nodes > 0 && !tree_ok) return fail("tree arrays missing");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail("no HIP device visible (this library has no CPU path)");
@@ -792,12 +851,13 @@ extern "C" int32_t nnd_searcher_set_tier(nnd_searcher_t s, int32_t tier) {
 }
 
 // the three forms of k_query (its Q8 / RR switches)
-enum q_form { Q_FORM_FLOAT, Q_FORM_U8, Q_FORM_RERANK };
+enum q_form { Q_FORM_FLOAT, Q_FORM_U8, Q_FORM_RERANK, Q_FORM_BOOL /* the float form of the boolean family: k_query_bool */ };
 template <bool BIG>
 static auto query_kernel(q_form form, int k) -> decltype(&k_query<BIG, 1>) {
     // (k > 64, round 5: the result list as two or four entries per lane; the reference takes any k, pynndescent_.py:2275-2379)
     switch (form) {
         case Q_FORM_U8: return k > 128 ? k_query<BIG, 4, true> : (k > 64 ? k_query<BIG, 2, true> : k_query<BIG, 1, true>);
+        case Q_FORM_BOOL: return k > 128 ? k_query_bool<BIG, 4> : (k > 64 ? k_query_bool<BIG, 2> : k_query_bool<BIG, 1>);
         case Q_FORM_RERANK: return k > 128 ? k_query<BIG, 4, false, true> : (k > 64 ? k_query<BIG, 2, false, true> : k_query<BIG, 1, false, true>);
         default: return k > 128 ? k_query<BIG, 4> : (k > 64 ? k_query<BIG, 2> : k_query<BIG, 1>);
     }
@@ -808,6 +868,7 @@ static auto query_kernel(q_form form, int k) -> decltype(&k_query<BIG, 1>) {
 static int searcher_run(nnd_searcher_s *s, const float *queries, int64_t nq, int32_t k, int32_t k_out, float epsilon, q_form form,
                         int32_t *out_idx, float *out_dist, bool on_device = false, hipStream_t user_stream = nullptr) {
     const bool q8 = form == Q_FORM_U8;
+    if (form == Q_FORM_FLOAT && nnd_metric_bool(s->metric)) form = Q_FORM_BOOL;
     auto kq_lds = query_kernel<false>(form, k);
     auto kq_big = query_kernel<true>(form, k);
     if (nq <= 0) return 0;

@@ -284,6 +284,9 @@ int nnd_d2h_parallel(nnd_ctx *ctx, void *dst, const void *src, size_t bytes, int
 int nnd_launch_prep(nnd_ctx *ctx);
 // the pieces of nnd_launch_prep (prep.hip), for the sharded build: a rank preps its own rows first, the others once they arrive
 bool nnd_prep_column_pass(int metric);
+// the `metric` argument of a ranking kernel: the code, and for the boolean family the true column count in the bits above it
+// (metric.h nnd_kernel_metric: six of its formulas need d, the kernels receive dp, and no argument block grows)
+static inline int nnd_kmetric(const nnd_ctx *ctx) { return ctx->p.metric >= NND_METRIC_JACCARD ? ctx->p.metric | (ctx->d << 8) : ctx->p.metric; }
 void nnd_prep_mean_geometry(int64_t n, int64_t *n_s, int64_t *stride);
 int nnd_prep_partial_blocks(int64_t members);
 double *nnd_prep_partial_buffer(nnd_ctx *ctx, size_t doubles);

@@ -81,6 +81,9 @@ class _Metric(NamedTuple):
     # carries a fixed linear map from metric_kwds (linear_map.py): the device works on y = A (x - c), a transformed float32 copy
     # of the rows, with the kernels of ``code`` unchanged; _raw_data stays the caller's rows
     linear: bool = False
+    # a function of the counts of indicator rows (x != 0): the device turns the rows into indicators itself (csrc/prep.hip), so
+    # the host hands over the caller's rows as they are; one GPU, no uint8 proxy
+    boolean: bool = False
 
 
 # corrections: numpy.sqrt, large float32 arrays through the library's threaded sqrtf (the same bits, the fresh pages touched in
@@ -106,6 +109,14 @@ _METRICS = {
 # these names take metric_kwds, the nine above ignore it
 _LINEAR_METRICS = {name: _Metric(_capi.METRIC_CODES["euclidean"], _capi.host_sqrt, device_kind=_capi.NND_CORRECT_SQRT, linear=True)
                    for name in linear_map.LINEAR_METRICS}
+# the boolean family (distances.py:259-552): functions of the Gram counts of indicator rows (DESIGN.md "Boolean metrics").  A
+# table of its own, like the linear one: tests enumerate ``_METRICS``.  jaccard is built on alternative_jaccard and corrected by
+# 1 - 2^-v (correct_alternative_jaccard, the same function as cosine's correction); the other eight are handed out as they are.
+# ``angular`` is what the reference reports (pynndescent_.py:1075-1086); the device splits indicator rows with euclidean trees.
+_BOOLEAN_METRICS = {name: _Metric(code, correct_alternative_cosine if name == "jaccard" else _capi.host_copy,
+                                  angular=name in ("jaccard", "dice"), boolean=True,
+                                  device_kind=_capi.NND_CORRECT_ALT_COSINE if name == "jaccard" else _capi.NND_CORRECT_COPY)
+                    for name, code in _capi.BOOLEAN_METRIC_CODES.items()}
 # views of the table by one field
 _DISTANCE_CORRECTIONS = {name: m.correction for name, m in _METRICS.items()}
 _ANGULAR_METRICS = frozenset(name for name, m in _METRICS.items() if m.angular)
@@ -113,7 +124,9 @@ _ANGULAR_METRICS = frozenset(name for name, m in _METRICS.items() if m.angular)
 
 def _metric_of(name):
     """The record of a metric an index already has (its name was accepted by ``_metric_record``)."""
-    return _METRICS[name] if name in _METRICS else _LINEAR_METRICS[name]
+    if name in _METRICS:
+        return _METRICS[name]
+    return _LINEAR_METRICS[name] if name in _LINEAR_METRICS else _BOOLEAN_METRICS[name]
 
 
 def _metric_record(metric, reference_fallback=True):
@@ -124,11 +137,14 @@ def _metric_record(metric, reference_fallback=True):
         return _METRICS[metric]
     if not callable(metric) and metric in _LINEAR_METRICS:
         return _LINEAR_METRICS[metric]
+    if not callable(metric) and metric in _BOOLEAN_METRICS:
+        return _BOOLEAN_METRICS[metric]
     if reference_fallback and (callable(metric) or metric in _KNOWN_REFERENCE_METRICS):
         raise NotImplementedError(
             "pynndescent_amd accelerates the dense euclidean / l2 / sqeuclidean / cosine / dot / inner_product / "
             "correlation / hellinger / proxy_inner_product / seuclidean / standardised_euclidean / mahalanobis build and the "
-            "p = 2 form of minkowski / wminkowski / weighted_minkowski only; "
+            "p = 2 form of minkowski / wminkowski / weighted_minkowski, and the boolean metrics jaccard / dice / sokalsneath / "
+            "matching / rogerstanimoto / sokalmichener / kulsinski / russellrao / yule only; "
             "use pynndescent.NNDescent for metric %r" % (metric,)
         )
     raise ValueError("Metric is neither callable, " + "nor a recognised string")
@@ -386,14 +402,14 @@ def _linear_map_of(metric, m, metric_kwds, dim):
 
 
 def _refuse_with_linear(metric, m, quantization, n_devices):
-    """What the metrics with a linear map do not combine with, reported before any device work."""
-    if not m.linear:
+    """What the metrics with a linear map, and the boolean metrics, do not combine with, reported before any device work."""
+    if not (m.linear or m.boolean):
         return
     if quantization == "uint8":
         _check_quantization(quantization, metric)  # the reference's ValueError("Not uint8 quantization version of ...")
     if int(n_devices) > 1:
         raise NotImplementedError("pynndescent_amd builds metric %r on one GPU (n_devices = %d): the row-sharded build has no "
-                                  "linear map; use n_devices=1" % (metric, int(n_devices)))
+                                  "%s; use n_devices=1" % (metric, int(n_devices), "linear map" if m.linear else "boolean metrics"))
 
 
 def _device_corrected(torch, dist, m, ordinal):
@@ -1423,6 +1439,10 @@ _ND_ALIASES = {"squared_euclidean": "sqeuclidean", "alternative_cosine": "cosine
 # nn_descent returns the finished arrays themselves)
 _ND_DISTS = {name: (m.code, None if m.correction is _capi.host_copy else m.correction) for name, m in _METRICS.items()}
 _ND_DISTS.update((alt, (_METRICS[name].code, None)) for alt, name in _ND_ALIASES.items())
+# the boolean family: the nine names (jaccard: corrected on return), and "alternative_jaccard" for its kernel distance
+_ND_ALIASES["alternative_jaccard"] = "jaccard"
+_ND_DISTS.update((name, (m.code, None if m.correction is _capi.host_copy else m.correction)) for name, m in _BOOLEAN_METRICS.items())
+_ND_DISTS["alternative_jaccard"] = (_BOOLEAN_METRICS["jaccard"].code, None)
 
 
 def nn_descent(data, n_neighbors, rng_state, max_candidates=50, dist="squared_euclidean", n_iters=10, delta=0.001,
@@ -1433,7 +1453,9 @@ def nn_descent(data, n_neighbors, rng_state, max_candidates=50, dist="squared_eu
     data float32 (n, d); rng_state int64[3]; ``dist``: "squared_euclidean" / "alternative_cosine" / "alternative_dot" /
     "alternative_inner_product" / "correlation" / "alternative_hellinger" (what NNDescent passes, pynndescent_.py:1247-1260),
     "euclidean" / "cosine" / "dot" / "inner_product" / "hellinger" (true distances: the same kernels, corrected on return),
-    "proxy_inner_product" (the proxy distances themselves: it has no correction),
+    "proxy_inner_product" (the proxy distances themselves: it has no correction), the boolean metrics "jaccard" (corrected
+    on return; "alternative_jaccard": its kernel distance) / "dice" / "sokalsneath" / "matching" / "rogerstanimoto" /
+    "sokalmichener" / "kulsinski" / "russellrao" / "yule",
     or the reference function of one of those names (dot: the kernels rank by the L2-normalised rows, as NNDescent's
     normalised data gives; hand in normalised rows for the reference's ranking); ``init_graph``: EMPTY_GRAPH, or the heap triple ``(indices (n, k),
     distances (n, k), flags (n, k))`` the reference accepts (entries with index -1 are empty); ``leaf_array`` int32
@@ -1442,7 +1464,7 @@ def nn_descent(data, n_neighbors, rng_state, max_candidates=50, dist="squared_eu
     name = dist if isinstance(dist, str) else getattr(dist, "__name__", None)
     if name not in _ND_DISTS:
         raise NotImplementedError("pynndescent_amd.nn_descent: dist must be one of %s (got %r)" % (sorted(_ND_DISTS), dist))
-    m, correction = _METRICS[_ND_ALIASES.get(name, name)], _ND_DISTS[name][1]
+    m, correction = _metric_of(_ND_ALIASES.get(name, name)), _ND_DISTS[name][1]
     data = np.ascontiguousarray(data, dtype=np.float32)
     n = data.shape[0]
     _check_supported_sizes(n_neighbors, max_candidates, None)
@@ -1740,7 +1762,8 @@ def _check_supported_sizes(n_neighbors, max_candidates, init_graph):
 
 def make_index(data, *args, **kwargs):
     """``NNDescent(data, ...)`` on the GPU when the input is in scope (dense data, euclidean / l2 / sqeuclidean / cosine / dot /
-    inner_product / correlation / hellinger / proxy_inner_product / seuclidean / mahalanobis / minkowski and wminkowski with p = 2,
+    inner_product / correlation / hellinger / proxy_inner_product / seuclidean / mahalanobis / minkowski and wminkowski with p = 2 /
+    the boolean metrics jaccard, dice, sokalsneath, matching, rogerstanimoto, sokalmichener, kulsinski, russellrao and yule,
     k <= 256);
     otherwise -- and only then -- the reference ``pynndescent.NNDescent`` on the CPU when that package is importable
     (SURVEY.md section 8b), with a warning.  A missing HIP library or GPU is never papered over: that still raises."""

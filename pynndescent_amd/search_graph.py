@@ -86,7 +86,7 @@ def build_search_graph(data, indices, distances, metric="euclidean", n_neighbors
         x = np.ascontiguousarray(data, dtype=np.float32)
         n, d = x.shape
         k = np.shape(indices)[1]
-        code = _capi.METRIC_CODES[metric]
+        code = _capi.metric_code(metric)
         # The device pass keeps 2 n k keyed edges with int32 positions and ~104 bytes of workspace per edge; a graph beyond that
         # (or a device too full for the workspace) goes through the kernels with the reference's scipy calls between them --
         # the rounds 2-4 form, same edges (tests/test_gpu_build.py), n k < 2^31 -- instead of failing prepare().
@@ -130,7 +130,7 @@ def _build_search_graph_host_glue(data, indices, distances, metric="euclidean", 
     n, d = x.shape
     k = indices.shape[1]
     n_neighbors = k if n_neighbors is None else n_neighbors
-    code = _capi.METRIC_CODES[metric]
+    code = _capi.metric_code(metric)
     b = _capi.Builder(n, d, code, k, 0, 60, 200, min(60, k), 1, 0.001, [1, 2, 3], [4, 5, 6], device=device,
                       flags=_capi.NND_FLAG_NO_GRAPH)  # the pass reads rows and norms only: no k-lists / proposal tables
     try:
