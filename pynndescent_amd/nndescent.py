@@ -18,24 +18,36 @@ and minkowski ``()`` or ``(2,)`` (linear_map.py; the device transforms every row
 Out of scope: sparse input, every other metric, ``n_neighbors`` above 256 or
 ``max_candidates`` above 128 (``query``: more than 256 results per query).  Those raise ``NotImplementedError`` naming the reference entry point to use
 instead; ``pynndescent_amd.make_index`` hands such inputs to ``pynndescent.NNDescent`` when it is importable.
+
+This file holds the class and the helpers that read an index's ``__dict__``; the metric table is metrics.py, the tensor plumbing
+device_arrays.py, the single-GPU build driver and ``nn_descent`` build.py, ``exact_knn`` exact.py.
 """
 import inspect
-import time
-from typing import Callable, NamedTuple
 from warnings import warn
 
 import numpy as np
 from sklearn.utils import check_array, check_random_state
 
-from . import _capi, linear_map
+from . import _capi, build, device_arrays, linear_map
+# Every name below was defined here once and is read here still (tests, tools/, and pickles, which name
+# pynndescent_amd.nndescent.correct_alternative_*): the same objects as in their home modules.  Two are replaced by tests and
+# are therefore CALLED through their home module alone -- ``build.ts()``, ``device_arrays._torch()``.
+from .build import (EMPTY_GRAPH, _build_graph, _check_array_no_scan, _check_supported_sizes, _descend,  # noqa: F401
+                    _raise_if_nonfinite, _reference_defaults, nn_descent, ts)
+from .device_arrays import (_DEVICE_DTYPES, _check_device_array, _device_corrected, _DeviceInput, _DeviceLinear,  # noqa: F401
+                            _DeviceRowsView, _dtype_name, _ids_to_host, _is_device_array, _OnTorchStream, _resolve_updated_indices,
+                            _rows_to_host, _shape_of, _stream_ms, _torch, _update_dtype)
+from .exact import _exact_knn_device, _exact_linear_rows, exact_knn  # noqa: F401
+from .metrics import (_ANGULAR_METRICS, _BOOLEAN_METRICS, _DISTANCE_CORRECTIONS, _KNOWN_REFERENCE_METRICS,  # noqa: F401
+                      _LINEAR_METRICS, _METRIC_TABLE, _METRICS, _ND_ALIASES, _ND_DISTS, _NEGATIVE_HELLINGER, _check_quantization,
+                      _linear_map_of, _Metric, _metric_of, _metric_record, _no_exact_for_proxy, _raise_if_negative_host,
+                      _refuse_uint8_and_sharding, correct_alternative_cosine, correct_alternative_hellinger,
+                      correct_alternative_inner_product)
+
+_refuse_with_linear = _refuse_uint8_and_sharding  # (its name before it said what it refuses)
 
 INT32_MIN = np.iinfo(np.int32).min + 1  # pynndescent_.py:62
 INT32_MAX = np.iinfo(np.int32).max - 1  # pynndescent_.py:63
-
-
-def ts():
-    """Timestamp used in verbose output (reference utils.py:881-883)."""
-    return time.ctime(time.time())
 
 
 def tau_rand_int(state):
@@ -49,121 +61,6 @@ def tau_rand_int(state):
     return r - (1 << 32) if r >= (1 << 31) else r
 
 
-def correct_alternative_cosine(d):
-    """1 - 2^-d (reference distances.py:704-711); float64 like the reference's ufunc."""
-    return 1.0 - np.power(2.0, -np.asarray(d, dtype=np.float64))
-
-
-def correct_alternative_inner_product(d):
-    """-1/d, and 0 for FLT_MAX (reference distances.py:842-853); float64 like the reference's ufunc."""
-    d = np.asarray(d, dtype=np.float64)
-    with np.errstate(divide="ignore"):
-        return np.where(d >= np.finfo(np.float32).max, 0.0, -1.0 / d)
-
-
-def correct_alternative_hellinger(d):
-    """sqrt(1 - 2^-d) (reference distances.py:1420-1426); float64 like the reference's ufunc."""
-    return np.sqrt(1.0 - np.power(2.0, -np.asarray(d, dtype=np.float64)))
-
-
-class _Metric(NamedTuple):
-    """What the host needs to know about one metric of the device path."""
-    code: int  # the kernels' metric (include/pynnd_amd.h NND_METRIC_*)
-    correction: Callable  # kernel distance -> the metric's own, always a new array (pynndescent_.py:1271-1298)
-    angular: bool = False  # angular trees in the reference (pynndescent_.py:1075-1086)
-    uint8: bool = False  # has a uint8 proxy distance (distances.py:2250-2255 quantized_distances["uint8"])
-    normalize: bool = False  # rows L2-normalised before anything else (pynndescent_.py:1101-1102)
-    nonnegative: bool = False  # hellinger takes sqrt(x): a negative entry is an error here, NaN distances in the reference
-    # a proxy with a true distance (distances.py:2190 proxy_distances): the graph is built and walked on the kernel distance, which
-    # neighbor_graph hands out as it is; query() keeps proxy_beam_size * k candidates and the device reranks them by the true one
-    proxy: bool = False
-    device_kind: int = _capi.NND_CORRECT_COPY  # the same correction on a device tensor (include/pynnd_amd.h NND_CORRECT_*)
-    # carries a fixed linear map from metric_kwds (linear_map.py): the device works on y = A (x - c), a transformed float32 copy
-    # of the rows, with the kernels of ``code`` unchanged; _raw_data stays the caller's rows
-    linear: bool = False
-    # a function of the counts of indicator rows (x != 0): the device turns the rows into indicators itself (csrc/prep.hip), so
-    # the host hands over the caller's rows as they are; one GPU, no uint8 proxy
-    boolean: bool = False
-
-
-# corrections: numpy.sqrt, large float32 arrays through the library's threaded sqrtf (the same bits, the fresh pages touched in
-# parallel); "sqeuclidean" and "correlation" are the kernels' own space, with no correction (pynndescent_.py:1271-1298) --
-# neighbor_graph still hands out a copy
-_METRICS = {
-    "euclidean": _Metric(_capi.METRIC_CODES["euclidean"], _capi.host_sqrt, uint8=True, device_kind=_capi.NND_CORRECT_SQRT),
-    "l2": _Metric(_capi.METRIC_CODES["l2"], _capi.host_sqrt, uint8=True, device_kind=_capi.NND_CORRECT_SQRT),
-    "sqeuclidean": _Metric(_capi.METRIC_CODES["sqeuclidean"], _capi.host_copy),
-    "cosine": _Metric(_capi.METRIC_CODES["cosine"], correct_alternative_cosine, angular=True, uint8=True,
-                      device_kind=_capi.NND_CORRECT_ALT_COSINE),
-    "dot": _Metric(_capi.METRIC_CODES["dot"], correct_alternative_cosine, angular=True, uint8=True, normalize=True,
-                   device_kind=_capi.NND_CORRECT_ALT_COSINE),
-    "inner_product": _Metric(_capi.METRIC_CODES["inner_product"], correct_alternative_inner_product,
-                             device_kind=_capi.NND_CORRECT_ALT_INNER_PRODUCT),
-    "correlation": _Metric(_capi.METRIC_CODES["correlation"], _capi.host_copy, angular=True),
-    "hellinger": _Metric(_capi.METRIC_CODES["hellinger"], correct_alternative_hellinger, angular=True, nonnegative=True,
-                         device_kind=_capi.NND_CORRECT_ALT_HELLINGER),
-    "proxy_inner_product": _Metric(_capi.METRIC_CODES["proxy_inner_product"], _capi.host_copy, proxy=True),
-}
-# euclidean distance after a fixed linear map of the rows (seuclidean, wminkowski with p = 2, mahalanobis; minkowski with p = 2
-# has no map and is the euclidean path itself): code 0 and euclidean's correction on the transformed rows.  A table of its own:
-# these names take metric_kwds, the nine above ignore it
-_LINEAR_METRICS = {name: _Metric(_capi.METRIC_CODES["euclidean"], _capi.host_sqrt, device_kind=_capi.NND_CORRECT_SQRT, linear=True)
-                   for name in linear_map.LINEAR_METRICS}
-# the boolean family (distances.py:259-552): functions of the Gram counts of indicator rows (DESIGN.md "Boolean metrics").  A
-# table of its own, like the linear one: tests enumerate ``_METRICS``.  jaccard is built on alternative_jaccard and corrected by
-# 1 - 2^-v (correct_alternative_jaccard, the same function as cosine's correction); the other eight are handed out as they are.
-# ``angular`` is what the reference reports (pynndescent_.py:1075-1086); the device splits indicator rows with euclidean trees.
-_BOOLEAN_METRICS = {name: _Metric(code, correct_alternative_cosine if name == "jaccard" else _capi.host_copy,
-                                  angular=name in ("jaccard", "dice"), boolean=True,
-                                  device_kind=_capi.NND_CORRECT_ALT_COSINE if name == "jaccard" else _capi.NND_CORRECT_COPY)
-                    for name, code in _capi.BOOLEAN_METRIC_CODES.items()}
-# views of the table by one field
-_DISTANCE_CORRECTIONS = {name: m.correction for name, m in _METRICS.items()}
-_ANGULAR_METRICS = frozenset(name for name, m in _METRICS.items() if m.angular)
-
-
-def _metric_of(name):
-    """The record of a metric an index already has (its name was accepted by ``_metric_record``)."""
-    if name in _METRICS:
-        return _METRICS[name]
-    return _LINEAR_METRICS[name] if name in _LINEAR_METRICS else _BOOLEAN_METRICS[name]
-
-
-def _metric_record(metric, reference_fallback=True):
-    """The row of ``_METRICS``.  A metric off the device path raises the reference's ValueError (pynndescent_.py:1292), or
-    with ``reference_fallback`` NotImplementedError when the reference runs it (a callable, a name it knows): what
-    ``make_index`` hands to ``pynndescent.NNDescent``."""
-    if not callable(metric) and metric in _METRICS:
-        return _METRICS[metric]
-    if not callable(metric) and metric in _LINEAR_METRICS:
-        return _LINEAR_METRICS[metric]
-    if not callable(metric) and metric in _BOOLEAN_METRICS:
-        return _BOOLEAN_METRICS[metric]
-    if reference_fallback and (callable(metric) or metric in _KNOWN_REFERENCE_METRICS):
-        raise NotImplementedError(
-            "pynndescent_amd accelerates the dense euclidean / l2 / sqeuclidean / cosine / dot / inner_product / "
-            "correlation / hellinger / proxy_inner_product / seuclidean / standardised_euclidean / mahalanobis build and the "
-            "p = 2 form of minkowski / wminkowski / weighted_minkowski, and the boolean metrics jaccard / dice / sokalsneath / "
-            "matching / rogerstanimoto / sokalmichener / kulsinski / russellrao / yule only; "
-            "use pynndescent.NNDescent for metric %r" % (metric,)
-        )
-    raise ValueError("Metric is neither callable, " + "nor a recognised string")
-
-
-def _reference_defaults(n, n_neighbors, n_trees=None, n_iters=None, leaf_size=None, max_candidates=None):
-    """The reference's derived defaults for what is None: (n_trees, n_iters, leaf_size, max_candidates) for ``n`` rows
-    (pynndescent_.py:1009-1012, 1135-1138; rp_trees.py:2845-2846)."""
-    if n_trees is None:
-        n_trees = max(3, min(12, int(round(2.0 * np.log10(n)))))
-    if n_iters is None:
-        n_iters = max(5, int(round(np.log2(n))))
-    if leaf_size is None:
-        leaf_size = max(60, min(256, 5 * int(n_neighbors)))
-    if max_candidates is None:
-        max_candidates = min(60, n_neighbors)
-    return n_trees, n_iters, leaf_size, max_candidates
-
-
 def _proxy_search_k(k, proxy_beam_size):
     """``search_k`` of a query that is reranked (pynndescent_.py:2309-2312), within what the query kernel keeps."""
     search_k = proxy_beam_size * k
@@ -173,27 +70,6 @@ def _proxy_search_k(k, proxy_beam_size):
         raise NotImplementedError("pynndescent_amd keeps proxy_beam_size * k <= 256 candidates per quantized query "
                                   "(got %d); use index.to_reference()" % search_k)
     return search_k
-
-
-def _no_exact_for_proxy(metric, m, what):
-    """The exact search certifies its answers with a float64 bound per formula; it has none for a proxy distance."""
-    if m.proxy:
-        raise NotImplementedError("pynndescent_amd.%s does not cover metric %r (a proxy distance: the float64 certificate of the "
-                                  "exact search has no bound for it)" % (what, metric))
-
-
-def _check_quantization(quantization, metric):
-    """The quantization checks of the reference's ``prepare()`` (pynndescent_.py:2175-2263), host only."""
-    if quantization is None:
-        return
-    if quantization == "uint8":
-        if not _metric_record(metric, reference_fallback=False).uint8:
-            raise ValueError(f"Not uint8 quantization version of {metric}")
-        return
-    if quantization in ("uint4", "binary"):
-        raise NotImplementedError("quantized search with quantization=%r is out of scope for pynndescent_amd (\"uint8\" is "
-                                  "supported); use index.to_reference()" % (quantization,))
-    raise ValueError(f"Unrecognized quantization type {quantization}")
 
 
 def uint8_codebook(raw, random_state):
@@ -208,61 +84,6 @@ def uint8_codebook(raw, random_state):
     return np.quantile(sample, np.linspace(0, 1, 256)).astype(np.float32)
 
 
-# ---- device arrays: input that lives on the GPU (in practice a torch.Tensor on a HIP device; torch is imported on this path only)
-_DEVICE_DTYPES = {"float32": _capi.NND_DTYPE_FLOAT32, "float16": _capi.NND_DTYPE_FLOAT16, "bfloat16": _capi.NND_DTYPE_BFLOAT16,
-                  "float64": _capi.NND_DTYPE_FLOAT64}
-
-
-def _is_device_array(a):
-    """A device array: ``is_cuda`` is true and there is a ``data_ptr()`` (with ``dtype``, ``shape``, ``device``, ``is_contiguous()``)."""
-    return getattr(a, "is_cuda", False) is True and callable(getattr(a, "data_ptr", None))
-
-
-def _check_device_array(a, device=0, what="data"):
-    """check_array for a device array: 2-D, float32 / float16 / bfloat16 / float64, on the GPU ``device`` names when that is not
-    0 (the default means "where the array is").  Returns ``(the array, contiguous -- a device copy when it was not --, its
-    NND_DTYPE_* code, its device ordinal)``; no device work besides that copy, no torch."""
-    name = str(a.dtype).rsplit(".", 1)[-1]
-    if name not in _DEVICE_DTYPES:
-        raise TypeError("pynndescent_amd takes device arrays of dtype float32, float16, bfloat16 or float64 (%s has dtype %s)"
-                        % (what, a.dtype))
-    if len(a.shape) != 2:
-        raise ValueError("Expected 2D array, got %dD array instead: %s has shape %s" % (len(a.shape), what, tuple(a.shape)))
-    ordinal = getattr(a.device, "index", None)
-    ordinal = 0 if ordinal is None else int(ordinal)
-    if device and int(device) != ordinal:
-        raise ValueError("device=%d, but %s is on device %d: the index runs where its data is" % (int(device), what, ordinal))
-    if not a.is_contiguous():
-        a = a.contiguous()
-    return a, _DEVICE_DTYPES[name], ordinal
-
-
-def _torch():
-    import torch  # (lazily: a host-only install never needs it)
-
-    return torch
-
-
-def _dtype_name(a):
-    """``float32`` of ``torch.float32``: the key of ``_DEVICE_DTYPES`` and the attribute of torch."""
-    return str(a.dtype).rsplit(".", 1)[-1]
-
-
-def _shape_of(a):
-    """The shape of a host array-like or a device array, without bringing either anywhere."""
-    return tuple(a.shape) if hasattr(a, "shape") else np.shape(a)
-
-
-def _rows_to_host(a):
-    """A device array as the float32 host rows ``check_array`` would make of its values (a host array: as it is)."""
-    return np.ascontiguousarray(a.detach().float().cpu().numpy()) if _is_device_array(a) else a
-
-
-def _ids_to_host(a):
-    """Row ids given as a device array, on the host (they are few); everything else as it is."""
-    return a.detach().cpu().numpy() if _is_device_array(a) else a
-
-
 def _updates_on_device(index, xs_fresh, xs_updated):
     """Whether ``update()`` of ``index`` stays on the device (``NNDescent._update_device``): the index holds its rows and its graph
     on one GPU, and at least one of the incoming arrays is a device array.  Reads ``__dict__`` only."""
@@ -270,167 +91,6 @@ def _updates_on_device(index, xs_fresh, xs_updated):
     if "_device_data" not in d or "_device_graph" not in d or int(d.get("n_devices", 1)) != 1:
         return False
     return _is_device_array(xs_fresh) or _is_device_array(xs_updated)
-
-
-def _resolve_updated_indices(updated_indices, n_old):
-    """``updated_indices`` as the host loop ``raw[i] = x`` reads them (pynndescent_.py:2467-2469), resolved to distinct pairs:
-    ``(row ids, source rows)``, int32, ids ascending -- a negative id wraps, of several entries that name one row the last one
-    wins, an id outside ``[-n_old, n_old)`` raises numpy's ``IndexError``.  No two pairs write one row."""
-    ids = np.asarray(updated_indices, dtype=np.int64).reshape(-1)
-    outside = (ids < -n_old) | (ids >= n_old)
-    if outside.any():
-        raise IndexError("index %d is out of bounds for axis 0 with size %d" % (int(ids[outside][0]), n_old))
-    ids = np.where(ids < 0, ids + n_old, ids)
-    unique, first_from_the_end = np.unique(ids[::-1], return_index=True)
-    return unique.astype(np.int32), (ids.shape[0] - 1 - first_from_the_end).astype(np.int32)
-
-
-def _update_dtype(names):
-    """The dtype rule of the device ``update()``: ``names`` -- the dtype names of the index's tensor and of every incoming array
-    (a host array counts as float32, what ``check_array`` makes of it) -- share one dtype: it is kept; otherwise float32."""
-    names = list(names)
-    return names[0] if all(name == names[0] for name in names) else "float32"
-
-
-class _OnTorchStream:
-    """The HIP stream a library call runs on so that it is ordered with torch's work on ``ordinal``: torch's current stream.  The
-    default stream has no handle a builder could adopt (NULL means the builder's own, which does not wait for it), so there
-    the call runs on a side stream that waits for the default stream first and that the default stream waits for afterwards
-    -- on the device; the host waits for nothing."""
-
-    def __init__(self, torch, ordinal):
-        self.current = torch.cuda.current_stream(ordinal)
-        self.side = None
-        if not self.current.cuda_stream:
-            self.side = torch.cuda.Stream(device=ordinal)
-            self.side.wait_stream(self.current)
-        self.ptr = (self.side or self.current).cuda_stream
-
-    def done(self):
-        if self.side is not None:
-            self.current.wait_stream(self.side)
-
-
-def _stream_ms(torch, stream, fn):
-    """``fn()`` between two events on the stream of an ``_OnTorchStream``: (its result, the stream time in ms).  For calls that
-    return with the stream drained (the entries of csrc/prepare.hip, the searcher's fill): reading the time waits for nothing."""
-    on = stream.side or stream.current
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record(on)
-    out = fn()
-    e1.record(on)
-    e1.synchronize()
-    return out, float(e0.elapsed_time(e1))
-
-
-class _DeviceInput:
-    """The device side of one single-GPU build (``_build_graph``): the caller's tensor in, the finished graph out as tensors."""
-
-    def __init__(self, tensor, dtype, ordinal, k, as_given=False, linear=None):
-        self.torch = _torch()
-        self.tensor, self.dtype, self.ordinal, self.k = tensor, dtype, ordinal, int(k)
-        # what the device works on: the caller's own tensor, dot's normalised float32 rows, or the rows a linear map transformed
-        self.rows = tensor
-        self.as_given = as_given  # update(): dot's rows enter as they are (float32, pynndescent_.py:2461-2476 normalises nothing)
-        self.linear = linear  # a _DeviceLinear: the metric's map on this device (None: the metric has none)
-
-    def host_rows(self):
-        """The caller's rows on the host, float32: for sklearn's wording of the NaN / inf error, the one place that needs them."""
-        return np.ascontiguousarray(self.tensor.detach().float().cpu().numpy())
-
-    def set_data(self, builder, m):
-        torch, t = self.torch, self.tensor
-        self.stream = _OnTorchStream(torch, self.ordinal)
-        builder.set_stream(self.stream.ptr)
-        if self.linear is not None:  # the builder borrows the transformed copy, and the index keeps it next to the caller's rows
-            self.rows = self.linear.rows(t, self.dtype, self.stream.ptr)
-            builder.set_data_device(self.rows.data_ptr(), keepalive=self.rows)
-        elif m.normalize and self.as_given:  # (the typed entry would normalise every dot input)
-            builder.set_data_device(t.data_ptr(), keepalive=t)
-        elif m.normalize:  # pynndescent_.py:1101-1102: the index holds the normalised rows; the builder borrows them
-            self.rows = torch.empty(tuple(t.shape), dtype=torch.float32, device=t.device)
-            _capi.device_rows_f32(self.ordinal, self.stream.ptr, t.data_ptr(), self.dtype, t.shape[0], t.shape[1], True,
-                                  self.rows.data_ptr())
-            builder.set_data_device(self.rows.data_ptr(), keepalive=self.rows)
-        else:
-            builder.set_data_device_typed(t.data_ptr(), self.dtype, keepalive=t)
-
-    def finalize(self, builder):
-        torch, n = self.torch, self.tensor.shape[0]
-        idx = torch.empty((n, self.k), dtype=torch.int32, device=self.tensor.device)
-        dist = torch.empty((n, self.k), dtype=torch.float32, device=self.tensor.device)
-        builder.finalize_device(idx.data_ptr(), dist.data_ptr())
-        return idx, dist
-
-    def close(self):
-        if getattr(self, "stream", None) is not None:
-            self.stream.done()
-            self.stream = None
-
-
-class _DeviceLinear:
-    """A metric's linear map (``linear_map.LinearMap``) on one device: ``a`` and ``shift`` as float32 tensors there (uploaded
-    here, on torch's current stream: make it before the ``_OnTorchStream`` of the call that uses it)."""
-
-    def __init__(self, lin, device, ordinal):
-        torch = _torch()
-        self.kind, self.ordinal = int(lin.kind), int(ordinal)
-        self.a = torch.from_numpy(np.ascontiguousarray(lin.a, dtype=np.float32)).to(device)
-        self.shift = torch.from_numpy(np.ascontiguousarray(lin.shift, dtype=np.float32)).to(device)
-
-    def rows(self, t, dtype, stream_ptr):
-        """``A (x - shift)`` of the contiguous (n, d) tensor ``t`` (``dtype``: its NND_DTYPE_*): a new float32 tensor, queued on
-        ``stream_ptr``.  The existing conversion to float32 runs first (csrc/devarray.hip), then csrc/linear.hip."""
-        torch = _torch()
-        n, dim = int(t.shape[0]), int(t.shape[1])
-        out = torch.empty((n, dim), dtype=torch.float32, device=t.device)
-        if n == 0:
-            return out
-        if dtype != _capi.NND_DTYPE_FLOAT32:
-            x32 = torch.empty((n, dim), dtype=torch.float32, device=t.device)
-            _capi.device_rows_f32(self.ordinal, stream_ptr, t.data_ptr(), dtype, n, dim, False, x32.data_ptr())
-            t = x32
-        _capi.device_linear_rows(self.ordinal, stream_ptr, self.kind, dim, self.a.data_ptr(), self.shift.data_ptr(), t.data_ptr(), n,
-                                 out.data_ptr())
-        return out
-
-
-def _linear_map_of(metric, m, metric_kwds, dim):
-    """The ``LinearMap`` (without its shift) of a metric that carries one; None for every other metric -- ``metric_kwds`` stays
-    unread for those -- and for minkowski with p = 2.  Raises what ``linear_map.parse_metric_kwds`` raises."""
-    return linear_map.parse_metric_kwds(metric, metric_kwds, dim) if m.linear else None
-
-
-def _refuse_with_linear(metric, m, quantization, n_devices):
-    """What the metrics with a linear map, and the boolean metrics, do not combine with, reported before any device work."""
-    if not (m.linear or m.boolean):
-        return
-    if quantization == "uint8":
-        _check_quantization(quantization, metric)  # the reference's ValueError("Not uint8 quantization version of ...")
-    if int(n_devices) > 1:
-        raise NotImplementedError("pynndescent_amd builds metric %r on one GPU (n_devices = %d): the row-sharded build has no "
-                                  "%s; use n_devices=1" % (metric, int(n_devices), "linear map" if m.linear else "boolean metrics"))
-
-
-def _device_corrected(torch, dist, m, ordinal):
-    """``m.correction`` of the float32 tensor ``dist``, on the device by the library (a new tensor; float64 where the host's is)."""
-    kind = m.device_kind
-    out = torch.empty_like(dist, dtype=torch.float32 if kind in (_capi.NND_CORRECT_COPY, _capi.NND_CORRECT_SQRT) else torch.float64)
-    _capi.device_correct(ordinal, torch.cuda.current_stream(ordinal).cuda_stream, kind, dist.data_ptr(), out.data_ptr(), dist.numel())
-    return out
-
-
-class _DeviceRowsView:
-    """The rows of a device tensor for ``uint8_codebook``: its shape, and ``view[rows]`` -- the sample, gathered on the device with
-    torch indexing and brought to the host as float32 (at most 10 000 rows cross the bus, in the order asked for)."""
-
-    def __init__(self, tensor):
-        self.tensor, self.shape = tensor, tuple(tensor.shape)
-
-    def __getitem__(self, rows):
-        torch = _torch()
-        at = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int64)).to(self.tensor.device)
-        return np.ascontiguousarray(self.tensor.detach()[at].float().cpu().numpy())
 
 
 def _prepares_on_device(index):
@@ -533,7 +193,7 @@ class NNDescent:
         # init_graph / init_dist tensors seed a device build where they are (cast on torch's stream here, before the builder's
         # stream is taken from it); every other combination meets on the host
         if dev_checked is not None and int(n_devices) == 1 and _is_device_array(init_graph) and (init_dist is None or _is_device_array(init_dist)):
-            torch = _torch()
+            torch = device_arrays._torch()
             init_graph = init_graph.detach().to(device=data.device, dtype=torch.int32).contiguous()
             if init_dist is not None:
                 init_dist = init_dist.detach().to(device=data.device, dtype=torch.float32).contiguous()
@@ -576,7 +236,7 @@ class NNDescent:
 
         m = _metric_record(metric)
         lin = _linear_map_of(metric, m, metric_kwds, data.shape[1])  # (host only: every error of metric_kwds comes first)
-        _refuse_with_linear(metric, m, quantization, self.n_devices)
+        _refuse_uint8_and_sharding(metric, m, quantization, self.n_devices)
         try:
             import scipy.sparse
 
@@ -619,7 +279,7 @@ class NNDescent:
         n = data.shape[0]
         if self.tree_init:
             if verbose:
-                print(ts(), "Building RP forest with", str(n_trees), "trees")
+                print(build.ts(), "Building RP forest with", str(n_trees), "trees")
             tree_states = current_random_state.randint(INT32_MIN, INT32_MAX, size=(n_trees, 3)).astype(np.int64)
             eff_trees = n_trees
         else:
@@ -702,7 +362,7 @@ class NNDescent:
         assert_all_finite(data)  # check_array's scan (pynndescent_.py:1054): the one-call multi-GPU build has no flag to read
         _raise_if_negative_host(data, _metric_of(self.metric))
         if verbose:
-            print(ts(), "NN descent for", str(self.n_iters), "iterations on", self.n_devices, "GPUs")
+            print(build.ts(), "NN descent for", str(self.n_iters), "iterations on", self.n_devices, "GPUs")
         idx, dst, st, info = sharded.build_multi(
             data, self.n_devices, self.devices, self.metric, self.n_neighbors, n_trees, leaf_size, max_candidates,
             self.n_iters, self.delta, max_rptree_depth=self.max_rptree_depth, rng_state=self.rng_state,
@@ -722,7 +382,7 @@ class NNDescent:
             warn("Compressed indexes do not have neighbor graph information.")
             return None
         if "_device_graph" in self.__dict__:  # built from a device array: fresh tensors there, corrected by the library
-            torch = _torch()
+            torch = device_arrays._torch()
             idx, dist = self._device_graph
             with torch.cuda.device(self.device):
                 return idx.clone(), _device_corrected(torch, dist, _metric_of(self.metric), self.device)
@@ -763,9 +423,21 @@ class NNDescent:
         d[name] = value
         return value
 
+    # The names of an index's device-resident and derived state, by group; the sites that drop state are unions of these.
+    # the device tensors: what a build from a device array leaves, and what a device prepare adds to it
+    _DEVICE_PREPARED = ("_device_order", "_device_search_graph", "_device_prepare_stats")
+    _DEVICE_TENSORS = ("_device_graph", "_device_data", "_device_raw") + _DEVICE_PREPARED
+    # the copies made of ``_linear_map``: the map as tensors (``_linear_on_device``) and the transformed rows
+    _LINEAR_COPIES = ("_device_linear", "_lin_data")
+    # what ``prepare()`` derives from the rows and the graph
+    _SEARCH_STRUCTURES = ("_search_graph", "_search_forest", "_vertex_order", "_searcher")
+    # what ``__getattr__`` fetches from the device tensors on first read
+    _HOST_MIRRORS = ("_raw_data", "_lin_data", "_neighbor_graph", "_search_graph", "_quantized_data")
+
     def _drop_device_copies(self):
-        """After the host mirrors have become the truth (``update()``), or for a pickle: the device tensors go."""
-        for name in ("_device_graph", "_device_data", "_device_raw", "_device_order", "_device_search_graph", "_device_prepare_stats"):
+        """After the host mirrors have become the truth (``update()``), or for a pickle: the device tensors go.  ``_device_linear``
+        stays: the map does not change with the rows, and a device query of the host index uses it again."""
+        for name in self._DEVICE_TENSORS:
             self.__dict__.pop(name, None)
 
     def _kernel_metric(self):
@@ -824,7 +496,7 @@ class NNDescent:
         """``recall`` of an index that holds its rows and its graph on the device: the sampled ids go up, the exact search runs on
         the tensors (``_device_data`` keeps the original order through ``prepare()``), one wave per sampled row counts the true ids
         found in the graph's row, and one integer comes back.  No host mirror is read or made."""
-        torch, d = _torch(), self.__dict__
+        torch, d = device_arrays._torch(), self.__dict__
         data, gidx = d["_device_data"], d["_device_graph"][0]
         n, ordinal = int(gidx.shape[0]), int(self.device)
         k = min(10, int(self.n_neighbors)) if k is None else int(k)
@@ -926,7 +598,7 @@ class NNDescent:
         self.tree_init = True
         self._dist_args = tuple((self.metric_kwds or {}).values())
         lin = _linear_map_of(metric, m, self.metric_kwds, data.shape[1])
-        _refuse_with_linear(metric, m, self.quantization, 1)
+        _refuse_uint8_and_sharding(metric, m, self.quantization, 1)
         self._set_up(data, m, random_state, copy=True)  # (dot: the data NNDescent would hold, in a new array)
         # (``distances`` of a metric with a linear map: squared, of the rows transformed with this shift -- what the build keeps)
         self._linear_map = None if lin is None else lin._replace(shift=linear_map.shift_of(self._raw_data))
@@ -958,13 +630,13 @@ class NNDescent:
                 self._search_forest = []  # pynndescent_.py:1377-1378: no tree, queries start from random vertices
             else:
                 if self.verbose:
-                    print(ts(), "Building hub-based search tree")
+                    print(build.ts(), "Building hub-based search tree")
                 self._search_forest = [make_hub_tree(self._work_rows(), self._neighbor_graph[0], self._kernel_metric(), search_leaf_size,
                                                      search_tree_depth, device=self.device,
                                                      seed=int(self.rng_state[0]) & 0x7FFFFFFF)]
                 self._rp_forest = None  # the reference deletes it here (pynndescent_.py:1444)
         if self.verbose:
-            print(ts(), "Diversifying and pruning the search graph")
+            print(build.ts(), "Diversifying and pruning the search graph")
         graph, stages = build_search_graph(
             self._work_rows(), self._neighbor_graph[0], self._neighbor_graph[1], self._kernel_metric(), self.n_neighbors,
             self.prune_degree_multiplier, self.diversify_prob, self.diversify_method,
@@ -973,7 +645,7 @@ class NNDescent:
         self._min_distance = np.float32(stages["min_distance"])                     # pynndescent_.py:1539
         self._visited = np.zeros((self._raw_data.shape[0] // 8) + 1, dtype=np.uint8, order="C")  # pynndescent_.py:1624-1626
         if self.verbose:
-            print(ts(), "Resorting data and graph based on tree order")
+            print(build.ts(), "Resorting data and graph based on tree order")
         if self._search_forest:
             graph, data, self._vertex_order, tree = reorder_by_tree(graph, self._work_rows(), self._search_forest[0])
             if self.__dict__.get("_linear_map") is not None:  # both copies in the leaf order
@@ -1002,7 +674,7 @@ class NNDescent:
 
         if self.diversify_method not in ("standard", "degree_aware"):
             raise ValueError("diversify_method must be 'standard' or 'degree_aware'")
-        torch, d, m = _torch(), self.__dict__, _metric_of(self.metric)
+        torch, d, m = device_arrays._torch(), self.__dict__, _metric_of(self.metric)
         data, (gidx, gdist) = d["_device_data"], d["_device_graph"]
         n, dim, k = int(data.shape[0]), int(data.shape[1]), int(gidx.shape[1])
         dtype, ordinal = _DEVICE_DTYPES[str(data.dtype).rsplit(".", 1)[-1]], int(self.device)
@@ -1023,7 +695,7 @@ class NNDescent:
                     self._search_forest = []  # pynndescent_.py:1377-1378: no tree, queries start from random vertices
                 else:
                     if self.verbose:
-                        print(ts(), "Building hub-based search tree")
+                        print(build.ts(), "Building hub-based search tree")
                     stream = _OnTorchStream(torch, ordinal)
                     b = None
                     try:
@@ -1047,7 +719,7 @@ class NNDescent:
                 vertex_order = np.asarray(tree.indices)
                 order = torch.from_numpy(np.ascontiguousarray(vertex_order, dtype=np.int32)).to(data.device)
             if self.verbose:
-                print(ts(), "Diversifying and pruning the search graph")
+                print(build.ts(), "Diversifying and pruning the search graph")
             stream = _OnTorchStream(torch, ordinal)  # (made after the upload: a side stream waits for it)
             b = None
             try:
@@ -1057,7 +729,7 @@ class NNDescent:
                     gidx.data_ptr(), gdist.data_ptr(), self.n_neighbors, self.prune_degree_multiplier, self.diversify_prob,
                     self.diversify_method == "degree_aware", self.degree_prune_aggressiveness, seed & 0xFFFFFFFF)
                 if self.verbose:
-                    print(ts(), "Resorting data and graph based on tree order")
+                    print(build.ts(), "Resorting data and graph based on tree order")
                 indptr = torch.empty((n + 1,), dtype=torch.int32, device=data.device)
                 indices = torch.empty((nnz,), dtype=torch.int32, device=data.device)
                 _, ms["ms_reorder"] = _stream_ms(torch, stream, lambda: _capi.reorder_csr_device(
@@ -1128,7 +800,7 @@ class NNDescent:
     def _searcher_from_device(self, tree):
         """The searcher of a device-prepared index, filled on torch's current stream from the caller's tensor (its rows gathered by
         the leaf order straight into the searcher's layout), the reordered device graph and the host tree tables."""
-        torch, d = _torch(), self.__dict__
+        torch, d = device_arrays._torch(), self.__dict__
         data, (indptr, indices), order = d["_device_data"], d["_device_search_graph"], d.get("_device_order")
         ordinal = int(self.device)
         with torch.cuda.device(ordinal):
@@ -1185,7 +857,7 @@ class NNDescent:
 
     def _query_device(self, q, m, k, search_k, epsilon):
         """``query`` for a device array: the three forms on the device-pointer entries of the searcher."""
-        torch = _torch()
+        torch = device_arrays._torch()
         q, dtype, ordinal = _check_device_array(q, what="query_data")
         if ordinal != int(self.device):
             raise ValueError("query_data is on device %d, the index on device %d" % (ordinal, int(self.device)))
@@ -1232,13 +904,9 @@ class NNDescent:
             for name in ("_neighbor_graph", "_search_graph", "_quantized_data"):
                 hasattr(self, name)
         state = self.__dict__.copy()
-        for name in ("_device_graph", "_device_data", "_device_order", "_device_search_graph", "_device_prepare_stats"):
-            state.pop(name, None)
         # a linear map travels as _linear_map (kind, A, c: float32); the transformed rows are derived again from _raw_data
-        for name in ("_device_raw", "_device_linear", "_lin_data"):
+        for name in self._DEVICE_TENSORS + self._LINEAR_COPIES + ("_rp_forest", "_searcher"):
             state.pop(name, None)
-        state.pop("_rp_forest", None)
-        state.pop("_searcher", None)
         state["_search_forest"] = tuple(tuple(t) for t in self._search_forest)  # rp_trees.py:3060-3069 denumbaify_tree
         return state
 
@@ -1352,7 +1020,8 @@ class NNDescent:
         self._rp_forest = _DeviceForestSentinel(self.n_trees, n_leaves, eff_leaf_size)
         self._raw_data = raw
         if self._prepared:  # pynndescent_.py:2538-2553: the derived structures are rebuilt
-            for name in ("_search_graph", "_search_forest", "_vertex_order", "_searcher"):
+            # (``_quantized_data`` stays where ``_update_device`` pops it: the fresh prepare() below resets it with the codebook)
+            for name in self._SEARCH_STRUCTURES:
                 self.__dict__.pop(name, None)
             self.prepare()
 
@@ -1370,7 +1039,7 @@ class NNDescent:
         linear = self._linear_on_device(data.device) if d.get("_linear_map") is not None else None
         n_old, dim, k, ordinal = int(data.shape[0]), int(data.shape[1]), int(gidx.shape[1]), int(self.device)
         ids, sources = _resolve_updated_indices(updated_indices, n_old)  # (IndexError: before any device work)
-        torch = _torch()
+        torch = device_arrays._torch()
         n_fresh = 0 if xs_fresh is None else int(xs_fresh.shape[0])
         n = n_old + n_fresh
         n_trees = self.n_trees_after_update  # pynndescent_.py:2498 (assigned with the new tensors: a rebuild that raises changes nothing)
@@ -1409,8 +1078,8 @@ class NNDescent:
         self.n_trees, self._build_stats = n_trees, build_stats
         self._rp_forest = _DeviceForestSentinel(n_trees, n_leaves, eff_leaf_size)
         was_prepared = self._prepared
-        for name in ("_device_order", "_device_search_graph", "_device_prepare_stats", "_raw_data", "_lin_data", "_neighbor_graph",
-                     "_search_graph", "_quantized_data", "_searcher", "_search_forest", "_vertex_order"):
+        # (the rows and the graph are replaced below; every mirror of the old ones is stale, ``_device_linear`` is the same map)
+        for name in self._DEVICE_PREPARED + self._HOST_MIRRORS + self._SEARCH_STRUCTURES:
             d.pop(name, None)
         self._device_data, self._device_graph = dev_in.rows, graph  # (the caller's original tensor is released)
         if linear is not None:
@@ -1427,338 +1096,6 @@ _FROM_GRAPH_DEFAULTS = {
     if name not in ("self", "data", "metric", "n_neighbors", "random_state", "tree_init", "init_graph", "init_dist",
                     "n_devices", "devices")
 }
-
-EMPTY_GRAPH = (np.array([[-1]], dtype=np.int32), np.array([[np.inf]], dtype=np.float32),
-               np.array([[0]], dtype=np.uint8))  # pynndescent_.py:64-68
-
-# the reference's functions of the kernels' own spaces (pynndescent_.py:1247-1260) -> the metric whose kernels they name
-_ND_ALIASES = {"squared_euclidean": "sqeuclidean", "alternative_cosine": "cosine", "alternative_dot": "dot",
-               "alternative_inner_product": "inner_product", "alternative_hellinger": "hellinger"}
-# distance arguments nn_descent understands: name (or __name__ of the reference's function) -> (kernel metric, correction);
-# the eight metrics give true distances (the same kernels, corrected on return), the aliases none (a copy is no correction:
-# nn_descent returns the finished arrays themselves)
-_ND_DISTS = {name: (m.code, None if m.correction is _capi.host_copy else m.correction) for name, m in _METRICS.items()}
-_ND_DISTS.update((alt, (_METRICS[name].code, None)) for alt, name in _ND_ALIASES.items())
-# the boolean family: the nine names (jaccard: corrected on return), and "alternative_jaccard" for its kernel distance
-_ND_ALIASES["alternative_jaccard"] = "jaccard"
-_ND_DISTS.update((name, (m.code, None if m.correction is _capi.host_copy else m.correction)) for name, m in _BOOLEAN_METRICS.items())
-_ND_DISTS["alternative_jaccard"] = (_BOOLEAN_METRICS["jaccard"].code, None)
-
-
-def nn_descent(data, n_neighbors, rng_state, max_candidates=50, dist="squared_euclidean", n_iters=10, delta=0.001,
-               init_graph=EMPTY_GRAPH, rp_tree_init=True, leaf_array=None, low_memory=True, verbose=False, device=0):
-    """The reference's ``nn_descent`` (pynndescent_.py:323-366) with the same arguments, on the GPU: the seam a caller
-    uses who keeps the reference's ``make_forest`` / ``rptree_leaf_array`` and hands the leaves in.
-
-    data float32 (n, d); rng_state int64[3]; ``dist``: "squared_euclidean" / "alternative_cosine" / "alternative_dot" /
-    "alternative_inner_product" / "correlation" / "alternative_hellinger" (what NNDescent passes, pynndescent_.py:1247-1260),
-    "euclidean" / "cosine" / "dot" / "inner_product" / "hellinger" (true distances: the same kernels, corrected on return),
-    "proxy_inner_product" (the proxy distances themselves: it has no correction), the boolean metrics "jaccard" (corrected
-    on return; "alternative_jaccard": its kernel distance) / "dice" / "sokalsneath" / "matching" / "rogerstanimoto" /
-    "sokalmichener" / "kulsinski" / "russellrao" / "yule",
-    or the reference function of one of those names (dot: the kernels rank by the L2-normalised rows, as NNDescent's
-    normalised data gives; hand in normalised rows for the reference's ranking); ``init_graph``: EMPTY_GRAPH, or the heap triple ``(indices (n, k),
-    distances (n, k), flags (n, k))`` the reference accepts (entries with index -1 are empty); ``leaf_array`` int32
-    (n_leaves, max_leaf_size), -1 padded, used when ``rp_tree_init``.  ``low_memory`` is accepted and unused, as in the
-    reference (pynndescent_.py:335).  Returns ``(indices int32 (n, k), distances float32 (n, k))``, rows ascending."""
-    name = dist if isinstance(dist, str) else getattr(dist, "__name__", None)
-    if name not in _ND_DISTS:
-        raise NotImplementedError("pynndescent_amd.nn_descent: dist must be one of %s (got %r)" % (sorted(_ND_DISTS), dist))
-    m, correction = _metric_of(_ND_ALIASES.get(name, name)), _ND_DISTS[name][1]
-    data = np.ascontiguousarray(data, dtype=np.float32)
-    n = data.shape[0]
-    _check_supported_sizes(n_neighbors, max_candidates, None)
-    empty = init_graph[0].shape[0] == 1  # EMPTY_GRAPH
-    if not empty and not (init_graph[0].shape[0] == n and init_graph[0].shape[1] == n_neighbors):
-        raise ValueError("Invalid initial graph specified!")  # pynndescent_.py:352
-    if empty and rp_tree_init and leaf_array is None:
-        raise ValueError("rp_tree_init=True needs a leaf_array (rptree_leaf_array of a forest)")
-    leaf_size = _reference_defaults(n, n_neighbors, 0, n_iters, None, max_candidates)[2]
-    # (a heap handed over: its entries, with their distances; flags restart as "new": they were never sampled here)
-    (idx, dst), _, _ = _build_graph(
-        data, m, n_neighbors, 0, leaf_size, 200, max_candidates, n_iters, delta, np.asarray(rng_state, np.int64),
-        np.zeros(3, np.int64), device, leaf_array=leaf_array if empty and rp_tree_init else None,
-        init_graph=None if empty else np.asarray(init_graph[0], np.int32),
-        init_dist=None if empty else np.asarray(init_graph[1], np.float32), random_fill=empty, stats=False, verbose=verbose)
-    if correction is not None:
-        dst = correction(dst).astype(np.float32)
-    return idx, dst
-
-
-def _exact_linear_rows(metric, m, metric_kwds, data, queries, device):
-    """``exact_knn`` of a metric with a linear map: ``(data, queries)`` transformed by the device (float32; tensors stay tensors),
-    on which the search is euclidean.  The shift is the one an index of ``data`` would fix; distances do not depend on it."""
-    if _is_device_array(data):
-        data, dtype, ordinal = _check_device_array(data, device)
-        lin = _linear_map_of(metric, m, metric_kwds, data.shape[1])
-        if lin is None:
-            return data, queries
-        torch = _torch()
-        with torch.cuda.device(ordinal):
-            dl = _DeviceLinear(lin._replace(shift=linear_map.shift_of(_DeviceRowsView(data))), data.device, ordinal)
-            stream = torch.cuda.current_stream(ordinal).cuda_stream
-            if queries is not None:
-                if _is_device_array(queries):
-                    queries, q_dtype, _ = _check_device_array(queries, what="queries")
-                    queries = queries.to(data.device)
-                else:
-                    queries, q_dtype = torch.from_numpy(_check_array_no_scan(queries)).to(data.device), _capi.NND_DTYPE_FLOAT32
-                if queries.shape[1] != data.shape[1]:
-                    raise ValueError("queries must have shape (n_queries, %d)" % data.shape[1])
-                queries = dl.rows(queries, q_dtype, stream)
-            return dl.rows(data, dtype, stream), queries
-    data = _check_array_no_scan(data)
-    lin = _linear_map_of(metric, m, metric_kwds, data.shape[1])
-    if lin is None:
-        return data, queries
-    lin = lin._replace(shift=linear_map.shift_of(data))
-    if queries is not None:
-        queries = _check_array_no_scan(_rows_to_host(queries))
-        if queries.shape[1] != data.shape[1]:
-            raise ValueError("queries must have shape (n_queries, %d)" % data.shape[1])
-        queries = _capi.linear_rows_host(lin.kind, lin.a, lin.shift, queries, device=device)
-    return _capi.linear_rows_host(lin.kind, lin.a, lin.shift, data, device=device), queries
-
-
-def exact_knn(data, queries=None, k=10, metric="euclidean", rows=None, device=0, return_stats=False, metric_kwds=None):
-    """Exact ``k`` nearest neighbours by brute force on the GPU (csrc/exact.hip): of every row of ``data`` (self included), of the
-    rows ``rows`` of it, or of the external ``queries``.  Returns ``(indices int32 (m, k), distances float32-precision (m, k))``
-    in the metric's own space (the correction ``NNDescent.neighbor_graph`` applies), rows ascending, ties to the smaller id;
-    with ``return_stats`` also the call's statistics (rows that needed the float64 tier, kernel times).  The metrics and the
-    input rules are the class's: dot rows and queries are L2-normalised, hellinger takes no negative entry, NaN / inf raise
-    the reference's error.  ``k`` is at most 256 and at most the number of rows.
-
-    ``data`` may be a device array (a 2-D ``torch.Tensor`` on a HIP device, float32 / float16 / bfloat16 / float64): the search
-    then runs on the tensor where it is, on torch's current stream, and the answers are tensors on that device -- int32 ids, and
-    the distances corrected on the device (float32 or float64, as ``NNDescent.neighbor_graph`` returns them for the metric; dot
-    normalises on the device, within rounding of the host's rows).  ``queries`` on the other side are moved to where ``data`` is;
-    ``rows`` may be a host array or a tensor (the ids are range-checked on the host).
-
-    ``metric_kwds``: the arguments of seuclidean / wminkowski (p = 2) / mahalanobis / minkowski (p = 2), read positionally as by
-    ``NNDescent``; every other metric ignores it.  For these metrics the answers are exact in this sense: (float64 distance, id)
-    on the float32 transformed rows -- the rows ``A (x - c)`` the device computes once (csrc/linear.hip), on which the search is
-    the euclidean one."""
-    if queries is not None and rows is not None:
-        raise ValueError("exact_knn takes `queries` (external points) or `rows` (ids of data rows), not both")
-    k = int(k)
-    if k > 256:
-        raise NotImplementedError("pynndescent_amd.exact_knn keeps at most k <= 256 neighbours per row (got k = %d)" % k)
-    m = _metric_record(metric)
-    _no_exact_for_proxy(metric, m, "exact_knn")
-    if m.linear:  # (metric_kwds is validated in there, before any device work)
-        data, queries = _exact_linear_rows(metric, m, metric_kwds, data, queries, device)
-        metric, m = "euclidean", _METRICS["euclidean"]
-    if _is_device_array(data):
-        return _exact_knn_device(data, queries, k, metric, m, rows, device, return_stats)
-    queries, rows = _rows_to_host(queries), _ids_to_host(rows)  # (the results live where the data lives)
-    data = _check_array_no_scan(data)
-    n = data.shape[0]
-    if k < 1 or k > n:
-        raise ValueError("k must be in 1 .. n = %d (got %d)" % (n, k))
-    _raise_if_negative_host(data, m)
-    if queries is not None:
-        from sklearn.utils import assert_all_finite
-
-        queries = _check_array_no_scan(queries)
-        if queries.shape[1] != data.shape[1]:
-            raise ValueError("queries must have shape (n_queries, %d)" % data.shape[1])
-        assert_all_finite(queries)
-        _raise_if_negative_host(queries, m)
-    if rows is not None:
-        rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
-        if rows.size and (rows.min() < 0 or rows.max() >= n):
-            raise ValueError("rows must be ids in [0, %d)" % n)
-    if m.normalize:  # pynndescent_.py:1101-1102, 2316-2318
-        from sklearn.preprocessing import normalize
-
-        data = normalize(data, norm="l2", copy=True)
-        if queries is not None:
-            queries = normalize(queries, norm="l2", copy=True)
-    # an auxiliary handle: the rows and their prepared copy, no k-lists
-    builder = _capi.Builder(n, data.shape[1], m.code, k, 0, 60, 200, min(60, k), 1, 0.001, [1, 2, 3], [4, 5, 6], device=device,
-                            flags=_capi.NND_FLAG_NO_GRAPH)
-    try:
-        builder.set_data_host(data)
-        _raise_if_nonfinite(builder, data)
-        if queries is not None:
-            idx, dist, stats = builder.exact_knn_queries(queries, k)
-        else:
-            idx, dist, stats = builder.exact_knn(rows, k)
-    finally:
-        builder.close()
-    dist = m.correction(dist)
-    return (idx, dist, stats) if return_stats else (idx, dist)
-
-
-def _exact_knn_device(data, queries, k, metric, m, rows, device, return_stats):
-    """``exact_knn`` for a device array ``data`` (``k``, the metric and queries-or-rows are checked already): an auxiliary handle
-    bound to the tensor on torch's current stream, the device entries of csrc/exact.hip, the answers corrected on the device.
-    ``rows``: a host array or a tensor of ids (range-checked on the host), or an int32 tensor on the data's device that the
-    caller has checked (``NNDescent._recall_device``).  What crosses the bus: the row ids, host queries, and scalars."""
-    data, dtype, ordinal = _check_device_array(data, device)
-    n, dim = int(data.shape[0]), int(data.shape[1])
-    if k < 1 or k > n:
-        raise ValueError("k must be in 1 .. n = %d (got %d)" % (n, k))
-    torch = _torch()
-    with torch.cuda.device(ordinal):
-        q = q_dtype = None
-        if queries is not None:
-            if _is_device_array(queries):
-                q, q_dtype, q_ordinal = _check_device_array(queries, what="queries")
-                if q_ordinal != ordinal:
-                    q = q.to(data.device)
-            else:
-                q, q_dtype = torch.from_numpy(_check_array_no_scan(queries)).to(data.device), _capi.NND_DTYPE_FLOAT32
-            if q.shape[1] != dim:
-                raise ValueError("queries must have shape (n_queries, %d)" % dim)
-            if q.shape[0] and not bool(torch.isfinite(q).all().item()):  # one scalar; only the error path brings the queries down
-                from sklearn.utils import assert_all_finite
-
-                assert_all_finite(_rows_to_host(q))
-            if m.nonnegative and q.shape[0] and bool((q.min() < 0).item()):
-                raise ValueError(_NEGATIVE_HELLINGER)
-        rows_dev = None
-        if rows is not None:
-            if _is_device_array(rows) and _dtype_name(rows) == "int32" and len(rows.shape) == 1 and rows.device == data.device:
-                rows_dev = rows
-            else:
-                rows = np.ascontiguousarray(_ids_to_host(rows), dtype=np.int64).reshape(-1)
-                if rows.size and (rows.min() < 0 or rows.max() >= n):
-                    raise ValueError("rows must be ids in [0, %d)" % n)
-                rows_dev = torch.from_numpy(rows.astype(np.int32)).to(data.device)
-        n_out = int(q.shape[0]) if q is not None else (n if rows_dev is None else int(rows_dev.shape[0]))
-        idx = torch.empty((n_out, k), dtype=torch.int32, device=data.device)
-        dist = torch.empty((n_out, k), dtype=torch.float32, device=data.device)
-        stream = _OnTorchStream(torch, ordinal)  # (made after the uploads: a side stream waits for them)
-        # an auxiliary handle: the rows and their prepared copy, no k-lists
-        builder = _capi.Builder(n, dim, m.code, k, 0, 60, 200, min(60, k), 1, 0.001, [1, 2, 3], [4, 5, 6], device=ordinal,
-                                flags=_capi.NND_FLAG_NO_GRAPH)
-        try:
-            builder.set_stream(stream.ptr)
-            builder.set_data_device_typed(data.data_ptr(), dtype, keepalive=data)  # (dot: normalised there, as the class does)
-            _raise_if_nonfinite(builder, lambda: _rows_to_host(data))
-            if m.nonnegative and builder.data_negative():
-                raise ValueError(_NEGATIVE_HELLINGER)
-            if n_out == 0:  # (nothing asked for: an empty tensor has no address to hand over)
-                stats = dict(_capi.NNDExactStats().as_dict(), slices=0)
-            elif q is not None:
-                stats = builder.exact_knn_device(k, idx.data_ptr(), dist.data_ptr(), q_ptr=q.data_ptr(), q_dtype=q_dtype, n_q=n_out)
-            else:
-                stats = builder.exact_knn_device(k, idx.data_ptr(), dist.data_ptr(), rows_ptr=0 if rows_dev is None else rows_dev.data_ptr(),
-                                                 n_rows=n_out)
-        finally:
-            builder.close()
-            stream.done()
-        dist = _device_corrected(torch, dist, m, ordinal)
-    return (idx, dist, stats) if return_stats else (idx, dist)
-
-
-def _build_graph(data, m, n_neighbors, n_trees, leaf_size, max_depth, max_candidates, n_iters, delta, rng_state, tree_rng,
-                 device, forest=False, leaf_array=None, init_graph=None, init_dist=None, old_graph=None, random_fill=False,
-                 check_finite=False, stats=True, verbose=False, announce=False, dev_in=None):
-    """Every single-GPU build (``_capi.Builder``): the data in, its flags read (the NaN / inf one only when
-    ``check_finite``), ``forest`` built on the device, the graph seeded -- ``old_graph`` (ids, distances) as "old" edges,
-    then ``init_graph`` / ``init_dist``, the caller's ``leaf_array`` or the forest's leaves, then the random fill when
-    ``random_fill`` -- NN-descent to the stop rule, the graph out.  ``announce``: the constructor's verbose line.  ``dev_in``
-    (a ``_DeviceInput``): the rows are a device array, read in place on torch's stream, and the graph comes out as tensors;
-    ``old_graph`` and ``init_graph`` / ``init_dist`` may then be tensors as well (int32 / float32, read in place).  Returns
-    ``((indices, distances), the stats (when ``stats``), the forest's leaf count)``."""
-    n = data.shape[0]
-    builder = _capi.Builder(n, data.shape[1], m.code, n_neighbors, n_trees, leaf_size, max_depth, max_candidates, n_iters,
-                            delta, rng_state, tree_rng, device=device)
-    try:
-        if dev_in is None:
-            builder.set_data_host(data)
-        else:
-            dev_in.set_data(builder, m)
-        if check_finite:
-            _raise_if_nonfinite(builder, data if dev_in is None else dev_in.host_rows)
-        if m.nonnegative and builder.data_negative():
-            raise ValueError(_NEGATIVE_HELLINGER)
-        n_leaves = None
-        if forest:
-            builder.make_forest()
-            n_leaves = builder.stats()["n_leaves"]
-        if announce:
-            print(ts(), "NN descent for", str(n_iters), "iterations")
-        if old_graph is not None:
-            builder.reset_graph()
-            if _is_device_array(old_graph[0]):  # (update() of a device-built index: the invalidated graph is a pair of tensors)
-                builder.init_from_neighbor_graph_device(old_graph[0].data_ptr(), old_graph[1].data_ptr(), old_graph[0].shape[1])
-            else:
-                builder.init_from_neighbor_graph(*old_graph)
-        if init_graph is not None and _is_device_array(init_graph):  # int32 / float32, contiguous, on the data's device
-            builder.init_from_graph_device(init_graph.data_ptr(), 0 if init_dist is None else init_dist.data_ptr(), init_graph.shape[1])
-        elif init_graph is not None:
-            builder.init_from_graph(init_graph, init_dist)
-        elif leaf_array is not None:
-            builder.init_from_leaf_array(leaf_array)
-        elif forest:
-            builder.init_from_leaves()
-        if random_fill:
-            builder.init_random()
-        _descend(builder, n, n_neighbors, n_iters, delta, verbose)
-        graph = builder.finalize() if dev_in is None else dev_in.finalize(builder)
-        return graph, builder.stats() if stats else None, n_leaves
-    finally:
-        builder.close()
-        if dev_in is not None:
-            dev_in.close()
-
-
-def _descend(builder, n, n_neighbors, n_iters, delta, verbose):
-    """nn_descent_internal (pynndescent_.py:296-320): the library's loop (nnd_descent, no host round trip per iteration),
-    or with ``verbose`` the same iterations and stop rule driven from here, so that the output matches the reference's."""
-    if not verbose:
-        builder.descent()
-        return
-    for it in range(n_iters):
-        print("\t", it + 1, " / ", n_iters)
-        c = builder.descent_iter()
-        if c <= delta * n_neighbors * n:
-            print("\tStopping threshold met -- exiting after", it + 1, "iterations")
-            break
-
-
-def _check_array_no_scan(data):
-    try:
-        return check_array(data, dtype=np.float32, order="C", ensure_all_finite=False)
-    except TypeError:  # scikit-learn < 1.6
-        return check_array(data, dtype=np.float32, order="C", force_all_finite=False)
-
-
-def _raise_if_nonfinite(builder, data):
-    """The ValueError check_array raises in the reference for NaN / inf input (pynndescent_.py:1054), from the device flag."""
-    if builder.data_nonfinite():
-        from sklearn.utils import assert_all_finite
-
-        if callable(data):  # a device array: only this error path brings the rows to the host, for sklearn's wording
-            data = data()
-        assert_all_finite(data)  # raises "Input contains NaN." / "... infinity or a value too large ..."
-        raise ValueError("Input contains NaN or infinity.")  # (unreachable unless the two scans disagree)
-
-
-# hellinger takes sqrt(x): the reference computes NaN distances from a negative entry without a word; here it is an error
-_NEGATIVE_HELLINGER = "the hellinger metric needs non-negative input: the data holds a negative entry"
-
-
-def _raise_if_negative_host(data, m):
-    if m.nonnegative and data.size and data.min() < 0:
-        raise ValueError(_NEGATIVE_HELLINGER)
-
-
-def _check_supported_sizes(n_neighbors, max_candidates, init_graph):
-    """The GPU k-lists hold at most 256 entries (four per lane of a wave; rows above 64 take the LDS-merge kernels) and the
-    candidate lists at most 128 (above 64: five passes of the 64-slot join over blocks of the lists); the reference has no such bounds (pynndescent_.py:976-982), so the limits are reported up
-    front and by name."""
-    if int(n_neighbors) > 256 or (max_candidates is not None and int(max_candidates) > 128):
-        raise NotImplementedError(
-            "pynndescent_amd supports n_neighbors <= 256 and max_candidates <= 128 (got n_neighbors=%s, max_candidates=%s); "
-            "use pynndescent.NNDescent (or pynndescent_amd.make_index) for wider graphs" % (n_neighbors, max_candidates))
-    if init_graph is not None and len(_shape_of(init_graph)) == 2 and _shape_of(init_graph)[1] > 256:
-        raise NotImplementedError("pynndescent_amd supports init_graph with at most 256 columns (got %d); use "
-                                  "pynndescent.NNDescent" % _shape_of(init_graph)[1])
-
 
 def make_index(data, *args, **kwargs):
     """``NNDescent(data, ...)`` on the GPU when the input is in scope (dense data, euclidean / l2 / sqeuclidean / cosine / dot /
@@ -1777,18 +1114,3 @@ def make_index(data, *args, **kwargs):
             raise exc
         warn("pynndescent_amd: %s -- building with pynndescent.NNDescent on the CPU instead" % exc)
         return pynndescent.NNDescent(data, *args, **kwargs)
-
-
-# string metrics the reference recognises (distances.py:2103-2168 named_distances keys, 2190-2239 proxy_distances keys) -- used only to
-# decide between NotImplementedError (valid in the reference, not accelerated) and the reference's ValueError.
-_KNOWN_REFERENCE_METRICS = frozenset(
-    """euclidean l2 sqeuclidean manhattan taxicab l1 chebyshev linfinity linfty linf minkowski seuclidean
-    standardised_euclidean wminkowski weighted_minkowski mahalanobis canberra cosine dot inner_product correlation
-    haversine braycurtis spearmanr tsss true_angular hellinger kantorovich wasserstein wasserstein_1d
-    wasserstein-1d kantorovich-1d kantorovich_1d circular_kantorovich circular_wasserstein sinkhorn jensen-shannon
-    jensen_shannon symmetric-kl symmetric_kl symmetric_kullback_liebler hamming jaccard dice matching kulsinski
-    rogerstanimoto russellrao sokalsneath sokalmichener yule bit_hamming bit_jaccard
-    proxy_inner_product proxy_wasserstein_1d proxy_wasserstein-1d proxy_kantorovich proxy_wasserstein
-    proxy_circular_kantorovich proxy_circular_wasserstein proxy_jensen_shannon proxy_jensen-shannon proxy_symmetric_kl
-    proxy_symmetric-kl proxy_sinkhorn""".split()
-)

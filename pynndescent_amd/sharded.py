@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import _capi
-from .nndescent import _reference_defaults
+from .build import _reference_defaults
 
 
 # ------------------------------------------------------------------------------------------------

@@ -170,7 +170,7 @@ def rec(monkeypatch):
 
     monkeypatch.setattr(_capi, "Builder", FakeBuilder)
     monkeypatch.setattr(sharded, "build_multi", fake_build_multi)
-    monkeypatch.setattr(nndescent, "_torch", no_torch)
+    monkeypatch.setattr(nndescent.device_arrays, "_torch", no_torch)
     calls_and_stop = type("Rec", (), {})()
     calls_and_stop.calls, calls_and_stop.Stop, calls_and_stop.builder = calls, Stop, FakeBuilder
     return calls_and_stop

@@ -141,7 +141,7 @@ def rec(monkeypatch):
 
     monkeypatch.setattr(_capi, "Builder", FakeBuilder)
     monkeypatch.setattr(sharded, "build_multi", fake_build_multi)
-    monkeypatch.setattr(nndescent, "ts", lambda: "TS")
+    monkeypatch.setattr(nndescent.build, "ts", lambda: "TS")
     return r
 
 
