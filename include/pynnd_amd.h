@@ -668,6 +668,28 @@ int32_t nnd_searcher_query_proxy_device(nnd_searcher_t s, const float *queries_d
                                         float epsilon, int32_t *out_idx_dev, float *out_dist_dev, void *hip_stream);
 int32_t nnd_searcher_query_rerank_device(nnd_searcher_t s, const float *queries_dev, int64_t nq, int32_t k, int32_t search_k,
                                          float epsilon, int32_t *out_idx_dev, float *out_dist_dev, void *hip_stream);
+/* Filtered queries (beyond the reference): an allow set, one for all queries of a call.  The filter is STATE of the searcher: once
+ * set, every query entry above (host and device forms, float / proxy / rerank) runs its filtered kernel instance until
+ * nnd_searcher_clear_filter or the next nnd_searcher_set_filter*; a searcher without a filter launches exactly the kernels it
+ * launched before.  The rule of the filtered walk: a vertex enters the walk's result list only if it is allowed.  It is still
+ * visited, pushed to the frontier and expanded, so the bound (taken from the allowed-only list, +inf while that is short), the
+ * stop rule and the hand-over to the global-memory tier are unchanged; the proxy / rerank entries rerank search_k allowed
+ * candidates.  Unfilled slots (-1, +inf).
+ *   kind NND_FILTER_MASK: `filter` is one byte per row (count == n), non-zero = allowed;
+ *   kind NND_FILTER_IDS:  `filter` is `count` int64 row ids (duplicates are fine); an id outside 0 .. n - 1 is reported by the
+ *                         return value 2, nothing is written for it and the searcher is left without a filter.
+ * Mask and ids are in the ORIGINAL row numbering; `order` (n, int32; NULL: the identity) is the searcher's row order, row i of
+ * the searcher being original row order[i] -- the bitset the kernels read (32 rows per word) is in the searcher's numbering.
+ * n_allowed (may be NULL): the number of allowed rows.  The host form copies filter and order to the device and runs on the
+ * searcher's stream; the device form reads device pointers on `hip_stream` (NULL: the default stream).  Both return when the
+ * stream has drained, so the caller's buffers are free again.  Returns 0, 1 (error) or 2 (id out of range). */
+#define NND_FILTER_MASK 0
+#define NND_FILTER_IDS 1
+int32_t nnd_searcher_set_filter(nnd_searcher_t s, const void *filter, int64_t count, int32_t kind, const int32_t *order /* may be NULL */,
+                                int64_t *n_allowed /* may be NULL */);
+int32_t nnd_searcher_set_filter_device(nnd_searcher_t s, const void *filter_dev, int64_t count, int32_t kind,
+                                       const int32_t *order_dev /* may be NULL */, int64_t *n_allowed /* may be NULL */, void *hip_stream);
+int32_t nnd_searcher_clear_filter(nnd_searcher_t s);
 int32_t nnd_searcher_destroy(nnd_searcher_t s);
 const char *nnd_searcher_last_error(nnd_searcher_t s /* NULL: the error of a failed create */);
 

@@ -38,6 +38,7 @@ def metric_code(name):
     return METRIC_CODES[name] if name in METRIC_CODES else BOOLEAN_METRIC_CODES[name]
 # element types of a device array (include/pynnd_amd.h NND_DTYPE_*) and the corrections of nnd_device_correct (NND_CORRECT_*)
 NND_DTYPE_FLOAT32, NND_DTYPE_FLOAT16, NND_DTYPE_BFLOAT16, NND_DTYPE_FLOAT64 = 0, 1, 2, 3
+NND_FILTER_MASK, NND_FILTER_IDS = 0, 1  # nnd_searcher_set_filter's `kind`
 NND_CORRECT_COPY, NND_CORRECT_SQRT, NND_CORRECT_ALT_COSINE, NND_CORRECT_ALT_INNER_PRODUCT, NND_CORRECT_ALT_HELLINGER = 0, 1, 2, 3, 4
 NND_LINEAR_DIAGONAL, NND_LINEAR_DENSE = 0, 1  # the kinds of a metric's linear map (include/pynnd_amd.h NND_LINEAR_*, csrc/linear.hip)
 NND_FLAG_NO_GRAPH = 1  # auxiliary handle: no k-lists / candidate / proposal tables (pruning pass, hub tree)
@@ -320,6 +321,9 @@ _SIGNATURES = [
                                                     C.c_void_p]),
     ("nnd_searcher_query_rerank_device", C.c_int32, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
                                                      C.c_void_p]),
+    ("nnd_searcher_set_filter", C.c_int32, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.POINTER(C.c_int64)]),
+    ("nnd_searcher_set_filter_device", C.c_int32, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),
+    ("nnd_searcher_clear_filter", C.c_int32, [_H]),
     ("nnd_searcher_destroy", C.c_int32, [_H]),
     ("nnd_searcher_last_error", C.c_char_p, [_H]),
 ]
@@ -801,6 +805,43 @@ class Searcher:
         else:
             rc = self.lib.nnd_searcher_query_rerank_device(self._h, q, int(nq), int(k), int(search_k), float(epsilon), oi, od, st)
         if rc != 0:
+            raise NNDError(self.lib.nnd_searcher_last_error(self._h).decode())
+
+    def set_filter(self, filter, order=None):
+        """The allow set of the next queries (``nnd_searcher_set_filter``), from host arrays: a bool / uint8 mask of n rows or an
+        integer array of row ids, in the ORIGINAL numbering; ``order`` (int32, n; None: the identity) is the searcher's row order.
+        Returns the number of allowed rows; ``ValueError`` for an id outside 0 .. n - 1."""
+        f = np.asarray(filter)
+        if f.dtype == np.bool_ or f.dtype == np.uint8:
+            f, kind = np.ascontiguousarray(f).view(np.uint8), NND_FILTER_MASK
+        else:
+            f, kind = np.ascontiguousarray(f, np.int64), NND_FILTER_IDS
+        assert f.ndim == 1 and (kind == NND_FILTER_IDS or f.shape[0] == self.n)
+        if order is not None:
+            order = np.ascontiguousarray(order, np.int32)
+            assert order.shape == (self.n,)
+        count = C.c_int64(0)
+        return self._filter_rc(self.lib.nnd_searcher_set_filter(self._h, _ptr(f), int(f.shape[0]), kind, _ptr(order), C.byref(count)), count)
+
+    def set_filter_device(self, filter_ptr, count, kind, order_ptr, stream_ptr):
+        """``set_filter`` from device memory (``nnd_searcher_set_filter_device``): ``count`` mask bytes (``NND_FILTER_MASK``) or int64
+        ids (``NND_FILTER_IDS``) at ``filter_ptr``, the int32 row order at ``order_ptr`` (0: the identity), on the HIP stream
+        ``stream_ptr`` (0: the default stream)."""
+        dev = lambda p: C.c_void_p(int(p)) if p else None  # noqa: E731
+        n_allowed = C.c_int64(0)
+        return self._filter_rc(self.lib.nnd_searcher_set_filter_device(self._h, dev(filter_ptr), int(count), int(kind), dev(order_ptr),
+                                                                       C.byref(n_allowed), dev(stream_ptr)), n_allowed)
+
+    def _filter_rc(self, rc, count):
+        if rc == 2:
+            raise ValueError(self.lib.nnd_searcher_last_error(self._h).decode())
+        if rc != 0:
+            raise NNDError(self.lib.nnd_searcher_last_error(self._h).decode())
+        return int(count.value)
+
+    def clear_filter(self):
+        """Back to unfiltered queries."""
+        if self.lib.nnd_searcher_clear_filter(self._h) != 0:
             raise NNDError(self.lib.nnd_searcher_last_error(self._h).decode())
 
     def last_spilled(self):

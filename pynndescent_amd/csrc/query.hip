@@ -74,6 +74,9 @@ struct nnd_searcher_s {
     hipStream_t stream = nullptr;
     int64_t last_spilled = 0;  // queries of the last call that ran on the global-memory tier
     bool force_big = false;    // nnd_searcher_set_tier(1): every query on the global-memory tier (tests)
+    uint32_t *allow = nullptr;            // the filter's bitset over the searcher's numbering, (n + 31) / 32 words (allocated on first use)
+    unsigned long long *fstat = nullptr;  // 2: allowed rows of the last filter, its out-of-range flag
+    bool filter_on = false;               // nnd_searcher_set_filter*: the query entries run the filtered instances
     nnd_devmem mem;            // owner of the device buffers above (devmem.h)
     char err[512] = {0};
     void set_error(const char *fmt, ...) {
@@ -184,8 +187,12 @@ __device__ __forceinline__ float q_rerank_dist(const float *__restrict__ x, cons
 // float rows by the proxy inner product, the rerank by -<q,x>; the query stays as given, a zero query is searched).
 // BM: the boolean family (codes 8..16, the instances of k_query_bool): the tree is descended with the query as given, then the
 // query becomes its indicator row and the walk's distances are metric.h nnd_bool_dist on exact counts.
+// FL: filtered (the instances of k_query_filtered / k_query_bool_filtered): a vertex enters the walk's result list only if its
+// bit in `allow` (a bitset over the searcher's numbering) is set.  It is still visited, pushed to the frontier and expanded, so
+// the bound, the stop rule and the hand-over to the big tier are those of the unfiltered walk relative to the allowed rows; the
+// rerank's candidates are the walk's results and so all allowed.  The other instances never read `allow`.
 // The body is shared by the kernels k_query (BM = false) and k_query_bool below.
-template <bool BIG, int KU, bool Q8, bool RR, bool BM>
+template <bool BIG, int KU, bool Q8, bool RR, bool BM, bool FL = false>
 __device__ __forceinline__ void q_body(const float *__restrict__ x, const float *__restrict__ xn2, int dp, int d, int metric,
                                                int64_t n, const int32_t *__restrict__ indptr, const int32_t *__restrict__ indices,
                                                const float *__restrict__ hyper, const float *__restrict__ offsets,
@@ -196,7 +203,8 @@ __device__ __forceinline__ void q_body(const float *__restrict__ x, const float 
                                                const int32_t *__restrict__ qlist /* BIG: the queries of this batch */,
                                                int n_list, unsigned char *__restrict__ scratch, size_t scratch_stride,
                                                const uint8_t *__restrict__ codes, int dcs, const float *__restrict__ lut,
-                                               const float *__restrict__ cn2, int k_out) {
+                                               const float *__restrict__ cn2, int k_out,
+                                               const uint32_t *__restrict__ allow = nullptr) {
     extern __shared__ __attribute__((aligned(16))) unsigned char qsm[];
     const int lane = nnd_lane(), w = threadIdx.x >> 6;
     if constexpr (Q8) {  // the codebook, once per workgroup (256 threads: one entry each)
@@ -306,6 +314,12 @@ __device__ __forceinline__ void q_body(const float *__restrict__ x, const float 
                 if (lane == p) { rd[u] = dc; rv[u] = vc; }
             }
         }
+    };
+    // FL: may `vc` (wave-uniform) enter the result list -- one word of the allow bitset
+    auto allowed = [&](int32_t vc) -> bool {
+        if constexpr (!FL) return true;
+        const uint32_t u = (uint32_t)__builtin_amdgcn_readfirstlane(vc);
+        return ((allow[u >> 5] >> (u & 31u)) & 1u) != 0u;
     };
     auto frontier_push = [&](float dc, int32_t vc) {
         if (fn == FCAP) {  // drop what can never be expanded any more (the bound only shrinks)
@@ -435,7 +449,7 @@ __device__ __forceinline__ void q_body(const float *__restrict__ x, const float 
             nnd_wave_lds_sync();
             chunk_dists(nc);
             for (int j = 0; j < nc; j++) {  // pynndescent_.py:1826-1832
-                result_push(cd[j], cl[j]);
+                if (allowed(cl[j])) result_push(cd[j], cl[j]);
                 frontier_push(cd[j], cl[j]);
             }
             nnd_wave_lds_sync();
@@ -453,7 +467,7 @@ __device__ __forceinline__ void q_body(const float *__restrict__ x, const float 
             if (lane == 0) cl[0] = (int32_t)u;
             nnd_wave_lds_sync();
             chunk_dists(1);
-            result_push(cd[0], cl[0]);
+            if (allowed(cl[0])) result_push(cd[0], cl[0]);
             frontier_push(cd[0], cl[0]);
             nnd_wave_lds_sync();
         }
@@ -505,7 +519,7 @@ __device__ __forceinline__ void q_body(const float *__restrict__ x, const float 
                     const float dc = cd[j];
                     const int32_t vc = cl[j];
                     if (dc < bound && !in_result(vc)) {  // pynndescent_.py:1866-1874
-                        result_push(dc, vc);
+                        if (allowed(vc)) result_push(dc, vc);
                         frontier_push(dc, vc);
                         update_bound();
                     }
@@ -591,6 +605,39 @@ __global__ __launch_bounds__(256) void k_query_bool(const float *__restrict__ x,
     q_body<BIG, KU, false, false, true>(x, xn2, dp, d, metric, n, indptr, indices, hyper, offsets, children, tree_idx, n_nodes, queries, nq, k, epsilon, min_distance,
                                n_neighbors, seed, out_idx, out_dist, overflow, qlist, n_list, scratch, scratch_stride, codes, dcs, lut, cn2, k_out);
 }
+// the filtered siblings (FL): the same arguments and `allow`
+template <bool BIG, int KU, bool Q8 = false, bool RR = Q8>
+__global__ __launch_bounds__(256) void k_query_filtered(const float *__restrict__ x, const float *__restrict__ xn2, int dp, int d, int metric,
+                                               int64_t n, const int32_t *__restrict__ indptr, const int32_t *__restrict__ indices,
+                                               const float *__restrict__ hyper, const float *__restrict__ offsets,
+                                               const int32_t *__restrict__ children, const int32_t *__restrict__ tree_idx,
+                                               int64_t n_nodes, const float *__restrict__ queries, int64_t nq, int k, float epsilon,
+                                               float min_distance, int n_neighbors, uint32_t seed, int32_t *__restrict__ out_idx,
+                                               float *__restrict__ out_dist, uint8_t *__restrict__ overflow /* (nq) LDS tier: set when the query needs the big tier */,
+                                               const int32_t *__restrict__ qlist /* BIG: the queries of this batch */,
+                                               int n_list, unsigned char *__restrict__ scratch, size_t scratch_stride,
+                                               const uint8_t *__restrict__ codes, int dcs, const float *__restrict__ lut,
+                                               const float *__restrict__ cn2, int k_out,
+                                               const uint32_t *__restrict__ allow /* (n + 31) / 32 words */) {
+    q_body<BIG, KU, Q8, RR, false, true>(x, xn2, dp, d, metric, n, indptr, indices, hyper, offsets, children, tree_idx, n_nodes, queries, nq, k, epsilon, min_distance,
+                               n_neighbors, seed, out_idx, out_dist, overflow, qlist, n_list, scratch, scratch_stride, codes, dcs, lut, cn2, k_out, allow);
+}
+template <bool BIG, int KU>
+__global__ __launch_bounds__(256) void k_query_bool_filtered(const float *__restrict__ x, const float *__restrict__ xn2, int dp, int d, int metric,
+                                               int64_t n, const int32_t *__restrict__ indptr, const int32_t *__restrict__ indices,
+                                               const float *__restrict__ hyper, const float *__restrict__ offsets,
+                                               const int32_t *__restrict__ children, const int32_t *__restrict__ tree_idx,
+                                               int64_t n_nodes, const float *__restrict__ queries, int64_t nq, int k, float epsilon,
+                                               float min_distance, int n_neighbors, uint32_t seed, int32_t *__restrict__ out_idx,
+                                               float *__restrict__ out_dist, uint8_t *__restrict__ overflow /* (nq) LDS tier: set when the query needs the big tier */,
+                                               const int32_t *__restrict__ qlist /* BIG: the queries of this batch */,
+                                               int n_list, unsigned char *__restrict__ scratch, size_t scratch_stride,
+                                               const uint8_t *__restrict__ codes, int dcs, const float *__restrict__ lut,
+                                               const float *__restrict__ cn2, int k_out,
+                                               const uint32_t *__restrict__ allow /* (n + 31) / 32 words */) {
+    q_body<BIG, KU, false, false, true, true>(x, xn2, dp, d, metric, n, indptr, indices, hyper, offsets, children, tree_idx, n_nodes, queries, nq, k, epsilon, min_distance,
+                               n_neighbors, seed, out_idx, out_dist, overflow, qlist, n_list, scratch, scratch_stride, codes, dcs, lut, cn2, k_out, allow);
+}
 
 
 // the searcher's copy of the rows for the codes 2..5: the build's row transform (metric.h), one wave per row, in place --
@@ -673,6 +720,37 @@ __global__ __launch_bounds__(256) void k_quantize_u8(const float *__restrict__ x
             s = nnd_wave_sum_f32(s);
             if (lane == 0) cn2[r] = s;
         }
+    }
+}
+
+// ---- the filter's allow set (nnd_searcher_set_filter*) ----
+// an id list (original numbering) marked into a byte mask; an id outside 0 .. n - 1 raises the flag and is never written
+__global__ void k_filter_mark_ids(const int64_t *__restrict__ ids, int64_t m, int64_t n, uint8_t *__restrict__ mask,
+                                  unsigned long long *__restrict__ fstat) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    const int64_t id = ids[i];
+    if (id < 0 || id >= n) {
+        atomicOr(&fstat[1], 1ull);
+        return;
+    }
+    mask[id] = 1;
+}
+// the bitset over the searcher's numbering: bit i = mask[order[i]] != 0 (order nullptr: the identity), 64 rows of a wave packed by
+// one ballot into two words; fstat[0] counts the allowed rows.  A wave's first row is a multiple of 64, so no two waves share a word.
+__global__ __launch_bounds__(256) void k_filter_bitset(const uint8_t *__restrict__ mask, const int32_t *__restrict__ order, int64_t n,
+                                                       uint32_t *__restrict__ bits, unsigned long long *__restrict__ fstat) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    bool on = false;
+    if (i < n) {
+        const int64_t r = order ? (int64_t)order[i] : i;
+        on = r >= 0 && r < n && mask[r] != 0;
+    }
+    const unsigned long long m = __ballot(on);
+    if (nnd_lane() == 0 && i < n) {
+        bits[i >> 5] = (uint32_t)m;
+        if (i + 32 < n) bits[(i >> 5) + 1] = (uint32_t)(m >> 32);
+        if (m) atomicAdd(&fstat[0], (unsigned long long)__popcll(m));
     }
 }
 
@@ -862,6 +940,16 @@ static auto query_kernel(q_form form, int k) -> decltype(&k_query<BIG, 1>) {
         default: return k > 128 ? k_query<BIG, 4> : (k > 64 ? k_query<BIG, 2> : k_query<BIG, 1>);
     }
 }
+template <bool BIG>
+static auto query_kernel_filtered(q_form form, int k) -> decltype(&k_query_filtered<BIG, 1>) {
+    switch (form) {
+        case Q_FORM_U8: return k > 128 ? k_query_filtered<BIG, 4, true> : (k > 64 ? k_query_filtered<BIG, 2, true> : k_query_filtered<BIG, 1, true>);
+        case Q_FORM_BOOL: return k > 128 ? k_query_bool_filtered<BIG, 4> : (k > 64 ? k_query_bool_filtered<BIG, 2> : k_query_bool_filtered<BIG, 1>);
+        case Q_FORM_RERANK:
+            return k > 128 ? k_query_filtered<BIG, 4, false, true> : (k > 64 ? k_query_filtered<BIG, 2, false, true> : k_query_filtered<BIG, 1, false, true>);
+        default: return k > 128 ? k_query_filtered<BIG, 4> : (k > 64 ? k_query_filtered<BIG, 2> : k_query_filtered<BIG, 1>);
+    }
+}
 
 // every query entry point: the walk keeps k results (the float rows) or k = search_k results and reranks them to k_out
 // (Q_FORM_U8: the walk on the code rows; Q_FORM_RERANK: on the float rows); out_idx / out_dist are (nq, k_out)
@@ -871,6 +959,9 @@ static int searcher_run(nnd_searcher_s *s, const float *queries, int64_t nq, int
     if (form == Q_FORM_FLOAT && nnd_metric_bool(s->metric)) form = Q_FORM_BOOL;
     auto kq_lds = query_kernel<false>(form, k);
     auto kq_big = query_kernel<true>(form, k);
+    auto fq_lds = query_kernel_filtered<false>(form, k);  // launched instead while a filter is set (nnd_searcher_set_filter*)
+    auto fq_big = query_kernel_filtered<true>(form, k);
+    const uint32_t *allow = s->filter_on ? s->allow : nullptr;
     if (nq <= 0) return 0;
     if (nq >= (int64_t)0x7FFFFFF0) { s->set_error("nnd_searcher_query: too many queries in one call"); return 1; }
     S_HIP(hipSetDevice(s->device));
@@ -894,13 +985,19 @@ static int searcher_run(nnd_searcher_s *s, const float *queries, int64_t nq, int
         if (!dq || !dd || !di || !dov) { s->set_error("nnd_searcher_query: out of device memory"); rc = 1; break; }
         if (!on_device && hipMemcpyAsync(dq, queries, sizeof(float) * (size_t)nq * s->d, hipMemcpyHostToDevice, st) != hipSuccess) { s->set_error("H2D of the queries failed"); rc = 1; break; }
         if (!s->force_big) {
-            if (smem > 64 * 1024 && hipFuncSetAttribute((const void *)kq_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) {
+            if (smem > 64 * 1024 && hipFuncSetAttribute(allow ? (const void *)fq_lds : (const void *)kq_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) {
                 s->set_error("nnd_searcher_query: rows of %d floats need %zu bytes of LDS per workgroup", s->d, smem); rc = 1; break;
             }
-            hipLaunchKernelGGL(kq_lds, dim3((unsigned)((nq + 3) / 4)), dim3(256), smem, st, s->x, s->xn2, s->dp, s->d, s->metric, s->n,
-                               s->indptr, s->indices, s->hyper, s->offsets, s->children, s->tree_idx, s->n_nodes, dq, nq, k, epsilon,
-                               s->min_distance, s->n_neighbors, s->seed, di, dd, dov, (const int32_t *)nullptr, 0, (unsigned char *)nullptr, (size_t)0,
-                               (const uint8_t *)s->codes, s->dcs, (const float *)s->lut, (const float *)s->cn2, k_out);
+            if (allow)
+                hipLaunchKernelGGL(fq_lds, dim3((unsigned)((nq + 3) / 4)), dim3(256), smem, st, s->x, s->xn2, s->dp, s->d, s->metric, s->n,
+                                   s->indptr, s->indices, s->hyper, s->offsets, s->children, s->tree_idx, s->n_nodes, dq, nq, k, epsilon,
+                                   s->min_distance, s->n_neighbors, s->seed, di, dd, dov, (const int32_t *)nullptr, 0, (unsigned char *)nullptr, (size_t)0,
+                                   (const uint8_t *)s->codes, s->dcs, (const float *)s->lut, (const float *)s->cn2, k_out, allow);
+            else
+                hipLaunchKernelGGL(kq_lds, dim3((unsigned)((nq + 3) / 4)), dim3(256), smem, st, s->x, s->xn2, s->dp, s->d, s->metric, s->n,
+                                   s->indptr, s->indices, s->hyper, s->offsets, s->children, s->tree_idx, s->n_nodes, dq, nq, k, epsilon,
+                                   s->min_distance, s->n_neighbors, s->seed, di, dd, dov, (const int32_t *)nullptr, 0, (unsigned char *)nullptr, (size_t)0,
+                                   (const uint8_t *)s->codes, s->dcs, (const float *)s->lut, (const float *)s->cn2, k_out);
             if (hipGetLastError() != hipSuccess) { s->set_error("k_query launch failed"); rc = 1; break; }
             if (hipMemcpyAsync(hov.data(), dov, (size_t)nq, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
                 s->set_error("nnd_searcher_query: kernel or D2H failed: %s", hipGetErrorString(hipGetLastError())); rc = 1; break;
@@ -922,10 +1019,16 @@ static int searcher_run(nnd_searcher_s *s, const float *queries, int64_t nq, int
             if (hipMemcpyAsync(dlist, again.data(), sizeof(int32_t) * again.size(), hipMemcpyHostToDevice, st) != hipSuccess) { s->set_error("H2D of the query list failed"); rc = 1; break; }
             for (size_t b0 = 0; b0 < again.size() && !rc; b0 += batch) {
                 const int nb = (int)(again.size() - b0 < batch ? again.size() - b0 : batch);
-                hipLaunchKernelGGL(kq_big, dim3((unsigned)((nb + 3) / 4)), dim3(256), 4 * per_wave_big + lut_bytes, st, s->x, s->xn2, s->dp, s->d,
-                                   s->metric, s->n, s->indptr, s->indices, s->hyper, s->offsets, s->children, s->tree_idx, s->n_nodes, dq, nq, k, epsilon,
-                                   s->min_distance, s->n_neighbors, s->seed, di, dd, (uint8_t *)nullptr, (const int32_t *)(dlist + b0), nb, scratch, stride,
-                                   (const uint8_t *)s->codes, s->dcs, (const float *)s->lut, (const float *)s->cn2, k_out);
+                if (allow)
+                    hipLaunchKernelGGL(fq_big, dim3((unsigned)((nb + 3) / 4)), dim3(256), 4 * per_wave_big + lut_bytes, st, s->x, s->xn2, s->dp, s->d,
+                                       s->metric, s->n, s->indptr, s->indices, s->hyper, s->offsets, s->children, s->tree_idx, s->n_nodes, dq, nq, k, epsilon,
+                                       s->min_distance, s->n_neighbors, s->seed, di, dd, (uint8_t *)nullptr, (const int32_t *)(dlist + b0), nb, scratch, stride,
+                                       (const uint8_t *)s->codes, s->dcs, (const float *)s->lut, (const float *)s->cn2, k_out, allow);
+                else
+                    hipLaunchKernelGGL(kq_big, dim3((unsigned)((nb + 3) / 4)), dim3(256), 4 * per_wave_big + lut_bytes, st, s->x, s->xn2, s->dp, s->d,
+                                       s->metric, s->n, s->indptr, s->indices, s->hyper, s->offsets, s->children, s->tree_idx, s->n_nodes, dq, nq, k, epsilon,
+                                       s->min_distance, s->n_neighbors, s->seed, di, dd, (uint8_t *)nullptr, (const int32_t *)(dlist + b0), nb, scratch, stride,
+                                       (const uint8_t *)s->codes, s->dcs, (const float *)s->lut, (const float *)s->cn2, k_out);
                 if (hipGetLastError() != hipSuccess) { s->set_error("k_query (global-memory tier) launch failed"); rc = 1; }
             }
             if (rc) break;
@@ -1043,6 +1146,74 @@ extern "C" int32_t nnd_searcher_query_rerank(nnd_searcher_t s, const float *quer
         return 1;
     }
     return searcher_run(s, queries, nq, search_k, k, epsilon, Q_FORM_RERANK, out_idx, out_dist);
+}
+
+// ---- the filter (include/pynnd_amd.h): the allow bitset, built on `st` from a mask or an id list in device memory ----
+static int searcher_build_filter(nnd_searcher_s *s, const char *who, const void *filter_dev, int64_t count, int32_t kind, const int32_t *order_dev,
+                                 hipStream_t st, nnd_scratch &tmp, int64_t *n_allowed) {
+    s->filter_on = false;  // a failed call leaves the searcher unfiltered
+    if (!s->allow) S_ALLOC(&s->allow, (size_t)((s->n + 31) / 32));
+    if (!s->fstat) S_ALLOC(&s->fstat, 2);
+    S_HIP(hipMemsetAsync(s->fstat, 0, 2 * sizeof(unsigned long long), st));
+    const uint8_t *mask = (const uint8_t *)filter_dev;
+    if (kind == NND_FILTER_IDS) {
+        uint8_t *marked = tmp.get<uint8_t>(s, (size_t)s->n);
+        if (!marked) return 1;
+        S_HIP(hipMemsetAsync(marked, 0, (size_t)s->n, st));
+        if (count > 0)
+            hipLaunchKernelGGL(k_filter_mark_ids, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, (const int64_t *)filter_dev, count, s->n, marked,
+                               s->fstat);
+        mask = marked;
+    }
+    hipLaunchKernelGGL(k_filter_bitset, dim3((unsigned)((s->n + 255) / 256)), dim3(256), 0, st, mask, order_dev, s->n, s->allow, s->fstat);
+    S_HIP(hipGetLastError());
+    unsigned long long stat[2] = {0, 0};
+    S_HIP(hipMemcpyAsync(stat, s->fstat, sizeof(stat), hipMemcpyDeviceToHost, st));
+    S_HIP(hipStreamSynchronize(st));
+    if (stat[1]) {
+        s->set_error("%s: an id of the filter is outside 0 .. %lld", who, (long long)(s->n - 1));
+        return 2;
+    }
+    if (n_allowed) *n_allowed = (int64_t)stat[0];
+    s->filter_on = true;
+    return 0;
+}
+static int filter_args(nnd_searcher_s *s, const char *who, const void *filter, int64_t count, int32_t kind) {
+    if (kind != NND_FILTER_MASK && kind != NND_FILTER_IDS) { s->set_error("%s: kind must be NND_FILTER_MASK or NND_FILTER_IDS (got %d)", who, kind); return 1; }
+    if (count < 0 || (count > 0 && !filter)) { s->set_error("%s: filter missing", who); return 1; }
+    if (kind == NND_FILTER_MASK && count != s->n) { s->set_error("%s: a mask has one byte per row (%lld), got %lld", who, (long long)s->n, (long long)count); return 1; }
+    if (count >= ((int64_t)1 << 40)) { s->set_error("%s: too many ids", who); return 1; }
+    return 0;
+}
+extern "C" int32_t nnd_searcher_set_filter(nnd_searcher_t s, const void *filter, int64_t count, int32_t kind, const int32_t *order, int64_t *n_allowed) {
+    if (!s) { snprintf(g_serr, sizeof(g_serr), "nnd_searcher_set_filter: null searcher"); return 1; }
+    if (filter_args(s, "nnd_searcher_set_filter", filter, count, kind)) return 1;
+    S_HIP(hipSetDevice(s->device));
+    nnd_scratch tmp;  // released on return, behind the synchronise of searcher_build_filter
+    const size_t bytes = (size_t)count * (kind == NND_FILTER_IDS ? sizeof(int64_t) : 1);
+    unsigned char *dfilter = tmp.get<unsigned char>(s, bytes);
+    int32_t *dorder = order ? tmp.get<int32_t>(s, (size_t)s->n) : nullptr;
+    if (!dfilter || (order && !dorder)) return 1;
+    if (bytes) S_HIP(hipMemcpyAsync(dfilter, filter, bytes, hipMemcpyHostToDevice, s->stream));
+    if (order) S_HIP(hipMemcpyAsync(dorder, order, sizeof(int32_t) * (size_t)s->n, hipMemcpyHostToDevice, s->stream));
+    const int rc = searcher_build_filter(s, "nnd_searcher_set_filter", dfilter, count, kind, dorder, s->stream, tmp, n_allowed);
+    if (rc) (void)hipStreamSynchronize(s->stream);  // nothing queued still reads tmp
+    return rc;
+}
+extern "C" int32_t nnd_searcher_set_filter_device(nnd_searcher_t s, const void *filter_dev, int64_t count, int32_t kind, const int32_t *order_dev,
+                                                  int64_t *n_allowed, void *hip_stream) {
+    if (!s) { snprintf(g_serr, sizeof(g_serr), "nnd_searcher_set_filter_device: null searcher"); return 1; }
+    if (filter_args(s, "nnd_searcher_set_filter_device", filter_dev, count, kind)) return 1;
+    S_HIP(hipSetDevice(s->device));
+    nnd_scratch tmp;
+    const int rc = searcher_build_filter(s, "nnd_searcher_set_filter_device", filter_dev, count, kind, order_dev, (hipStream_t)hip_stream, tmp, n_allowed);
+    if (rc) (void)hipStreamSynchronize((hipStream_t)hip_stream);
+    return rc;
+}
+extern "C" int32_t nnd_searcher_clear_filter(nnd_searcher_t s) {
+    if (!s) { snprintf(g_serr, sizeof(g_serr), "nnd_searcher_clear_filter: null searcher"); return 1; }
+    s->filter_on = false;  // the bitset stays allocated for the next filter
+    return 0;
 }
 
 // ---- the same three entries for queries and results that live on the device (include/pynnd_amd.h) ----

@@ -28,7 +28,7 @@ from warnings import warn
 import numpy as np
 from sklearn.utils import check_array, check_random_state
 
-from . import _capi, build, device_arrays, linear_map
+from . import _capi, build, device_arrays, filtered, linear_map
 # Every name below was defined here once and is read here still (tests, tools/, and pickles, which name
 # pynndescent_amd.nndescent.correct_alternative_*): the same objects as in their home modules.  Two are replaced by tests and
 # are therefore CALLED through their home module alone -- ``build.ts()``, ``device_arrays._torch()``.
@@ -818,16 +818,64 @@ class NNDescent:
             searcher.vertex_order_device = order  # what _query_device maps the answers' ids through
         return searcher
 
-    def query(self, query_data, k=10, epsilon=0.1, proxy_beam_size=4):
+    def query(self, query_data, k=10, epsilon=0.1, proxy_beam_size=4, filter=None, filter_mode="auto"):
         """``NNDescent.query`` (pynndescent_.py:2275-2379) on the GPU: one wave per query (csrc/query.hip).
         Returns (indices (n_queries, k) in the ORIGINAL numbering, true distances (n_queries, k)).  A device array
         ``query_data`` (float32 / float16 / bfloat16 / float64, on the index's device) is answered with device tensors: the
         queries are converted, the ids mapped back and the distances corrected on the device, on torch's current stream;
-        the index may have been built from host or device data alike, and a host ``query_data`` returns numpy on both."""
+        the index may have been built from host or device data alike, and a host ``query_data`` returns numpy on both.
+
+        ``filter`` (beyond the reference; filtered.py): the rows that may be returned, one set for all queries of the call, in
+        the ORIGINAL numbering -- a 1-D boolean mask of n rows (True: allowed) or a 1-D integer array of row ids, numpy or a
+        tensor on the index's device, whichever side the queries are on.  Places that no allowed row fills hold (-1, inf).
+        ``filter_mode``: "walk" -- the graph walk in which a vertex enters the result list only if it is allowed (it is still
+        traversed, so bound and stop rule are those of the walk relative to the allowed rows); "exact" -- brute force over a
+        compact copy of the allowed rows, by (float64 distance, id) as ``exact_knn`` (not for proxy_inner_product); "auto" --
+        "exact" for at most ``filtered.FILTER_EXACT_MAX_ROWS`` allowed rows when the metric has an exact search, else "walk".
+        After a filtered call ``self.last_filter`` says what ran: ``{"mode": "walk" | "exact" | "empty", "n_allowed": rows}``
+        ("empty": no row allowed, answered without a launch).  Soft deletion: keep a mask of the live rows and pass it."""
         if k > 256:
             raise NotImplementedError("pynndescent_amd answers queries with k <= 256; use index.to_reference() for k = %d" % k)
         _check_quantization(self.quantization, self.metric)
         m = _metric_of(self.metric)
+        if filter_mode not in filtered.FILTER_MODES:
+            raise ValueError("filter_mode must be one of %s (got %r)" % (", ".join(filtered.FILTER_MODES), filter_mode))
+        if filter is not None:
+            return self._query_filtered(query_data, m, k, epsilon, proxy_beam_size, filter, filter_mode)
+        return self._query_walk(query_data, m, k, epsilon, proxy_beam_size)
+
+    def _query_filtered(self, query_data, m, k, epsilon, proxy_beam_size, filter, filter_mode):
+        """``query`` with a filter: everything is validated before any device work, then the path ``filtered.choose_mode`` names."""
+        if self.quantization is not None or m.proxy:
+            _proxy_search_k(k, proxy_beam_size)
+        f = filtered.check_filter(filter, int(self._raw_data_n()), self.device)
+        if tuple(_shape_of(query_data))[1:] != (self.dim,):
+            raise ValueError("query_data must have shape (n_queries, %d)" % self.dim)
+        mode = filtered.choose_mode(filter_mode, f.n_allowed, self.metric)
+        self.last_filter = {"mode": mode, "n_allowed": f.n_allowed}
+        if mode == "exact":
+            _no_exact_for_proxy(self.metric, m, 'NNDescent.query(filter_mode="exact")')
+        if mode == "empty":
+            return filtered.empty_answer(query_data, k)
+        if not self._prepared:
+            self.prepare()
+        if mode == "exact":
+            return filtered.query_exact(self, query_data, k, f)
+        if getattr(self, "_searcher", None) is None or (self.quantization is not None and not self._searcher.has_codes):
+            self.prepare()
+        filtered.set_walk_filter(self, f)
+        try:
+            return self._query_walk(query_data, m, k, epsilon, proxy_beam_size)
+        finally:
+            self._searcher.clear_filter()
+
+    def _raw_data_n(self):
+        """The number of rows, without fetching a host mirror."""
+        d = self.__dict__
+        return d["_device_data"].shape[0] if "_device_data" in d else self._raw_data.shape[0]
+
+    def _query_walk(self, query_data, m, k, epsilon, proxy_beam_size):
+        """The graph walk of ``query`` (with the searcher's filter, when ``_query_filtered`` has set one)."""
         search_k = k
         if self.quantization is not None or m.proxy:  # pynndescent_.py:2309-2312
             search_k = _proxy_search_k(k, proxy_beam_size)
