@@ -224,6 +224,14 @@ int32_t nnd_set_data_device_typed(nnd_handle_t h, const void *x_dev, int32_t dty
  * it; dot's rows where the caller keeps the normalised copy itself.  Asynchronous: nothing is waited for. */
 int32_t nnd_device_rows_f32(int32_t device, void *hip_stream, const void *src_dev, int32_t dtype, int64_t n, int32_t dim,
                             int32_t normalize, float *dst_dev);
+/* Sparse input: the CSR matrix at indptr_dev (n + 1 entries) / indices_dev / values_dev (float32), all on `device`, written
+ * dense into the (n, dim) float32 buffer dst_dev (row stride dim, any dim >= 1; aligned to a float).  indptr_width and
+ * indices_width are the byte widths of the two index arrays, 4 (int32) or 8 (int64) each, as scipy hands them out.  The matrix
+ * is CANONICAL (column indices ascending within a row, no duplicates; the caller sees to it): every element of dst is then
+ * written exactly once -- an explicitly stored zero like any other value -- and dst is never read.  indices_dev / values_dev may be
+ * NULL for a matrix without a stored entry.  Queued on `hip_stream` (NULL: the device's default stream): nothing is waited for. */
+int32_t nnd_device_csr_rows(int32_t device, void *hip_stream, const void *indptr_dev, int32_t indptr_width, const void *indices_dev,
+                            int32_t indices_width, const float *values_dev, int64_t n, int32_t dim, float *dst_dev);
 /* Corrections of the kernels' distances (the reference's distance_correction, pynndescent_.py:1271-1298) on the device, without
  * a handle: a graph is corrected when NNDescent.neighbor_graph is read, long after its builder is gone.  `count` float32 values
  * at in_dev -> out_dev, asynchronous on `hip_stream` of `device`.  Unfilled entries (+inf) come out as the host functions map

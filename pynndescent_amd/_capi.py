@@ -211,6 +211,8 @@ _SIGNATURES = [
     ("nnd_set_data_device", C.c_int32, [_H, C.c_void_p]),
     ("nnd_set_data_device_typed", C.c_int32, [_H, C.c_void_p, C.c_int32]),
     ("nnd_device_rows_f32", C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
+    ("nnd_device_csr_rows", C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32,
+                                        C.c_void_p]),
     ("nnd_device_correct", C.c_int32, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64]),
     ("nnd_device_linear_rows", C.c_int32, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     ("nnd_linear_rows_host", C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
@@ -960,6 +962,17 @@ def device_rows_f32(device, stream_ptr, src_ptr, dtype, n, dim, normalize, dst_p
     lib = load_library()
     if lib.nnd_device_rows_f32(int(device), C.c_void_p(int(stream_ptr)) if stream_ptr else None, C.c_void_p(int(src_ptr)), int(dtype),
                                int(n), int(dim), 1 if normalize else 0, C.c_void_p(int(dst_ptr))) != 0:
+        raise NNDError(lib.nnd_last_global_error().decode())
+
+
+def device_csr_rows(device, stream_ptr, indptr_ptr, indptr_width, indices_ptr, indices_width, values_ptr, n, dim, dst_ptr):
+    """The canonical CSR matrix at the device addresses ``indptr_ptr`` (n + 1 entries of ``indptr_width`` bytes, 4 or 8) /
+    ``indices_ptr`` (``indices_width`` bytes each) / ``values_ptr`` (float32) -> its dense (n, dim) float32 rows at ``dst_ptr``
+    (csrc/sparse.hip); queued on ``stream_ptr`` of ``device``, nothing is waited for."""
+    lib = load_library()
+    dev = lambda p: C.c_void_p(int(p)) if p else None  # noqa: E731
+    if lib.nnd_device_csr_rows(int(device), dev(stream_ptr), dev(indptr_ptr), int(indptr_width), dev(indices_ptr), int(indices_width),
+                               dev(values_ptr), int(n), int(dim), dev(dst_ptr)) != 0:
         raise NNDError(lib.nnd_last_global_error().decode())
 
 

@@ -2,10 +2,10 @@
 """
 import numpy as np
 
-from . import _capi, device_arrays, linear_map
+from . import _capi, device_arrays, linear_map, sparse_input
 from .build import _check_array_no_scan, _raise_if_nonfinite
 from .device_arrays import (_check_device_array, _device_corrected, _DeviceLinear, _DeviceRowsView, _dtype_name, _ids_to_host,
-                            _is_device_array, _OnTorchStream, _rows_to_host)
+                            _is_device_array, _OnTorchStream, _rows_to_host, _shape_of)
 from .metrics import (_METRICS, _NEGATIVE_HELLINGER, _linear_map_of, _metric_record, _no_exact_for_proxy,
                       _raise_if_negative_host)
 
@@ -45,7 +45,31 @@ def _exact_linear_rows(metric, m, metric_kwds, data, queries, device):
     return _capi.linear_rows_host(lin.kind, lin.a, lin.shift, data, device=device), queries
 
 
-def exact_knn(data, queries=None, k=10, metric="euclidean", rows=None, device=0, return_stats=False, metric_kwds=None):
+def _exact_knn_sparse(data, queries, k, metric, m, rows, device, return_stats, metric_kwds):
+    """``exact_knn`` with a ``scipy.sparse`` ``data`` and / or ``queries``: the metric rule of sparse input, then whatever is
+    sparse is uploaded as CSR and made dense on the device (sparse_input.py), host ``data`` given with sparse queries is
+    uploaded, and the device route searches.  Scipy or numpy ``data`` gets numpy answers with the host's correction (the bits of
+    the host route); a tensor ``data`` gets tensors."""
+    sparse_input.check_sparse_metric(metric)
+    if m.linear:  # minkowski: metric_kwds under the dense rule (p = 2 alone), then the euclidean path itself
+        _linear_map_of(metric, m, metric_kwds, data.shape[1])
+        metric, m = "euclidean", _METRICS["euclidean"]
+    host_answers = not _is_device_array(data)
+    if queries is not None and tuple(_shape_of(queries))[1:] != (data.shape[1],):
+        raise ValueError("queries must have shape (n_queries, %d)" % data.shape[1])
+    if sparse_input.is_sparse(data):
+        data = sparse_input.dense_rows_on_device(sparse_input.canonical_csr(data), device, check_fit=True)
+    elif host_answers:
+        torch = device_arrays._torch()
+        data = torch.from_numpy(_check_array_no_scan(data)).to(torch.device("cuda", int(device)))
+    ordinal = getattr(data.device, "index", None) or 0
+    if sparse_input.is_sparse(queries):
+        queries = sparse_input.query_rows(queries, data.shape[1], ordinal, what="queries")
+    return _exact_knn_device(data, queries, k, metric, m, rows, ordinal, return_stats, host_answers=host_answers)
+
+
+def exact_knn(data, queries=None, k=10, metric="euclidean", rows=None, device=0, return_stats=False, metric_kwds=None,
+              _host_answers=False):
     """Exact ``k`` nearest neighbours by brute force on the GPU (csrc/exact.hip): of every row of ``data`` (self included), of the
     rows ``rows`` of it, or of the external ``queries``.  Returns ``(indices int32 (m, k), distances float32-precision (m, k))``
     in the metric's own space (the correction ``NNDescent.neighbor_graph`` applies), rows ascending, ties to the smaller id;
@@ -62,7 +86,11 @@ def exact_knn(data, queries=None, k=10, metric="euclidean", rows=None, device=0,
     ``metric_kwds``: the arguments of seuclidean / wminkowski (p = 2) / mahalanobis / minkowski (p = 2), read positionally as by
     ``NNDescent``; every other metric ignores it.  For these metrics the answers are exact in this sense: (float64 distance, id)
     on the float32 transformed rows -- the rows ``A (x - c)`` the device computes once (csrc/linear.hip), on which the search is
-    the euclidean one."""
+    the euclidean one.
+
+    ``data`` and / or ``queries`` may be ``scipy.sparse`` matrices, for the metrics ``NNDescent`` takes with sparse input: they
+    are made dense on the device (sparse_input.py) and the device route searches; the answers are numpy arrays, those of the dense
+    call bit for bit, unless ``data`` is a tensor."""
     if queries is not None and rows is not None:
         raise ValueError("exact_knn takes `queries` (external points) or `rows` (ids of data rows), not both")
     k = int(k)
@@ -70,11 +98,13 @@ def exact_knn(data, queries=None, k=10, metric="euclidean", rows=None, device=0,
         raise NotImplementedError("pynndescent_amd.exact_knn keeps at most k <= 256 neighbours per row (got k = %d)" % k)
     m = _metric_record(metric)
     _no_exact_for_proxy(metric, m, "exact_knn")
+    if sparse_input.is_sparse(data) or sparse_input.is_sparse(queries):
+        return _exact_knn_sparse(data, queries, k, metric, m, rows, device, return_stats, metric_kwds)
     if m.linear:  # (metric_kwds is validated in there, before any device work)
         data, queries = _exact_linear_rows(metric, m, metric_kwds, data, queries, device)
         metric, m = "euclidean", _METRICS["euclidean"]
     if _is_device_array(data):
-        return _exact_knn_device(data, queries, k, metric, m, rows, device, return_stats)
+        return _exact_knn_device(data, queries, k, metric, m, rows, device, return_stats, host_answers=_host_answers)
     queries, rows = _rows_to_host(queries), _ids_to_host(rows)  # (the results live where the data lives)
     data = _check_array_no_scan(data)
     n = data.shape[0]
@@ -115,11 +145,13 @@ def exact_knn(data, queries=None, k=10, metric="euclidean", rows=None, device=0,
     return (idx, dist, stats) if return_stats else (idx, dist)
 
 
-def _exact_knn_device(data, queries, k, metric, m, rows, device, return_stats):
+def _exact_knn_device(data, queries, k, metric, m, rows, device, return_stats, host_answers=False):
     """``exact_knn`` for a device array ``data`` (``k``, the metric and queries-or-rows are checked already): an auxiliary handle
     bound to the tensor on torch's current stream, the device entries of csrc/exact.hip, the answers corrected on the device.
     ``rows``: a host array or a tensor of ids (range-checked on the host), or an int32 tensor on the data's device that the
-    caller has checked (``NNDescent._recall_device``).  What crosses the bus: the row ids, host queries, and scalars."""
+    caller has checked (``NNDescent._recall_device``).  What crosses the bus: the row ids, host queries, and scalars.
+    ``host_answers``: the ids and the kernels' distances are brought to the host and corrected there, as the host route does (the
+    same bits; the device's correction agrees with numpy's within rounding only) -- for callers whose input came from the host."""
     data, dtype, ordinal = _check_device_array(data, device)
     n, dim = int(data.shape[0]), int(data.shape[1])
     if k < 1 or k > n:
@@ -174,5 +206,8 @@ def _exact_knn_device(data, queries, k, metric, m, rows, device, return_stats):
         finally:
             builder.close()
             stream.done()
-        dist = _device_corrected(torch, dist, m, ordinal)
+        if host_answers:
+            idx, dist = np.ascontiguousarray(idx.cpu().numpy()), m.correction(np.ascontiguousarray(dist.cpu().numpy()))
+        else:
+            dist = _device_corrected(torch, dist, m, ordinal)
     return (idx, dist, stats) if return_stats else (idx, dist)

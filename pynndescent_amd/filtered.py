@@ -106,10 +106,12 @@ def _allowed_ids(f):
     return np.flatnonzero(f.values).astype(np.int64) if f.kind == "mask" else np.unique(f.values)
 
 
-def query_exact(index, query_data, k, f):
+def query_exact(index, query_data, k, f, host_answers=False):
     """``filter_mode="exact"``: the allowed rows of the rows the index works on, gathered in ascending id order into a compact
     copy; ``exact_knn`` answers the queries on it -- by (float64 distance, id), the compact id order being the original one --
-    and the ids are mapped back.  Fewer allowed rows than ``k`` leave (-1, inf).  Results live where ``query_data`` lives."""
+    and the ids are mapped back.  Fewer allowed rows than ``k`` leave (-1, inf).  Results live where ``query_data`` lives;
+    ``host_answers``: the queries are a tensor made from a host batch (a sparse one), and the answers are numpy arrays corrected
+    on the host, the bits of the host route."""
     d = index.__dict__
     on_device = _is_device_array(query_data)
     ids = _allowed_ids(f)
@@ -127,7 +129,10 @@ def query_exact(index, query_data, k, f):
         order = np.asarray(index._vertex_order)
         position = np.empty(order.shape[0], np.int64)
         position[order] = np.arange(order.shape[0])
-        compact = np.ascontiguousarray(index._work_rows()[position[ids_host()]])
+        if d.get("_is_sparse"):  # (a sparse index without its tensor, e.g. unpickled: the allowed rows alone are made dense)
+            compact = np.ascontiguousarray(index._raw_data[position[ids_host()]].toarray(), dtype=np.float32)
+        else:
+            compact = np.ascontiguousarray(index._work_rows()[position[ids_host()]])
         if on_device:
             compact = device_arrays._torch().from_numpy(compact).to(query_data.device)
     if lin is not None:  # the queries through the index's own (A, c); the search on the transformed rows is euclidean
@@ -140,7 +145,8 @@ def query_exact(index, query_data, k, f):
             query_data = _capi.linear_rows_host(lin.kind, lin.a, lin.shift, np.asarray(query_data).astype(np.float32, order="C"),
                                                 device=index.device)
     kk = min(int(k), int(f.n_allowed))
-    idx, dist = exact_knn(compact, queries=query_data, k=kk, metric=index._kernel_metric(), device=index.device)
+    idx, dist = exact_knn(compact, queries=query_data, k=kk, metric=index._kernel_metric(), device=index.device,
+                          _host_answers=host_answers)
     if _is_device_array(idx):
         torch = device_arrays._torch()
         idx = ids_on(idx.device)[idx.long()].to(torch.int32)

@@ -15,7 +15,10 @@ proxy_inner_product (graph and walk on the reference's proxy distance, queries r
 metrics that are euclidean after a fixed linear map of the rows, with ``metric_kwds`` read positionally as the reference reads
 it: seuclidean / standardised_euclidean ``(V,)``, wminkowski / weighted_minkowski ``(w,)`` or ``(w, 2)``, mahalanobis ``(VI,)``
 and minkowski ``()`` or ``(2,)`` (linear_map.py; the device transforms every row once, csrc/linear.hip).
-Out of scope: sparse input, every other metric, ``n_neighbors`` above 256 or
+Sparse input (any ``scipy.sparse`` matrix, for the metrics the reference's sparse path has too) is uploaded as CSR and made dense
+on the device (sparse_input.py, csrc/sparse.hip); from there it is a device-resident index whose ``_raw_data`` is the CSR matrix.
+Out of scope: sparse input whose dense rows do not fit the device or with ``n_devices`` > 1, torch sparse tensors, every other
+metric, ``n_neighbors`` above 256 or
 ``max_candidates`` above 128 (``query``: more than 256 results per query).  Those raise ``NotImplementedError`` naming the reference entry point to use
 instead; ``pynndescent_amd.make_index`` hands such inputs to ``pynndescent.NNDescent`` when it is importable.
 
@@ -28,7 +31,7 @@ from warnings import warn
 import numpy as np
 from sklearn.utils import check_array, check_random_state
 
-from . import _capi, build, device_arrays, filtered, linear_map
+from . import _capi, build, device_arrays, filtered, linear_map, sparse_input
 # Every name below was defined here once and is read here still (tests, tools/, and pickles, which name
 # pynndescent_amd.nndescent.correct_alternative_*): the same objects as in their home modules.  Two are replaced by tests and
 # are therefore CALLED through their home module alone -- ``build.ts()``, ``device_arrays._torch()``.
@@ -86,11 +89,14 @@ def uint8_codebook(raw, random_state):
 
 def _updates_on_device(index, xs_fresh, xs_updated):
     """Whether ``update()`` of ``index`` stays on the device (``NNDescent._update_device``): the index holds its rows and its graph
-    on one GPU, and at least one of the incoming arrays is a device array.  Reads ``__dict__`` only."""
+    on one GPU, and at least one of the incoming arrays is a device array or a ``scipy.sparse`` matrix (made dense on the device),
+    or the index was built from sparse input.  Reads ``__dict__`` only."""
     d = index.__dict__
     if "_device_data" not in d or "_device_graph" not in d or int(d.get("n_devices", 1)) != 1:
         return False
-    return _is_device_array(xs_fresh) or _is_device_array(xs_updated)
+    if d.get("_is_sparse"):  # (a sparse index has no host rows to fall back on: every update is assembled on the device)
+        return True
+    return any(_is_device_array(a) or sparse_input.is_sparse(a) for a in (xs_fresh, xs_updated))
 
 
 def _prepares_on_device(index):
@@ -185,7 +191,13 @@ class NNDescent:
         (``nnd_init_from_graph_device``); in every other combination they are brought to the host.  Out of scope: the hub
         tree's FlatTree assembly on the device; producers other than torch (``__cuda_array_interface__``, DLPack); and a sharded
         build from device memory -- with ``n_devices`` > 1 the rows are brought to the host first and the index is a host index,
-        as for host input."""
+        as for host input.
+
+        ``data`` may be a ``scipy.sparse`` matrix or array (sparse_input.py): made canonical float32 CSR on the host, uploaded as
+        CSR and written dense on ``device`` by one kernel, after which it is the float32 tensor of the paragraph above in every
+        respect but two -- ``_raw_data`` is the CSR matrix (``_is_sparse`` is True; no dense host mirror is ever made), and the
+        answers are numpy arrays.  ``NotImplementedError`` when the dense rows and their prepared copy do not fit the free device
+        memory, or with ``n_devices`` > 1; the reference's ``ValueError`` for a metric its sparse path lacks."""
         dev_checked = None
         if _is_device_array(data):  # dtype, shape and device first: before any device work, and before the shape is read
             dev_checked = _check_device_array(data, device)
@@ -237,17 +249,16 @@ class NNDescent:
         m = _metric_record(metric)
         lin = _linear_map_of(metric, m, metric_kwds, data.shape[1])  # (host only: every error of metric_kwds comes first)
         _refuse_uint8_and_sharding(metric, m, quantization, self.n_devices)
-        try:
-            import scipy.sparse
-
-            if scipy.sparse.issparse(data):
-                raise NotImplementedError(
-                    "sparse input is out of scope for pynndescent_amd; use pynndescent.NNDescent (sparse_nndescent)"
-                )
-        except ImportError:  # pragma: no cover
-            pass
+        sparse = sparse_input.is_sparse(data)
+        if sparse:  # the metric rule of sparse input, decided before any device work
+            sparse_input.check_sparse_metric(metric, self.n_devices)
 
         _check_supported_sizes(n_neighbors, max_candidates, init_graph)
+        csr = None
+        if sparse:  # the CSR arrays go up and are made dense there: from here on the input is a float32 device array
+            csr = sparse_input.canonical_csr(data)
+            data = sparse_input.dense_rows_on_device(csr, device, check_fit=True)
+            dev_checked = _check_device_array(data, device)
         # pynndescent_.py:1054 check_array(data, dtype=np.float32, order="C") -- minus its single-core scan for NaN / inf
         # (24 ms at 1 M x 128): the prep kernel looks at every value anyway and raises a flag; _raise_if_nonfinite then
         # lets sklearn produce the reference's own error
@@ -266,6 +277,8 @@ class NNDescent:
         self.tree_init = not (not tree_init or n_trees == 0 or init_graph is not None)  # pynndescent_.py:1059-1062
         self._dist_args = tuple((metric_kwds or {}).values())
         current_random_state = self._set_up(None if dev_in is not None else data, m, random_state, copy_on_normalize)
+        if csr is not None:  # pynndescent_.py:1114-1116: the index holds the CSR matrix, never dense rows
+            self._is_sparse, self._raw_data = True, csr
         if dev_in is None:
             data = self._raw_data
         self._linear_map = None
@@ -381,7 +394,8 @@ class NNDescent:
         if self.compressed and not hasattr(self, "_neighbor_graph"):
             warn("Compressed indexes do not have neighbor graph information.")
             return None
-        if "_device_graph" in self.__dict__:  # built from a device array: fresh tensors there, corrected by the library
+        # built from a device array: fresh tensors there, corrected by the library (scipy input gets numpy answers: the mirror's)
+        if "_device_graph" in self.__dict__ and not self.__dict__.get("_is_sparse"):
             torch = device_arrays._torch()
             idx, dist = self._device_graph
             with torch.cuda.device(self.device):
@@ -395,6 +409,8 @@ class NNDescent:
         (scipy CSR uint8, sorted indices) and ``_quantized_data`` (the searcher's uint8 codes).  Every line that reads the names
         finds them as on a host-built index, and ``hasattr`` keeps its meaning."""
         d = self.__dict__
+        if name == "_raw_data" and d.get("_is_sparse"):  # (a sparse index holds its CSR matrix itself: there is no dense mirror)
+            raise AttributeError("%r object has no attribute %r" % (type(self).__name__, name))
         if name in ("_raw_data", "_lin_data") and "_device_data" in d and (name == "_raw_data" or d.get("_linear_map") is not None):
             # (a metric with a linear map: _device_data holds the transformed rows, _device_raw the caller's)
             rows = d["_device_raw" if name == "_raw_data" and "_device_raw" in d else "_device_data"].detach()
@@ -445,7 +461,10 @@ class NNDescent:
         return "euclidean" if _metric_of(self.metric).linear else self.metric
 
     def _work_rows(self):
-        """The host rows the device works on: ``_raw_data``, or its transformed copy ``_lin_data`` for a metric with a linear map."""
+        """The host rows the device works on: ``_raw_data``, its transformed copy ``_lin_data`` for a metric with a linear map, or
+        the dense form of a sparse index's CSR matrix (a row's dense form depends on the row alone: the bits the device made)."""
+        if self.__dict__.get("_is_sparse"):  # (the host path of a sparse index, e.g. an unpickled one: dense for this call, not kept)
+            return np.ascontiguousarray(self._raw_data.toarray(), dtype=np.float32)
         return self._lin_data if self.__dict__.get("_linear_map") is not None else self._raw_data
 
     def _linear_on_device(self, device):
@@ -479,6 +498,8 @@ class NNDescent:
         so the two paths may differ where two true neighbours are that close; every other metric gives the same value."""
         _no_exact_for_proxy(self.metric, _metric_of(self.metric), "NNDescent.recall")
         d = self.__dict__
+        if d.get("_is_sparse"):  # (an unpickled one: its rows and its graph go up again first)
+            self._sparse_to_device()
         if "_device_data" in d and "_device_graph" in d and int(d.get("n_devices", 1)) == 1:
             return self._recall_device(k, n_rows, random_state)
         graph_idx = self._neighbor_graph[0]
@@ -544,6 +565,9 @@ class NNDescent:
         over holds true distances, and the search structures of a prepared index are LEFT OUT of the hand-over (its tree's
         hyperplanes split the transformed space, the reference's tree descent takes raw queries): the rows go back to their
         original order and the reference's own ``prepare()`` rebuilds tree and search graph from the graph."""
+        if self.__dict__.get("_is_sparse"):
+            raise NotImplementedError("to_reference() of an index built from sparse input: the reference's sparse search "
+                                      "structures (sparse hub tree, sparse distances) are not produced; build with pynndescent.NNDescent")
         import pynndescent
 
         linear = _metric_of(self.metric).linear
@@ -650,6 +674,8 @@ class NNDescent:
             graph, data, self._vertex_order, tree = reorder_by_tree(graph, self._work_rows(), self._search_forest[0])
             if self.__dict__.get("_linear_map") is not None:  # both copies in the leaf order
                 self._lin_data, self._raw_data = data, np.ascontiguousarray(self._raw_data[self._vertex_order, :])
+            elif self.__dict__.get("_is_sparse"):  # pynndescent_.py:1630: the CSR rows in the leaf order
+                self._raw_data = self._raw_data[self._vertex_order, :]
             else:
                 self._raw_data = data
             self._search_forest = [tree] + list(self._search_forest[1: self.n_search_trees])
@@ -748,7 +774,11 @@ class NNDescent:
             self._search_forest = [new_tree] + list(self._search_forest[1: self.n_search_trees])
         else:
             self._vertex_order = np.arange(n)
-        d.pop("_raw_data", None)  # (a mirror fetched before: the rows in their original order; the next read gathers them)
+        if d.get("_is_sparse"):  # the CSR matrix follows the leaf order on the host (pynndescent_.py:1630); _device_data stays as it is
+            if order is not None:
+                d["_raw_data"] = d["_raw_data"][vertex_order, :]
+        else:
+            d.pop("_raw_data", None)  # (a mirror fetched before: the rows in their original order; the next read gathers them)
         d.pop("_lin_data", None)
         self._device_search_graph = (indptr, indices)
         self._device_prepare_stats = dict(ms, ms_search_graph=float(st["ms_device"]), final_nnz=int(nnz))
@@ -773,6 +803,8 @@ class NNDescent:
                 raw = _DeviceRowsView(d["_device_data"])
             else:
                 raw = self._raw_data if fresh else self._raw_data[np.argsort(self._vertex_order)]
+                if d.get("_is_sparse"):
+                    raw = sparse_input.CsrRowsView(raw)
             self._quantized_values = uint8_codebook(raw, self.random_state)
             self._quantized_data = None  # derived by the device below, in the searcher's order
         if fresh:
@@ -840,12 +872,41 @@ class NNDescent:
         m = _metric_of(self.metric)
         if filter_mode not in filtered.FILTER_MODES:
             raise ValueError("filter_mode must be one of %s (got %r)" % (", ".join(filtered.FILTER_MODES), filter_mode))
+        if sparse_input.is_sparse(query_data):
+            return self._query_sparse(query_data, m, k, epsilon, proxy_beam_size, filter, filter_mode)
         if filter is not None:
             return self._query_filtered(query_data, m, k, epsilon, proxy_beam_size, filter, filter_mode)
         return self._query_walk(query_data, m, k, epsilon, proxy_beam_size)
 
-    def _query_filtered(self, query_data, m, k, epsilon, proxy_beam_size, filter, filter_mode):
-        """``query`` with a filter: everything is validated before any device work, then the path ``filtered.choose_mode`` names."""
+    def _query_sparse(self, query_data, m, k, epsilon, proxy_beam_size, filter, filter_mode):
+        """``query`` for a ``scipy.sparse`` batch, on an index built from sparse or dense data alike: the batch is made canonical,
+        uploaded as CSR and made dense on the device (sparse_input.py), and answered by the device-array forms of every query
+        path.  Scipy in, numpy out: the ids and the kernels' distances come down and the host applies the metric's correction,
+        so the answers are those of ``query(query_data.toarray())``, bit for bit."""
+        if tuple(_shape_of(query_data))[1:] != (self.dim,):
+            raise ValueError("query_data must have shape (n_queries, %d)" % self.dim)
+        if filter is not None:  # (validated on the host, before the upload; a host filter goes where the queries will be)
+            f = filtered.check_filter(filter, int(self._raw_data_n()), self.device)
+            if f.n_allowed == 0:
+                self.last_filter = {"mode": "empty", "n_allowed": 0}
+                return filtered.empty_answer(query_data, k)
+        q = sparse_input.query_rows(query_data, self.dim, self.device)
+        if filter is not None:
+            if not f.on_device:
+                filter = device_arrays._torch().from_numpy(f.values).to(q.device)
+            indices, dists = self._query_filtered(q, m, k, epsilon, proxy_beam_size, filter, filter_mode, host_answers=True)
+            if not _is_device_array(indices):  # (the exact path has brought them down and corrected them)
+                return indices, dists
+        else:
+            indices, dists = self._query_walk(q, m, k, epsilon, proxy_beam_size, host_answers=True)
+        indices, dists = np.ascontiguousarray(indices.cpu().numpy()), np.ascontiguousarray(dists.cpu().numpy())
+        if self._distance_correction is not None:  # pynndescent_.py:2375-2376
+            dists = self._distance_correction(dists)
+        return indices, dists
+
+    def _query_filtered(self, query_data, m, k, epsilon, proxy_beam_size, filter, filter_mode, host_answers=False):
+        """``query`` with a filter: everything is validated before any device work, then the path ``filtered.choose_mode`` names.
+        ``host_answers`` (device queries made from a sparse batch): see ``_query_device``."""
         if self.quantization is not None or m.proxy:
             _proxy_search_k(k, proxy_beam_size)
         f = filtered.check_filter(filter, int(self._raw_data_n()), self.device)
@@ -860,12 +921,14 @@ class NNDescent:
         if not self._prepared:
             self.prepare()
         if mode == "exact":
+            if host_answers:
+                return filtered.query_exact(self, query_data, k, f, host_answers=True)
             return filtered.query_exact(self, query_data, k, f)
         if getattr(self, "_searcher", None) is None or (self.quantization is not None and not self._searcher.has_codes):
             self.prepare()
         filtered.set_walk_filter(self, f)
         try:
-            return self._query_walk(query_data, m, k, epsilon, proxy_beam_size)
+            return self._query_walk(query_data, m, k, epsilon, proxy_beam_size, host_answers=host_answers)
         finally:
             self._searcher.clear_filter()
 
@@ -874,7 +937,7 @@ class NNDescent:
         d = self.__dict__
         return d["_device_data"].shape[0] if "_device_data" in d else self._raw_data.shape[0]
 
-    def _query_walk(self, query_data, m, k, epsilon, proxy_beam_size):
+    def _query_walk(self, query_data, m, k, epsilon, proxy_beam_size, host_answers=False):
         """The graph walk of ``query`` (with the searcher's filter, when ``_query_filtered`` has set one)."""
         search_k = k
         if self.quantization is not None or m.proxy:  # pynndescent_.py:2309-2312
@@ -883,7 +946,7 @@ class NNDescent:
                 or (self.quantization is not None and not self._searcher.has_codes)):
             self.prepare()
         if _is_device_array(query_data):
-            return self._query_device(query_data, m, k, search_k, epsilon)
+            return self._query_device(query_data, m, k, search_k, epsilon, corrected=not host_answers)
         query_data = np.asarray(query_data).astype(np.float32, order="C")  # pynndescent_.py:2316
         if query_data.ndim != 2 or query_data.shape[1] != self.dim:
             raise ValueError("query_data must have shape (n_queries, %d)" % self.dim)
@@ -903,8 +966,10 @@ class NNDescent:
             dists = self._distance_correction(dists)
         return indices, dists
 
-    def _query_device(self, q, m, k, search_k, epsilon):
-        """``query`` for a device array: the three forms on the device-pointer entries of the searcher."""
+    def _query_device(self, q, m, k, search_k, epsilon, corrected=True):
+        """``query`` for a device array: the three forms on the device-pointer entries of the searcher.  ``corrected`` False: the
+        kernels' own distances are returned -- the caller brings them to the host and applies the host's correction there, for
+        answers that equal a host query's bit for bit (the device's 1 - 2^-d agrees with numpy's within rounding only)."""
         torch = device_arrays._torch()
         q, dtype, ordinal = _check_device_array(q, what="query_data")
         if ordinal != int(self.device):
@@ -938,7 +1003,7 @@ class NNDescent:
                 self._searcher.vertex_order_device = order
             found = indices >= 0
             indices = torch.where(found, order[indices.clamp(min=0).long()], torch.full_like(indices, -1))  # pynndescent_.py:2373
-            if self._distance_correction is not None and m.device_kind != _capi.NND_CORRECT_COPY:  # pynndescent_.py:2375-2376
+            if corrected and self._distance_correction is not None and m.device_kind != _capi.NND_CORRECT_COPY:  # pynndescent_.py:2375-2376
                 dists = _device_corrected(torch, dists, m, ordinal)
         return indices, dists
 
@@ -978,14 +1043,28 @@ class NNDescent:
         (``_update_device``), ``neighbor_graph`` keeps returning tensors and a prepared index is prepared again on the device.
         With host arrays alone such an index becomes a host index, as before; a device array given to a host index, or to one
         built on several GPUs, is brought to the host.  ``updated_indices`` may be a tensor; the ids are read on the host."""
+        sparse_index = bool(self.__dict__.get("_is_sparse"))
+        if sparse_index:  # (an unpickled one: its rows and its graph go up again first)
+            self._sparse_to_device()
         on_device = _updates_on_device(self, xs_fresh, xs_updated)
-        if not on_device:  # a tensor on an index that cannot stay on the device: its values, through the host path
-            xs_fresh, xs_updated = _rows_to_host(xs_fresh), _rows_to_host(xs_updated)
+        if not on_device:  # a tensor or a sparse matrix on an index that cannot stay on the device: its values, through the host path
+            xs_fresh, xs_updated = (sparse_input.canonical_csr(a).toarray() if sparse_input.is_sparse(a) else _rows_to_host(a)
+                                    for a in (xs_fresh, xs_updated))
         updated_indices = _ids_to_host(updated_indices)  # (a tensor of ids: they are few, and they stay a host list)
+        csr_rows = {}  # a sparse index: the incoming rows as CSR as well, for its _raw_data
 
         def checked(rows, what):  # check_array; a device array of the device path: its validator, nothing is read
+            if sparse_input.is_sparse(rows):  # (the device path: made canonical, checked, then dense on the device)
+                rows = sparse_input.canonical_csr(rows)
+                if rows.shape[1] != self.dim:
+                    raise ValueError("%s must have shape (n_rows, %d), got %s" % (what, self.dim, tuple(rows.shape)))
+                csr_rows[what] = rows
+                return sparse_input.dense_rows_on_device(rows, self.device)
             if not _is_device_array(rows):
-                return check_array(rows, dtype=self._input_dtype, order="C")
+                rows = check_array(rows, dtype=self._input_dtype, order="C")
+                if sparse_index:
+                    csr_rows[what] = sparse_input.as_csr(rows)
+                return rows
             rows, _, ordinal = _check_device_array(rows, what=what)
             if ordinal != int(self.device):
                 raise ValueError("%s is on device %d, the index on device %d" % (what, ordinal, int(self.device)))
@@ -1015,7 +1094,7 @@ class NNDescent:
             updated_indices = None
         if on_device:
             return self._update_device(None if xs_fresh is None else checked(xs_fresh, "xs_fresh"), xs_updated, updated_indices or [],
-                                       current_random_state)
+                                       current_random_state, csr_rows=csr_rows)
         if updated_indices is None:
             xs_updated = np.zeros((0, self._raw_data.shape[1]), self._input_dtype)
             updated_indices = []
@@ -1074,7 +1153,21 @@ class NNDescent:
             self.prepare()
 
 
-    def _update_device(self, xs_fresh, xs_updated, updated_indices, current_random_state):
+    def _sparse_to_device(self):
+        """A sparse index that has lost its device tensors (unpickled) gets them again: the CSR rows, back in their original order,
+        are made dense on the device -- a row's dense form depends on the row alone, so the bits are those of the build -- and the
+        graph's host mirror goes up.  ``update()`` and ``recall()`` then run where they run for a freshly built index."""
+        d = self.__dict__
+        if "_device_data" not in d:
+            raw = d["_raw_data"]
+            if "_vertex_order" in d:
+                raw = raw[np.argsort(d["_vertex_order"]), :]
+            d["_device_data"] = sparse_input.dense_rows_on_device(raw, self.device)
+        if "_device_graph" not in d and "_neighbor_graph" in d:
+            torch = device_arrays._torch()
+            d["_device_graph"] = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(d["_device_data"].device) for a in d["_neighbor_graph"])
+
+    def _update_device(self, xs_fresh, xs_updated, updated_indices, current_random_state, csr_rows=None):
         """``update`` of an index that holds its rows and its graph on the device, entry for entry what the host path computes
         from the mirrors -- on torch's current stream (``_OnTorchStream``), with no host leg: the new ``(n_old + n_fresh, d)``
         tensor (old rows, fresh rows, updated rows scattered to their ids; the dtype all arrays share, else float32) and the
@@ -1126,10 +1219,16 @@ class NNDescent:
         self.n_trees, self._build_stats = n_trees, build_stats
         self._rp_forest = _DeviceForestSentinel(n_trees, n_leaves, eff_leaf_size)
         was_prepared = self._prepared
+        new_csr = None
+        if d.get("_is_sparse"):  # _raw_data is updated as CSR, in the original order (pynndescent_.py:2461-2476)
+            raw = d["_raw_data"][np.argsort(d["_vertex_order"]), :] if "_vertex_order" in d else d["_raw_data"]
+            new_csr = sparse_input.updated_csr(raw, (csr_rows or {}).get("xs_updated"), ids, sources, (csr_rows or {}).get("xs_fresh"))
         # (the rows and the graph are replaced below; every mirror of the old ones is stale, ``_device_linear`` is the same map)
         for name in self._DEVICE_PREPARED + self._HOST_MIRRORS + self._SEARCH_STRUCTURES:
             d.pop(name, None)
         self._device_data, self._device_graph = dev_in.rows, graph  # (the caller's original tensor is released)
+        if new_csr is not None:
+            d["_raw_data"] = new_csr
         if linear is not None:
             self._device_raw = new_data
         if was_prepared:  # pynndescent_.py:2538-2553: the derived structures are rebuilt, from the tensors when _prepares_on_device
@@ -1146,7 +1245,8 @@ _FROM_GRAPH_DEFAULTS = {
 }
 
 def make_index(data, *args, **kwargs):
-    """``NNDescent(data, ...)`` on the GPU when the input is in scope (dense data, euclidean / l2 / sqeuclidean / cosine / dot /
+    """``NNDescent(data, ...)`` on the GPU when the input is in scope (dense data, or sparse data whose dense rows fit the device
+    and a metric the reference's sparse path has too; euclidean / l2 / sqeuclidean / cosine / dot /
     inner_product / correlation / hellinger / proxy_inner_product / seuclidean / mahalanobis / minkowski and wminkowski with p = 2 /
     the boolean metrics jaccard, dice, sokalsneath, matching, rogerstanimoto, sokalmichener, kulsinski, russellrao and yule,
     k <= 256);
