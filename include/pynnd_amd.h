@@ -514,6 +514,20 @@ int32_t nnd_exact_knn_rows_device(nnd_handle_t h, const int32_t *rows_dev, int64
                                   int32_t *out_idx_dev, float *out_dist_dev, nnd_exact_stats *st /* may be NULL */);
 int32_t nnd_exact_knn_queries_device(nnd_handle_t h, const void *q_dev, int32_t dtype, int64_t n_q, int32_t k,
                                      int32_t *out_idx_dev, float *out_dist_dev, nnd_exact_stats *st);
+/* The four entries above under a predicate per query row (the masked instances of the scan and of the float64 tier): `tags` holds
+ * one 64-bit tag word per row of the point set, `masks` one mask word per query row (in the order of rows / q), and data row c
+ * belongs to query row i's point set iff tags[c] & masks[i] != 0.  The answer is the exact top k by (float64 distance, id) AMONG
+ * THOSE ROWS; a pair that does not meet is neither a candidate nor counted into the certificate's bound.  Fewer than k such rows
+ * (a mask of 0: none) leave (-1, +inf) in the last places.  Host forms take host words, device forms words on the handle's device. */
+int32_t nnd_exact_knn_rows_tagged(nnd_handle_t h, const int64_t *rows, int64_t n_rows, int32_t k, const uint64_t *tags,
+                                  const uint64_t *masks, int32_t *out_idx, float *out_dist, nnd_exact_stats *st /* may be NULL */);
+int32_t nnd_exact_knn_queries_tagged(nnd_handle_t h, const float *q, int64_t n_q, int32_t k, const uint64_t *tags,
+                                     const uint64_t *masks, int32_t *out_idx, float *out_dist, nnd_exact_stats *st);
+int32_t nnd_exact_knn_rows_tagged_device(nnd_handle_t h, const int32_t *rows_dev, int64_t n_rows, int32_t k, const uint64_t *tags_dev,
+                                         const uint64_t *masks_dev, int32_t *out_idx_dev, float *out_dist_dev, nnd_exact_stats *st);
+int32_t nnd_exact_knn_queries_tagged_device(nnd_handle_t h, const void *q_dev, int32_t dtype, int64_t n_q, int32_t k,
+                                            const uint64_t *tags_dev, const uint64_t *masks_dev, int32_t *out_idx_dev,
+                                            float *out_dist_dev, nnd_exact_stats *st);
 /* data slices the scan splits the point set into when n_rows query rows are asked for (a function of the shapes alone: few
  * query blocks -> many slices, so that the chip is filled); tests */
 int32_t nnd_exact_slice_count(nnd_handle_t h, int64_t n_rows);
@@ -698,6 +712,30 @@ int32_t nnd_searcher_set_filter(nnd_searcher_t s, const void *filter, int64_t co
 int32_t nnd_searcher_set_filter_device(nnd_searcher_t s, const void *filter_dev, int64_t count, int32_t kind,
                                        const int32_t *order_dev /* may be NULL */, int64_t *n_allowed /* may be NULL */, void *hip_stream);
 int32_t nnd_searcher_clear_filter(nnd_searcher_t s);
+/* Per-query filters (beyond the reference): every row may carry a tag word (64 bits, one per tag), every query of a call a mask
+ * word; row r may be returned to query i iff tags[r] & masks[i] != 0.  A row with tag word 0 is never returned, a query with
+ * mask 0 gets (-1, +inf) in every place.  The tag words are STATE of the searcher (its own copy, n x 8 bytes, in the searcher's
+ * numbering: `tags` is in the ORIGINAL numbering and gathered through `order` as for the filter above); the masks come with the
+ * call.  nnd_searcher_query_tagged* is the walk of the query entries above with the filter's rule per query -- a vertex enters the
+ * result list only if its tag word meets the query's mask; it is still visited and expanded -- for the three forms: NND_QUERY_FLOAT
+ * (nnd_searcher_query; search_k is ignored), NND_QUERY_PROXY (nnd_searcher_query_proxy) and NND_QUERY_RERANK
+ * (nnd_searcher_query_rerank).  It fails without tags and while a filter is set (the two do not combine).
+ * nnd_searcher_count_tags*: counts[u] = rows whose tag word meets masks[u], one pass over the tag words for all n_masks masks.
+ * Host forms copy their arrays and run on the searcher's stream, device forms read and write device memory on `hip_stream`; all
+ * return with the stream drained.  nnd_searcher_clear_tags releases the searcher's copy. */
+#define NND_QUERY_FLOAT 0
+#define NND_QUERY_PROXY 1
+#define NND_QUERY_RERANK 2
+int32_t nnd_searcher_set_tags(nnd_searcher_t s, const uint64_t *tags /* (n) */, const int32_t *order /* may be NULL */);
+int32_t nnd_searcher_set_tags_device(nnd_searcher_t s, const uint64_t *tags_dev, const int32_t *order_dev /* may be NULL */, void *hip_stream);
+int32_t nnd_searcher_clear_tags(nnd_searcher_t s);
+int32_t nnd_searcher_count_tags(nnd_searcher_t s, const uint64_t *masks, int32_t n_masks, int64_t *counts);
+int32_t nnd_searcher_count_tags_device(nnd_searcher_t s, const uint64_t *masks_dev, int32_t n_masks, int64_t *counts_dev, void *hip_stream);
+int32_t nnd_searcher_query_tagged(nnd_searcher_t s, int32_t form, const float *queries, int64_t nq, int32_t k, int32_t search_k,
+                                  float epsilon, const uint64_t *masks /* (nq) */, int32_t *out_idx, float *out_dist);
+int32_t nnd_searcher_query_tagged_device(nnd_searcher_t s, int32_t form, const float *queries_dev, int64_t nq, int32_t k, int32_t search_k,
+                                         float epsilon, const uint64_t *masks_dev, int32_t *out_idx_dev, float *out_dist_dev,
+                                         void *hip_stream);
 int32_t nnd_searcher_destroy(nnd_searcher_t s);
 const char *nnd_searcher_last_error(nnd_searcher_t s /* NULL: the error of a failed create */);
 

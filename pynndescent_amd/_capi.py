@@ -39,6 +39,7 @@ def metric_code(name):
 # element types of a device array (include/pynnd_amd.h NND_DTYPE_*) and the corrections of nnd_device_correct (NND_CORRECT_*)
 NND_DTYPE_FLOAT32, NND_DTYPE_FLOAT16, NND_DTYPE_BFLOAT16, NND_DTYPE_FLOAT64 = 0, 1, 2, 3
 NND_FILTER_MASK, NND_FILTER_IDS = 0, 1  # nnd_searcher_set_filter's `kind`
+NND_QUERY_FORMS = {"float": 0, "proxy": 1, "rerank": 2}  # nnd_searcher_query_tagged's `form` (NND_QUERY_*)
 NND_CORRECT_COPY, NND_CORRECT_SQRT, NND_CORRECT_ALT_COSINE, NND_CORRECT_ALT_INNER_PRODUCT, NND_CORRECT_ALT_HELLINGER = 0, 1, 2, 3, 4
 NND_LINEAR_DIAGONAL, NND_LINEAR_DENSE = 0, 1  # the kinds of a metric's linear map (include/pynnd_amd.h NND_LINEAR_*, csrc/linear.hip)
 NND_FLAG_NO_GRAPH = 1  # auxiliary handle: no k-lists / candidate / proposal tables (pruning pass, hub tree)
@@ -326,6 +327,23 @@ _SIGNATURES = [
     ("nnd_searcher_set_filter", C.c_int32, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.POINTER(C.c_int64)]),
     ("nnd_searcher_set_filter_device", C.c_int32, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),
     ("nnd_searcher_clear_filter", C.c_int32, [_H]),
+    ("nnd_searcher_set_tags", C.c_int32, [_H, C.c_void_p, C.c_void_p]),
+    ("nnd_searcher_set_tags_device", C.c_int32, [_H, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("nnd_searcher_clear_tags", C.c_int32, [_H]),
+    ("nnd_searcher_count_tags", C.c_int32, [_H, C.c_void_p, C.c_int32, C.c_void_p]),
+    ("nnd_searcher_count_tags_device", C.c_int32, [_H, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    ("nnd_searcher_query_tagged", C.c_int32, [_H, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
+                                              C.c_void_p]),
+    ("nnd_searcher_query_tagged_device", C.c_int32, [_H, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("nnd_exact_knn_rows_tagged", C.c_int32, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.POINTER(NNDExactStats)]),
+    ("nnd_exact_knn_queries_tagged", C.c_int32, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.POINTER(NNDExactStats)]),
+    ("nnd_exact_knn_rows_tagged_device", C.c_int32, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.POINTER(NNDExactStats)]),
+    ("nnd_exact_knn_queries_tagged_device", C.c_int32, [_H, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p, C.POINTER(NNDExactStats)]),
     ("nnd_searcher_destroy", C.c_int32, [_H]),
     ("nnd_searcher_last_error", C.c_char_p, [_H]),
 ]
@@ -641,42 +659,60 @@ class Builder:
 
 
     # -- exact search (csrc/exact.hip) --------------------------------------------------------------
-    def _exact(self, call, arg, m, k):
+    def _exact(self, call, arg, m, k, tags=None, masks=None):
         idx = np.empty((m, int(k)), np.int32)
         dist = np.empty((m, int(k)), np.float32)
         st = NNDExactStats()
-        self._check(call(self._h, _ptr(arg), m, int(k), _ptr(idx), _ptr(dist), C.byref(st)))
+        if tags is not None:  # the masked search (the *_tagged entry given as ``call``): uint64 words, n tags and m masks
+            tags, masks = np.ascontiguousarray(tags, np.uint64), np.ascontiguousarray(masks, np.uint64)
+            assert tags.shape == (self.n,) and masks.shape == (m,)
+            self._check(call(self._h, _ptr(arg), m, int(k), _ptr(tags), _ptr(masks), _ptr(idx), _ptr(dist), C.byref(st)))
+        else:
+            self._check(call(self._h, _ptr(arg), m, int(k), _ptr(idx), _ptr(dist), C.byref(st)))
         stats = st.as_dict()
         stats["slices"] = int(self.lib.nnd_exact_slice_count(self._h, m))
         return idx, dist, stats
 
-    def exact_knn(self, rows=None, k=10):
+    def exact_knn(self, rows=None, k=10, tags=None, masks=None):
         """Exact k nearest neighbours (self included) of ``rows`` of the handle's point set (None: all of them): int32 ids and
-        float32 alt-space distances (m, k), rows ascending by (float64 distance, id), and the call's statistics."""
+        float32 alt-space distances (m, k), rows ascending by (float64 distance, id), and the call's statistics.  ``tags`` (n
+        uint64 words) and ``masks`` (one per query row): the masked search among the rows whose tag word meets the row's mask."""
         if rows is not None:
             rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
-        return self._exact(self.lib.nnd_exact_knn_rows, rows, self.n if rows is None else rows.shape[0], k)
+        call = self.lib.nnd_exact_knn_rows if tags is None else self.lib.nnd_exact_knn_rows_tagged
+        return self._exact(call, rows, self.n if rows is None else rows.shape[0], k, tags, masks)
 
-    def exact_knn_queries(self, q, k):
+    def exact_knn_queries(self, q, k, tags=None, masks=None):
         """The same for external queries, float32 (m, dim), prepared with the point set's own transform."""
         q = np.ascontiguousarray(q, dtype=np.float32)
         assert q.ndim == 2 and q.shape[1] == self.dim
-        return self._exact(self.lib.nnd_exact_knn_queries, q, q.shape[0], k)
+        call = self.lib.nnd_exact_knn_queries if tags is None else self.lib.nnd_exact_knn_queries_tagged
+        return self._exact(call, q, q.shape[0], k, tags, masks)
 
 
-    def exact_knn_device(self, k, idx_ptr, dist_ptr, rows_ptr=0, n_rows=None, q_ptr=0, q_dtype=NND_DTYPE_FLOAT32, n_q=0):
+    def exact_knn_device(self, k, idx_ptr, dist_ptr, rows_ptr=0, n_rows=None, q_ptr=0, q_dtype=NND_DTYPE_FLOAT32, n_q=0, tags_ptr=0,
+                         masks_ptr=0):
         """The exact search with every array on the handle's device, on the handle's stream: of the int32 row ids at ``rows_ptr``
         (0: all rows), or of the (n_q, dim) queries of ``q_dtype`` at ``q_ptr``; int32 / float32 (m, k) answers written at
-        ``idx_ptr`` / ``dist_ptr``.  Returns the call's statistics."""
+        ``idx_ptr`` / ``dist_ptr``.  ``tags_ptr`` / ``masks_ptr``: the masked search (n tag words, m mask words on the device).
+        Returns the call's statistics."""
         st = NNDExactStats()
         dev = lambda p: C.c_void_p(int(p)) if p else None  # noqa: E731
         if q_ptr:
             m = int(n_q)
-            self._check(self.lib.nnd_exact_knn_queries_device(self._h, dev(q_ptr), int(q_dtype), m, int(k), dev(idx_ptr), dev(dist_ptr),
-                                                              C.byref(st)))
+            if tags_ptr:
+                self._check(self.lib.nnd_exact_knn_queries_tagged_device(self._h, dev(q_ptr), int(q_dtype), m, int(k), dev(tags_ptr),
+                                                                         dev(masks_ptr), dev(idx_ptr), dev(dist_ptr), C.byref(st)))
+            else:
+                self._check(self.lib.nnd_exact_knn_queries_device(self._h, dev(q_ptr), int(q_dtype), m, int(k), dev(idx_ptr), dev(dist_ptr),
+                                                                  C.byref(st)))
         else:
             m = self.n if not rows_ptr else int(n_rows)
-            self._check(self.lib.nnd_exact_knn_rows_device(self._h, dev(rows_ptr), m, int(k), dev(idx_ptr), dev(dist_ptr), C.byref(st)))
+            if tags_ptr:
+                self._check(self.lib.nnd_exact_knn_rows_tagged_device(self._h, dev(rows_ptr), m, int(k), dev(tags_ptr), dev(masks_ptr),
+                                                                      dev(idx_ptr), dev(dist_ptr), C.byref(st)))
+            else:
+                self._check(self.lib.nnd_exact_knn_rows_device(self._h, dev(rows_ptr), m, int(k), dev(idx_ptr), dev(dist_ptr), C.byref(st)))
         stats = st.as_dict()
         stats["slices"] = int(self.lib.nnd_exact_slice_count(self._h, m))
         return stats
@@ -845,6 +881,60 @@ class Searcher:
         """Back to unfiltered queries."""
         if self.lib.nnd_searcher_clear_filter(self._h) != 0:
             raise NNDError(self.lib.nnd_searcher_last_error(self._h).decode())
+
+    # -- per-query filters: the rows' tag words, the counts per mask, the tagged walk --------------------
+    def _rc(self, rc):
+        if rc != 0:
+            raise NNDError(self.lib.nnd_searcher_last_error(self._h).decode())
+
+    def set_tags(self, tags, order=None):
+        """The rows' tag words (``nnd_searcher_set_tags``) from a host array of n 64-bit words in the ORIGINAL numbering; ``order``
+        (int32, n; None: the identity) is the searcher's row order."""
+        t = np.ascontiguousarray(tags).view(np.uint64)
+        assert t.shape == (self.n,)
+        if order is not None:
+            order = np.ascontiguousarray(order, np.int32)
+            assert order.shape == (self.n,)
+        self._rc(self.lib.nnd_searcher_set_tags(self._h, _ptr(t), _ptr(order)))
+
+    def set_tags_device(self, tags_ptr, order_ptr, stream_ptr):
+        """``set_tags`` from device memory: n 64-bit words at ``tags_ptr``, the int32 row order at ``order_ptr`` (0: the identity)."""
+        dev = lambda p: C.c_void_p(int(p)) if p else None  # noqa: E731
+        self._rc(self.lib.nnd_searcher_set_tags_device(self._h, dev(tags_ptr), dev(order_ptr), dev(stream_ptr)))
+
+    def clear_tags(self):
+        """Releases the searcher's copy of the tag words."""
+        self._rc(self.lib.nnd_searcher_clear_tags(self._h))
+
+    def count_tags(self, masks):
+        """For every 64-bit mask word of the host array ``masks``: the rows whose tag word meets it (int64)."""
+        m = np.ascontiguousarray(masks).view(np.uint64).reshape(-1)
+        counts = np.zeros(m.shape[0], np.int64)
+        self._rc(self.lib.nnd_searcher_count_tags(self._h, _ptr(m), int(m.shape[0]), _ptr(counts)))
+        return counts
+
+    def count_tags_device(self, masks_ptr, n_masks, counts_ptr, stream_ptr):
+        """``count_tags`` on device memory: ``n_masks`` words at ``masks_ptr``, int64 counts written at ``counts_ptr``."""
+        dev = lambda p: C.c_void_p(int(p)) if p else None  # noqa: E731
+        self._rc(self.lib.nnd_searcher_count_tags_device(self._h, dev(masks_ptr), int(n_masks), dev(counts_ptr), dev(stream_ptr)))
+
+    def query_tagged(self, form, queries, masks, k, search_k, epsilon):
+        """The walk of ``query`` / ``query_proxy`` / ``query_rerank`` (``form``: "float", "proxy", "rerank") in which a vertex
+        enters query i's result list only if its tag word meets ``masks[i]`` (host arrays)."""
+        q = np.ascontiguousarray(queries, np.float32)
+        m = np.ascontiguousarray(masks).view(np.uint64)
+        assert q.ndim == 2 and q.shape[1] == self.dim and m.shape == (q.shape[0],)
+        idx = np.empty((q.shape[0], k), np.int32)
+        dist = np.empty((q.shape[0], k), np.float32)
+        self._rc(self.lib.nnd_searcher_query_tagged(self._h, NND_QUERY_FORMS[form], _ptr(q), q.shape[0], int(k), int(search_k), float(epsilon),
+                                                    _ptr(m), _ptr(idx), _ptr(dist)))
+        return idx, dist
+
+    def query_tagged_device(self, form, q_ptr, masks_ptr, nq, k, search_k, epsilon, idx_ptr, dist_ptr, stream_ptr):
+        """``query_tagged`` on device buffers (see ``query_device``); ``masks_ptr``: nq 64-bit words."""
+        dev = lambda p: C.c_void_p(int(p)) if p else None  # noqa: E731
+        self._rc(self.lib.nnd_searcher_query_tagged_device(self._h, NND_QUERY_FORMS[form], dev(q_ptr), int(nq), int(k), int(search_k),
+                                                           float(epsilon), dev(masks_ptr), dev(idx_ptr), dev(dist_ptr), dev(stream_ptr)))
 
     def last_spilled(self):
         """Queries of the last call whose search outgrew the LDS structures and ran on the global-memory tier."""

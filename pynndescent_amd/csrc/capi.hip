@@ -492,6 +492,69 @@ extern "C" int32_t nnd_exact_knn_queries_device(nnd_handle_t ctx, const void *q_
     const nnd_exact_dev dev{nullptr, q_dev, dtype};
     return nnd_exact_knn_impl(ctx, nullptr, nullptr, n_q, k, out_idx_dev, out_dist_dev, st, &dev);
 }
+// ... among the rows a predicate allows (exact.hip, the masked instances): n tag words, one mask word per query row
+static int exact_tag_checks(nnd_ctx *ctx, const char *who, const void *tags, const void *masks, int64_t nq) {
+    if (!tags || (nq > 0 && !masks)) { ctx->set_error("%s: tags or masks missing", who); return 1; }
+    return 0;
+}
+// the host forms' words go up into buffers of the call (released behind the search's last synchronise)
+static int exact_upload_tags(nnd_ctx *ctx, nnd_scratch &tmp, const uint64_t *tags, const uint64_t *masks, int64_t nq, nnd_exact_tags *tg) {
+    uint64_t *dt = tmp.get<uint64_t>(ctx, (size_t)ctx->n), *dm = tmp.get<uint64_t>(ctx, (size_t)nq);
+    if (!dt || !dm) return 1;
+    NND_HIP_CHECK(hipMemcpyAsync(dt, tags, sizeof(uint64_t) * (size_t)ctx->n, hipMemcpyHostToDevice, ctx->stream));
+    if (nq > 0) NND_HIP_CHECK(hipMemcpyAsync(dm, masks, sizeof(uint64_t) * (size_t)nq, hipMemcpyHostToDevice, ctx->stream));
+    *tg = nnd_exact_tags{dt, dm};
+    return 0;
+}
+extern "C" int32_t nnd_exact_knn_rows_tagged(nnd_handle_t ctx, const int64_t *rows, int64_t n_rows, int32_t k, const uint64_t *tags, const uint64_t *masks,
+                                             int32_t *out_idx, float *out_dist, nnd_exact_stats *st) {
+    ENTER(ctx, NEED_PREP);
+    if (!rows) n_rows = ctx->n;
+    if (exact_checks(ctx, "nnd_exact_knn_rows_tagged", n_rows, k, out_idx, out_dist)) return 1;
+    if (exact_tag_checks(ctx, "nnd_exact_knn_rows_tagged", tags, masks, n_rows)) return 1;
+    nnd_scratch tmp;
+    nnd_exact_tags tg;
+    int rc = exact_upload_tags(ctx, tmp, tags, masks, n_rows, &tg);
+    if (!rc) rc = nnd_exact_knn_impl(ctx, rows, nullptr, n_rows, k, out_idx, out_dist, st, nullptr, &tg);
+    if (rc) (void)nnd_sync_spin(ctx);  // nothing queued still reads tmp
+    return rc;
+}
+extern "C" int32_t nnd_exact_knn_queries_tagged(nnd_handle_t ctx, const float *q, int64_t n_q, int32_t k, const uint64_t *tags, const uint64_t *masks,
+                                                int32_t *out_idx, float *out_dist, nnd_exact_stats *st) {
+    ENTER(ctx, NEED_PREP);
+    if (exact_checks(ctx, "nnd_exact_knn_queries_tagged", n_q, k, out_idx, out_dist)) return 1;
+    if (!q && n_q > 0) { ctx->set_error("nnd_exact_knn_queries_tagged: null queries"); return 1; }
+    if (!q) { if (st) *st = nnd_exact_stats{}; return 0; }
+    if (exact_tag_checks(ctx, "nnd_exact_knn_queries_tagged", tags, masks, n_q)) return 1;
+    nnd_scratch tmp;
+    nnd_exact_tags tg;
+    int rc = exact_upload_tags(ctx, tmp, tags, masks, n_q, &tg);
+    if (!rc) rc = nnd_exact_knn_impl(ctx, nullptr, q, n_q, k, out_idx, out_dist, st, nullptr, &tg);
+    if (rc) (void)nnd_sync_spin(ctx);
+    return rc;
+}
+extern "C" int32_t nnd_exact_knn_rows_tagged_device(nnd_handle_t ctx, const int32_t *rows_dev, int64_t n_rows, int32_t k, const uint64_t *tags_dev,
+                                                    const uint64_t *masks_dev, int32_t *out_idx_dev, float *out_dist_dev, nnd_exact_stats *st) {
+    ENTER(ctx, NEED_PREP);
+    if (!rows_dev) n_rows = ctx->n;
+    if (exact_checks(ctx, "nnd_exact_knn_rows_tagged_device", n_rows, k, out_idx_dev, out_dist_dev)) return 1;
+    if (exact_tag_checks(ctx, "nnd_exact_knn_rows_tagged_device", tags_dev, masks_dev, n_rows)) return 1;
+    const nnd_exact_dev dev{rows_dev, nullptr, NND_DTYPE_FLOAT32};
+    const nnd_exact_tags tg{tags_dev, masks_dev};
+    return nnd_exact_knn_impl(ctx, nullptr, nullptr, n_rows, k, out_idx_dev, out_dist_dev, st, &dev, &tg);
+}
+extern "C" int32_t nnd_exact_knn_queries_tagged_device(nnd_handle_t ctx, const void *q_dev, int32_t dtype, int64_t n_q, int32_t k, const uint64_t *tags_dev,
+                                                       const uint64_t *masks_dev, int32_t *out_idx_dev, float *out_dist_dev, nnd_exact_stats *st) {
+    ENTER(ctx, NEED_PREP);
+    if (exact_checks(ctx, "nnd_exact_knn_queries_tagged_device", n_q, k, out_idx_dev, out_dist_dev)) return 1;
+    if (dtype < NND_DTYPE_FLOAT32 || dtype > NND_DTYPE_FLOAT64) { ctx->set_error("nnd_exact_knn_queries_tagged_device: dtype %d is none of NND_DTYPE_*", (int)dtype); return 1; }
+    if (!q_dev && n_q > 0) { ctx->set_error("nnd_exact_knn_queries_tagged_device: null queries"); return 1; }
+    if (!q_dev) { if (st) *st = nnd_exact_stats{}; return 0; }
+    if (exact_tag_checks(ctx, "nnd_exact_knn_queries_tagged_device", tags_dev, masks_dev, n_q)) return 1;
+    const nnd_exact_dev dev{nullptr, q_dev, dtype};
+    const nnd_exact_tags tg{tags_dev, masks_dev};
+    return nnd_exact_knn_impl(ctx, nullptr, nullptr, n_q, k, out_idx_dev, out_dist_dev, st, &dev, &tg);
+}
 extern "C" int32_t nnd_exact_slice_count(nnd_handle_t ctx, int64_t n_rows) {
     if (!ctx) return 0;
     return nnd_exact_slices_for(ctx->n, n_rows);  // (of the first batch: exact.hip takes at most EX_BATCH query rows per pass)

@@ -82,15 +82,21 @@ __device__ __forceinline__ void ex_merge_into(uint64_t *scr, uint32_t *__restric
 // once); XM: the codes 2..5 (metric.h NND_CODES_0_5; code 6 is refused by the host), else 0 / 1; WIDE: W > 64 (rows merged through LDS).
 // The body is shared by the kernels' instances: k_exact_scan (XM as above) and k_exact_scan_bool, the boolean family's (FAM =
 // NND_CODES_BOOL: `metric` carries the column count, metric.h nnd_kernel_metric).
-template <int DC, int FAM, bool WIDE>
+// MK: the masked scan (k_exact_scan_masked): data row c is part of query row i's point set only if tags[c] & qmasks[i] != 0 -- `tags`
+// one word per data row, `qmasks` one per query row of the batch.  The masks of a lane group's four rows live in registers beside
+// th and rej, the tags of a data tile are staged beside snrm.  A pair that does not meet is neither admitted nor counted into rej:
+// it is no rejected candidate, and the certificate's T must not see it.
+template <int DC, int FAM, bool WIDE, bool MK = false>
 __device__ __forceinline__ void ex_scan_body(const float *__restrict__ xp, const float *__restrict__ nrm, int64_t n, int dp, int metric,
                                                     const float *__restrict__ qx, const float *__restrict__ qnrm, const int32_t *__restrict__ qids,
                                                     int self, int nq, int nq_pad, int W, int64_t rows_per_slice, uint32_t *__restrict__ list_e,
-                                                    float *__restrict__ list_d, float *__restrict__ list_th, float *__restrict__ list_rej) {
+                                                    float *__restrict__ list_d, float *__restrict__ list_th, float *__restrict__ list_rej,
+                                                    const uint64_t *__restrict__ tags = nullptr, const uint64_t *__restrict__ qmasks = nullptr) {
     extern __shared__ __align__(16) unsigned char ex_smem[];
     float *Xs = (float *)ex_smem;                              // (EX_QB + EX_TB) rows of DC floats, swizzled: queries, then the data tile
     float *snrm = Xs + (EX_QB + EX_TB) * DC;                   // (EX_TB) nrm of the data tile
-    int32_t *sq = (int32_t *)(snrm + EX_TB);                   // (EX_QB) ids of the query rows, -1 = none
+    uint64_t *stag = (uint64_t *)(snrm + EX_TB);               // MK: (EX_TB) tag words of the data tile (the other instances have no such array)
+    int32_t *sq = (int32_t *)(snrm + EX_TB + (MK ? 2 * EX_TB : 0));  // (EX_QB) ids of the query rows, -1 = none
     uint2 *pend = (uint2 *)(sq + EX_QB);                       // (EX_QB, EX_PC) queues: (id, distance bits)
     uint64_t *wscr = (uint64_t *)(pend + EX_QB * EX_PC);       // WIDE: NND_WIDE_SCRATCH_WORDS per wave
     const int tid = threadIdx.x, lane = nnd_lane(), w = tid >> 6, g = lane >> 4, c16 = lane & 15;
@@ -119,6 +125,11 @@ __device__ __forceinline__ void ex_scan_body(const float *__restrict__ xp, const
         sid[r] = (self && qok[r]) ? id : -2;
         th[r] = rej[r] = INFINITY;
         fill[r] = 0;
+    }
+    uint64_t qm[4] = {0ull, 0ull, 0ull, 0ull};
+    if constexpr (MK) {
+#pragma unroll
+        for (int r = 0; r < 4; r++) qm[r] = qok[r] ? qmasks[q0 + 16 * w + 4 * g + r] : 0ull;
     }
     // merge the queues of this wave's rows into their lists
     auto flush = [&]() {
@@ -169,6 +180,9 @@ __device__ __forceinline__ void ex_scan_body(const float *__restrict__ xp, const
                 *(float4 *)&Xs[nnd_swz<DC>(EX_QB + r, ch)] = v;
             }
             if (c0 == 0 && tid < EX_TB) snrm[tid] = t0 + tid < c_hi ? nrm[t0 + tid] : 0.0f;
+            if constexpr (MK) {
+                if (c0 == 0 && tid < EX_TB) stag[tid] = t0 + tid < c_hi ? tags[t0 + tid] : 0ull;
+            }
             __syncthreads();
             nnd_gram_chunk<DC, 4>(Xs, 16 * w, EX_QB, cw, acc, [](int) { return true; });
         }
@@ -179,12 +193,16 @@ __device__ __forceinline__ void ex_scan_body(const float *__restrict__ xp, const
             const int64_t cid = t0 + col;
             const bool cv = cid < c_hi;
             const float nb = snrm[col];
+            uint64_t tg = 0ull;
+            if constexpr (MK) tg = stag[col];
 #pragma unroll
             for (int r = 0; r < 4; r++) {
                 float val = nnd_gram_to_dist<FAM>(metric, a[r], na[r], nb);
                 if ((int64_t)sid[r] == cid) val = nnd_self_dist<FAM>(metric, na[r]);
-                const bool ok = cv && qok[r] && val < th[r];
-                if (cv && !ok) rej[r] = fminf(rej[r], val);
+                bool in_set = cv;  // MK: and the pair's words meet
+                if constexpr (MK) in_set = cv && (tg & qm[r]) != 0ull;
+                const bool ok = in_set && qok[r] && val < th[r];
+                if (in_set && !ok) rej[r] = fminf(rej[r], val);
                 const uint32_t m16 = (uint32_t)(__ballot(ok) >> (16 * g)) & 0xFFFFu;
                 if (ok) pend[(16 * w + 4 * g + r) * EX_PC + fill[r] + __popc(m16 & ((1u << c16) - 1u))] = make_uint2((uint32_t)cid, __float_as_uint(val));
                 fill[r] += __popc(m16);
@@ -215,7 +233,15 @@ __global__ __launch_bounds__(256) void k_exact_scan_bool(const float *__restrict
                                                     float *__restrict__ list_d, float *__restrict__ list_th, float *__restrict__ list_rej) {
     ex_scan_body<DC, NND_CODES_BOOL, WIDE>(xp, nrm, n, dp, metric, qx, qnrm, qids, self, nq, nq_pad, W, rows_per_slice, list_e, list_d, list_th, list_rej);
 }
-
+// the masked scan, all three families in one kernel template (FAM: NND_CODES_01, NND_CODES_0_5 or NND_CODES_BOOL)
+template <int DC, int FAM, bool WIDE>
+__global__ __launch_bounds__(256) void k_exact_scan_masked(const float *__restrict__ xp, const float *__restrict__ nrm, int64_t n, int dp, int metric,
+                                                    const float *__restrict__ qx, const float *__restrict__ qnrm, const int32_t *__restrict__ qids,
+                                                    int self, int nq, int nq_pad, int W, int64_t rows_per_slice, uint32_t *__restrict__ list_e,
+                                                    float *__restrict__ list_d, float *__restrict__ list_th, float *__restrict__ list_rej,
+                                                    const uint64_t *__restrict__ tags /* (n) */, const uint64_t *__restrict__ qmasks /* (nq) */) {
+    ex_scan_body<DC, FAM, WIDE, true>(xp, nrm, n, dp, metric, qx, qnrm, qids, self, nq, nq_pad, W, rows_per_slice, list_e, list_d, list_th, list_rej, tags, qmasks);
+}
 
 // ---- the slices' lists folded into slice 0's, one wave per query row ----
 template <bool WIDE>
@@ -369,11 +395,13 @@ __global__ __launch_bounds__(256) void k_exact_refine_bool(const float *__restri
 // ---- tier 2: all n original rows in float64, one workgroup per listed query row ----
 // Wave w takes data rows 16 i + 4 w + (0..3), four at a time (16 lanes each), in ascending order, and keeps its k best in an LDS
 // list sorted by (distance, id): a row enters only if it is strictly closer than the list's last (its id is larger than every
-// id the wave has seen).  The four lists are then ranked against each other.
-template <int FAM>
+// id the wave has seen).  The four lists are then ranked against each other.  MK (k_exact_f64_masked): rows whose tag word does not
+// meet the query row's mask are passed over, and the places that fewer than k allowed rows leave open get (-1, inf).
+template <int FAM, bool MK = false>
 __device__ __forceinline__ void ex_f64_body(const float *__restrict__ x, int64_t n, int d, int metric, const float *__restrict__ qraw,
                                                    const int32_t *__restrict__ qids, int k, const int32_t *__restrict__ list,
-                                                   int32_t *__restrict__ out_idx, float *__restrict__ out_dist) {
+                                                   int32_t *__restrict__ out_idx, float *__restrict__ out_dist,
+                                                   const uint64_t *__restrict__ tags = nullptr, const uint64_t *__restrict__ qmasks = nullptr) {
     __shared__ double ld[4][NND_WIDE_K];
     __shared__ int32_t li[4][NND_WIDE_K];
     __shared__ int scnt[4];
@@ -381,6 +409,8 @@ __device__ __forceinline__ void ex_f64_body(const float *__restrict__ x, int64_t
     const int q = list[blockIdx.x];
     const float *xa = qraw + (int64_t)qids[q] * d;
     const double mua = metric == 4 ? nnd_row_mean_f64<16>(xa, d, l16) : 0.0;
+    uint64_t qm = 0ull;
+    if constexpr (MK) qm = qmasks[q];
     int cnt = 0;
     double worst = INFINITY;
     for (int64_t b0 = 4 * w; b0 < n; b0 += 16) {
@@ -391,6 +421,9 @@ __device__ __forceinline__ void ex_f64_body(const float *__restrict__ x, int64_t
             const double ru = __longlong_as_double((long long)nnd_readlane_u64((uint64_t)__double_as_longlong(v.r), 16 * u));
             const int64_t ju = b0 + u;
             if (ju >= n || !(cnt < k || ru < worst)) continue;  // wave-uniform
+            if constexpr (MK) {
+                if ((tags[ju] & qm) == 0ull) continue;  // wave-uniform
+            }
             double old_d[NND_WIDE_U];
             int32_t old_i[NND_WIDE_U];
             int below = 0;
@@ -441,6 +474,13 @@ __device__ __forceinline__ void ex_f64_body(const float *__restrict__ x, int64_t
             out_dist[(size_t)q * k + rank] = (float)myr;
         }
     }
+    if constexpr (MK) {  // every allowed row is in one of the four lists while they hold fewer than k together
+        const int total = scnt[0] + scnt[1] + scnt[2] + scnt[3];
+        for (int j = total + (int)threadIdx.x; j < k; j += 256) {
+            out_idx[(size_t)q * k + j] = -1;
+            out_dist[(size_t)q * k + j] = INFINITY;
+        }
+    }
 }
 template <bool XM>
 __global__ __launch_bounds__(256) void k_exact_f64(const float *__restrict__ x, int64_t n, int d, int metric, const float *__restrict__ qraw,
@@ -453,7 +493,13 @@ __global__ __launch_bounds__(256) void k_exact_f64_bool(const float *__restrict_
                                                    int32_t *__restrict__ out_idx, float *__restrict__ out_dist) {
     ex_f64_body<NND_CODES_BOOL>(x, n, d, metric, qraw, qids, k, list, out_idx, out_dist);
 }
-
+template <int FAM>
+__global__ __launch_bounds__(256) void k_exact_f64_masked(const float *__restrict__ x, int64_t n, int d, int metric, const float *__restrict__ qraw,
+                                                   const int32_t *__restrict__ qids, int k, const int32_t *__restrict__ list,
+                                                   int32_t *__restrict__ out_idx, float *__restrict__ out_dist,
+                                                   const uint64_t *__restrict__ tags, const uint64_t *__restrict__ qmasks) {
+    ex_f64_body<FAM, true>(x, n, d, metric, qraw, qids, k, list, out_idx, out_dist, tags, qmasks);
+}
 
 // the largest nrm of the point set (codes 0, 3), or the largest |x|^2 of the rows as given (code 2), as a double; 16 lanes per row
 __global__ __launch_bounds__(256) void k_exact_nmax(const float *__restrict__ x, const float *__restrict__ nrm, int64_t n, int d, int metric,
@@ -514,9 +560,19 @@ static size_t ex_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
 template <int DC>
 static int ex_launch_scan(nnd_ctx *ctx, bool xm, bool wide, dim3 grid, const float *qx, const float *qnrm, const int32_t *qids, int self, int nq, int nq_pad,
-                          int W, int64_t rows_per_slice, uint32_t *le, float *ld, float *lth, float *lrej) {
+                          int W, int64_t rows_per_slice, uint32_t *le, float *ld, float *lth, float *lrej, const uint64_t *tags, const uint64_t *qmasks) {
     const size_t lds = sizeof(float) * ((EX_QB + EX_TB) * DC + EX_TB) + sizeof(int32_t) * EX_QB + sizeof(uint2) * EX_QB * EX_PC +
-                       (wide ? sizeof(uint64_t) * 4 * NND_WIDE_SCRATCH_WORDS : 0);
+                       (wide ? sizeof(uint64_t) * 4 * NND_WIDE_SCRATCH_WORDS : 0) + (tags ? sizeof(uint64_t) * EX_TB : 0);
+    if (tags) {  // the masked scan: one kernel template over the three families
+        auto mk = xm ? (wide ? k_exact_scan_masked<DC, NND_CODES_0_5, true> : k_exact_scan_masked<DC, NND_CODES_0_5, false>)
+                     : (wide ? k_exact_scan_masked<DC, NND_CODES_01, true> : k_exact_scan_masked<DC, NND_CODES_01, false>);
+        if (nnd_metric_bool(ctx->p.metric)) mk = wide ? k_exact_scan_masked<DC, NND_CODES_BOOL, true> : k_exact_scan_masked<DC, NND_CODES_BOOL, false>;
+        if (lds > 48 * 1024) NND_HIP_CHECK(hipFuncSetAttribute((const void *)mk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(mk, grid, dim3(256), lds, ctx->stream, ctx->xp, ctx->nrm, ctx->n, ctx->dp, nnd_kmetric(ctx), qx, qnrm, qids, self, nq, nq_pad, W,
+                           rows_per_slice, le, ld, lth, lrej, tags, qmasks);
+        NND_HIP_CHECK(hipGetLastError());
+        return 0;
+    }
     auto kern = xm ? (wide ? k_exact_scan<DC, true, true> : k_exact_scan<DC, true, false>) : (wide ? k_exact_scan<DC, false, true> : k_exact_scan<DC, false, false>);
     if (nnd_metric_bool(ctx->p.metric)) kern = wide ? k_exact_scan_bool<DC, true> : k_exact_scan_bool<DC, false>;
     if (lds > 48 * 1024) NND_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -530,8 +586,10 @@ static size_t ex_dtype_size(int dtype) { return dtype == NND_DTYPE_FLOAT64 ? 8 :
 
 // `dev` (the device entries): row ids / queries are read from, and the answers written to, memory of the handle's device -- every
 // copy below becomes device to device on the handle's stream; only the per-batch scalars cross the bus
+// `tg` (the masked entries): device pointers to the n tag words of the point set and the nq_all mask words of the query rows
 int nnd_exact_knn_impl(nnd_ctx *ctx, const int64_t *rows, const float *q, int64_t nq_all, int k, int32_t *out_idx, float *out_dist, nnd_exact_stats *st,
-                       const nnd_exact_dev *dev) {
+                       const nnd_exact_dev *dev, const nnd_exact_tags *tg) {
+    const uint64_t *tags = tg ? tg->tags_dev : nullptr;
     const int64_t n = ctx->n;
     const int d = ctx->d, dp = ctx->dp, metric = ctx->p.metric;
     const bool self = dev ? dev->q_dev == nullptr : q == nullptr, xm = metric >= 2, bm = nnd_metric_bool(metric), force_f64 = (ctx->p.flags & NND_FLAG_TEST_EXACT_F64) != 0;
@@ -616,6 +674,7 @@ int nnd_exact_knn_impl(nnd_ctx *ctx, const int64_t *rows, const float *q, int64_
             qraw = qraw_own; qx = qp; qnrm = qn;
         }
         NND_HIP_CHECK(hipMemsetAsync(n_unc, 0, sizeof(int32_t), ctx->stream));
+        const uint64_t *qmasks = tg ? tg->masks_dev + b0 : nullptr;
         int n_fallback = nq;
         if (!force_f64) {
             const int S = nnd_exact_slices_for(n, nq);
@@ -623,9 +682,9 @@ int nnd_exact_knn_impl(nnd_ctx *ctx, const int64_t *rows, const float *q, int64_
             const dim3 grid((unsigned)(nq_pad / EX_QB), (unsigned)S);
             const int t_scan = t_begin(ctx);
             int rc;
-            if (dp <= 32) rc = ex_launch_scan<32>(ctx, xm, wide, grid, qx, qnrm, qids, self, nq, nq_pad, W, rows_per_slice, le, ld, lth, lrej);
-            else if (dp <= 64) rc = ex_launch_scan<64>(ctx, xm, wide, grid, qx, qnrm, qids, self, nq, nq_pad, W, rows_per_slice, le, ld, lth, lrej);
-            else rc = ex_launch_scan<128>(ctx, xm, wide, grid, qx, qnrm, qids, self, nq, nq_pad, W, rows_per_slice, le, ld, lth, lrej);
+            if (dp <= 32) rc = ex_launch_scan<32>(ctx, xm, wide, grid, qx, qnrm, qids, self, nq, nq_pad, W, rows_per_slice, le, ld, lth, lrej, tags, qmasks);
+            else if (dp <= 64) rc = ex_launch_scan<64>(ctx, xm, wide, grid, qx, qnrm, qids, self, nq, nq_pad, W, rows_per_slice, le, ld, lth, lrej, tags, qmasks);
+            else rc = ex_launch_scan<128>(ctx, xm, wide, grid, qx, qnrm, qids, self, nq, nq_pad, W, rows_per_slice, le, ld, lth, lrej, tags, qmasks);
             if (rc) return 1;
             if (S > 1) {
                 hipLaunchKernelGGL(wide ? k_exact_merge<true> : k_exact_merge<false>, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, ctx->stream, nq, nq_pad, W, S, le, ld, lth, lrej);
@@ -649,7 +708,11 @@ int nnd_exact_knn_impl(nnd_ctx *ctx, const int64_t *rows, const float *q, int64_
         }
         if (n_fallback > 0) {
             const int t_fb = t_begin(ctx);
-            hipLaunchKernelGGL(bm ? k_exact_f64_bool : (xm ? k_exact_f64<true> : k_exact_f64<false>), dim3((unsigned)n_fallback), dim3(256), 0, ctx->stream, ctx->x_orig, n, d, metric, qraw, qids,
+            if (tags)
+                hipLaunchKernelGGL(bm ? k_exact_f64_masked<NND_CODES_BOOL> : (xm ? k_exact_f64_masked<NND_CODES_0_5> : k_exact_f64_masked<NND_CODES_01>), dim3((unsigned)n_fallback),
+                                   dim3(256), 0, ctx->stream, ctx->x_orig, n, d, metric, qraw, qids, k, unc, oi, od, tags, qmasks);
+            else
+                hipLaunchKernelGGL(bm ? k_exact_f64_bool : (xm ? k_exact_f64<true> : k_exact_f64<false>), dim3((unsigned)n_fallback), dim3(256), 0, ctx->stream, ctx->x_orig, n, d, metric, qraw, qids,
                                k, unc, oi, od);
             NND_HIP_CHECK(hipGetLastError());
             t_end(ctx, t_fb, &s.ms_fallback, true);

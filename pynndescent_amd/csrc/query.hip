@@ -77,6 +77,7 @@ struct nnd_searcher_s {
     uint32_t *allow = nullptr;            // the filter's bitset over the searcher's numbering, (n + 31) / 32 words (allocated on first use)
     unsigned long long *fstat = nullptr;  // 2: allowed rows of the last filter, its out-of-range flag
     bool filter_on = false;               // nnd_searcher_set_filter*: the query entries run the filtered instances
+    uint64_t *tags = nullptr;             // nnd_searcher_set_tags*: (n) tag words in the searcher's numbering (the tagged query entries)
     nnd_devmem mem;            // owner of the device buffers above (devmem.h)
     char err[512] = {0};
     void set_error(const char *fmt, ...) {
@@ -191,8 +192,11 @@ __device__ __forceinline__ float q_rerank_dist(const float *__restrict__ x, cons
 // bit in `allow` (a bitset over the searcher's numbering) is set.  It is still visited, pushed to the frontier and expanded, so
 // the bound, the stop rule and the hand-over to the big tier are those of the unfiltered walk relative to the allowed rows; the
 // rerank's candidates are the walk's results and so all allowed.  The other instances never read `allow`.
+// TG: tagged (the instances of k_query_tagged / k_query_bool_tagged): the same rule with a predicate per query -- the vertex's tag
+// word (`tags`, the searcher's numbering) must meet the query's mask word (`qmasks`, one per query of the call, read once into
+// scalar registers: one wave serves one query).  A query whose mask is 0 has no allowed row and does not walk.
 // The body is shared by the kernels k_query (BM = false) and k_query_bool below.
-template <bool BIG, int KU, bool Q8, bool RR, bool BM, bool FL = false>
+template <bool BIG, int KU, bool Q8, bool RR, bool BM, bool FL = false, bool TG = false>
 __device__ __forceinline__ void q_body(const float *__restrict__ x, const float *__restrict__ xn2, int dp, int d, int metric,
                                                int64_t n, const int32_t *__restrict__ indptr, const int32_t *__restrict__ indices,
                                                const float *__restrict__ hyper, const float *__restrict__ offsets,
@@ -204,7 +208,8 @@ __device__ __forceinline__ void q_body(const float *__restrict__ x, const float 
                                                int n_list, unsigned char *__restrict__ scratch, size_t scratch_stride,
                                                const uint8_t *__restrict__ codes, int dcs, const float *__restrict__ lut,
                                                const float *__restrict__ cn2, int k_out,
-                                               const uint32_t *__restrict__ allow = nullptr) {
+                                               const uint32_t *__restrict__ allow = nullptr,
+                                               const uint64_t *__restrict__ tags = nullptr, const uint64_t *__restrict__ qmasks = nullptr) {
     extern __shared__ __attribute__((aligned(16))) unsigned char qsm[];
     const int lane = nnd_lane(), w = threadIdx.x >> 6;
     if constexpr (Q8) {  // the codebook, once per workgroup (256 threads: one entry each)
@@ -250,6 +255,12 @@ __device__ __forceinline__ void q_body(const float *__restrict__ x, const float 
     float qn2 = nnd_wave_sum_f32(part);
     for (int64_t s = lane; s < vis_words; s += 64) vis[s] = BIG ? 0u : Q_EMPTY;
     bool dead = false;
+    uint64_t qmask = 0;  // TG: this query's mask word, wave-uniform
+    if constexpr (TG) {
+        const uint64_t m = qmasks[qi];
+        qmask = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(m >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)m);
+        dead = qmask == 0ull;
+    }
     if (metric == 1 || metric == 2) {  // cosine / dot (the reference's normalize_query, pynndescent_.py:1764-1768)
         const float nrm = sqrtf(qn2);
         if (nrm > 0.0f) {
@@ -315,8 +326,9 @@ __device__ __forceinline__ void q_body(const float *__restrict__ x, const float 
             }
         }
     };
-    // FL: may `vc` (wave-uniform) enter the result list -- one word of the allow bitset
+    // FL: may `vc` (wave-uniform) enter the result list -- one word of the allow bitset; TG: its tag word against the query's mask
     auto allowed = [&](int32_t vc) -> bool {
+        if constexpr (TG) return (tags[(uint32_t)__builtin_amdgcn_readfirstlane(vc)] & qmask) != 0ull;
         if constexpr (!FL) return true;
         const uint32_t u = (uint32_t)__builtin_amdgcn_readfirstlane(vc);
         return ((allow[u >> 5] >> (u & 31u)) & 1u) != 0u;
@@ -639,6 +651,40 @@ __global__ __launch_bounds__(256) void k_query_bool_filtered(const float *__rest
                                n_neighbors, seed, out_idx, out_dist, overflow, qlist, n_list, scratch, scratch_stride, codes, dcs, lut, cn2, k_out, allow);
 }
 
+// the tagged siblings (TG): the same arguments, the tag words and the queries' mask words
+template <bool BIG, int KU, bool Q8 = false, bool RR = Q8>
+__global__ __launch_bounds__(256) void k_query_tagged(const float *__restrict__ x, const float *__restrict__ xn2, int dp, int d, int metric,
+                                               int64_t n, const int32_t *__restrict__ indptr, const int32_t *__restrict__ indices,
+                                               const float *__restrict__ hyper, const float *__restrict__ offsets,
+                                               const int32_t *__restrict__ children, const int32_t *__restrict__ tree_idx,
+                                               int64_t n_nodes, const float *__restrict__ queries, int64_t nq, int k, float epsilon,
+                                               float min_distance, int n_neighbors, uint32_t seed, int32_t *__restrict__ out_idx,
+                                               float *__restrict__ out_dist, uint8_t *__restrict__ overflow /* (nq) LDS tier: set when the query needs the big tier */,
+                                               const int32_t *__restrict__ qlist /* BIG: the queries of this batch */,
+                                               int n_list, unsigned char *__restrict__ scratch, size_t scratch_stride,
+                                               const uint8_t *__restrict__ codes, int dcs, const float *__restrict__ lut,
+                                               const float *__restrict__ cn2, int k_out,
+                                               const uint64_t *__restrict__ tags /* (n) */, const uint64_t *__restrict__ qmasks /* (nq) */) {
+    q_body<BIG, KU, Q8, RR, false, false, true>(x, xn2, dp, d, metric, n, indptr, indices, hyper, offsets, children, tree_idx, n_nodes, queries, nq, k, epsilon, min_distance,
+                               n_neighbors, seed, out_idx, out_dist, overflow, qlist, n_list, scratch, scratch_stride, codes, dcs, lut, cn2, k_out, nullptr, tags, qmasks);
+}
+template <bool BIG, int KU>
+__global__ __launch_bounds__(256) void k_query_bool_tagged(const float *__restrict__ x, const float *__restrict__ xn2, int dp, int d, int metric,
+                                               int64_t n, const int32_t *__restrict__ indptr, const int32_t *__restrict__ indices,
+                                               const float *__restrict__ hyper, const float *__restrict__ offsets,
+                                               const int32_t *__restrict__ children, const int32_t *__restrict__ tree_idx,
+                                               int64_t n_nodes, const float *__restrict__ queries, int64_t nq, int k, float epsilon,
+                                               float min_distance, int n_neighbors, uint32_t seed, int32_t *__restrict__ out_idx,
+                                               float *__restrict__ out_dist, uint8_t *__restrict__ overflow /* (nq) LDS tier: set when the query needs the big tier */,
+                                               const int32_t *__restrict__ qlist /* BIG: the queries of this batch */,
+                                               int n_list, unsigned char *__restrict__ scratch, size_t scratch_stride,
+                                               const uint8_t *__restrict__ codes, int dcs, const float *__restrict__ lut,
+                                               const float *__restrict__ cn2, int k_out,
+                                               const uint64_t *__restrict__ tags /* (n) */, const uint64_t *__restrict__ qmasks /* (nq) */) {
+    q_body<BIG, KU, false, false, true, false, true>(x, xn2, dp, d, metric, n, indptr, indices, hyper, offsets, children, tree_idx, n_nodes, queries, nq, k, epsilon, min_distance,
+                               n_neighbors, seed, out_idx, out_dist, overflow, qlist, n_list, scratch, scratch_stride, codes, dcs, lut, cn2, k_out, nullptr, tags, qmasks);
+}
+
 
 // the searcher's copy of the rows for the codes 2..5: the build's row transform (metric.h), one wave per row, in place --
 // dot: L2-normalised; correlation: minus the row mean (float64), then normalised; hellinger: sqrt, then normalised
@@ -751,6 +797,50 @@ __global__ __launch_bounds__(256) void k_filter_bitset(const uint8_t *__restrict
         bits[i >> 5] = (uint32_t)m;
         if (i + 32 < n) bits[(i >> 5) + 1] = (uint32_t)(m >> 32);
         if (m) atomicAdd(&fstat[0], (unsigned long long)__popcll(m));
+    }
+}
+
+// ---- per-query filters: the rows' tag words (nnd_searcher_set_tags*) ----
+// the tag words in the searcher's numbering: out[i] = tags[order[i]] (order nullptr: the identity); the sibling of k_filter_bitset
+__global__ __launch_bounds__(256) void k_tags_gather(const uint64_t *__restrict__ tags, const int32_t *__restrict__ order, int64_t n,
+                                                     uint64_t *__restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int64_t r = order ? (int64_t)order[i] : i;
+    out[i] = r >= 0 && r < n ? tags[r] : 0ull;
+}
+// counts[u] += rows whose tag word meets masks[u], u < n_masks: one pass over the tag words.  A workgroup keeps Q_COUNT_ROWS rows
+// per thread in registers and takes the masks (wave-uniform loads) in groups of Q_COUNT_MASKS: a wave reduction per mask, the four
+// waves' sums meet in LDS, and one global atomic per workgroup and mask adds what is not zero.
+#define Q_COUNT_ROWS 8
+#define Q_COUNT_MASKS 1024
+__global__ __launch_bounds__(256) void k_tags_count(const uint64_t *__restrict__ tags, int64_t n, const uint64_t *__restrict__ masks, int n_masks,
+                                                    unsigned long long *__restrict__ counts) {
+    __shared__ int part[Q_COUNT_MASKS];
+    const int lane = nnd_lane();
+    uint64_t t[Q_COUNT_ROWS];
+    const int64_t base = (int64_t)blockIdx.x * (256 * Q_COUNT_ROWS) + threadIdx.x;
+#pragma unroll
+    for (int j = 0; j < Q_COUNT_ROWS; j++) {
+        const int64_t i = base + 256 * j;
+        t[j] = i < n ? tags[i] : 0ull;
+    }
+    for (int u0 = 0; u0 < n_masks; u0 += Q_COUNT_MASKS) {
+        const int nu = n_masks - u0 < Q_COUNT_MASKS ? n_masks - u0 : Q_COUNT_MASKS;
+        for (int u = threadIdx.x; u < nu; u += 256) part[u] = 0;
+        __syncthreads();
+        for (int u = 0; u < nu; u++) {
+            const uint64_t m = masks[u0 + u];
+            int c = 0;
+#pragma unroll
+            for (int j = 0; j < Q_COUNT_ROWS; j++) c += (t[j] & m) != 0ull ? 1 : 0;
+            c = nnd_wave_sum_i32(c);
+            if (lane == 0 && c) atomicAdd(&part[u], c);
+        }
+        __syncthreads();
+        for (int u = threadIdx.x; u < nu; u += 256)
+            if (part[u]) atomicAdd(&counts[u0 + u], (unsigned long long)part[u]);
+        __syncthreads();
     }
 }
 
@@ -950,11 +1040,22 @@ static auto query_kernel_filtered(q_form form, int k) -> decltype(&k_query_filte
         default: return k > 128 ? k_query_filtered<BIG, 4> : (k > 64 ? k_query_filtered<BIG, 2> : k_query_filtered<BIG, 1>);
     }
 }
+template <bool BIG>
+static auto query_kernel_tagged(q_form form, int k) -> decltype(&k_query_tagged<BIG, 1>) {
+    switch (form) {
+        case Q_FORM_U8: return k > 128 ? k_query_tagged<BIG, 4, true> : (k > 64 ? k_query_tagged<BIG, 2, true> : k_query_tagged<BIG, 1, true>);
+        case Q_FORM_BOOL: return k > 128 ? k_query_bool_tagged<BIG, 4> : (k > 64 ? k_query_bool_tagged<BIG, 2> : k_query_bool_tagged<BIG, 1>);
+        case Q_FORM_RERANK:
+            return k > 128 ? k_query_tagged<BIG, 4, false, true> : (k > 64 ? k_query_tagged<BIG, 2, false, true> : k_query_tagged<BIG, 1, false, true>);
+        default: return k > 128 ? k_query_tagged<BIG, 4> : (k > 64 ? k_query_tagged<BIG, 2> : k_query_tagged<BIG, 1>);
+    }
+}
 
 // every query entry point: the walk keeps k results (the float rows) or k = search_k results and reranks them to k_out
 // (Q_FORM_U8: the walk on the code rows; Q_FORM_RERANK: on the float rows); out_idx / out_dist are (nq, k_out)
 static int searcher_run(nnd_searcher_s *s, const float *queries, int64_t nq, int32_t k, int32_t k_out, float epsilon, q_form form,
-                        int32_t *out_idx, float *out_dist, bool on_device = false, hipStream_t user_stream = nullptr) {
+                        int32_t *out_idx, float *out_dist, bool on_device = false, hipStream_t user_stream = nullptr,
+                        const uint64_t *qmasks = nullptr /* the tagged entries: (nq) mask words, where the queries are */) {
     const bool q8 = form == Q_FORM_U8;
     if (form == Q_FORM_FLOAT && nnd_metric_bool(s->metric)) form = Q_FORM_BOOL;
     auto kq_lds = query_kernel<false>(form, k);
@@ -962,6 +1063,9 @@ static int searcher_run(nnd_searcher_s *s, const float *queries, int64_t nq, int
     auto fq_lds = query_kernel_filtered<false>(form, k);  // launched instead while a filter is set (nnd_searcher_set_filter*)
     auto fq_big = query_kernel_filtered<true>(form, k);
     const uint32_t *allow = s->filter_on ? s->allow : nullptr;
+    auto tq_lds = query_kernel_tagged<false>(form, k);  // launched instead by the tagged entries (nnd_searcher_query_tagged*)
+    auto tq_big = query_kernel_tagged<true>(form, k);
+    const uint64_t *dmasks = nullptr;
     if (nq <= 0) return 0;
     if (nq >= (int64_t)0x7FFFFFF0) { s->set_error("nnd_searcher_query: too many queries in one call"); return 1; }
     S_HIP(hipSetDevice(s->device));
@@ -984,11 +1088,25 @@ static int searcher_run(nnd_searcher_s *s, const float *queries, int64_t nq, int
         uint8_t *dov = tmp.get<uint8_t>(s, (size_t)nq);
         if (!dq || !dd || !di || !dov) { s->set_error("nnd_searcher_query: out of device memory"); rc = 1; break; }
         if (!on_device && hipMemcpyAsync(dq, queries, sizeof(float) * (size_t)nq * s->d, hipMemcpyHostToDevice, st) != hipSuccess) { s->set_error("H2D of the queries failed"); rc = 1; break; }
+        if (qmasks) {
+            dmasks = qmasks;
+            if (!on_device) {
+                uint64_t *dm = tmp.get<uint64_t>(s, (size_t)nq);
+                if (!dm) { rc = 1; break; }
+                if (hipMemcpyAsync(dm, qmasks, sizeof(uint64_t) * (size_t)nq, hipMemcpyHostToDevice, st) != hipSuccess) { s->set_error("H2D of the query masks failed"); rc = 1; break; }
+                dmasks = dm;
+            }
+        }
         if (!s->force_big) {
-            if (smem > 64 * 1024 && hipFuncSetAttribute(allow ? (const void *)fq_lds : (const void *)kq_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) {
+            if (smem > 64 * 1024 && hipFuncSetAttribute(dmasks ? (const void *)tq_lds : allow ? (const void *)fq_lds : (const void *)kq_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) {
                 s->set_error("nnd_searcher_query: rows of %d floats need %zu bytes of LDS per workgroup", s->d, smem); rc = 1; break;
             }
-            if (allow)
+            if (dmasks)
+                hipLaunchKernelGGL(tq_lds, dim3((unsigned)((nq + 3) / 4)), dim3(256), smem, st, s->x, s->xn2, s->dp, s->d, s->metric, s->n,
+                                   s->indptr, s->indices, s->hyper, s->offsets, s->children, s->tree_idx, s->n_nodes, dq, nq, k, epsilon,
+                                   s->min_distance, s->n_neighbors, s->seed, di, dd, dov, (const int32_t *)nullptr, 0, (unsigned char *)nullptr, (size_t)0,
+                                   (const uint8_t *)s->codes, s->dcs, (const float *)s->lut, (const float *)s->cn2, k_out, (const uint64_t *)s->tags, dmasks);
+            else if (allow)
                 hipLaunchKernelGGL(fq_lds, dim3((unsigned)((nq + 3) / 4)), dim3(256), smem, st, s->x, s->xn2, s->dp, s->d, s->metric, s->n,
                                    s->indptr, s->indices, s->hyper, s->offsets, s->children, s->tree_idx, s->n_nodes, dq, nq, k, epsilon,
                                    s->min_distance, s->n_neighbors, s->seed, di, dd, dov, (const int32_t *)nullptr, 0, (unsigned char *)nullptr, (size_t)0,
@@ -1019,7 +1137,12 @@ static int searcher_run(nnd_searcher_s *s, const float *queries, int64_t nq, int
             if (hipMemcpyAsync(dlist, again.data(), sizeof(int32_t) * again.size(), hipMemcpyHostToDevice, st) != hipSuccess) { s->set_error("H2D of the query list failed"); rc = 1; break; }
             for (size_t b0 = 0; b0 < again.size() && !rc; b0 += batch) {
                 const int nb = (int)(again.size() - b0 < batch ? again.size() - b0 : batch);
-                if (allow)
+                if (dmasks)
+                    hipLaunchKernelGGL(tq_big, dim3((unsigned)((nb + 3) / 4)), dim3(256), 4 * per_wave_big + lut_bytes, st, s->x, s->xn2, s->dp, s->d,
+                                       s->metric, s->n, s->indptr, s->indices, s->hyper, s->offsets, s->children, s->tree_idx, s->n_nodes, dq, nq, k, epsilon,
+                                       s->min_distance, s->n_neighbors, s->seed, di, dd, (uint8_t *)nullptr, (const int32_t *)(dlist + b0), nb, scratch, stride,
+                                       (const uint8_t *)s->codes, s->dcs, (const float *)s->lut, (const float *)s->cn2, k_out, (const uint64_t *)s->tags, dmasks);
+                else if (allow)
                     hipLaunchKernelGGL(fq_big, dim3((unsigned)((nb + 3) / 4)), dim3(256), 4 * per_wave_big + lut_bytes, st, s->x, s->xn2, s->dp, s->d,
                                        s->metric, s->n, s->indptr, s->indices, s->hyper, s->offsets, s->children, s->tree_idx, s->n_nodes, dq, nq, k, epsilon,
                                        s->min_distance, s->n_neighbors, s->seed, di, dd, (uint8_t *)nullptr, (const int32_t *)(dlist + b0), nb, scratch, stride,
@@ -1257,4 +1380,118 @@ extern "C" int32_t nnd_searcher_query_rerank_device(nnd_searcher_t s, const floa
     }
     if (device_args(s, "nnd_searcher_query_rerank_device", queries_dev, nq, out_idx_dev, out_dist_dev)) return 1;
     return searcher_run(s, queries_dev, nq, search_k, k, epsilon, Q_FORM_RERANK, out_idx_dev, out_dist_dev, true, (hipStream_t)hip_stream);
+}
+
+// ---- per-query filters (include/pynnd_amd.h): the tag words, the counts per mask, the tagged query ----
+static int searcher_gather_tags(nnd_searcher_s *s, const uint64_t *tags_dev, const int32_t *order_dev, hipStream_t st) {
+    if (!s->tags) S_ALLOC(&s->tags, (size_t)s->n);
+    hipLaunchKernelGGL(k_tags_gather, dim3((unsigned)((s->n + 255) / 256)), dim3(256), 0, st, tags_dev, order_dev, s->n, s->tags);
+    S_HIP(hipGetLastError());
+    S_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+extern "C" int32_t nnd_searcher_clear_tags(nnd_searcher_t s) {
+    if (!s) { snprintf(g_serr, sizeof(g_serr), "nnd_searcher_clear_tags: null searcher"); return 1; }
+    S_HIP(hipSetDevice(s->device));
+    S_HIP(hipStreamSynchronize(s->stream));
+    s->mem.free(&s->tags);
+    return 0;
+}
+extern "C" int32_t nnd_searcher_set_tags(nnd_searcher_t s, const uint64_t *tags, const int32_t *order) {
+    if (!s) { snprintf(g_serr, sizeof(g_serr), "nnd_searcher_set_tags: null searcher"); return 1; }
+    if (!tags) { s->set_error("nnd_searcher_set_tags: tags missing"); return 1; }
+    S_HIP(hipSetDevice(s->device));
+    nnd_scratch tmp;  // released on return, behind the synchronise of searcher_gather_tags
+    uint64_t *dtags = tmp.get<uint64_t>(s, (size_t)s->n);
+    int32_t *dorder = order ? tmp.get<int32_t>(s, (size_t)s->n) : nullptr;
+    if (!dtags || (order && !dorder)) return 1;
+    S_HIP(hipMemcpyAsync(dtags, tags, sizeof(uint64_t) * (size_t)s->n, hipMemcpyHostToDevice, s->stream));
+    if (order) S_HIP(hipMemcpyAsync(dorder, order, sizeof(int32_t) * (size_t)s->n, hipMemcpyHostToDevice, s->stream));
+    const int rc = searcher_gather_tags(s, dtags, dorder, s->stream);
+    if (rc) (void)hipStreamSynchronize(s->stream);
+    return rc;
+}
+extern "C" int32_t nnd_searcher_set_tags_device(nnd_searcher_t s, const uint64_t *tags_dev, const int32_t *order_dev, void *hip_stream) {
+    if (!s) { snprintf(g_serr, sizeof(g_serr), "nnd_searcher_set_tags_device: null searcher"); return 1; }
+    if (!tags_dev) { s->set_error("nnd_searcher_set_tags_device: tags missing"); return 1; }
+    S_HIP(hipSetDevice(s->device));
+    return searcher_gather_tags(s, tags_dev, order_dev, (hipStream_t)hip_stream);
+}
+static int searcher_count_tags(nnd_searcher_s *s, const uint64_t *masks_dev, int32_t n_masks, unsigned long long *counts_dev, hipStream_t st) {
+    S_HIP(hipMemsetAsync(counts_dev, 0, sizeof(unsigned long long) * (size_t)n_masks, st));
+    const int64_t per_block = 256 * Q_COUNT_ROWS;
+    hipLaunchKernelGGL(k_tags_count, dim3((unsigned)((s->n + per_block - 1) / per_block)), dim3(256), 0, st, (const uint64_t *)s->tags, s->n, masks_dev, (int)n_masks,
+                       counts_dev);
+    S_HIP(hipGetLastError());
+    return 0;
+}
+static int count_args(nnd_searcher_s *s, const char *who, const void *masks, int32_t n_masks, const void *counts) {
+    if (!s->tags) { s->set_error("%s: the searcher has no tags (nnd_searcher_set_tags first)", who); return 1; }
+    if (n_masks < 0 || (n_masks > 0 && (!masks || !counts))) { s->set_error("%s: masks or counts missing", who); return 1; }
+    return 0;
+}
+extern "C" int32_t nnd_searcher_count_tags(nnd_searcher_t s, const uint64_t *masks, int32_t n_masks, int64_t *counts) {
+    if (!s) { snprintf(g_serr, sizeof(g_serr), "nnd_searcher_count_tags: null searcher"); return 1; }
+    if (count_args(s, "nnd_searcher_count_tags", masks, n_masks, counts)) return 1;
+    if (n_masks == 0) return 0;
+    S_HIP(hipSetDevice(s->device));
+    nnd_scratch tmp;
+    uint64_t *dm = tmp.get<uint64_t>(s, (size_t)n_masks);
+    unsigned long long *dc = tmp.get<unsigned long long>(s, (size_t)n_masks);
+    if (!dm || !dc) return 1;
+    int rc = 0;
+    if (hipMemcpyAsync(dm, masks, sizeof(uint64_t) * (size_t)n_masks, hipMemcpyHostToDevice, s->stream) != hipSuccess) { s->set_error("nnd_searcher_count_tags: H2D of the masks failed"); rc = 1; }
+    if (!rc) rc = searcher_count_tags(s, dm, n_masks, dc, s->stream);
+    if (!rc && hipMemcpyAsync(counts, dc, sizeof(int64_t) * (size_t)n_masks, hipMemcpyDeviceToHost, s->stream) != hipSuccess) { s->set_error("nnd_searcher_count_tags: D2H of the counts failed"); rc = 1; }
+    if (hipStreamSynchronize(s->stream) != hipSuccess && !rc) { s->set_error("nnd_searcher_count_tags: kernel failed: %s", hipGetErrorString(hipGetLastError())); rc = 1; }
+    return rc;
+}
+extern "C" int32_t nnd_searcher_count_tags_device(nnd_searcher_t s, const uint64_t *masks_dev, int32_t n_masks, int64_t *counts_dev, void *hip_stream) {
+    if (!s) { snprintf(g_serr, sizeof(g_serr), "nnd_searcher_count_tags_device: null searcher"); return 1; }
+    if (count_args(s, "nnd_searcher_count_tags_device", masks_dev, n_masks, counts_dev)) return 1;
+    if (n_masks == 0) return 0;
+    S_HIP(hipSetDevice(s->device));
+    if (searcher_count_tags(s, masks_dev, n_masks, (unsigned long long *)counts_dev, (hipStream_t)hip_stream)) return 1;
+    S_HIP(hipStreamSynchronize((hipStream_t)hip_stream));
+    return 0;
+}
+// the tagged query: `form` NND_QUERY_FLOAT (search_k is ignored), NND_QUERY_PROXY or NND_QUERY_RERANK -- the checks of the three entries
+static int tagged_args(nnd_searcher_s *s, const char *who, int32_t form, int32_t k, int32_t *search_k, const void *masks, int64_t nq, q_form *qf) {
+    if (!s->tags) { s->set_error("%s: the searcher has no tags (nnd_searcher_set_tags first)", who); return 1; }
+    if (s->filter_on) { s->set_error("%s: the searcher has a filter set; an allow set and query masks do not combine", who); return 1; }
+    if (nq > 0 && !masks) { s->set_error("%s: masks missing", who); return 1; }
+    if (form == NND_QUERY_FLOAT) {
+        if (k < 1 || k > 256) { s->set_error("%s: k must be in 1..256 (got %d)", who, k); return 1; }
+        if (s->metric == NND_METRIC_PROXY_INNER_PRODUCT) { s->set_error("%s: metric %d is a proxy distance: its queries take NND_QUERY_RERANK", who, s->metric); return 1; }
+        *search_k = k;
+        *qf = Q_FORM_FLOAT;
+        return 0;
+    }
+    if (form == NND_QUERY_PROXY) {
+        if (!s->codes) { s->set_error("%s: the searcher has no codes (nnd_searcher_quantize_u8 first)", who); return 1; }
+        *qf = Q_FORM_U8;
+    } else if (form == NND_QUERY_RERANK) {
+        if (s->metric != NND_METRIC_PROXY_INNER_PRODUCT) { s->set_error("%s: metric %d has no true distance to rerank by", who, s->metric); return 1; }
+        *qf = Q_FORM_RERANK;
+    } else {
+        s->set_error("%s: form must be NND_QUERY_FLOAT, NND_QUERY_PROXY or NND_QUERY_RERANK (got %d)", who, form);
+        return 1;
+    }
+    if (*search_k < 1 || *search_k > 256 || k < 1 || k > *search_k) { s->set_error("%s: need 1 <= k <= search_k <= 256 (got k %d, search_k %d)", who, k, *search_k); return 1; }
+    return 0;
+}
+extern "C" int32_t nnd_searcher_query_tagged(nnd_searcher_t s, int32_t form, const float *queries, int64_t nq, int32_t k, int32_t search_k, float epsilon,
+                                             const uint64_t *masks, int32_t *out_idx, float *out_dist) {
+    if (!s) { snprintf(g_serr, sizeof(g_serr), "nnd_searcher_query_tagged: null searcher"); return 1; }
+    q_form qf;
+    if (tagged_args(s, "nnd_searcher_query_tagged", form, k, &search_k, masks, nq, &qf)) return 1;
+    return searcher_run(s, queries, nq, search_k, k, epsilon, qf, out_idx, out_dist, false, nullptr, masks);
+}
+extern "C" int32_t nnd_searcher_query_tagged_device(nnd_searcher_t s, int32_t form, const float *queries_dev, int64_t nq, int32_t k, int32_t search_k,
+                                                    float epsilon, const uint64_t *masks_dev, int32_t *out_idx_dev, float *out_dist_dev, void *hip_stream) {
+    if (!s) { snprintf(g_serr, sizeof(g_serr), "nnd_searcher_query_tagged_device: null searcher"); return 1; }
+    q_form qf;
+    if (tagged_args(s, "nnd_searcher_query_tagged_device", form, k, &search_k, masks_dev, nq, &qf)) return 1;
+    if (device_args(s, "nnd_searcher_query_tagged_device", queries_dev, nq, out_idx_dev, out_dist_dev)) return 1;
+    return searcher_run(s, queries_dev, nq, search_k, k, epsilon, qf, out_idx_dev, out_dist_dev, true, (hipStream_t)hip_stream, masks_dev);
 }

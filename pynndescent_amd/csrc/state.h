@@ -367,8 +367,14 @@ struct nnd_exact_dev {
     const void *q_dev;
     int q_dtype;
 };
+// `tg`: the masked search -- data row c belongs to query row i's point set iff tags_dev[c] & masks_dev[i] != 0 (device pointers: n
+// tag words, nq mask words in the order of the query rows); the answer is exact among those rows, short rows end in (-1, inf)
+struct nnd_exact_tags {
+    const uint64_t *tags_dev;
+    const uint64_t *masks_dev;
+};
 int nnd_exact_knn_impl(nnd_ctx *ctx, const int64_t *rows, const float *q, int64_t nq, int k, int32_t *out_idx, float *out_dist, nnd_exact_stats *st,
-                       const nnd_exact_dev *dev = nullptr);
+                       const nnd_exact_dev *dev = nullptr, const nnd_exact_tags *tg = nullptr);
 int nnd_exact_slices_for(int64_t n, int64_t nq);  // data slices (gridDim.y) of the scan for nq query rows
 int nnd_read_counters(nnd_ctx *ctx);  // device -> ctx->h_counters (synchronises the stream)
 int nnd_zero_counters(nnd_ctx *ctx);

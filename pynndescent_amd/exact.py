@@ -2,7 +2,7 @@
 """
 import numpy as np
 
-from . import _capi, device_arrays, linear_map, sparse_input
+from . import _capi, device_arrays, linear_map, sparse_input, tags as tagwords
 from .build import _check_array_no_scan, _raise_if_nonfinite
 from .device_arrays import (_check_device_array, _device_corrected, _DeviceLinear, _DeviceRowsView, _dtype_name, _ids_to_host,
                             _is_device_array, _OnTorchStream, _rows_to_host, _shape_of)
@@ -45,7 +45,7 @@ def _exact_linear_rows(metric, m, metric_kwds, data, queries, device):
     return _capi.linear_rows_host(lin.kind, lin.a, lin.shift, data, device=device), queries
 
 
-def _exact_knn_sparse(data, queries, k, metric, m, rows, device, return_stats, metric_kwds):
+def _exact_knn_sparse(data, queries, k, metric, m, rows, device, return_stats, metric_kwds, words=None):
     """``exact_knn`` with a ``scipy.sparse`` ``data`` and / or ``queries``: the metric rule of sparse input, then whatever is
     sparse is uploaded as CSR and made dense on the device (sparse_input.py), host ``data`` given with sparse queries is
     uploaded, and the device route searches.  Scipy or numpy ``data`` gets numpy answers with the host's correction (the bits of
@@ -65,11 +65,34 @@ def _exact_knn_sparse(data, queries, k, metric, m, rows, device, return_stats, m
     ordinal = getattr(data.device, "index", None) or 0
     if sparse_input.is_sparse(queries):
         queries = sparse_input.query_rows(queries, data.shape[1], ordinal, what="queries")
-    return _exact_knn_device(data, queries, k, metric, m, rows, ordinal, return_stats, host_answers=host_answers)
+    return _exact_knn_device(data, queries, k, metric, m, rows, ordinal, return_stats, host_answers=host_answers, words=words)
+
+
+def _check_tag_arguments(data, queries, rows, row_tags, query_tags, device):
+    """``(tags, masks)`` of a masked ``exact_knn`` call, each as ``tags.check_words`` returns it, or None without them."""
+    if row_tags is None and query_tags is None:
+        return None
+    if row_tags is None or query_tags is None:
+        raise ValueError("exact_knn takes row_tags and query_tags together: a predicate needs both sides")
+    n = int(_shape_of(data)[0])
+    if _is_device_array(data):
+        device = getattr(data.device, "index", None) or 0
+    m = int(_shape_of(queries)[0]) if queries is not None else (n if rows is None else int(_shape_of(rows)[0]))
+    return (tagwords.check_words(row_tags, n, device, "row_tags", "row"),
+            tagwords.check_words(query_tags, m, device, "query_tags", "query"))
+
+
+def _unfilled_to_inf(idx, dist):
+    """The places no allowed row fills hold (-1, inf) whatever the metric's correction made of inf."""
+    if _is_device_array(dist):
+        return dist.masked_fill(idx < 0, float("inf"))
+    dist = np.array(dist, copy=True)
+    dist[idx < 0] = np.inf
+    return dist
 
 
 def exact_knn(data, queries=None, k=10, metric="euclidean", rows=None, device=0, return_stats=False, metric_kwds=None,
-              _host_answers=False):
+              _host_answers=False, row_tags=None, query_tags=None):
     """Exact ``k`` nearest neighbours by brute force on the GPU (csrc/exact.hip): of every row of ``data`` (self included), of the
     rows ``rows`` of it, or of the external ``queries``.  Returns ``(indices int32 (m, k), distances float32-precision (m, k))``
     in the metric's own space (the correction ``NNDescent.neighbor_graph`` applies), rows ascending, ties to the smaller id;
@@ -90,21 +113,28 @@ def exact_knn(data, queries=None, k=10, metric="euclidean", rows=None, device=0,
 
     ``data`` and / or ``queries`` may be ``scipy.sparse`` matrices, for the metrics ``NNDescent`` takes with sparse input: they
     are made dense on the device (sparse_input.py) and the device route searches; the answers are numpy arrays, those of the dense
-    call bit for bit, unless ``data`` is a tensor."""
+    call bit for bit, unless ``data`` is a tensor.
+
+    ``row_tags`` and ``query_tags`` (both or neither; DESIGN.md "Per-query filters"): 64 tag bits per row of ``data`` and a mask
+    word per query -- with ``queries=None`` per row searched, the masks belonging to the rows themselves -- each a 1-D numpy
+    ``uint64`` / ``int64`` array or an ``int64`` tensor on the device.  Row r is a candidate of query i iff
+    ``row_tags[r] & query_tags[i] != 0``, and the answer is exact by (float64 distance, id) among those rows: the ground truth for
+    recall under a predicate.  Places that fewer than ``k`` such rows leave open hold (-1, inf)."""
     if queries is not None and rows is not None:
         raise ValueError("exact_knn takes `queries` (external points) or `rows` (ids of data rows), not both")
+    words = _check_tag_arguments(data, queries, rows, row_tags, query_tags, device)
     k = int(k)
     if k > 256:
         raise NotImplementedError("pynndescent_amd.exact_knn keeps at most k <= 256 neighbours per row (got k = %d)" % k)
     m = _metric_record(metric)
     _no_exact_for_proxy(metric, m, "exact_knn")
     if sparse_input.is_sparse(data) or sparse_input.is_sparse(queries):
-        return _exact_knn_sparse(data, queries, k, metric, m, rows, device, return_stats, metric_kwds)
+        return _exact_knn_sparse(data, queries, k, metric, m, rows, device, return_stats, metric_kwds, words)
     if m.linear:  # (metric_kwds is validated in there, before any device work)
         data, queries = _exact_linear_rows(metric, m, metric_kwds, data, queries, device)
         metric, m = "euclidean", _METRICS["euclidean"]
     if _is_device_array(data):
-        return _exact_knn_device(data, queries, k, metric, m, rows, device, return_stats, host_answers=_host_answers)
+        return _exact_knn_device(data, queries, k, metric, m, rows, device, return_stats, host_answers=_host_answers, words=words)
     queries, rows = _rows_to_host(queries), _ids_to_host(rows)  # (the results live where the data lives)
     data = _check_array_no_scan(data)
     n = data.shape[0]
@@ -135,17 +165,20 @@ def exact_knn(data, queries=None, k=10, metric="euclidean", rows=None, device=0,
     try:
         builder.set_data_host(data)
         _raise_if_nonfinite(builder, data)
+        tm = {} if words is None else {"tags": tagwords.to_host(*words[0]), "masks": tagwords.to_host(*words[1])}
         if queries is not None:
-            idx, dist, stats = builder.exact_knn_queries(queries, k)
+            idx, dist, stats = builder.exact_knn_queries(queries, k, **tm)
         else:
-            idx, dist, stats = builder.exact_knn(rows, k)
+            idx, dist, stats = builder.exact_knn(rows, k, **tm)
     finally:
         builder.close()
     dist = m.correction(dist)
+    if words is not None:
+        dist = _unfilled_to_inf(idx, dist)
     return (idx, dist, stats) if return_stats else (idx, dist)
 
 
-def _exact_knn_device(data, queries, k, metric, m, rows, device, return_stats, host_answers=False):
+def _exact_knn_device(data, queries, k, metric, m, rows, device, return_stats, host_answers=False, words=None):
     """``exact_knn`` for a device array ``data`` (``k``, the metric and queries-or-rows are checked already): an auxiliary handle
     bound to the tensor on torch's current stream, the device entries of csrc/exact.hip, the answers corrected on the device.
     ``rows``: a host array or a tensor of ids (range-checked on the host), or an int32 tensor on the data's device that the
@@ -184,6 +217,10 @@ def _exact_knn_device(data, queries, k, metric, m, rows, device, return_stats, h
                     raise ValueError("rows must be ids in [0, %d)" % n)
                 rows_dev = torch.from_numpy(rows.astype(np.int32)).to(data.device)
         n_out = int(q.shape[0]) if q is not None else (n if rows_dev is None else int(rows_dev.shape[0]))
+        tm = {}
+        if words is not None:  # (host words go up here, before the side stream is made)
+            tags_dev, masks_dev = tagwords.to_device(*words[0], data.device), tagwords.to_device(*words[1], data.device)
+            tm = {"tags_ptr": tags_dev.data_ptr(), "masks_ptr": masks_dev.data_ptr() if n_out else 0}
         idx = torch.empty((n_out, k), dtype=torch.int32, device=data.device)
         dist = torch.empty((n_out, k), dtype=torch.float32, device=data.device)
         stream = _OnTorchStream(torch, ordinal)  # (made after the uploads: a side stream waits for them)
@@ -199,10 +236,10 @@ def _exact_knn_device(data, queries, k, metric, m, rows, device, return_stats, h
             if n_out == 0:  # (nothing asked for: an empty tensor has no address to hand over)
                 stats = dict(_capi.NNDExactStats().as_dict(), slices=0)
             elif q is not None:
-                stats = builder.exact_knn_device(k, idx.data_ptr(), dist.data_ptr(), q_ptr=q.data_ptr(), q_dtype=q_dtype, n_q=n_out)
+                stats = builder.exact_knn_device(k, idx.data_ptr(), dist.data_ptr(), q_ptr=q.data_ptr(), q_dtype=q_dtype, n_q=n_out, **tm)
             else:
                 stats = builder.exact_knn_device(k, idx.data_ptr(), dist.data_ptr(), rows_ptr=0 if rows_dev is None else rows_dev.data_ptr(),
-                                                 n_rows=n_out)
+                                                 n_rows=n_out, **tm)
         finally:
             builder.close()
             stream.done()
@@ -210,4 +247,6 @@ def _exact_knn_device(data, queries, k, metric, m, rows, device, return_stats, h
             idx, dist = np.ascontiguousarray(idx.cpu().numpy()), m.correction(np.ascontiguousarray(dist.cpu().numpy()))
         else:
             dist = _device_corrected(torch, dist, m, ordinal)
+        if words is not None:
+            dist = _unfilled_to_inf(idx, dist)
     return (idx, dist, stats) if return_stats else (idx, dist)

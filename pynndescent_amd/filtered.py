@@ -5,6 +5,11 @@ row ids, numpy or a tensor on the index's device.  Two paths: ``walk`` -- the gr
 result list only if it is allowed" (csrc/query.hip, the FL instances; the allow bitset is built on the device by
 ``nnd_searcher_set_filter*``), and ``exact`` -- the allowed rows gathered into a compact copy that ``exact_knn`` searches.
 ``auto`` takes the exact path for at most ``FILTER_EXACT_MAX_ROWS`` allowed rows.
+
+Per-query filters (DESIGN.md "Per-query filters"): ``index.set_row_tags(tags)`` and ``query(..., query_tags=masks)`` -- 64 tag bits
+per row, a mask word per query, row r allowed for query i iff ``tags[r] & masks[i] != 0``.  ``walk``: the TG instances of
+csrc/query.hip on the searcher's own copy of the tag words; ``exact``: the masked scan of csrc/exact.hip over all rows;
+``auto``: per query, by the number of rows its mask allows (``tag_auto_paths``).
 """
 from collections import namedtuple
 
@@ -21,6 +26,16 @@ FILTER_MODES = ("auto", "walk", "exact")
 # they cross: at 1 M x 128, k = 10, 10 000 queries between 49 690 allowed rows (walk 23.35 ms, exact 10.77 ms) and 99 546
 # (12.32 / 15.60 ms), by interpolation at about 85 000 (profiles/filtered_query_1m.txt, tools/ab/filtered_query_timing.py).
 FILTER_EXACT_MAX_ROWS = 85000
+
+# Per-query filters, ``auto``: a query whose mask allows at most this many rows is answered by the masked exact scan.  That scan
+# streams ALL rows past every query block whatever the mask allows (66 .. 75 ms at 1 M x 128, k = 10, 10 000 queries), so its
+# crossing with the walk lies lower than the compact copy's: between 99 921 allowed rows (walk 13.06 ms, exact 75.15 ms) and 9 957
+# (506.43 / 71.13 ms); the walk's time over that decade goes as rows^-1.59, which puts the crossing at about 34 000
+# (profiles/tag_filter_1m.txt, tools/ab/tag_filter_timing.py).
+TAG_EXACT_MAX_ROWS = 34000
+# ``auto`` counts the allowed rows of at most this many distinct masks per call (one pass over the tag words for all of them);
+# a call with more distinct masks walks every query.  A bound on the counting work: a condition, not a measurement.
+TAG_COUNT_MAX_MASKS = 1024
 
 # kind "mask" (bool, n) or "ids" (int64); ``values`` numpy or tensor; ``n_allowed`` distinct allowed rows
 _Filter = namedtuple("_Filter", ["kind", "values", "on_device", "n_allowed"])
@@ -158,6 +173,123 @@ def query_exact(index, query_data, k, f, host_answers=False):
             idx, dist = idx.cpu().numpy(), dist.cpu().numpy()
         return idx, dist
     idx = ids_host()[idx].astype(np.int32)
+    if kk < k:
+        idx = np.concatenate([idx, np.full((idx.shape[0], k - kk), -1, np.int32)], 1)
+        dist = np.concatenate([dist, np.full((dist.shape[0], k - kk), np.inf, dist.dtype)], 1)
+    return idx, dist
+
+
+# ------------------------------------------------------------------------------------------------ per-query filters
+def tag_mask_paths(distinct, counts, exact_ok=True):
+    """The ``auto`` rule per DISTINCT mask: "empty" (the mask is 0, or it allows no row), "exact" (it allows at most
+    ``TAG_EXACT_MAX_ROWS`` rows and the metric has an exact search) or "walk".  ``counts`` (allowed rows per distinct mask) is None
+    when the call has more than ``TAG_COUNT_MAX_MASKS`` distinct masks: then nothing was counted and every non-zero mask walks."""
+    distinct = np.asarray(distinct).view(np.uint64)
+    paths = np.full(distinct.shape[0], "walk", dtype=object)
+    paths[distinct == 0] = "empty"
+    if counts is not None:
+        counts = np.asarray(counts, np.int64)
+        paths[counts == 0] = "empty"
+        if exact_ok:
+            paths[(counts > 0) & (counts <= TAG_EXACT_MAX_ROWS) & (distinct != 0)] = "exact"
+    return paths
+
+
+def tag_counts_taken(n_distinct):
+    """Does ``auto`` count the allowed rows of a call with ``n_distinct`` distinct masks?"""
+    return int(n_distinct) <= TAG_COUNT_MAX_MASKS
+
+
+def tag_auto_paths(inverse, distinct, counts, exact_ok=True):
+    """The ``auto`` rule per QUERY: ``(walk, exact, empty)``, the positions in the batch of the queries each path answers.
+    ``distinct``: the distinct masks of the call; ``inverse``: for every query the position of its mask in ``distinct``;
+    ``counts``: the allowed rows per distinct mask, or None if they were not taken (``tag_counts_taken``)."""
+    if counts is not None and not tag_counts_taken(len(distinct)):
+        counts = None
+    per_query = tag_mask_paths(distinct, counts, exact_ok)[np.asarray(inverse, np.int64)]
+    return tuple(np.flatnonzero(per_query == name) for name in ("walk", "exact", "empty"))
+
+
+def ensure_searcher_tags(index):
+    """The searcher's copy of the index's tag words (its own numbering), built when tags are first used: a host array goes up
+    through the host entry, a tensor is gathered where it is.  The copy lives until the tags change or the searcher is rebuilt."""
+    searcher = index._searcher
+    if getattr(searcher, "tags_set", False):
+        return
+    values = index._row_tags
+    if not _is_device_array(values):
+        searcher.set_tags(values, index._vertex_order)
+    else:
+        torch = device_arrays._torch()
+        ordinal = int(index.device)
+        with torch.cuda.device(ordinal):
+            searcher.set_tags_device(values.data_ptr(), _searcher_order(index, values.device).data_ptr(),
+                                     torch.cuda.current_stream(ordinal).cuda_stream)
+    searcher.tags_set = True
+
+
+def _searcher_order(index, where):
+    """The searcher's row order as an int32 tensor (lives and dies with the searcher)."""
+    order = getattr(index._searcher, "vertex_order_device", None)
+    if order is None:
+        order = device_arrays._torch().from_numpy(np.ascontiguousarray(index._vertex_order, dtype=np.int32)).to(where)
+        index._searcher.vertex_order_device = order
+    return order
+
+
+def tag_counts(index, distinct):
+    """Allowed rows per distinct mask (numpy uint64 ``distinct``), counted by the device in one pass over the searcher's tag words."""
+    ensure_searcher_tags(index)
+    return index._searcher.count_tags(distinct)
+
+
+def rows_in_original_order(index, where=None):
+    """Every row the index works on, in the ORIGINAL numbering, for the masked exact scan: the caller's tensor (a linear map: its
+    transformed rows) where there is one, else a host copy un-permuted from the searcher's order (a sparse index without its
+    tensor: made dense).  ``where``: a torch device the host copy is moved to."""
+    d = index.__dict__
+    if "_device_data" in d:
+        return d["_device_data"]
+    order = np.asarray(index._vertex_order)
+    position = np.empty(order.shape[0], np.int64)
+    position[order] = np.arange(order.shape[0])
+    if d.get("_is_sparse"):
+        rows = np.ascontiguousarray(index._raw_data[position].toarray(), dtype=np.float32)
+    else:
+        rows = np.ascontiguousarray(index._work_rows()[position])
+    if where is not None:
+        rows = device_arrays._torch().from_numpy(rows).to(where)
+    return rows
+
+
+def query_tagged_exact(index, query_data, k, masks, masks_on_device, host_answers=False):
+    """``filter_mode="exact"`` of a tagged call: ``exact_knn`` with ``row_tags`` / ``query_tags`` over all rows in the original
+    numbering -- exact by (float64 distance, id) among each query's allowed rows, (-1, inf) where they run out.  Results live where
+    ``query_data`` lives (``host_answers``: see ``query_exact``)."""
+    d = index.__dict__
+    on_device = _is_device_array(query_data)
+    rows = rows_in_original_order(index, query_data.device if on_device else None)
+    lin = d.get("_linear_map")
+    if lin is not None:  # the queries through the index's own (A, c); the search on the transformed rows is euclidean
+        if on_device:
+            torch = device_arrays._torch()
+            q, dtype, ordinal = device_arrays._check_device_array(query_data, what="query_data")
+            with torch.cuda.device(ordinal):
+                query_data = index._linear_on_device(q.device).rows(q, dtype, torch.cuda.current_stream(ordinal).cuda_stream)
+        else:
+            query_data = _capi.linear_rows_host(lin.kind, lin.a, lin.shift, np.asarray(query_data).astype(np.float32, order="C"),
+                                                device=index.device)
+    kk = min(int(k), int(_shape_of(rows)[0]))
+    idx, dist = exact_knn(rows, queries=query_data, k=kk, metric=index._kernel_metric(), device=index.device, _host_answers=host_answers,
+                          row_tags=index._row_tags, query_tags=masks)
+    if _is_device_array(idx):
+        torch = device_arrays._torch()
+        if kk < k:
+            idx = torch.cat([idx, torch.full((idx.shape[0], k - kk), -1, dtype=idx.dtype, device=idx.device)], 1)
+            dist = torch.cat([dist, torch.full((dist.shape[0], k - kk), float("inf"), dtype=dist.dtype, device=dist.device)], 1)
+        if not on_device:
+            idx, dist = idx.cpu().numpy(), dist.cpu().numpy()
+        return idx, dist
     if kk < k:
         idx = np.concatenate([idx, np.full((idx.shape[0], k - kk), -1, np.int32)], 1)
         dist = np.concatenate([dist, np.full((dist.shape[0], k - kk), np.inf, dist.dtype)], 1)

@@ -31,7 +31,7 @@ from warnings import warn
 import numpy as np
 from sklearn.utils import check_array, check_random_state
 
-from . import _capi, build, device_arrays, filtered, linear_map, sparse_input
+from . import _capi, build, device_arrays, filtered, linear_map, sparse_input, tags as tagwords
 # Every name below was defined here once and is read here still (tests, tools/, and pickles, which name
 # pynndescent_amd.nndescent.correct_alternative_*): the same objects as in their home modules.  Two are replaced by tests and
 # are therefore CALLED through their home module alone -- ``build.ts()``, ``device_arrays._torch()``.
@@ -850,7 +850,24 @@ class NNDescent:
             searcher.vertex_order_device = order  # what _query_device maps the answers' ids through
         return searcher
 
-    def query(self, query_data, k=10, epsilon=0.1, proxy_beam_size=4, filter=None, filter_mode="auto"):
+    def set_row_tags(self, tags):
+        """The rows' tag words for per-query filters (``query(..., query_tags=...)``; beyond the reference): 1-D, one entry per row
+        in the ORIGINAL numbering, 64 tag bits each -- a numpy ``uint64`` or ``int64`` array (the bit pattern counts: bit 63 is a
+        tag like any other) or an ``int64`` tensor on the index's device; anything else raises ``ValueError``.  ``None`` removes
+        the tags.  The index keeps what it is given: a tensor stays where it is, a host array goes to the device once, when a
+        query first needs it, not once per call; a pickle carries a host copy.  ``update()`` clears the tags."""
+        d = self.__dict__
+        if tags is None:
+            d.pop("_row_tags", None)
+        else:
+            d["_row_tags"] = tagwords.check_words(tags, int(self._raw_data_n()), self.device, "tags", "row")[0]
+        d.pop("_row_tags_cleared", None)
+        searcher = d.get("_searcher")
+        if searcher is not None and getattr(searcher, "tags_set", False):  # the searcher's copy is of the old tags
+            searcher.clear_tags()
+            searcher.tags_set = False
+
+    def query(self, query_data, k=10, epsilon=0.1, proxy_beam_size=4, filter=None, filter_mode="auto", query_tags=None):
         """``NNDescent.query`` (pynndescent_.py:2275-2379) on the GPU: one wave per query (csrc/query.hip).
         Returns (indices (n_queries, k) in the ORIGINAL numbering, true distances (n_queries, k)).  A device array
         ``query_data`` (float32 / float16 / bfloat16 / float64, on the index's device) is answered with device tensors: the
@@ -865,13 +882,24 @@ class NNDescent:
         compact copy of the allowed rows, by (float64 distance, id) as ``exact_knn`` (not for proxy_inner_product); "auto" --
         "exact" for at most ``filtered.FILTER_EXACT_MAX_ROWS`` allowed rows when the metric has an exact search, else "walk".
         After a filtered call ``self.last_filter`` says what ran: ``{"mode": "walk" | "exact" | "empty", "n_allowed": rows}``
-        ("empty": no row allowed, answered without a launch).  Soft deletion: keep a mask of the live rows and pass it."""
+        ("empty": no row allowed, answered without a launch).  Soft deletion: keep a mask of the live rows and pass it.
+
+        ``query_tags`` (per-query filters; needs ``set_row_tags``, does not combine with ``filter``): a mask word per query, 1-D,
+        the dtypes of ``set_row_tags``, on the host or on the index's device whichever side the queries are on.  Row r may be
+        returned to query i iff ``tags[r] & query_tags[i] != 0``; a query with mask 0 gets (-1, inf) in every place.
+        ``filter_mode``: "walk" -- the walk with that rule per query; "exact" -- the masked brute-force scan over all rows (not for
+        proxy_inner_product); "auto" -- per query: the device counts the rows each distinct mask of the call allows, a query whose
+        mask allows at most ``filtered.TAG_EXACT_MAX_ROWS`` rows goes to the exact path, one whose mask allows none is answered
+        without a search, the others walk; with more than ``filtered.TAG_COUNT_MAX_MASKS`` distinct masks nothing is counted and
+        every query walks.  ``self.last_filter`` is then ``{"mode": "tags", "n_walk", "n_exact", "n_empty", "n_masks"}``."""
         if k > 256:
             raise NotImplementedError("pynndescent_amd answers queries with k <= 256; use index.to_reference() for k = %d" % k)
         _check_quantization(self.quantization, self.metric)
         m = _metric_of(self.metric)
         if filter_mode not in filtered.FILTER_MODES:
             raise ValueError("filter_mode must be one of %s (got %r)" % (", ".join(filtered.FILTER_MODES), filter_mode))
+        if query_tags is not None:
+            return self._query_tagged(query_data, m, k, epsilon, proxy_beam_size, filter, filter_mode, query_tags)
         if sparse_input.is_sparse(query_data):
             return self._query_sparse(query_data, m, k, epsilon, proxy_beam_size, filter, filter_mode)
         if filter is not None:
@@ -932,21 +960,105 @@ class NNDescent:
         finally:
             self._searcher.clear_filter()
 
+    def _query_tagged(self, query_data, m, k, epsilon, proxy_beam_size, filter, filter_mode, query_tags):
+        """``query`` with ``query_tags``: everything is validated before any device work; then the walk on the whole batch (a
+        query's seed depends on its place in the batch, so the queries another path answers stay in it with mask 0, which ends
+        their wave at once), the masked exact scan on the queries ``auto`` or "exact" gives it, and the two scattered into one
+        answer where ``query_data`` lives."""
+        d = self.__dict__
+        if filter is not None:
+            raise ValueError("query takes filter or query_tags, not both: an allow set and per-query masks do not combine")
+        if "_row_tags" not in d:
+            if d.get("_row_tags_cleared"):
+                raise ValueError("update() cleared the row tags, the row set has changed: set the row tags again (set_row_tags)")
+            raise ValueError("query_tags needs the rows' tags: call set_row_tags first")
+        if getattr(self, "n_devices", 1) > 1:
+            raise NotImplementedError("query_tags is not available on an index built with n_devices > 1")
+        if self.quantization is not None or m.proxy:
+            _proxy_search_k(k, proxy_beam_size)
+        if tuple(_shape_of(query_data))[1:] != (self.dim,):
+            raise ValueError("query_data must have shape (n_queries, %d)" % self.dim)
+        nq = int(_shape_of(query_data)[0])
+        masks, masks_on_device = tagwords.check_words(query_tags, nq, self.device, "query_tags", "query")
+        if filter_mode == "exact":
+            _no_exact_for_proxy(self.metric, m, 'NNDescent.query(filter_mode="exact")')
+        sparse = sparse_input.is_sparse(query_data)
+        if sparse:  # uploaded as CSR and made dense on the device; the answers come down again (``_query_sparse``)
+            query_data = sparse_input.query_rows(query_data, self.dim, self.device)
+        on_device = _is_device_array(query_data)
+        if (not self._prepared or getattr(self, "_searcher", None) is None
+                or (self.quantization is not None and not self._searcher.has_codes)):
+            self.prepare()
+        # the path of every query, on the host: the masks of a call are 8 bytes per query
+        host_masks = tagwords.to_host(masks, masks_on_device)
+        distinct, inverse = np.unique(host_masks, return_inverse=True)
+        if filter_mode == "auto":
+            counts = filtered.tag_counts(self, distinct) if filtered.tag_counts_taken(len(distinct)) and len(distinct) else None
+            walk, exact, empty = filtered.tag_auto_paths(inverse, distinct, counts, exact_ok=not m.proxy)
+        else:
+            empty = np.flatnonzero(host_masks == 0)
+            rest = np.flatnonzero(host_masks != 0)
+            walk, exact = (rest, rest[:0]) if filter_mode == "walk" else (rest[:0], rest)
+        self.last_filter = {"mode": "tags", "n_walk": len(walk), "n_exact": len(exact), "n_empty": len(empty), "n_masks": len(distinct)}
+        indices, dists = filtered.empty_answer(query_data, k)
+        if len(walk):
+            walk_masks = host_masks
+            if len(walk) != nq:
+                walk_masks = np.zeros(nq, np.uint64)
+                walk_masks[walk] = host_masks[walk]
+            elif masks_on_device and on_device:
+                walk_masks = masks  # (the caller's tensor as it is)
+            indices, dists = self._query_walk(query_data, m, k, epsilon, proxy_beam_size, host_answers=sparse, query_masks=walk_masks)
+            if sparse:
+                indices, dists = np.ascontiguousarray(indices.cpu().numpy()), np.ascontiguousarray(dists.cpu().numpy())
+                if self._distance_correction is not None:
+                    dists = self._distance_correction(dists)
+        if len(exact):
+            whole = len(exact) == nq
+            if on_device:
+                torch = device_arrays._torch()
+                where = torch.from_numpy(exact).to(query_data.device)
+                sub_q = query_data if whole else query_data[where]
+            else:
+                sub_q = query_data if whole else np.asarray(query_data)[exact]
+            sub_i, sub_d = filtered.query_tagged_exact(self, sub_q, k, host_masks[exact], False, host_answers=sparse)
+            if _is_device_array(indices) and not _is_device_array(sub_i):  # (a sparse batch whose queries all went exact)
+                indices, dists = indices.cpu().numpy(), dists.cpu().numpy()
+            if _is_device_array(indices):
+                indices[where] = sub_i.to(indices.dtype)
+                dists = dists.to(sub_d.dtype) if dists.dtype != sub_d.dtype else dists
+                dists[where] = sub_d
+            else:
+                dists = dists.astype(sub_d.dtype, copy=False)
+                indices[exact], dists[exact] = sub_i, sub_d
+        if sparse and _is_device_array(indices):  # (nothing ran: the empty answer was made where the dense queries are)
+            indices, dists = indices.cpu().numpy(), dists.cpu().numpy()
+        # the places no allowed row fills hold (-1, inf), whatever the metric's correction makes of inf
+        if _is_device_array(dists):
+            dists = dists.masked_fill(indices < 0, float("inf"))
+        else:
+            dists = np.array(dists, copy=True)
+            dists[indices < 0] = np.inf
+        return indices, dists
+
     def _raw_data_n(self):
         """The number of rows, without fetching a host mirror."""
         d = self.__dict__
         return d["_device_data"].shape[0] if "_device_data" in d else self._raw_data.shape[0]
 
-    def _query_walk(self, query_data, m, k, epsilon, proxy_beam_size, host_answers=False):
-        """The graph walk of ``query`` (with the searcher's filter, when ``_query_filtered`` has set one)."""
+    def _query_walk(self, query_data, m, k, epsilon, proxy_beam_size, host_answers=False, query_masks=None):
+        """The graph walk of ``query`` (with the searcher's filter, when ``_query_filtered`` has set one; ``query_masks``: the
+        tagged walk, a mask word per query -- numpy uint64, or an int64 tensor beside device queries)."""
         search_k = k
         if self.quantization is not None or m.proxy:  # pynndescent_.py:2309-2312
             search_k = _proxy_search_k(k, proxy_beam_size)
         if (not self._prepared or getattr(self, "_searcher", None) is None
                 or (self.quantization is not None and not self._searcher.has_codes)):
             self.prepare()
+        if query_masks is not None:
+            filtered.ensure_searcher_tags(self)
         if _is_device_array(query_data):
-            return self._query_device(query_data, m, k, search_k, epsilon, corrected=not host_answers)
+            return self._query_device(query_data, m, k, search_k, epsilon, corrected=not host_answers, query_masks=query_masks)
         query_data = np.asarray(query_data).astype(np.float32, order="C")  # pynndescent_.py:2316
         if query_data.ndim != 2 or query_data.shape[1] != self.dim:
             raise ValueError("query_data must have shape (n_queries, %d)" % self.dim)
@@ -954,7 +1066,10 @@ class NNDescent:
         lin = self.__dict__.get("_linear_map")
         if lin is not None:  # the queries through the index's own (A, c), by the kernel that transformed its rows
             query_data = _capi.linear_rows_host(lin.kind, lin.a, lin.shift, query_data, device=self.device)
-        if self.quantization is not None:  # the walk on the codes, the rerank in its epilogue (pynndescent_.py:2321-2322, 2363-2371)
+        if query_masks is not None:  # the same three forms, eps as below
+            form = "proxy" if self.quantization is not None else ("rerank" if m.proxy else "float")
+            indices, dists = self._searcher.query_tagged(form, query_data, query_masks, k, search_k, epsilon + (1e-32 if form == "proxy" else 0.0))
+        elif self.quantization is not None:  # the walk on the codes, the rerank in its epilogue (pynndescent_.py:2321-2322, 2363-2371)
             indices, dists = self._searcher.query_proxy(query_data, k, search_k, epsilon + 1e-32)
         elif m.proxy:  # the walk on the proxy distance, the rerank by the true one; epsilon as given (pynndescent_.py:2321-2322)
             indices, dists = self._searcher.query_rerank(query_data, k, search_k, epsilon)
@@ -966,7 +1081,7 @@ class NNDescent:
             dists = self._distance_correction(dists)
         return indices, dists
 
-    def _query_device(self, q, m, k, search_k, epsilon, corrected=True):
+    def _query_device(self, q, m, k, search_k, epsilon, corrected=True, query_masks=None):
         """``query`` for a device array: the three forms on the device-pointer entries of the searcher.  ``corrected`` False: the
         kernels' own distances are returned -- the caller brings them to the host and applies the host's correction there, for
         answers that equal a host query's bit for bit (the device's 1 - 2^-d agrees with numpy's within rounding only)."""
@@ -995,7 +1110,11 @@ class NNDescent:
                 form, eps = "rerank", epsilon
             else:
                 form, eps = "float", epsilon
-            if nq:
+            if nq and query_masks is not None:
+                masks = tagwords.to_device(query_masks, _is_device_array(query_masks), q.device)
+                self._searcher.query_tagged_device(form, q.data_ptr(), masks.data_ptr(), nq, k, search_k, eps, indices.data_ptr(),
+                                                   dists.data_ptr(), stream)
+            elif nq:
                 self._searcher.query_device(form, q.data_ptr(), nq, k, search_k, eps, indices.data_ptr(), dists.data_ptr(), stream)
             order = getattr(self._searcher, "vertex_order_device", None)  # lives and dies with the searcher
             if order is None:
@@ -1017,6 +1136,8 @@ class NNDescent:
             for name in ("_neighbor_graph", "_search_graph", "_quantized_data"):
                 hasattr(self, name)
         state = self.__dict__.copy()
+        if _is_device_array(state.get("_row_tags")):  # the tag words travel as a host copy
+            state["_row_tags"] = tagwords.to_host(state["_row_tags"], True)
         # a linear map travels as _linear_map (kind, A, c: float32); the transformed rows are derived again from _raw_data
         for name in self._DEVICE_TENSORS + self._LINEAR_COPIES + ("_rp_forest", "_searcher"):
             state.pop(name, None)
@@ -1092,6 +1213,8 @@ class NNDescent:
             if updated_indices is not None:
                 warn("xs_updated not provided, while update_indices provided. " "They will be ignored.")
             updated_indices = None
+        if self.__dict__.pop("_row_tags", None) is not None:  # the row set changes: the tags are the caller's to set again
+            self._row_tags_cleared = True
         if on_device:
             return self._update_device(None if xs_fresh is None else checked(xs_fresh, "xs_fresh"), xs_updated, updated_indices or [],
                                        current_random_state, csr_rows=csr_rows)
