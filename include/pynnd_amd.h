@@ -235,12 +235,13 @@ int32_t nnd_device_csr_rows(int32_t device, void *hip_stream, const void *indptr
 /* Corrections of the kernels' distances (the reference's distance_correction, pynndescent_.py:1271-1298) on the device, without
  * a handle: a graph is corrected when NNDescent.neighbor_graph is read, long after its builder is gone.  `count` float32 values
  * at in_dev -> out_dev, asynchronous on `hip_stream` of `device`.  Unfilled entries (+inf) come out as the host functions map
- * them: sqrt +inf, cosine 1, inner product 0, hellinger 1. */
+ * them: sqrt +inf, cosine 1, inner product 0, hellinger 1, haversine pi. */
 #define NND_CORRECT_COPY 0              /* 32-bit words out, bit for bit (sqeuclidean, correlation, the proxies; the ids of a graph) */
 #define NND_CORRECT_SQRT 1              /* float32 out, correctly rounded: the bits of numpy.sqrt */
 #define NND_CORRECT_ALT_COSINE 2        /* float64 out: 1 - 2^-d */
 #define NND_CORRECT_ALT_INNER_PRODUCT 3 /* float64 out: d >= FLT_MAX ? 0 : -1 / d (an IEEE division: the host's bits) */
 #define NND_CORRECT_ALT_HELLINGER 4     /* float64 out: sqrt(1 - 2^-d) */
+#define NND_CORRECT_HAVERSINE 5         /* float64 out: 2 asin(min(1, sqrt(d) / 2)), the angle of the squared chord d (+inf: pi) */
 int32_t nnd_device_correct(int32_t device, void *hip_stream, int32_t kind, const float *in_dev, void *out_dev, int64_t count);
 /* ---- metrics with a fixed linear map (csrc/linear.hip; DESIGN.md "Metrics"): seuclidean, wminkowski with p = 2, mahalanobis ----
  * They are NND_METRIC_SQEUCLIDEAN after y = A (x - c): the caller transforms every row that enters the library (training
@@ -257,6 +258,22 @@ int32_t nnd_device_linear_rows(int32_t device, void *hip_stream, int32_t kind, i
                                const float *x_dev, int64_t n, float *y_dev);
 int32_t nnd_linear_rows_host(int32_t device, int32_t kind, int32_t dim, const float *map, const float *shift, const float *x, int64_t n,
                              float *y);
+/* ---- derived metrics: a per-row map, then a metric above (csrc/rowmap.hip; DESIGN.md "Row maps") ----
+ * As with the linear maps, the caller maps every row that enters the library and hands the float32 result to the entry points
+ * of the base metric's code, unchanged.  kind: */
+#define NND_ROWMAP_RANK 0   /* dim in, dim out: the average ranks of the row's values (ties share the mean of their places); exact.
+                             * spearmanr = NND_METRIC_CORRELATION of the rank rows.  1 <= dim <= 16384; shift is not read */
+#define NND_ROWMAP_SPHERE 1 /* 2 in (lat, lon; radians), 3 out: (cos lat cos lon, cos lat sin lon, sin lat) - shift, in float64,
+                             * rounded once.  haversine = NND_CORRECT_HAVERSINE of NND_METRIC_SQEUCLIDEAN of these rows; shift: 3 floats */
+/* (n, dim) float32 rows at x, row i at x + i * x_stride (x_stride >= dim, in elements; the elements between the rows are never
+ * read) -> contiguous float32 rows at y, of the kind's output width.  A row's result depends on that row alone, bit for bit.
+ * A kind, width or stride outside the above is refused (nonzero, nnd_last_global_error), never clamped.  The two entries relate
+ * as nnd_device_linear_rows and nnd_linear_rows_host do: device pointers, queued on `hip_stream`, nothing waited for or
+ * allocated; or host pointers (x: (n - 1) * x_stride + dim floats), and the call returns when the result is there. */
+int32_t nnd_device_map_rows(int32_t device, void *hip_stream, int32_t kind, int32_t dim, int64_t x_stride, const float *shift_dev,
+                            const float *x_dev, int64_t n, float *y_dev);
+int32_t nnd_map_rows_host(int32_t device, int32_t kind, int32_t dim, int64_t x_stride, const float *shift, const float *x, int64_t n,
+                          float *y);
 /* ---- NNDescent.update() / recall() of an index whose rows and graph live on the device (csrc/devarray.hip, csrc/update.hip;
  * DESIGN.md "Device arrays") ----  Like the two entries above: a device ordinal and a HIP stream (NULL: the device's default
  * stream) instead of a handle, everything is queued there and nothing is waited for; every array is the caller's and must stay

@@ -41,7 +41,10 @@ NND_DTYPE_FLOAT32, NND_DTYPE_FLOAT16, NND_DTYPE_BFLOAT16, NND_DTYPE_FLOAT64 = 0,
 NND_FILTER_MASK, NND_FILTER_IDS = 0, 1  # nnd_searcher_set_filter's `kind`
 NND_QUERY_FORMS = {"float": 0, "proxy": 1, "rerank": 2}  # nnd_searcher_query_tagged's `form` (NND_QUERY_*)
 NND_CORRECT_COPY, NND_CORRECT_SQRT, NND_CORRECT_ALT_COSINE, NND_CORRECT_ALT_INNER_PRODUCT, NND_CORRECT_ALT_HELLINGER = 0, 1, 2, 3, 4
+NND_CORRECT_HAVERSINE = 5
 NND_LINEAR_DIAGONAL, NND_LINEAR_DENSE = 0, 1  # the kinds of a metric's linear map (include/pynnd_amd.h NND_LINEAR_*, csrc/linear.hip)
+NND_ROWMAP_RANK, NND_ROWMAP_SPHERE = 0, 1  # the kinds of a derived metric's row map (include/pynnd_amd.h NND_ROWMAP_*, csrc/rowmap.hip)
+ROWMAP_RANK_MAX_DIM = 16384  # the widest row nnd_device_map_rows ranks (csrc/rowmap.hip RM_RANK_MAX)
 NND_FLAG_NO_GRAPH = 1  # auxiliary handle: no k-lists / candidate / proposal tables (pruning pass, hub tree)
 NND_FLAG_NO_PREP = 2   # ... and no prepared copy of the rows (hub tree only)
 NND_FLAG_TEST_SELECT_WAVE = 4  # test hook: the one-wave-per-vertex selection kernel
@@ -217,6 +220,8 @@ _SIGNATURES = [
     ("nnd_device_correct", C.c_int32, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64]),
     ("nnd_device_linear_rows", C.c_int32, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     ("nnd_linear_rows_host", C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    ("nnd_device_map_rows", C.c_int32, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    ("nnd_map_rows_host", C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     ("nnd_device_update_rows", C.c_int32, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int64,
                                            C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32]),
     ("nnd_device_update_graph", C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int64,
@@ -1085,6 +1090,38 @@ def linear_rows_host(kind, a, shift, x, device=0):
     assert shift.shape == (dim,) and a.shape == ((dim, dim) if kind == NND_LINEAR_DENSE else (dim,))
     y = np.empty((n, dim), np.float32)
     if lib.nnd_linear_rows_host(int(device), int(kind), dim, _ptr(a), _ptr(shift), _ptr(x), n, _ptr(y)) != 0:
+        raise NNDError(lib.nnd_last_global_error().decode())
+    return y
+
+
+def rowmap_out_dim(kind, dim):
+    """The output width of a row map (``NND_ROWMAP_*``) for rows of ``dim`` columns."""
+    return 3 if int(kind) == NND_ROWMAP_SPHERE else int(dim)
+
+
+def device_map_rows(device, stream_ptr, kind, dim, x_stride, shift_ptr, x_ptr, n, y_ptr):
+    """The row map ``kind`` (NND_ROWMAP_*) of the (n, dim) float32 rows at the device address ``x_ptr`` (row stride ``x_stride``
+    elements) into the contiguous rows at ``y_ptr`` (``rowmap_out_dim`` columns; ``shift_ptr``: 3 floats for the sphere, else 0);
+    queued on ``stream_ptr`` of ``device``."""
+    lib = load_library()
+    dev = lambda p: C.c_void_p(int(p)) if p else None  # noqa: E731
+    if lib.nnd_device_map_rows(int(device), dev(stream_ptr), int(kind), int(dim), int(x_stride), dev(shift_ptr), dev(x_ptr), int(n),
+                               dev(y_ptr)) != 0:
+        raise NNDError(lib.nnd_last_global_error().decode())
+
+
+def map_rows_host(kind, shift, x, device=0, dim=None):
+    """The row map ``kind`` of the float32 host rows ``x`` by the device kernel (``nnd_map_rows_host``): a new float32 array.
+    ``dim``: the live columns of ``x`` when it has more (the rest is a stride's padding, never read)."""
+    lib = load_library()
+    x = np.ascontiguousarray(x, np.float32)
+    n, stride = x.shape
+    dim = stride if dim is None else int(dim)
+    if shift is not None:
+        shift = np.ascontiguousarray(shift, np.float32)
+        assert shift.shape == (3,)
+    y = np.empty((n, rowmap_out_dim(kind, dim)), np.float32)
+    if lib.nnd_map_rows_host(int(device), int(kind), dim, stride, None if shift is None else _ptr(shift), _ptr(x), n, _ptr(y)) != 0:
         raise NNDError(lib.nnd_last_global_error().decode())
     return y
 

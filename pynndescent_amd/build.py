@@ -72,7 +72,8 @@ def _build_graph(data, m, n_neighbors, n_trees, leaf_size, max_depth, max_candid
     ``old_graph`` and ``init_graph`` / ``init_dist`` may then be tensors as well (int32 / float32, read in place).  Returns
     ``((indices, distances), the stats (when ``stats``), the forest's leaf count)``."""
     n = data.shape[0]
-    builder = _capi.Builder(n, data.shape[1], m.code, n_neighbors, n_trees, leaf_size, max_depth, max_candidates, n_iters,
+    dim = data.shape[1] if dev_in is None else dev_in.work_dim()  # (a row map may change the width: 2 in, 3 out)
+    builder = _capi.Builder(n, dim, m.code, n_neighbors, n_trees, leaf_size, max_depth, max_candidates, n_iters,
                             delta, rng_state, tree_rng, device=device)
     try:
         if dev_in is None:

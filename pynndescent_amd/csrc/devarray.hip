@@ -336,6 +336,7 @@ __global__ __launch_bounds__(256) void k_correct(const float *__restrict__ in, O
         if (KIND == NND_CORRECT_SQRT) out[i] = (OUT)sqrt_rn_f32(d);
         else if (KIND == NND_CORRECT_ALT_COSINE) out[i] = (OUT)(1.0 - exp2(-(double)d));
         else if (KIND == NND_CORRECT_ALT_INNER_PRODUCT) out[i] = (OUT)(d >= FLT_MAX ? 0.0 : __ddiv_rn(-1.0, (double)d));
+        else if (KIND == NND_CORRECT_HAVERSINE) out[i] = (OUT)(2.0 * asin(fmin(1.0, __dsqrt_rn((double)d) * 0.5)));
         else out[i] = (OUT)__dsqrt_rn(1.0 - exp2(-(double)d));
     }
 }
@@ -367,7 +368,7 @@ extern "C" int32_t nnd_device_rows_f32(int32_t device, void *hip_stream, const v
 }
 
 extern "C" int32_t nnd_device_correct(int32_t device, void *hip_stream, int32_t kind, const float *in_dev, void *out_dev, int64_t count) {
-    if (count < 0 || kind < NND_CORRECT_COPY || kind > NND_CORRECT_ALT_HELLINGER) return da_fail("nnd_device_correct: bad kind or count");
+    if (count < 0 || kind < NND_CORRECT_COPY || kind > NND_CORRECT_HAVERSINE) return da_fail("nnd_device_correct: bad kind or count");
     if (count == 0) return 0;
     if (!in_dev || !out_dev) return da_fail("nnd_device_correct: null pointer");
     if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return da_fail("nnd_device_correct: no such device"); }
@@ -380,6 +381,7 @@ extern "C" int32_t nnd_device_correct(int32_t device, void *hip_stream, int32_t 
         case NND_CORRECT_SQRT: hipLaunchKernelGGL((k_correct<NND_CORRECT_SQRT, float>), g, b, 0, st, in_dev, (float *)out_dev, count); break;
         case NND_CORRECT_ALT_COSINE: hipLaunchKernelGGL((k_correct<NND_CORRECT_ALT_COSINE, double>), g, b, 0, st, in_dev, (double *)out_dev, count); break;
         case NND_CORRECT_ALT_INNER_PRODUCT: hipLaunchKernelGGL((k_correct<NND_CORRECT_ALT_INNER_PRODUCT, double>), g, b, 0, st, in_dev, (double *)out_dev, count); break;
+        case NND_CORRECT_HAVERSINE: hipLaunchKernelGGL((k_correct<NND_CORRECT_HAVERSINE, double>), g, b, 0, st, in_dev, (double *)out_dev, count); break;
         default: hipLaunchKernelGGL((k_correct<NND_CORRECT_ALT_HELLINGER, double>), g, b, 0, st, in_dev, (double *)out_dev, count); break;
     }
     if (hipGetLastError() != hipSuccess) return da_fail("nnd_device_correct: kernel launch failed");

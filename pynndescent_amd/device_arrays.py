@@ -5,7 +5,7 @@ torch is imported by ``_torch()`` alone, on the paths that meet a tensor: import
 """
 import numpy as np
 
-from . import _capi
+from . import _capi, row_map
 
 _DEVICE_DTYPES = {"float32": _capi.NND_DTYPE_FLOAT32, "float16": _capi.NND_DTYPE_FLOAT16, "bfloat16": _capi.NND_DTYPE_BFLOAT16,
                   "float64": _capi.NND_DTYPE_FLOAT64}
@@ -59,6 +59,17 @@ def _rows_to_host(a):
 def _ids_to_host(a):
     """Row ids given as a device array, on the host (they are few); everything else as it is."""
     return a.detach().cpu().numpy() if _is_device_array(a) else a
+
+
+def _assert_all_finite(a):
+    """sklearn's ``assert_all_finite`` (the reference's ``check_array`` scan) for host rows or a device array; of a device array
+    one scalar comes back, and only the error path brings the rows down, for sklearn's wording."""
+    from sklearn.utils import assert_all_finite
+
+    if not _is_device_array(a):
+        assert_all_finite(a)
+    elif a.shape[0] and not bool(_torch().isfinite(a).all().item()):
+        assert_all_finite(_rows_to_host(a))
 
 
 def _resolve_updated_indices(updated_indices, n_old):
@@ -121,7 +132,12 @@ class _DeviceInput:
         # what the device works on: the caller's own tensor, dot's normalised float32 rows, or the rows a linear map transformed
         self.rows = tensor
         self.as_given = as_given  # update(): dot's rows enter as they are (float32, pynndescent_.py:2461-2476 normalises nothing)
-        self.linear = linear  # a _DeviceLinear: the metric's map on this device (None: the metric has none)
+        self.linear = linear  # a _DeviceLinear or a _DeviceRowMap: the metric's map on this device (None: the metric has none)
+
+    def work_dim(self):
+        """The width of the rows the device works on: the tensor's, or what the metric's map makes of it."""
+        dim = int(self.tensor.shape[1])
+        return dim if self.linear is None else self.linear.out_dim(dim)
 
     def host_rows(self):
         """The caller's rows on the host, float32: for sklearn's wording of the NaN / inf error, the one place that needs them."""
@@ -167,6 +183,9 @@ class _DeviceLinear:
         self.a = torch.from_numpy(np.ascontiguousarray(lin.a, dtype=np.float32)).to(device)
         self.shift = torch.from_numpy(np.ascontiguousarray(lin.shift, dtype=np.float32)).to(device)
 
+    def out_dim(self, dim):
+        return int(dim)
+
     def rows(self, t, dtype, stream_ptr):
         """``A (x - shift)`` of the contiguous (n, d) tensor ``t`` (``dtype``: its NND_DTYPE_*): a new float32 tensor, queued on
         ``stream_ptr``.  The existing conversion to float32 runs first (csrc/devarray.hip), then csrc/linear.hip."""
@@ -182,6 +201,39 @@ class _DeviceLinear:
         _capi.device_linear_rows(self.ordinal, stream_ptr, self.kind, dim, self.a.data_ptr(), self.shift.data_ptr(), t.data_ptr(), n,
                                  out.data_ptr())
         return out
+
+
+class _DeviceRowMap:
+    """A derived metric's row map (``row_map.RowMap``) on one device, with the interface of ``_DeviceLinear``: the sphere's shift
+    as a float32 tensor there (uploaded here, on torch's current stream); the ranks have nothing to upload."""
+
+    def __init__(self, m, device, ordinal):
+        self.kind, self.ordinal = int(m.kind), int(ordinal)
+        self.shift = None if m.shift is None else _torch().from_numpy(np.ascontiguousarray(m.shift, dtype=np.float32)).to(device)
+
+    def out_dim(self, dim):
+        return _capi.rowmap_out_dim(self.kind, dim)
+
+    def rows(self, t, dtype, stream_ptr):
+        """The map of the contiguous (n, d) tensor ``t`` (``dtype``: its NND_DTYPE_*): a new float32 tensor of the map's output
+        width, queued on ``stream_ptr``.  The existing conversion to float32 runs first (csrc/devarray.hip), then csrc/rowmap.hip."""
+        torch = _torch()
+        n, dim = int(t.shape[0]), int(t.shape[1])
+        out = torch.empty((n, _capi.rowmap_out_dim(self.kind, dim)), dtype=torch.float32, device=t.device)
+        if n == 0:
+            return out
+        if dtype != _capi.NND_DTYPE_FLOAT32:
+            x32 = torch.empty((n, dim), dtype=torch.float32, device=t.device)
+            _capi.device_rows_f32(self.ordinal, stream_ptr, t.data_ptr(), dtype, n, dim, False, x32.data_ptr())
+            t = x32
+        _capi.device_map_rows(self.ordinal, stream_ptr, self.kind, dim, dim, 0 if self.shift is None else self.shift.data_ptr(),
+                              t.data_ptr(), n, out.data_ptr())
+        return out
+
+
+def _device_map(m, device, ordinal):
+    """``m`` -- an index's ``LinearMap`` or ``RowMap`` -- on ``device``: the object whose ``rows()`` maps a tensor there."""
+    return (_DeviceRowMap if isinstance(m, row_map.RowMap) else _DeviceLinear)(m, device, ordinal)
 
 
 def _device_corrected(torch, dist, m, ordinal):

@@ -2,17 +2,18 @@
 """
 import numpy as np
 
-from . import _capi, device_arrays, linear_map, sparse_input, tags as tagwords
+from . import _capi, device_arrays, row_map, sparse_input, tags as tagwords
 from .build import _check_array_no_scan, _raise_if_nonfinite
-from .device_arrays import (_check_device_array, _device_corrected, _DeviceLinear, _DeviceRowsView, _dtype_name, _ids_to_host,
+from .device_arrays import (_check_device_array, _device_corrected, _DeviceRowsView, _dtype_name, _ids_to_host,
                             _is_device_array, _OnTorchStream, _rows_to_host, _shape_of)
 from .metrics import (_METRICS, _NEGATIVE_HELLINGER, _linear_map_of, _metric_record, _no_exact_for_proxy,
                       _raise_if_negative_host)
 
 
 def _exact_linear_rows(metric, m, metric_kwds, data, queries, device):
-    """``exact_knn`` of a metric with a linear map: ``(data, queries)`` transformed by the device (float32; tensors stay tensors),
-    on which the search is euclidean.  The shift is the one an index of ``data`` would fix; distances do not depend on it."""
+    """``exact_knn`` of a metric with a linear map or a row map: ``(data, queries)`` transformed by the device (float32; tensors
+    stay tensors), on which the search is the base metric's (euclidean; spearmanr: correlation).  The shift is the one an index of
+    ``data`` would fix; distances do not depend on it."""
     if _is_device_array(data):
         data, dtype, ordinal = _check_device_array(data, device)
         lin = _linear_map_of(metric, m, metric_kwds, data.shape[1])
@@ -20,7 +21,9 @@ def _exact_linear_rows(metric, m, metric_kwds, data, queries, device):
             return data, queries
         torch = device_arrays._torch()
         with torch.cuda.device(ordinal):
-            dl = _DeviceLinear(lin._replace(shift=linear_map.shift_of(_DeviceRowsView(data))), data.device, ordinal)
+            if m.row_map is not None:
+                device_arrays._assert_all_finite(data)
+            dl = device_arrays._device_map(row_map.with_shift(lin, _DeviceRowsView(data)), data.device, ordinal)
             stream = torch.cuda.current_stream(ordinal).cuda_stream
             if queries is not None:
                 if _is_device_array(queries):
@@ -30,19 +33,25 @@ def _exact_linear_rows(metric, m, metric_kwds, data, queries, device):
                     queries, q_dtype = torch.from_numpy(_check_array_no_scan(queries)).to(data.device), _capi.NND_DTYPE_FLOAT32
                 if queries.shape[1] != data.shape[1]:
                     raise ValueError("queries must have shape (n_queries, %d)" % data.shape[1])
+                if m.row_map is not None:
+                    device_arrays._assert_all_finite(queries)
                 queries = dl.rows(queries, q_dtype, stream)
             return dl.rows(data, dtype, stream), queries
     data = _check_array_no_scan(data)
     lin = _linear_map_of(metric, m, metric_kwds, data.shape[1])
     if lin is None:
         return data, queries
-    lin = lin._replace(shift=linear_map.shift_of(data))
+    if m.row_map is not None:  # (mapped rows are finite whatever the input holds: the scan comes first)
+        device_arrays._assert_all_finite(data)
+    lin = row_map.with_shift(lin, data)
     if queries is not None:
         queries = _check_array_no_scan(_rows_to_host(queries))
         if queries.shape[1] != data.shape[1]:
             raise ValueError("queries must have shape (n_queries, %d)" % data.shape[1])
-        queries = _capi.linear_rows_host(lin.kind, lin.a, lin.shift, queries, device=device)
-    return _capi.linear_rows_host(lin.kind, lin.a, lin.shift, data, device=device), queries
+        if m.row_map is not None:
+            device_arrays._assert_all_finite(queries)
+        queries = row_map.rows_host(lin, queries, device=device)
+    return row_map.rows_host(lin, data, device=device), queries
 
 
 def _exact_knn_sparse(data, queries, k, metric, m, rows, device, return_stats, metric_kwds, words=None):
@@ -92,7 +101,7 @@ def _unfilled_to_inf(idx, dist):
 
 
 def exact_knn(data, queries=None, k=10, metric="euclidean", rows=None, device=0, return_stats=False, metric_kwds=None,
-              _host_answers=False, row_tags=None, query_tags=None):
+              _host_answers=False, row_tags=None, query_tags=None, _record=None):
     """Exact ``k`` nearest neighbours by brute force on the GPU (csrc/exact.hip): of every row of ``data`` (self included), of the
     rows ``rows`` of it, or of the external ``queries``.  Returns ``(indices int32 (m, k), distances float32-precision (m, k))``
     in the metric's own space (the correction ``NNDescent.neighbor_graph`` applies), rows ascending, ties to the smaller id;
@@ -109,7 +118,10 @@ def exact_knn(data, queries=None, k=10, metric="euclidean", rows=None, device=0,
     ``metric_kwds``: the arguments of seuclidean / wminkowski (p = 2) / mahalanobis / minkowski (p = 2), read positionally as by
     ``NNDescent``; every other metric ignores it.  For these metrics the answers are exact in this sense: (float64 distance, id)
     on the float32 transformed rows -- the rows ``A (x - c)`` the device computes once (csrc/linear.hip), on which the search is
-    the euclidean one.
+    the euclidean one.  spearmanr and haversine (2-D ``(lat, lon)`` rows, radians) likewise: exact on the float32 rows their row
+    map makes (csrc/rowmap.hip) -- rank rows, which are exact themselves, and the points of the unit sphere.  ``_record``
+    (``NNDescent``'s filtered paths): a derived metric's record for rows and queries that are mapped already; ``metric`` then
+    names the base metric.
 
     ``data`` and / or ``queries`` may be ``scipy.sparse`` matrices, for the metrics ``NNDescent`` takes with sparse input: they
     are made dense on the device (sparse_input.py) and the device route searches; the answers are numpy arrays, those of the dense
@@ -126,13 +138,16 @@ def exact_knn(data, queries=None, k=10, metric="euclidean", rows=None, device=0,
     k = int(k)
     if k > 256:
         raise NotImplementedError("pynndescent_amd.exact_knn keeps at most k <= 256 neighbours per row (got k = %d)" % k)
-    m = _metric_record(metric)
+    m = _metric_record(metric) if _record is None else _record
     _no_exact_for_proxy(metric, m, "exact_knn")
     if sparse_input.is_sparse(data) or sparse_input.is_sparse(queries):
         return _exact_knn_sparse(data, queries, k, metric, m, rows, device, return_stats, metric_kwds, words)
     if m.linear:  # (metric_kwds is validated in there, before any device work)
         data, queries = _exact_linear_rows(metric, m, metric_kwds, data, queries, device)
         metric, m = "euclidean", _METRICS["euclidean"]
+    elif m.row_map is not None and _record is None:  # the base metric's kernels, the derived metric's own correction
+        data, queries = _exact_linear_rows(metric, m, metric_kwds, data, queries, device)
+        metric = m.row_map.base
     if _is_device_array(data):
         return _exact_knn_device(data, queries, k, metric, m, rows, device, return_stats, host_answers=_host_answers, words=words)
     queries, rows = _rows_to_host(queries), _ids_to_host(rows)  # (the results live where the data lives)

@@ -15,7 +15,7 @@ from collections import namedtuple
 
 import numpy as np
 
-from . import _capi, device_arrays
+from . import _capi, device_arrays, row_map
 from .device_arrays import _dtype_name, _is_device_array, _shape_of
 from .exact import exact_knn
 from .metrics import _metric_of
@@ -157,11 +157,11 @@ def query_exact(index, query_data, k, f, host_answers=False):
             with torch.cuda.device(ordinal):
                 query_data = index._linear_on_device(q.device).rows(q, dtype, torch.cuda.current_stream(ordinal).cuda_stream)
         else:
-            query_data = _capi.linear_rows_host(lin.kind, lin.a, lin.shift, np.asarray(query_data).astype(np.float32, order="C"),
+            query_data = row_map.rows_host(lin, np.asarray(query_data).astype(np.float32, order="C"),
                                                 device=index.device)
     kk = min(int(k), int(f.n_allowed))
     idx, dist = exact_knn(compact, queries=query_data, k=kk, metric=index._kernel_metric(), device=index.device,
-                          _host_answers=host_answers)
+                          _host_answers=host_answers, _record=index._mapped_record())
     if _is_device_array(idx):
         torch = device_arrays._torch()
         idx = ids_on(idx.device)[idx.long()].to(torch.int32)
@@ -277,11 +277,11 @@ def query_tagged_exact(index, query_data, k, masks, masks_on_device, host_answer
             with torch.cuda.device(ordinal):
                 query_data = index._linear_on_device(q.device).rows(q, dtype, torch.cuda.current_stream(ordinal).cuda_stream)
         else:
-            query_data = _capi.linear_rows_host(lin.kind, lin.a, lin.shift, np.asarray(query_data).astype(np.float32, order="C"),
+            query_data = row_map.rows_host(lin, np.asarray(query_data).astype(np.float32, order="C"),
                                                 device=index.device)
     kk = min(int(k), int(_shape_of(rows)[0]))
     idx, dist = exact_knn(rows, queries=query_data, k=kk, metric=index._kernel_metric(), device=index.device, _host_answers=host_answers,
-                          row_tags=index._row_tags, query_tags=masks)
+                          row_tags=index._row_tags, query_tags=masks, _record=index._mapped_record())
     if _is_device_array(idx):
         torch = device_arrays._torch()
         if kk < k:

@@ -1,12 +1,14 @@
 """The metrics of the device path: one table of records, the corrections, and what each metric refuses.
 
-Host only: numpy, the constants and host helpers of ``_capi`` (the library is not loaded here) and ``linear_map``.
+Host only: numpy, the constants and host helpers of ``_capi`` (the library is not loaded here), ``linear_map`` and ``row_map``
+(the derived metrics: a registry of their own, consulted after the table).
 """
 from typing import Callable, NamedTuple
 
 import numpy as np
 
-from . import _capi, linear_map
+from . import _capi, linear_map, row_map
+from .row_map import correct_haversine  # noqa: F401
 
 
 def correct_alternative_cosine(d):
@@ -44,6 +46,19 @@ class _Metric(NamedTuple):
     # a function of the counts of indicator rows (x != 0): the device turns the rows into indicators itself (csrc/prep.hip), so
     # the host hands over the caller's rows as they are; one GPU, no uint8 proxy
     boolean: bool = False
+    # a derived metric (row_map.py): its ``RowMapMetric`` -- the device works on a mapped float32 copy of the rows with the kernels
+    # of the base metric's ``code``; _raw_data stays the caller's rows.  None for every record of the table
+    row_map: object = None
+
+    @property
+    def mapped(self):
+        """The device works on a transformed copy of the rows (a linear map or a row map), which the index keeps next to them."""
+        return self.linear or self.row_map is not None
+
+    @property
+    def kernel_metric(self):
+        """The name of the table whose kernels run on the mapped rows; None for a metric that is its own."""
+        return "euclidean" if self.linear else (self.row_map.base if self.row_map is not None else None)
 
 
 # every accepted name.  Corrections: numpy.sqrt, large float32 arrays through the library's threaded sqrtf (the same bits, the
@@ -85,23 +100,35 @@ _DISTANCE_CORRECTIONS = {name: m.correction for name, m in _METRICS.items()}
 _ANGULAR_METRICS = frozenset(name for name, m in _METRICS.items() if m.angular)
 
 
+def _derived_record(spec):
+    """The record of a derived metric: the base record's kernels, the derived metric's own corrections, and no flag of the base
+    metric's but its code -- ``angular`` is what the reference reports for these names (False, pynndescent_.py:1075-1086; the
+    device splits the mapped rows as the base metric does)."""
+    return _Metric(_METRIC_TABLE[spec.base].code, spec.correction, device_kind=spec.device_kind, row_map=spec)
+
+
+_DERIVED_METRICS = {name: _derived_record(spec) for name, spec in row_map.ROW_MAP_METRICS.items()}
+
+
 def _metric_of(name):
     """The record of a metric an index already has (its name was accepted by ``_metric_record``)."""
-    return _METRIC_TABLE[name]
+    return _METRIC_TABLE[name] if name in _METRIC_TABLE else _DERIVED_METRICS[name]
 
 
 def _metric_record(metric, reference_fallback=True):
-    """The row of ``_METRIC_TABLE``.  A metric off the device path raises the reference's ValueError (pynndescent_.py:1292), or
+    """The row of ``_METRIC_TABLE``, or the record of a derived metric (``row_map.ROW_MAP_METRICS``).  A metric off the device path raises the reference's ValueError (pynndescent_.py:1292), or
     with ``reference_fallback`` NotImplementedError when the reference runs it (a callable, a name it knows): what
     ``make_index`` hands to ``pynndescent.NNDescent``."""
     if not callable(metric) and metric in _METRIC_TABLE:
         return _METRIC_TABLE[metric]
+    if not callable(metric) and metric in _DERIVED_METRICS:
+        return _DERIVED_METRICS[metric]
     if reference_fallback and (callable(metric) or metric in _KNOWN_REFERENCE_METRICS):
         raise NotImplementedError(
             "pynndescent_amd accelerates the dense euclidean / l2 / sqeuclidean / cosine / dot / inner_product / "
             "correlation / hellinger / proxy_inner_product / seuclidean / standardised_euclidean / mahalanobis build and the "
             "p = 2 form of minkowski / wminkowski / weighted_minkowski, and the boolean metrics jaccard / dice / sokalsneath / "
-            "matching / rogerstanimoto / sokalmichener / kulsinski / russellrao / yule only; "
+            "matching / rogerstanimoto / sokalmichener / kulsinski / russellrao / yule, and spearmanr / haversine only; "
             "use pynndescent.NNDescent for metric %r" % (metric,)
         )
     raise ValueError("Metric is neither callable, " + "nor a recognised string")
@@ -129,20 +156,24 @@ def _check_quantization(quantization, metric):
 
 
 def _linear_map_of(metric, m, metric_kwds, dim):
-    """The ``LinearMap`` (without its shift) of a metric that carries one; None for every other metric -- ``metric_kwds`` stays
-    unread for those -- and for minkowski with p = 2.  Raises what ``linear_map.parse_metric_kwds`` raises."""
+    """The ``LinearMap`` (without its shift) of a metric that carries one, the ``RowMap`` of a derived metric; None for every other
+    metric -- ``metric_kwds`` stays unread for those -- and for minkowski with p = 2.  Raises what
+    ``linear_map.parse_metric_kwds`` / ``row_map.row_map_of`` raise."""
+    if m.row_map is not None:
+        return row_map.row_map_of(m.row_map, dim)
     return linear_map.parse_metric_kwds(metric, metric_kwds, dim) if m.linear else None
 
 
 def _refuse_uint8_and_sharding(metric, m, quantization, n_devices):
-    """What the metrics with a linear map, and the boolean metrics, do not combine with, reported before any device work."""
-    if not (m.linear or m.boolean):
+    """What the metrics with a linear map or a row map, and the boolean metrics, do not combine with, reported before any device
+    work."""
+    if not (m.mapped or m.boolean):
         return
     if quantization == "uint8":
         _check_quantization(quantization, metric)  # the reference's ValueError("Not uint8 quantization version of ...")
     if int(n_devices) > 1:
         raise NotImplementedError("pynndescent_amd builds metric %r on one GPU (n_devices = %d): the row-sharded build has no "
-                                  "%s; use n_devices=1" % (metric, int(n_devices), "linear map" if m.linear else "boolean metrics"))
+                                  "%s; use n_devices=1" % (metric, int(n_devices), "linear map" if m.linear else ("row map" if m.row_map is not None else "boolean metrics")))
 
 
 # the reference's functions of the kernels' own spaces (pynndescent_.py:1247-1260) -> the metric whose kernels they name;

@@ -14,7 +14,9 @@ must be non-negative: a negative entry raises ``ValueError``, where the referenc
 proxy_inner_product (graph and walk on the reference's proxy distance, queries reranked by the true inner product); and the
 metrics that are euclidean after a fixed linear map of the rows, with ``metric_kwds`` read positionally as the reference reads
 it: seuclidean / standardised_euclidean ``(V,)``, wminkowski / weighted_minkowski ``(w,)`` or ``(w, 2)``, mahalanobis ``(VI,)``
-and minkowski ``()`` or ``(2,)`` (linear_map.py; the device transforms every row once, csrc/linear.hip).
+and minkowski ``()`` or ``(2,)`` (linear_map.py; the device transforms every row once, csrc/linear.hip); and the derived metrics
+spearmanr (correlation of the rows' average ranks) and haversine (2-D rows ``(lat, lon)`` in radians: euclidean on their points of
+the unit sphere, handed out as the angle), whose rows the device maps once as well (row_map.py, csrc/rowmap.hip).
 Sparse input (any ``scipy.sparse`` matrix, for the metrics the reference's sparse path has too) is uploaded as CSR and made dense
 on the device (sparse_input.py, csrc/sparse.hip); from there it is a device-resident index whose ``_raw_data`` is the CSR matrix.
 Out of scope: sparse input whose dense rows do not fit the device or with ``n_devices`` > 1, torch sparse tensors, every other
@@ -31,7 +33,7 @@ from warnings import warn
 import numpy as np
 from sklearn.utils import check_array, check_random_state
 
-from . import _capi, build, device_arrays, filtered, linear_map, sparse_input, tags as tagwords
+from . import _capi, build, device_arrays, filtered, linear_map, row_map, sparse_input, tags as tagwords
 # Every name below was defined here once and is read here still (tests, tools/, and pickles, which name
 # pynndescent_amd.nndescent.correct_alternative_*): the same objects as in their home modules.  Two are replaced by tests and
 # are therefore CALLED through their home module alone -- ``build.ts()``, ``device_arrays._torch()``.
@@ -282,10 +284,13 @@ class NNDescent:
         if dev_in is None:
             data = self._raw_data
         self._linear_map = None
+        if m.row_map is not None:  # (the mapped rows are finite whatever the input holds: the prep kernel's flag cannot tell)
+            device_arrays._assert_all_finite(data)
         if lin is not None:  # the shift is fixed here, once; the device builds on the transformed copy, _raw_data stays the caller's
-            self._linear_map = lin = lin._replace(shift=linear_map.shift_of(data if dev_in is None else _DeviceRowsView(data)))
+            # (_linear_map: the index's LinearMap, or the RowMap of a derived metric -- one attribute, one set of code paths)
+            self._linear_map = lin = row_map.with_shift(lin, data if dev_in is None else _DeviceRowsView(data))
             if dev_in is None:
-                data = self._lin_data = _capi.linear_rows_host(lin.kind, lin.a, lin.shift, data, device=device)
+                data = self._lin_data = row_map.rows_host(lin, data, device=device)
             else:
                 dev_in.linear = self._linear_on_device(data.device)
 
@@ -421,7 +426,7 @@ class NNDescent:
             # the transformed rows of a host index that has none at hand (unpickled, from_graph): a row's transform depends on
             # the row alone, so transforming _raw_data again gives the bits the index was built on, in _raw_data's order
             lin = d["_linear_map"]
-            value = _capi.linear_rows_host(lin.kind, lin.a, lin.shift, self._raw_data, device=self.device)
+            value = row_map.rows_host(lin, self._raw_data, device=self.device)
         elif name == "_neighbor_graph" and "_device_graph" in d:
             value = tuple(np.ascontiguousarray(t.cpu().numpy()) for t in d["_device_graph"])
         elif name == "_search_graph" and "_device_search_graph" in d:
@@ -457,8 +462,15 @@ class NNDescent:
             self.__dict__.pop(name, None)
 
     def _kernel_metric(self):
-        """The metric name the kernels run: the index's own, or euclidean on the transformed rows of a linear map."""
-        return "euclidean" if _metric_of(self.metric).linear else self.metric
+        """The metric name the kernels run: the index's own, euclidean on the transformed rows of a linear map, or the base
+        metric of a derived one on its mapped rows."""
+        return _metric_of(self.metric).kernel_metric or self.metric
+
+    def _mapped_record(self):
+        """For ``exact_knn`` on rows a row map has made already: the derived metric's record (the base metric's kernels, its own
+        correction); None for every other metric, whose ``_kernel_metric()`` says it all."""
+        m = _metric_of(self.metric)
+        return m if m.row_map is not None else None
 
     def _work_rows(self):
         """The host rows the device works on: ``_raw_data``, its transformed copy ``_lin_data`` for a metric with a linear map, or
@@ -468,11 +480,12 @@ class NNDescent:
         return self._lin_data if self.__dict__.get("_linear_map") is not None else self._raw_data
 
     def _linear_on_device(self, device):
-        """The index's linear map as tensors on ``device`` (a ``_DeviceLinear``), uploaded once."""
+        """The index's linear map as tensors on ``device`` (a ``_DeviceLinear``; a derived metric: its ``_DeviceRowMap``), uploaded
+        once."""
         d = self.__dict__
         if d.get("_device_linear") is None:
             ordinal = getattr(device, "index", None)
-            d["_device_linear"] = _DeviceLinear(d["_linear_map"], device, int(self.device) if ordinal is None else ordinal)
+            d["_device_linear"] = device_arrays._device_map(d["_linear_map"], device, int(self.device) if ordinal is None else ordinal)
         return d["_device_linear"]
 
     @property
@@ -564,13 +577,15 @@ class NNDescent:
         seuclidean / wminkowski / mahalanobis / minkowski: the reference keeps no squared space for them, so the graph handed
         over holds true distances, and the search structures of a prepared index are LEFT OUT of the hand-over (its tree's
         hyperplanes split the transformed space, the reference's tree descent takes raw queries): the rows go back to their
-        original order and the reference's own ``prepare()`` rebuilds tree and search graph from the graph."""
+        original order and the reference's own ``prepare()`` rebuilds tree and search graph from the graph.  spearmanr /
+        haversine: the same, for the same reason (the graph's distances go over as the metric's own, float32)."""
         if self.__dict__.get("_is_sparse"):
             raise NotImplementedError("to_reference() of an index built from sparse input: the reference's sparse search "
                                       "structures (sparse hub tree, sparse distances) are not produced; build with pynndescent.NNDescent")
         import pynndescent
 
-        linear = _metric_of(self.metric).linear
+        m = _metric_of(self.metric)
+        linear = m.mapped
         ref = object.__new__(pynndescent.NNDescent)
         for name in self._HANDOVER:
             if hasattr(self, name):
@@ -579,7 +594,9 @@ class NNDescent:
             ref._raw_data = np.ascontiguousarray(self._raw_data[np.argsort(self._vertex_order), :])
         if hasattr(self, "_neighbor_graph"):
             dist = self._neighbor_graph[1]
-            ref._neighbor_graph = (self._neighbor_graph[0].copy(), np.sqrt(dist) if linear else dist.copy())
+            if linear:  # true distances: sqrt of the code-0 value, or the derived metric's own correction
+                dist = np.sqrt(dist) if m.linear else m.correction(dist).astype(np.float32)
+            ref._neighbor_graph = (self._neighbor_graph[0].copy(), dist.copy() if not linear else dist)
         ref._distance_correction = None
         ref._set_distance_func()  # pynndescent_.py:1271-1298: numba distance, correction, proxy flags
         if hasattr(self, "_search_graph") and not linear:  # prepared on the GPU: the reference's prepare() has nothing left to build
@@ -625,7 +642,7 @@ class NNDescent:
         _refuse_uint8_and_sharding(metric, m, self.quantization, 1)
         self._set_up(data, m, random_state, copy=True)  # (dot: the data NNDescent would hold, in a new array)
         # (``distances`` of a metric with a linear map: squared, of the rows transformed with this shift -- what the build keeps)
-        self._linear_map = None if lin is None else lin._replace(shift=linear_map.shift_of(self._raw_data))
+        self._linear_map = None if lin is None else row_map.with_shift(lin, self._raw_data)
         self._rp_forest = _DeviceForestSentinel(self.n_trees, 0, 0)
         self._neighbor_graph = (indices, distances)
         return self
@@ -1065,7 +1082,7 @@ class NNDescent:
         _raise_if_negative_host(query_data, m)
         lin = self.__dict__.get("_linear_map")
         if lin is not None:  # the queries through the index's own (A, c), by the kernel that transformed its rows
-            query_data = _capi.linear_rows_host(lin.kind, lin.a, lin.shift, query_data, device=self.device)
+            query_data = row_map.rows_host(lin, query_data, device=self.device)
         if query_masks is not None:  # the same three forms, eps as below
             form = "proxy" if self.quantization is not None else ("rerank" if m.proxy else "float")
             indices, dists = self._searcher.query_tagged(form, query_data, query_masks, k, search_k, epsilon + (1e-32 if form == "proxy" else 0.0))
@@ -1261,8 +1278,10 @@ class NNDescent:
         else:  # pynndescent_.py:2512-2517: the old graph's entries as "old" edges, then the forest's; no random fill
             lin, work = self.__dict__.get("_linear_map"), raw
             self.__dict__.pop("_lin_data", None)
+            if _metric_of(self.metric).row_map is not None:
+                device_arrays._assert_all_finite(raw)
             if lin is not None:  # old, updated and fresh rows through the index's own (A, c): old rows come out as they were
-                work = self._lin_data = _capi.linear_rows_host(lin.kind, lin.a, lin.shift, raw, device=self.device)
+                work = self._lin_data = row_map.rows_host(lin, raw, device=self.device)
             self._neighbor_graph, self._build_stats, n_leaves = _build_graph(
                 work, _metric_of(self.metric), self.n_neighbors, self.n_trees, eff_leaf_size, self.max_rptree_depth,
                 eff_max_candidates, self.n_iters, self.delta, self.rng_state, tree_states[0], self.device, forest=True,
@@ -1333,6 +1352,8 @@ class NNDescent:
                                           updated_map.data_ptr(), pad_i.data_ptr(), pad_d.data_ptr())
             finally:
                 stream.done()
+            if m.row_map is not None:
+                device_arrays._assert_all_finite(new_data)
             # pynndescent_.py:2512-2517: the old graph's entries as "old" edges, then the forest's; no random fill
             dev_in = _DeviceInput(new_data, _DEVICE_DTYPES[out_name], ordinal, self.n_neighbors, as_given=True, linear=linear)
             graph, build_stats, n_leaves = _build_graph(
@@ -1371,7 +1392,7 @@ def make_index(data, *args, **kwargs):
     """``NNDescent(data, ...)`` on the GPU when the input is in scope (dense data, or sparse data whose dense rows fit the device
     and a metric the reference's sparse path has too; euclidean / l2 / sqeuclidean / cosine / dot /
     inner_product / correlation / hellinger / proxy_inner_product / seuclidean / mahalanobis / minkowski and wminkowski with p = 2 /
-    the boolean metrics jaccard, dice, sokalsneath, matching, rogerstanimoto, sokalmichener, kulsinski, russellrao and yule,
+    spearmanr / haversine / the boolean metrics jaccard, dice, sokalsneath, matching, rogerstanimoto, sokalmichener, kulsinski, russellrao and yule,
     k <= 256);
     otherwise -- and only then -- the reference ``pynndescent.NNDescent`` on the CPU when that package is importable
     (SURVEY.md section 8b), with a warning.  A missing HIP library or GPU is never papered over: that still raises."""

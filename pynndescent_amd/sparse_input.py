@@ -15,10 +15,11 @@ import numpy as np
 
 from . import _capi, device_arrays
 
-# names of the project's metric table that the reference's sparse path does not have (sparse.py sparse_named_distances): the
-# reference refuses them for sparse data with a ValueError, and so does this path, with the same words (pynndescent_.py:1122)
+# names of the project's metric table, and its derived metrics, that the reference's sparse path does not have (sparse.py
+# sparse_named_distances): the reference refuses them for sparse data with a ValueError, and so does this path, with the same
+# words (pynndescent_.py:1122)
 SPARSE_REFUSED_METRICS = frozenset(("dot", "inner_product", "proxy_inner_product", "yule", "seuclidean", "standardised_euclidean",
-                                    "wminkowski", "weighted_minkowski", "mahalanobis"))
+                                    "wminkowski", "weighted_minkowski", "mahalanobis", "spearmanr", "haversine"))
 
 
 def is_sparse(a):
