@@ -756,6 +756,33 @@ int32_t nnd_searcher_query_tagged_device(nnd_searcher_t s, int32_t form, const f
 int32_t nnd_searcher_destroy(nnd_searcher_t s);
 const char *nnd_searcher_last_error(nnd_searcher_t s /* NULL: the error of a failed create */);
 
+/* ---- graph export: k-lists to canonical CSR on the device (csrc/csr_graph.hip; DESIGN.md "Graph export") ----
+ * ids: (m, k) int32 or int64 (id_bytes 4 or 8), vals: float32 (m, k), k <= 256; a place whose id is -1 -- or anything else
+ * outside [0, n) -- is empty.  A row must not hold one id twice.  Result: the (m, n) matrix in CSR form -- indptr int64
+ * (m + 1), indices int32 (nnz), data float32 (nnz), columns strictly ascending in every row: scipy's coo.tocsr() +
+ * sum_duplicates().  mode: NND_CSR_DISTANCE keeps the values, NND_CSR_CONNECTIVITY stores 1.0f; | NND_CSR_DROP_SELF drops
+ * the places (i, i).  symmetric (m == n only): the union of the matrix and its transpose; an entry present on both sides
+ * holds the smaller of the two floats, so the result does not depend on the order the device found the edges in.
+ * A row whose k places and reverse edges together are more than 512 (a hub) is merged by a workgroup in global memory, the
+ * others by one wave in registers; long_rows counts the former.
+ *
+ * nnd_graph_csr_device: device pointers, row stride ld >= k elements, on `hip_stream` (NULL: the device's default stream) of
+ * `device`; returns with the stream drained.  The arrays belong to the nnd_csr_t: nnd_csr_arrays hands out their device
+ * addresses and nnz (any out pointer may be NULL), nnd_csr_destroy frees them.
+ * nnd_graph_csr: the same on host arrays (contiguous rows); indices / data have room for `capacity` entries -- m * k always
+ * suffices for the directed form, 2 * m * k for the symmetric one; *nnz is set even when the room does not suffice. */
+#define NND_CSR_DISTANCE 0
+#define NND_CSR_CONNECTIVITY 1
+#define NND_CSR_DROP_SELF 2
+typedef struct nnd_csr_s *nnd_csr_t;
+int32_t nnd_graph_csr_device(int32_t device, void *hip_stream, const void *ids_dev, int32_t id_bytes, const float *vals_dev, int64_t m,
+                             int32_t k, int64_t ld, int64_t n, int32_t mode, int32_t symmetric, nnd_csr_t *out);
+int32_t nnd_csr_arrays(nnd_csr_t g, const int64_t **indptr_dev, const int32_t **indices_dev, const float **data_dev, int64_t *nnz,
+                       int64_t *long_rows);
+int32_t nnd_csr_destroy(nnd_csr_t g);
+int32_t nnd_graph_csr(int32_t device, const void *ids, int32_t id_bytes, const float *vals, int64_t m, int32_t k, int64_t n, int32_t mode,
+                      int32_t symmetric, int64_t *indptr, int32_t *indices, float *data, int64_t capacity, int64_t *nnz, int64_t *long_rows);
+
 #ifdef __cplusplus
 }
 #endif

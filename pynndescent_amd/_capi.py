@@ -43,6 +43,8 @@ NND_QUERY_FORMS = {"float": 0, "proxy": 1, "rerank": 2}  # nnd_searcher_query_ta
 NND_CORRECT_COPY, NND_CORRECT_SQRT, NND_CORRECT_ALT_COSINE, NND_CORRECT_ALT_INNER_PRODUCT, NND_CORRECT_ALT_HELLINGER = 0, 1, 2, 3, 4
 NND_CORRECT_HAVERSINE = 5
 NND_LINEAR_DIAGONAL, NND_LINEAR_DENSE = 0, 1  # the kinds of a metric's linear map (include/pynnd_amd.h NND_LINEAR_*, csrc/linear.hip)
+NND_CSR_DISTANCE, NND_CSR_CONNECTIVITY, NND_CSR_DROP_SELF = 0, 1, 2  # nnd_graph_csr's `mode` (csrc/csr_graph.hip); DROP_SELF is or-ed in
+CSR_MAX_K = 256  # the widest k-list nnd_graph_csr takes (csrc/csr_graph.hip CSR_REG_CAP)
 NND_ROWMAP_RANK, NND_ROWMAP_SPHERE = 0, 1  # the kinds of a derived metric's row map (include/pynnd_amd.h NND_ROWMAP_*, csrc/rowmap.hip)
 ROWMAP_RANK_MAX_DIM = 16384  # the widest row nnd_device_map_rows ranks (csrc/rowmap.hip RM_RANK_MAX)
 NND_FLAG_NO_GRAPH = 1  # auxiliary handle: no k-lists / candidate / proposal tables (pruning pass, hub tree)
@@ -351,6 +353,13 @@ _SIGNATURES = [
                                                         C.c_void_p, C.POINTER(NNDExactStats)]),
     ("nnd_searcher_destroy", C.c_int32, [_H]),
     ("nnd_searcher_last_error", C.c_char_p, [_H]),
+    ("nnd_graph_csr_device", C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64,
+                                         C.c_int32, C.c_int32, C.POINTER(_H)]),
+    ("nnd_csr_arrays", C.c_int32, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
+                                   C.POINTER(C.c_int64)]),
+    ("nnd_csr_destroy", C.c_int32, [_H]),
+    ("nnd_graph_csr", C.c_int32, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
 ]
 EXPORTED_SYMBOLS = [s[0] for s in _SIGNATURES]
 
@@ -1205,3 +1214,76 @@ def reorder_host(order, indptr, indices, x, device=0):
                             _ptr(out_x)) != 0:
         raise NNDError(lib.nnd_last_global_error().decode())
     return out_ptr, out_ind[:nnz], out_x
+
+
+def _csr_mode(mode, drop_self=False):
+    """``"distance"`` / ``"connectivity"`` (or an NND_CSR_* code) as nnd_graph_csr's ``mode``, NND_CSR_DROP_SELF or-ed in."""
+    code = {"distance": NND_CSR_DISTANCE, "connectivity": NND_CSR_CONNECTIVITY}.get(mode, mode)
+    if code not in (NND_CSR_DISTANCE, NND_CSR_CONNECTIVITY):
+        raise ValueError("mode must be 'distance' or 'connectivity' (got %r)" % (mode,))
+    return code | (NND_CSR_DROP_SELF if drop_self else 0)
+
+
+def graph_csr(ids, vals, n, mode="distance", symmetric=False, drop_self=False, device=0, want_long_rows=False):
+    """Host k-lists -> canonical CSR by the device kernels (``nnd_graph_csr``, csrc/csr_graph.hip): ``ids`` (m, k) int32 or int64
+    with -1 for an empty place, ``vals`` (m, k) float32, ``n`` columns.  Returns (indptr int64 (m + 1), indices int32, data
+    float32)[, rows of the symmetric union that took the long-row kernel]."""
+    lib = load_library()
+    ids = np.asarray(ids)
+    ids = np.ascontiguousarray(ids, dtype=np.int64 if ids.dtype == np.int64 else np.int32)
+    vals = np.ascontiguousarray(vals, dtype=np.float32)
+    assert ids.ndim == 2 and vals.shape == ids.shape
+    m, k = ids.shape
+    cap = max(1, m * k * (2 if symmetric else 1))
+    indptr, indices, data = np.empty(m + 1, np.int64), np.empty(cap, np.int32), np.empty(cap, np.float32)
+    nnz, long_rows = C.c_int64(), C.c_int64()
+    if lib.nnd_graph_csr(int(device), _ptr(ids), ids.dtype.itemsize, _ptr(vals), m, k, int(n), _csr_mode(mode, drop_self), 1 if symmetric else 0,
+                         _ptr(indptr), _ptr(indices), _ptr(data), cap, C.byref(nnz), C.byref(long_rows)) != 0:
+        raise NNDError(lib.nnd_last_global_error().decode())
+    out = (indptr, indices[: nnz.value].copy(), data[: nnz.value].copy())
+    return out + (int(long_rows.value),) if want_long_rows else out
+
+
+class _DeviceBuffer:
+    """A stretch of a ``DeviceCsr``'s memory as an object with ``__cuda_array_interface__``: ``torch.as_tensor`` wraps it without
+    a copy and keeps this object -- and through it the owner -- alive as long as the tensor lives."""
+
+    def __init__(self, owner, address, count, typestr):
+        self.owner = owner
+        self.__cuda_array_interface__ = {"shape": (int(count),), "typestr": typestr, "data": (int(address), False), "strides": None,
+                                         "version": 2}
+
+
+class DeviceCsr:
+    """Device k-lists -> canonical CSR where they lie (``nnd_graph_csr_device``): ``ids_ptr`` / ``vals_ptr`` are device addresses
+    of an (m, k) int32 / int64 (``id_bytes``) and float32 array with row stride ``ld`` elements; queued on ``stream_ptr`` of
+    ``device``, drained on return.  The object owns the three result arrays (freed with it): ``indptr`` (int64, m + 1),
+    ``indices`` (int32, nnz), ``data`` (float32, nnz) are ``__cuda_array_interface__`` views of them; ``nnz``, ``long_rows``."""
+
+    def __init__(self, device, stream_ptr, ids_ptr, id_bytes, vals_ptr, m, k, ld, n, mode="distance", symmetric=False, drop_self=False):
+        self.lib = load_library()
+        self._h = _H()
+        dev = lambda p: C.c_void_p(int(p)) if p else None  # noqa: E731
+        if self.lib.nnd_graph_csr_device(int(device), dev(stream_ptr), dev(ids_ptr), int(id_bytes), dev(vals_ptr), int(m), int(k), int(ld), int(n),
+                                         _csr_mode(mode, drop_self), 1 if symmetric else 0, C.byref(self._h)) != 0:
+            raise NNDError(self.lib.nnd_last_global_error().decode())
+        indptr, indices, data, nnz, long_rows = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int64(), C.c_int64()
+        self.lib.nnd_csr_arrays(self._h, C.byref(indptr), C.byref(indices), C.byref(data), C.byref(nnz), C.byref(long_rows))
+        self.m, self.n, self.nnz, self.long_rows = int(m), int(n), int(nnz.value), int(long_rows.value)
+        self._addresses = (indptr.value, indices.value, data.value)
+
+    # (made per read: a view kept on the object would be a reference cycle, and the arrays would wait for the collector)
+    indptr = property(lambda self: _DeviceBuffer(self, self._addresses[0], self.m + 1, "<i8"))
+    indices = property(lambda self: _DeviceBuffer(self, self._addresses[1], self.nnz, "<i4"))
+    data = property(lambda self: _DeviceBuffer(self, self._addresses[2], self.nnz, "<f4"))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self.lib.nnd_csr_destroy(self._h)
+            self._h = _H()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -33,7 +33,7 @@ from warnings import warn
 import numpy as np
 from sklearn.utils import check_array, check_random_state
 
-from . import _capi, build, device_arrays, filtered, linear_map, row_map, sparse_input, tags as tagwords
+from . import _capi, build, device_arrays, filtered, graph_export, linear_map, row_map, sparse_input, tags as tagwords
 # Every name below was defined here once and is read here still (tests, tools/, and pickles, which name
 # pynndescent_amd.nndescent.correct_alternative_*): the same objects as in their home modules.  Two are replaced by tests and
 # are therefore CALLED through their home module alone -- ``build.ts()``, ``device_arrays._torch()``.
@@ -922,6 +922,22 @@ class NNDescent:
         if filter is not None:
             return self._query_filtered(query_data, m, k, epsilon, proxy_beam_size, filter, filter_mode)
         return self._query_walk(query_data, m, k, epsilon, proxy_beam_size)
+
+    def kneighbors_graph(self, X=None, k=None, mode="distance", symmetric=False, include_self=True, epsilon=0.1, **query_kwds):
+        """The index's answers as a sparse neighbour matrix in canonical CSR form (graph_export.py, csrc/csr_graph.hip): columns
+        ascending in every row, float32 data, int32 column ids, assembled on the GPU.
+
+        ``X`` None: the built graph, (n, n), with the distances ``neighbor_graph`` hands out; ``k`` (default ``n_neighbors``)
+        takes the first k columns.  ``X`` given: the answers of ``query(X, k, epsilon, **query_kwds)`` as an (n_queries, n)
+        matrix -- ``filter``, ``filter_mode``, ``query_tags`` and ``proxy_beam_size`` pass through, and the (-1, inf) places a
+        filter leaves are dropped, so such a row holds fewer than k entries.
+        ``mode``: "distance" stores the distances, "connectivity" 1.0.  ``symmetric`` (built graph only): the union of the matrix
+        and its transpose; where the two sides of a pair differ in the last bits the entry holds the smaller value.
+        ``include_self=False`` (built graph only) drops every entry (i, i), wherever in the row it stands.
+        Returns ``scipy.sparse.csr_array`` for an index of host (or scipy.sparse) data or one built with ``n_devices`` > 1, and a
+        ``torch.sparse_csr_tensor`` on the index's device, on torch's current stream, for a device-resident index; that tensor
+        is built on the kernels' own buffers, nothing is copied."""
+        return graph_export.kneighbors_graph(self, X, k, mode, symmetric, include_self, epsilon, **query_kwds)
 
     def _query_sparse(self, query_data, m, k, epsilon, proxy_beam_size, filter, filter_mode):
         """``query`` for a ``scipy.sparse`` batch, on an index built from sparse or dense data alike: the batch is made canonical,
