@@ -6,7 +6,7 @@
 //   symmetric   k_csr_sym_count   -> scan -> k_csr_sym_scatter -> k_csr_sym_merge (+ k_csr_sym_merge_long) -> scan -> k_csr_copy_rows
 //
 // A row is sorted as 64-bit keys (column << 32 | value bits) by one wave: a bitonic network over 64, 128 or 256 keys, one,
-// two or four per lane (the KU of query.hip; the symmetric merge also eight, 512 keys), partners at distance < 64 through a
+// two or four per lane (the KU of query.hip's k_query; the symmetric merge also eight, 512 keys), partners at distance < 64 through a
 // lane exchange, the others inside the lane.
 // An empty place is the all-ones key and sorts to the end.  A row of at most 16 or 32 places needs the network's first stages
 // only (W = 16 or 32 lanes: 10 or 15 exchanges where 64 lanes take 21), and the directed form then gives every W lanes of the

@@ -79,19 +79,21 @@ __device__ __forceinline__ void ex_merge_into(uint64_t *scr, uint32_t *__restric
 // 16 w .. 16 w + 15: lane l holds, per accumulator tile J, the Gram values of rows 4 (l >> 4) + r, r = 0..3, and column
 // 16 J + (l & 15) -- so the threshold th[r], the reject minimum rej[r] and the queue fill fill[r] of those four rows live in
 // registers, the same in all 16 lanes of a group.  DC: floats of a row staged per K chunk (dp <= DC: the query rows are staged
-// once); XM: the codes 2..5 (metric.h NND_CODES_0_5; code 6 is refused by the host), else 0 / 1; WIDE: W > 64 (rows merged through LDS).
-// The body is shared by the kernels' instances: k_exact_scan (XM as above) and k_exact_scan_bool, the boolean family's (FAM =
-// NND_CODES_BOOL: `metric` carries the column count, metric.h nnd_kernel_metric).
-// MK: the masked scan (k_exact_scan_masked): data row c is part of query row i's point set only if tags[c] & qmasks[i] != 0 -- `tags`
-// one word per data row, `qmasks` one per query row of the batch.  The masks of a lane group's four rows live in registers beside
-// th and rej, the tags of a data tile are staged beside snrm.  A pair that does not meet is neither admitted nor counted into rej:
-// it is no rejected candidate, and the certificate's T must not see it.
-template <int DC, int FAM, bool WIDE, bool MK = false>
+// once); WIDE: W > 64 (rows merged through LDS).
+// FAM: the metric family (metric.h) -- NND_CODES_01, NND_CODES_0_5 (the codes 2..5; code 6 is refused by the host) or
+// NND_CODES_BOOL (the boolean family: `metric` carries the column count, metric.h nnd_kernel_metric).
+// MK: the masked scan: data row c is part of query row i's point set only if tags[c] & qmasks[i] != 0 -- `tags` one word per
+// data row, `qmasks` one per query row of the batch; the other instances never read either.  The masks of a lane group's four
+// rows live in registers beside th and rej, the tags of a data tile are staged beside snrm.  A pair that does not meet is neither
+// admitted nor counted into rej: it is no rejected candidate, and the certificate's T must not see it.
+// The three kernels of this file (k_exact_scan, k_exact_refine, k_exact_f64) are each one template around an inlined body: with
+// the body in the __global__ function itself the compiler emits other code (DESIGN.md "The search kernels").
+template <int DC, int FAM, bool WIDE, bool MK>
 __device__ __forceinline__ void ex_scan_body(const float *__restrict__ xp, const float *__restrict__ nrm, int64_t n, int dp, int metric,
                                                     const float *__restrict__ qx, const float *__restrict__ qnrm, const int32_t *__restrict__ qids,
                                                     int self, int nq, int nq_pad, int W, int64_t rows_per_slice, uint32_t *__restrict__ list_e,
                                                     float *__restrict__ list_d, float *__restrict__ list_th, float *__restrict__ list_rej,
-                                                    const uint64_t *__restrict__ tags = nullptr, const uint64_t *__restrict__ qmasks = nullptr) {
+                                                    const uint64_t *__restrict__ tags /* MK: (n) */, const uint64_t *__restrict__ qmasks /* MK: (nq) */) {
     extern __shared__ __align__(16) unsigned char ex_smem[];
     float *Xs = (float *)ex_smem;                              // (EX_QB + EX_TB) rows of DC floats, swizzled: queries, then the data tile
     float *snrm = Xs + (EX_QB + EX_TB) * DC;                   // (EX_TB) nrm of the data tile
@@ -219,28 +221,13 @@ __device__ __forceinline__ void ex_scan_body(const float *__restrict__ xp, const
         if (c16 == 0) list_rej[lbase + 4 * g + r] = v;
     }
 }
-template <int DC, bool XM, bool WIDE>
+template <int DC, int FAM, bool WIDE, bool MK>
 __global__ __launch_bounds__(256) void k_exact_scan(const float *__restrict__ xp, const float *__restrict__ nrm, int64_t n, int dp, int metric,
                                                     const float *__restrict__ qx, const float *__restrict__ qnrm, const int32_t *__restrict__ qids,
                                                     int self, int nq, int nq_pad, int W, int64_t rows_per_slice, uint32_t *__restrict__ list_e,
-                                                    float *__restrict__ list_d, float *__restrict__ list_th, float *__restrict__ list_rej) {
-    ex_scan_body<DC, XM ? NND_CODES_0_5 : NND_CODES_01, WIDE>(xp, nrm, n, dp, metric, qx, qnrm, qids, self, nq, nq_pad, W, rows_per_slice, list_e, list_d, list_th, list_rej);
-}
-template <int DC, bool WIDE>
-__global__ __launch_bounds__(256) void k_exact_scan_bool(const float *__restrict__ xp, const float *__restrict__ nrm, int64_t n, int dp, int metric,
-                                                    const float *__restrict__ qx, const float *__restrict__ qnrm, const int32_t *__restrict__ qids,
-                                                    int self, int nq, int nq_pad, int W, int64_t rows_per_slice, uint32_t *__restrict__ list_e,
-                                                    float *__restrict__ list_d, float *__restrict__ list_th, float *__restrict__ list_rej) {
-    ex_scan_body<DC, NND_CODES_BOOL, WIDE>(xp, nrm, n, dp, metric, qx, qnrm, qids, self, nq, nq_pad, W, rows_per_slice, list_e, list_d, list_th, list_rej);
-}
-// the masked scan, all three families in one kernel template (FAM: NND_CODES_01, NND_CODES_0_5 or NND_CODES_BOOL)
-template <int DC, int FAM, bool WIDE>
-__global__ __launch_bounds__(256) void k_exact_scan_masked(const float *__restrict__ xp, const float *__restrict__ nrm, int64_t n, int dp, int metric,
-                                                    const float *__restrict__ qx, const float *__restrict__ qnrm, const int32_t *__restrict__ qids,
-                                                    int self, int nq, int nq_pad, int W, int64_t rows_per_slice, uint32_t *__restrict__ list_e,
                                                     float *__restrict__ list_d, float *__restrict__ list_th, float *__restrict__ list_rej,
-                                                    const uint64_t *__restrict__ tags /* (n) */, const uint64_t *__restrict__ qmasks /* (nq) */) {
-    ex_scan_body<DC, FAM, WIDE, true>(xp, nrm, n, dp, metric, qx, qnrm, qids, self, nq, nq_pad, W, rows_per_slice, list_e, list_d, list_th, list_rej, tags, qmasks);
+                                                    const uint64_t *__restrict__ tags /* MK: (n) */, const uint64_t *__restrict__ qmasks /* MK: (nq) */) {
+    ex_scan_body<DC, FAM, WIDE, MK>(xp, nrm, n, dp, metric, qx, qnrm, qids, self, nq, nq_pad, W, rows_per_slice, list_e, list_d, list_th, list_rej, tags, qmasks);
 }
 
 // ---- the slices' lists folded into slice 0's, one wave per query row ----
@@ -376,32 +363,25 @@ __device__ __forceinline__ void ex_refine_body(const float *__restrict__ x, int 
     nnd_wave_lds_sync();
     if (lane == 0 && !ex_certified<FAM>(metric, d, dp, kth[w][0], kth[w][1], axq, list_rej[q], qnrm[qid], *nmax)) uncert[atomicAdd(n_uncert, 1)] = q;
 }
-template <bool XM>
+template <int FAM>
 __global__ __launch_bounds__(256) void k_exact_refine(const float *__restrict__ x, int d, int dp, int metric, const float *__restrict__ qraw,
                                                       const int32_t *__restrict__ qids, const float *__restrict__ qnrm, int nq, int k, int W,
                                                       const uint32_t *__restrict__ list_e, const float *__restrict__ list_rej,
                                                       const double *__restrict__ nmax, int32_t *__restrict__ out_idx, float *__restrict__ out_dist,
                                                       int32_t *__restrict__ uncert, int32_t *__restrict__ n_uncert) {
-    ex_refine_body<XM ? NND_CODES_0_5 : NND_CODES_01>(x, d, dp, metric, qraw, qids, qnrm, nq, k, W, list_e, list_rej, nmax, out_idx, out_dist, uncert, n_uncert);
-}
-__global__ __launch_bounds__(256) void k_exact_refine_bool(const float *__restrict__ x, int d, int dp, int metric, const float *__restrict__ qraw,
-                                                      const int32_t *__restrict__ qids, const float *__restrict__ qnrm, int nq, int k, int W,
-                                                      const uint32_t *__restrict__ list_e, const float *__restrict__ list_rej,
-                                                      const double *__restrict__ nmax, int32_t *__restrict__ out_idx, float *__restrict__ out_dist,
-                                                      int32_t *__restrict__ uncert, int32_t *__restrict__ n_uncert) {
-    ex_refine_body<NND_CODES_BOOL>(x, d, dp, metric, qraw, qids, qnrm, nq, k, W, list_e, list_rej, nmax, out_idx, out_dist, uncert, n_uncert);
+    ex_refine_body<FAM>(x, d, dp, metric, qraw, qids, qnrm, nq, k, W, list_e, list_rej, nmax, out_idx, out_dist, uncert, n_uncert);
 }
 
 // ---- tier 2: all n original rows in float64, one workgroup per listed query row ----
 // Wave w takes data rows 16 i + 4 w + (0..3), four at a time (16 lanes each), in ascending order, and keeps its k best in an LDS
 // list sorted by (distance, id): a row enters only if it is strictly closer than the list's last (its id is larger than every
-// id the wave has seen).  The four lists are then ranked against each other.  MK (k_exact_f64_masked): rows whose tag word does not
+// id the wave has seen).  The four lists are then ranked against each other.  MK: rows whose tag word does not
 // meet the query row's mask are passed over, and the places that fewer than k allowed rows leave open get (-1, inf).
-template <int FAM, bool MK = false>
+template <int FAM, bool MK>
 __device__ __forceinline__ void ex_f64_body(const float *__restrict__ x, int64_t n, int d, int metric, const float *__restrict__ qraw,
                                                    const int32_t *__restrict__ qids, int k, const int32_t *__restrict__ list,
                                                    int32_t *__restrict__ out_idx, float *__restrict__ out_dist,
-                                                   const uint64_t *__restrict__ tags = nullptr, const uint64_t *__restrict__ qmasks = nullptr) {
+                                                   const uint64_t *__restrict__ tags /* MK: (n) */, const uint64_t *__restrict__ qmasks /* MK: (nq) */) {
     __shared__ double ld[4][NND_WIDE_K];
     __shared__ int32_t li[4][NND_WIDE_K];
     __shared__ int scnt[4];
@@ -482,23 +462,12 @@ __device__ __forceinline__ void ex_f64_body(const float *__restrict__ x, int64_t
         }
     }
 }
-template <bool XM>
+template <int FAM, bool MK>
 __global__ __launch_bounds__(256) void k_exact_f64(const float *__restrict__ x, int64_t n, int d, int metric, const float *__restrict__ qraw,
                                                    const int32_t *__restrict__ qids, int k, const int32_t *__restrict__ list,
-                                                   int32_t *__restrict__ out_idx, float *__restrict__ out_dist) {
-    ex_f64_body<XM ? NND_CODES_0_5 : NND_CODES_01>(x, n, d, metric, qraw, qids, k, list, out_idx, out_dist);
-}
-__global__ __launch_bounds__(256) void k_exact_f64_bool(const float *__restrict__ x, int64_t n, int d, int metric, const float *__restrict__ qraw,
-                                                   const int32_t *__restrict__ qids, int k, const int32_t *__restrict__ list,
-                                                   int32_t *__restrict__ out_idx, float *__restrict__ out_dist) {
-    ex_f64_body<NND_CODES_BOOL>(x, n, d, metric, qraw, qids, k, list, out_idx, out_dist);
-}
-template <int FAM>
-__global__ __launch_bounds__(256) void k_exact_f64_masked(const float *__restrict__ x, int64_t n, int d, int metric, const float *__restrict__ qraw,
-                                                   const int32_t *__restrict__ qids, int k, const int32_t *__restrict__ list,
                                                    int32_t *__restrict__ out_idx, float *__restrict__ out_dist,
-                                                   const uint64_t *__restrict__ tags, const uint64_t *__restrict__ qmasks) {
-    ex_f64_body<FAM, true>(x, n, d, metric, qraw, qids, k, list, out_idx, out_dist, tags, qmasks);
+                                                   const uint64_t *__restrict__ tags /* MK: (n) */, const uint64_t *__restrict__ qmasks /* MK: (nq) */) {
+    ex_f64_body<FAM, MK>(x, n, d, metric, qraw, qids, k, list, out_idx, out_dist, tags, qmasks);
 }
 
 // the largest nrm of the point set (codes 0, 3), or the largest |x|^2 of the rows as given (code 2), as a double; 16 lanes per row
@@ -558,26 +527,37 @@ static int ex_list_width(int k) {
 }
 static size_t ex_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
+// the metric's family as a table index: NND_CODES_01, NND_CODES_0_5, NND_CODES_BOOL
+static int ex_family(int metric) { return nnd_metric_bool(metric) ? 2 : metric >= 2 ? 1 : 0; }
+// every instance of the scan for one DC, by [family][wide][masked]
 template <int DC>
-static int ex_launch_scan(nnd_ctx *ctx, bool xm, bool wide, dim3 grid, const float *qx, const float *qnrm, const int32_t *qids, int self, int nq, int nq_pad,
+static auto ex_scan_kernel(int fam, bool wide, bool masked) -> decltype(&k_exact_scan<DC, NND_CODES_01, false, false>) {
+#define EX_SCAN(FAM) {{k_exact_scan<DC, FAM, false, false>, k_exact_scan<DC, FAM, false, true>}, {k_exact_scan<DC, FAM, true, false>, k_exact_scan<DC, FAM, true, true>}}
+    static const decltype(&k_exact_scan<DC, NND_CODES_01, false, false>) table[3][2][2] = {EX_SCAN(NND_CODES_01), EX_SCAN(NND_CODES_0_5), EX_SCAN(NND_CODES_BOOL)};
+#undef EX_SCAN
+    return table[fam][wide][masked];
+}
+static auto ex_refine_kernel(int fam) -> decltype(&k_exact_refine<NND_CODES_01>) {
+    static const decltype(&k_exact_refine<NND_CODES_01>) table[3] = {k_exact_refine<NND_CODES_01>, k_exact_refine<NND_CODES_0_5>, k_exact_refine<NND_CODES_BOOL>};
+    return table[fam];
+}
+static auto ex_f64_kernel(int fam, bool masked) -> decltype(&k_exact_f64<NND_CODES_01, false>) {
+    static const decltype(&k_exact_f64<NND_CODES_01, false>) table[3][2] = {{k_exact_f64<NND_CODES_01, false>, k_exact_f64<NND_CODES_01, true>},
+                                                                            {k_exact_f64<NND_CODES_0_5, false>, k_exact_f64<NND_CODES_0_5, true>},
+                                                                            {k_exact_f64<NND_CODES_BOOL, false>, k_exact_f64<NND_CODES_BOOL, true>}};
+    return table[fam][masked];
+}
+
+// `tags` (with `qmasks`): the masked scan; nullptr: the plain one
+template <int DC>
+static int ex_launch_scan(nnd_ctx *ctx, bool wide, dim3 grid, const float *qx, const float *qnrm, const int32_t *qids, int self, int nq, int nq_pad,
                           int W, int64_t rows_per_slice, uint32_t *le, float *ld, float *lth, float *lrej, const uint64_t *tags, const uint64_t *qmasks) {
     const size_t lds = sizeof(float) * ((EX_QB + EX_TB) * DC + EX_TB) + sizeof(int32_t) * EX_QB + sizeof(uint2) * EX_QB * EX_PC +
                        (wide ? sizeof(uint64_t) * 4 * NND_WIDE_SCRATCH_WORDS : 0) + (tags ? sizeof(uint64_t) * EX_TB : 0);
-    if (tags) {  // the masked scan: one kernel template over the three families
-        auto mk = xm ? (wide ? k_exact_scan_masked<DC, NND_CODES_0_5, true> : k_exact_scan_masked<DC, NND_CODES_0_5, false>)
-                     : (wide ? k_exact_scan_masked<DC, NND_CODES_01, true> : k_exact_scan_masked<DC, NND_CODES_01, false>);
-        if (nnd_metric_bool(ctx->p.metric)) mk = wide ? k_exact_scan_masked<DC, NND_CODES_BOOL, true> : k_exact_scan_masked<DC, NND_CODES_BOOL, false>;
-        if (lds > 48 * 1024) NND_HIP_CHECK(hipFuncSetAttribute((const void *)mk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(mk, grid, dim3(256), lds, ctx->stream, ctx->xp, ctx->nrm, ctx->n, ctx->dp, nnd_kmetric(ctx), qx, qnrm, qids, self, nq, nq_pad, W,
-                           rows_per_slice, le, ld, lth, lrej, tags, qmasks);
-        NND_HIP_CHECK(hipGetLastError());
-        return 0;
-    }
-    auto kern = xm ? (wide ? k_exact_scan<DC, true, true> : k_exact_scan<DC, true, false>) : (wide ? k_exact_scan<DC, false, true> : k_exact_scan<DC, false, false>);
-    if (nnd_metric_bool(ctx->p.metric)) kern = wide ? k_exact_scan_bool<DC, true> : k_exact_scan_bool<DC, false>;
+    auto kern = ex_scan_kernel<DC>(ex_family(ctx->p.metric), wide, tags != nullptr);
     if (lds > 48 * 1024) NND_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(kern, grid, dim3(256), lds, ctx->stream, ctx->xp, ctx->nrm, ctx->n, ctx->dp, nnd_kmetric(ctx), qx, qnrm, qids, self, nq, nq_pad, W, rows_per_slice,
-                       le, ld, lth, lrej);
+                       le, ld, lth, lrej, tags, qmasks);
     NND_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -592,7 +572,7 @@ int nnd_exact_knn_impl(nnd_ctx *ctx, const int64_t *rows, const float *q, int64_
     const uint64_t *tags = tg ? tg->tags_dev : nullptr;
     const int64_t n = ctx->n;
     const int d = ctx->d, dp = ctx->dp, metric = ctx->p.metric;
-    const bool self = dev ? dev->q_dev == nullptr : q == nullptr, xm = metric >= 2, bm = nnd_metric_bool(metric), force_f64 = (ctx->p.flags & NND_FLAG_TEST_EXACT_F64) != 0;
+    const bool self = dev ? dev->q_dev == nullptr : q == nullptr, force_f64 = (ctx->p.flags & NND_FLAG_TEST_EXACT_F64) != 0;
     const bool some_rows = dev ? dev->rows_dev != nullptr : rows != nullptr;
     const hipMemcpyKind out_kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     if (n > (int64_t)NND_IDX_MASK) { ctx->set_error("exact search: more than 2^31 - 1 points"); return 1; }
@@ -682,9 +662,9 @@ int nnd_exact_knn_impl(nnd_ctx *ctx, const int64_t *rows, const float *q, int64_
             const dim3 grid((unsigned)(nq_pad / EX_QB), (unsigned)S);
             const int t_scan = t_begin(ctx);
             int rc;
-            if (dp <= 32) rc = ex_launch_scan<32>(ctx, xm, wide, grid, qx, qnrm, qids, self, nq, nq_pad, W, rows_per_slice, le, ld, lth, lrej, tags, qmasks);
-            else if (dp <= 64) rc = ex_launch_scan<64>(ctx, xm, wide, grid, qx, qnrm, qids, self, nq, nq_pad, W, rows_per_slice, le, ld, lth, lrej, tags, qmasks);
-            else rc = ex_launch_scan<128>(ctx, xm, wide, grid, qx, qnrm, qids, self, nq, nq_pad, W, rows_per_slice, le, ld, lth, lrej, tags, qmasks);
+            if (dp <= 32) rc = ex_launch_scan<32>(ctx, wide, grid, qx, qnrm, qids, self, nq, nq_pad, W, rows_per_slice, le, ld, lth, lrej, tags, qmasks);
+            else if (dp <= 64) rc = ex_launch_scan<64>(ctx, wide, grid, qx, qnrm, qids, self, nq, nq_pad, W, rows_per_slice, le, ld, lth, lrej, tags, qmasks);
+            else rc = ex_launch_scan<128>(ctx, wide, grid, qx, qnrm, qids, self, nq, nq_pad, W, rows_per_slice, le, ld, lth, lrej, tags, qmasks);
             if (rc) return 1;
             if (S > 1) {
                 hipLaunchKernelGGL(wide ? k_exact_merge<true> : k_exact_merge<false>, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, ctx->stream, nq, nq_pad, W, S, le, ld, lth, lrej);
@@ -692,7 +672,7 @@ int nnd_exact_knn_impl(nnd_ctx *ctx, const int64_t *rows, const float *q, int64_
             }
             t_end(ctx, t_scan, &s.ms_scan, true);
             const int t_ref = t_begin(ctx);
-            hipLaunchKernelGGL(bm ? k_exact_refine_bool : (xm ? k_exact_refine<true> : k_exact_refine<false>), dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, ctx->stream, ctx->x_orig, d, dp, metric, qraw,
+            hipLaunchKernelGGL(ex_refine_kernel(ex_family(metric)), dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, ctx->stream, ctx->x_orig, d, dp, metric, qraw,
                                qids, qnrm, nq, k, W, le, lrej, nmax, oi, od, unc, n_unc);
             NND_HIP_CHECK(hipGetLastError());
             t_end(ctx, t_ref, &s.ms_refine, true);
@@ -708,12 +688,8 @@ int nnd_exact_knn_impl(nnd_ctx *ctx, const int64_t *rows, const float *q, int64_
         }
         if (n_fallback > 0) {
             const int t_fb = t_begin(ctx);
-            if (tags)
-                hipLaunchKernelGGL(bm ? k_exact_f64_masked<NND_CODES_BOOL> : (xm ? k_exact_f64_masked<NND_CODES_0_5> : k_exact_f64_masked<NND_CODES_01>), dim3((unsigned)n_fallback),
-                                   dim3(256), 0, ctx->stream, ctx->x_orig, n, d, metric, qraw, qids, k, unc, oi, od, tags, qmasks);
-            else
-                hipLaunchKernelGGL(bm ? k_exact_f64_bool : (xm ? k_exact_f64<true> : k_exact_f64<false>), dim3((unsigned)n_fallback), dim3(256), 0, ctx->stream, ctx->x_orig, n, d, metric, qraw, qids,
-                               k, unc, oi, od);
+            hipLaunchKernelGGL(ex_f64_kernel(ex_family(metric), tags != nullptr), dim3((unsigned)n_fallback), dim3(256), 0, ctx->stream, ctx->x_orig, n, d, metric, qraw, qids,
+                               k, unc, oi, od, tags, qmasks);
             NND_HIP_CHECK(hipGetLastError());
             t_end(ctx, t_fb, &s.ms_fallback, true);
         }

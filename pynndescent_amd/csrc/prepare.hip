@@ -1,6 +1,6 @@
 // prepare.hip -- the device glue of NNDescent.prepare() for an index whose rows and graph live on the device (built from a
 // torch tensor): what search_tree.py / nndescent.py do with numpy and scipy on the host path, between kernels that were on the
-// device already (hubtree.hip, prune.hip / searchgraph.hip, query.hip):
+// device already (hubtree.hip, prune.hip / searchgraph.hip, searcher.hip / query.hip):
 //   nnd_rank_order_device    compute_global_degrees (rp_trees.py:714-744) + the (-degree, id) order of make_hub_tree:
 //                            k_prep_degrees -> k_prep_rank_keys -> rocprim::radix_sort_keys -> k_prep_rank_ids
 //   nnd_reorder_csr_device   the search graph in the hub tree's leaf order (pynndescent_.py:1629-1651; scipy's
@@ -9,7 +9,7 @@
 //   nnd_reorder_host         the same and the rows' gather (devarray.hip nnd_launch_gather_rows) on host arrays: the test entry
 // Bytes moved at n points, k neighbours, nnz edges: the rank reads the graph once (4 n k) and sorts n 8-byte keys; the reorder
 // reads and writes the CSR once (8 nnz + 8 n) plus one 4-byte gather per edge through the inverse permutation; the rows' gather
-// (query.hip nnd_searcher_create_device) reads and writes the point set once.  None of the entries has a handle: they take a
+// (searcher.hip nnd_searcher_create_device) reads and writes the point set once.  None of the entries has a handle: they take a
 // device ordinal and a stream, like those of devarray.hip, and return when the stream has drained.
 #include <stdarg.h>
 #include <stdio.h>

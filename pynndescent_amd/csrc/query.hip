@@ -19,28 +19,20 @@
 //     skipped as for cosine; correlation: centred, then normalised; hellinger: sqrt, then normalised; inner product: raw);
 //   * stop rule: the nearest unexpanded frontier vertex is farther than
 //         bound = worst + epsilon * (worst - min_distance)                         (pynndescent_.py:1850-1853).
-//   * quantization="uint8" (Q8 instances, euclidean / cosine / dot): the walk runs on the searcher's uint8 code rows with
+//   * quantization="uint8" (the Q_FORM_U8 instances, euclidean / cosine / dot): the walk runs on the searcher's uint8 code rows with
 //     the reference's proxy distances (q_quad_proxy) and keeps search_k = proxy_beam_size * k results; its epilogue is
 //     the reference's rerank (pynndescent_.py:776-789): exact distances of the RAW query to the float rows of those
 //     candidates, pushed in ascending proxy order into a list of k (DESIGN.md "Quantized search").
-//   * metric="proxy_inner_product" (RR instances without Q8, code 6): the walk runs on the float rows with the proxy
+//   * metric="proxy_inner_product" (the Q_FORM_RERANK instances, code 6): the walk runs on the float rows with the proxy
 //     -log2(cos) + 1 / sqrt<q,x> and keeps search_k results; the same epilogue reranks them by -<q,x> (DESIGN.md "Proxy
 //     distances").
 // Random choices (ties in the tree descent, random start vertices when the tree leaf holds fewer than
 // min(k, n_neighbors) points) come from the counter hash, keyed by the query's number.
-#include <stdarg.h>
-#include <stdio.h>
-#include <string.h>
-
+// The searcher itself (searcher.h) is created, filled and quantized in searcher.hip; its allow set and tag words are made in
+// searcher_filter.hip.  Here: the walk (k_query), its table and launch (searcher_run) and the query entries.
 #include <vector>
 
-#include "common.h"
-#include "metric.h"
-#include "devmem.h"
-#include "../../include/pynnd_amd.h"
-
-// devarray.hip: rows of NND_DTYPE_* `dtype` gathered by `order` (nullptr: identity) into float32 rows of dp floats, zero padded
-int nnd_launch_gather_rows(hipStream_t st, const void *src, int dtype, const int32_t *order, int64_t n, int d, int dp, float *dst);
+#include "searcher.h"
 
 #define Q_FRONTIER 512   // frontier entries per query (LDS tier)
 #define Q_VISITED 4096   // visited-set slots per query (power of two; LDS tier)
@@ -54,41 +46,6 @@ int nnd_launch_gather_rows(hipStream_t st, const void *src, int dtype, const int
 // of Q_BIG_FRONTIER entries in HBM -- so no result ever comes from a search the reference would have continued.
 #define Q_CHUNK 64       // candidates handled per step
 #define Q_EMPTY 0xFFFFFFFFu
-
-struct nnd_searcher_s {
-    int device = 0;
-    int64_t n = 0, nnz = 0, n_nodes = 0;
-    int d = 0, dp = 0, metric = 0, n_neighbors = 0;
-    float min_distance = 0.0f;
-    uint32_t seed = 0;
-    float *x = nullptr;        // (n, dp) rows padded to a multiple of 4 floats
-    float *xn2 = nullptr;      // (n) squared norms (cosine; the prepared rows' for the codes 2..5)
-    uint8_t *codes = nullptr;  // quantization="uint8": (n, dcs) codes, rows padded to 16 bytes with code 0
-    float *cn2 = nullptr;      // (n) sum of LUT[c]^2 over a code row (cosine / dot)
-    float *lut = nullptr;      // 512: the walk's codebook (256, padded with the last value), then the search table (+inf padded)
-    int dcs = 0;               // code row stride: d rounded up to 16
-    float tab_host[512];       // the host side of `lut` (the source of its stream-ordered upload)
-    int32_t *indptr = nullptr, *indices = nullptr;
-    float *hyper = nullptr, *offsets = nullptr;  // (n_nodes, dp), (n_nodes)
-    int32_t *children = nullptr, *tree_idx = nullptr;
-    hipStream_t stream = nullptr;
-    int64_t last_spilled = 0;  // queries of the last call that ran on the global-memory tier
-    bool force_big = false;    // nnd_searcher_set_tier(1): every query on the global-memory tier (tests)
-    uint32_t *allow = nullptr;            // the filter's bitset over the searcher's numbering, (n + 31) / 32 words (allocated on first use)
-    unsigned long long *fstat = nullptr;  // 2: allowed rows of the last filter, its out-of-range flag
-    bool filter_on = false;               // nnd_searcher_set_filter*: the query entries run the filtered instances
-    uint64_t *tags = nullptr;             // nnd_searcher_set_tags*: (n) tag words in the searcher's numbering (the tagged query entries)
-    nnd_devmem mem;            // owner of the device buffers above (devmem.h)
-    char err[512] = {0};
-    void set_error(const char *fmt, ...) {
-        va_list ap;
-        va_start(ap, fmt);
-        vsnprintf(err, sizeof(err), fmt, ap);
-        va_end(ap);
-    }
-};
-
-static thread_local char g_serr[512] = {0};
 
 // sum over the four lanes of a quad, in every one of them (two DPP quad permutes)
 __device__ __forceinline__ float q_quad_sum(float acc) {
@@ -180,23 +137,32 @@ __device__ __forceinline__ float q_rerank_dist(const float *__restrict__ x, cons
     return acc > 0.0f ? -log2f(acc) : NND_FLT_MAX;
 }
 
+// the forms of the walk, and what may enter its result list
+enum q_form { Q_FORM_FLOAT, Q_FORM_U8, Q_FORM_RERANK, Q_FORM_BOOL };
+enum q_filt { Q_FILT_NONE, Q_FILT_ALLOW, Q_FILT_TAGS };
+
 // KU: result entries per lane -- entry u of lane j is position 64 u + j of the list (k <= 64 KU: 1, 2 or 4)
-// Q8: quantization="uint8" -- the walk on the code rows (k = search_k), the rerank to k_out in the epilogue; the codebook
-// (256 floats) sits in front of the waves' LDS.  The float instances (Q8 = false) never touch the codes, the codebook and cn2.
-// RR: the rerank epilogue (k = search_k, the k_out best by the true distance leave).  Three forms: the float walk without it,
-// the uint8 walk with it, and the float walk with it (Q8 = false, RR = true: metric code 6 and nothing else -- the walk on the
-// float rows by the proxy inner product, the rerank by -<q,x>; the query stays as given, a zero query is searched).
-// BM: the boolean family (codes 8..16, the instances of k_query_bool): the tree is descended with the query as given, then the
-// query becomes its indicator row and the walk's distances are metric.h nnd_bool_dist on exact counts.
-// FL: filtered (the instances of k_query_filtered / k_query_bool_filtered): a vertex enters the walk's result list only if its
-// bit in `allow` (a bitset over the searcher's numbering) is set.  It is still visited, pushed to the frontier and expanded, so
-// the bound, the stop rule and the hand-over to the big tier are those of the unfiltered walk relative to the allowed rows; the
-// rerank's candidates are the walk's results and so all allowed.  The other instances never read `allow`.
-// TG: tagged (the instances of k_query_tagged / k_query_bool_tagged): the same rule with a predicate per query -- the vertex's tag
-// word (`tags`, the searcher's numbering) must meet the query's mask word (`qmasks`, one per query of the call, read once into
-// scalar registers: one wave serves one query).  A query whose mask is 0 has no allowed row and does not walk.
-// The body is shared by the kernels k_query (BM = false) and k_query_bool below.
-template <bool BIG, int KU, bool Q8, bool RR, bool BM, bool FL = false, bool TG = false>
+// FORM, a q_form:
+//   Q_FORM_FLOAT   the walk on the float rows, k results.  Never touches the codes, the codebook and cn2.
+//   Q_FORM_U8      quantization="uint8" (Q8, RR below) -- the walk on the code rows (k = search_k), then the rerank epilogue: the
+//                  k_out best by the true distance leave.  The codebook (256 floats) sits in front of the waves' LDS.
+//   Q_FORM_RERANK  the float walk with the rerank epilogue (RR without Q8: metric code 6 and nothing else) -- the walk on the float
+//                  rows by the proxy inner product, the rerank by -<q,x>; the query stays as given, a zero query is searched.
+//   Q_FORM_BOOL    the boolean family (BM, codes 8..16): the tree is descended with the query as given, then the query becomes its
+//                  indicator row and the walk's distances are metric.h nnd_bool_dist on exact counts.
+// FILT, a q_filt:
+//   Q_FILT_NONE    every vertex may enter the result list; `allow`, `tags` and `qmasks` are never read.
+//   Q_FILT_ALLOW   filtered (FL): a vertex enters the walk's result list only if its bit in `allow` (a bitset over the searcher's
+//                  numbering, (n + 31) / 32 words) is set.  It is still visited, pushed to the frontier and expanded, so the bound,
+//                  the stop rule and the hand-over to the big tier are those of the unfiltered walk relative to the allowed rows;
+//                  the rerank's candidates are the walk's results and so all allowed.
+//   Q_FILT_TAGS    tagged (TG): the same rule with a predicate per query -- the vertex's tag word (`tags`, (n), the searcher's
+//                  numbering) must meet the query's mask word (`qmasks`, one per query of the call, read once into scalar
+//                  registers: one wave serves one query).  A query whose mask is 0 has no allowed row and does not walk.
+// The body of k_query below; it stays an inlined function of its own because every instance compiles to other code when the
+// body stands in the kernel itself (KU 1: mostly the same instructions in another order; KU 2 and 4: up to 17 instructions more
+// or fewer; profiles/search_fold_isa.txt).
+template <bool BIG, int KU, int FORM, int FILT>
 __device__ __forceinline__ void q_body(const float *__restrict__ x, const float *__restrict__ xn2, int dp, int d, int metric,
                                                int64_t n, const int32_t *__restrict__ indptr, const int32_t *__restrict__ indices,
                                                const float *__restrict__ hyper, const float *__restrict__ offsets,
@@ -208,8 +174,9 @@ __device__ __forceinline__ void q_body(const float *__restrict__ x, const float 
                                                int n_list, unsigned char *__restrict__ scratch, size_t scratch_stride,
                                                const uint8_t *__restrict__ codes, int dcs, const float *__restrict__ lut,
                                                const float *__restrict__ cn2, int k_out,
-                                               const uint32_t *__restrict__ allow = nullptr,
-                                               const uint64_t *__restrict__ tags = nullptr, const uint64_t *__restrict__ qmasks = nullptr) {
+                                               const uint32_t *__restrict__ allow, const uint64_t *__restrict__ tags, const uint64_t *__restrict__ qmasks) {
+    constexpr bool Q8 = FORM == Q_FORM_U8, RR = FORM == Q_FORM_U8 || FORM == Q_FORM_RERANK, BM = FORM == Q_FORM_BOOL;
+    constexpr bool FL = FILT == Q_FILT_ALLOW, TG = FILT == Q_FILT_TAGS;
     extern __shared__ __attribute__((aligned(16))) unsigned char qsm[];
     const int lane = nnd_lane(), w = threadIdx.x >> 6;
     if constexpr (Q8) {  // the codebook, once per workgroup (256 threads: one entry each)
@@ -587,7 +554,8 @@ __device__ __forceinline__ void q_body(const float *__restrict__ x, const float 
             out_dist[qi * k + 64 * u + lane] = rd[u];
         }
 }
-template <bool BIG, int KU, bool Q8 = false, bool RR = Q8>
+// every instance of the walk: 2 tiers x 3 KU x 4 forms x 3 filters, one signature
+template <bool BIG, int KU, int FORM, int FILT>
 __global__ __launch_bounds__(256) void k_query(const float *__restrict__ x, const float *__restrict__ xn2, int dp, int d, int metric,
                                                int64_t n, const int32_t *__restrict__ indptr, const int32_t *__restrict__ indices,
                                                const float *__restrict__ hyper, const float *__restrict__ offsets,
@@ -598,457 +566,46 @@ __global__ __launch_bounds__(256) void k_query(const float *__restrict__ x, cons
                                                const int32_t *__restrict__ qlist /* BIG: the queries of this batch */,
                                                int n_list, unsigned char *__restrict__ scratch, size_t scratch_stride,
                                                const uint8_t *__restrict__ codes, int dcs, const float *__restrict__ lut,
-                                               const float *__restrict__ cn2, int k_out) {
-    q_body<BIG, KU, Q8, RR, false>(x, xn2, dp, d, metric, n, indptr, indices, hyper, offsets, children, tree_idx, n_nodes, queries, nq, k, epsilon, min_distance,
-                               n_neighbors, seed, out_idx, out_dist, overflow, qlist, n_list, scratch, scratch_stride, codes, dcs, lut, cn2, k_out);
-}
-template <bool BIG, int KU>
-__global__ __launch_bounds__(256) void k_query_bool(const float *__restrict__ x, const float *__restrict__ xn2, int dp, int d, int metric,
-                                               int64_t n, const int32_t *__restrict__ indptr, const int32_t *__restrict__ indices,
-                                               const float *__restrict__ hyper, const float *__restrict__ offsets,
-                                               const int32_t *__restrict__ children, const int32_t *__restrict__ tree_idx,
-                                               int64_t n_nodes, const float *__restrict__ queries, int64_t nq, int k, float epsilon,
-                                               float min_distance, int n_neighbors, uint32_t seed, int32_t *__restrict__ out_idx,
-                                               float *__restrict__ out_dist, uint8_t *__restrict__ overflow /* (nq) LDS tier: set when the query needs the big tier */,
-                                               const int32_t *__restrict__ qlist /* BIG: the queries of this batch */,
-                                               int n_list, unsigned char *__restrict__ scratch, size_t scratch_stride,
-                                               const uint8_t *__restrict__ codes, int dcs, const float *__restrict__ lut,
-                                               const float *__restrict__ cn2, int k_out) {
-    q_body<BIG, KU, false, false, true>(x, xn2, dp, d, metric, n, indptr, indices, hyper, offsets, children, tree_idx, n_nodes, queries, nq, k, epsilon, min_distance,
-                               n_neighbors, seed, out_idx, out_dist, overflow, qlist, n_list, scratch, scratch_stride, codes, dcs, lut, cn2, k_out);
-}
-// the filtered siblings (FL): the same arguments and `allow`
-template <bool BIG, int KU, bool Q8 = false, bool RR = Q8>
-__global__ __launch_bounds__(256) void k_query_filtered(const float *__restrict__ x, const float *__restrict__ xn2, int dp, int d, int metric,
-                                               int64_t n, const int32_t *__restrict__ indptr, const int32_t *__restrict__ indices,
-                                               const float *__restrict__ hyper, const float *__restrict__ offsets,
-                                               const int32_t *__restrict__ children, const int32_t *__restrict__ tree_idx,
-                                               int64_t n_nodes, const float *__restrict__ queries, int64_t nq, int k, float epsilon,
-                                               float min_distance, int n_neighbors, uint32_t seed, int32_t *__restrict__ out_idx,
-                                               float *__restrict__ out_dist, uint8_t *__restrict__ overflow /* (nq) LDS tier: set when the query needs the big tier */,
-                                               const int32_t *__restrict__ qlist /* BIG: the queries of this batch */,
-                                               int n_list, unsigned char *__restrict__ scratch, size_t scratch_stride,
-                                               const uint8_t *__restrict__ codes, int dcs, const float *__restrict__ lut,
                                                const float *__restrict__ cn2, int k_out,
-                                               const uint32_t *__restrict__ allow /* (n + 31) / 32 words */) {
-    q_body<BIG, KU, Q8, RR, false, true>(x, xn2, dp, d, metric, n, indptr, indices, hyper, offsets, children, tree_idx, n_nodes, queries, nq, k, epsilon, min_distance,
-                               n_neighbors, seed, out_idx, out_dist, overflow, qlist, n_list, scratch, scratch_stride, codes, dcs, lut, cn2, k_out, allow);
+                                               const uint32_t *__restrict__ allow /* Q_FILT_ALLOW */, const uint64_t *__restrict__ tags /* Q_FILT_TAGS */,
+                                               const uint64_t *__restrict__ qmasks /* Q_FILT_TAGS: (nq) */) {
+    q_body<BIG, KU, FORM, FILT>(x, xn2, dp, d, metric, n, indptr, indices, hyper, offsets, children, tree_idx, n_nodes, queries, nq, k, epsilon, min_distance,
+                                n_neighbors, seed, out_idx, out_dist, overflow, qlist, n_list, scratch, scratch_stride, codes, dcs, lut, cn2, k_out, allow, tags, qmasks);
 }
-template <bool BIG, int KU>
-__global__ __launch_bounds__(256) void k_query_bool_filtered(const float *__restrict__ x, const float *__restrict__ xn2, int dp, int d, int metric,
-                                               int64_t n, const int32_t *__restrict__ indptr, const int32_t *__restrict__ indices,
-                                               const float *__restrict__ hyper, const float *__restrict__ offsets,
-                                               const int32_t *__restrict__ children, const int32_t *__restrict__ tree_idx,
-                                               int64_t n_nodes, const float *__restrict__ queries, int64_t nq, int k, float epsilon,
-                                               float min_distance, int n_neighbors, uint32_t seed, int32_t *__restrict__ out_idx,
-                                               float *__restrict__ out_dist, uint8_t *__restrict__ overflow /* (nq) LDS tier: set when the query needs the big tier */,
-                                               const int32_t *__restrict__ qlist /* BIG: the queries of this batch */,
-                                               int n_list, unsigned char *__restrict__ scratch, size_t scratch_stride,
-                                               const uint8_t *__restrict__ codes, int dcs, const float *__restrict__ lut,
-                                               const float *__restrict__ cn2, int k_out,
-                                               const uint32_t *__restrict__ allow /* (n + 31) / 32 words */) {
-    q_body<BIG, KU, false, false, true, true>(x, xn2, dp, d, metric, n, indptr, indices, hyper, offsets, children, tree_idx, n_nodes, queries, nq, k, epsilon, min_distance,
-                               n_neighbors, seed, out_idx, out_dist, overflow, qlist, n_list, scratch, scratch_stride, codes, dcs, lut, cn2, k_out, allow);
+using q_kernel = decltype(&k_query<false, 1, Q_FORM_FLOAT, Q_FILT_NONE>);
+// (k > 64: the result list as two or four entries per lane; the reference takes any k, pynndescent_.py:2275-2379)
+static q_kernel query_kernel(bool big, q_form form, q_filt filt, int k) {
+#define Q_KU(BIG, FORM, FILT) {k_query<BIG, 1, FORM, FILT>, k_query<BIG, 2, FORM, FILT>, k_query<BIG, 4, FORM, FILT>}
+#define Q_FILTS(BIG, FORM) {Q_KU(BIG, FORM, Q_FILT_NONE), Q_KU(BIG, FORM, Q_FILT_ALLOW), Q_KU(BIG, FORM, Q_FILT_TAGS)}
+#define Q_FORMS(BIG) {Q_FILTS(BIG, Q_FORM_FLOAT), Q_FILTS(BIG, Q_FORM_U8), Q_FILTS(BIG, Q_FORM_RERANK), Q_FILTS(BIG, Q_FORM_BOOL)}
+    static const q_kernel table[2][4][3][3] = {Q_FORMS(false), Q_FORMS(true)};
+#undef Q_FORMS
+#undef Q_FILTS
+#undef Q_KU
+    return table[big][form][filt][k > 128 ? 2 : k > 64 ? 1 : 0];
 }
 
-// the tagged siblings (TG): the same arguments, the tag words and the queries' mask words
-template <bool BIG, int KU, bool Q8 = false, bool RR = Q8>
-__global__ __launch_bounds__(256) void k_query_tagged(const float *__restrict__ x, const float *__restrict__ xn2, int dp, int d, int metric,
-                                               int64_t n, const int32_t *__restrict__ indptr, const int32_t *__restrict__ indices,
-                                               const float *__restrict__ hyper, const float *__restrict__ offsets,
-                                               const int32_t *__restrict__ children, const int32_t *__restrict__ tree_idx,
-                                               int64_t n_nodes, const float *__restrict__ queries, int64_t nq, int k, float epsilon,
-                                               float min_distance, int n_neighbors, uint32_t seed, int32_t *__restrict__ out_idx,
-                                               float *__restrict__ out_dist, uint8_t *__restrict__ overflow /* (nq) LDS tier: set when the query needs the big tier */,
-                                               const int32_t *__restrict__ qlist /* BIG: the queries of this batch */,
-                                               int n_list, unsigned char *__restrict__ scratch, size_t scratch_stride,
-                                               const uint8_t *__restrict__ codes, int dcs, const float *__restrict__ lut,
-                                               const float *__restrict__ cn2, int k_out,
-                                               const uint64_t *__restrict__ tags /* (n) */, const uint64_t *__restrict__ qmasks /* (nq) */) {
-    q_body<BIG, KU, Q8, RR, false, false, true>(x, xn2, dp, d, metric, n, indptr, indices, hyper, offsets, children, tree_idx, n_nodes, queries, nq, k, epsilon, min_distance,
-                               n_neighbors, seed, out_idx, out_dist, overflow, qlist, n_list, scratch, scratch_stride, codes, dcs, lut, cn2, k_out, nullptr, tags, qmasks);
-}
-template <bool BIG, int KU>
-__global__ __launch_bounds__(256) void k_query_bool_tagged(const float *__restrict__ x, const float *__restrict__ xn2, int dp, int d, int metric,
-                                               int64_t n, const int32_t *__restrict__ indptr, const int32_t *__restrict__ indices,
-                                               const float *__restrict__ hyper, const float *__restrict__ offsets,
-                                               const int32_t *__restrict__ children, const int32_t *__restrict__ tree_idx,
-                                               int64_t n_nodes, const float *__restrict__ queries, int64_t nq, int k, float epsilon,
-                                               float min_distance, int n_neighbors, uint32_t seed, int32_t *__restrict__ out_idx,
-                                               float *__restrict__ out_dist, uint8_t *__restrict__ overflow /* (nq) LDS tier: set when the query needs the big tier */,
-                                               const int32_t *__restrict__ qlist /* BIG: the queries of this batch */,
-                                               int n_list, unsigned char *__restrict__ scratch, size_t scratch_stride,
-                                               const uint8_t *__restrict__ codes, int dcs, const float *__restrict__ lut,
-                                               const float *__restrict__ cn2, int k_out,
-                                               const uint64_t *__restrict__ tags /* (n) */, const uint64_t *__restrict__ qmasks /* (nq) */) {
-    q_body<BIG, KU, false, false, true, false, true>(x, xn2, dp, d, metric, n, indptr, indices, hyper, offsets, children, tree_idx, n_nodes, queries, nq, k, epsilon, min_distance,
-                               n_neighbors, seed, out_idx, out_dist, overflow, qlist, n_list, scratch, scratch_stride, codes, dcs, lut, cn2, k_out, nullptr, tags, qmasks);
-}
-
-
-// the searcher's copy of the rows for the codes 2..5: the build's row transform (metric.h), one wave per row, in place --
-// dot: L2-normalised; correlation: minus the row mean (float64), then normalised; hellinger: sqrt, then normalised
-__global__ void k_searcher_prep_rows(float *__restrict__ x, int64_t n, int d, int dp, int metric) {
-    const int lane = nnd_lane();
-    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= n) return;
-    float *row = x + r * dp;
-    const double mu = metric == 4 ? nnd_row_mean_f64<64>(row, d, lane) : 0.0;
-    float s = 0.0f;
-    for (int j = lane; j < d; j += 64) {
-        const float v = nnd_unit_transform(metric, row[j], mu);
-        row[j] = v;
-        s += v * v;
-    }
-    s = nnd_wave_sum_f32(s);
-    const float inv = s > 0.0f ? 1.0f / sqrtf(s) : 0.0f;
-    for (int j = lane; j < d; j += 64) row[j] *= inv;
-}
-
-// the boolean family: the searcher's rows become indicator rows in place (x != 0 -> 1, else 0; the padding stays 0), so that
-// k_row_norm2 gives nnz(x) and every product of the walk is a count
-__global__ void k_searcher_indicator_rows(float *__restrict__ x, int64_t n, int dp) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n * dp) x[i] = x[i] != 0.0f ? 1.0f : 0.0f;
-}
-static void searcher_indicator_rows(nnd_searcher_s *s, hipStream_t st) {
-    const int64_t total = s->n * s->dp;
-    hipLaunchKernelGGL(k_searcher_indicator_rows, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, s->x, s->n, s->dp);
-}
-
-// squared norms of the padded rows (alternative_cosine recomputes them per call, distances.py:617-620)
-__global__ void k_row_norm2(const float *__restrict__ x, int64_t n, int dp, float *__restrict__ out) {
-    const int lane = nnd_lane();
-    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= n) return;
-    float s = 0.0f;
-    for (int j = lane; j < dp; j += 64) {
-        const float v = x[r * dp + j];
-        s += v * v;
-    }
-    s = nnd_wave_sum_f32(s);
-    if (lane == 0) out[r] = s;
-}
-
-// uint8 codes of the searcher's rows (pynndescent_.py:2207-2209: np.searchsorted(values, raw).astype(np.uint8)): one wave
-// per row, one element per lane.  The search is a branchless searchsorted-left over the 256-entry table `tab` (the codebook,
-// +inf past its n_values entries): a value above the last entry gets n_values, and 256 wraps to code 0 through the uint8
-// cast, bit for bit as the reference.  Code rows have stride dcs, padding bytes 0.  cn2 (cosine / dot; may be null): the
-// row's sum of lut[c]^2 with the walk's table.  x == nullptr: the codes are already in place, only cn2 is computed.
-__global__ __launch_bounds__(256) void k_quantize_u8(const float *__restrict__ x, int64_t xstride, int64_t n, int d, int dcs,
-                                                     const float *__restrict__ lut, const float *__restrict__ tab,
-                                                     uint8_t *__restrict__ codes, float *__restrict__ cn2) {
-    __shared__ float st[256], lt[256];
-    st[threadIdx.x] = tab[threadIdx.x];
-    lt[threadIdx.x] = lut[threadIdx.x];
-    __syncthreads();
-    const int lane = nnd_lane();
-    for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < n; r += (int64_t)gridDim.x * 4) {  // wave-uniform
-        float s = 0.0f;
-        for (int j = lane; j < dcs; j += 64) {
-            uint32_t c = 0;
-            if (x) {
-                if (j < d) {
-                    const float v = x[r * xstride + j];
-                    int lo = 0;
-#pragma unroll
-                    for (int h = 128; h > 0; h >>= 1) lo += st[lo + h - 1] < v ? h : 0;
-                    lo += st[lo] < v ? 1 : 0;  // 0 .. 256
-                    c = (uint32_t)lo & 0xFFu;
-                }
-                codes[r * dcs + j] = (uint8_t)c;
-            } else {
-                c = codes[r * dcs + j];
-            }
-            if (j < d) s += lt[c] * lt[c];
-        }
-        if (cn2) {
-            s = nnd_wave_sum_f32(s);
-            if (lane == 0) cn2[r] = s;
-        }
-    }
-}
-
-// ---- the filter's allow set (nnd_searcher_set_filter*) ----
-// an id list (original numbering) marked into a byte mask; an id outside 0 .. n - 1 raises the flag and is never written
-__global__ void k_filter_mark_ids(const int64_t *__restrict__ ids, int64_t m, int64_t n, uint8_t *__restrict__ mask,
-                                  unsigned long long *__restrict__ fstat) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= m) return;
-    const int64_t id = ids[i];
-    if (id < 0 || id >= n) {
-        atomicOr(&fstat[1], 1ull);
-        return;
-    }
-    mask[id] = 1;
-}
-// the bitset over the searcher's numbering: bit i = mask[order[i]] != 0 (order nullptr: the identity), 64 rows of a wave packed by
-// one ballot into two words; fstat[0] counts the allowed rows.  A wave's first row is a multiple of 64, so no two waves share a word.
-__global__ __launch_bounds__(256) void k_filter_bitset(const uint8_t *__restrict__ mask, const int32_t *__restrict__ order, int64_t n,
-                                                       uint32_t *__restrict__ bits, unsigned long long *__restrict__ fstat) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    bool on = false;
-    if (i < n) {
-        const int64_t r = order ? (int64_t)order[i] : i;
-        on = r >= 0 && r < n && mask[r] != 0;
-    }
-    const unsigned long long m = __ballot(on);
-    if (nnd_lane() == 0 && i < n) {
-        bits[i >> 5] = (uint32_t)m;
-        if (i + 32 < n) bits[(i >> 5) + 1] = (uint32_t)(m >> 32);
-        if (m) atomicAdd(&fstat[0], (unsigned long long)__popcll(m));
-    }
-}
-
-// ---- per-query filters: the rows' tag words (nnd_searcher_set_tags*) ----
-// the tag words in the searcher's numbering: out[i] = tags[order[i]] (order nullptr: the identity); the sibling of k_filter_bitset
-__global__ __launch_bounds__(256) void k_tags_gather(const uint64_t *__restrict__ tags, const int32_t *__restrict__ order, int64_t n,
-                                                     uint64_t *__restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const int64_t r = order ? (int64_t)order[i] : i;
-    out[i] = r >= 0 && r < n ? tags[r] : 0ull;
-}
-// counts[u] += rows whose tag word meets masks[u], u < n_masks: one pass over the tag words.  A workgroup keeps Q_COUNT_ROWS rows
-// per thread in registers and takes the masks (wave-uniform loads) in groups of Q_COUNT_MASKS: a wave reduction per mask, the four
-// waves' sums meet in LDS, and one global atomic per workgroup and mask adds what is not zero.
-#define Q_COUNT_ROWS 8
-#define Q_COUNT_MASKS 1024
-__global__ __launch_bounds__(256) void k_tags_count(const uint64_t *__restrict__ tags, int64_t n, const uint64_t *__restrict__ masks, int n_masks,
-                                                    unsigned long long *__restrict__ counts) {
-    __shared__ int part[Q_COUNT_MASKS];
-    const int lane = nnd_lane();
-    uint64_t t[Q_COUNT_ROWS];
-    const int64_t base = (int64_t)blockIdx.x * (256 * Q_COUNT_ROWS) + threadIdx.x;
-#pragma unroll
-    for (int j = 0; j < Q_COUNT_ROWS; j++) {
-        const int64_t i = base + 256 * j;
-        t[j] = i < n ? tags[i] : 0ull;
-    }
-    for (int u0 = 0; u0 < n_masks; u0 += Q_COUNT_MASKS) {
-        const int nu = n_masks - u0 < Q_COUNT_MASKS ? n_masks - u0 : Q_COUNT_MASKS;
-        for (int u = threadIdx.x; u < nu; u += 256) part[u] = 0;
-        __syncthreads();
-        for (int u = 0; u < nu; u++) {
-            const uint64_t m = masks[u0 + u];
-            int c = 0;
-#pragma unroll
-            for (int j = 0; j < Q_COUNT_ROWS; j++) c += (t[j] & m) != 0ull ? 1 : 0;
-            c = nnd_wave_sum_i32(c);
-            if (lane == 0 && c) atomicAdd(&part[u], c);
-        }
-        __syncthreads();
-        for (int u = threadIdx.x; u < nu; u += 256)
-            if (part[u]) atomicAdd(&counts[u0 + u], (unsigned long long)part[u]);
-        __syncthreads();
-    }
-}
-
-#define S_HIP(expr)                                                                                 \
-    do {                                                                                            \
-        hipError_t _e = (expr);                                                                     \
-        if (_e != hipSuccess) {                                                                     \
-            s->set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__);  \
-            return 1;                                                                               \
-        }                                                                                           \
-    } while (0)
-#define S_ALLOC(p, count)                                                                      \
-    do {                                                                                       \
-        if (!s->mem.alloc(p, count)) {                                                         \
-            s->set_error("out of device memory: %s, %zu elements (%s:%d)", #p, (size_t)(count), __FILE__, __LINE__); \
-            return 1;                                                                          \
-        }                                                                                      \
-    } while (0)
-
-static int upload_padded(nnd_searcher_s *s, float **dst, const float *src, int64_t rows, int d, int dp) {
-    S_ALLOC(dst, (size_t)(rows ? rows : 1) * dp);
-    if (rows == 0) return 0;
-    if (d == dp) {
-        S_HIP(hipMemcpy(*dst, src, sizeof(float) * (size_t)rows * d, hipMemcpyHostToDevice));
-    } else {
-        S_HIP(hipMemset(*dst, 0, sizeof(float) * (size_t)rows * dp));
-        S_HIP(hipMemcpy2D(*dst, sizeof(float) * dp, src, sizeof(float) * d, sizeof(float) * d, (size_t)rows, hipMemcpyHostToDevice));
-    }
-    return 0;
-}
-
-extern "C" const char *nnd_searcher_last_error(nnd_searcher_t s) { return s ? s->err : g_serr; }
-
-extern "C" int32_t nnd_searcher_destroy(nnd_searcher_t s) {
-    if (!s) return 0;
-    (void)hipSetDevice(s->device);
-    if (s->stream) (void)hipStreamSynchronize(s->stream);
-    s->mem.release_all();
-    if (s->stream) (void)hipStreamDestroy(s->stream);
-    delete s;
-    return 0;
-}
-
-static int searcher_fill(nnd_searcher_s *s, const float *data, const int32_t *indptr, const int32_t *indices, const float *hyperplanes,
-                         const float *offsets, const int32_t *children, const int32_t *tree_indices) {
-    S_HIP(hipSetDevice(s->device));
-    S_HIP(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-    if (upload_padded(s, &s->x, data, s->n, s->d, s->dp)) return 1;
-    S_ALLOC(&s->xn2, (size_t)s->n);
-    if (s->metric == NND_METRIC_ALT_DOT || s->metric == NND_METRIC_CORRELATION || s->metric == NND_METRIC_ALT_HELLINGER)
-        hipLaunchKernelGGL(k_searcher_prep_rows, dim3((unsigned)((s->n + 3) / 4)), dim3(256), 0, s->stream, s->x, s->n, s->d, s->dp, s->metric);
-    if (nnd_metric_bool(s->metric)) searcher_indicator_rows(s, s->stream);
-    hipLaunchKernelGGL(k_row_norm2, dim3((unsigned)((s->n + 3) / 4)), dim3(256), 0, s->stream, s->x, s->n, s->dp, s->xn2);
-    S_ALLOC(&s->indptr, (size_t)(s->n + 1));
-    S_HIP(hipMemcpy(s->indptr, indptr, sizeof(int32_t) * (size_t)(s->n + 1), hipMemcpyHostToDevice));
-    S_ALLOC(&s->indices, (size_t)s->nnz);
-    S_HIP(hipMemcpy(s->indices, indices, sizeof(int32_t) * (size_t)s->nnz, hipMemcpyHostToDevice));
-    if (s->n_nodes > 0) {
-        if (upload_padded(s, &s->hyper, hyperplanes, s->n_nodes, s->d, s->dp)) return 1;
-        S_ALLOC(&s->offsets, (size_t)s->n_nodes);
-        S_HIP(hipMemcpy(s->offsets, offsets, sizeof(float) * (size_t)s->n_nodes, hipMemcpyHostToDevice));
-        S_ALLOC(&s->children, 2 * (size_t)s->n_nodes);
-        S_HIP(hipMemcpy(s->children, children, sizeof(int32_t) * 2 * (size_t)s->n_nodes, hipMemcpyHostToDevice));
-        S_ALLOC(&s->tree_idx, (size_t)s->n);
-        S_HIP(hipMemcpy(s->tree_idx, tree_indices, sizeof(int32_t) * (size_t)s->n, hipMemcpyHostToDevice));
-    }
-    S_HIP(hipStreamSynchronize(s->stream));
-    return 0;
-}
-
-// the same state from device memory, on the caller's stream: rows gathered by `order` straight into the padded layout
-// (devarray.hip), the CSR copied device to device; the tree tables come from the host as above
-static int searcher_fill_device(nnd_searcher_s *s, const void *rows, int dtype, const int32_t *order, const int32_t *indptr, const int32_t *indices,
-                                const float *hyperplanes, const float *offsets, const int32_t *children, const int32_t *tree_indices, hipStream_t st) {
-    S_HIP(hipSetDevice(s->device));
-    S_HIP(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-    S_ALLOC(&s->x, (size_t)s->n * s->dp);
-    S_ALLOC(&s->xn2, (size_t)s->n);
-    S_ALLOC(&s->indptr, (size_t)(s->n + 1));
-    S_ALLOC(&s->indices, (size_t)s->nnz);
-    if (nnd_launch_gather_rows(st, rows, dtype, order, s->n, s->d, s->dp, s->x)) {
-        (void)hipGetLastError();
-        s->set_error("the rows' gather could not be launched (dtype %d)", dtype);
-        return 1;
-    }
-    if (s->metric == NND_METRIC_ALT_DOT || s->metric == NND_METRIC_CORRELATION || s->metric == NND_METRIC_ALT_HELLINGER)
-        hipLaunchKernelGGL(k_searcher_prep_rows, dim3((unsigned)((s->n + 3) / 4)), dim3(256), 0, st, s->x, s->n, s->d, s->dp, s->metric);
-    if (nnd_metric_bool(s->metric)) searcher_indicator_rows(s, st);
-    hipLaunchKernelGGL(k_row_norm2, dim3((unsigned)((s->n + 3) / 4)), dim3(256), 0, st, s->x, s->n, s->dp, s->xn2);
-    S_HIP(hipGetLastError());
-    S_HIP(hipMemcpyAsync(s->indptr, indptr, sizeof(int32_t) * (size_t)(s->n + 1), hipMemcpyDeviceToDevice, st));
-    if (s->nnz > 0) S_HIP(hipMemcpyAsync(s->indices, indices, sizeof(int32_t) * (size_t)s->nnz, hipMemcpyDeviceToDevice, st));
-    if (s->n_nodes > 0) {
-        if (upload_padded(s, &s->hyper, hyperplanes, s->n_nodes, s->d, s->dp)) return 1;
-        S_ALLOC(&s->offsets, (size_t)s->n_nodes);
-        S_HIP(hipMemcpy(s->offsets, offsets, sizeof(float) * (size_t)s->n_nodes, hipMemcpyHostToDevice));
-        S_ALLOC(&s->children, 2 * (size_t)s->n_nodes);
-        S_HIP(hipMemcpy(s->children, children, sizeof(int32_t) * 2 * (size_t)s->n_nodes, hipMemcpyHostToDevice));
-        S_ALLOC(&s->tree_idx, (size_t)s->n);
-        S_HIP(hipMemcpy(s->tree_idx, tree_indices, sizeof(int32_t) * (size_t)s->n, hipMemcpyHostToDevice));
-    }
-    S_HIP(hipStreamSynchronize(st));  // the caller's buffers are free again, and the searcher's own stream may read what was written
-    return 0;
-}
-
-// what the two create entries share: the argument and device checks, and the searcher with its scalars set (nullptr: g_serr says why)
-static nnd_searcher_s *searcher_new(const char *who, bool args_ok, int32_t device, int64_t n, int32_t dim, int32_t metric, int64_t nnz,
-                                    bool tree_ok, int64_t n_nodes, float min_distance, int32_t n_neighbors, const int64_t *rng_state) {
-    auto fail = [&](const char *msg) -> nnd_searcher_s * {
-        snprintf(g_serr, sizeof(g_serr), "%s: %s", who, msg);
-        return nullptr;
-    };
-    if (!args_ok || n < 1 || dim < 1 || nnz < 0) return fail("bad arguments");
-    if (metric < NND_METRIC_SQEUCLIDEAN || metric > NND_METRIC_YULE || metric == NND_METRIC_PROXY_INNER_PRODUCT + 1) return fail("unknown metric");
-    if (nnd_metric_bool(metric) && dim >= (1 << 23)) return fail("the boolean metrics need dim < 2^23");
-    if (n_nodes > 0 && !tree_ok) return fail("tree arrays missing");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail("no HIP device visible (this library has no CPU path)");
-    if (device < 0 || device >= ndev) return fail("device out of range");
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess || strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return fail("this build targets gfx950 (MI355X) only");
-    nnd_searcher_s *s = new nnd_searcher_s();
-    s->device = device;
-    s->n = n;
-    s->nnz = nnz;
-    s->n_nodes = n_nodes;
-    s->d = dim;
-    s->dp = (dim + 3) & ~3;
-    s->metric = metric;
-    s->n_neighbors = n_neighbors;
-    s->min_distance = min_distance;
-    s->seed = rng_state ? nnd_mix32((uint32_t)rng_state[0] ^ nnd_mix32((uint32_t)rng_state[1] + 0x9E3779B9u) ^ nnd_mix32((uint32_t)rng_state[2] + 0x7F4A7C15u)) : 1u;
-    return s;
-}
-static int searcher_filled(const char *who, nnd_searcher_s *s, int rc, nnd_searcher_t *out) {
-    if (rc) {
-        snprintf(g_serr, sizeof(g_serr), "%s: %s", who, s->err);
-        nnd_searcher_destroy(s);
-        return 1;
-    }
-    *out = s;
-    return 0;
-}
-
-extern "C" int32_t nnd_searcher_create(nnd_searcher_t *out, int32_t device, int64_t n, int32_t dim, int32_t metric, const float *data,
-                                       const int32_t *indptr, const int32_t *indices, int64_t nnz, const float *hyperplanes,
-                                       const float *offsets, const int32_t *children, const int32_t *tree_indices, int64_t n_nodes,
-                                       float min_distance, int32_t n_neighbors, const int64_t *rng_state) {
-    nnd_searcher_s *s = searcher_new("nnd_searcher_create", out && data && indptr && indices, device, n, dim, metric, nnz,
-                                     hyperplanes && offsets && children && tree_indices, n_nodes, min_distance, n_neighbors, rng_state);
-    if (!s) return 1;
-    return searcher_filled("nnd_searcher_create", s, searcher_fill(s, data, indptr, indices, hyperplanes, offsets, children, tree_indices), out);
-}
-
-extern "C" int32_t nnd_searcher_create_device(nnd_searcher_t *out, int32_t device, int64_t n, int32_t dim, int32_t metric, const void *rows_dev,
-                                              int32_t dtype, const int32_t *order_dev, const int32_t *indptr_dev, const int32_t *indices_dev,
-                                              int64_t nnz, const float *hyperplanes, const float *offsets, const int32_t *children,
-                                              const int32_t *tree_indices, int64_t n_nodes, float min_distance, int32_t n_neighbors,
-                                              const int64_t *rng_state, void *hip_stream) {
-    const bool args_ok = out && rows_dev && indptr_dev && (indices_dev || nnz == 0) && dtype >= NND_DTYPE_FLOAT32 && dtype <= NND_DTYPE_FLOAT64;
-    nnd_searcher_s *s = searcher_new("nnd_searcher_create_device", args_ok, device, n, dim, metric, nnz,
-                                     hyperplanes && offsets && children && tree_indices, n_nodes, min_distance, n_neighbors, rng_state);
-    if (!s) return 1;
-    return searcher_filled("nnd_searcher_create_device", s,
-                           searcher_fill_device(s, rows_dev, dtype, order_dev, indptr_dev, indices_dev, hyperplanes, offsets, children, tree_indices,
-                                                (hipStream_t)hip_stream), out);
-}
-
-extern "C" int64_t nnd_searcher_last_spilled(nnd_searcher_t s) { return s ? s->last_spilled : -1; }
-extern "C" int32_t nnd_searcher_set_tier(nnd_searcher_t s, int32_t tier) {
-    if (!s) { snprintf(g_serr, sizeof(g_serr), "nnd_searcher_set_tier: null searcher"); return 1; }
-    if (tier != 0 && tier != 1) { s->set_error("nnd_searcher_set_tier: tier must be 0 (automatic) or 1 (global-memory tier for every query)"); return 1; }
-    s->force_big = tier == 1;
-    return 0;
-}
-
-// the three forms of k_query (its Q8 / RR switches)
-enum q_form { Q_FORM_FLOAT, Q_FORM_U8, Q_FORM_RERANK, Q_FORM_BOOL /* the float form of the boolean family: k_query_bool */ };
-template <bool BIG>
-static auto query_kernel(q_form form, int k) -> decltype(&k_query<BIG, 1>) {
-    // (k > 64, round 5: the result list as two or four entries per lane; the reference takes any k, pynndescent_.py:2275-2379)
-    switch (form) {
-        case Q_FORM_U8: return k > 128 ? k_query<BIG, 4, true> : (k > 64 ? k_query<BIG, 2, true> : k_query<BIG, 1, true>);
-        case Q_FORM_BOOL: return k > 128 ? k_query_bool<BIG, 4> : (k > 64 ? k_query_bool<BIG, 2> : k_query_bool<BIG, 1>);
-        case Q_FORM_RERANK: return k > 128 ? k_query<BIG, 4, false, true> : (k > 64 ? k_query<BIG, 2, false, true> : k_query<BIG, 1, false, true>);
-        default: return k > 128 ? k_query<BIG, 4> : (k > 64 ? k_query<BIG, 2> : k_query<BIG, 1>);
-    }
-}
-template <bool BIG>
-static auto query_kernel_filtered(q_form form, int k) -> decltype(&k_query_filtered<BIG, 1>) {
-    switch (form) {
-        case Q_FORM_U8: return k > 128 ? k_query_filtered<BIG, 4, true> : (k > 64 ? k_query_filtered<BIG, 2, true> : k_query_filtered<BIG, 1, true>);
-        case Q_FORM_BOOL: return k > 128 ? k_query_bool_filtered<BIG, 4> : (k > 64 ? k_query_bool_filtered<BIG, 2> : k_query_bool_filtered<BIG, 1>);
-        case Q_FORM_RERANK:
-            return k > 128 ? k_query_filtered<BIG, 4, false, true> : (k > 64 ? k_query_filtered<BIG, 2, false, true> : k_query_filtered<BIG, 1, false, true>);
-        default: return k > 128 ? k_query_filtered<BIG, 4> : (k > 64 ? k_query_filtered<BIG, 2> : k_query_filtered<BIG, 1>);
-    }
-}
-template <bool BIG>
-static auto query_kernel_tagged(q_form form, int k) -> decltype(&k_query_tagged<BIG, 1>) {
-    switch (form) {
-        case Q_FORM_U8: return k > 128 ? k_query_tagged<BIG, 4, true> : (k > 64 ? k_query_tagged<BIG, 2, true> : k_query_tagged<BIG, 1, true>);
-        case Q_FORM_BOOL: return k > 128 ? k_query_bool_tagged<BIG, 4> : (k > 64 ? k_query_bool_tagged<BIG, 2> : k_query_bool_tagged<BIG, 1>);
-        case Q_FORM_RERANK:
-            return k > 128 ? k_query_tagged<BIG, 4, false, true> : (k > 64 ? k_query_tagged<BIG, 2, false, true> : k_query_tagged<BIG, 1, false, true>);
-        default: return k > 128 ? k_query_tagged<BIG, 4> : (k > 64 ? k_query_tagged<BIG, 2> : k_query_tagged<BIG, 1>);
-    }
+// what one launch of the walk takes beside the searcher's own state (host side only: the kernel takes plain arguments)
+struct q_call {
+    const float *dq;
+    int64_t nq;
+    int k, k_out;
+    float epsilon;
+    int32_t *di;
+    float *dd;
+    uint8_t *dov;          // LDS tier: the queries' overflow flags
+    const int32_t *qlist;  // big tier: the queries of this batch, n_list of them
+    int n_list;
+    unsigned char *scratch;
+    size_t stride;
+    const uint32_t *allow;
+    const uint64_t *dmasks;
+};
+static void query_launch(q_kernel kern, unsigned grid, size_t lds, hipStream_t st, const nnd_searcher_s *s, const q_call &c) {
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, s->x, s->xn2, s->dp, s->d, s->metric, s->n, s->indptr, s->indices, s->hyper, s->offsets,
+                       s->children, s->tree_idx, s->n_nodes, c.dq, c.nq, c.k, c.epsilon, s->min_distance, s->n_neighbors, s->seed, c.di, c.dd, c.dov,
+                       c.qlist, c.n_list, c.scratch, c.stride, (const uint8_t *)s->codes, s->dcs, (const float *)s->lut, (const float *)s->cn2, c.k_out,
+                       c.allow, (const uint64_t *)s->tags, c.dmasks);
 }
 
 // every query entry point: the walk keeps k results (the float rows) or k = search_k results and reranks them to k_out
@@ -1057,14 +614,9 @@ static int searcher_run(nnd_searcher_s *s, const float *queries, int64_t nq, int
                         int32_t *out_idx, float *out_dist, bool on_device = false, hipStream_t user_stream = nullptr,
                         const uint64_t *qmasks = nullptr /* the tagged entries: (nq) mask words, where the queries are */) {
     const bool q8 = form == Q_FORM_U8;
-    if (form == Q_FORM_FLOAT && nnd_metric_bool(s->metric)) form = Q_FORM_BOOL;
-    auto kq_lds = query_kernel<false>(form, k);
-    auto kq_big = query_kernel<true>(form, k);
-    auto fq_lds = query_kernel_filtered<false>(form, k);  // launched instead while a filter is set (nnd_searcher_set_filter*)
-    auto fq_big = query_kernel_filtered<true>(form, k);
-    const uint32_t *allow = s->filter_on ? s->allow : nullptr;
-    auto tq_lds = query_kernel_tagged<false>(form, k);  // launched instead by the tagged entries (nnd_searcher_query_tagged*)
-    auto tq_big = query_kernel_tagged<true>(form, k);
+    const uint32_t *allow = s->filter_on ? s->allow : nullptr;  // set by nnd_searcher_set_filter*
+    const q_filt filt = qmasks ? Q_FILT_TAGS : allow ? Q_FILT_ALLOW : Q_FILT_NONE;
+    const q_kernel kq_lds = query_kernel(false, form, filt, k), kq_big = query_kernel(true, form, filt, k);
     const uint64_t *dmasks = nullptr;
     if (nq <= 0) return 0;
     if (nq >= (int64_t)0x7FFFFFF0) { s->set_error("nnd_searcher_query: too many queries in one call"); return 1; }
@@ -1097,25 +649,12 @@ static int searcher_run(nnd_searcher_s *s, const float *queries, int64_t nq, int
                 dmasks = dm;
             }
         }
+        q_call call = {dq, nq, k, k_out, epsilon, di, dd, dov, nullptr, 0, nullptr, 0, allow, dmasks};
         if (!s->force_big) {
-            if (smem > 64 * 1024 && hipFuncSetAttribute(dmasks ? (const void *)tq_lds : allow ? (const void *)fq_lds : (const void *)kq_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) {
+            if (smem > 64 * 1024 && hipFuncSetAttribute((const void *)kq_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) {
                 s->set_error("nnd_searcher_query: rows of %d floats need %zu bytes of LDS per workgroup", s->d, smem); rc = 1; break;
             }
-            if (dmasks)
-                hipLaunchKernelGGL(tq_lds, dim3((unsigned)((nq + 3) / 4)), dim3(256), smem, st, s->x, s->xn2, s->dp, s->d, s->metric, s->n,
-                                   s->indptr, s->indices, s->hyper, s->offsets, s->children, s->tree_idx, s->n_nodes, dq, nq, k, epsilon,
-                                   s->min_distance, s->n_neighbors, s->seed, di, dd, dov, (const int32_t *)nullptr, 0, (unsigned char *)nullptr, (size_t)0,
-                                   (const uint8_t *)s->codes, s->dcs, (const float *)s->lut, (const float *)s->cn2, k_out, (const uint64_t *)s->tags, dmasks);
-            else if (allow)
-                hipLaunchKernelGGL(fq_lds, dim3((unsigned)((nq + 3) / 4)), dim3(256), smem, st, s->x, s->xn2, s->dp, s->d, s->metric, s->n,
-                                   s->indptr, s->indices, s->hyper, s->offsets, s->children, s->tree_idx, s->n_nodes, dq, nq, k, epsilon,
-                                   s->min_distance, s->n_neighbors, s->seed, di, dd, dov, (const int32_t *)nullptr, 0, (unsigned char *)nullptr, (size_t)0,
-                                   (const uint8_t *)s->codes, s->dcs, (const float *)s->lut, (const float *)s->cn2, k_out, allow);
-            else
-                hipLaunchKernelGGL(kq_lds, dim3((unsigned)((nq + 3) / 4)), dim3(256), smem, st, s->x, s->xn2, s->dp, s->d, s->metric, s->n,
-                                   s->indptr, s->indices, s->hyper, s->offsets, s->children, s->tree_idx, s->n_nodes, dq, nq, k, epsilon,
-                                   s->min_distance, s->n_neighbors, s->seed, di, dd, dov, (const int32_t *)nullptr, 0, (unsigned char *)nullptr, (size_t)0,
-                                   (const uint8_t *)s->codes, s->dcs, (const float *)s->lut, (const float *)s->cn2, k_out);
+            query_launch(kq_lds, (unsigned)((nq + 3) / 4), smem, st, s, call);
             if (hipGetLastError() != hipSuccess) { s->set_error("k_query launch failed"); rc = 1; break; }
             if (hipMemcpyAsync(hov.data(), dov, (size_t)nq, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
                 s->set_error("nnd_searcher_query: kernel or D2H failed: %s", hipGetErrorString(hipGetLastError())); rc = 1; break;
@@ -1135,23 +674,13 @@ static int searcher_run(nnd_searcher_s *s, const float *queries, int64_t nq, int
                 s->set_error("nnd_searcher_query: out of device memory for the global-memory tier (%zu bytes)", stride * batch); rc = 1; break;
             }
             if (hipMemcpyAsync(dlist, again.data(), sizeof(int32_t) * again.size(), hipMemcpyHostToDevice, st) != hipSuccess) { s->set_error("H2D of the query list failed"); rc = 1; break; }
+            call.dov = nullptr;
+            call.scratch = scratch;
+            call.stride = stride;
             for (size_t b0 = 0; b0 < again.size() && !rc; b0 += batch) {
-                const int nb = (int)(again.size() - b0 < batch ? again.size() - b0 : batch);
-                if (dmasks)
-                    hipLaunchKernelGGL(tq_big, dim3((unsigned)((nb + 3) / 4)), dim3(256), 4 * per_wave_big + lut_bytes, st, s->x, s->xn2, s->dp, s->d,
-                                       s->metric, s->n, s->indptr, s->indices, s->hyper, s->offsets, s->children, s->tree_idx, s->n_nodes, dq, nq, k, epsilon,
-                                       s->min_distance, s->n_neighbors, s->seed, di, dd, (uint8_t *)nullptr, (const int32_t *)(dlist + b0), nb, scratch, stride,
-                                       (const uint8_t *)s->codes, s->dcs, (const float *)s->lut, (const float *)s->cn2, k_out, (const uint64_t *)s->tags, dmasks);
-                else if (allow)
-                    hipLaunchKernelGGL(fq_big, dim3((unsigned)((nb + 3) / 4)), dim3(256), 4 * per_wave_big + lut_bytes, st, s->x, s->xn2, s->dp, s->d,
-                                       s->metric, s->n, s->indptr, s->indices, s->hyper, s->offsets, s->children, s->tree_idx, s->n_nodes, dq, nq, k, epsilon,
-                                       s->min_distance, s->n_neighbors, s->seed, di, dd, (uint8_t *)nullptr, (const int32_t *)(dlist + b0), nb, scratch, stride,
-                                       (const uint8_t *)s->codes, s->dcs, (const float *)s->lut, (const float *)s->cn2, k_out, allow);
-                else
-                    hipLaunchKernelGGL(kq_big, dim3((unsigned)((nb + 3) / 4)), dim3(256), 4 * per_wave_big + lut_bytes, st, s->x, s->xn2, s->dp, s->d,
-                                       s->metric, s->n, s->indptr, s->indices, s->hyper, s->offsets, s->children, s->tree_idx, s->n_nodes, dq, nq, k, epsilon,
-                                       s->min_distance, s->n_neighbors, s->seed, di, dd, (uint8_t *)nullptr, (const int32_t *)(dlist + b0), nb, scratch, stride,
-                                       (const uint8_t *)s->codes, s->dcs, (const float *)s->lut, (const float *)s->cn2, k_out);
+                call.qlist = dlist + b0;
+                call.n_list = (int)(again.size() - b0 < batch ? again.size() - b0 : batch);
+                query_launch(kq_big, (unsigned)((call.n_list + 3) / 4), 4 * per_wave_big + lut_bytes, st, s, call);
                 if (hipGetLastError() != hipSuccess) { s->set_error("k_query (global-memory tier) launch failed"); rc = 1; }
             }
             if (rc) break;
@@ -1163,315 +692,34 @@ static int searcher_run(nnd_searcher_s *s, const float *queries, int64_t nq, int
     return rc;
 }
 
-extern "C" int32_t nnd_searcher_query(nnd_searcher_t s, const float *queries, int64_t nq, int32_t k, float epsilon, int32_t *out_idx,
-                                      float *out_dist) {
-    if (!s) { snprintf(g_serr, sizeof(g_serr), "nnd_searcher_query: null searcher"); return 1; }
-    if (k < 1 || k > 256) { s->set_error("nnd_searcher_query: k must be in 1..256 (got %d)", k); return 1; }
-    if (s->metric == NND_METRIC_PROXY_INNER_PRODUCT) {
-        s->set_error("nnd_searcher_query: metric %d is a proxy distance: its queries go through nnd_searcher_query_rerank", s->metric);
-        return 1;
+// ---- the query entries (include/pynnd_amd.h) ----
+// The checks of all eight.  `form`: NND_QUERY_FLOAT (search_k is ignored: the walk keeps k), NND_QUERY_PROXY (quantization="uint8",
+// pynndescent_.py:2191-2225, 2309-2364) or NND_QUERY_RERANK (metric="proxy_inner_product", pynndescent_.py:2309-2312, 2363-2371);
+// `rerank_via`: how this entry's caller reaches the rerank form; `masks`: the tagged entries' mask words (tagged = true), which
+// need the searcher's tags and no allow set.  On 0, *search_k is the walk's list length and *qf its form.
+static int query_args(nnd_searcher_s *s, const char *who, int32_t form, int32_t k, int32_t *search_k, const char *rerank_via, bool tagged,
+                      const void *masks, int64_t nq, q_form *qf) {
+    if (tagged) {
+        if (!s->tags) { s->set_error("%s: the searcher has no tags (nnd_searcher_set_tags first)", who); return 1; }
+        if (s->filter_on) { s->set_error("%s: the searcher has a filter set; an allow set and query masks do not combine", who); return 1; }
+        if (nq > 0 && !masks) { s->set_error("%s: masks missing", who); return 1; }
     }
-    return searcher_run(s, queries, nq, k, k, epsilon, Q_FORM_FLOAT, out_idx, out_dist);
-}
-
-// ---- quantization="uint8" (pynndescent_.py:2191-2225, 2309-2364) ----
-// the two 256-entry tables: the walk's codebook (entries past n_values = the last value; the reference reads past its
-// array there, DESIGN.md "Quantized search") and the search table (+inf past n_values)
-static int quant_tables(nnd_searcher_s *s, const char *who, const float *values, int32_t n_values) {
-    if (s->metric != NND_METRIC_SQEUCLIDEAN && s->metric != NND_METRIC_ALT_COSINE && s->metric != NND_METRIC_ALT_DOT) {
-        s->set_error("%s: uint8 quantization supports the sqeuclidean, alternative cosine and alternative dot metrics (metric %d)", who, s->metric);
-        return 1;
-    }
-    if (!values || n_values < 1 || n_values > 256) { s->set_error("%s: the codebook must have 1..256 values (got %d)", who, n_values); return 1; }
-    S_HIP(hipSetDevice(s->device));
-    S_HIP(hipStreamSynchronize(s->stream));  // no kernel or copy of an earlier call still uses the tables
-    float *tab = s->tab_host;
-    for (int i = 0; i < 256; i++) {
-        tab[i] = values[i < n_values ? i : n_values - 1];
-        tab[256 + i] = i < n_values ? values[i] : INFINITY;
-    }
-    s->dcs = (s->d + 15) & ~15;
-    if (!s->lut) S_ALLOC(&s->lut, 512);
-    if (!s->codes) S_ALLOC(&s->codes, (size_t)s->n * s->dcs);
-    if (!s->cn2 && s->metric != NND_METRIC_SQEUCLIDEAN) S_ALLOC(&s->cn2, (size_t)s->n);
-    // queued on the searcher's stream, so the kernels that read the tables are ordered after it (the stream is
-    // non-blocking: it does not wait for copies on the null stream); tab_host outlives the copy (next call syncs first)
-    S_HIP(hipMemcpyAsync(s->lut, tab, sizeof(float) * 512, hipMemcpyHostToDevice, s->stream));
-    return 0;
-}
-
-static int quant_launch(nnd_searcher_s *s, const float *x, int64_t xstride) {
-    const int64_t blocks = (s->n + 3) / 4 < 4096 ? (s->n + 3) / 4 : 4096;
-    hipLaunchKernelGGL(k_quantize_u8, dim3((unsigned)blocks), dim3(256), 0, s->stream, x, xstride, s->n, s->d, s->dcs, (const float *)s->lut,
-                       (const float *)(s->lut + 256), s->codes, s->cn2);
-    S_HIP(hipGetLastError());
-    return 0;
-}
-
-extern "C" int32_t nnd_searcher_quantize_u8(nnd_searcher_t s, const float *rows, const float *values, int32_t n_values, uint8_t *codes_out) {
-    if (!s) { snprintf(g_serr, sizeof(g_serr), "nnd_searcher_quantize_u8: null searcher"); return 1; }
-    if (quant_tables(s, "nnd_searcher_quantize_u8", values, n_values)) return 1;
-    nnd_scratch tmp;  // released on return, behind the synchronise below
-    float *drows = nullptr;
-    if (rows) {
-        if (!(drows = tmp.get<float>(s, (size_t)s->n * s->d))) return 1;
-        if (hipMemcpyAsync(drows, rows, sizeof(float) * (size_t)s->n * s->d, hipMemcpyHostToDevice, s->stream) != hipSuccess) {
-            s->set_error("nnd_searcher_quantize_u8: H2D of the rows failed");
-            return 1;
-        }
-    }
-    int rc = rows ? quant_launch(s, drows, s->d) : quant_launch(s, s->x, s->dp);
-    if (!rc && codes_out &&
-        hipMemcpy2DAsync(codes_out, (size_t)s->d, s->codes, (size_t)s->dcs, (size_t)s->d, (size_t)s->n, hipMemcpyDeviceToHost, s->stream) != hipSuccess) {
-        s->set_error("nnd_searcher_quantize_u8: D2H of the codes failed");
-        rc = 1;
-    }
-    if (hipStreamSynchronize(s->stream) != hipSuccess && !rc) {
-        s->set_error("nnd_searcher_quantize_u8: kernel failed: %s", hipGetErrorString(hipGetLastError()));
-        rc = 1;
-    }
-    return rc;
-}
-
-extern "C" int32_t nnd_searcher_set_codes_u8(nnd_searcher_t s, const float *values, int32_t n_values, const uint8_t *codes) {
-    if (!s) { snprintf(g_serr, sizeof(g_serr), "nnd_searcher_set_codes_u8: null searcher"); return 1; }
-    if (!codes) { s->set_error("nnd_searcher_set_codes_u8: codes missing"); return 1; }
-    if (quant_tables(s, "nnd_searcher_set_codes_u8", values, n_values)) return 1;
-    S_HIP(hipMemsetAsync(s->codes, 0, (size_t)s->n * s->dcs, s->stream));
-    S_HIP(hipMemcpy2DAsync(s->codes, (size_t)s->dcs, codes, (size_t)s->d, (size_t)s->d, (size_t)s->n, hipMemcpyHostToDevice, s->stream));
-    if (s->cn2 && quant_launch(s, nullptr, 0)) return 1;
-    S_HIP(hipStreamSynchronize(s->stream));
-    return 0;
-}
-
-extern "C" int32_t nnd_searcher_query_proxy(nnd_searcher_t s, const float *queries, int64_t nq, int32_t k, int32_t search_k, float epsilon,
-                                            int32_t *out_idx, float *out_dist) {
-    if (!s) { snprintf(g_serr, sizeof(g_serr), "nnd_searcher_query_proxy: null searcher"); return 1; }
-    if (!s->codes) { s->set_error("nnd_searcher_query_proxy: the searcher has no codes (nnd_searcher_quantize_u8 first)"); return 1; }
-    if (search_k < 1 || search_k > 256 || k < 1 || k > search_k) {
-        s->set_error("nnd_searcher_query_proxy: need 1 <= k <= search_k <= 256 (got k %d, search_k %d)", k, search_k);
-        return 1;
-    }
-    return searcher_run(s, queries, nq, search_k, k, epsilon, Q_FORM_U8, out_idx, out_dist);
-}
-
-// ---- metric="proxy_inner_product" (pynndescent_.py:2309-2312, 2363-2371): the float walk with the rerank epilogue ----
-extern "C" int32_t nnd_searcher_query_rerank(nnd_searcher_t s, const float *queries, int64_t nq, int32_t k, int32_t search_k, float epsilon,
-                                             int32_t *out_idx, float *out_dist) {
-    if (!s) { snprintf(g_serr, sizeof(g_serr), "nnd_searcher_query_rerank: null searcher"); return 1; }
-    if (s->metric != NND_METRIC_PROXY_INNER_PRODUCT) {
-        s->set_error("nnd_searcher_query_rerank: metric %d has no true distance to rerank by (the proxy inner product, %d, has)", s->metric,
-                     NND_METRIC_PROXY_INNER_PRODUCT);
-        return 1;
-    }
-    if (search_k < 1 || search_k > 256 || k < 1 || k > search_k) {
-        s->set_error("nnd_searcher_query_rerank: need 1 <= k <= search_k <= 256 (got k %d, search_k %d)", k, search_k);
-        return 1;
-    }
-    return searcher_run(s, queries, nq, search_k, k, epsilon, Q_FORM_RERANK, out_idx, out_dist);
-}
-
-// ---- the filter (include/pynnd_amd.h): the allow bitset, built on `st` from a mask or an id list in device memory ----
-static int searcher_build_filter(nnd_searcher_s *s, const char *who, const void *filter_dev, int64_t count, int32_t kind, const int32_t *order_dev,
-                                 hipStream_t st, nnd_scratch &tmp, int64_t *n_allowed) {
-    s->filter_on = false;  // a failed call leaves the searcher unfiltered
-    if (!s->allow) S_ALLOC(&s->allow, (size_t)((s->n + 31) / 32));
-    if (!s->fstat) S_ALLOC(&s->fstat, 2);
-    S_HIP(hipMemsetAsync(s->fstat, 0, 2 * sizeof(unsigned long long), st));
-    const uint8_t *mask = (const uint8_t *)filter_dev;
-    if (kind == NND_FILTER_IDS) {
-        uint8_t *marked = tmp.get<uint8_t>(s, (size_t)s->n);
-        if (!marked) return 1;
-        S_HIP(hipMemsetAsync(marked, 0, (size_t)s->n, st));
-        if (count > 0)
-            hipLaunchKernelGGL(k_filter_mark_ids, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, (const int64_t *)filter_dev, count, s->n, marked,
-                               s->fstat);
-        mask = marked;
-    }
-    hipLaunchKernelGGL(k_filter_bitset, dim3((unsigned)((s->n + 255) / 256)), dim3(256), 0, st, mask, order_dev, s->n, s->allow, s->fstat);
-    S_HIP(hipGetLastError());
-    unsigned long long stat[2] = {0, 0};
-    S_HIP(hipMemcpyAsync(stat, s->fstat, sizeof(stat), hipMemcpyDeviceToHost, st));
-    S_HIP(hipStreamSynchronize(st));
-    if (stat[1]) {
-        s->set_error("%s: an id of the filter is outside 0 .. %lld", who, (long long)(s->n - 1));
-        return 2;
-    }
-    if (n_allowed) *n_allowed = (int64_t)stat[0];
-    s->filter_on = true;
-    return 0;
-}
-static int filter_args(nnd_searcher_s *s, const char *who, const void *filter, int64_t count, int32_t kind) {
-    if (kind != NND_FILTER_MASK && kind != NND_FILTER_IDS) { s->set_error("%s: kind must be NND_FILTER_MASK or NND_FILTER_IDS (got %d)", who, kind); return 1; }
-    if (count < 0 || (count > 0 && !filter)) { s->set_error("%s: filter missing", who); return 1; }
-    if (kind == NND_FILTER_MASK && count != s->n) { s->set_error("%s: a mask has one byte per row (%lld), got %lld", who, (long long)s->n, (long long)count); return 1; }
-    if (count >= ((int64_t)1 << 40)) { s->set_error("%s: too many ids", who); return 1; }
-    return 0;
-}
-extern "C" int32_t nnd_searcher_set_filter(nnd_searcher_t s, const void *filter, int64_t count, int32_t kind, const int32_t *order, int64_t *n_allowed) {
-    if (!s) { snprintf(g_serr, sizeof(g_serr), "nnd_searcher_set_filter: null searcher"); return 1; }
-    if (filter_args(s, "nnd_searcher_set_filter", filter, count, kind)) return 1;
-    S_HIP(hipSetDevice(s->device));
-    nnd_scratch tmp;  // released on return, behind the synchronise of searcher_build_filter
-    const size_t bytes = (size_t)count * (kind == NND_FILTER_IDS ? sizeof(int64_t) : 1);
-    unsigned char *dfilter = tmp.get<unsigned char>(s, bytes);
-    int32_t *dorder = order ? tmp.get<int32_t>(s, (size_t)s->n) : nullptr;
-    if (!dfilter || (order && !dorder)) return 1;
-    if (bytes) S_HIP(hipMemcpyAsync(dfilter, filter, bytes, hipMemcpyHostToDevice, s->stream));
-    if (order) S_HIP(hipMemcpyAsync(dorder, order, sizeof(int32_t) * (size_t)s->n, hipMemcpyHostToDevice, s->stream));
-    const int rc = searcher_build_filter(s, "nnd_searcher_set_filter", dfilter, count, kind, dorder, s->stream, tmp, n_allowed);
-    if (rc) (void)hipStreamSynchronize(s->stream);  // nothing queued still reads tmp
-    return rc;
-}
-extern "C" int32_t nnd_searcher_set_filter_device(nnd_searcher_t s, const void *filter_dev, int64_t count, int32_t kind, const int32_t *order_dev,
-                                                  int64_t *n_allowed, void *hip_stream) {
-    if (!s) { snprintf(g_serr, sizeof(g_serr), "nnd_searcher_set_filter_device: null searcher"); return 1; }
-    if (filter_args(s, "nnd_searcher_set_filter_device", filter_dev, count, kind)) return 1;
-    S_HIP(hipSetDevice(s->device));
-    nnd_scratch tmp;
-    const int rc = searcher_build_filter(s, "nnd_searcher_set_filter_device", filter_dev, count, kind, order_dev, (hipStream_t)hip_stream, tmp, n_allowed);
-    if (rc) (void)hipStreamSynchronize((hipStream_t)hip_stream);
-    return rc;
-}
-extern "C" int32_t nnd_searcher_clear_filter(nnd_searcher_t s) {
-    if (!s) { snprintf(g_serr, sizeof(g_serr), "nnd_searcher_clear_filter: null searcher"); return 1; }
-    s->filter_on = false;  // the bitset stays allocated for the next filter
-    return 0;
-}
-
-// ---- the same three entries for queries and results that live on the device (include/pynnd_amd.h) ----
-static int device_args(nnd_searcher_s *s, const char *who, const void *q, int64_t nq, const void *oi, const void *od) {
-    if (nq > 0 && (!q || !oi || !od)) { s->set_error("%s: null device pointer", who); return 1; }
-    return 0;
-}
-extern "C" int32_t nnd_searcher_query_device(nnd_searcher_t s, const float *queries_dev, int64_t nq, int32_t k, float epsilon,
-                                             int32_t *out_idx_dev, float *out_dist_dev, void *hip_stream) {
-    if (!s) { snprintf(g_serr, sizeof(g_serr), "nnd_searcher_query_device: null searcher"); return 1; }
-    if (k < 1 || k > 256) { s->set_error("nnd_searcher_query_device: k must be in 1..256 (got %d)", k); return 1; }
-    if (s->metric == NND_METRIC_PROXY_INNER_PRODUCT) {
-        s->set_error("nnd_searcher_query_device: metric %d is a proxy distance: its queries go through nnd_searcher_query_rerank_device", s->metric);
-        return 1;
-    }
-    if (device_args(s, "nnd_searcher_query_device", queries_dev, nq, out_idx_dev, out_dist_dev)) return 1;
-    return searcher_run(s, queries_dev, nq, k, k, epsilon, Q_FORM_FLOAT, out_idx_dev, out_dist_dev, true, (hipStream_t)hip_stream);
-}
-extern "C" int32_t nnd_searcher_query_proxy_device(nnd_searcher_t s, const float *queries_dev, int64_t nq, int32_t k, int32_t search_k,
-                                                   float epsilon, int32_t *out_idx_dev, float *out_dist_dev, void *hip_stream) {
-    if (!s) { snprintf(g_serr, sizeof(g_serr), "nnd_searcher_query_proxy_device: null searcher"); return 1; }
-    if (!s->codes) { s->set_error("nnd_searcher_query_proxy_device: the searcher has no codes (nnd_searcher_quantize_u8 first)"); return 1; }
-    if (search_k < 1 || search_k > 256 || k < 1 || k > search_k) {
-        s->set_error("nnd_searcher_query_proxy_device: need 1 <= k <= search_k <= 256 (got k %d, search_k %d)", k, search_k);
-        return 1;
-    }
-    if (device_args(s, "nnd_searcher_query_proxy_device", queries_dev, nq, out_idx_dev, out_dist_dev)) return 1;
-    return searcher_run(s, queries_dev, nq, search_k, k, epsilon, Q_FORM_U8, out_idx_dev, out_dist_dev, true, (hipStream_t)hip_stream);
-}
-extern "C" int32_t nnd_searcher_query_rerank_device(nnd_searcher_t s, const float *queries_dev, int64_t nq, int32_t k, int32_t search_k,
-                                                    float epsilon, int32_t *out_idx_dev, float *out_dist_dev, void *hip_stream) {
-    if (!s) { snprintf(g_serr, sizeof(g_serr), "nnd_searcher_query_rerank_device: null searcher"); return 1; }
-    if (s->metric != NND_METRIC_PROXY_INNER_PRODUCT) {
-        s->set_error("nnd_searcher_query_rerank_device: metric %d has no true distance to rerank by (the proxy inner product, %d, has)", s->metric,
-                     NND_METRIC_PROXY_INNER_PRODUCT);
-        return 1;
-    }
-    if (search_k < 1 || search_k > 256 || k < 1 || k > search_k) {
-        s->set_error("nnd_searcher_query_rerank_device: need 1 <= k <= search_k <= 256 (got k %d, search_k %d)", k, search_k);
-        return 1;
-    }
-    if (device_args(s, "nnd_searcher_query_rerank_device", queries_dev, nq, out_idx_dev, out_dist_dev)) return 1;
-    return searcher_run(s, queries_dev, nq, search_k, k, epsilon, Q_FORM_RERANK, out_idx_dev, out_dist_dev, true, (hipStream_t)hip_stream);
-}
-
-// ---- per-query filters (include/pynnd_amd.h): the tag words, the counts per mask, the tagged query ----
-static int searcher_gather_tags(nnd_searcher_s *s, const uint64_t *tags_dev, const int32_t *order_dev, hipStream_t st) {
-    if (!s->tags) S_ALLOC(&s->tags, (size_t)s->n);
-    hipLaunchKernelGGL(k_tags_gather, dim3((unsigned)((s->n + 255) / 256)), dim3(256), 0, st, tags_dev, order_dev, s->n, s->tags);
-    S_HIP(hipGetLastError());
-    S_HIP(hipStreamSynchronize(st));
-    return 0;
-}
-extern "C" int32_t nnd_searcher_clear_tags(nnd_searcher_t s) {
-    if (!s) { snprintf(g_serr, sizeof(g_serr), "nnd_searcher_clear_tags: null searcher"); return 1; }
-    S_HIP(hipSetDevice(s->device));
-    S_HIP(hipStreamSynchronize(s->stream));
-    s->mem.free(&s->tags);
-    return 0;
-}
-extern "C" int32_t nnd_searcher_set_tags(nnd_searcher_t s, const uint64_t *tags, const int32_t *order) {
-    if (!s) { snprintf(g_serr, sizeof(g_serr), "nnd_searcher_set_tags: null searcher"); return 1; }
-    if (!tags) { s->set_error("nnd_searcher_set_tags: tags missing"); return 1; }
-    S_HIP(hipSetDevice(s->device));
-    nnd_scratch tmp;  // released on return, behind the synchronise of searcher_gather_tags
-    uint64_t *dtags = tmp.get<uint64_t>(s, (size_t)s->n);
-    int32_t *dorder = order ? tmp.get<int32_t>(s, (size_t)s->n) : nullptr;
-    if (!dtags || (order && !dorder)) return 1;
-    S_HIP(hipMemcpyAsync(dtags, tags, sizeof(uint64_t) * (size_t)s->n, hipMemcpyHostToDevice, s->stream));
-    if (order) S_HIP(hipMemcpyAsync(dorder, order, sizeof(int32_t) * (size_t)s->n, hipMemcpyHostToDevice, s->stream));
-    const int rc = searcher_gather_tags(s, dtags, dorder, s->stream);
-    if (rc) (void)hipStreamSynchronize(s->stream);
-    return rc;
-}
-extern "C" int32_t nnd_searcher_set_tags_device(nnd_searcher_t s, const uint64_t *tags_dev, const int32_t *order_dev, void *hip_stream) {
-    if (!s) { snprintf(g_serr, sizeof(g_serr), "nnd_searcher_set_tags_device: null searcher"); return 1; }
-    if (!tags_dev) { s->set_error("nnd_searcher_set_tags_device: tags missing"); return 1; }
-    S_HIP(hipSetDevice(s->device));
-    return searcher_gather_tags(s, tags_dev, order_dev, (hipStream_t)hip_stream);
-}
-static int searcher_count_tags(nnd_searcher_s *s, const uint64_t *masks_dev, int32_t n_masks, unsigned long long *counts_dev, hipStream_t st) {
-    S_HIP(hipMemsetAsync(counts_dev, 0, sizeof(unsigned long long) * (size_t)n_masks, st));
-    const int64_t per_block = 256 * Q_COUNT_ROWS;
-    hipLaunchKernelGGL(k_tags_count, dim3((unsigned)((s->n + per_block - 1) / per_block)), dim3(256), 0, st, (const uint64_t *)s->tags, s->n, masks_dev, (int)n_masks,
-                       counts_dev);
-    S_HIP(hipGetLastError());
-    return 0;
-}
-static int count_args(nnd_searcher_s *s, const char *who, const void *masks, int32_t n_masks, const void *counts) {
-    if (!s->tags) { s->set_error("%s: the searcher has no tags (nnd_searcher_set_tags first)", who); return 1; }
-    if (n_masks < 0 || (n_masks > 0 && (!masks || !counts))) { s->set_error("%s: masks or counts missing", who); return 1; }
-    return 0;
-}
-extern "C" int32_t nnd_searcher_count_tags(nnd_searcher_t s, const uint64_t *masks, int32_t n_masks, int64_t *counts) {
-    if (!s) { snprintf(g_serr, sizeof(g_serr), "nnd_searcher_count_tags: null searcher"); return 1; }
-    if (count_args(s, "nnd_searcher_count_tags", masks, n_masks, counts)) return 1;
-    if (n_masks == 0) return 0;
-    S_HIP(hipSetDevice(s->device));
-    nnd_scratch tmp;
-    uint64_t *dm = tmp.get<uint64_t>(s, (size_t)n_masks);
-    unsigned long long *dc = tmp.get<unsigned long long>(s, (size_t)n_masks);
-    if (!dm || !dc) return 1;
-    int rc = 0;
-    if (hipMemcpyAsync(dm, masks, sizeof(uint64_t) * (size_t)n_masks, hipMemcpyHostToDevice, s->stream) != hipSuccess) { s->set_error("nnd_searcher_count_tags: H2D of the masks failed"); rc = 1; }
-    if (!rc) rc = searcher_count_tags(s, dm, n_masks, dc, s->stream);
-    if (!rc && hipMemcpyAsync(counts, dc, sizeof(int64_t) * (size_t)n_masks, hipMemcpyDeviceToHost, s->stream) != hipSuccess) { s->set_error("nnd_searcher_count_tags: D2H of the counts failed"); rc = 1; }
-    if (hipStreamSynchronize(s->stream) != hipSuccess && !rc) { s->set_error("nnd_searcher_count_tags: kernel failed: %s", hipGetErrorString(hipGetLastError())); rc = 1; }
-    return rc;
-}
-extern "C" int32_t nnd_searcher_count_tags_device(nnd_searcher_t s, const uint64_t *masks_dev, int32_t n_masks, int64_t *counts_dev, void *hip_stream) {
-    if (!s) { snprintf(g_serr, sizeof(g_serr), "nnd_searcher_count_tags_device: null searcher"); return 1; }
-    if (count_args(s, "nnd_searcher_count_tags_device", masks_dev, n_masks, counts_dev)) return 1;
-    if (n_masks == 0) return 0;
-    S_HIP(hipSetDevice(s->device));
-    if (searcher_count_tags(s, masks_dev, n_masks, (unsigned long long *)counts_dev, (hipStream_t)hip_stream)) return 1;
-    S_HIP(hipStreamSynchronize((hipStream_t)hip_stream));
-    return 0;
-}
-// the tagged query: `form` NND_QUERY_FLOAT (search_k is ignored), NND_QUERY_PROXY or NND_QUERY_RERANK -- the checks of the three entries
-static int tagged_args(nnd_searcher_s *s, const char *who, int32_t form, int32_t k, int32_t *search_k, const void *masks, int64_t nq, q_form *qf) {
-    if (!s->tags) { s->set_error("%s: the searcher has no tags (nnd_searcher_set_tags first)", who); return 1; }
-    if (s->filter_on) { s->set_error("%s: the searcher has a filter set; an allow set and query masks do not combine", who); return 1; }
-    if (nq > 0 && !masks) { s->set_error("%s: masks missing", who); return 1; }
     if (form == NND_QUERY_FLOAT) {
         if (k < 1 || k > 256) { s->set_error("%s: k must be in 1..256 (got %d)", who, k); return 1; }
-        if (s->metric == NND_METRIC_PROXY_INNER_PRODUCT) { s->set_error("%s: metric %d is a proxy distance: its queries take NND_QUERY_RERANK", who, s->metric); return 1; }
+        if (s->metric == NND_METRIC_PROXY_INNER_PRODUCT) { s->set_error("%s: metric %d is a proxy distance: its queries %s", who, s->metric, rerank_via); return 1; }
         *search_k = k;
-        *qf = Q_FORM_FLOAT;
+        *qf = nnd_metric_bool(s->metric) ? Q_FORM_BOOL : Q_FORM_FLOAT;
         return 0;
     }
     if (form == NND_QUERY_PROXY) {
         if (!s->codes) { s->set_error("%s: the searcher has no codes (nnd_searcher_quantize_u8 first)", who); return 1; }
         *qf = Q_FORM_U8;
     } else if (form == NND_QUERY_RERANK) {
-        if (s->metric != NND_METRIC_PROXY_INNER_PRODUCT) { s->set_error("%s: metric %d has no true distance to rerank by", who, s->metric); return 1; }
+        if (s->metric != NND_METRIC_PROXY_INNER_PRODUCT) {
+            if (tagged) s->set_error("%s: metric %d has no true distance to rerank by", who, s->metric);
+            else s->set_error("%s: metric %d has no true distance to rerank by (the proxy inner product, %d, has)", who, s->metric, NND_METRIC_PROXY_INNER_PRODUCT);
+            return 1;
+        }
         *qf = Q_FORM_RERANK;
     } else {
         s->set_error("%s: form must be NND_QUERY_FLOAT, NND_QUERY_PROXY or NND_QUERY_RERANK (got %d)", who, form);
@@ -1480,18 +728,84 @@ static int tagged_args(nnd_searcher_s *s, const char *who, int32_t form, int32_t
     if (*search_k < 1 || *search_k > 256 || k < 1 || k > *search_k) { s->set_error("%s: need 1 <= k <= search_k <= 256 (got k %d, search_k %d)", who, k, *search_k); return 1; }
     return 0;
 }
+// queries and results that live on the device
+static int device_args(nnd_searcher_s *s, const char *who, const void *q, int64_t nq, const void *oi, const void *od) {
+    if (nq > 0 && (!q || !oi || !od)) { s->set_error("%s: null device pointer", who); return 1; }
+    return 0;
+}
+static int no_searcher(const char *who) {
+    snprintf(g_serr, sizeof(g_serr), "%s: null searcher", who);
+    return 1;
+}
+
+extern "C" int32_t nnd_searcher_query(nnd_searcher_t s, const float *queries, int64_t nq, int32_t k, float epsilon, int32_t *out_idx,
+                                      float *out_dist) {
+    if (!s) return no_searcher("nnd_searcher_query");
+    q_form qf;
+    int32_t search_k = k;
+    if (query_args(s, "nnd_searcher_query", NND_QUERY_FLOAT, k, &search_k, "go through nnd_searcher_query_rerank", false, nullptr, nq, &qf)) return 1;
+    return searcher_run(s, queries, nq, search_k, k, epsilon, qf, out_idx, out_dist);
+}
+extern "C" int32_t nnd_searcher_query_proxy(nnd_searcher_t s, const float *queries, int64_t nq, int32_t k, int32_t search_k, float epsilon,
+                                            int32_t *out_idx, float *out_dist) {
+    if (!s) return no_searcher("nnd_searcher_query_proxy");
+    q_form qf;
+    if (query_args(s, "nnd_searcher_query_proxy", NND_QUERY_PROXY, k, &search_k, nullptr, false, nullptr, nq, &qf)) return 1;
+    return searcher_run(s, queries, nq, search_k, k, epsilon, qf, out_idx, out_dist);
+}
+extern "C" int32_t nnd_searcher_query_rerank(nnd_searcher_t s, const float *queries, int64_t nq, int32_t k, int32_t search_k, float epsilon,
+                                             int32_t *out_idx, float *out_dist) {
+    if (!s) return no_searcher("nnd_searcher_query_rerank");
+    q_form qf;
+    if (query_args(s, "nnd_searcher_query_rerank", NND_QUERY_RERANK, k, &search_k, nullptr, false, nullptr, nq, &qf)) return 1;
+    return searcher_run(s, queries, nq, search_k, k, epsilon, qf, out_idx, out_dist);
+}
 extern "C" int32_t nnd_searcher_query_tagged(nnd_searcher_t s, int32_t form, const float *queries, int64_t nq, int32_t k, int32_t search_k, float epsilon,
                                              const uint64_t *masks, int32_t *out_idx, float *out_dist) {
-    if (!s) { snprintf(g_serr, sizeof(g_serr), "nnd_searcher_query_tagged: null searcher"); return 1; }
+    if (!s) return no_searcher("nnd_searcher_query_tagged");
     q_form qf;
-    if (tagged_args(s, "nnd_searcher_query_tagged", form, k, &search_k, masks, nq, &qf)) return 1;
+    if (query_args(s, "nnd_searcher_query_tagged", form, k, &search_k, "take NND_QUERY_RERANK", true, masks, nq, &qf)) return 1;
     return searcher_run(s, queries, nq, search_k, k, epsilon, qf, out_idx, out_dist, false, nullptr, masks);
+}
+
+extern "C" int32_t nnd_searcher_query_device(nnd_searcher_t s, const float *queries_dev, int64_t nq, int32_t k, float epsilon,
+                                             int32_t *out_idx_dev, float *out_dist_dev, void *hip_stream) {
+    if (!s) return no_searcher("nnd_searcher_query_device");
+    q_form qf;
+    int32_t search_k = k;
+    if (query_args(s, "nnd_searcher_query_device", NND_QUERY_FLOAT, k, &search_k, "go through nnd_searcher_query_rerank_device", false, nullptr, nq, &qf)) return 1;
+    if (device_args(s, "nnd_searcher_query_device", queries_dev, nq, out_idx_dev, out_dist_dev)) return 1;
+    return searcher_run(s, queries_dev, nq, search_k, k, epsilon, qf, out_idx_dev, out_dist_dev, true, (hipStream_t)hip_stream);
+}
+extern "C" int32_t nnd_searcher_query_proxy_device(nnd_searcher_t s, const float *queries_dev, int64_t nq, int32_t k, int32_t search_k,
+                                                   float epsilon, int32_t *out_idx_dev, float *out_dist_dev, void *hip_stream) {
+    if (!s) return no_searcher("nnd_searcher_query_proxy_device");
+    q_form qf;
+    if (query_args(s, "nnd_searcher_query_proxy_device", NND_QUERY_PROXY, k, &search_k, nullptr, false, nullptr, nq, &qf)) return 1;
+    if (device_args(s, "nnd_searcher_query_proxy_device", queries_dev, nq, out_idx_dev, out_dist_dev)) return 1;
+    return searcher_run(s, queries_dev, nq, search_k, k, epsilon, qf, out_idx_dev, out_dist_dev, true, (hipStream_t)hip_stream);
+}
+extern "C" int32_t nnd_searcher_query_rerank_device(nnd_searcher_t s, const float *queries_dev, int64_t nq, int32_t k, int32_t search_k,
+                                                    float epsilon, int32_t *out_idx_dev, float *out_dist_dev, void *hip_stream) {
+    if (!s) return no_searcher("nnd_searcher_query_rerank_device");
+    q_form qf;
+    if (query_args(s, "nnd_searcher_query_rerank_device", NND_QUERY_RERANK, k, &search_k, nullptr, false, nullptr, nq, &qf)) return 1;
+    if (device_args(s, "nnd_searcher_query_rerank_device", queries_dev, nq, out_idx_dev, out_dist_dev)) return 1;
+    return searcher_run(s, queries_dev, nq, search_k, k, epsilon, qf, out_idx_dev, out_dist_dev, true, (hipStream_t)hip_stream);
 }
 extern "C" int32_t nnd_searcher_query_tagged_device(nnd_searcher_t s, int32_t form, const float *queries_dev, int64_t nq, int32_t k, int32_t search_k,
                                                     float epsilon, const uint64_t *masks_dev, int32_t *out_idx_dev, float *out_dist_dev, void *hip_stream) {
-    if (!s) { snprintf(g_serr, sizeof(g_serr), "nnd_searcher_query_tagged_device: null searcher"); return 1; }
+    if (!s) return no_searcher("nnd_searcher_query_tagged_device");
     q_form qf;
-    if (tagged_args(s, "nnd_searcher_query_tagged_device", form, k, &search_k, masks_dev, nq, &qf)) return 1;
+    if (query_args(s, "nnd_searcher_query_tagged_device", form, k, &search_k, "take NND_QUERY_RERANK", true, masks_dev, nq, &qf)) return 1;
     if (device_args(s, "nnd_searcher_query_tagged_device", queries_dev, nq, out_idx_dev, out_dist_dev)) return 1;
     return searcher_run(s, queries_dev, nq, search_k, k, epsilon, qf, out_idx_dev, out_dist_dev, true, (hipStream_t)hip_stream, masks_dev);
+}
+
+extern "C" int64_t nnd_searcher_last_spilled(nnd_searcher_t s) { return s ? s->last_spilled : -1; }
+extern "C" int32_t nnd_searcher_set_tier(nnd_searcher_t s, int32_t tier) {
+    if (!s) { snprintf(g_serr, sizeof(g_serr), "nnd_searcher_set_tier: null searcher"); return 1; }
+    if (tier != 0 && tier != 1) { s->set_error("nnd_searcher_set_tier: tier must be 0 (automatic) or 1 (global-memory tier for every query)"); return 1; }
+    s->force_big = tier == 1;
+    return 0;
 }

@@ -2,13 +2,13 @@
 
 One allow set for all queries of a call, in the ORIGINAL row numbering: a 1-D boolean mask of n rows or a 1-D integer array of
 row ids, numpy or a tensor on the index's device.  Two paths: ``walk`` -- the graph walk with the rule "a vertex enters the
-result list only if it is allowed" (csrc/query.hip, the FL instances; the allow bitset is built on the device by
+result list only if it is allowed" (csrc/query.hip, k_query's Q_FILT_ALLOW instances; the allow bitset is built on the device by
 ``nnd_searcher_set_filter*``), and ``exact`` -- the allowed rows gathered into a compact copy that ``exact_knn`` searches.
 ``auto`` takes the exact path for at most ``FILTER_EXACT_MAX_ROWS`` allowed rows.
 
 Per-query filters (DESIGN.md "Per-query filters"): ``index.set_row_tags(tags)`` and ``query(..., query_tags=masks)`` -- 64 tag bits
-per row, a mask word per query, row r allowed for query i iff ``tags[r] & masks[i] != 0``.  ``walk``: the TG instances of
-csrc/query.hip on the searcher's own copy of the tag words; ``exact``: the masked scan of csrc/exact.hip over all rows;
+per row, a mask word per query, row r allowed for query i iff ``tags[r] & masks[i] != 0``.  ``walk``: k_query's Q_FILT_TAGS instances
+(csrc/query.hip) on the searcher's own copy of the tag words; ``exact``: the masked scan of csrc/exact.hip over all rows;
 ``auto``: per query, by the number of rows its mask allows (``tag_auto_paths``).
 """
 from collections import namedtuple

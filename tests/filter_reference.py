@@ -1,4 +1,4 @@
-"""The filtered walk (csrc/query.hip, the FL instances) as a step-exact model: tests/search_reference.py with one rule added --
+"""The filtered walk (csrc/query.hip, k_query's Q_FILT_ALLOW instances) as a step-exact model: tests/search_reference.py with one rule added --
 a vertex enters the walk's result list only if it is allowed.  Everything else is the unfiltered walk: the descent, the seeds,
 the visited set, every accepted candidate pushed to the frontier, the bound taken from the (allowed-only) result list and +inf
 while that list is short, the stop rule.  Test infrastructure.

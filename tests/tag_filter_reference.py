@@ -1,4 +1,4 @@
-"""The tagged walk (csrc/query.hip, the TG instances) as a step-exact model: tests/filter_reference.py with a different allow array
+"""The tagged walk (csrc/query.hip, k_query's Q_FILT_TAGS instances) as a step-exact model: tests/filter_reference.py with a different allow array
 per query -- ``allowed_i = (tags & masks[i]) != 0``.  Every query keeps its place in the batch: the kernel's seed for a query
 (ties in the tree descent, the random start vertices) is keyed by the query's number.  Test infrastructure.
 

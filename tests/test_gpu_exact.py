@@ -48,8 +48,8 @@ SAMPLE_257 = np.sort(np.random.RandomState(5).choice(3000, 257, replace=False)).
 
 @pytest.mark.parametrize("sample", [False, True], ids=["all", "257rows"])
 @pytest.mark.parametrize("k", [1, 10, 33, 64, 65, 100, 256])
-@pytest.mark.parametrize("metric", ["euclidean", "cosine"])
-@pytest.mark.parametrize("d", [7, 24, 130])
+@pytest.mark.parametrize("metric", ["euclidean", "cosine", "correlation"])
+@pytest.mark.parametrize("d", [7, 24, 40, 130])
 def test_rows_mode_tile_edges(d, metric, k, sample):
     x, b_def, b_f64 = _edge_set(d, metric)
     rows = SAMPLE_257 if sample else None
@@ -81,7 +81,7 @@ def _named_data(metric):
     return x
 
 
-@pytest.mark.parametrize("k", [10, 33])
+@pytest.mark.parametrize("k", [10, 33, 65])
 @pytest.mark.parametrize("metric", NAMES)
 def test_all_eight_names(metric, k):
     x = _named_data(metric)

@@ -1,4 +1,4 @@
-"""Filtered queries on the GPU: the FL instances of csrc/query.hip against the filtered step-exact model
+"""Filtered queries on the GPU: the Q_FILT_ALLOW instances of k_query (csrc/query.hip) against the filtered step-exact model
 (tests/filter_reference.py) through _capi.Searcher, the kernel that builds the allow bitset, and ``NNDescent.query(filter=...)``
 with its walk, exact and auto paths.
 
@@ -173,9 +173,9 @@ def _bool_case(metric="dice", n=1500, d=133, nq=30):
 
 
 @pytest.mark.parametrize("tier", TIERS)
-@pytest.mark.parametrize("k", [10, 100])
+@pytest.mark.parametrize("k", [10, 100, 129])
 def test_boolean_family_walk(k, tier):
-    """k_query_bool_filtered (dice, 1500 x 133).  The family is full of exact ties, which a step-exact model leaves to the weak
+    """k_query's boolean form under an allow set (dice, 1500 x 133; k = 10 / 100 / 129: one, two and four result entries per lane).  The family is full of exact ties, which a step-exact model leaves to the weak
     checks query after query, so the rule is checked where it has one answer: with a bound that never closes (epsilon 1e6) the
     walk visits the whole connected graph, and then the returned distances ARE the k smallest over the allowed rows, bit for
     bit (the ids among equal distances are the walk's choice).  With the usual epsilon: every id allowed, rows sorted and

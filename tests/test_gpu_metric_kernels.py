@@ -14,7 +14,7 @@ up to 16; the padded max_candidates mcp is 16 / 32 / 64 / 128 (the same function
   finalize.hip nnd_launch_finalize: k > 64 -> k_finalize_wide<true>; else k_finalize<M> (float4 loads when d % 4 == 0,
                                  scalar loads otherwise)
   prune.hip:                     k > 64 -> k_diversify_rows_wide / k_diversify_csr_wide (AWARE for degree_aware)
-  query.hip:                     query k <= 64 -> KU 1, <= 128 -> KU 2, else KU 4; set_tier(1): the global-memory tier
+  query.hip (k_query):           query k <= 64 -> KU 1, <= 128 -> KU 2, else KU 4; set_tier(1): the global-memory tier
 """
 import numpy as np
 import pytest

@@ -1,4 +1,4 @@
-"""The query kernel's float walk with the rerank epilogue (metric code 6, csrc/query.hip k_query<*, *, false, true>) against its
+"""The query kernel's float walk with the rerank epilogue (metric code 6, csrc/query.hip k_query<*, *, Q_FORM_RERANK, *>) against its
 step-exact model (tests/proxy_reference.py), through _capi.Searcher.query_rerank directly: no index build.  For every query
 the model does not flag, the ids are the model's and every distance is -<q, x> of its id within the float32 dot-product
 radius (bit for bit on the lattice); flagged queries keep the weak checks.  Every case runs on the LDS tier and on the

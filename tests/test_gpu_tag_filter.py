@@ -1,4 +1,4 @@
-"""Per-query filters on the GPU: the TG instances of csrc/query.hip against the tagged step-exact model
+"""Per-query filters on the GPU: the Q_FILT_TAGS instances of k_query (csrc/query.hip) against the tagged step-exact model
 (tests/tag_filter_reference.py), the masked instances of csrc/exact.hip against numpy float64 brute force among the allowed
 rows, the count kernel, and ``NNDescent.set_row_tags`` / ``query(query_tags=...)`` with its walk, exact and auto paths."""
 import types
@@ -94,9 +94,10 @@ def test_proxy_inner_product_rerank(which):
 
 
 @pytest.mark.parametrize("tier", TIERS)
-@pytest.mark.parametrize("k", [10, 100])
+@pytest.mark.parametrize("k", [10, 100, 129])
 def test_boolean_family_walk(k, tier):
-    """k_query_bool_tagged (dice, 1500 x 133), as the single-set test: with a bound that never closes the walk visits the whole
+    """k_query's boolean form under query masks (dice, 1500 x 133; k = 10 / 100 / 129: one, two and four result entries per lane), as
+    the single-set test: with a bound that never closes the walk visits the whole
     connected graph, and the returned distances are the k smallest over the rows the query's own mask allows, bit for bit."""
     case = _bool_case()
     n = case.data.shape[0]
@@ -199,8 +200,8 @@ def _alt64(metric, x, q):
     a, b = q.astype(np.float64), x.astype(np.float64)
     if metric in ("sqeuclidean", "euclidean"):
         return np.stack([((b - row) ** 2).sum(1) for row in a])
-    if metric == "cosine":
-        return np.stack([XU.alt_pairs("cosine", row[None, :], b[None, :, :])[0] for row in a])
+    if metric in ("cosine", "correlation"):
+        return np.stack([XU.alt_pairs(metric, row[None, :], b[None, :, :])[0] for row in a])
     return BU.dist(metric, q, x)
 
 
@@ -236,9 +237,15 @@ def _compare(label, got, want):
 
 
 @pytest.mark.parametrize("metric,d,k,nq", [("sqeuclidean", 24, 5, 100), ("sqeuclidean", 130, 70, 200), ("cosine", 130, 5, 200),
-                                           ("cosine", 24, 70, 100), ("dice", 130, 70, 100), ("dice", 24, 5, 200)])
+                                           ("cosine", 24, 70, 100), ("dice", 130, 70, 100), ("dice", 24, 5, 200),
+                                           # the rest of k_exact_scan's masked instances: every row width (d = 24 / 40 / 130: 32, 64 and
+                                           # 128 floats staged per chunk) x every family (correlation: the codes 2..5) x both list widths
+                                           ("dice", 24, 70, 100), ("dice", 130, 5, 100), ("sqeuclidean", 40, 5, 100), ("cosine", 40, 70, 100),
+                                           ("dice", 40, 5, 100), ("dice", 40, 70, 100), ("correlation", 24, 5, 100), ("correlation", 24, 70, 100),
+                                           ("correlation", 40, 5, 100), ("correlation", 40, 70, 100), ("correlation", 130, 5, 100),
+                                           ("correlation", 130, 70, 100)])
 def test_masked_exact_scan(metric, d, k, nq):
-    """n = 3000; d = 24 and 130 (more than one K chunk); k = 5 and 70 (the WIDE lists); 100 and 200 queries (no multiple of 64).
+    """n = 3000; d = 24, 40 and 130 (more than one K chunk); k = 5 and 70 (the WIDE lists); 100 and 200 queries (no multiple of 64).
     A tag no row has, a tag on exactly 3 rows (fewer than k: padded), rows with tag word 0, queries with mask 0, bit 63."""
     x, q = _exact_rows(metric, d, 3)
     q = q[:nq]
