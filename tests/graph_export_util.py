@@ -5,15 +5,17 @@ import scipy.sparse as sp
 
 def model_csr(ids, vals, n, mode="distance", symmetric=False, drop_self=False):
     """The canonical CSR matrix of the k-lists ``ids`` / ``vals`` (m, k) with ``n`` columns: ``coo_array(...).tocsr()`` of the
-    places whose id is not -1 (a row never holds an id twice, so nothing is summed); ``symmetric``: the union with the
-    transpose, an entry present on both sides holding the smaller float; ``connectivity`` stores 1.0.  Returns
-    (indptr int64, indices int32, data float32)."""
+    places whose id names a column -- an id outside [0, n) is an empty place like -1 -- (a row never holds an id twice, so
+    nothing is summed); ``symmetric``: the union with the transpose, an entry present on both sides holding the smaller float,
+    and of two equal floats of different bits (+0.0 and -0.0) the one with the smaller bit pattern: what the kernels' sort by
+    (column, value bits) followed by ``b < a ? b : a`` on the neighbours keeps; ``connectivity`` stores 1.0.  No NaN.
+    Returns (indptr int64, indices int32, data float32)."""
     ids = np.asarray(ids).astype(np.int64)
     vals = np.asarray(vals, dtype=np.float32)
     m, k = ids.shape
     rows = np.repeat(np.arange(m, dtype=np.int64), k)
     cols, data = ids.ravel(), vals.ravel()
-    keep = cols >= 0
+    keep = (cols >= 0) & (cols < n)
     if drop_self:
         keep &= cols != rows
     rows, cols, data = rows[keep], cols[keep], data[keep]
@@ -21,8 +23,12 @@ def model_csr(ids, vals, n, mode="distance", symmetric=False, drop_self=False):
         assert m == n
         off = rows != cols  # the diagonal is its own reverse
         rows, cols, data = np.concatenate([rows, cols[off]]), np.concatenate([cols, rows[off]]), np.concatenate([data, data[off]])
-        # explicit min-union: sort by (row, column, value) and keep the first entry of every (row, column)
-        order = np.lexsort((data, cols, rows))
+        # explicit min-union: sort by (row, column, value, value bits) and keep the first entry of every (row, column)
+        # (the float order taken from the bits -- sign and magnitude, +0.0 and -0.0 equal -- so that a subnormal compares as the
+        # device compares it even in a process whose host arithmetic flushes subnormals: a -ffast-math library, once loaded, sets that)
+        bits = data.view(np.uint32)
+        magnitude = (bits & np.uint32(0x7FFFFFFF)).astype(np.int64)
+        order = np.lexsort((bits, np.where(bits >> np.uint32(31), -magnitude, magnitude), cols, rows))
         rows, cols, data = rows[order], cols[order], data[order]
         first = np.ones(rows.shape[0], bool)
         first[1:] = (rows[1:] != rows[:-1]) | (cols[1:] != cols[:-1])

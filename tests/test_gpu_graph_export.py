@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 from pynndescent_amd import _capi
+from tests.graph_export_cases import merge_instance, stretch_lengths
 from tests.graph_export_util import assert_same_csr, model_csr, random_klists, symmetric_values
 
 pytestmark = pytest.mark.gpu
@@ -72,7 +73,7 @@ def test_symmetric_hub_row_takes_the_long_path_and_is_deterministic():
     want = model_csr(ids, vals, 600, symmetric=True)
     assert want[0][1] - want[0][0] > 256  # row 0 of the union: everybody
     first = _capi.graph_csr(ids, vals, 600, symmetric=True, want_long_rows=True)
-    assert first[3] >= 1
+    assert first[3] == sum(merge_instance(int(v)) == "long" for v in stretch_lengths(ids, 600, 15)) == 1
     assert_same_csr(first[:3], want)
     second = _capi.graph_csr(ids, vals, 600, symmetric=True, want_long_rows=True)  # (the scatter order may differ between runs)
     for a, b in zip(first[:3], second[:3]):
