@@ -280,9 +280,8 @@ __global__ __launch_bounds__(256, METRIC == 0 ? 6 : 4) void k_finalize16(const f
 }
 
 // 64 < k <= NND_WIDE_K: one wave per row, ids / exact distances through LDS, four neighbours at a time (16 lanes each), ranks by
-// counting over the LDS copy.  Same arithmetic as k_finalize.  XM: the instance for the metrics of codes 2..6 (the
-// sqeuclidean / cosine instance does not carry their registers).
-// The body is shared with k_finalize_wide_bool, the boolean family's instance (FAM = NND_CODES_BOOL).
+// counting over the LDS copy.  Same arithmetic as k_finalize.  FAM: NND_CODES_01, NND_CODES_ANY for the metrics of codes 2..6 (the
+// sqeuclidean / cosine instance does not carry their registers) or NND_CODES_BOOL (metric.h nnd_metric_family).
 template <int FAM>
 __device__ __forceinline__ void fin_wide_body(const float *__restrict__ x, int d, int64_t lo, int64_t n, int k, int ks, int metric,
                                               const uint32_t *__restrict__ knn_e, int32_t *__restrict__ out_idx,
@@ -324,22 +323,17 @@ __device__ __forceinline__ void fin_wide_body(const float *__restrict__ x, int d
         out_dist[(v - lo) * k + r] = sdist[w][j];
     }
 }
-template <bool XM>
+template <int FAM>
 __global__ __launch_bounds__(256) void k_finalize_wide(const float *__restrict__ x, int d, int64_t lo, int64_t n, int k, int ks, int metric,
                                                        const uint32_t *__restrict__ knn_e, int32_t *__restrict__ out_idx,
                                                        float *__restrict__ out_dist) {
-    fin_wide_body<XM ? NND_CODES_ANY : NND_CODES_01>(x, d, lo, n, k, ks, metric, knn_e, out_idx, out_dist);
-}
-__global__ __launch_bounds__(256) void k_finalize_wide_bool(const float *__restrict__ x, int d, int64_t lo, int64_t n, int k, int ks, int metric,
-                                                            const uint32_t *__restrict__ knn_e, int32_t *__restrict__ out_idx,
-                                                            float *__restrict__ out_dist) {
-    fin_wide_body<NND_CODES_BOOL>(x, d, lo, n, k, ks, metric, knn_e, out_idx, out_dist);
+    fin_wide_body<FAM>(x, d, lo, n, k, ks, metric, knn_e, out_idx, out_dist);
 }
 
 int nnd_launch_finalize(nnd_ctx *ctx, int32_t *out_idx_dev, float *out_dist_dev) {
     unsigned grid = (unsigned)((ctx->own_hi - ctx->own_lo + 3) / 4);
     if (ctx->k > 64) {
-        hipLaunchKernelGGL(ctx->p.metric >= NND_BOOL_FIRST ? k_finalize_wide_bool : (ctx->p.metric >= 2 ? k_finalize_wide<true> : k_finalize_wide<false>), dim3(grid), dim3(256), 0, ctx->stream, ctx->x_orig, ctx->d, ctx->own_lo, ctx->own_hi, ctx->k, ctx->ks,
+        hipLaunchKernelGGL(nnd_metric_bool(ctx->p.metric) ? k_finalize_wide<NND_CODES_BOOL> : (ctx->p.metric >= 2 ? k_finalize_wide<NND_CODES_ANY> : k_finalize_wide<NND_CODES_01>), dim3(grid), dim3(256), 0, ctx->stream, ctx->x_orig, ctx->d, ctx->own_lo, ctx->own_hi, ctx->k, ctx->ks,
                            ctx->p.metric, ctx->knn_e, out_idx_dev, out_dist_dev);
         NND_HIP_CHECK(hipGetLastError());
         return 0;
@@ -379,7 +373,7 @@ int nnd_launch_finalize(nnd_ctx *ctx, int32_t *out_idx_dev, float *out_dist_dev)
 // ---- debug / parity: the MFMA Gram tile on arbitrary row lists (tests/test_gpu_kernels.py) ----
 // one wave per 16x16 output tile; operands come straight from global memory with the same K mapping
 // as gram.h (chunk c of a row feeds lane group c & 3).
-// (the body of k_pairwise and of k_pairwise_bool, the instance of the boolean family: metric.h nnd_metric_family)
+// (the body of k_pairwise; FAM: NND_CODES_ANY, or NND_CODES_BOOL for the boolean family: metric.h nnd_metric_family)
 template <int FAM>
 __device__ __forceinline__ void fin_pairwise_body(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
                                                  int metric, const int32_t *__restrict__ rows_a, int na,
@@ -407,20 +401,16 @@ __device__ __forceinline__ void fin_pairwise_body(const float *__restrict__ xp, 
         if (row < na && col < nb) out[(int64_t)row * nb + col] = nnd_gram_to_dist<FAM>(metric, acc[r], idr >= 0 ? nrm[idr] : 0.0f, nbv);
     }
 }
+template <int FAM>
 __global__ __launch_bounds__(64) void k_pairwise(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
                                                  int metric, const int32_t *__restrict__ rows_a, int na,
                                                  const int32_t *__restrict__ rows_b, int nb, float *__restrict__ out) {
-    fin_pairwise_body<NND_CODES_ANY>(xp, dp, nrm, metric, rows_a, na, rows_b, nb, out);
-}
-__global__ __launch_bounds__(64) void k_pairwise_bool(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
-                                                 int metric, const int32_t *__restrict__ rows_a, int na,
-                                                 const int32_t *__restrict__ rows_b, int nb, float *__restrict__ out) {
-    fin_pairwise_body<NND_CODES_BOOL>(xp, dp, nrm, metric, rows_a, na, rows_b, nb, out);
+    fin_pairwise_body<FAM>(xp, dp, nrm, metric, rows_a, na, rows_b, nb, out);
 }
 
 int nnd_launch_pairwise(nnd_ctx *ctx, const int32_t *rows_a_dev, int na, const int32_t *rows_b_dev, int nb, float *out_dev) {
     dim3 grid((nb + 15) / 16, (na + 15) / 16);
-    hipLaunchKernelGGL(nnd_metric_bool(ctx->p.metric) ? k_pairwise_bool : k_pairwise, grid, dim3(64), 0, ctx->stream, ctx->xp, ctx->dp, ctx->nrm, nnd_kmetric(ctx), rows_a_dev, na,
+    hipLaunchKernelGGL(nnd_metric_bool(ctx->p.metric) ? k_pairwise<NND_CODES_BOOL> : k_pairwise<NND_CODES_ANY>, grid, dim3(64), 0, ctx->stream, ctx->xp, ctx->dp, ctx->nrm, nnd_kmetric(ctx), rows_a_dev, na,
                        rows_b_dev, nb, out_dev);
     NND_HIP_CHECK(hipGetLastError());
     return 0;

@@ -14,12 +14,14 @@
 // thread, pynndescent_.py:154-185).  Trees are processed one launch after another, so thresholds
 // tighten between trees exactly like the reference's leaf blocks tighten them (pynndescent_.py:137-152).
 #include <type_traits>
+#include <utility>
 
 #include "common.h"
 #include "metric.h"
 #include "gram.h"
 #include "merge.h"
 #include "state.h"
+#include "leaf_plan.h"
 
 #ifndef NND_LEAF_QW_OCC
 #define NND_LEAF_QW_OCC 6  // waves per SIMD of the 4-wave class: 80 VGPRs, no spills (7: 72 VGPRs with 7 spilled -- 0.1 GB of scratch traffic per tree and 2-5 % slower)
@@ -45,7 +47,7 @@ struct leaf_cfg {
 };
 
 // QW (host: k <= 16 and the whole distance block in LDS): quarter-wave merges, four rows per wave (merge.h)
-// (the body of k_leaf_join and of k_leaf_join_bool, the instance of the boolean family: metric.h nnd_metric_family)
+// (the body of k_leaf_join; FAM: NND_CODES_ANY, or NND_CODES_BOOL for the boolean family: metric.h nnd_metric_family)
 template <int FAM, int NT, int NW, int DC, bool QW = false>
 __device__ __forceinline__ void lf_leaf_join_body(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
                                                        int metric, const int32_t *__restrict__ perm,
@@ -374,7 +376,7 @@ __device__ __forceinline__ void lf_leaf_join_body(const float *__restrict__ xp, 
         nnd_count(counters, CNT_MFMA, (long long)(C::FULLD ? nt * (nt + 1) / 2 : nt * nt) * (dp >> 2));
     }
 }
-template <int NT, int NW, int DC, bool QW = false>
+template <int FAM, int NT, int NW, int DC, bool QW = false>
 __global__ __launch_bounds__(NW * 64, (NT <= 5 && NW == 8) ? 8 : (QW && NT <= 5 && NW == 4) ? NND_LEAF_QW_OCC : 1) void k_leaf_join(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
                                                        int metric, const int32_t *__restrict__ perm,
                                                        const int32_t *__restrict__ wl_start,
@@ -382,17 +384,7 @@ __global__ __launch_bounds__(NW * 64, (NT <= 5 && NW == 8) ? 8 : (QW && NT <= 5 
                                                        int64_t n_leaves, int k, int ks, uint32_t *__restrict__ knn_e,
                                                        float *__restrict__ knn_d, float *__restrict__ th,
                                                        long long *__restrict__ counters, int m_lo) {
-    lf_leaf_join_body<NND_CODES_ANY, NT, NW, DC, QW>(xp, dp, nrm, metric, perm, wl_start, wl_len, leaf0, n_leaves, k, ks, knn_e, knn_d, th, counters, m_lo);
-}
-template <int NT, int NW, int DC, bool QW = false>
-__global__ __launch_bounds__(NW * 64, (NT <= 5 && NW == 8) ? 8 : (QW && NT <= 5 && NW == 4) ? NND_LEAF_QW_OCC : 1) void k_leaf_join_bool(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
-                                                       int metric, const int32_t *__restrict__ perm,
-                                                       const int32_t *__restrict__ wl_start,
-                                                       const int32_t *__restrict__ wl_len, int64_t leaf0,
-                                                       int64_t n_leaves, int k, int ks, uint32_t *__restrict__ knn_e,
-                                                       float *__restrict__ knn_d, float *__restrict__ th,
-                                                       long long *__restrict__ counters, int m_lo) {
-    lf_leaf_join_body<NND_CODES_BOOL, NT, NW, DC, QW>(xp, dp, nrm, metric, perm, wl_start, wl_len, leaf0, n_leaves, k, ks, knn_e, knn_d, th, counters, m_lo);
+    lf_leaf_join_body<FAM, NT, NW, DC, QW>(xp, dp, nrm, metric, perm, wl_start, wl_len, leaf0, n_leaves, k, ks, knn_e, knn_d, th, counters, m_lo);
 }
 
 // Leaves of more than 96 points (k = 30, the reference's default, gives leaf_size 150).  The one-workgroup-per-leaf kernel
@@ -404,7 +396,7 @@ __global__ __launch_bounds__(NW * 64, (NT <= 5 && NW == 8) ? 8 : (QW && NT <= 5 
 // same share of the merges; the leaf's Gram block is computed twice (no symmetry across workgroups) and its rows are
 // staged once per block (the reason for 64-row blocks: 32-row blocks staged every leaf five times).  Rows of one leaf
 // are owned by exactly one workgroup: no atomics.
-// (the body of k_leaf_join_rb and of k_leaf_join_rb_bool, the instance of the boolean family: metric.h nnd_metric_family)
+// (the body of k_leaf_join_rb; FAM as above)
 template <int FAM, int NT, int NW = 8, bool WIDE = false>
 __device__ __forceinline__ void lf_leaf_join_rb_body(const float *__restrict__ xp, int dp, const float *__restrict__ nrm, int metric,
                                                          const int32_t *__restrict__ perm, const int32_t *__restrict__ wl_start,
@@ -556,21 +548,14 @@ __device__ __forceinline__ void lf_leaf_join_rb_body(const float *__restrict__ x
         nnd_count(counters, CNT_MFMA, (long long)trows * nt * (dp >> 2));
     }
 }
-template <int NT, int NW = 8, bool WIDE = false>
+// (the trailing m_lo is not read -- a row-block launch takes every leaf: one argument list for the three kinds, leaf_kernel below)
+template <int FAM, int NT, int NW = 8, bool WIDE = false>
 __global__ __launch_bounds__(NW * 64, 2) void k_leaf_join_rb(const float *__restrict__ xp, int dp, const float *__restrict__ nrm, int metric,
                                                          const int32_t *__restrict__ perm, const int32_t *__restrict__ wl_start,
                                                          const int32_t *__restrict__ wl_len, int64_t leaf0, int64_t n_leaves, int k, int ks,
                                                          uint32_t *__restrict__ knn_e, float *__restrict__ knn_d, float *__restrict__ th,
-                                                         long long *__restrict__ counters) {
-    lf_leaf_join_rb_body<NND_CODES_ANY, NT, NW, WIDE>(xp, dp, nrm, metric, perm, wl_start, wl_len, leaf0, n_leaves, k, ks, knn_e, knn_d, th, counters);
-}
-template <int NT, int NW = 8, bool WIDE = false>
-__global__ __launch_bounds__(NW * 64, 2) void k_leaf_join_rb_bool(const float *__restrict__ xp, int dp, const float *__restrict__ nrm, int metric,
-                                                         const int32_t *__restrict__ perm, const int32_t *__restrict__ wl_start,
-                                                         const int32_t *__restrict__ wl_len, int64_t leaf0, int64_t n_leaves, int k, int ks,
-                                                         uint32_t *__restrict__ knn_e, float *__restrict__ knn_d, float *__restrict__ th,
-                                                         long long *__restrict__ counters) {
-    lf_leaf_join_rb_body<NND_CODES_BOOL, NT, NW, WIDE>(xp, dp, nrm, metric, perm, wl_start, wl_len, leaf0, n_leaves, k, ks, knn_e, knn_d, th, counters);
+                                                         long long *__restrict__ counters, int) {
+    lf_leaf_join_rb_body<FAM, NT, NW, WIDE>(xp, dp, nrm, metric, perm, wl_start, wl_len, leaf0, n_leaves, k, ks, knn_e, knn_d, th, counters);
 }
 
 // Rows of 17 .. 32 neighbours (k = 30, the reference's default, with leaves of up to 150 points), round 6.  k_leaf_join_rb above
@@ -588,7 +573,7 @@ __global__ __launch_bounds__(NW * 64, 2) void k_leaf_join_rb_bool(const float *_
 #ifndef NND_SYM_OCC_L
 #define NND_SYM_OCC_L 3
 #endif
-// (the body of k_leaf_join_sym and of k_leaf_join_sym_bool, the instance of the boolean family: metric.h nnd_metric_family)
+// (the body of k_leaf_join_sym; FAM as above)
 template <int FAM, int NT, int NW = 8>
 __device__ __forceinline__ void lf_leaf_join_sym_body(const float *__restrict__ xp, int dp, const float *__restrict__ nrm, int metric,
                                                           const int32_t *__restrict__ perm, const int32_t *__restrict__ wl_start,
@@ -737,26 +722,36 @@ __device__ __forceinline__ void lf_leaf_join_sym_body(const float *__restrict__ 
         nnd_count(counters, CNT_MFMA, (long long)(nt * (nt + 1) / 2) * (dp >> 2));
     }
 }
-template <int NT, int NW = 8>
+template <int FAM, int NT, int NW = 8>
 __global__ __launch_bounds__(NW * 64, NT <= 6 ? NND_SYM_OCC_S : NND_SYM_OCC_L) void k_leaf_join_sym(const float *__restrict__ xp, int dp, const float *__restrict__ nrm, int metric,
                                                           const int32_t *__restrict__ perm, const int32_t *__restrict__ wl_start,
                                                           const int32_t *__restrict__ wl_len, int64_t leaf0, int64_t n_leaves, int k, int ks,
                                                           uint32_t *__restrict__ knn_e, float *__restrict__ knn_d, float *__restrict__ th,
                                                           long long *__restrict__ counters, int m_lo) {
-    lf_leaf_join_sym_body<NND_CODES_ANY, NT, NW>(xp, dp, nrm, metric, perm, wl_start, wl_len, leaf0, n_leaves, k, ks, knn_e, knn_d, th, counters, m_lo);
-}
-template <int NT, int NW = 8>
-__global__ __launch_bounds__(NW * 64, NT <= 6 ? NND_SYM_OCC_S : NND_SYM_OCC_L) void k_leaf_join_sym_bool(const float *__restrict__ xp, int dp, const float *__restrict__ nrm, int metric,
-                                                          const int32_t *__restrict__ perm, const int32_t *__restrict__ wl_start,
-                                                          const int32_t *__restrict__ wl_len, int64_t leaf0, int64_t n_leaves, int k, int ks,
-                                                          uint32_t *__restrict__ knn_e, float *__restrict__ knn_d, float *__restrict__ th,
-                                                          long long *__restrict__ counters, int m_lo) {
-    lf_leaf_join_sym_body<NND_CODES_BOOL, NT, NW>(xp, dp, nrm, metric, perm, wl_start, wl_len, leaf0, n_leaves, k, ks, knn_e, knn_d, th, counters, m_lo);
+    lf_leaf_join_sym_body<FAM, NT, NW>(xp, dp, nrm, metric, perm, wl_start, wl_len, leaf0, n_leaves, k, ks, knn_e, knn_d, th, counters, m_lo);
 }
 
 // Work list: leaves longer than 256 points (possible only when max_depth cuts the recursion short,
 // rp_trees.py:2188) are cut into runs of <= 256 consecutive positions for seeding purposes.
 static constexpr int LEAF_MAX = 256;
+
+// Every instance, by [boolean family][form]: the kernels are instantiated from nnd_leaf_forms (leaf_plan.h) itself, so the table
+// cannot disagree with the plan about what a form is.
+using leaf_kernel_t = decltype(&k_leaf_join<NND_CODES_ANY, 4, 8, 64, true>);
+template <int FAM, int F>
+static constexpr leaf_kernel_t leaf_instance() {
+    constexpr nnd_leaf_form f = nnd_leaf_forms[F];
+    if constexpr (f.kind == NND_LEAF_SYM) return k_leaf_join_sym<FAM, f.nt, f.nw>;
+    else if constexpr (f.kind == NND_LEAF_RB) return k_leaf_join_rb<FAM, f.nt, f.nw, f.flag>;
+    else return k_leaf_join<FAM, f.nt, f.nw, 64, f.flag>;
+}
+template <int... F>
+static leaf_kernel_t leaf_kernel_of(bool bm, int form, std::integer_sequence<int, F...>) {
+    static const leaf_kernel_t table[2][NND_LEAF_FORMS] = {{leaf_instance<NND_CODES_ANY, F>()...}, {leaf_instance<NND_CODES_BOOL, F>()...}};
+    return table[bm][form];
+}
+static leaf_kernel_t leaf_kernel(bool bm, int form) { return leaf_kernel_of(bm, form, std::make_integer_sequence<int, NND_LEAF_FORMS>{}); }
+static_assert(NND_MAX_K == 64 && LEAF_MAX == 256, "the columns and the last row of nnd_leaf_table");
 
 // Seed the k-lists from leaves given as a work list: members of leaf i are members[wl_start[i] .. + wl_len[i]); the leaves
 // of round r are [tb[r], tb[r + 1]).  Inside a round no point may belong to two leaves -- the workgroup of a leaf owns
@@ -765,63 +760,17 @@ static int run_leaf_rounds(nnd_ctx *ctx, const int32_t *perm, const int32_t *d_w
                            const std::vector<int64_t> &tb, int maxlen) {
     if (nnd_zero_counters(ctx)) return 1;
     const bool bm = nnd_metric_bool(ctx->p.metric);  // the boolean family's instances (metric.h NND_CODES_BOOL)
+    const nnd_leaf_cell &plan = nnd_leaf_plan(ctx->k, maxlen);
     const int T = (int)tb.size() - 1;
     for (int t = 0; t < T; t++) {
         int64_t cnt = tb[t + 1] - tb[t];
         if (cnt <= 0) continue;
-        dim3 grid((unsigned)cnt);
-#define LEAF_ARGS ctx->xp, ctx->dp, ctx->nrm, nnd_kmetric(ctx), perm, d_ws, d_wl, tb[t], tb[t + 1], ctx->k, ctx->ks, \
-                  ctx->knn_e, ctx->knn_d, ctx->th, ctx->counters
-        const bool qw = ctx->k <= 16;
-        if (ctx->k > NND_MAX_K) {  // wide rows: the row-block kernel with LDS merges, whatever the leaf size
-            if (maxlen <= 128)
-                hipLaunchKernelGGL((bm ? k_leaf_join_rb_bool<8, 8, true> : k_leaf_join_rb<8, 8, true>), dim3((unsigned)cnt, 2), dim3(512), 0, ctx->stream, LEAF_ARGS);
-            else if (maxlen <= 160)
-                hipLaunchKernelGGL((bm ? k_leaf_join_rb_bool<10, 8, true> : k_leaf_join_rb<10, 8, true>), dim3((unsigned)cnt, 3), dim3(512), 0, ctx->stream, LEAF_ARGS);
-            else
-                hipLaunchKernelGGL((bm ? k_leaf_join_rb_bool<16, 8, true> : k_leaf_join_rb<16, 8, true>), dim3((unsigned)cnt, 4), dim3(512), 0, ctx->stream, LEAF_ARGS);
+        for (int i = 0; i < plan.n; i++) {
+            const nnd_leaf_form &f = nnd_leaf_forms[plan.launch[i].form];
+            hipLaunchKernelGGL(leaf_kernel(bm, plan.launch[i].form), dim3((unsigned)cnt, f.grid_y()), dim3(f.threads()), 0, ctx->stream, ctx->xp, ctx->dp,
+                               ctx->nrm, nnd_kmetric(ctx), perm, d_ws, d_wl, tb[t], tb[t + 1], ctx->k, ctx->ks, ctx->knn_e, ctx->knn_d, ctx->th,
+                               ctx->counters, plan.launch[i].m_lo);
         }
-#ifndef NND_LEAF_OLD_K32
-        else if (!qw && ctx->k <= 32 && maxlen <= 160) {  // k = 17 .. 32: one workgroup per leaf, two rows per wave (k_leaf_join_sym)
-            hipLaunchKernelGGL((bm ? k_leaf_join_sym_bool<6, 8> : k_leaf_join_sym<6, 8>), grid, dim3(512), 0, ctx->stream, LEAF_ARGS, 0);
-            if (maxlen > 96) hipLaunchKernelGGL((bm ? k_leaf_join_sym_bool<10, 8> : k_leaf_join_sym<10, 8>), grid, dim3(512), 0, ctx->stream, LEAF_ARGS, 96);
-        }
-#endif
-        else if (maxlen <= 64 && qw)
-            hipLaunchKernelGGL((bm ? k_leaf_join_bool<4, 8, 64, true> : k_leaf_join<4, 8, 64, true>), grid, dim3(512), 0, ctx->stream, LEAF_ARGS, 0);
-        else if (maxlen <= 64)
-            hipLaunchKernelGGL((bm ? k_leaf_join_bool<4, 8, 64> : k_leaf_join<4, 8, 64>), grid, dim3(512), 0, ctx->stream, LEAF_ARGS, 0);
-        else if (maxlen <= 80 && qw) {  // the default leaf_size (<= 75 points) with k <= 16
-            // Two size classes, two launches over the tree's leaf table (a workgroup whose leaf belongs to the other class
-            // leaves at once): leaves of <= 64 points -- 85 % of the leaves, 3/4 of the points -- get FOUR waves and 21 KB of LDS,
-            // so that 6 of them are in flight per CU instead of 4.  The kernel is bound by exposed latency, not by a pipe
-            // (profiles/r06_leaf_occupancy.log: 375 / 425 / 535 us per tree with 4 / 3 / 2 workgroups per CU).
-#ifdef NND_LEAF_ONE_CLASS
-            hipLaunchKernelGGL((bm ? k_leaf_join_bool<5, 8, 64, true> : k_leaf_join<5, 8, 64, true>), grid, dim3(512), 0, ctx->stream, LEAF_ARGS, 0);
-#else
-            hipLaunchKernelGGL((bm ? k_leaf_join_bool<4, 4, 64, true> : k_leaf_join<4, 4, 64, true>), grid, dim3(256), 0, ctx->stream, LEAF_ARGS, 0);
-#ifdef NND_LEAF_EMPTY_L  // timing experiment: what do the workgroups that leave at once cost?
-            hipLaunchKernelGGL((bm ? k_leaf_join_bool<5, 8, 64, true> : k_leaf_join<5, 8, 64, true>), grid, dim3(512), 0, ctx->stream, LEAF_ARGS, 1000);
-#elif defined(NND_LEAF_L_NW4)  // experiment: the large class with four waves too
-            hipLaunchKernelGGL((bm ? k_leaf_join_bool<5, 4, 64, true> : k_leaf_join<5, 4, 64, true>), grid, dim3(256), 0, ctx->stream, LEAF_ARGS, 64);
-#else
-            hipLaunchKernelGGL((bm ? k_leaf_join_bool<5, 8, 64, true> : k_leaf_join<5, 8, 64, true>), grid, dim3(512), 0, ctx->stream, LEAF_ARGS, 64);
-#endif
-#endif
-        }
-        else if (maxlen <= 80)
-            hipLaunchKernelGGL((bm ? k_leaf_join_bool<5, 8, 64> : k_leaf_join<5, 8, 64>), grid, dim3(512), 0, ctx->stream, LEAF_ARGS, 0);
-        else if (maxlen <= 96 && qw)
-            hipLaunchKernelGGL((bm ? k_leaf_join_bool<6, 8, 64, true> : k_leaf_join<6, 8, 64, true>), grid, dim3(512), 0, ctx->stream, LEAF_ARGS, 0);
-        else if (maxlen <= 96)
-            hipLaunchKernelGGL((bm ? k_leaf_join_bool<6, 8, 64> : k_leaf_join<6, 8, 64>), grid, dim3(512), 0, ctx->stream, LEAF_ARGS, 0);
-        else if (maxlen <= 128)  // larger leaves: a workgroup per block of 32 rows (k_leaf_join_rb)
-            hipLaunchKernelGGL((bm ? k_leaf_join_rb_bool<8, 8> : k_leaf_join_rb<8, 8>), dim3((unsigned)cnt, 2), dim3(512), 0, ctx->stream, LEAF_ARGS);
-        else if (maxlen <= 160)  // k = 30 (leaf_size 150)
-            hipLaunchKernelGGL((bm ? k_leaf_join_rb_bool<10, 8> : k_leaf_join_rb<10, 8>), dim3((unsigned)cnt, 3), dim3(512), 0, ctx->stream, LEAF_ARGS);
-        else
-            hipLaunchKernelGGL((bm ? k_leaf_join_rb_bool<16, 8> : k_leaf_join_rb<16, 8>), dim3((unsigned)cnt, 4), dim3(512), 0, ctx->stream, LEAF_ARGS);
-#undef LEAF_ARGS
     }
     NND_HIP_CHECK(hipGetLastError());
     if (nnd_read_counters(ctx)) return 1;

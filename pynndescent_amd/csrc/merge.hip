@@ -234,7 +234,7 @@ __device__ __forceinline__ void random_init_row(const float *__restrict__ xp, in
 // A wave screens 64 rows first, one row per lane: the lane counts the filled ones of its row's first k slots (wherever they sit in
 // the row; rows are ks = 16 m words, read 16 bytes at a time), and the wave then works through the rows that are not full.  After
 // leaf seeding that is next to none of them: a full row costs its 64 bytes and no wave of its own.
-// (the body of k_random_init and of k_random_init_bool, the instance of the boolean family: metric.h nnd_metric_family)
+// (the body of k_random_init<FAM, false>; FAM: NND_CODES_ANY, or NND_CODES_BOOL for the boolean family: metric.h nnd_metric_family)
 template <int FAM>
 __device__ __forceinline__ void mg_random_init_body(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
                                                      int metric, int64_t n, int64_t lo, int64_t hi, int k, int ks,
@@ -260,20 +260,8 @@ __device__ __forceinline__ void mg_random_init_body(const float *__restrict__ xp
         random_init_row<FAM>(xp, dp, nrm, metric, n, v, k, ks, knn_e, seed, pbuf, pdirty, pcap);
     }
 }
-__global__ __launch_bounds__(256) void k_random_init(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
-                                                     int metric, int64_t n, int64_t lo, int64_t hi, int k, int ks,
-                                                     const uint32_t *__restrict__ knn_e, uint32_t seed,
-                                                     uint64_t *__restrict__ pbuf, uint8_t *__restrict__ pdirty, int pcap) {
-    mg_random_init_body<NND_CODES_ANY>(xp, dp, nrm, metric, n, lo, hi, k, ks, knn_e, seed, pbuf, pdirty, pcap);
-}
-__global__ __launch_bounds__(256) void k_random_init_bool(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
-                                                     int metric, int64_t n, int64_t lo, int64_t hi, int k, int ks,
-                                                     const uint32_t *__restrict__ knn_e, uint32_t seed,
-                                                     uint64_t *__restrict__ pbuf, uint8_t *__restrict__ pdirty, int pcap) {
-    mg_random_init_body<NND_CODES_BOOL>(xp, dp, nrm, metric, n, lo, hi, k, ks, knn_e, seed, pbuf, pdirty, pcap);
-}
 // one wave per row (NND_FLAG_TEST_RANDOM_INIT_ROWWISE: the form the screening kernel is compared with)
-// (the body of k_random_init_rowwise and of k_random_init_rowwise_bool, the instance of the boolean family: metric.h nnd_metric_family)
+// (the body of k_random_init<FAM, true>)
 template <int FAM>
 __device__ __forceinline__ void mg_random_init_rowwise_body(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
                                                              int metric, int64_t n, int64_t lo, int64_t hi, int k, int ks,
@@ -283,25 +271,23 @@ __device__ __forceinline__ void mg_random_init_rowwise_body(const float *__restr
     if (v >= hi) return;
     random_init_row<FAM>(xp, dp, nrm, metric, n, v, k, ks, knn_e, seed, pbuf, pdirty, pcap);
 }
-__global__ __launch_bounds__(256) void k_random_init_rowwise(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
-                                                             int metric, int64_t n, int64_t lo, int64_t hi, int k, int ks,
-                                                             const uint32_t *__restrict__ knn_e, uint32_t seed,
-                                                             uint64_t *__restrict__ pbuf, uint8_t *__restrict__ pdirty, int pcap) {
-    mg_random_init_rowwise_body<NND_CODES_ANY>(xp, dp, nrm, metric, n, lo, hi, k, ks, knn_e, seed, pbuf, pdirty, pcap);
-}
-__global__ __launch_bounds__(256) void k_random_init_rowwise_bool(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
-                                                             int metric, int64_t n, int64_t lo, int64_t hi, int k, int ks,
-                                                             const uint32_t *__restrict__ knn_e, uint32_t seed,
-                                                             uint64_t *__restrict__ pbuf, uint8_t *__restrict__ pdirty, int pcap) {
-    mg_random_init_rowwise_body<NND_CODES_BOOL>(xp, dp, nrm, metric, n, lo, hi, k, ks, knn_e, seed, pbuf, pdirty, pcap);
+template <int FAM, bool ROWWISE>
+__global__ __launch_bounds__(256) void k_random_init(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
+                                                     int metric, int64_t n, int64_t lo, int64_t hi, int k, int ks,
+                                                     const uint32_t *__restrict__ knn_e, uint32_t seed,
+                                                     uint64_t *__restrict__ pbuf, uint8_t *__restrict__ pdirty, int pcap) {
+    if constexpr (ROWWISE) mg_random_init_rowwise_body<FAM>(xp, dp, nrm, metric, n, lo, hi, k, ks, knn_e, seed, pbuf, pdirty, pcap);
+    else mg_random_init_body<FAM>(xp, dp, nrm, metric, n, lo, hi, k, ks, knn_e, seed, pbuf, pdirty, pcap);
 }
 
 int nnd_launch_random_init(nnd_ctx *ctx) {
-    const bool rowwise = (ctx->p.flags & NND_FLAG_TEST_RANDOM_INIT_ROWWISE) != 0, bm = nnd_metric_bool(ctx->p.metric);
+    static const decltype(&k_random_init<NND_CODES_ANY, false>) table[2][2] = {{k_random_init<NND_CODES_ANY, false>, k_random_init<NND_CODES_ANY, true>},
+                                                                               {k_random_init<NND_CODES_BOOL, false>, k_random_init<NND_CODES_BOOL, true>}};
+    const bool rowwise = (ctx->p.flags & NND_FLAG_TEST_RANDOM_INIT_ROWWISE) != 0;
     const int64_t rows = ctx->own_hi - ctx->own_lo;
     for (int pass = 0; pass < (ctx->k + 63) / 64; pass++) {
         ctx->pbuf_clean = false;
-        hipLaunchKernelGGL(bm ? (rowwise ? k_random_init_rowwise_bool : k_random_init_bool) : (rowwise ? k_random_init_rowwise : k_random_init), dim3((unsigned)(rowwise ? (rows + 3) / 4 : (rows + 255) / 256)),
+        hipLaunchKernelGGL(table[nnd_metric_bool(ctx->p.metric)][rowwise], dim3((unsigned)(rowwise ? (rows + 3) / 4 : (rows + 255) / 256)),
                            dim3(256), 0, ctx->stream, ctx->xp, ctx->dp, ctx->nrm, nnd_kmetric(ctx), ctx->n, ctx->own_lo, ctx->own_hi, ctx->k,
                            ctx->ks, ctx->knn_e, ctx->seed ^ 0x3C6EF372u ^ (uint32_t)(pass * 0x9E3779B9u), ctx->pbuf, ctx->pdirty, ctx->pcap);
         NND_HIP_CHECK(hipGetLastError());
@@ -311,7 +297,7 @@ int nnd_launch_random_init(nnd_ctx *ctx) {
 }
 
 // utils.py:836-860: every valid (i, j=graph[i][c]) is pushed with distance metric(x_i, x_j) or the given one
-// (the body of k_graph_init and of k_graph_init_bool, the instance of the boolean family: metric.h nnd_metric_family)
+// (the body of k_graph_init; FAM as in k_random_init)
 template <int FAM>
 __device__ __forceinline__ void mg_graph_init_body(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
                                                     int metric, int64_t n, int64_t lo, int64_t hi, const int32_t *__restrict__ gidx,
@@ -339,17 +325,12 @@ __device__ __forceinline__ void mg_graph_init_body(const float *__restrict__ xp,
     }
     if (lane == 0) pdirty[v] = 1;
 }
+template <int FAM>
 __global__ __launch_bounds__(256) void k_graph_init(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
                                                     int metric, int64_t n, int64_t lo, int64_t hi, const int32_t *__restrict__ gidx,
                                                     const float *__restrict__ gdist, int width, int col0, int wchunk,
                                                     uint64_t *__restrict__ pbuf, uint8_t *__restrict__ pdirty, int pcap) {
-    mg_graph_init_body<NND_CODES_ANY>(xp, dp, nrm, metric, n, lo, hi, gidx, gdist, width, col0, wchunk, pbuf, pdirty, pcap);
-}
-__global__ __launch_bounds__(256) void k_graph_init_bool(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
-                                                    int metric, int64_t n, int64_t lo, int64_t hi, const int32_t *__restrict__ gidx,
-                                                    const float *__restrict__ gdist, int width, int col0, int wchunk,
-                                                    uint64_t *__restrict__ pbuf, uint8_t *__restrict__ pdirty, int pcap) {
-    mg_graph_init_body<NND_CODES_BOOL>(xp, dp, nrm, metric, n, lo, hi, gidx, gdist, width, col0, wchunk, pbuf, pdirty, pcap);
+    mg_graph_init_body<FAM>(xp, dp, nrm, metric, n, lo, hi, gidx, gdist, width, col0, wchunk, pbuf, pdirty, pcap);
 }
 
 int nnd_launch_init_from_graph(nnd_ctx *ctx, const int32_t *idx_dev, const float *dist_dev, int width) {
@@ -361,7 +342,7 @@ int nnd_launch_init_from_graph(nnd_ctx *ctx, const int32_t *idx_dev, const float
     for (int col0 = 0; col0 < width; col0 += 64) {
         const int wchunk = width - col0 < 64 ? width - col0 : 64;
         ctx->pbuf_clean = false;
-        hipLaunchKernelGGL(nnd_metric_bool(ctx->p.metric) ? k_graph_init_bool : k_graph_init, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, ctx->stream, ctx->xp, ctx->dp,
+        hipLaunchKernelGGL(nnd_metric_bool(ctx->p.metric) ? k_graph_init<NND_CODES_BOOL> : k_graph_init<NND_CODES_ANY>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, ctx->stream, ctx->xp, ctx->dp,
                            ctx->nrm, nnd_kmetric(ctx), ctx->n, ctx->own_lo, ctx->own_hi, idx_dev, dist_dev, width, col0, wchunk, ctx->pbuf, ctx->pdirty,
                            ctx->pcap);
         NND_HIP_CHECK(hipGetLastError());

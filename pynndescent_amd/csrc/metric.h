@@ -54,7 +54,8 @@ enum nnd_metric_family {
     NND_CODES_0_5 = 1,  // every code but 6 (kernels where code 6 has an instance of its own, or is refused by the host)
     NND_CODE_6 = 2,     // proxy inner product alone: no branch on the code
     NND_CODES_BOOL = 3, // the boolean family alone (8..16, `metric` packed by nnd_kernel_metric): the branch among its nine formulas
-    NND_CODES_ANY = 4,  // 0..6, by a branch on the code (no kernel is named by this value); the boolean family is never part of
+    NND_CODES_ANY = 4,  // 0..6, by a branch on the code (the first template argument of the build kernels' instances for these codes:
+                        // k_leaf_join<4, ...>, k_diversify_rows<4, ...>; no join kernel has it); the boolean family is never part of
                         // a branch: every kernel that ranks has instances of its own for it (NND_CODES_BOOL)
 };
 

@@ -38,7 +38,7 @@ __device__ __forceinline__ bool prune_coin(uint32_t seed, uint32_t row, uint32_t
 // (-1, +inf); kept entries stay in order.  AWARE: an entry u whose undirected degree exceeds max_degree is pruned
 // against d(i,u) * threshold_factor * alpha (pynndescent_.py:506-531); there is no coin in that variant (the
 // reference call site hands diversify_prob to `alpha`, pynndescent_.py:1486-1497 -- the host passes it the same way).
-// (the body of k_diversify_rows and of k_diversify_rows_bool, the instance of the boolean family: metric.h nnd_metric_family)
+// (the body of k_diversify_rows; FAM: NND_CODES_ANY, or NND_CODES_BOOL for the boolean family: metric.h nnd_metric_family)
 template <int FAM, bool AWARE>
 __device__ __forceinline__ void pr_diversify_rows_body(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
                                                         int metric, int64_t n, int k, int32_t *__restrict__ idx,
@@ -93,21 +93,13 @@ __device__ __forceinline__ void pr_diversify_rows_body(const float *__restrict__
         dist[i * k + lane] = lane < nk ? out_d : INFINITY;
     }
 }
-template <bool AWARE>
+template <int FAM, bool AWARE>
 __global__ __launch_bounds__(256) void k_diversify_rows(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
                                                         int metric, int64_t n, int k, int32_t *__restrict__ idx,
                                                         float *__restrict__ dist, float prob, uint32_t seed,
                                                         const int32_t *__restrict__ degree, int max_degree,
                                                         float base_rate, float alpha) {
-    pr_diversify_rows_body<NND_CODES_ANY, AWARE>(xp, dp, nrm, metric, n, k, idx, dist, prob, seed, degree, max_degree, base_rate, alpha);
-}
-template <bool AWARE>
-__global__ __launch_bounds__(256) void k_diversify_rows_bool(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
-                                                        int metric, int64_t n, int k, int32_t *__restrict__ idx,
-                                                        float *__restrict__ dist, float prob, uint32_t seed,
-                                                        const int32_t *__restrict__ degree, int max_degree,
-                                                        float base_rate, float alpha) {
-    pr_diversify_rows_body<NND_CODES_BOOL, AWARE>(xp, dp, nrm, metric, n, k, idx, dist, prob, seed, degree, max_degree, base_rate, alpha);
+    pr_diversify_rows_body<FAM, AWARE>(xp, dp, nrm, metric, n, k, idx, dist, prob, seed, degree, max_degree, base_rate, alpha);
 }
 
 // pynndescent_.py:549-588 (AWARE = false) / 625-726 (AWARE = true) on CSR rows of length <= 64 (rows of a diversified
@@ -117,7 +109,7 @@ __global__ __launch_bounds__(256) void k_diversify_rows_bool(const float *__rest
 // AWARE = true (pynndescent_.py:682-719): the walk starts at the first entry, skips weight-0 entries, compares with
 // the point at order[k], has no FLOAT32_EPS guard, and prunes when d * threshold_factor(degree of entry j) < w_j.
 // Pruned entries get weight 0.
-// (the body of k_diversify_csr and of k_diversify_csr_bool, the instance of the boolean family: metric.h nnd_metric_family)
+// (the body of k_diversify_csr; FAM: NND_CODES_ANY, or NND_CODES_BOOL for the boolean family: metric.h nnd_metric_family)
 template <int FAM, bool AWARE>
 __device__ __forceinline__ void pr_diversify_csr_body(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
                                                        int metric, int64_t n_rows, const int32_t *__restrict__ indptr,
@@ -175,23 +167,14 @@ __device__ __forceinline__ void pr_diversify_csr_body(const float *__restrict__ 
     }
     if (lane < len && !((retained >> lane) & 1ull)) data[a + lane] = 0.0f;
 }
-template <bool AWARE>
+template <int FAM, bool AWARE>
 __global__ __launch_bounds__(256) void k_diversify_csr(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
                                                        int metric, int64_t n_rows, const int32_t *__restrict__ indptr,
                                                        const int32_t *__restrict__ indices, float *__restrict__ data,
                                                        int *__restrict__ too_long, float prob, uint32_t seed,
                                                        const int32_t *__restrict__ degree, int max_degree,
                                                        float aggressiveness) {
-    pr_diversify_csr_body<NND_CODES_ANY, AWARE>(xp, dp, nrm, metric, n_rows, indptr, indices, data, too_long, prob, seed, degree, max_degree, aggressiveness);
-}
-template <bool AWARE>
-__global__ __launch_bounds__(256) void k_diversify_csr_bool(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
-                                                       int metric, int64_t n_rows, const int32_t *__restrict__ indptr,
-                                                       const int32_t *__restrict__ indices, float *__restrict__ data,
-                                                       int *__restrict__ too_long, float prob, uint32_t seed,
-                                                       const int32_t *__restrict__ degree, int max_degree,
-                                                       float aggressiveness) {
-    pr_diversify_csr_body<NND_CODES_BOOL, AWARE>(xp, dp, nrm, metric, n_rows, indptr, indices, data, too_long, prob, seed, degree, max_degree, aggressiveness);
+    pr_diversify_csr_body<FAM, AWARE>(xp, dp, nrm, metric, n_rows, indptr, indices, data, too_long, prob, seed, degree, max_degree, aggressiveness);
 }
 
 
@@ -207,7 +190,7 @@ struct prune_wide_row {
     uint8_t kept[PRUNE_WIDE];
 };
 
-// (the body of k_diversify_rows_wide and of k_diversify_rows_wide_bool, the instance of the boolean family: metric.h nnd_metric_family)
+// (the body of k_diversify_rows_wide; FAM: NND_CODES_ANY, or NND_CODES_BOOL for the boolean family: metric.h nnd_metric_family)
 template <int FAM, bool AWARE>
 __device__ __forceinline__ void pr_diversify_rows_wide_body(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
                                                              int metric, int64_t n, int k, int32_t *__restrict__ idx,
@@ -266,24 +249,16 @@ __device__ __forceinline__ void pr_diversify_rows_wide_body(const float *__restr
         dist[i * k + j] = INFINITY;
     }
 }
-template <bool AWARE>
+template <int FAM, bool AWARE>
 __global__ __launch_bounds__(256) void k_diversify_rows_wide(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
                                                              int metric, int64_t n, int k, int32_t *__restrict__ idx,
                                                              float *__restrict__ dist, float prob, uint32_t seed,
                                                              const int32_t *__restrict__ degree, int max_degree,
                                                              float base_rate, float alpha) {
-    pr_diversify_rows_wide_body<NND_CODES_ANY, AWARE>(xp, dp, nrm, metric, n, k, idx, dist, prob, seed, degree, max_degree, base_rate, alpha);
-}
-template <bool AWARE>
-__global__ __launch_bounds__(256) void k_diversify_rows_wide_bool(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
-                                                             int metric, int64_t n, int k, int32_t *__restrict__ idx,
-                                                             float *__restrict__ dist, float prob, uint32_t seed,
-                                                             const int32_t *__restrict__ degree, int max_degree,
-                                                             float base_rate, float alpha) {
-    pr_diversify_rows_wide_body<NND_CODES_BOOL, AWARE>(xp, dp, nrm, metric, n, k, idx, dist, prob, seed, degree, max_degree, base_rate, alpha);
+    pr_diversify_rows_wide_body<FAM, AWARE>(xp, dp, nrm, metric, n, k, idx, dist, prob, seed, degree, max_degree, base_rate, alpha);
 }
 
-// (the body of k_diversify_csr_wide and of k_diversify_csr_wide_bool, the instance of the boolean family: metric.h nnd_metric_family)
+// (the body of k_diversify_csr_wide; FAM: NND_CODES_ANY, or NND_CODES_BOOL for the boolean family: metric.h nnd_metric_family)
 template <int FAM, bool AWARE>
 __device__ __forceinline__ void pr_diversify_csr_wide_body(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
                                                             int metric, int64_t n_rows, const int32_t *__restrict__ indptr,
@@ -348,23 +323,14 @@ __device__ __forceinline__ void pr_diversify_csr_wide_body(const float *__restri
     for (int j = lane; j < len; j += 64)
         if (!r.kept[j]) data[a + j] = 0.0f;
 }
-template <bool AWARE>
+template <int FAM, bool AWARE>
 __global__ __launch_bounds__(256) void k_diversify_csr_wide(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
                                                             int metric, int64_t n_rows, const int32_t *__restrict__ indptr,
                                                             const int32_t *__restrict__ indices, float *__restrict__ data,
                                                             int *__restrict__ too_long, float prob, uint32_t seed,
                                                             const int32_t *__restrict__ degree, int max_degree,
                                                             float aggressiveness) {
-    pr_diversify_csr_wide_body<NND_CODES_ANY, AWARE>(xp, dp, nrm, metric, n_rows, indptr, indices, data, too_long, prob, seed, degree, max_degree, aggressiveness);
-}
-template <bool AWARE>
-__global__ __launch_bounds__(256) void k_diversify_csr_wide_bool(const float *__restrict__ xp, int dp, const float *__restrict__ nrm,
-                                                            int metric, int64_t n_rows, const int32_t *__restrict__ indptr,
-                                                            const int32_t *__restrict__ indices, float *__restrict__ data,
-                                                            int *__restrict__ too_long, float prob, uint32_t seed,
-                                                            const int32_t *__restrict__ degree, int max_degree,
-                                                            float aggressiveness) {
-    pr_diversify_csr_wide_body<NND_CODES_BOOL, AWARE>(xp, dp, nrm, metric, n_rows, indptr, indices, data, too_long, prob, seed, degree, max_degree, aggressiveness);
+    pr_diversify_csr_wide_body<FAM, AWARE>(xp, dp, nrm, metric, n_rows, indptr, indices, data, too_long, prob, seed, degree, max_degree, aggressiveness);
 }
 
 // pynndescent_.py:728-738: rows longer than max_degree keep the entries <= sorted(row)[max_degree]
@@ -397,57 +363,40 @@ __global__ __launch_bounds__(256) void k_degree_prune(int64_t n_rows, const int3
         if (data[a + e] > cut) data[a + e] = 0.0f;
 }
 
+// every instance of a pruning kernel (rows or csr), by [boolean family][wide][AWARE]
+#define PR_TABLE(K, KW) {{{K<NND_CODES_ANY, false>, K<NND_CODES_ANY, true>}, {KW<NND_CODES_ANY, false>, KW<NND_CODES_ANY, true>}}, \
+                         {{K<NND_CODES_BOOL, false>, K<NND_CODES_BOOL, true>}, {KW<NND_CODES_BOOL, false>, KW<NND_CODES_BOOL, true>}}}
+
 int nnd_launch_diversify_rows(nnd_ctx *ctx, int32_t *idx_dev, float *dist_dev, const nnd_prune_opts *o, const int32_t *degree_dev) {
-    const bool bm = nnd_metric_bool(ctx->p.metric);  // the boolean family's instances (metric.h NND_CODES_BOOL)
-    const dim3 grid((unsigned)((ctx->n + 3) / 4));
+    static const decltype(&k_diversify_rows<NND_CODES_ANY, false>) table[2][2][2] = PR_TABLE(k_diversify_rows, k_diversify_rows_wide);
     if (ctx->k > PRUNE_WIDE) { ctx->set_error("the pruning pass handles rows of at most %d neighbours", PRUNE_WIDE); return 1; }
-    if (ctx->k > 64) {  // rows that do not fit one entry per lane: the LDS variants
-        const float base_rate = 0.04f * fmaxf(0.0f, o->aggressiveness);
-        if (o->degree_aware)
-            hipLaunchKernelGGL(bm ? k_diversify_rows_wide_bool<true> : k_diversify_rows_wide<true>, grid, dim3(256), 0, ctx->stream, ctx->xp, ctx->dp, ctx->nrm, nnd_kmetric(ctx), ctx->n, ctx->k,
-                               idx_dev, dist_dev, 1.0f, o->seed, degree_dev, o->max_degree, base_rate, o->alpha);
-        else
-            hipLaunchKernelGGL(bm ? k_diversify_rows_wide_bool<false> : k_diversify_rows_wide<false>, grid, dim3(256), 0, ctx->stream, ctx->xp, ctx->dp, ctx->nrm, nnd_kmetric(ctx), ctx->n, ctx->k,
-                               idx_dev, dist_dev, o->prune_probability, o->seed, (const int32_t *)nullptr, 1, 0.0f, 1.0f);
-        NND_HIP_CHECK(hipGetLastError());
-        return 0;
-    }
-    if (o->degree_aware) {
-        const float base_rate = 0.04f * fmaxf(0.0f, o->aggressiveness);  // pynndescent_.py:487-488
-        hipLaunchKernelGGL(bm ? k_diversify_rows_bool<true> : k_diversify_rows<true>, grid, dim3(256), 0, ctx->stream, ctx->xp, ctx->dp, ctx->nrm, nnd_kmetric(ctx),
-                           ctx->n, ctx->k, idx_dev, dist_dev, 1.0f, o->seed, degree_dev, o->max_degree, base_rate, o->alpha);
-    } else {
-        hipLaunchKernelGGL(bm ? k_diversify_rows_bool<false> : k_diversify_rows<false>, grid, dim3(256), 0, ctx->stream, ctx->xp, ctx->dp, ctx->nrm, nnd_kmetric(ctx),
-                           ctx->n, ctx->k, idx_dev, dist_dev, o->prune_probability, o->seed, (const int32_t *)nullptr, 1, 0.0f, 1.0f);
-    }
+    // the degree-aware variant has no coin; the plain one reads no degrees
+    const bool aware = o->degree_aware;
+    const float prob = aware ? 1.0f : o->prune_probability, alpha = aware ? o->alpha : 1.0f;
+    const float base_rate = aware ? 0.04f * fmaxf(0.0f, o->aggressiveness) : 0.0f;  // pynndescent_.py:487-488
+    const int32_t *degree = aware ? degree_dev : nullptr;
+    const int max_degree = aware ? o->max_degree : 1;
+    // k > 64: rows that do not fit one entry per lane, the LDS variants
+    hipLaunchKernelGGL(table[nnd_metric_bool(ctx->p.metric)][ctx->k > 64][aware], dim3((unsigned)((ctx->n + 3) / 4)), dim3(256), 0, ctx->stream, ctx->xp, ctx->dp,
+                       ctx->nrm, nnd_kmetric(ctx), ctx->n, ctx->k, idx_dev, dist_dev, prob, o->seed, degree, max_degree, base_rate, alpha);
     NND_HIP_CHECK(hipGetLastError());
     return 0;
 }
 int nnd_launch_diversify_csr(nnd_ctx *ctx, const int32_t *indptr_dev, const int32_t *indices_dev, float *data_dev,
                              int *too_long_dev, const nnd_prune_opts *o, const int32_t *degree_dev) {
-    const bool bm = nnd_metric_bool(ctx->p.metric);  // the boolean family's instances (metric.h NND_CODES_BOOL)
-    const dim3 grid((unsigned)((ctx->n + 3) / 4));
-    if (ctx->k > 64) {  // rows of up to PRUNE_WIDE entries: the LDS variants
-        if (o->degree_aware)
-            hipLaunchKernelGGL(bm ? k_diversify_csr_wide_bool<true> : k_diversify_csr_wide<true>, grid, dim3(256), 0, ctx->stream, ctx->xp, ctx->dp, ctx->nrm, nnd_kmetric(ctx), ctx->n, indptr_dev,
-                               indices_dev, data_dev, too_long_dev, o->prune_probability, o->seed ^ 0x51ED270Bu, degree_dev, o->max_degree, o->aggressiveness);
-        else
-            hipLaunchKernelGGL(bm ? k_diversify_csr_wide_bool<false> : k_diversify_csr_wide<false>, grid, dim3(256), 0, ctx->stream, ctx->xp, ctx->dp, ctx->nrm, nnd_kmetric(ctx), ctx->n, indptr_dev,
-                               indices_dev, data_dev, too_long_dev, o->prune_probability, o->seed ^ 0x51ED270Bu, (const int32_t *)nullptr, 1, 0.0f);
-        NND_HIP_CHECK(hipGetLastError());
-        return 0;
-    }
-    if (o->degree_aware)
-        hipLaunchKernelGGL(bm ? k_diversify_csr_bool<true> : k_diversify_csr<true>, grid, dim3(256), 0, ctx->stream, ctx->xp, ctx->dp, ctx->nrm, nnd_kmetric(ctx),
-                           ctx->n, indptr_dev, indices_dev, data_dev, too_long_dev, o->prune_probability, o->seed ^ 0x51ED270Bu,
-                           degree_dev, o->max_degree, o->aggressiveness);
-    else
-        hipLaunchKernelGGL(bm ? k_diversify_csr_bool<false> : k_diversify_csr<false>, grid, dim3(256), 0, ctx->stream, ctx->xp, ctx->dp, ctx->nrm, nnd_kmetric(ctx),
-                           ctx->n, indptr_dev, indices_dev, data_dev, too_long_dev, o->prune_probability, o->seed ^ 0x51ED270Bu,
-                           (const int32_t *)nullptr, 1, 0.0f);
+    static const decltype(&k_diversify_csr<NND_CODES_ANY, false>) table[2][2][2] = PR_TABLE(k_diversify_csr, k_diversify_csr_wide);
+    const bool aware = o->degree_aware;  // the plain variant reads no degrees
+    const int32_t *degree = aware ? degree_dev : nullptr;
+    const int max_degree = aware ? o->max_degree : 1;
+    const float aggressiveness = aware ? o->aggressiveness : 0.0f;
+    // k > 64: rows of up to PRUNE_WIDE entries, the LDS variants
+    hipLaunchKernelGGL(table[nnd_metric_bool(ctx->p.metric)][ctx->k > 64][aware], dim3((unsigned)((ctx->n + 3) / 4)), dim3(256), 0, ctx->stream, ctx->xp, ctx->dp,
+                       ctx->nrm, nnd_kmetric(ctx), ctx->n, indptr_dev, indices_dev, data_dev, too_long_dev, o->prune_probability, o->seed ^ 0x51ED270Bu,
+                       degree, max_degree, aggressiveness);
     NND_HIP_CHECK(hipGetLastError());
     return 0;
 }
+#undef PR_TABLE
 int nnd_launch_degree_prune(nnd_ctx *ctx, const int32_t *indptr_dev, float *data_dev, int max_degree) {
     hipLaunchKernelGGL(k_degree_prune, dim3((unsigned)((ctx->n + 3) / 4)), dim3(256), 0, ctx->stream, ctx->n, indptr_dev, data_dev,
                        max_degree);

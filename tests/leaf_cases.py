@@ -2,7 +2,10 @@
 ambiguity caps.  The leaf arrays are built HERE, not by the forest: a case reaches the kernel instance it names whatever the
 forest would do at its k.
 
-Which instance a (k, longest run) pair reaches (csrc/leaf_join.hip run_leaf_rounds; restated by leaf_reference.forms):
+Which instance a (k, longest run) pair reaches (csrc/leaf_plan.h nnd_leaf_table, the one statement of this table in the library;
+restated by leaf_reference.forms, and the two compared pair by pair in tests/test_leaf_plan_cpu.py).  The names are written
+without the kernels' first template argument, the metric family: NND_CODES_BOOL for the boolean metrics (the leaf cases of
+tests/test_gpu_boolean_metrics.py), NND_CODES_ANY for every case of this file.
 
     longest run   k <= 16                        k 17-32                 k 33-64                 k > 64
     <= 64         k_leaf_join<4,8,64,true>       k_leaf_join_sym<6,8>    k_leaf_join<4,8,64>     k_leaf_join_rb<8,8,true>

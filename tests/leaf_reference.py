@@ -38,7 +38,8 @@ Counters (run_leaf_rounds zeroes them once per call; leaf_join.hip :369-373, :52
 and leaf_rows = sum m over the runs; leaf_mfma = sum tiles(m) * (dp / 4) with dp = d rounded up to 32 and nt = ceil(m / 16) tile
 rows: nt (nt + 1) / 2 for the forms that compute the upper triangle (k_leaf_join with the whole block in LDS, k_leaf_join_sym),
 nt * nt for k_leaf_join_rb (its row blocks add trows * nt each and the trows of a leaf's blocks add up to nt).  ``forms(k,
-longest)`` restates the table of run_leaf_rounds (:719-767); the longest run of the whole call selects the launches of every round.
+longest)`` restates the table of csrc/leaf_plan.h (nnd_leaf_plan), by which run_leaf_rounds launches: tests/test_leaf_plan_cpu.py
+compares the two over every (k, longest); the longest run of the whole call selects the launches of every round.
 """
 from collections import namedtuple
 
@@ -108,7 +109,9 @@ def work_list(leaf_array, n):
 
 # ------------------------------------------------------------------------------------------------ the dispatch table
 def forms(k, longest):
-    """The launches of one round (run_leaf_rounds) for rows of k neighbours when the longest run has ``longest`` points."""
+    """The launches of one round (csrc/leaf_plan.h nnd_leaf_plan) for rows of k neighbours when the longest run has ``longest``
+    points.  The names are the kernels' without their first template argument, the metric family (metric.h nnd_metric_family):
+    a form has one instance for the boolean metrics and one for all others, and the table is the same for both."""
     if k > 64:
         nt = 8 if longest <= 128 else (10 if longest <= 160 else 16)
         return [Form("k_leaf_join_rb<%d,8,true>" % nt, "full", 0, nt * 16)]

@@ -2,7 +2,7 @@
 numpy: test infrastructure, nothing under pynndescent_amd/ imports it.
 
 What is restated, and from where:
-  * csrc/prune.hip k_diversify_rows<AWARE> :41-94 and k_diversify_rows_wide<AWARE> :174-231 (one walk, two forms: the row in
+  * csrc/prune.hip k_diversify_rows<FAM, AWARE> :41-94 and k_diversify_rows_wide<FAM, AWARE> :174-231 (one walk, two forms: the row in
     lanes for k <= 64, in LDS for k 65-256) -> ``diversify_rows``.  Position 0 is always kept (:60, :195); the walk stops at the
     first -1 (:63, :200); entry j is tested against the entries kept so far, in position order (:67-80, :204-213), those with a
     stored distance > PRUNE_EPS only (:72, :206); the row's own vertex as a comparison point takes the stored d(i, j) (:74, :207);
@@ -10,7 +10,7 @@ What is restated, and from where:
     :190-193, :202), which has no coin; kept entries are packed to the front in order, the tail is (-1, +inf) (:83-93, :217-230).
     Precondition: position 0 holds an id wherever position 1 does (the kernel -- like the reference -- reads the point of an
     entry it kept without looking at its id).
-  * k_diversify_csr<AWARE> :103-159 and k_diversify_csr_wide<AWARE> :233-296 -> ``diversify_csr``.  Rows of length <= 1 are left
+  * k_diversify_csr<FAM, AWARE> :103-159 and k_diversify_csr_wide<FAM, AWARE> :233-296 -> ``diversify_csr``.  Rows of length <= 1 are left
     alone (:114, :245).  order[] = the storage positions by ascending (weight, position) (:127-132, :265-271).  The standard walk
     starts at rank 1, the aware walk at rank 0 and skips entries of weight 0 (:134-137, :273-276).  Entry j = order[idx] is tested
     against kk < idx: the retained flag and the weight come from l = order[kk], the comparison POINT from storage position kk in

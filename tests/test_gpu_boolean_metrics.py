@@ -15,6 +15,7 @@ from pynndescent_amd import NNDescent, _capi
 from tests import boolean_util as BU
 from tests import descent_cases as DC
 from tests import descent_reference as DR
+from tests import leaf_cases as LC
 from tests import leaf_reference as LR
 from tests import prune_reference as PR
 
@@ -46,12 +47,42 @@ def _stored_equal(label, pw, idx, dist):
         label, int(bad.sum()), np.argwhere(bad)[0], dist[bad][0], want[bad][0])
 
 
+# (k, longest run) -> the launches of the leaf table (csrc/leaf_plan.h; names as tests/leaf_cases.py writes them, without the
+# family argument): all 15 forms, the smallest k and the upper edge of the size class of each
+LEAF_FORMS = {
+    (16, 64): (LC.QW4,), (16, 80): (LC.QW44, LC.QW5), (16, 96): (LC.QW6,), (16, 128): (LC.RB8,),
+    (30, 160): (LC.SYM6, LC.SYM10), (32, 256): (LC.RB16,),
+    (40, 64): (LC.P4,), (40, 80): (LC.P5,), (64, 96): (LC.P6,), (40, 160): (LC.RB10,),
+    (100, 128): (LC.W8,), (100, 160): (LC.W10,), (100, 256): (LC.W16,),
+}
+assert {f for fs in LEAF_FORMS.values() for f in fs} == {LC.QW4, LC.QW44, LC.QW5, LC.QW6, LC.P4, LC.P5, LC.P6, LC.SYM6, LC.SYM10,
+                                                        LC.RB8, LC.RB10, LC.RB16, LC.W8, LC.W10, LC.W16}
+
+
+def _leaf_rows(n, longest):
+    """disjoint leaves over n rows as an int32 leaf array, and their sizes: the longest run first, then sizes on both sides of
+    the tile, size-class and row-block edges below it, until the rows run out"""
+    perm = np.random.RandomState(longest).permutation(n).astype(np.int32)
+    sizes, left = [], n
+    for s in [longest] + [e for e in (97, 96, 65, 64, 33, 17, 2) if e < longest] * 4:
+        s = min(s, left)
+        if s < 2:
+            break
+        sizes.append(s)
+        left -= s
+    la = np.full((len(sizes), longest), -1, np.int32)
+    for i, (a, s) in enumerate(zip(np.cumsum([0] + sizes[:-1]), sizes)):
+        la[i, :s] = perm[a:a + s]
+    return la, sizes
+
+
 # ------------------------------------------------------------------------------------------------ 1. kernel agreement
 @pytest.mark.parametrize("d", [20, 133])
 @pytest.mark.parametrize("metric", BU.METRICS)
 def test_kernels_agree_bit_for_bit(metric, d):
-    """k_pairwise against float32 numpy; then the leaf kernels (k = 8 / 16 / 17 / 32 / 100: every leaf form), nnd_row_pair_dist
-    (random init) and k_query's reported distances against k_pairwise, bit for bit, on 300 rows (dp != d, several K blocks)."""
+    """k_pairwise against float32 numpy; then the leaf kernels (the library's forest at k = 8 / 16 / 17 / 32 / 100, and every
+    form of the leaf table on hand-built leaves: LEAF_FORMS), nnd_row_pair_dist (random init) and k_query's reported distances
+    against k_pairwise, bit for bit, on 300 rows (dp != d, several K blocks)."""
     x = BU.random_rows(300, d, 100 + d)
     pw = _pairwise(x, metric)
     want = BU.dist(metric, x, x, f32=True).astype(np.float32)
@@ -78,6 +109,24 @@ def test_kernels_agree_bit_for_bit(metric, d):
             _stored_equal("random init k = %d" % k, pw, idx, dist)
         finally:
             b.close()
+    # every form of the leaf table (csrc/leaf_plan.h) in the family's instance: a hand-built leaf array whose longest run sits in
+    # the form's size class, at the form's k.  leaf_pairs / leaf_rows / leaf_mfma are the model's counts for the forms named: that
+    # separates the row-block forms (whole blocks) from the others (upper triangle) and catches a leaf that no launch of the round
+    # took (a wrong m_lo or size class), not two forms that count alike (QW4 / QW6, P4 / P6 on the same leaves); which form a
+    # (k, longest run) pair launches is pinned on the CPU (tests/test_leaf_plan_cpu.py)
+    for (k, longest), names in sorted(LEAF_FORMS.items()):
+        la, sizes = _leaf_rows(x.shape[0], longest)
+        pairs, rows, mfma, fs = LR.counters(sizes, k, d)
+        assert tuple(f.name for f in fs) == names
+        b = BU.make_builder(x, metric, k=k, n_trees=0)
+        try:
+            b.init_from_leaf_array(la)
+            idx, dist, _ = b.graph()
+            st = b.stats()
+        finally:
+            b.close()
+        _stored_equal("leaf array k = %d, longest run %d (%s)" % (k, longest, ", ".join(names)), pw, idx, dist)
+        assert (st["leaf_pairs"], st["leaf_rows"], st["leaf_mfma"]) == (pairs, rows, mfma), (k, longest, names)
     # k_query: both tiers and every KU (k <= 64, <= 128, <= 256) report the bits of the pair
     index = NNDescent(x, metric=metric, n_neighbors=10, random_state=2)
     index.prepare()
@@ -242,7 +291,7 @@ def test_pruning_pass_has_the_models_edges(metric):
 @pytest.mark.parametrize("k", [10, 30, 100])
 @pytest.mark.parametrize("metric", BU.METRICS)
 def test_finalize_hands_out_the_float64_formula(metric, k):
-    """k_finalize<code> (k <= 64) and k_finalize_wide_bool: within 1 ulp of the float64 formula rounded to float32; duplicates at
+    """k_finalize<code> (k <= 64) and k_finalize_wide<NND_CODES_BOOL>: within 1 ulp of the float64 formula rounded to float32; duplicates at
     0; an all-zero row against a non-zero row as the table says; rows by (distance, id)."""
     x = BU.fixture_data(1500, 48, 0)[0]
     x = x * np.float32(2.5)  # non-indicator values: the counts are taken on x != 0

@@ -9,9 +9,9 @@ up to 16; the padded max_candidates mcp is 16 / 32 / 64 / 128 (the same function
                                  (DC by the same dp rule), its neighbour lists staged in LDS when ks <= 32 on one GPU, from
                                  global memory with NND_FLAG_TEST_JOIN_UNSTAGED; mcp 64 -> k_local_join_w<64>;
                                  mcp 128 -> launch_join_blocked (five passes of the 64-slot kernel)
-  leaf_join.hip run_leaf_rounds: k > 64 -> k_leaf_join_rb<*, 8, true>; k 17..32 and leaves <= 160 -> k_leaf_join_sym;
+  leaf_join.hip run_leaf_rounds (the table of leaf_plan.h): k > 64 -> k_leaf_join_rb<*, 8, true>; k 17..32 and leaves <= 160 -> k_leaf_join_sym;
                                  k <= 16 -> k_leaf_join<.., true> up to 96 points; leaves of 97.. points -> k_leaf_join_rb<8..16, 8>
-  finalize.hip nnd_launch_finalize: k > 64 -> k_finalize_wide<true>; else k_finalize<M> (float4 loads when d % 4 == 0,
+  finalize.hip nnd_launch_finalize: k > 64 -> k_finalize_wide<NND_CODES_ANY>; else k_finalize<M> (float4 loads when d % 4 == 0,
                                  scalar loads otherwise)
   prune.hip:                     k > 64 -> k_diversify_rows_wide / k_diversify_csr_wide (AWARE for degree_aware)
   query.hip (k_query):           query k <= 64 -> KU 1, <= 128 -> KU 2, else KU 4; set_tier(1): the global-memory tier
