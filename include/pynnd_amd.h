@@ -783,6 +783,22 @@ int32_t nnd_csr_destroy(nnd_csr_t g);
 int32_t nnd_graph_csr(int32_t device, const void *ids, int32_t id_bytes, const float *vals, int64_t m, int32_t k, int64_t n, int32_t mode,
                       int32_t symmetric, int64_t *indptr, int32_t *indices, float *data, int64_t capacity, int64_t *nnz, int64_t *long_rows);
 
+/* ---- fuzzy simplicial set: UMAP's graph weights from k-lists (csrc/fuzzy.hip; DESIGN.md "Fuzzy simplicial set") ----
+ * ids / dists: (m, k) as above, 2 <= k <= 256; an empty place adds nothing to a sum, a mean or the matrix.  Per row:
+ * rho from the row's positive distances (local_connectivity, 0 < lc <= k - 1), sigma by at most 64 rounds of bisection to
+ * sum_{j >= 1} exp(-max(d_j - rho, 0) / sigma) = log2(k) * bandwidth with UMAP's floor of 1e-3 times the row's (rho == 0: the
+ * global) mean distance; the entry (i, j) holds 1 where d - rho <= 0, else exp(-(d - rho) / sigma); (i, i) and entries that
+ * are 0 are not stored.  apply_set_ops (m == n only): mix * (A + A^T - A o A^T) + (1 - mix) * (A o A^T), evaluated in float32
+ * on the two strengths in the order of their bits, so the matrix is exactly symmetric; entries that become 0 are dropped.
+ * sigmas / rhos: float32 (m), written by the call.  The result is an nnd_csr_t as above (nnd_csr_arrays, nnd_csr_destroy);
+ * nnd_fuzzy_set is the same on host arrays, with the room rules of nnd_graph_csr.  Same bits on every run. */
+int32_t nnd_fuzzy_set_device(int32_t device, void *hip_stream, const void *ids_dev, int32_t id_bytes, const float *dists_dev, int64_t m,
+                             int32_t k, int64_t ld, int64_t n, float local_connectivity, float bandwidth, float set_op_mix_ratio,
+                             int32_t apply_set_ops, float *sigmas_dev, float *rhos_dev, nnd_csr_t *out);
+int32_t nnd_fuzzy_set(int32_t device, const void *ids, int32_t id_bytes, const float *dists, int64_t m, int32_t k, int64_t n,
+                      float local_connectivity, float bandwidth, float set_op_mix_ratio, int32_t apply_set_ops, float *sigmas, float *rhos,
+                      int64_t *indptr, int32_t *indices, float *data, int64_t capacity, int64_t *nnz, int64_t *long_rows);
+
 #ifdef __cplusplus
 }
 #endif

@@ -360,6 +360,11 @@ _SIGNATURES = [
     ("nnd_csr_destroy", C.c_int32, [_H]),
     ("nnd_graph_csr", C.c_int32, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    ("nnd_fuzzy_set_device", C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64,
+                                         C.c_float, C.c_float, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(_H)]),
+    ("nnd_fuzzy_set", C.c_int32, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_float, C.c_float, C.c_float,
+                                  C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64),
+                                  C.POINTER(C.c_int64)]),
 ]
 EXPORTED_SYMBOLS = [s[0] for s in _SIGNATURES]
 
@@ -1267,6 +1272,9 @@ class DeviceCsr:
         if self.lib.nnd_graph_csr_device(int(device), dev(stream_ptr), dev(ids_ptr), int(id_bytes), dev(vals_ptr), int(m), int(k), int(ld), int(n),
                                          _csr_mode(mode, drop_self), 1 if symmetric else 0, C.byref(self._h)) != 0:
             raise NNDError(self.lib.nnd_last_global_error().decode())
+        self._read(m, n)
+
+    def _read(self, m, n):
         indptr, indices, data, nnz, long_rows = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int64(), C.c_int64()
         self.lib.nnd_csr_arrays(self._h, C.byref(indptr), C.byref(indices), C.byref(data), C.byref(nnz), C.byref(long_rows))
         self.m, self.n, self.nnz, self.long_rows = int(m), int(n), int(nnz.value), int(long_rows.value)
@@ -1287,3 +1295,43 @@ class DeviceCsr:
             self.close()
         except Exception:
             pass
+
+
+class DeviceFuzzySet(DeviceCsr):
+    """Device k-lists -> UMAP's fuzzy simplicial set where they lie (``nnd_fuzzy_set_device``, csrc/fuzzy.hip): the arguments of
+    ``DeviceCsr`` with distances for values, the three parameters, and the device addresses of two float32 (m) arrays the call
+    fills with the rows' sigmas and rhos.  The CSR arrays are owned and handed out as there."""
+
+    def __init__(self, device, stream_ptr, ids_ptr, id_bytes, dists_ptr, m, k, ld, n, local_connectivity, bandwidth, set_op_mix_ratio,
+                 apply_set_operations, sigmas_ptr, rhos_ptr):
+        self.lib = load_library()
+        self._h = _H()
+        dev = lambda p: C.c_void_p(int(p)) if p else None  # noqa: E731
+        if self.lib.nnd_fuzzy_set_device(int(device), dev(stream_ptr), dev(ids_ptr), int(id_bytes), dev(dists_ptr), int(m), int(k), int(ld), int(n),
+                                         float(local_connectivity), float(bandwidth), float(set_op_mix_ratio), 1 if apply_set_operations else 0,
+                                         dev(sigmas_ptr), dev(rhos_ptr), C.byref(self._h)) != 0:
+            raise NNDError(self.lib.nnd_last_global_error().decode())
+        self._read(m, n)
+
+
+def fuzzy_set(ids, dists, n, local_connectivity=1.0, bandwidth=1.0, set_op_mix_ratio=1.0, apply_set_operations=True, device=0,
+              want_long_rows=False):
+    """Host k-lists -> UMAP's fuzzy simplicial set by the device kernels (``nnd_fuzzy_set``, csrc/fuzzy.hip).  Returns (indptr
+    int64 (m + 1), indices int32, data float32, sigmas float32 (m), rhos float32 (m))[, rows of the union that took the
+    long-row kernel]."""
+    lib = load_library()
+    ids = np.asarray(ids)
+    ids = np.ascontiguousarray(ids, dtype=np.int64 if ids.dtype == np.int64 else np.int32)
+    dists = np.ascontiguousarray(dists, dtype=np.float32)
+    assert ids.ndim == 2 and dists.shape == ids.shape
+    m, k = ids.shape
+    cap = max(1, m * k * (2 if apply_set_operations else 1))
+    indptr, indices, data = np.empty(m + 1, np.int64), np.empty(cap, np.int32), np.empty(cap, np.float32)
+    sigmas, rhos = np.empty(m, np.float32), np.empty(m, np.float32)
+    nnz, long_rows = C.c_int64(), C.c_int64()
+    if lib.nnd_fuzzy_set(int(device), _ptr(ids), ids.dtype.itemsize, _ptr(dists), m, k, int(n), float(local_connectivity), float(bandwidth),
+                         float(set_op_mix_ratio), 1 if apply_set_operations else 0, _ptr(sigmas), _ptr(rhos), _ptr(indptr), _ptr(indices),
+                         _ptr(data), cap, C.byref(nnz), C.byref(long_rows)) != 0:
+        raise NNDError(lib.nnd_last_global_error().decode())
+    out = (indptr, indices[: nnz.value].copy(), data[: nnz.value].copy(), sigmas, rhos)
+    return out + (int(long_rows.value),) if want_long_rows else out

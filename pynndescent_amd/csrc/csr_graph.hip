@@ -18,6 +18,8 @@
 // the sort by (column, value bits) that follows does not see that order, and where a column appears twice (the edge and its
 // reverse) the entry keeps the smaller of the two floats.  Counts come from integer additions, which commute.
 // No atomic here is anything but an integer add, nothing spins, and every store is a vector store.
+// The merge kernels' FUZZY instances serve fuzzy.hip (through csr_build_i32, csr_graph.h): the twin rule is UMAP's fuzzy union
+// instead of the min, and an entry whose value comes out 0 is dropped where the row's survivors are counted.
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -26,10 +28,8 @@
 
 #include "../../include/pynnd_amd.h"
 #include "common.h"
-#include "devmem.h"
-#include "state.h"
+#include "csr_graph.h"
 
-#define CSR_REG_CAP 256    // the widest k-list
 #define CSR_UNION_CAP 512  // staged keys of a row (its k places and its reverse edges) one wave sorts in registers; more: k_csr_sym_merge_long
 #define CSR_EMPTY 0xFFFFFFFFFFFFFFFFull
 
@@ -171,9 +171,23 @@ __device__ __forceinline__ uint64_t csr_min_with_twin(uint64_t key, uint64_t nex
     }
     return key;
 }
-// one stretch of at most W * KU staged keys: sort, collapse equal columns with min, write back packed; returns the entries left
-template <int KU, int W>
-__device__ __forceinline__ int csr_union_row(uint64_t *seg, int len) {
+// The fuzzy union of an entry and its twin, mix * (a + b - a * b) + (1 - mix) * (a * b); of a lone entry, mix * a.  The sort
+// has put the smaller bits first, so both rows of a pair evaluate the same expression on the same operands: (i, j) and (j, i)
+// hold the same bits.  Contraction is off: the value is the one a float32 restatement on the host gives.
+__device__ __forceinline__ uint64_t csr_fuzzy_with_twin(uint64_t key, uint64_t next, float mix) {
+#pragma clang fp contract(off)
+    const float a = csr_key_val(key);
+    float v = mix * a;
+    if (next != CSR_EMPTY && csr_key_col(next) == csr_key_col(key)) {
+        const float b = csr_key_val(next), p = a * b;
+        v = mix * (a + b - p) + (1.0f - mix) * p;
+    }
+    return csr_key((int32_t)csr_key_col(key), v);
+}
+// one stretch of at most W * KU staged keys: sort, collapse equal columns with min (FUZZY: the fuzzy union, and an entry whose
+// value is 0 goes), write back packed; returns the entries left
+template <int KU, int W, bool FUZZY>
+__device__ __forceinline__ int csr_union_row(uint64_t *seg, int len, float mix) {
     const int lane = nnd_lane();
     uint64_t key[KU];
 #pragma unroll
@@ -187,17 +201,26 @@ __device__ __forceinline__ int csr_union_row(uint64_t *seg, int len) {
         const uint64_t after_out = u < KU - 1 ? csr_shfl64(key[u + 1], 0) : CSR_EMPTY;
         const uint64_t before = lane == 0 ? before_out : before_in, after = lane == 63 ? after_out : after_in;
         const bool first = (u == 0 && lane == 0);
-        const bool keep = key[u] != CSR_EMPTY && (first || csr_key_col(before) != csr_key_col(key[u]));
-        const unsigned long long mask = __ballot(keep);
-        if (keep) seg[base + nnd_prefix_popc(mask)] = csr_min_with_twin(key[u], after);  // (every key is in registers by now)
-        base += __popcll(mask);
+        bool keep = key[u] != CSR_EMPTY && (first || csr_key_col(before) != csr_key_col(key[u]));
+        if constexpr (FUZZY) {
+            const uint64_t out = csr_fuzzy_with_twin(key[u], after, mix);
+            keep = keep && csr_key_val(out) != 0.0f;
+            const unsigned long long mask = __ballot(keep);
+            if (keep) seg[base + nnd_prefix_popc(mask)] = out;
+            base += __popcll(mask);
+        } else {
+            const unsigned long long mask = __ballot(keep);
+            if (keep) seg[base + nnd_prefix_popc(mask)] = csr_min_with_twin(key[u], after);  // (every key is in registers by now)
+            base += __popcll(mask);
+        }
     }
     return base;
 }
 // one wave per row; a stretch of more than CSR_UNION_CAP staged keys is put on the list of k_csr_sym_merge_long
+template <bool FUZZY>
 __global__ __launch_bounds__(256) void k_csr_sym_merge(int64_t n, int32_t k, const int64_t *__restrict__ roff, uint64_t *stage,
                                                        unsigned long long *__restrict__ ucnt, int32_t *__restrict__ long_rows,
-                                                       unsigned int *__restrict__ n_long) {
+                                                       unsigned int *__restrict__ n_long, float mix) {
     const int lane = nnd_lane();
     for (int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < n; row += (int64_t)gridDim.x * 4) {  // wave-uniform
         int64_t len;
@@ -207,12 +230,12 @@ __global__ __launch_bounds__(256) void k_csr_sym_merge(int64_t n, int32_t k, con
             continue;
         }
         int left;
-        if (len <= 16) left = csr_union_row<1, 16>(stage + a, (int)len);
-        else if (len <= 32) left = csr_union_row<1, 32>(stage + a, (int)len);
-        else if (len <= 64) left = csr_union_row<1, 64>(stage + a, (int)len);
-        else if (len <= 128) left = csr_union_row<2, 64>(stage + a, (int)len);
-        else if (len <= 256) left = csr_union_row<4, 64>(stage + a, (int)len);
-        else left = csr_union_row<8, 64>(stage + a, (int)len);
+        if (len <= 16) left = csr_union_row<1, 16, FUZZY>(stage + a, (int)len, mix);
+        else if (len <= 32) left = csr_union_row<1, 32, FUZZY>(stage + a, (int)len, mix);
+        else if (len <= 64) left = csr_union_row<1, 64, FUZZY>(stage + a, (int)len, mix);
+        else if (len <= 128) left = csr_union_row<2, 64, FUZZY>(stage + a, (int)len, mix);
+        else if (len <= 256) left = csr_union_row<4, 64, FUZZY>(stage + a, (int)len, mix);
+        else left = csr_union_row<8, 64, FUZZY>(stage + a, (int)len, mix);
         if (lane == 0) ucnt[row] = (unsigned long long)left;
     }
 }
@@ -220,9 +243,10 @@ __global__ __launch_bounds__(256) void k_csr_sym_merge(int64_t n, int32_t k, con
 // lower index (the first step of a merge mirrors the upper half), so the places past the row's end, which would hold +inf,
 // never take part; then the collapse of equal columns, 256 keys at a time from the front (what a piece writes lies at or in
 // front of what it read, and the column of the key in front of a piece is carried over in LDS).
+template <bool FUZZY>
 __global__ __launch_bounds__(256) void k_csr_sym_merge_long(int32_t k, const int64_t *__restrict__ roff, uint64_t *stage,
                                                             unsigned long long *__restrict__ ucnt, const int32_t *__restrict__ long_rows,
-                                                            const unsigned int *__restrict__ n_long) {
+                                                            const unsigned int *__restrict__ n_long, float mix) {
     __shared__ int s_wave[4];
     __shared__ uint32_t s_last_col;
     const int tid = threadIdx.x, lane = nnd_lane(), w = tid >> 6;
@@ -262,14 +286,16 @@ __global__ __launch_bounds__(256) void k_csr_sym_merge_long(int32_t k, const int
             const uint64_t after = e + 1 < len ? seg[e + 1] : CSR_EMPTY;
             const uint32_t before_col = tid > 0 ? csr_key_col(e - 1 < len ? seg[e - 1] : CSR_EMPTY) : (c0 > 0 ? s_last_col : 0xFFFFFFFFu);
             __syncthreads();  // every read of the piece is done (and s_last_col read) before anything is written
-            const bool keep = key != CSR_EMPTY && csr_key_col(key) != before_col;
+            bool keep = key != CSR_EMPTY && csr_key_col(key) != before_col;
+            const uint64_t out = FUZZY ? csr_fuzzy_with_twin(key, after, mix) : csr_min_with_twin(key, after);
+            if constexpr (FUZZY) keep = keep && csr_key_val(out) != 0.0f;
             const unsigned long long mask = __ballot(keep);
             if (lane == 0) s_wave[w] = __popcll(mask);
             if (tid == 255) s_last_col = csr_key_col(key);  // (only read when another piece follows: then e < len)
             __syncthreads();
             int pos = nnd_prefix_popc(mask), all = 0;
             for (int i = 0; i < 4; i++) { pos += i < w ? s_wave[i] : 0; all += s_wave[i]; }
-            if (keep) seg[written + pos] = csr_min_with_twin(key, after);
+            if (keep) seg[written + pos] = out;
             written += all;
             __syncthreads();
         }
@@ -294,39 +320,11 @@ __global__ __launch_bounds__(256) void k_csr_copy_rows(int64_t n, int32_t k, int
 }
 
 // ---------------------------------------------------------------------------------------------- host side
-struct nnd_csr_s {
-    nnd_devmem mem;  // one block: the three arrays below are pieces of it
-    int device = 0;
-    int64_t m = 0, nnz = 0, long_rows = 0;
-    int64_t *indptr = nullptr;
-    int32_t *indices = nullptr;
-    float *data = nullptr;
-};
-
 namespace {
-struct csr_err {  // the error sink of an entry without a handle: what nnd_last_global_error returns
-    char msg[256];
-    void set_error(const char *fmt, ...) {
-        va_list ap;
-        va_start(ap, fmt);
-        vsnprintf(msg, sizeof(msg), fmt, ap);
-        va_end(ap);
-        nnd_set_global_error(msg);
-    }
-};
 unsigned csr_grid(int64_t items, int per_block, int64_t cap) {
     const int64_t b = (items + per_block - 1) / per_block;
     return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
 }
-#define CSR_HIP(expr)                                                                                       \
-    do {                                                                                                    \
-        hipError_t _e = (expr);                                                                             \
-        if (_e != hipSuccess) {                                                                             \
-            (void)hipGetLastError();                                                                        \
-            err.set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__);       \
-            return 1;                                                                                       \
-        }                                                                                                   \
-    } while (0)
 
 // Device allocations are the expensive part of a call at this size (a hipMalloc or hipFree costs about what the directed
 // form's kernels cost together), so a call makes few: one block for all its small scratch arrays, one for the staging buffer
@@ -386,7 +384,7 @@ void launch_write_rows(hipStream_t st, const IdT *ids, const float *vals, int64_
 // at the two places where a total has to reach the host; the caller drains it once more before the scratch goes.
 template <typename IdT>
 int csr_build(csr_err &err, nnd_scratch &tmp, hipStream_t st, nnd_csr_s *g, const IdT *ids, const float *vals, int64_t m, int32_t k, int64_t ld,
-              int64_t n, int conn, int symmetric, int drop_self) {
+              int64_t n, int conn, int symmetric, int drop_self, csr_combine combine = csr_combine()) {
     const size_t scan_bytes = csr_scan_bytes(m);
     if (!scan_bytes) { err.set_error("nnd_graph_csr: the scan's storage query failed"); return 1; }
     const size_t rows1 = (size_t)m + 1;
@@ -422,10 +420,12 @@ int csr_build(csr_err &err, nnd_scratch &tmp, hipStream_t st, nnd_csr_s *g, cons
         hipLaunchKernelGGL((k_csr_sym_scatter<IdT>), dim3(csr_grid(places, 256, 8192)), dim3(256), 0, st, ids, vals, n, k, ld, drop_self,
                            (const int64_t *)roff, cursor, stage);
         CSR_HIP(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * rows1, st));  // from here on: the rows' final lengths
-        hipLaunchKernelGGL(k_csr_sym_merge, dim3(csr_grid(n, 4, 1 << 20)), dim3(256), 0, st, n, k, (const int64_t *)roff, stage, cnt, long_rows,
-                           cursor + n);
-        hipLaunchKernelGGL(k_csr_sym_merge_long, dim3(256), dim3(256), 0, st, k, (const int64_t *)roff, stage, cnt, (const int32_t *)long_rows,
-                           (const unsigned int *)(cursor + n));
+        const auto merge = combine.fuzzy ? k_csr_sym_merge<true> : k_csr_sym_merge<false>;
+        const auto merge_long = combine.fuzzy ? k_csr_sym_merge_long<true> : k_csr_sym_merge_long<false>;
+        hipLaunchKernelGGL(merge, dim3(csr_grid(n, 4, 1 << 20)), dim3(256), 0, st, n, k, (const int64_t *)roff, stage, cnt, long_rows, cursor + n,
+                           combine.mix);
+        hipLaunchKernelGGL(merge_long, dim3(256), dim3(256), 0, st, k, (const int64_t *)roff, stage, cnt, (const int32_t *)long_rows,
+                           (const unsigned int *)(cursor + n), combine.mix);
     }
     unsigned int n_long = 0;
     CSR_HIP(hipMemcpyAsync(&n_long, cursor + n, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
@@ -468,6 +468,12 @@ int csr_run(csr_err &err, hipStream_t st, nnd_csr_s *g, const void *ids, int32_t
     return 0;
 }
 }  // namespace
+
+int csr_build_i32(csr_err &err, nnd_scratch &tmp, hipStream_t st, nnd_csr_s *g, const int32_t *ids, const float *vals, int64_t m, int32_t k,
+                  int64_t ld, int64_t n, int symmetric, csr_combine combine) {
+    g->m = m;
+    return csr_build<int32_t>(err, tmp, st, g, ids, vals, m, k, ld, n, 0, symmetric, 0, combine);
+}
 
 extern "C" int32_t nnd_graph_csr_device(int32_t device, void *hip_stream, const void *ids_dev, int32_t id_bytes, const float *vals_dev, int64_t m,
                                         int32_t k, int64_t ld, int64_t n, int32_t mode, int32_t symmetric, nnd_csr_t *out) {

@@ -66,19 +66,23 @@ def _torch_csr(torch, ids, vals, n, k, mode, symmetric, drop_self, ordinal):
         csr = _capi.DeviceCsr(ordinal, on.ptr, ids.data_ptr(), ids.element_size(), vals.data_ptr(), m, k, ld, n, mode=mode,
                               symmetric=symmetric, drop_self=drop_self)
         on.done()
-        device = ids.device
-        indptr = torch.as_tensor(csr.indptr, device=device)
-        if csr.nnz:
-            indices, data = torch.as_tensor(csr.indices, device=device), torch.as_tensor(csr.data, device=device)
-        else:
-            indices, data = torch.empty(0, dtype=torch.int32, device=device), torch.empty(0, dtype=torch.float32, device=device)
-        # torch wants one integer type for both index arrays: the m + 1 offsets are narrowed (the entries are not touched)
-        narrow = csr.nnz < 2 ** 31
-        with warnings.catch_warnings():  # (torch announces once per process that its CSR layout is in beta)
-            warnings.filterwarnings("ignore", message="Sparse CSR tensor support is in beta state")
-            out = torch.sparse_csr_tensor(indptr.to(torch.int32) if narrow else indptr, indices if narrow else indices.long(), data,
-                                          size=(m, int(n)))
-    return out
+        return _wrap_device_csr(torch, csr, ids.device)
+
+
+def _wrap_device_csr(torch, csr, device):
+    """A ``sparse_csr`` tensor on the three arrays of a ``_capi.DeviceCsr``; they stay the library's own buffers.  Called with
+    the tensors' device current."""
+    indptr = torch.as_tensor(csr.indptr, device=device)
+    if csr.nnz:
+        indices, data = torch.as_tensor(csr.indices, device=device), torch.as_tensor(csr.data, device=device)
+    else:
+        indices, data = torch.empty(0, dtype=torch.int32, device=device), torch.empty(0, dtype=torch.float32, device=device)
+    # torch wants one integer type for both index arrays: the m + 1 offsets are narrowed (the entries are not touched)
+    narrow = csr.nnz < 2 ** 31
+    with warnings.catch_warnings():  # (torch announces once per process that its CSR layout is in beta)
+        warnings.filterwarnings("ignore", message="Sparse CSR tensor support is in beta state")
+        return torch.sparse_csr_tensor(indptr.to(torch.int32) if narrow else indptr, indices if narrow else indices.long(), data,
+                                       size=(csr.m, csr.n))
 
 
 def _as_device_lists(torch, ids, vals, device):

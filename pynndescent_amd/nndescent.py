@@ -33,7 +33,7 @@ from warnings import warn
 import numpy as np
 from sklearn.utils import check_array, check_random_state
 
-from . import _capi, build, device_arrays, filtered, graph_export, linear_map, row_map, sparse_input, tags as tagwords
+from . import _capi, build, device_arrays, filtered, fuzzy, graph_export, linear_map, row_map, sparse_input, tags as tagwords
 # Every name below was defined here once and is read here still (tests, tools/, and pickles, which name
 # pynndescent_amd.nndescent.correct_alternative_*): the same objects as in their home modules.  Two are replaced by tests and
 # are therefore CALLED through their home module alone -- ``build.ts()``, ``device_arrays._torch()``.
@@ -938,6 +938,17 @@ class NNDescent:
         ``torch.sparse_csr_tensor`` on the index's device, on torch's current stream, for a device-resident index; that tensor
         is built on the kernels' own buffers, nothing is copied."""
         return graph_export.kneighbors_graph(self, X, k, mode, symmetric, include_self, epsilon, **query_kwds)
+
+    def fuzzy_simplicial_set(self, n_neighbors=None, set_op_mix_ratio=1.0, local_connectivity=1.0, bandwidth=1.0, apply_set_operations=True):
+        """UMAP's fuzzy simplicial set of the built graph, ``(graph, sigmas, rhos)``, computed on the GPU (fuzzy.py,
+        csrc/fuzzy.hip): the first ``n_neighbors`` columns (default: all) with the distances ``neighbor_graph`` hands out.
+        Per row rho is the distance to the ``local_connectivity``-th neighbour (interpolated) and sigma solves
+        sum_j exp(-max(d_j - rho, 0) / sigma) = log2(n_neighbors) * bandwidth; the entry (i, j) is exp(-max(d - rho, 0) / sigma),
+        and ``apply_set_operations`` joins the matrix with its transpose, ``set_op_mix_ratio`` between fuzzy union (1) and
+        intersection (0).  A (-1, inf) place adds nothing to any sum or mean.  The result is exactly symmetric and the same
+        bits on every run.  Returns ``scipy.sparse.csr_array`` and numpy arrays for an index of host data or one built with
+        ``n_devices`` > 1, a ``torch.sparse_csr_tensor`` and tensors on the index's device for a device-resident index."""
+        return fuzzy.index_fuzzy_simplicial_set(self, n_neighbors, set_op_mix_ratio, local_connectivity, bandwidth, apply_set_operations)
 
     def _query_sparse(self, query_data, m, k, epsilon, proxy_beam_size, filter, filter_mode):
         """``query`` for a ``scipy.sparse`` batch, on an index built from sparse or dense data alike: the batch is made canonical,
