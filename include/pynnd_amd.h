@@ -799,6 +799,25 @@ int32_t nnd_fuzzy_set(int32_t device, const void *ids, int32_t id_bytes, const f
                       float local_connectivity, float bandwidth, float set_op_mix_ratio, int32_t apply_set_ops, float *sigmas, float *rhos,
                       int64_t *indptr, int32_t *indices, float *data, int64_t capacity, int64_t *nnz, int64_t *long_rows);
 
+/* ---- perplexity affinities: t-SNE's input matrix from k-lists (csrc/affinity.hip; DESIGN.md "Perplexity affinities") ----
+ * ids / dists: (m, k) as above, 1 <= k <= 256.  A place counts when its id lies in [0, n), is not the row itself (m == n
+ * only) and its energy e = d * d (squared) or d is finite.  perplexities: n_scales (1..4) positive floats on the host.  Per
+ * row and scale the search of sklearn's _binary_search_perplexity on e - min e: beta = 1, at most 100 evaluations of
+ * H = log(s) + beta * sum(e p) / s with p = exp(-beta e), s = max(sum p, 1e-8), stop at |H - log(perplexity)| <= 1e-5, else
+ * double / halve beta while the other bound is infinite and bisect afterwards; no update follows the 100th evaluation.  The
+ * conditional entry is the mean over the scales of p / s; an entry that is 0 is not stored.  betas: float32 (m, n_scales),
+ * written by the call.  symmetrize (m == n only): entry (i, j) = (c_ij + c_ji) * scale, the two added in the order of their
+ * bits, so the matrix is exactly symmetric; normalize: scale = 1 / total of the matrix (float64 sum in a fixed order), else
+ * 1; entries that become 0 are dropped.  The result is an nnd_csr_t as above (nnd_csr_arrays, nnd_csr_destroy);
+ * nnd_perplexity_affinities is the same on host arrays, with the room rules of nnd_graph_csr.  Same bits on every run. */
+int32_t nnd_perplexity_affinities_device(int32_t device, void *hip_stream, const void *ids_dev, int32_t id_bytes, const float *dists_dev,
+                                         int64_t m, int32_t k, int64_t ld, int64_t n, const float *perplexities, int32_t n_scales,
+                                         int32_t squared, int32_t symmetrize, int32_t normalize, float *betas_dev, nnd_csr_t *out);
+int32_t nnd_perplexity_affinities(int32_t device, const void *ids, int32_t id_bytes, const float *dists, int64_t m, int32_t k, int64_t n,
+                                  const float *perplexities, int32_t n_scales, int32_t squared, int32_t symmetrize, int32_t normalize,
+                                  float *betas, int64_t *indptr, int32_t *indices, float *data, int64_t capacity, int64_t *nnz,
+                                  int64_t *long_rows);
+
 #ifdef __cplusplus
 }
 #endif

@@ -45,6 +45,7 @@ NND_CORRECT_HAVERSINE = 5
 NND_LINEAR_DIAGONAL, NND_LINEAR_DENSE = 0, 1  # the kinds of a metric's linear map (include/pynnd_amd.h NND_LINEAR_*, csrc/linear.hip)
 NND_CSR_DISTANCE, NND_CSR_CONNECTIVITY, NND_CSR_DROP_SELF = 0, 1, 2  # nnd_graph_csr's `mode` (csrc/csr_graph.hip); DROP_SELF is or-ed in
 CSR_MAX_K = 256  # the widest k-list nnd_graph_csr takes (csrc/csr_graph.hip CSR_REG_CAP)
+AFFINITY_MAX_SCALES = 4  # the most perplexities of one nnd_perplexity_affinities call (csrc/affinity.hip AF_MAX_SCALES)
 NND_ROWMAP_RANK, NND_ROWMAP_SPHERE = 0, 1  # the kinds of a derived metric's row map (include/pynnd_amd.h NND_ROWMAP_*, csrc/rowmap.hip)
 ROWMAP_RANK_MAX_DIM = 16384  # the widest row nnd_device_map_rows ranks (csrc/rowmap.hip RM_RANK_MAX)
 NND_FLAG_NO_GRAPH = 1  # auxiliary handle: no k-lists / candidate / proposal tables (pruning pass, hub tree)
@@ -365,6 +366,11 @@ _SIGNATURES = [
     ("nnd_fuzzy_set", C.c_int32, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_float, C.c_float, C.c_float,
                                   C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64),
                                   C.POINTER(C.c_int64)]),
+    ("nnd_perplexity_affinities_device", C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int64,
+                                                     C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(_H)]),
+    ("nnd_perplexity_affinities", C.c_int32, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_int32,
+                                              C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                              C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
 ]
 EXPORTED_SYMBOLS = [s[0] for s in _SIGNATURES]
 
@@ -1334,4 +1340,45 @@ def fuzzy_set(ids, dists, n, local_connectivity=1.0, bandwidth=1.0, set_op_mix_r
                          _ptr(data), cap, C.byref(nnz), C.byref(long_rows)) != 0:
         raise NNDError(lib.nnd_last_global_error().decode())
     out = (indptr, indices[: nnz.value].copy(), data[: nnz.value].copy(), sigmas, rhos)
+    return out + (int(long_rows.value),) if want_long_rows else out
+
+
+class DeviceAffinities(DeviceCsr):
+    """Device k-lists -> t-SNE's perplexity affinities where they lie (``nnd_perplexity_affinities_device``, csrc/affinity.hip):
+    the arguments of ``DeviceCsr`` with distances for values, the perplexities (a sequence of 1..AFFINITY_MAX_SCALES floats),
+    the three switches, and the device address of a float32 (m, scales) array the call fills with the rows' betas.  The CSR
+    arrays are owned and handed out as there."""
+
+    def __init__(self, device, stream_ptr, ids_ptr, id_bytes, dists_ptr, m, k, ld, n, perplexities, squared, symmetrize, normalize, betas_ptr):
+        self.lib = load_library()
+        self._h = _H()
+        dev = lambda p: C.c_void_p(int(p)) if p else None  # noqa: E731
+        scales = np.ascontiguousarray(perplexities, dtype=np.float32)
+        if self.lib.nnd_perplexity_affinities_device(int(device), dev(stream_ptr), dev(ids_ptr), int(id_bytes), dev(dists_ptr), int(m), int(k),
+                                                     int(ld), int(n), _ptr(scales), int(scales.shape[0]), 1 if squared else 0,
+                                                     1 if symmetrize else 0, 1 if normalize else 0, dev(betas_ptr), C.byref(self._h)) != 0:
+            raise NNDError(self.lib.nnd_last_global_error().decode())
+        self._read(m, n)
+
+
+def perplexity_affinities(ids, dists, n, perplexities=(30.0,), squared=True, symmetrize=True, normalize=True, device=0, want_long_rows=False):
+    """Host k-lists -> t-SNE's perplexity affinities by the device kernels (``nnd_perplexity_affinities``, csrc/affinity.hip).
+    Returns (indptr int64 (m + 1), indices int32, data float32, betas float32 (m, scales))[, rows of the union that took the
+    long-row kernel]."""
+    lib = load_library()
+    ids = np.asarray(ids)
+    ids = np.ascontiguousarray(ids, dtype=np.int64 if ids.dtype == np.int64 else np.int32)
+    dists = np.ascontiguousarray(dists, dtype=np.float32)
+    scales = np.ascontiguousarray(perplexities, dtype=np.float32)
+    assert ids.ndim == 2 and dists.shape == ids.shape and scales.ndim == 1
+    m, k = ids.shape
+    cap = max(1, m * k * (2 if symmetrize else 1))
+    indptr, indices, data = np.empty(m + 1, np.int64), np.empty(cap, np.int32), np.empty(cap, np.float32)
+    betas = np.empty((m, scales.shape[0]), np.float32)
+    nnz, long_rows = C.c_int64(), C.c_int64()
+    if lib.nnd_perplexity_affinities(int(device), _ptr(ids), ids.dtype.itemsize, _ptr(dists), m, k, int(n), _ptr(scales), int(scales.shape[0]),
+                                     1 if squared else 0, 1 if symmetrize else 0, 1 if normalize else 0, _ptr(betas), _ptr(indptr),
+                                     _ptr(indices), _ptr(data), cap, C.byref(nnz), C.byref(long_rows)) != 0:
+        raise NNDError(lib.nnd_last_global_error().decode())
+    out = (indptr, indices[: nnz.value].copy(), data[: nnz.value].copy(), betas)
     return out + (int(long_rows.value),) if want_long_rows else out

@@ -1,4 +1,4 @@
-// csr_graph.h -- what csr_graph.hip shares with the other producer of an nnd_csr_t (fuzzy.hip): the result's struct, the
+// csr_graph.h -- what csr_graph.hip shares with the other producers of an nnd_csr_t (fuzzy.hip, affinity.hip): the result's struct, the
 // error sink of an entry without a handle, and the build of a CSR matrix from int32 k-lists that already lie on the device.
 #pragma once
 #include <stdarg.h>
@@ -42,11 +42,15 @@ struct csr_err {  // the error sink of an entry without a handle: what nnd_last_
     } while (0)
 
 // How the symmetric form joins an entry and its twin: the smaller float (the graph export), or UMAP's fuzzy union of two
-// membership strengths, mix * (a + b - a * b) + (1 - mix) * (a * b), a lone entry mix * a, and no entry where that is 0.
+// membership strengths, mix * (a + b - a * b) + (1 - mix) * (a * b), a lone entry mix * a, and no entry where that is 0; or
+// (sum, affinity.hip) the sum of the two times a scale, (a + b) * scale, a lone entry a * scale, and no entry where that is 0.
 struct csr_combine {
     int fuzzy = 0;
     float mix = 1.0f;
+    int sum = 0;
+    float scale = 1.0f;
 };
+enum { CSR_RULE_MIN = 0, CSR_RULE_FUZZY = 1, CSR_RULE_SUM = 2 };  // the merge kernels' template argument
 
 // The kernels of one export of the int32 k-lists ids / vals (device, row stride ld) on `st`; the result's arrays are allocated
 // in g->mem, the scratch in tmp.  The stream is drained where a total has to reach the host; the caller drains it once more

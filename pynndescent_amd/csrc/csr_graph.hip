@@ -18,8 +18,9 @@
 // the sort by (column, value bits) that follows does not see that order, and where a column appears twice (the edge and its
 // reverse) the entry keeps the smaller of the two floats.  Counts come from integer additions, which commute.
 // No atomic here is anything but an integer add, nothing spins, and every store is a vector store.
-// The merge kernels' FUZZY instances serve fuzzy.hip (through csr_build_i32, csr_graph.h): the twin rule is UMAP's fuzzy union
-// instead of the min, and an entry whose value comes out 0 is dropped where the row's survivors are counted.
+// The merge kernels' CSR_RULE_FUZZY instances serve fuzzy.hip (through csr_build_i32, csr_graph.h): the twin rule is UMAP's
+// fuzzy union instead of the min, and an entry whose value comes out 0 is dropped where the row's survivors are counted.  The
+// CSR_RULE_SUM instances serve affinity.hip the same way: the twin rule is (a + b) * scale.
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -184,9 +185,25 @@ __device__ __forceinline__ uint64_t csr_fuzzy_with_twin(uint64_t key, uint64_t n
     }
     return csr_key((int32_t)csr_key_col(key), v);
 }
-// one stretch of at most W * KU staged keys: sort, collapse equal columns with min (FUZZY: the fuzzy union, and an entry whose
+// The sum of an entry and its twin times a scale, (a + b) * scale; of a lone entry, a * scale.  The sort has put the smaller
+// bits first, so both rows of a pair add the same two operands in the same order and round the same product: (i, j) and
+// (j, i) hold the same bits.
+__device__ __forceinline__ uint64_t csr_sum_with_twin(uint64_t key, uint64_t next, float scale) {
+#pragma clang fp contract(off)
+    float v = csr_key_val(key);
+    if (next != CSR_EMPTY && csr_key_col(next) == csr_key_col(key)) v = v + csr_key_val(next);
+    return csr_key((int32_t)csr_key_col(key), v * scale);
+}
+// an entry joined with its twin by RULE (csr_graph.h); mix is the fuzzy rule's ratio or the sum rule's scale
+template <int RULE>
+__device__ __forceinline__ uint64_t csr_with_twin(uint64_t key, uint64_t next, float mix) {
+    if constexpr (RULE == CSR_RULE_FUZZY) return csr_fuzzy_with_twin(key, next, mix);
+    else if constexpr (RULE == CSR_RULE_SUM) return csr_sum_with_twin(key, next, mix);
+    else return csr_min_with_twin(key, next);
+}
+// one stretch of at most W * KU staged keys: sort, collapse equal columns with min (FUZZY, SUM: their rule, and an entry whose
 // value is 0 goes), write back packed; returns the entries left
-template <int KU, int W, bool FUZZY>
+template <int KU, int W, int RULE>
 __device__ __forceinline__ int csr_union_row(uint64_t *seg, int len, float mix) {
     const int lane = nnd_lane();
     uint64_t key[KU];
@@ -202,8 +219,8 @@ __device__ __forceinline__ int csr_union_row(uint64_t *seg, int len, float mix) 
         const uint64_t before = lane == 0 ? before_out : before_in, after = lane == 63 ? after_out : after_in;
         const bool first = (u == 0 && lane == 0);
         bool keep = key[u] != CSR_EMPTY && (first || csr_key_col(before) != csr_key_col(key[u]));
-        if constexpr (FUZZY) {
-            const uint64_t out = csr_fuzzy_with_twin(key[u], after, mix);
+        if constexpr (RULE != CSR_RULE_MIN) {
+            const uint64_t out = csr_with_twin<RULE>(key[u], after, mix);
             keep = keep && csr_key_val(out) != 0.0f;
             const unsigned long long mask = __ballot(keep);
             if (keep) seg[base + nnd_prefix_popc(mask)] = out;
@@ -217,7 +234,7 @@ __device__ __forceinline__ int csr_union_row(uint64_t *seg, int len, float mix) 
     return base;
 }
 // one wave per row; a stretch of more than CSR_UNION_CAP staged keys is put on the list of k_csr_sym_merge_long
-template <bool FUZZY>
+template <int RULE>
 __global__ __launch_bounds__(256) void k_csr_sym_merge(int64_t n, int32_t k, const int64_t *__restrict__ roff, uint64_t *stage,
                                                        unsigned long long *__restrict__ ucnt, int32_t *__restrict__ long_rows,
                                                        unsigned int *__restrict__ n_long, float mix) {
@@ -230,12 +247,12 @@ __global__ __launch_bounds__(256) void k_csr_sym_merge(int64_t n, int32_t k, con
             continue;
         }
         int left;
-        if (len <= 16) left = csr_union_row<1, 16, FUZZY>(stage + a, (int)len, mix);
-        else if (len <= 32) left = csr_union_row<1, 32, FUZZY>(stage + a, (int)len, mix);
-        else if (len <= 64) left = csr_union_row<1, 64, FUZZY>(stage + a, (int)len, mix);
-        else if (len <= 128) left = csr_union_row<2, 64, FUZZY>(stage + a, (int)len, mix);
-        else if (len <= 256) left = csr_union_row<4, 64, FUZZY>(stage + a, (int)len, mix);
-        else left = csr_union_row<8, 64, FUZZY>(stage + a, (int)len, mix);
+        if (len <= 16) left = csr_union_row<1, 16, RULE>(stage + a, (int)len, mix);
+        else if (len <= 32) left = csr_union_row<1, 32, RULE>(stage + a, (int)len, mix);
+        else if (len <= 64) left = csr_union_row<1, 64, RULE>(stage + a, (int)len, mix);
+        else if (len <= 128) left = csr_union_row<2, 64, RULE>(stage + a, (int)len, mix);
+        else if (len <= 256) left = csr_union_row<4, 64, RULE>(stage + a, (int)len, mix);
+        else left = csr_union_row<8, 64, RULE>(stage + a, (int)len, mix);
         if (lane == 0) ucnt[row] = (unsigned long long)left;
     }
 }
@@ -243,7 +260,7 @@ __global__ __launch_bounds__(256) void k_csr_sym_merge(int64_t n, int32_t k, con
 // lower index (the first step of a merge mirrors the upper half), so the places past the row's end, which would hold +inf,
 // never take part; then the collapse of equal columns, 256 keys at a time from the front (what a piece writes lies at or in
 // front of what it read, and the column of the key in front of a piece is carried over in LDS).
-template <bool FUZZY>
+template <int RULE>
 __global__ __launch_bounds__(256) void k_csr_sym_merge_long(int32_t k, const int64_t *__restrict__ roff, uint64_t *stage,
                                                             unsigned long long *__restrict__ ucnt, const int32_t *__restrict__ long_rows,
                                                             const unsigned int *__restrict__ n_long, float mix) {
@@ -287,8 +304,8 @@ __global__ __launch_bounds__(256) void k_csr_sym_merge_long(int32_t k, const int
             const uint32_t before_col = tid > 0 ? csr_key_col(e - 1 < len ? seg[e - 1] : CSR_EMPTY) : (c0 > 0 ? s_last_col : 0xFFFFFFFFu);
             __syncthreads();  // every read of the piece is done (and s_last_col read) before anything is written
             bool keep = key != CSR_EMPTY && csr_key_col(key) != before_col;
-            const uint64_t out = FUZZY ? csr_fuzzy_with_twin(key, after, mix) : csr_min_with_twin(key, after);
-            if constexpr (FUZZY) keep = keep && csr_key_val(out) != 0.0f;
+            const uint64_t out = csr_with_twin<RULE>(key, after, mix);
+            if constexpr (RULE != CSR_RULE_MIN) keep = keep && csr_key_val(out) != 0.0f;
             const unsigned long long mask = __ballot(keep);
             if (lane == 0) s_wave[w] = __popcll(mask);
             if (tid == 255) s_last_col = csr_key_col(key);  // (only read when another piece follows: then e < len)
@@ -420,12 +437,14 @@ int csr_build(csr_err &err, nnd_scratch &tmp, hipStream_t st, nnd_csr_s *g, cons
         hipLaunchKernelGGL((k_csr_sym_scatter<IdT>), dim3(csr_grid(places, 256, 8192)), dim3(256), 0, st, ids, vals, n, k, ld, drop_self,
                            (const int64_t *)roff, cursor, stage);
         CSR_HIP(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * rows1, st));  // from here on: the rows' final lengths
-        const auto merge = combine.fuzzy ? k_csr_sym_merge<true> : k_csr_sym_merge<false>;
-        const auto merge_long = combine.fuzzy ? k_csr_sym_merge_long<true> : k_csr_sym_merge_long<false>;
+        const auto merge = combine.sum ? k_csr_sym_merge<CSR_RULE_SUM> : (combine.fuzzy ? k_csr_sym_merge<CSR_RULE_FUZZY> : k_csr_sym_merge<CSR_RULE_MIN>);
+        const auto merge_long = combine.sum ? k_csr_sym_merge_long<CSR_RULE_SUM>
+                                            : (combine.fuzzy ? k_csr_sym_merge_long<CSR_RULE_FUZZY> : k_csr_sym_merge_long<CSR_RULE_MIN>);
+        const float mix = combine.sum ? combine.scale : combine.mix;
         hipLaunchKernelGGL(merge, dim3(csr_grid(n, 4, 1 << 20)), dim3(256), 0, st, n, k, (const int64_t *)roff, stage, cnt, long_rows, cursor + n,
-                           combine.mix);
+                           mix);
         hipLaunchKernelGGL(merge_long, dim3(256), dim3(256), 0, st, k, (const int64_t *)roff, stage, cnt, (const int32_t *)long_rows,
-                           (const unsigned int *)(cursor + n), combine.mix);
+                           (const unsigned int *)(cursor + n), mix);
     }
     unsigned int n_long = 0;
     CSR_HIP(hipMemcpyAsync(&n_long, cursor + n, sizeof(unsigned int), hipMemcpyDeviceToHost, st));

@@ -33,7 +33,7 @@ from warnings import warn
 import numpy as np
 from sklearn.utils import check_array, check_random_state
 
-from . import _capi, build, device_arrays, filtered, fuzzy, graph_export, linear_map, row_map, sparse_input, tags as tagwords
+from . import _capi, affinity, build, device_arrays, filtered, fuzzy, graph_export, linear_map, row_map, sparse_input, tags as tagwords
 # Every name below was defined here once and is read here still (tests, tools/, and pickles, which name
 # pynndescent_amd.nndescent.correct_alternative_*): the same objects as in their home modules.  Two are replaced by tests and
 # are therefore CALLED through their home module alone -- ``build.ts()``, ``device_arrays._torch()``.
@@ -949,6 +949,19 @@ class NNDescent:
         bits on every run.  Returns ``scipy.sparse.csr_array`` and numpy arrays for an index of host data or one built with
         ``n_devices`` > 1, a ``torch.sparse_csr_tensor`` and tensors on the index's device for a device-resident index."""
         return fuzzy.index_fuzzy_simplicial_set(self, n_neighbors, set_op_mix_ratio, local_connectivity, bandwidth, apply_set_operations)
+
+    def perplexity_affinities(self, perplexity=30.0, n_neighbors=None, squared=True, symmetrize=True, normalize=True):
+        """t-SNE's perplexity affinities of the built graph, ``(P, betas)``, computed on the GPU (affinity.py,
+        csrc/affinity.hip): the first ``n_neighbors`` columns (default: all, at most 256; t-SNE takes 3 * perplexity) with the
+        distances ``neighbor_graph`` hands out, the row itself left out.  Per row beta solves, by sklearn's binary search on
+        the energies d * d (``squared``) or d, for the conditional distribution exp(-beta e) / sum whose entropy is
+        log(perplexity); a sequence of up to 4 perplexities gives the mean of their distributions (multiscale) and ``betas``
+        of shape (n, S).  ``symmetrize`` adds the transpose, ``normalize`` divides by the total of the matrix;
+        ``symmetrize=False`` is the row-normalised conditional matrix.  A (-1, inf) place adds nothing to any sum.  The result
+        is exactly symmetric and the same bits on every run.  Returns ``scipy.sparse.csr_array`` and a numpy array for an
+        index of host data or one built with ``n_devices`` > 1, a ``torch.sparse_csr_tensor`` and a tensor on the index's
+        device for a device-resident index."""
+        return affinity.index_perplexity_affinities(self, perplexity, n_neighbors, squared, symmetrize, normalize)
 
     def _query_sparse(self, query_data, m, k, epsilon, proxy_beam_size, filter, filter_mode):
         """``query`` for a ``scipy.sparse`` batch, on an index built from sparse or dense data alike: the batch is made canonical,
