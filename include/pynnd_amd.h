@@ -818,6 +818,22 @@ int32_t nnd_perplexity_affinities(int32_t device, const void *ids, int32_t id_by
                                   float *betas, int64_t *indptr, int32_t *indices, float *data, int64_t capacity, int64_t *nnz,
                                   int64_t *long_rows);
 
+/* ---- shared-neighbour graph: SNN / Jaccard weights of the k-NN edges (csrc/snn.hip; DESIGN.md "Shared-neighbour graph") ----
+ * ids: (m, k) as above, square (row i is point i), 2 <= k <= 256; a place whose id is outside [0, m) is empty.  O(i): the
+ * distinct ids of row i other than i; N(i) = O(i) + {i} (include_self) or O(i).  Every i and j in O(i) is an edge with
+ * c = |N(i) & N(j)| and u = |N(i)| + |N(j)| - c; its weight is (float)c (NND_SNN_COUNT) or the correctly rounded float32
+ * quotient c / u (NND_SNN_JACCARD), stored iff w > 0 and w >= prune (prune >= 0).  symmetric: the union with the transpose;
+ * both directions hold the same bits, so the matrix is exactly symmetric.  No diagonal.  The result is an nnd_csr_t as above
+ * (nnd_csr_arrays, nnd_csr_destroy); nnd_snn_graph is the same on host arrays, with the room rules of nnd_graph_csr.  Same
+ * bits on every run. */
+#define NND_SNN_JACCARD 0
+#define NND_SNN_COUNT 1
+int32_t nnd_snn_graph_device(int32_t device, void *hip_stream, const void *ids_dev, int32_t id_bytes, int64_t m, int32_t k, int64_t ld,
+                             int32_t weight, int32_t include_self, float prune, int32_t symmetric, nnd_csr_t *out);
+int32_t nnd_snn_graph(int32_t device, const void *ids, int32_t id_bytes, int64_t m, int32_t k, int32_t weight, int32_t include_self,
+                      float prune, int32_t symmetric, int64_t *indptr, int32_t *indices, float *data, int64_t capacity, int64_t *nnz,
+                      int64_t *long_rows);
+
 #ifdef __cplusplus
 }
 #endif

@@ -45,6 +45,7 @@ NND_CORRECT_HAVERSINE = 5
 NND_LINEAR_DIAGONAL, NND_LINEAR_DENSE = 0, 1  # the kinds of a metric's linear map (include/pynnd_amd.h NND_LINEAR_*, csrc/linear.hip)
 NND_CSR_DISTANCE, NND_CSR_CONNECTIVITY, NND_CSR_DROP_SELF = 0, 1, 2  # nnd_graph_csr's `mode` (csrc/csr_graph.hip); DROP_SELF is or-ed in
 CSR_MAX_K = 256  # the widest k-list nnd_graph_csr takes (csrc/csr_graph.hip CSR_REG_CAP)
+SNN_WEIGHTS = {"jaccard": 0, "count": 1}  # NND_SNN_JACCARD, NND_SNN_COUNT
 AFFINITY_MAX_SCALES = 4  # the most perplexities of one nnd_perplexity_affinities call (csrc/affinity.hip AF_MAX_SCALES)
 NND_ROWMAP_RANK, NND_ROWMAP_SPHERE = 0, 1  # the kinds of a derived metric's row map (include/pynnd_amd.h NND_ROWMAP_*, csrc/rowmap.hip)
 ROWMAP_RANK_MAX_DIM = 16384  # the widest row nnd_device_map_rows ranks (csrc/rowmap.hip RM_RANK_MAX)
@@ -371,6 +372,10 @@ _SIGNATURES = [
     ("nnd_perplexity_affinities", C.c_int32, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_int32,
                                               C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                               C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    ("nnd_snn_graph_device", C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
+                                         C.c_float, C.c_int32, C.POINTER(_H)]),
+    ("nnd_snn_graph", C.c_int32, [C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
 ]
 EXPORTED_SYMBOLS = [s[0] for s in _SIGNATURES]
 
@@ -1381,4 +1386,44 @@ def perplexity_affinities(ids, dists, n, perplexities=(30.0,), squared=True, sym
                                      _ptr(indices), _ptr(data), cap, C.byref(nnz), C.byref(long_rows)) != 0:
         raise NNDError(lib.nnd_last_global_error().decode())
     out = (indptr, indices[: nnz.value].copy(), data[: nnz.value].copy(), betas)
+    return out + (int(long_rows.value),) if want_long_rows else out
+
+
+def _snn_weight(weight):
+    """``"jaccard"`` / ``"count"`` as nnd_snn_graph's ``weight``."""
+    if weight not in SNN_WEIGHTS:
+        raise ValueError("weight must be one of %s (got %r)" % (", ".join(SNN_WEIGHTS), weight))
+    return SNN_WEIGHTS[weight]
+
+
+class DeviceSnnGraph(DeviceCsr):
+    """Device k-lists -> the shared-neighbour graph where they lie (``nnd_snn_graph_device``, csrc/snn.hip): the ids of
+    ``DeviceCsr`` (square: m rows, m columns), the weight's name, the two switches and the pruning bound.  The CSR arrays are
+    owned and handed out as there."""
+
+    def __init__(self, device, stream_ptr, ids_ptr, id_bytes, m, k, ld, weight, include_self, prune, symmetric):
+        self.lib = load_library()
+        self._h = _H()
+        dev = lambda p: C.c_void_p(int(p)) if p else None  # noqa: E731
+        if self.lib.nnd_snn_graph_device(int(device), dev(stream_ptr), dev(ids_ptr), int(id_bytes), int(m), int(k), int(ld), _snn_weight(weight),
+                                         1 if include_self else 0, float(prune), 1 if symmetric else 0, C.byref(self._h)) != 0:
+            raise NNDError(self.lib.nnd_last_global_error().decode())
+        self._read(m, m)
+
+
+def snn_graph(ids, weight="jaccard", include_self=True, prune=0.0, symmetric=True, device=0, want_long_rows=False):
+    """Host k-lists -> the shared-neighbour graph by the device kernels (``nnd_snn_graph``, csrc/snn.hip).  Returns (indptr
+    int64 (m + 1), indices int32, data float32)[, rows of the union that took the long-row kernel]."""
+    lib = load_library()
+    ids = np.asarray(ids)
+    ids = np.ascontiguousarray(ids, dtype=np.int64 if ids.dtype == np.int64 else np.int32)
+    assert ids.ndim == 2
+    m, k = ids.shape
+    cap = max(1, m * k * (2 if symmetric else 1))
+    indptr, indices, data = np.empty(m + 1, np.int64), np.empty(cap, np.int32), np.empty(cap, np.float32)
+    nnz, long_rows = C.c_int64(), C.c_int64()
+    if lib.nnd_snn_graph(int(device), _ptr(ids), ids.dtype.itemsize, m, k, _snn_weight(weight), 1 if include_self else 0, float(prune),
+                         1 if symmetric else 0, _ptr(indptr), _ptr(indices), _ptr(data), cap, C.byref(nnz), C.byref(long_rows)) != 0:
+        raise NNDError(lib.nnd_last_global_error().decode())
+    out = (indptr, indices[: nnz.value].copy(), data[: nnz.value].copy())
     return out + (int(long_rows.value),) if want_long_rows else out

@@ -33,7 +33,7 @@ from warnings import warn
 import numpy as np
 from sklearn.utils import check_array, check_random_state
 
-from . import _capi, affinity, build, device_arrays, filtered, fuzzy, graph_export, linear_map, row_map, sparse_input, tags as tagwords
+from . import _capi, affinity, build, device_arrays, filtered, fuzzy, graph_export, linear_map, row_map, snn, sparse_input, tags as tagwords
 # Every name below was defined here once and is read here still (tests, tools/, and pickles, which name
 # pynndescent_amd.nndescent.correct_alternative_*): the same objects as in their home modules.  Two are replaced by tests and
 # are therefore CALLED through their home module alone -- ``build.ts()``, ``device_arrays._torch()``.
@@ -962,6 +962,17 @@ class NNDescent:
         index of host data or one built with ``n_devices`` > 1, a ``torch.sparse_csr_tensor`` and a tensor on the index's
         device for a device-resident index."""
         return affinity.index_perplexity_affinities(self, perplexity, n_neighbors, squared, symmetrize, normalize)
+
+    def shared_neighbor_graph(self, n_neighbors=None, weight="jaccard", include_self=True, prune=0.0, symmetric=True):
+        """The shared-nearest-neighbour graph of the built graph, the matrix graph clustering (Leiden, Louvain) runs on,
+        computed on the GPU (snn.py, csrc/snn.hip): the first ``n_neighbors`` columns (default: all).  Every k-NN edge (i, j)
+        is weighted by the neighbours its ends share: with N(i) the neighbours of i, and i itself if ``include_self``,
+        ``weight="count"`` gives |N(i) & N(j)| (scran's ``"number"``) and ``"jaccard"`` |N(i) & N(j)| / |N(i) | N(j)| (PhenoGraph,
+        Seurat's ``FindNeighbors``, scran's ``"jaccard"``).  An entry is stored when it is above 0 and at least ``prune``
+        (Seurat's ``prune.SNN``); ``symmetric`` joins the matrix with its transpose.  The result has no diagonal, is exactly
+        symmetric and the same bits on every run.  Returns a ``scipy.sparse.csr_array`` for an index of host data or one built
+        with ``n_devices`` > 1, a ``torch.sparse_csr_tensor`` on the index's device for a device-resident index."""
+        return snn.index_shared_neighbor_graph(self, n_neighbors, weight, include_self, prune, symmetric)
 
     def _query_sparse(self, query_data, m, k, epsilon, proxy_beam_size, filter, filter_mode):
         """``query`` for a ``scipy.sparse`` batch, on an index built from sparse or dense data alike: the batch is made canonical,
