@@ -834,6 +834,24 @@ int32_t nnd_snn_graph(int32_t device, const void *ids, int32_t id_bytes, int64_t
                       float prune, int32_t symmetric, int64_t *indptr, int32_t *indices, float *data, int64_t capacity, int64_t *nnz,
                       int64_t *long_rows);
 
+/* ---- spanning forest: mutual-reachability MST and connected components (csrc/mst.hip; DESIGN.md "Spanning forest") ----
+ * ids / dists: (m, k) as above, square (row i is point i), 1 <= k <= 256, row strides ld_ids / ld_dists elements.  A place is
+ * live when 0 <= id < m, id != i and its distance is finite and >= 0 (-0.0 is +0.0).  core(i): 0 when min_samples == 0, else
+ * (1 <= min_samples <= k) the min_samples-th smallest distance among row i's places with a valid id and a valid distance, the
+ * row's own place included when it is listed; with fewer such places the largest, with none 0.  A live place has the weight
+ * w = max(core(i), core(j), d); the key of an undirected edge is (bits of w, min(i, j), max(i, j)), the smallest copy of a pair
+ * counting.  The result is the unique minimum spanning forest under that order (Kruskal over the sorted keys) as an exactly
+ * symmetric canonical CSR matrix of the weights, zeros stored: an nnd_csr_t as above (nnd_csr_arrays, nnd_csr_destroy).
+ * labels: int32 (m), the connected component of every point, numbered by ascending smallest member; core: float32 (m); both
+ * written by the call.  *rounds (may be NULL): the Boruvka rounds that joined components.  nnd_spanning_forest is the same on
+ * host arrays (contiguous rows), with the room rules of nnd_graph_csr: 2 * m entries always suffice.  Same bits on every run. */
+int32_t nnd_spanning_forest_device(int32_t device, void *hip_stream, const void *ids_dev, int32_t id_bytes, const float *dists_dev, int64_t m,
+                                   int32_t k, int64_t ld_ids, int64_t ld_dists, int32_t min_samples, int32_t *labels_dev, float *core_dev,
+                                   int32_t *rounds, nnd_csr_t *out);
+int32_t nnd_spanning_forest(int32_t device, const void *ids, int32_t id_bytes, const float *dists, int64_t m, int32_t k, int32_t min_samples,
+                            int32_t *labels, float *core, int32_t *rounds, int64_t *indptr, int32_t *indices, float *data, int64_t capacity,
+                            int64_t *nnz);
+
 #ifdef __cplusplus
 }
 #endif

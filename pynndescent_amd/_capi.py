@@ -376,6 +376,10 @@ _SIGNATURES = [
                                          C.c_float, C.c_int32, C.POINTER(_H)]),
     ("nnd_snn_graph", C.c_int32, [C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    ("nnd_spanning_forest_device", C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64,
+                                               C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(_H)]),
+    ("nnd_spanning_forest", C.c_int32, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                        C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
 ]
 EXPORTED_SYMBOLS = [s[0] for s in _SIGNATURES]
 
@@ -1427,3 +1431,44 @@ def snn_graph(ids, weight="jaccard", include_self=True, prune=0.0, symmetric=Tru
         raise NNDError(lib.nnd_last_global_error().decode())
     out = (indptr, indices[: nnz.value].copy(), data[: nnz.value].copy())
     return out + (int(long_rows.value),) if want_long_rows else out
+
+
+class DeviceSpanningForest(DeviceCsr):
+    """Device k-lists -> the minimum spanning forest of their mutual-reachability graph where they lie
+    (``nnd_spanning_forest_device``, csrc/mst.hip): the ids and distances of ``DeviceCsr`` (square: m rows, m columns) with a
+    row stride each, ``min_samples``, and the device addresses of an int32 (m) and a float32 (m) array the call fills with the
+    component labels and the core distances.  ``rounds``: the Boruvka rounds that joined components.  The CSR arrays are owned
+    and handed out as there."""
+
+    def __init__(self, device, stream_ptr, ids_ptr, id_bytes, dists_ptr, m, k, ld_ids, ld_dists, min_samples, labels_ptr, core_ptr):
+        self.lib = load_library()
+        self._h = _H()
+        dev = lambda p: C.c_void_p(int(p)) if p else None  # noqa: E731
+        rounds = C.c_int32()
+        if self.lib.nnd_spanning_forest_device(int(device), dev(stream_ptr), dev(ids_ptr), int(id_bytes), dev(dists_ptr), int(m), int(k), int(ld_ids),
+                                               int(ld_dists), int(min_samples), dev(labels_ptr), dev(core_ptr), C.byref(rounds),
+                                               C.byref(self._h)) != 0:
+            raise NNDError(self.lib.nnd_last_global_error().decode())
+        self.rounds = int(rounds.value)
+        self._read(m, m)
+
+
+def spanning_forest(ids, dists, min_samples=5, device=0, want_rounds=False):
+    """Host k-lists -> the minimum spanning forest of their mutual-reachability graph by the device kernels
+    (``nnd_spanning_forest``, csrc/mst.hip).  Returns (indptr int64 (m + 1), indices int32, data float32, labels int32 (m),
+    core float32 (m))[, the rounds that joined components]."""
+    lib = load_library()
+    ids = np.asarray(ids)
+    ids = np.ascontiguousarray(ids, dtype=np.int64 if ids.dtype == np.int64 else np.int32)
+    dists = np.ascontiguousarray(dists, dtype=np.float32)
+    assert ids.ndim == 2 and dists.shape == ids.shape
+    m, k = ids.shape
+    cap = max(1, 2 * m)  # a forest has fewer than m edges
+    indptr, indices, data = np.empty(m + 1, np.int64), np.empty(cap, np.int32), np.empty(cap, np.float32)
+    labels, core = np.empty(m, np.int32), np.empty(m, np.float32)
+    nnz, rounds = C.c_int64(), C.c_int32()
+    if lib.nnd_spanning_forest(int(device), _ptr(ids), ids.dtype.itemsize, _ptr(dists), m, k, int(min_samples), _ptr(labels), _ptr(core),
+                               C.byref(rounds), _ptr(indptr), _ptr(indices), _ptr(data), cap, C.byref(nnz)) != 0:
+        raise NNDError(lib.nnd_last_global_error().decode())
+    out = (indptr, indices[: nnz.value].copy(), data[: nnz.value].copy(), labels, core)
+    return out + (int(rounds.value),) if want_rounds else out

@@ -33,7 +33,7 @@ from warnings import warn
 import numpy as np
 from sklearn.utils import check_array, check_random_state
 
-from . import _capi, affinity, build, device_arrays, filtered, fuzzy, graph_export, linear_map, row_map, snn, sparse_input, tags as tagwords
+from . import _capi, affinity, build, device_arrays, filtered, fuzzy, graph_export, linear_map, row_map, snn, spanning, sparse_input, tags as tagwords
 # Every name below was defined here once and is read here still (tests, tools/, and pickles, which name
 # pynndescent_amd.nndescent.correct_alternative_*): the same objects as in their home modules.  Two are replaced by tests and
 # are therefore CALLED through their home module alone -- ``build.ts()``, ``device_arrays._torch()``.
@@ -973,6 +973,18 @@ class NNDescent:
         symmetric and the same bits on every run.  Returns a ``scipy.sparse.csr_array`` for an index of host data or one built
         with ``n_devices`` > 1, a ``torch.sparse_csr_tensor`` on the index's device for a device-resident index."""
         return snn.index_shared_neighbor_graph(self, n_neighbors, weight, include_self, prune, symmetric)
+
+    def spanning_forest(self, min_samples=5, n_neighbors=None):
+        """The minimum spanning forest of the built graph under mutual reachability, ``(forest, labels, core_distances)``,
+        computed on the GPU (spanning.py, csrc/mst.hip): the first ``n_neighbors`` columns (default: all) with the distances
+        ``neighbor_graph`` hands out.  ``core_distances[i]`` is the ``min_samples``-th smallest distance of row i, the point
+        itself counted as sklearn's HDBSCAN counts it (``min_samples=0``: all 0, plain single linkage); an edge weighs
+        max(core(i), core(j), d) and ties are broken by (weight, min(i, j), max(i, j)), so ``forest`` -- exactly symmetric,
+        zero weights stored -- is a function of the graph and the same bits on every run.  ``labels`` holds the connected
+        component of every point, numbered as ``scipy.sparse.csgraph.connected_components`` numbers them.  Returns a
+        ``scipy.sparse.csr_array`` and numpy arrays for an index of host data or one built with ``n_devices`` > 1, a
+        ``torch.sparse_csr_tensor`` and tensors on the index's device for a device-resident index."""
+        return spanning.index_spanning_forest(self, min_samples, n_neighbors)
 
     def _query_sparse(self, query_data, m, k, epsilon, proxy_beam_size, filter, filter_mode):
         """``query`` for a ``scipy.sparse`` batch, on an index built from sparse or dense data alike: the batch is made canonical,
