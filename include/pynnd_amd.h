@@ -151,6 +151,8 @@ typedef struct nnd_params {
 /* test hook: nnd_init_random launches one wave per row (the earlier form) where it would let one wave screen 64 rows and work on
  * those that are not full: the two forms must leave identical k-lists (tests/test_gpu_random_init.py) */
 #define NND_FLAG_TEST_RANDOM_INIT_ROWWISE 65536
+/* test hook: nnd_spanning_tree* answers every query row through the float64 tier (tests/test_gpu_spanning_tree.py compares the two) */
+#define NND_FLAG_TEST_TREE_F64 131072
 
 /* Run-time statistics for measurement (bench.py roofline). */
 typedef struct nnd_stats {
@@ -851,6 +853,34 @@ int32_t nnd_spanning_forest_device(int32_t device, void *hip_stream, const void 
 int32_t nnd_spanning_forest(int32_t device, const void *ids, int32_t id_bytes, const float *dists, int64_t m, int32_t k, int32_t min_samples,
                             int32_t *labels, float *core, int32_t *rounds, int64_t *indptr, int32_t *indices, float *data, int64_t capacity,
                             int64_t *nnz);
+
+/* ---- spanning tree: the forest's components joined by their lightest cross-component edges (csrc/cross.hip; DESIGN.md
+ * "Spanning tree") ----
+ * The handle holds the m = n rows (metric code 0 or 1, one device, NND_FLAG_NO_GRAPH suffices); ids / dists are square k-lists
+ * of those rows, as for nnd_spanning_forest.  F, core: the spanning forest of the lists and its core distances.  For i, j in
+ * different components of F, w(i, j) = max(core(i), core(j), d(i, j)) in float32, d the float32 rounding of the float64 distance
+ * of the rows as given in the metric's own space: metric 0 the squared distance, or its square root with `euclidean`; metric 1
+ * 1 - 2^-v of the alternative cosine v.  A pair whose d is not finite is no edge.  The key of a pair is (bits of w, min(i, j),
+ * max(i, j)); the weight between two components is the smallest key over their cross pairs; C is the unique minimum spanning
+ * tree of the complete graph of the components under that order.  The result is F + C as an exactly symmetric canonical CSR
+ * matrix, zeros stored (an nnd_csr_t; the host form has the room rules of nnd_graph_csr, 2 * m entries always suffice): m - 1
+ * edges unless components have no finite weight between them.  It is NOT the minimum spanning tree of the complete
+ * mutual-reachability graph.  core: float32 (m), written by the call.  The device form runs on the handle's stream and reads
+ * one counter block per round.  Same bits on every run. */
+typedef struct nnd_tree_stats {
+    int32_t n_components;   /* of the forest, before the joining */
+    int32_t forest_rounds;  /* the forest's Boruvka rounds that joined components */
+    int32_t rounds;         /* the joining rounds that hooked */
+    int32_t slices;         /* the most data slices a scan was split into */
+    int64_t query_rows;     /* the points outside the largest component in the first round */
+    int64_t query_rows_all; /* ... summed over the rounds */
+    int64_t tier2_rows;     /* query rows (over all rounds) the float64 tier answered */
+    int64_t mfma;           /* v_mfma_f32_16x16x4_f32 issued by the scans, per wave */
+} nnd_tree_stats;
+int32_t nnd_spanning_tree_device(nnd_handle_t h, const void *ids_dev, int32_t id_bytes, const float *dists_dev, int32_t k, int64_t ld_ids,
+                                 int64_t ld_dists, int32_t min_samples, int32_t euclidean, float *core_dev, nnd_tree_stats *stats, nnd_csr_t *out);
+int32_t nnd_spanning_tree(nnd_handle_t h, const void *ids, int32_t id_bytes, const float *dists, int32_t k, int32_t min_samples, int32_t euclidean,
+                          float *core, nnd_tree_stats *stats, int64_t *indptr, int32_t *indices, float *data, int64_t capacity, int64_t *nnz);
 
 #ifdef __cplusplus
 }

@@ -8,7 +8,7 @@ from .affinity import perplexity_affinities  # noqa: F401
 from .fuzzy import fuzzy_simplicial_set  # noqa: F401
 from .graph_export import PyNNDescentTransformer  # noqa: F401
 from .snn import shared_neighbor_graph  # noqa: F401
-from .spanning import spanning_forest  # noqa: F401
+from .spanning import spanning_forest, spanning_tree  # noqa: F401
 from .nndescent import EMPTY_GRAPH, NNDescent, exact_knn, make_index, nn_descent  # noqa: F401
 
 __version__ = "0.1.0"

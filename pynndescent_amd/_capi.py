@@ -65,6 +65,7 @@ NND_FLAG_TEST_SELECT_HALF = 4096  # test hook: the fused selection with 32 lanes
 NND_FLAG_TEST_SAMPLE_NOMEM = 2048  # test hook: the sampler's record regions "cannot be allocated": the handle must fall back to the hashed slots
 NND_FLAG_TEST_EXACT_F64 = 32768  # test hook: the exact search answers every row through its float64 tier
 NND_FLAG_TEST_RANDOM_INIT_ROWWISE = 65536  # test hook: init_random with one wave per row instead of one screening wave per 64 rows
+NND_FLAG_TEST_TREE_F64 = 131072  # test hook: the spanning tree answers every query row through its float64 tier
 NND_FLAG_TEST_SAMPLE_ATOMIC = 256  # test hook: reverse offers by one global atomicMin per edge (rounds 1-4) instead of the bucketed transposition
 
 
@@ -178,6 +179,15 @@ class NNDShardInfo(C.Structure):
 
 HOST_EXCHANGE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p,
                                C.POINTER(C.c_int64), C.POINTER(C.c_int64))
+
+
+class NNDTreeStats(C.Structure):
+    """``nnd_tree_stats``: what a spanning-tree call did (include/pynnd_amd.h)."""
+    _fields_ = [("n_components", C.c_int32), ("forest_rounds", C.c_int32), ("rounds", C.c_int32), ("slices", C.c_int32),
+                ("query_rows", C.c_int64), ("query_rows_all", C.c_int64), ("tier2_rows", C.c_int64), ("mfma", C.c_int64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
 class NNDExactStats(C.Structure):
@@ -380,6 +390,10 @@ _SIGNATURES = [
                                                C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(_H)]),
     ("nnd_spanning_forest", C.c_int32, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                         C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    ("nnd_spanning_tree_device", C.c_int32, [_H, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
+                                             C.POINTER(NNDTreeStats), C.POINTER(_H)]),
+    ("nnd_spanning_tree", C.c_int32, [_H, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(NNDTreeStats),
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
 ]
 EXPORTED_SYMBOLS = [s[0] for s in _SIGNATURES]
 
@@ -1472,3 +1486,36 @@ def spanning_forest(ids, dists, min_samples=5, device=0, want_rounds=False):
         raise NNDError(lib.nnd_last_global_error().decode())
     out = (indptr, indices[: nnz.value].copy(), data[: nnz.value].copy(), labels, core)
     return out + (int(rounds.value),) if want_rounds else out
+
+
+class DeviceSpanningTree(DeviceCsr):
+    """Device k-lists of the rows a ``Builder`` holds -> the spanning tree where they lie (``nnd_spanning_tree_device``,
+    csrc/cross.hip), on the handle's stream: the ids and distances with a row stride each, ``min_samples``, ``euclidean`` (metric
+    code 0: weights are square roots), and the device address of a float32 (m) array the call fills with the core distances.
+    ``stats``: the call's ``nnd_tree_stats`` as a dict.  The CSR arrays are owned and handed out as by ``DeviceCsr``."""
+
+    def __init__(self, builder, ids_ptr, id_bytes, dists_ptr, k, ld_ids, ld_dists, min_samples, euclidean, core_ptr):
+        self.lib = load_library()
+        self._h = _H()
+        dev = lambda p: C.c_void_p(int(p)) if p else None  # noqa: E731
+        st = NNDTreeStats()
+        builder._check(self.lib.nnd_spanning_tree_device(builder._h, dev(ids_ptr), int(id_bytes), dev(dists_ptr), int(k), int(ld_ids), int(ld_dists),
+                                                         int(min_samples), 1 if euclidean else 0, dev(core_ptr), C.byref(st), C.byref(self._h)))
+        self.stats = st.as_dict()
+        self._read(builder.n, builder.n)
+
+
+def spanning_tree(builder, ids, dists, min_samples=5, euclidean=True):
+    """Host k-lists of the rows a ``Builder`` holds -> the spanning tree by the device kernels (``nnd_spanning_tree``,
+    csrc/cross.hip).  Returns (indptr int64 (m + 1), indices int32, data float32, core float32 (m), the call's statistics)."""
+    ids = np.asarray(ids)
+    ids = np.ascontiguousarray(ids, dtype=np.int64 if ids.dtype == np.int64 else np.int32)
+    dists = np.ascontiguousarray(dists, dtype=np.float32)
+    assert ids.ndim == 2 and dists.shape == ids.shape and ids.shape[0] == builder.n
+    m, k = ids.shape
+    cap = max(1, 2 * m)  # a tree has fewer than m edges
+    indptr, indices, data, core = np.empty(m + 1, np.int64), np.empty(cap, np.int32), np.empty(cap, np.float32), np.empty(m, np.float32)
+    nnz, st = C.c_int64(), NNDTreeStats()
+    builder._check(builder.lib.nnd_spanning_tree(builder._h, _ptr(ids), ids.dtype.itemsize, _ptr(dists), k, int(min_samples), 1 if euclidean else 0,
+                                                 _ptr(core), C.byref(st), _ptr(indptr), _ptr(indices), _ptr(data), cap, C.byref(nnz)))
+    return indptr, indices[: nnz.value].copy(), data[: nnz.value].copy(), core, st.as_dict()

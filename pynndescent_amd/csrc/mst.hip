@@ -46,10 +46,7 @@
 #include "../../include/pynnd_amd.h"
 #include "common.h"
 #include "csr_graph.h"
-
-#define MST_EMPTY 0xFFFFFFFFFFFFFFFFull  // no key: above every (w, lo)
-#define MST_NO_KEY 0xFFFFFFFFu           // the distance bits of a place that does not count; no hi
-#define MST_FAULT 0x80000000u            // in a round's hook counter: a device loop met its bound, or a key was not whole
+#include "mst.h"
 
 // the bits of a ballot that belong to this lane's group, moved down to bit 0
 template <int W>
@@ -133,23 +130,6 @@ __global__ __launch_bounds__(256) void k_mst_weights(const int32_t *__restrict__
 }
 
 // ---------------------------------------------------------------------------------------------- the rounds' state
-struct mst_state {
-    int64_t m;
-    int32_t cols;                // the columns of edge_ids / edge_w: one per round
-    int32_t *comp, *comp_next;   // the component (a root's id) of every point
-    int32_t *parent;             // of a root: itself, or the root it hooked to
-    unsigned long long *best1;   // per root: the smallest (w bits << 32 | lo) of its rows
-    uint32_t *best2;             // ... and the smallest hi among the rows that hold it
-    unsigned long long *rec1;    // per row: its own smallest key
-    uint32_t *rec2;
-    unsigned char *dead;         // the row has no edge that leaves its component
-    int32_t *edge_ids;           // (m, cols): the forest edge row i won in a round, -1
-    float *edge_w;
-    unsigned int *hooks;         // [cols + 1]: the hooks of a round, MST_FAULT
-    int32_t *smallest;           // per root: its smallest member
-    int32_t *flag, *pos;         // 1 at a smallest member; the exclusive sums
-};
-
 __global__ __launch_bounds__(256) void k_mst_init(mst_state s) {
     const int64_t total = s.m * (int64_t)s.cols;
     for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
@@ -274,28 +254,6 @@ __global__ __launch_bounds__(256) void k_mst_labels_rank(mst_state s, int32_t *_
 }
 
 // ---------------------------------------------------------------------------------------------- host side
-namespace {
-size_t mst_room(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-struct mst_carve {
-    unsigned char *base = nullptr;
-    size_t at = 0;
-    template <typename T>
-    T *take(size_t count) {
-        T *p = (T *)(base + at);
-        at += mst_room(sizeof(T) * (count ? count : 1));
-        return p;
-    }
-};
-unsigned mst_grid(int64_t items, int per_block) {
-    const int64_t b = (items + per_block - 1) / per_block;
-    return (unsigned)(b < 1 ? 1 : (b > (1 << 20) ? (1 << 20) : b));
-}
-int mst_ceil_log2(int64_t m) {
-    int r = 0;
-    while (((int64_t)1 << r) < m) r++;
-    return r;
-}
-
 int mst_check(csr_err &err, const char *who, const void *ids, int32_t id_bytes, const float *dists, int64_t m, int32_t k, int64_t ld_ids,
               int64_t ld_dists, int32_t min_samples, const int32_t *labels, const float *core) {
     if (m < 0 || k < 1 || k > CSR_REG_CAP || ld_ids < k || ld_dists < k || m >= (int64_t)0x7FFFFFF0) {
@@ -309,6 +267,7 @@ int mst_check(csr_err &err, const char *who, const void *ids, int32_t id_bytes, 
     return 0;
 }
 
+namespace {
 template <typename IdT>
 void mst_launch_core(hipStream_t st, const IdT *ids, const float *dists, int64_t m, int32_t k, int64_t ld_ids, int64_t ld_dists, int32_t min_samples,
                      int32_t *clean, float *core) {
@@ -359,12 +318,11 @@ int mst_rounds(csr_err &err, hipStream_t st, const nnd_csr_s &sym, mst_state &s,
     return 1;
 }
 
-template <typename IdT>
-int mst_build(csr_err &err, nnd_scratch &tmp, nnd_csr_s &sym, hipStream_t st, nnd_csr_s *g, const IdT *ids, const float *dists, int64_t m, int32_t k,
-              int64_t ld_ids, int64_t ld_dists, int32_t min_samples, int32_t *labels, float *core, int32_t *rounds_out) {
-    if (rounds_out) *rounds_out = 0;
-    if (m == 0) return csr_build_i32(err, tmp, st, g, nullptr, nullptr, 0, 1, 1, 1, 0, csr_combine());
-    mst_state s;
+}  // namespace
+
+int mst_forest_rounds(csr_err &err, nnd_scratch &tmp, nnd_csr_s &sym, hipStream_t st, const void *ids, int32_t id_bytes, const float *dists, int64_t m,
+                      int32_t k, int64_t ld_ids, int64_t ld_dists, int32_t min_samples, float *core, mst_work &w, int *rounds) {
+    mst_state &s = w.s;
     s.m = m;
     s.cols = mst_ceil_log2(m) + 1;
     const size_t rows = (size_t)m, places = rows * (size_t)k, slots = rows * (size_t)s.cols;
@@ -387,22 +345,45 @@ int mst_build(csr_err &err, nnd_scratch &tmp, nnd_csr_s &sym, hipStream_t st, nn
     s.best1 = c.take<unsigned long long>(rows); s.rec1 = c.take<unsigned long long>(rows);
     s.best2 = c.take<uint32_t>(rows); s.dead = c.take<unsigned char>(rows);
     s.hooks = c.take<unsigned int>((size_t)s.cols + 1);
-    unsigned char *scan_tmp = c.take<unsigned char>(scan_bytes + 256);
+    w.scan_tmp = c.take<unsigned char>(scan_bytes + 256);
+    w.scan_bytes = scan_bytes;
 
     CSR_HIP(hipMemsetAsync(s.hooks, 0, sizeof(unsigned int) * ((size_t)s.cols + 1), st));
-    mst_launch_core<IdT>(st, ids, dists, m, k, ld_ids, ld_dists, min_samples, clean, core);
+    if (id_bytes == 4) mst_launch_core<int32_t>(st, (const int32_t *)ids, dists, m, k, ld_ids, ld_dists, min_samples, clean, core);
+    else mst_launch_core<int64_t>(st, (const int64_t *)ids, dists, m, k, ld_ids, ld_dists, min_samples, clean, core);
     hipLaunchKernelGGL(k_mst_weights, dim3(mst_grid((int64_t)places, 256)), dim3(256), 0, st, (const int32_t *)clean, dists, m, k, ld_dists,
                        (const float *)core, weights);
     hipLaunchKernelGGL(k_mst_init, dim3(mst_grid((int64_t)slots, 256)), dim3(256), 0, st, s);
     CSR_HIP(hipGetLastError());
     if (csr_build_i32(err, tmp, st, &sym, clean, weights, m, k, k, m, 1, csr_combine())) return 1;  // the min-union
+    return mst_rounds(err, st, sym, s, rounds);
+}
+
+void mst_launch_join(hipStream_t st, mst_state &s, int32_t round) {
+    const dim3 rows(mst_grid(s.m, 256)), block(256);
+    hipLaunchKernelGGL(k_mst_pick, rows, block, 0, st, s);
+    hipLaunchKernelGGL(k_mst_hook, rows, block, 0, st, s, round);
+    hipLaunchKernelGGL(k_mst_jump, rows, block, 0, st, s, round);  // (nothing hooked: every root stays its own parent)
+    hipLaunchKernelGGL(k_mst_flatten, rows, block, 0, st, s);
+    int32_t *t = s.comp;
+    s.comp = s.comp_next;
+    s.comp_next = t;
+}
+
+namespace {
+int mst_build(csr_err &err, nnd_scratch &tmp, nnd_csr_s &sym, hipStream_t st, nnd_csr_s *g, const void *ids, int32_t id_bytes, const float *dists, int64_t m,
+              int32_t k, int64_t ld_ids, int64_t ld_dists, int32_t min_samples, int32_t *labels, float *core, int32_t *rounds_out) {
+    if (rounds_out) *rounds_out = 0;
+    if (m == 0) return csr_build_i32(err, tmp, st, g, nullptr, nullptr, 0, 1, 1, 1, 0, csr_combine());
+    mst_work w;
     int rounds = 0;
-    if (mst_rounds(err, st, sym, s, &rounds)) return 1;
+    if (mst_forest_rounds(err, tmp, sym, st, ids, id_bytes, dists, m, k, ld_ids, ld_dists, min_samples, core, w, &rounds)) return 1;
+    mst_state &s = w.s;
     if (rounds_out) *rounds_out = rounds;
     const dim3 grid(mst_grid(m, 256)), block(256);
     hipLaunchKernelGGL(k_mst_labels_min, grid, block, 0, st, s);
     hipLaunchKernelGGL(k_mst_labels_flag, grid, block, 0, st, s);
-    CSR_HIP(rocprim::exclusive_scan(scan_tmp, scan_bytes, (const int32_t *)s.flag, s.pos, (int32_t)0, rows, rocprim::plus<int32_t>(), st));
+    CSR_HIP(rocprim::exclusive_scan(w.scan_tmp, w.scan_bytes, (const int32_t *)s.flag, s.pos, (int32_t)0, (size_t)m, rocprim::plus<int32_t>(), st));
     hipLaunchKernelGGL(k_mst_labels_rank, grid, block, 0, st, s, labels);
     CSR_HIP(hipGetLastError());
     return csr_build_i32(err, tmp, st, g, s.edge_ids, s.edge_w, m, rounds > 0 ? rounds : 1, s.cols, m, 1, csr_combine());
@@ -412,9 +393,7 @@ int mst_run(csr_err &err, hipStream_t st, nnd_csr_s *g, const void *ids, int32_t
             int64_t ld_dists, int32_t min_samples, int32_t *labels, float *core, int32_t *rounds) {
     nnd_scratch tmp;  // released on return, behind the synchronise below
     nnd_csr_s sym;    // the symmetric mutual-reachability matrix: likewise
-    const int rc = id_bytes == 4
-                       ? mst_build<int32_t>(err, tmp, sym, st, g, (const int32_t *)ids, dists, m, k, ld_ids, ld_dists, min_samples, labels, core, rounds)
-                       : mst_build<int64_t>(err, tmp, sym, st, g, (const int64_t *)ids, dists, m, k, ld_ids, ld_dists, min_samples, labels, core, rounds);
+    const int rc = mst_build(err, tmp, sym, st, g, ids, id_bytes, dists, m, k, ld_ids, ld_dists, min_samples, labels, core, rounds);
     const hipError_t e = hipStreamSynchronize(st);  // (on every path: the scratch goes when this returns)
     if (rc) return 1;
     if (e != hipSuccess) { (void)hipGetLastError(); err.set_error("nnd_spanning_forest: a kernel failed: %s", hipGetErrorString(e)); return 1; }

@@ -986,6 +986,19 @@ class NNDescent:
         ``torch.sparse_csr_tensor`` and tensors on the index's device for a device-resident index."""
         return spanning.index_spanning_forest(self, min_samples, n_neighbors)
 
+    def spanning_tree(self, min_samples=5, n_neighbors=None):
+        """One spanning tree of the indexed points under mutual reachability, ``(tree, core_distances, n_components)``, computed
+        on the GPU (spanning.py, csrc/mst.hip and csrc/cross.hip): ``spanning_forest`` of the built graph, and its components
+        joined by their lightest cross-component edges, searched over all rows of the other components -- an edge there weighs
+        max(core(i), core(j), d(i, j)) with ``d`` the float32 rounding of the float64 distance of the two rows.  ``tree`` is exactly
+        symmetric with zero weights stored and m - 1 edges; ``n_components`` is the forest's component count before the joining.
+        It is the forest plus the joining edges, not the minimum spanning tree of the complete mutual-reachability graph (a cross
+        edge may make a forest edge redundant), as cuML's "connect components" step.  Metrics: euclidean, l2, sqeuclidean,
+        cosine.  Returns a ``scipy.sparse.csr_array`` and an array for an index of host data or one built with ``n_devices`` > 1,
+        a ``torch.sparse_csr_tensor`` and a tensor on the index's device for a device-resident index.  An index that does not hold
+        its rows (compressed, ``from_graph``) raises ValueError."""
+        return spanning.index_spanning_tree(self, min_samples, n_neighbors)
+
     def _query_sparse(self, query_data, m, k, epsilon, proxy_beam_size, filter, filter_mode):
         """``query`` for a ``scipy.sparse`` batch, on an index built from sparse or dense data alike: the batch is made canonical,
         uploaded as CSR and made dense on the device (sparse_input.py), and answered by the device-array forms of every query
